@@ -34,9 +34,6 @@ for p in (str(ROOT), str(ROOT / "tests")):
     if p not in sys.path:
         sys.path.insert(0, p)
 
-# A hardware queue per stream (the runtime's default is four; the PCIe-inclusive pass drives seven streams, the resident step four: the resident
-# number does not move with this setting, profiles/r03_scheduling_experiments.md).  Read by the HIP runtime when it initialises: set before torch.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 # multi-process runs (one rank per GPU over RCCL): the host driver supports dmabuf IPC only; exported on the GPU boxes already, kept here for any other launcher
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 import numpy as np
@@ -99,6 +96,44 @@ def step_profile_fields(bytes_per_frame, B, dominant):
     return out
 
 
+DUMP_FRAMES = 32        # frames of the last timed step that --dump-outputs writes (about 18 MB at the default K and line capacity)
+
+
+def dump_outputs(out_dir, ts, buf, plp, H):
+    """--dump-outputs: the arrays a caller of the step receives, from the step that filled feature set `buf`, as float32 / float64 .npy files.
+    Per-frame arrays are written for a fixed sample of frames (seeded, the same for every run with the same --batch); the slots past a frame's
+    count hold stale bytes and are zeroed (matches: -1; H = the halo rows before a rank's own frames), so two builds can be compared array for array.  Descriptors and match indices are exact in float32, the key point / key line fields in float64."""
+    B, cap, lcap = ts.B, ts.cap, ts.lcap
+    c = lambda t: t.cpu().numpy()
+    frames = np.sort(np.random.default_rng(20240615).choice(B, size=min(B, DUMP_FRAMES), replace=False))
+    rows = frames + H
+    live = lambda counts, n: np.arange(n)[None, :] < counts[:, None]
+    struct_cols = lambda a, dt: np.stack([a[f].astype(np.float64) for f in dt.names], -1)   # every float32 / int32 field exactly
+    cnt, n = c(ts.cnt2[buf])[H:], [c(ts.n1), c(ts.n2)] + ([] if ts.orb_only else [c(ts.n3), c(ts.n4)])
+    pk = live(cnt[frames], cap)
+    out = {"frames": frames.astype(np.float64), "kp_counts": cnt.astype(np.float64),
+           "kps": np.where(pk[..., None], struct_cols(c(ts.kps2[buf]).view(plp.KP_DTYPE).reshape(-1, cap)[rows], plp.KP_DTYPE), 0),
+           "desc": np.where(pk[..., None], c(ts.desc2[buf])[rows], 0).astype(np.float32),
+           "match_last_frame": np.where(pk, c(ts.m1)[frames], -1).astype(np.float32),
+           "match_landmarks": np.where(pk, c(ts.m2)[frames], -1).astype(np.float32)}
+    if not ts.orb_only:
+        lcnt = c(ts.lcnt2[buf])[H:]
+        pl = live(lcnt[frames], lcap)
+        out.update({"line_counts": lcnt.astype(np.float64),
+                    "keylines": np.where(pl[..., None], struct_cols(c(ts.kl2[buf]).view(plp.KL_DTYPE).reshape(-1, lcap)[rows], plp.KL_DTYPE), 0),
+                    "lbd": np.where(pl[..., None], c(ts.lbd2[buf])[rows], 0).astype(np.float32),
+                    "line_functions": np.where(pl[..., None], c(ts.fn2[buf])[frames], 0).astype(np.float64),
+                    "match_last_frame_line": np.where(pl, c(ts.m3)[frames], -1).astype(np.float32),
+                    "match_landmarks_line": np.where(pl, c(ts.m4)[frames], -1).astype(np.float32)})
+    names = ["n_match_last_frame", "n_match_landmarks", "n_match_last_frame_line", "n_match_landmarks_line"]
+    out.update({nm: v.astype(np.float64) for nm, v in zip(names, n)})
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes, more than 64 MB"
+    os.makedirs(out_dir, exist_ok=True)
+    for nm, a in out.items():
+        np.save(os.path.join(out_dir, nm + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -118,6 +153,9 @@ def main():
                     "device; the library's default) or the cheaper stable order (PLP_SEED_ORDER_STABLE); the other one is timed beside it (`other_seed_order`)")
     ap.add_argument("--verify", type=int, default=64, help="after the timed region: re-derive N frames of the last step (features and the four matcher "
                     "results) with the CPU oracle and compare (0 = off; rank 0, N = 1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: write what the last timed step computed for a fixed, seeded "
+                    f"sample of {DUMP_FRAMES} frames (features, line functions, the four matchers' results; every count of the step) as DIR/<name>.npy, "
+                    "float32 / float64, slots past a frame's count zeroed (rank 0)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -184,6 +222,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     ts.last_batch_status()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts, last_buf, plp, HALO)
     # ---- parity of the timed step itself: N frames of the LAST timed step (features + the four matcher results) against the CPU oracle.
     # After the timed region; the oracle is the checker here, never part of what is measured (tests/bench_step_check.py).
     # At N > 1 EVERY rank checks its own block (at most 8 frames each: the oracle runs on the host cores all ranks share) -- frames 0 and 1, whose
@@ -384,8 +424,7 @@ def main():
 
         # The next step's upload is enqueued before the host waits for this step's offsets (PLP_BENCH_PREFETCH=0: at the start of its own step).
         # This pass drives seven streams: on the runtime's default of four hardware queues an 11 ms copy queued early sits in front of another
-        # stream's kernels and the early upload LOSES (31.8 against 28.7 ms per step); with a queue per stream (GPU_MAX_HW_QUEUES=8, set at the top of
-        # this file) it wins (27.7 ms).  profiles/r03_pcie.md
+        # stream's kernels and the early upload LOSES (31.8 against 28.7 ms per step); with a hardware queue per stream it won (27.7 ms).  profiles/r03_pcie.md
         prefetch = os.environ.get("PLP_BENCH_PREFETCH", "1") == "1"
         uploaded = {}
 

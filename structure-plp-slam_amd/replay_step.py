@@ -72,7 +72,7 @@ class tracker_step:
         self.grid = plp.make_grid(cols, rows)
         self.sf = self.ex.get_scale_factors()
         self.cur = torch.cuda.current_stream(dev)
-        # Four streams = the runtime's four hardware queues (GPU_MAX_HW_QUEUES): a fifth would share a queue with one of these and its
+        # Four streams = the runtime's default four hardware queues: a fifth would share a queue with one of these and its
         # kernels would wait behind that stream's.  The line streams carry the step's longest dependent chain (region growing is ~15 ms
         # however few frames it gets): line_prio < 0 gives them the higher stream priority, so their kernels are dispatched first.
         line_prio = int(os.environ.get("PLP_BENCH_LINE_PRIO", "0"))
