@@ -9,8 +9,10 @@
 // Whether the production kernel kept its wait depended on unrelated code before the loop.
 //
 // wg_barrier() therefore issues the wait itself, as inline assembly the compiler cannot drop (where it would have waited anyway the second wait costs one issue slot).
-// tools/isa_barrier_check.py / tests/test_kernel_resources.py prove on the ISA the build keeps (csrc/build/*.s) that EVERY s_barrier of EVERY kernel of the library is
-// reached with the wave's LDS writes drained on every path -- kernels that still use __syncthreads() included.
+// tools/isa_barrier_check.py / tests/test_kernel_resources.py check on the ISA the build keeps (csrc/build/*.s) that EVERY s_barrier of EVERY kernel of the library is
+// reached with the wave's LDS writes drained on every path -- DS writes by lgkmcnt(0), LDS-DMA (glds) by vmcnt(0) -- kernels that still use __syncthreads() included.
+// Assumed there: a call leaves LDS writes in flight, an LDS-DMA never spans a barrier unless its kernel is on the tool's allow-list, unknown control flow is an error.
+// Not checked: whether a barrier also needs the wave's GLOBAL stores sent (wg_barrier_after_global_stores() below) -- that depends on what the data means.
 #pragma once
 #include <hip/hip_runtime.h>
 
