@@ -471,6 +471,41 @@ plp_status plp_post_extract_host(plp_matcher* ctx, const plp_camera* cam, const 
                                  int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right, float* depths,
                                  const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right);
 
+/* The same step for every camera model of the reference (camera::base model_type_, chosen by Camera.model in config.cc:62-72):
+ *   PLP_CAMERA_PERSPECTIVE      as plp_post_extract_* above, bit for bit
+ *   PLP_CAMERA_FISHEYE          camera::fisheye::undistort_keypoints          camera/fisheye.cc:172-204 (cv::fisheye::undistortPoints with
+ *                                                                              R empty, P = K, on the float cv_cam_matrix_ / cv_dist_params_,
+ *                                                                              :47-48; OpenCV 3.4.16's loop: 10 Newton steps, |theta_fix| < 1e-8;
+ *                                                                              a point that does not converge or changes sides -> (-1e6, -1e6))
+ *                               camera::fisheye::convert_keypoints_to_bearings fisheye.cc:206-216 (the perspective formula)
+ *                               undist: pt from the result, angle / size / octave copied, response 0, class_id -1; depth and key lines
+ *                               as for perspective (frame.cc:1169-1219 does not depend on the model)
+ *   PLP_CAMERA_EQUIRECTANGULAR  camera::equirectangular::undistort_keypoints   camera/equirectangular.cc:70-73 (undist = dist, every field)
+ *                               camera::equirectangular::convert_keypoints_to_bearings :75-88 (lon = (x / (float)cols - 0.5) 2 pi,
+ *                                                                              lat = -(y / (float)rows - 0.5) pi, float division then f64)
+ *                               monocular only (:36): depth or key lines -> PLP_ERR_UNSUPPORTED
+ * Bearings of the two new models use f64 tan / sin / cos of the device, not glibc's.
+ * Invalid: an unknown model; fx or fy 0 (perspective, fisheye); cols or rows <= 0 (equirectangular).  The camera is checked before
+ * anything else; then the arguments as for plp_post_extract_* (nothing to do -> PLP_OK, nothing written). */
+typedef enum { PLP_CAMERA_PERSPECTIVE = 0, PLP_CAMERA_FISHEYE = 1, PLP_CAMERA_EQUIRECTANGULAR = 2 } plp_camera_model_type;
+typedef struct plp_camera_model {
+    int32_t model;                       /* a plp_camera_model_type: camera::base model_type_ */
+    int32_t cols, rows;                  /* camera::base cols_, rows_ (unsigned int in the reference) */
+    double fx, fy, cx, cy;               /* perspective / fisheye; ignored for equirectangular */
+    double k1, k2, p1, p2, k3, k4;       /* perspective: k1 k2 p1 p2 k3; fisheye: k1 k2 k3 k4 (yaml names) */
+    double focal_x_baseline;             /* camera::base focal_x_baseline_ */
+} plp_camera_model;
+/* B frames, device pointers, asynchronous: the parameters of plp_post_extract_device. */
+plp_status plp_post_extract_model_device(plp_matcher* ctx, const plp_camera_model* cam, const plp_keypoint* d_kps, const int32_t* d_counts,
+                                         int32_t cap, int32_t B, const float* d_depth, int32_t rows, int32_t cols, size_t depth_step,
+                                         size_t depth_frame_stride, plp_keypoint* d_undist, double* d_bearings, float* d_x_right, float* d_depths,
+                                         const plp_keyline* d_kl, const int32_t* d_kl_counts, int32_t kl_cap, float* d_kl_depths,
+                                         float* d_kl_x_right, void* hip_stream);
+/* One frame, host pointers, synchronous: the parameters of plp_post_extract_host. */
+plp_status plp_post_extract_model_host(plp_matcher* ctx, const plp_camera_model* cam, const plp_keypoint* kps, int32_t n, const float* depth,
+                                       int32_t rows, int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right,
+                                       float* depths, const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right);
+
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the
  * raw colour / 16-bit depth frames can go straight to HBM.  B frames, device pointers, asynchronous.

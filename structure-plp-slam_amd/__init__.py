@@ -7,6 +7,7 @@ the bench: class and method names follow the reference's C++ interface
 fallback: if the shared library is missing or no GPU is visible the calls raise.
 """
 import ctypes as C
+import math
 import os
 import pathlib
 import subprocess
@@ -106,6 +107,8 @@ _API = [
     ("plp_landmark_descriptor_host", C.c_int, [_VP, _VP, _VP, _I32, _VP]),
     ("plp_post_extract_device", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     ("plp_post_extract_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_post_extract_model_device", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
+    ("plp_post_extract_model_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -444,6 +447,91 @@ class camera_c(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "focal_x_baseline")]
 
 
+CAMERA_PERSPECTIVE, CAMERA_FISHEYE, CAMERA_EQUIRECTANGULAR = 0, 1, 2     # plp_camera_model_type (camera::model_type_t)
+CAMERA_MODEL_NAMES = {"perspective": CAMERA_PERSPECTIVE, "fisheye": CAMERA_FISHEYE, "equirectangular": CAMERA_EQUIRECTANGULAR}   # camera/base.cc:81-98
+
+
+class camera_model_c(C.Structure):
+    """plp_camera_model: any of the reference's three camera models"""
+    _fields_ = [("model", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32)] + \
+               [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "focal_x_baseline")]
+
+
+class camera_model(camera_model_c):
+    """Mirror of the camera the reference's config builds from the yaml's Camera.* keys (config.cc:62-72 switches on Camera.model):
+    camera::perspective (perspective.cc:59-75), camera::fisheye (fisheye.cc:59-75) or camera::equirectangular (equirectangular.cc:45-50).
+    The object IS the plp_camera_model struct (ctypes.byref(cam) goes to plp_post_extract_model_*); img_bounds is camera::base
+    img_bounds_ (min_x, max_x, min_y, max_y as float32, camera/base.h:68-82) and grid() the matcher grid the constructors derive from it."""
+
+    NUM_GRID_COLS, NUM_GRID_ROWS = 64, 48      # camera::base defaults (camera/base.h:91)
+
+    def __init__(self, yaml_node, device=0):
+        super().__init__()
+        name = yaml_node["Camera.model"]
+        if name not in CAMERA_MODEL_NAMES:
+            raise PlpError(PLP_ERR_INVALID_ARG, f"Invalid camera model: {name}")
+        self.model = CAMERA_MODEL_NAMES[name]
+        self.cols, self.rows = int(yaml_node["Camera.cols"]), int(yaml_node["Camera.rows"])
+        if self.model != CAMERA_EQUIRECTANGULAR:
+            dist = ("k1", "k2", "p1", "p2", "k3") if self.model == CAMERA_PERSPECTIVE else ("k1", "k2", "k3", "k4")
+            for k in ("fx", "fy", "cx", "cy") + dist:
+                setattr(self, k, float(yaml_node[f"Camera.{k}"]))
+            self.focal_x_baseline = float(yaml_node.get("Camera.focal_x_baseline", 0.0))
+        self.device = device
+        self._bounds = None
+
+    @property
+    def img_bounds(self):
+        """(min_x, max_x, min_y, max_y) float32: compute_image_bounds() of the model (the distorted corners go through the GPU's undistortion)"""
+        if self._bounds is None:
+            self._bounds = self._compute_image_bounds()
+        return self._bounds
+
+    def _undistort(self, pts):
+        k = np.zeros(len(pts), KP_DTYPE)
+        k["x"] = [np.float32(x) for x, _ in pts]; k["y"] = [np.float32(y) for _, y in pts]; k["size"] = 1.0   # cv::KeyPoint(x, y, 1.0): float x, y
+        u = matcher(device=self.device).post_extract(self, k)["undist_keypts"]
+        return [(np.float32(a), np.float32(b)) for a, b in zip(u["x"], u["y"])]
+
+    def _compute_image_bounds(self):
+        f32 = np.float32
+        cols, rows = f32(self.cols), f32(self.rows)            # unsigned int -> float
+        whole = np.array([0.0, cols, 0.0, rows], np.float32)
+        if self.model == CAMERA_EQUIRECTANGULAR:                # equirectangular.cc:62-67
+            return whole
+        lo = lambda a, b: b if b < a else a                     # std::min / std::max
+        hi = lambda a, b: b if a < b else a
+        if self.model == CAMERA_PERSPECTIVE:                    # perspective.cc:100-128
+            if self.k1 == 0 and self.k2 == 0 and self.p1 == 0 and self.p2 == 0 and self.k3 == 0:
+                return whole
+            c = self._undistort([(0.0, 0.0), (cols, 0.0), (0.0, rows), (cols, rows)])
+            return np.array([lo(c[0][0], c[2][0]), hi(c[1][0], c[3][0]), lo(c[0][1], c[1][1]), hi(c[2][1], c[3][1])], np.float32)
+        # fisheye.cc:98-168
+        if self.k1 == 0 and self.k2 == 0 and self.k3 == 0 and self.k4 == 0:
+            return whole
+        pwx, pwy = (0.0 - self.cx) / self.fx, (0.0 - self.cy) / self.fy
+        if math.sqrt(pwx * pwx + pwy * pwy) > math.pi / 2:       # super wide: the four corners are out of view (edge midpoints, 5 degree limit)
+            c = self._undistort([(self.cx, 0.0), (cols, self.cy), (0.0, self.cy), (self.cx, rows)])
+            dist_thr_x = f32(self.fx / math.tan(5.0 * math.pi / 180.0))
+            dist_thr_y = f32(self.fy / math.tan(5.0 * math.pi / 180.0))
+            min_x_thr, max_x_thr = f32(-float(dist_thr_x) + self.cx), f32(float(dist_thr_x) + self.cx)
+            min_y_thr, max_y_thr = f32(-float(dist_thr_y) + self.cy), f32(float(dist_thr_y) + self.cy)
+            umin_x, umax_x, umin_y, umax_y = c[2][0], c[1][0], c[0][1], c[3][1]
+            return np.array([min_x_thr if (umin_x < min_x_thr or float(umin_x) > self.cx) else umin_x,
+                             max_x_thr if (umax_x > max_x_thr or float(umax_x) < self.cx) else umax_x,
+                             min_y_thr if (umin_y < min_y_thr or float(umin_y) > self.cy) else umin_y,
+                             max_y_thr if (umax_y > max_y_thr or float(umax_y) < self.cy) else umax_y], np.float32)
+        c = self._undistort([(0.0, 0.0), (cols, 0.0), (0.0, rows), (cols, rows)])
+        return np.array([lo(c[0][0], c[2][0]), hi(c[1][0], c[3][0]), lo(c[0][1], c[1][1]), hi(c[2][1], c[3][1])], np.float32)
+
+    def grid(self):
+        """camera::base grid: inv_cell_width = (double)num_grid_cols / (float)(max_x - min_x) (fisheye.cc:55-56 and the other two constructors)"""
+        b = self.img_bounds
+        inv_w = np.float64(self.NUM_GRID_COLS) / np.float64(np.float32(b[1] - b[0]))
+        inv_h = np.float64(self.NUM_GRID_ROWS) / np.float64(np.float32(b[3] - b[2]))
+        return match_grid_c(float(b[0]), float(b[2]), float(inv_w), float(inv_h), self.NUM_GRID_COLS, self.NUM_GRID_ROWS)
+
+
 class match_grid_c(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("inv_cell_width", C.c_double), ("inv_cell_height", C.c_double),
                 ("cols", C.c_int32), ("rows", C.c_int32)]
@@ -567,6 +655,7 @@ class matcher:
 
     def post_extract(self, camera, keypts, depth=None, keylines=None, kl_depths=None, kl_x_right=None):
         """undistort_keypoints + convert_keypoints_to_bearings (+ compute_stereo_from_depth when a depth image is given).
+        camera: a camera_c (perspective, plp_post_extract_host) or a camera_model / camera_model_c (any model, plp_post_extract_model_host).
         Returns dict(undist_keypts, bearings[, stereo_x_right, depths][, kl_depths, kl_x_right])."""
         k = np.ascontiguousarray(keypts, KP_DTYPE)
         n = len(k)
@@ -578,7 +667,8 @@ class matcher:
         nl = len(kl) if kl is not None else 0
         kd = np.ascontiguousarray(kl_depths, np.float32).copy() if kl is not None else None
         kx = np.ascontiguousarray(kl_x_right, np.float32).copy() if kl is not None else None
-        _check(lib().plp_post_extract_host(self._h, C.byref(camera), _p(k) if n else None, n, _p(d) if d is not None else None,
+        entry = lib().plp_post_extract_model_host if isinstance(camera, camera_model_c) else lib().plp_post_extract_host
+        _check(entry(self._h, C.byref(camera), _p(k) if n else None, n, _p(d) if d is not None else None,
                                            d.shape[0] if d is not None else 0, d.shape[1] if d is not None else 0, d.strides[0] if d is not None else 0,
                                            _p(und), _p(bear), _p(xr) if d is not None else None, _p(dep) if d is not None else None,
                                            _p(kl) if nl else None, nl, _p(kd) if nl else None, _p(kx) if nl else None))

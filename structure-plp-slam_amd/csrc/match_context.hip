@@ -342,6 +342,52 @@ PostArgs post_args(const plp_camera* cam) {
     A.fxb = cam->focal_x_baseline;
     return A;
 }
+
+// plp_camera_model -> PostArgs, as the three constructors store the camera (perspective.cc:47-48, fisheye.cc:47-48, equirectangular.cc:36)
+PostArgs model_post_args(const plp_camera_model* cam) {
+    PostArgs A{};
+    A.model = cam->model;
+    if (cam->model == PLP_CAMERA_EQUIRECTANGULAR) {
+        A.cols_f = (float)(unsigned)cam->cols; A.rows_f = (float)(unsigned)cam->rows;
+        return A;
+    }
+    const plp_camera p{cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2, cam->k3, cam->focal_x_baseline};
+    const PostArgs P = post_args(&p);
+    A.fx = P.fx; A.fy = P.fy; A.cx = P.cx; A.cy = P.cy; A.fx_f = P.fx_f; A.fy_f = P.fy_f; A.cx_f = P.cx_f; A.cy_f = P.cy_f;
+    A.fxb = P.fxb;
+    if (cam->model == PLP_CAMERA_FISHEYE) {   // cv_dist_params_ = (k1, k2, k3, k4) as cv::Mat_<float>
+        const double k[4] = {cam->k1, cam->k2, cam->k3, cam->k4};
+        for (int i = 0; i < 4; ++i) A.k[i] = (double)(float)k[i];
+    } else {
+        for (int i = 0; i < 5; ++i) A.k[i] = P.k[i];
+    }
+    return A;
+}
+
+plp_status check_camera_model(const plp_camera_model* cam, bool depth_or_lines) {
+    if (!cam) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    switch (cam->model) {
+    case PLP_CAMERA_PERSPECTIVE:
+    case PLP_CAMERA_FISHEYE:
+        if (!(cam->fx != 0) || !(cam->fy != 0)) return set_error(PLP_ERR_INVALID_ARG, "fx, fy must be non-zero");
+        return PLP_OK;
+    case PLP_CAMERA_EQUIRECTANGULAR:
+        if (cam->cols <= 0 || cam->rows <= 0) return set_error(PLP_ERR_INVALID_ARG, "cols, rows must be positive");
+        if (depth_or_lines) return set_error(PLP_ERR_UNSUPPORTED, "the equirectangular camera is monocular: no depth, no key lines");
+        return PLP_OK;
+    default:
+        return set_error(PLP_ERR_INVALID_ARG, "unknown camera model");
+    }
+}
+
+plp_status post_extract_device(plp_matcher* c, const PostArgs& cam_args, const plp_keypoint* d_kps, const int32_t* d_counts, int32_t cap,
+                               int32_t B, const float* d_depth, int32_t rows, int32_t cols, size_t depth_step, size_t depth_frame_stride,
+                               plp_keypoint* d_undist, double* d_bearings, float* d_x_right, float* d_depths,
+                               const plp_keyline* d_kl, const int32_t* d_kl_counts, int32_t kl_cap, float* d_kl_depths,
+                               float* d_kl_x_right, void* hip_stream);
+plp_status post_extract_host(plp_matcher* c, const PostArgs& cam_args, const plp_keypoint* kps, int32_t n, const float* depth, int32_t rows,
+                             int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right, float* depths,
+                             const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right);
 }  // namespace
 
 plp_status plp_post_extract_device(plp_matcher* c, const plp_camera* cam, const plp_keypoint* d_kps, const int32_t* d_counts, int32_t cap,
@@ -356,9 +402,50 @@ plp_status plp_post_extract_device(plp_matcher* c, const plp_camera* cam, const 
     if (d_depth && (rows <= 0 || cols <= 0 || depth_step < (size_t)cols * 4)) return set_error(PLP_ERR_INVALID_ARG, "bad depth geometry");
     if (d_kl && (!d_depth || !d_kl_depths || !d_kl_x_right)) return set_error(PLP_ERR_INVALID_ARG, "key lines need depth, d_kl_depths, d_kl_x_right");
     if (!(cam->fx != 0) || !(cam->fy != 0)) return set_error(PLP_ERR_INVALID_ARG, "fx, fy must be non-zero");
+    return post_extract_device(c, post_args(cam), d_kps, d_counts, cap, B, d_depth, rows, cols, depth_step, depth_frame_stride, d_undist, d_bearings,
+                               d_x_right, d_depths, d_kl, d_kl_counts, kl_cap, d_kl_depths, d_kl_x_right, hip_stream);
+}
+
+plp_status plp_post_extract_model_device(plp_matcher* c, const plp_camera_model* cam, const plp_keypoint* d_kps, const int32_t* d_counts,
+                                         int32_t cap, int32_t B, const float* d_depth, int32_t rows, int32_t cols, size_t depth_step,
+                                         size_t depth_frame_stride, plp_keypoint* d_undist, double* d_bearings, float* d_x_right, float* d_depths,
+                                         const plp_keyline* d_kl, const int32_t* d_kl_counts, int32_t kl_cap, float* d_kl_depths,
+                                         float* d_kl_x_right, void* hip_stream) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(cam, d_depth || d_kl)) return s;
+    return post_extract_device(c, model_post_args(cam), d_kps, d_counts, cap, B, d_depth, rows, cols, depth_step, depth_frame_stride, d_undist, d_bearings,
+                               d_x_right, d_depths, d_kl, d_kl_counts, kl_cap, d_kl_depths, d_kl_x_right, hip_stream);
+}
+
+plp_status plp_post_extract_host(plp_matcher* c, const plp_camera* cam, const plp_keypoint* kps, int32_t n, const float* depth, int32_t rows,
+                                 int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right, float* depths,
+                                 const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right) {
+    if (!c || !cam) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    return post_extract_host(c, post_args(cam), kps, n, depth, rows, cols, depth_step, undist, bearings, x_right, depths, kl, n_kl, kl_depths, kl_x_right);
+}
+
+plp_status plp_post_extract_model_host(plp_matcher* c, const plp_camera_model* cam, const plp_keypoint* kps, int32_t n, const float* depth,
+                                       int32_t rows, int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right,
+                                       float* depths, const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(cam, depth || kl || n_kl > 0)) return s;
+    return post_extract_host(c, model_post_args(cam), kps, n, depth, rows, cols, depth_step, undist, bearings, x_right, depths, kl, n_kl, kl_depths, kl_x_right);
+}
+
+namespace {
+plp_status post_extract_device(plp_matcher* c, const PostArgs& cam_args, const plp_keypoint* d_kps, const int32_t* d_counts, int32_t cap,
+                               int32_t B, const float* d_depth, int32_t rows, int32_t cols, size_t depth_step, size_t depth_frame_stride,
+                               plp_keypoint* d_undist, double* d_bearings, float* d_x_right, float* d_depths,
+                               const plp_keyline* d_kl, const int32_t* d_kl_counts, int32_t kl_cap, float* d_kl_depths,
+                               float* d_kl_x_right, void* hip_stream) {
+    if (B <= 0 || (d_kps && cap <= 0) || (d_kl && kl_cap <= 0)) return set_error(PLP_ERR_INVALID_ARG, "bad sizes");
+    if (!d_kps && !d_kl) return PLP_OK;
+    if (d_kps && !d_undist) return set_error(PLP_ERR_INVALID_ARG, "d_undist is required with d_kps");
+    if (d_depth && (rows <= 0 || cols <= 0 || depth_step < (size_t)cols * 4)) return set_error(PLP_ERR_INVALID_ARG, "bad depth geometry");
+    if (d_kl && (!d_depth || !d_kl_depths || !d_kl_x_right)) return set_error(PLP_ERR_INVALID_ARG, "key lines need depth, d_kl_depths, d_kl_x_right");
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    PostArgs A = post_args(cam);
+    PostArgs A = cam_args;
     A.kps = d_kps; A.counts = d_counts; A.cap = d_kps ? cap : 0;
     A.depth = d_depth; A.depth_step = depth_step; A.depth_frame_stride = depth_frame_stride;
     A.undist = d_undist; A.bearings = d_bearings; A.x_right = d_x_right; A.depths = d_depths;
@@ -368,10 +455,9 @@ plp_status plp_post_extract_device(plp_matcher* c, const plp_camera* cam, const 
     return PLP_OK;
 }
 
-plp_status plp_post_extract_host(plp_matcher* c, const plp_camera* cam, const plp_keypoint* kps, int32_t n, const float* depth, int32_t rows,
-                                 int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right, float* depths,
-                                 const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right) {
-    if (!c || !cam) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+plp_status post_extract_host(plp_matcher* c, const PostArgs& cam_args, const plp_keypoint* kps, int32_t n, const float* depth, int32_t rows,
+                             int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right, float* depths,
+                             const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right) {
     if (n < 0 || n_kl < 0) return set_error(PLP_ERR_INVALID_ARG, "negative count");
     if (n == 0 && n_kl == 0) return PLP_OK;
     if (n > 0 && (!kps || !undist)) return set_error(PLP_ERR_INVALID_ARG, "kps and undist are required");
@@ -400,7 +486,7 @@ plp_status plp_post_extract_host(plp_matcher* c, const plp_camera* cam, const pl
             c->pin.pack(0, reinterpret_cast<const uint8_t*>(depth), depth_step, rows, cols * 4);
             PLP_HIP(hipMemcpyAsync(base + o_img, c->pin.p, (size_t)rows * cols * 4, hipMemcpyHostToDevice, st));
         }
-        PostArgs A = post_args(cam);
+        PostArgs A = cam_args;
         A.kps = n ? (const plp_keypoint*)(base + o_k) : nullptr; A.counts = nullptr; A.cap = n;
         A.depth = depth ? (const float*)(base + o_img) : nullptr; A.depth_step = (size_t)cols * 4; A.depth_frame_stride = 0;
         A.undist = (plp_keypoint*)(base + o_u); A.bearings = bearings ? (double*)(base + o_b) : nullptr;
@@ -425,6 +511,7 @@ plp_status plp_post_extract_host(plp_matcher* c, const plp_camera* cam, const pl
     }
     return PLP_OK;
 }
+}  // namespace
 
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
                                            size_t src_frame_stride, int32_t channels, int32_t color_order, int32_t B, uint8_t* d_gray,

@@ -93,6 +93,8 @@ struct PostArgs {
     const float* depth; size_t depth_step, depth_frame_stride;
     plp_keypoint* undist; double* bearings; float* x_right; float* depths;
     const plp_keyline* kl; const int32_t* kl_counts; int kl_cap; float* kl_depths; float* kl_x_right;
+    int model;                        // plp_camera_model_type: which instantiation of k_post_extract runs (0 = perspective)
+    float cols_f, rows_f;             // equirectangular: (float)cols_, (float)rows_ (unsigned int -> float in pt.x / cols_)
 };
 void launch_post_extract(hipStream_t st, const PostArgs& A, int B);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,

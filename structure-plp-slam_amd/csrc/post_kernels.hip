@@ -3,6 +3,22 @@
 // OpenCV 3.4.16 imgproc/undistort.cpp (cvUndistortPointsInternal), f64 throughout (+, -, *, /, sqrt only: IEEE
 // operations, so the results are the oracle's bit for bit; the file is compiled with -ffp-contract=off).
 // One thread per key point / key line; grid = (ceil(cap / 256), B).
+//
+// The other two camera models of the reference (plp_post_extract_model_*), one instantiation of k_post_extract per model:
+//   camera::fisheye (camera/fisheye.cc:172-216): cv::fisheye::undistortPoints(pts, pts, K, D, noArray(), K) on the float
+//     matrix / distortion vector (:47-48), restated from OpenCV 3.4.16 calib3d/src/fisheye.cpp.  The restated loop is the
+//     guarded form: fixed criteria (10 Newton steps on theta, exit when |theta_fix| < 1e-8), a 'converged' flag, the
+//     'theta_flipped' test and the (-1e6, -1e6) result for a point that did not converge or changed sides.  Why this form:
+//     the flip guard went into the 3.4 branch before 3.4.16 was released, while the TermCriteria argument that makes 10 / 1e-8
+//     configurable came with 4.x only, so 3.4.16 has the guard with constant criteria.  That is recalled from OpenCV's
+//     public history, not checked against its source (no OpenCV source or build pins it here).  Both forms exit early on
+//     |theta_fix| < 1e-8, so they differ only on the points that get the sentinel.  Bearings: the perspective formula
+//     (fisheye.cc:206-216).
+//   camera::equirectangular (camera/equirectangular.cc:70-88): undist = dist (every field), bearings from longitude /
+//     latitude.  No depth (the reference builds this camera as monocular only, :36).
+// tan, sin and cos are ocml's f64 routines, not glibc's: the one place where this step is not IEEE-exact (DESIGN.md
+// section 5, D4).  Their arguments are bounded (|theta| <= pi/2, |lon| <= pi, |lat| <= pi/2); the build's resource check
+// shows they bring no scratch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -62,16 +78,70 @@ __device__ __forceinline__ void undistort_point(const PostArgs& A, float u_in, f
     out_y = (float)(yy * ww);
 }
 
+// cv::fisheye::undistortPoints, one point (OpenCV 3.4.16 calib3d/src/fisheye.cpp; the guarded form, see the file header).
+// f = (fx, fy), c = (cx, cy) and k of the float cv_cam_matrix_ / cv_dist_params_; R empty, P = K: RR = P * I = P.
+__device__ __forceinline__ void undistort_point_fisheye(const PostArgs& A, float u_in, float v_in, float& out_x, float& out_y) {
+    const double fx = A.fx_f, fy = A.fy_f, cx = A.cx_f, cy = A.cy_f;
+    const double pwx = ((double)u_in - cx) / fx, pwy = ((double)v_in - cy) / fy;
+    double scale = 1.0;
+    double theta_d = sqrt(pwx * pwx + pwy * pwy);
+    const double half_pi = 3.14159265358979323846 / 2.;
+    theta_d = -half_pi < theta_d ? theta_d : -half_pi;     // std::min(std::max(-CV_PI / 2., theta_d), CV_PI / 2.)
+    theta_d = half_pi < theta_d ? half_pi : theta_d;
+    bool converged = false;
+    double theta = theta_d;
+    if (theta_d > 1e-8) {
+        for (int j = 0; j < 10; j++) {
+            const double theta2 = theta * theta, theta4 = theta2 * theta2, theta6 = theta4 * theta2, theta8 = theta6 * theta2;
+            const double k0_theta2 = A.k[0] * theta2, k1_theta4 = A.k[1] * theta4, k2_theta6 = A.k[2] * theta6, k3_theta8 = A.k[3] * theta8;
+            const double theta_fix = (theta * (1 + k0_theta2 + k1_theta4 + k2_theta6 + k3_theta8) - theta_d) /
+                                     (1 + 3 * k0_theta2 + 5 * k1_theta4 + 7 * k2_theta6 + 9 * k3_theta8);
+            theta = theta - theta_fix;
+            if (fabs(theta_fix) < 1e-8) { converged = true; break; }
+        }
+        scale = tan(theta) / theta_d;
+    } else {
+        converged = true;
+    }
+    const bool theta_flipped = (theta_d < 0 && theta > 0) || (theta_d > 0 && theta < 0);
+    if (converged && !theta_flipped) {
+        const double pux = pwx * scale, puy = pwy * scale;
+        // pr = RR * (pu, 1), Matx product (s = 0; s += a(i, k) * b(k)), every zero term kept
+        double p0 = 0, p1 = 0, p2 = 0;
+        p0 += fx * pux; p0 += 0.0 * puy; p0 += cx * 1.0;
+        p1 += 0.0 * pux; p1 += fy * puy; p1 += cy * 1.0;
+        p2 += 0.0 * pux; p2 += 0.0 * puy; p2 += 1.0 * 1.0;
+        out_x = (float)(p0 / p2);
+        out_y = (float)(p1 / p2);
+    } else {
+        out_x = -1000000.f;
+        out_y = -1000000.f;
+    }
+}
+
+template <int MODEL>   // plp_camera_model_type: 0 perspective, 1 fisheye, 2 equirectangular
 __global__ __launch_bounds__(256) void k_post_extract(PostArgs A) {
     const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     if (A.kps && i < (A.counts ? min(A.counts[b], A.cap) : A.cap)) {
         const size_t o = (size_t)b * A.cap + i;
         const plp_keypoint k = A.kps[o];
+        if constexpr (MODEL == PLP_CAMERA_EQUIRECTANGULAR) {   // equirectangular.cc:70-88
+            if (A.undist) A.undist[o] = k;                     // undist_keypts = dist_keypts: response and class_id too
+            if (A.bearings) {
+                const double lon = ((double)(k.x / A.cols_f) - 0.5) * (2 * 3.14159265358979323846);   // float / (float)cols_, then double
+                const double lat = -((double)(k.y / A.rows_f) - 0.5) * 3.14159265358979323846;
+                const double cl = cos(lat);
+                double* bo = A.bearings + 3 * o;
+                bo[0] = cl * sin(lon); bo[1] = -sin(lat); bo[2] = cl * cos(lon);
+            }
+            return;
+        }
         plp_keypoint un;
-        undistort_point(A, k.x, k.y, un.x, un.y);
+        if constexpr (MODEL == PLP_CAMERA_FISHEYE) undistort_point_fisheye(A, k.x, k.y, un.x, un.y);
+        else undistort_point(A, k.x, k.y, un.x, un.y);
         un.size = k.size; un.angle = k.angle; un.response = 0.f; un.octave = k.octave; un.class_id = -1;
         if (A.undist) A.undist[o] = un;
-        if (A.bearings) {   // perspective.cc:165-175 (true double intrinsics, float point)
+        if (A.bearings) {   // perspective.cc:165-175, fisheye.cc:206-216 (true double intrinsics, float point)
             const double xn = ((double)un.x - A.cx) / A.fx, yn = ((double)un.y - A.cy) / A.fy;
             const double l2 = sqrt(xn * xn + yn * yn + 1.0);
             double* bo = A.bearings + 3 * o;
@@ -85,7 +155,7 @@ __global__ __launch_bounds__(256) void k_post_extract(PostArgs A) {
             A.x_right[o] = xr; A.depths[o] = dp;
         }
     }
-    if (A.kl && A.depth && i < (A.kl_counts ? min(A.kl_counts[b], A.kl_cap) : A.kl_cap)) {   // frame.cc:1196-1217
+    if (MODEL != PLP_CAMERA_EQUIRECTANGULAR && A.kl && A.depth && i < (A.kl_counts ? min(A.kl_counts[b], A.kl_cap) : A.kl_cap)) {   // frame.cc:1196-1217
         const size_t o = (size_t)b * A.kl_cap + i;
         const plp_keyline l = A.kl[o];
         const uint8_t* D = reinterpret_cast<const uint8_t*>(A.depth) + (size_t)b * A.depth_frame_stride;
@@ -322,7 +392,9 @@ void launch_remap_linear(hipStream_t st, const uint8_t* src, int rows, int cols,
 
 void launch_post_extract(hipStream_t st, const PostArgs& A, int B) {
     const int n = A.cap > A.kl_cap ? A.cap : A.kl_cap;
-    hipLaunchKernelGGL(k_post_extract, dim3((n + 255) / 256, B), dim3(256), 0, st, A);
+    if (A.model == PLP_CAMERA_FISHEYE) hipLaunchKernelGGL(k_post_extract<PLP_CAMERA_FISHEYE>, dim3((n + 255) / 256, B), dim3(256), 0, st, A);
+    else if (A.model == PLP_CAMERA_EQUIRECTANGULAR) hipLaunchKernelGGL(k_post_extract<PLP_CAMERA_EQUIRECTANGULAR>, dim3((n + 255) / 256, B), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(k_post_extract<PLP_CAMERA_PERSPECTIVE>, dim3((n + 255) / 256, B), dim3(256), 0, st, A);
 }
 
 }  // namespace plp
