@@ -18,11 +18,11 @@ struct plp_line {
     HostPinned pin;            // staging of the host-pointer entry point's image
     int device = 0;
     hipStream_t stream = nullptr;
+    hipStream_t idle_stream = nullptr;   // never used: see plp_line_create
     int rows = 0, cols = 0, capB = 0;
     int grow_waves = 0;   // plp_line_set_grow_waves
     int seed_order = PLP_SEED_ORDER_LIBSTDCXX;   // plp_line_set_seed_order.  The reference's order is the default on every device; one that refuses the sort's LDS
                                                  // (seed_sort_ok false) gets an error from extract until the caller selects PLP_SEED_ORDER_STABLE -- never a silent change of results
-    bool grow_on_side = false;                 // PLP_GROW_CUS: region growing on the CU-masked side stream
     bool mw_ok = false, seed_sort_ok = false;  // this device accepted the large dynamic-LDS limits of k_lsd_grow_mw / k_lsd_seed_sort
     int mw_capB = 0, seed_capB = 0;            // frames the lazily allocated buffers of those two paths hold
     LinePlanes P{};
@@ -40,7 +40,6 @@ struct plp_line {
     bool profiling = false;
     bool grow_big_ok = false;
     hipEvent_t ev[9] = {};
-    LineSideStream side{};                      // blur5 + Sobel beside the LSD chain
     double stage_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // 8 stages + total
     long stage_batches = 0;
     std::mutex mu;
@@ -199,7 +198,7 @@ plp_status run(plp_line* c, const uint8_t* d_imgs, int B, int rows, int cols, si
     c->lp.seed_exact = exact ? 1 : 0;
     const SeedSortBufs ssb{(uint32_t*)c->seed_ent.p, (uint32_t*)c->seed_ws.p, seed_sort_ws_entries((size_t)(c->P.sw - 1) * (c->P.sh - 1))};
     launch_line_front(st, c->P, c->lp, c->rt, c->t11, c->t5, c->w, d_kl, d_lbd, d_fn, cap, d_counts, B, c->profiling ? c->ev : nullptr,
-                      c->side.stream ? &c->side : nullptr, c->grow_waves, exact ? &ssb : nullptr, c->mw_ok, c->grow_on_side);
+                      c->grow_waves, exact ? &ssb : nullptr, c->mw_ok);
     PLP_HIP(hipGetLastError());
     if (c->profiling) {
         PLP_HIP(hipEventSynchronize(c->ev[8]));
@@ -208,6 +207,21 @@ plp_status run(plp_line* c, const uint8_t* d_imgs, int B, int rows, int cols, si
         ++c->stage_batches;
     }
     c->last_B = B; c->last_stream = st; c->last_profiled = c->profiling;
+    return PLP_OK;
+}
+
+// The status word of a batch (k_line_finalize and the LSD kernels OR their bits into s[0]; s[1..3] detail bit 32).  Bit 1 (more lines than
+// `cap`) is left to the caller when `check_cap` is false: plp_line_extract compares the count with its caller's capacity itself.
+plp_status batch_status(const int32_t s[4], bool check_cap) {
+    if (check_cap && (s[0] & 1)) return set_error(PLP_ERR_CAPACITY, "a frame produced more lines than `cap`; output truncated");
+    if (s[0] & 4) return set_error(PLP_ERR_OVERFLOW, "more LSD segments than the per-frame capacity");
+    if (s[0] & 16) return set_error(PLP_ERR_HIP, "region growing with several waves per frame timed out in a wait (protocol error, please report the frame)");
+    if (s[0] & 32) {
+        static thread_local char msg[320];
+        snprintf(msg, sizeof msg, "the exact seed sort stopped short in frame %d of the batch (reason %d: 1 = a partition's swap count / cut failed its check [m = %d], 2-3, 6-8 = a list or stack of its LDS ran out of space, "
+                 "4-5 = a wave waited beyond the limit): the seed order of this batch is not guaranteed; please report the frame", s[2], s[1], s[3]);
+        return set_error(PLP_ERR_OVERFLOW, msg);
+    }
     return PLP_OK;
 }
 
@@ -230,20 +244,12 @@ plp_status plp_line_create(int device, plp_line** out) {
     c->seed_sort_ok = seed_sort_configure() == hipSuccess;
     (void)hipGetLastError();
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return set_error(PLP_ERR_HIP, "hipStreamCreate failed"); }
-    // Experiment (profiles/r04_grow_cu_mask.md): PLP_GROW_CUS=n runs region growing on a stream of its own that may only use n of the CUs
-    // (hipExtStreamCreateWithCUMask; the mask's bits go round the XCDs, so the first n bits are n / 8 CUs of each), the rest of the chip stays free
-    // of the growers' LDS and registers.  The side stream then serves this purpose (PLP_LINE_SIDE_STREAM is ignored).
-    const char* gcu = getenv("PLP_GROW_CUS");
-    const int n_gcu = gcu ? atoi(gcu) : 0;
-    hipError_t side_err;
-    if (n_gcu > 0) {
-        uint32_t mask[16] = {0};
-        for (int i = 0; i < n_gcu && i < 512; ++i) mask[i >> 5] |= 1u << (i & 31);
-        side_err = hipExtStreamCreateWithCUMask(&c->side.stream, 16, mask);
-        c->grow_on_side = side_err == hipSuccess;
-    } else side_err = hipStreamCreateWithFlags(&c->side.stream, hipStreamNonBlocking);
-    if (side_err != hipSuccess || hipEventCreateWithFlags(&c->side.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&c->side.join, hipEventDisableTiming) != hipSuccess) { c->side.stream = nullptr; c->grow_on_side = false; }   // optional: falls back to one stream
+    // A second stream that nothing is launched on.  Until round 7 it was the side stream of experiments (the LBD image pass, region growing on a CU
+    // mask).  Without it the bench step ran 0.3 - 0.6 % slower, and on two of three boxes the median lay below the slowest run with it (same-box
+    // A/B; on the box with five runs of each: 89.6 k frames/s before, 89.1 k with one stream, 89.9 k with this idle one -- profiles/INDEX.md round 7).
+    // The device code is the same either way: the runtime spreads streams over the hardware queues as they are created, so one stream fewer per line
+    // context changes which of the step's busy streams share a queue.  Optional: a context whose second stream is refused works the same.
+    if (hipStreamCreateWithFlags(&c->idle_stream, hipStreamNonBlocking) != hipSuccess) c->idle_stream = nullptr;
     *out = c;
     return PLP_OK;
 }
@@ -252,9 +258,7 @@ void plp_line_destroy(plp_line* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->side.stream) { (void)hipStreamSynchronize(c->side.stream); (void)hipStreamDestroy(c->side.stream); }
-    if (c->side.fork) (void)hipEventDestroy(c->side.fork);
-    if (c->side.join) (void)hipEventDestroy(c->side.join);
+    if (c->idle_stream) (void)hipStreamDestroy(c->idle_stream);
     for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
     delete c;
 }
@@ -276,16 +280,7 @@ plp_status plp_line_last_batch_status(plp_line* c) {
     int32_t s[4] = {0, 0, 0, 0};
     PLP_HIP(hipMemcpyAsync(s, c->status.p, 16, hipMemcpyDeviceToHost, c->last_stream));
     PLP_HIP(hipStreamSynchronize(c->last_stream));
-    if (s[0] & 1) return set_error(PLP_ERR_CAPACITY, "a frame produced more lines than `cap`; output truncated");
-    if (s[0] & 4) return set_error(PLP_ERR_OVERFLOW, "more LSD segments than the per-frame capacity");
-    if (s[0] & 16) return set_error(PLP_ERR_HIP, "region growing with several waves per frame timed out in a wait (protocol error, please report the frame)");
-    if (s[0] & 32) {
-        static thread_local char msg[320];
-        snprintf(msg, sizeof msg, "the exact seed sort stopped short in frame %d of the batch (reason %d: 1 = a partition's swap count / cut failed its check [m = %d], 2-3, 6-8 = a list or stack of its LDS ran out of space, "
-                 "4-5 = a wave waited beyond the limit): the seed order of this batch is not guaranteed; please report the frame", s[2], s[1], s[3]);
-        return set_error(PLP_ERR_OVERFLOW, msg);
-    }
-    return PLP_OK;
+    return batch_status(s, true);
 }
 
 plp_status plp_line_extract(plp_line* c, const uint8_t* img, int32_t rows, int32_t cols, size_t step, plp_keyline* kl, uint8_t* lbd,
@@ -325,15 +320,7 @@ plp_status plp_line_extract(plp_line* c, const uint8_t* img, int32_t rows, int32
     }
     int32_t s[4];
     PLP_HIP(hipMemcpy(s, c->status.p, 16, hipMemcpyDeviceToHost));
-    if (s[0] & 4) return set_error(PLP_ERR_OVERFLOW, "more LSD segments than the per-frame capacity");
-    if (s[0] & 16) return set_error(PLP_ERR_HIP, "region growing with several waves per frame timed out in a wait (protocol error, please report the frame)");
-    if (s[0] & 32) {
-        static thread_local char msg[320];
-        snprintf(msg, sizeof msg, "the exact seed sort stopped short in frame %d of the batch (reason %d: 1 = a partition's swap count / cut failed its check [m = %d], 2-3, 6-8 = a list or stack of its LDS ran out of space, "
-                 "4-5 = a wave waited beyond the limit): the seed order of this batch is not guaranteed; please report the frame", s[2], s[1], s[3]);
-        return set_error(PLP_ERR_OVERFLOW, msg);
-    }
-    return PLP_OK;
+    return batch_status(s, false);
 }
 
 plp_status plp_line_debug_grow_profile(plp_line* c, int64_t* out12) {

@@ -89,8 +89,6 @@ struct ResizeExactTab { const int16_t *xo, *xc, *yo, *yc; };   // offsets + 8.8 
 struct BlurTapsN { int k[11]; };
 struct LbdWeightsDev { float g[63], l[21]; };
 
-struct LineSideStream { hipStream_t stream; hipEvent_t fork, join; };   // optional second stream of a line context
-
 // Seed order of a reference built with libstdc++ (seed_sort_kernels.hip): `ent` = [B][(sw-1)(sh-1)] entries, `ws` = [B][ws_stride] scratch
 struct SeedSortBufs { uint32_t* ent; uint32_t* ws; size_t ws_stride; };
 size_t seed_sort_ws_entries(size_t nv);
@@ -104,6 +102,6 @@ hipError_t grow_configure();         // ... and for k_lsd_grow: kLsdGrowLdsBytes
 // blur5+sobel, LBD, finalize}
 void launch_line_front(hipStream_t st, const LinePlanes& P, const LsdParams& lp, const ResizeExactTab& rt, const BlurTapsN& t11,
                        const BlurTapsN& t5, const LbdWeightsDev& w, plp_keyline* out_kl, uint8_t* out_lbd, double* out_fn, int cap,
-                       int32_t* out_counts, int B, hipEvent_t* ev, const LineSideStream* side, int grow_waves, const SeedSortBufs* seed_exact, bool mw_ok, bool grow_on_side = false);
+                       int32_t* out_counts, int B, hipEvent_t* ev, int grow_waves, const SeedSortBufs* seed_exact, bool mw_ok);
 
 }  // namespace plp

@@ -29,10 +29,6 @@
 #include "sincos_ziv.hpp"
 #include "xcd_map.hpp"
 
-#ifndef PLP_CHAIN_BATCH         // addends per LDS round trip in the rectangle fit's sequential sums (rect_from_ring); 0 / 4 / 8 / 16 measured: profiles/r03_lsd_grow.md
-#define PLP_CHAIN_BATCH 8
-#endif
-
 namespace plp {
 
 // the two divisions of a tile kernel's workgroup index by launch constants, as multipliers (xcd_map.hpp plp_div_magic)
@@ -732,29 +728,14 @@ template <bool FROM_LIST = false> __device__ void rect_from_ring(const GrowCtx& 
             }
             __builtin_amdgcn_wave_barrier();
             const int cnt = min(32, nreg - 32 * c);
-            if (lane < 3) {   // PLP_CHAIN_BATCH addends are fetched together, then added one after the other: the chain is the additions, not one LDS
-                int t = 0;        // round trip per point (the loop used to be ds_read -> wait -> add per point: ~130 cycles each, a sixth of the kernel)
-#if PLP_CHAIN_BATCH >= 16
-                for (; t + 16 <= cnt; t += 16) {
-                    double v[16];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) v[u] = sc[3 * (t + u) + lane];
-#pragma unroll
-                    for (int u = 0; u < 16; ++u) acc += v[u];
-                }
-#endif
-#if PLP_CHAIN_BATCH >= 8
+            if (lane < 3) {   // 8 addends are fetched together, then added one after the other: the chain is the additions, not one LDS
+                int t = 0;        // round trip per point (the loop used to be ds_read -> wait -> add per point: ~130 cycles each, a sixth of the kernel;
+                                  // batches of 0 / 4 / 8 / 16 measured: profiles/r03_lsd_grow.md)
                 for (; t + 8 <= cnt; t += 8) {
                     const double v0 = sc[3 * t + lane], v1 = sc[3 * t + 3 + lane], v2 = sc[3 * t + 6 + lane], v3 = sc[3 * t + 9 + lane];
                     const double v4 = sc[3 * t + 12 + lane], v5 = sc[3 * t + 15 + lane], v6 = sc[3 * t + 18 + lane], v7 = sc[3 * t + 21 + lane];
                     acc += v0; acc += v1; acc += v2; acc += v3; acc += v4; acc += v5; acc += v6; acc += v7;
                 }
-#elif PLP_CHAIN_BATCH >= 4
-                for (; t + 4 <= cnt; t += 4) {
-                    const double v0 = sc[3 * t + lane], v1 = sc[3 * t + 3 + lane], v2 = sc[3 * t + 6 + lane], v3 = sc[3 * t + 9 + lane];
-                    acc += v0; acc += v1; acc += v2; acc += v3;
-                }
-#endif
                 for (; t < cnt; ++t) acc += sc[3 * t + lane];
             }
             __builtin_amdgcn_wave_barrier();
@@ -1091,19 +1072,11 @@ __global__ __launch_bounds__(256) void k_lsd_grow(LinePlanes P, LsdParams lp, in
 // respect) only changes how much speculation is wasted.  Model with random interleavings: tests/test_spec_grow_model.py.  Results equal
 // k_lsd_grow's bit for bit (tests/test_gpu_line.py runs both).
 // kMwHeap (line_device.hpp): list entries per helper and group buffer (both lists + the assumed pixels of all its regions of one group); kMwBufs buffers per helper
-#ifndef PLP_MW_GROUP      // tuning knobs of the several-waves path (tools/build_variant.sh; measured: profiles/r03_lsd_grow.md)
-#define PLP_MW_GROUP 64
-#endif
-#ifndef PLP_MW_BUFS
-#define PLP_MW_BUFS 2
-#endif
-#ifndef PLP_MW_ENTRIES
-#define PLP_MW_ENTRIES 16
-#endif
-constexpr int kMwGroup = PLP_MW_GROUP;   // seeds per ownership unit (a helper claims a group, main walks them in order; its own loads are 64 seeds)
-static_assert(PLP_MW_BUFS == kMwHeapBufs && 64 % PLP_MW_GROUP == 0 && PLP_MW_ENTRIES <= 64, "line_device.hpp sizes the helpers' lists by kMwHeapBufs");
-constexpr int kMwBufs = PLP_MW_BUFS;         // group buffers per helper: groups it may have finished before main has walked through them
-constexpr int kMwEntries = PLP_MW_ENTRIES;      // results per group buffer; beyond them the rest of the group is main's (16 / 32 / 64 seeds x 8 / 4 / 2 buffers x 4 / 8 / 16 entries measured)
+// tuning of the several-waves path, measured: profiles/r03_lsd_grow.md
+constexpr int kMwGroup = 64;     // seeds per ownership unit (a helper claims a group, main walks them in order; its own loads are 64 seeds)
+constexpr int kMwBufs = 2;       // group buffers per helper: groups it may have finished before main has walked through them
+constexpr int kMwEntries = 16;   // results per group buffer; beyond them the rest of the group is main's (16 / 32 / 64 seeds x 8 / 4 / 2 buffers x 4 / 8 / 16 entries measured)
+static_assert(kMwBufs == kMwHeapBufs && 64 % kMwGroup == 0 && kMwEntries <= 64, "line_device.hpp sizes the helpers' lists by kMwHeapBufs");
 constexpr int kMwInline = 8;         // list entries of a small region kept in the LDS entry itself (main then never touches HBM for it)
 constexpr int kMwAssumed = 192;      // assumed-used pixels per attempt (a pixel is listed once per time it is looked at: up to 8 times)
 struct MwResult { int n1, n2, nfinal, na; bool second, keep; float4 line; };
@@ -1118,15 +1091,10 @@ __device__ __forceinline__ void lds_st(int* p, int v) { __hip_atomic_store(p, v,
 // (the lists in HBM go from one wave of the workgroup to another: WORKGROUP scope -- the waves share the CU's vector cache.  Until round 5 the
 // loads, the stores and the release fence of the hand-over had agent scope: cache-bypassing loads and a write-back of the L2 (buffer_wbl2) per
 // finished region, for readers that do not exist)
-// REQUIREMENT: workgroup scope is enough only while the waves of a workgroup share one CU's vector L1 -- not in threadgroup-split mode.  The build pins
-// -mno-tgsplit (csrc/Makefile; checked by tests/test_kernel_resources.py); a tgsplit build must define PLP_MW_AGENT_SCOPE.
-#ifdef PLP_MW_AGENT_SCOPE      // diagnostic build only (tools/build_variant.sh): the scope of rounds 3 / 4
-#define PLP_MW_SCOPE __HIP_MEMORY_SCOPE_AGENT
-#define PLP_MW_SCOPE_NAME "agent"
-#else
+// REQUIREMENT: workgroup scope is enough only while the waves of a workgroup share one CU's vector L1 -- not in threadgroup-split mode.  A tgsplit
+// build is not supported: the build pins -mno-tgsplit (csrc/Makefile; checked by tests/test_kernel_resources.py).
 #define PLP_MW_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
 #define PLP_MW_SCOPE_NAME "workgroup"
-#endif
 __device__ __forceinline__ uint32_t heap_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, PLP_MW_SCOPE); }
 __device__ __forceinline__ int pix_of(uint32_t c, int sw) { return (int)(c >> 16) * sw + (int)(c & 0xffff); }
 
@@ -1704,10 +1672,7 @@ __constant__ int c_comb[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}
 
 // grid = (2, B), block = 256: one wave per line, 8 lines of a frame in flight (more waves thrash L1/L2: every wave
 // keeps 63 image rows live).
-#ifndef PLP_LBD_U
-#define PLP_LBD_U 8
-#endif
-constexpr int kLbdU = PLP_LBD_U;   // band steps whose gathers are in flight together (per lane = band row)
+constexpr int kLbdU = 8;   // band steps whose gathers are in flight together (per lane = band row)
 __global__ __launch_bounds__(256) void k_lbd(LinePlanes P, LbdWeightsDev W) {
     __shared__ float s_row[4][63][8];   // per row: pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2 (after the global weight)
     __shared__ float s_des[4][72], s_des2[4][72], s_norm[4][4];
@@ -1873,28 +1838,19 @@ __global__ __launch_bounds__(64) void k_line_finalize(LinePlanes P, LsdParams lp
 // ------------------------------------------------------------------------------------------ launch sequence
 void launch_line_front(hipStream_t st, const LinePlanes& P, const LsdParams& lp, const ResizeExactTab& rt, const BlurTapsN& t11,
                        const BlurTapsN& t5, const LbdWeightsDev& w, plp_keyline* out_kl, uint8_t* out_lbd, double* out_fn, int cap,
-                       int32_t* out_counts, int B, hipEvent_t* ev, const LineSideStream* side, int grow_waves, const SeedSortBufs* seed_exact, bool mw_ok, bool grow_on_side) {
+                       int32_t* out_counts, int B, hipEvent_t* ev, int grow_waves, const SeedSortBufs* seed_exact, bool mw_ok) {
     auto mark = [&](int i) { if (ev) (void)hipEventRecord(ev[i], st); };
     // The LBD image pass (5-tap blur + Sobel) does not depend on LSD.  Unless per-stage timing is requested it is launched FIRST, on the
     // same stream: it then overlaps whatever the other streams of the caller run, and nothing has to join before k_lbd.  (A side
     // stream per context did this until round 3: with two line contexts, the ORB stream and the matcher stream that made six streams
     // on the runtime's four hardware queues, and a context's Sobel pass queued behind 8 ms of matcher kernels of an unrelated stream
-    // while its k_lbd waited for it -- profiles/r03c_step_timeline.md.  PLP_LINE_SIDE_STREAM=1 brings the side stream back.)
-    static const bool use_side = [] { const char* e = getenv("PLP_LINE_SIDE_STREAM"); return e && e[0] == '1'; }();
-    const bool fork = side && !ev && use_side && !grow_on_side;
-    const bool sobel_first = !ev && !fork;
-    hipStream_t st2 = fork ? side->stream : st;
+    // while its k_lbd waited for it -- profiles/r03c_step_timeline.md.)
+    const bool sobel_first = !ev;
     const size_t plane_fs = (size_t)P.pitch * P.H, splane_fs = (size_t)P.spitch * P.sh;
     const int tiles = ((P.W + 127) / 128) * ((P.H + kBlurTH - 1) / kBlurTH);
     const int sobel_tiles = ((P.W + kSobelTW - 1) / kSobelTW) * ((P.H + kSobelTH - 1) / kSobelTH);
     const TileDiv blur_td = tile_div(tiles, (P.W + 127) / 128, B), sobel_td = tile_div(sobel_tiles, (P.W + kSobelTW - 1) / kSobelTW, B);
     mark(0);
-    if (fork) {
-        (void)hipEventRecord(side->fork, st);
-        (void)hipStreamWaitEvent(st2, side->fork, 0);
-        hipLaunchKernelGGL(k_blur_sobel, dim3(sobel_tiles, B), dim3(256), 0, st2, P.img, P.img_frame_stride, P.img_pitch, P.dxy, P.W, P.H, t5, sobel_td);
-        (void)hipEventRecord(side->join, st2);
-    }
     if (sobel_first) hipLaunchKernelGGL(k_blur_sobel, dim3(sobel_tiles, B), dim3(256), 0, st, P.img, P.img_frame_stride, P.img_pitch, P.dxy, P.W, P.H, t5, sobel_td);
     if (P.half_exact)
         hipLaunchKernelGGL(k_blur_half, dim3(tiles, B), dim3(256), 0, st, P.img, P.img_frame_stride, P.img_pitch, P.scaled, splane_fs, P.spitch, P.W, P.H, t11, blur_td);
@@ -1913,55 +1869,38 @@ void launch_line_front(hipStream_t st, const LinePlanes& P, const LsdParams& lp,
     mark(3);
     // per wave: USED bitmap + frontier ring (a power of two; the HBM copy of the region list backs larger frontiers).
     // ~10.6 KB of LDS per wave; at 2048 frames every SIMD carries two of these latency-bound waves.
-    static const int ring = [] { const char* e = getenv("PLP_LSD_RING"); int r = e ? atoi(e) : 256; return (r >= 64 && (r & (r - 1)) == 0) ? r : 256; }();
+    constexpr int ring = 256;
     // four waves per workgroup = one per SIMD of the CU that takes the workgroup: with 147 registers three of these waves fit a SIMD, and 2048
     // one-wave workgroups had spread unevenly (13.2 -> 14.2 ms); profiles/r03_lsd_grow.md section 2
-    static const int wpb_env = [] { const char* e = getenv("PLP_LSD_WPB"); return e ? atoi(e) : 4; }();
     const size_t per_wave = (size_t)((((n + 31) / 32 + 1) & ~1) + ring) * 4;
-    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(std::min(4, std::max(1, wpb_env)), 65536 / per_wave));   // (one wave of the largest admitted frame: kLsdGrowLdsBytes, above 64 KB)
-    // diagnostic only (what the rest of a step costs without region growing): PLP_LSD_SKIP_GROW=k leaves the kernel out after
-    // the k-th launch; the later stages then chew on the previous launch's segments
-    static const int skip_after = [] { const char* e = getenv("PLP_LSD_SKIP_GROW"); return e ? atoi(e) : -1; }();
-    static int n_launch = 0;
+    const int wpb = (int)std::max<size_t>(1, std::min<size_t>(4, 65536 / per_wave));   // (one wave of the largest admitted frame: kLsdGrowLdsBytes, above 64 KB)
     // Few frames (plp_line_extract brings one): a workgroup of several waves per frame (k_lsd_grow_mw: one main wave + helpers that
-    // speculate ahead); many frames: one wave per frame, the chip is full of independent scans anyway.
-    static const int mw_max_b = [] { const char* e = getenv("PLP_LSD_MW_MAX_B"); return std::min(e ? atoi(e) : 256, kLsdMwMaxFrames); }();   // 256 = one workgroup per CU
-    static const int mw_waves = [] { const char* e = getenv("PLP_LSD_MW_WAVES"); int r = e ? atoi(e) : kMwMaxWaves; return std::min(std::max(r, 0), kMwMaxWaves); }();
-    static const int mw_policy = [] { const char* e = getenv("PLP_LSD_MW_POLICY"); return e ? atoi(e) : 0; }();   // how helpers treat the claims of finished regions (region_grow)
+    // speculate ahead); many frames: one wave per frame, the chip is full of independent scans anyway.  Up to kLsdMwMaxFrames = 256
+    // frames = one workgroup per CU.
     MwLayout L{};
     size_t mw_bytes = 0;
-    const int want_waves = grow_waves > 0 ? std::min(grow_waves, kMwMaxWaves) : mw_waves;          // plp_line_set_grow_waves overrides the automatic choice
-    if (mw_ok && B <= (grow_waves > 1 ? kLsdMwMaxFrames : mw_max_b) && want_waves >= 2 && P.mw_heap && P.reg_frame_stride >= 2 * (size_t)n) {
+    const int want_waves = grow_waves > 0 ? std::min(grow_waves, kMwMaxWaves) : kMwMaxWaves;          // plp_line_set_grow_waves overrides the automatic choice
+    if (mw_ok && B <= kLsdMwMaxFrames && want_waves >= 2 && P.mw_heap && P.reg_frame_stride >= 2 * (size_t)n) {
         const int nw_al = (((n + 31) / 32 + 1) & ~1), groups_cap = ((P.sw - 1) * (P.sh - 1) + kMwGroup - 1) / kMwGroup + 64 / kMwGroup;
         for (int w = want_waves; w >= 2; --w) {
             const size_t bytes = (size_t)5 * nw_al * 4 + (size_t)w * (nw_al + 256 + kMwAssumed + 2) * 4 + (8 + (4 + 2 * kMwBufs) * kMwMaxWaves) * 4 + ((groups_cap + 15) & ~15) + 16 +
                                  (size_t)(w - 1) * kMwBufs * kMwEntries * sizeof(MwEntry);
-            if (bytes <= 160 * 1024) { L.waves = w; L.ring = 256; L.nw_al = nw_al; L.n_groups_cap = groups_cap; L.lookahead = kMwBufs * (w - 1); L.policy = mw_policy; L.prof = ev ? 1 : 0; mw_bytes = bytes; break; }
+            if (bytes <= 160 * 1024) { L.waves = w; L.ring = 256; L.nw_al = nw_al; L.n_groups_cap = groups_cap; L.lookahead = kMwBufs * (w - 1); L.policy = 0; L.prof = ev ? 1 : 0; mw_bytes = bytes; break; }
         }
     }
-    hipStream_t st_main = st;
-    const bool grow_fork = grow_on_side && side && L.waves < 2;
-    if (grow_fork) { (void)hipEventRecord(side->fork, st); (void)hipStreamWaitEvent(side->stream, side->fork, 0); st = side->stream; }
-    if (skip_after < 0 || n_launch++ < skip_after) {
-        if (L.waves >= 2) {
-            hipLaunchKernelGGL(k_lsd_grow_mw, dim3(B), dim3(64 * L.waves), mw_bytes, st, P, lp, L);
-        } else
-            hipLaunchKernelGGL(k_lsd_grow, dim3((B + wpb - 1) / wpb), dim3(64 * wpb), per_wave * wpb, st, P, lp, B, wpb, ring);
-    }
-    if (grow_fork) { (void)hipEventRecord(side->join, side->stream); st = st_main; (void)hipStreamWaitEvent(st, side->join, 0); }
+    if (L.waves >= 2)
+        hipLaunchKernelGGL(k_lsd_grow_mw, dim3(B), dim3(64 * L.waves), mw_bytes, st, P, lp, L);
+    else
+        hipLaunchKernelGGL(k_lsd_grow, dim3((B + wpb - 1) / wpb), dim3(64 * wpb), per_wave * wpb, st, P, lp, B, wpb, ring);
     mark(4);
     hipLaunchKernelGGL(k_keylines, dim3(B), dim3(64), 0, st, P, lp);
     mark(5);
-    if (fork) (void)hipStreamWaitEvent(st, side->join, 0);
-    else if (!sobel_first) {
-        hipLaunchKernelGGL(k_blur_sobel, dim3(sobel_tiles, B), dim3(256), 0, st, P.img, P.img_frame_stride, P.img_pitch, P.dxy, P.W, P.H, t5, sobel_td);
-    }
+    if (!sobel_first) hipLaunchKernelGGL(k_blur_sobel, dim3(sobel_tiles, B), dim3(256), 0, st, P.img, P.img_frame_stride, P.img_pitch, P.dxy, P.W, P.H, t5, sobel_td);
     mark(6);
     // few resident waves per frame: their 63-row working sets have to stay in L1 / L2.  Workgroups of four waves per frame, kernel alone / step: 1: 1.41 ms /
     // 87.4 k frames/s, 2: 1.37 / 88.0 k, 3: 1.30 / 86.7 k, 4: 1.40 / 87.5 k, 8: 1.64 / 86.8 k, 16: 1.78 / 86.8 k (sessions 35, 36; the step numbers are within
     // their run-to-run spread of each other below 8)
-    static const int lbd_blocks_env = [] { const char* e = getenv("PLP_LBD_BLOCKS"); int r = e ? atoi(e) : 0; return r > 0 ? r : 0; }();
-    const int lbd_blocks = lbd_blocks_env ? lbd_blocks_env : (B >= 64 ? 2 : 16);   // a single frame (plp_line_extract): the chip is empty, one wave per line
+    const int lbd_blocks = B >= 64 ? 2 : 16;   // a single frame (plp_line_extract): the chip is empty, one wave per line
     hipLaunchKernelGGL(k_lbd, dim3(lbd_blocks, B), dim3(256), 0, st, P, w);
     mark(7);
     hipLaunchKernelGGL(k_line_finalize, dim3(B), dim3(64), 0, st, P, lp, out_kl, out_lbd, out_fn, cap, out_counts);

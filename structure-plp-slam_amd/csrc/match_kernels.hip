@@ -537,15 +537,11 @@ __global__ __launch_bounds__(256) void k_match_prep(MatchProblem P) {
     for (int i = tid; i <= ncell; i += 256) P.cell_start[(size_t)b * kCellStride + i] = start[min(i, 4096)];
 }
 
-#ifndef PLP_MATCH_LANE_CAND      // candidates a lane collects before it fetches their descriptors = descriptor fetches in flight per lane.  6: 97 VGPRs, one wave
-#define PLP_MATCH_LANE_CAND 1    // per SIMD beside two region growers; 3: 72, two; 1: 54, three -- and alone the kernel is FASTER with one (the four matcher calls
-#endif                           // 3.84 -> 3.52 ms): its occupancy, not its memory-level parallelism per lane, is what it runs on.  profiles/r03_scheduling_experiments.md
-#if PLP_MATCH_LANE_CAND <= 4
+// candidates a lane collects before it fetches their descriptors = descriptor fetches in flight per lane.  6: 97 VGPRs, one wave per SIMD beside
+// two region growers; 3: 72, two; 1: 54, three -- and alone the kernel is FASTER with one (the four matcher calls 3.84 -> 3.52 ms): its occupancy,
+// not its memory-level parallelism per lane, is what it runs on.  profiles/r03_scheduling_experiments.md
+constexpr int kLaneCand = 1;
 #define PLP_TOPK_CELLS_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8)))
-#else
-#define PLP_TOPK_CELLS_BOUNDS __launch_bounds__(256)
-#endif
-constexpr int kLaneCand = PLP_MATCH_LANE_CAND;   // candidate positions a lane collects before it fetches their descriptors
 
 // 16-lane (DPP row) reductions: four queries share a wave
 __device__ __forceinline__ uint32_t row16_min_u32(uint32_t v) {
@@ -1176,9 +1172,8 @@ void launch_match(hipStream_t st, const MatchProblem& P, int B) {
         Q.sorted_valid = 1;
         // queries per workgroup = queries that share one staging of the frame's targets.  Batches: 512 (alone the kernel is 3 % faster with 256 -- more
         // workgroups in flight -- but the step is 0.7 % faster with 512, six passes each: half as many stagings beside the region growers).  A single
-        // frame or a few (the synchronous host-pointer entry): the CHIP is empty, so many small workgroups (PLP_MATCH_QPB overrides both).
-        static const int qpb_env = [] { const char* e = getenv("PLP_MATCH_QPB"); const int v = e ? atoi(e) : 0; return v >= 16 && v % 16 == 0 ? v : 0; }();
-        const int qpb = qpb_env ? qpb_env : (B >= 64 ? 512 : 32);   // one frame: last-frame matcher 0.40 ms with 32, 0.43 with 64, 0.46 with 256, 0.59 with 512
+        // frame or a few (the synchronous host-pointer entry): the CHIP is empty, so many small workgroups.
+        const int qpb = B >= 64 ? 512 : 32;   // one frame: last-frame matcher 0.40 ms with 32, 0.43 with 64, 0.46 with 256, 0.59 with 512
         hipLaunchKernelGGL(k_match_topk_cells, dim3((P.m_cap + qpb - 1) / qpb, B), dim3(256), staged, st, P, qpb);
     } else if (!line && !windowed && staged <= 64 * 1024) {
         hipLaunchKernelGGL(k_match_topk_lds, qgrid, dim3(256), staged, st, P);

@@ -208,12 +208,7 @@ plp_status run_batch(plp_orb* c, const uint8_t* d_imgs, int B, int rows, int col
     const int nl = g.n_levels;
 
     const bool prof = c->profiling;
-    // PLP_TRACE=1 (diagnostic): every stage boundary waits for the stream and is logged, so that a device fault names its stage
-    static const bool trace = getenv("PLP_TRACE") != nullptr;
-    auto mark = [&](int i) {
-        if (prof) (void)hipEventRecord(c->ev[i], st);
-        if (trace) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "plp_orb: stage boundary %d reached (%dx%d, B=%d)%s\n", i, cols, rows, B, e == hipSuccess ? "" : " ERROR"); fflush(stderr); }
-    };
+    auto mark = [&](int i) { if (prof) (void)hipEventRecord(c->ev[i], st); };
     mark(0);
     OrbPlanes pl{};
     pl.pyr = (uint8_t*)c->pyr.p; pl.pyr_frame_stride = g.frame_plane_bytes;
@@ -256,7 +251,6 @@ plp_status run_batch(plp_orb* c, const uint8_t* d_imgs, int B, int rows, int col
     launch_orient_rbrief(st, pl, (const uint8_t*)c->blur.p, g.frame_plane_bytes, (const LevelDev*)c->d_lv.p, nl, (const int32_t*)c->sel.p,
                          (const int32_t*)c->sel_count.p, g.total_sel_cap, um, d_kps, d_desc, cap, d_counts, (int32_t*)c->status.p, B);
     PLP_HIP(hipGetLastError());
-    if (trace) { const hipError_t e = hipStreamSynchronize(st); fprintf(stderr, "plp_orb: batch done%s\n", e == hipSuccess ? "" : " ERROR"); fflush(stderr); }
     if (prof) {
         mark(6);
         PLP_HIP(hipEventSynchronize(c->ev[6]));

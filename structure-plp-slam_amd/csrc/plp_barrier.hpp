@@ -17,13 +17,8 @@
 #include <hip/hip_runtime.h>
 
 namespace plp {
-#ifdef PLP_SOFT_BARRIERS   // DIAGNOSTIC build only: the barriers as they were until round 6 (with -DPLP_SS_VADDR_GLOBAL this is the reproducer of the failure)
-__device__ __forceinline__ void wg_barrier() { __syncthreads(); }
-__device__ __forceinline__ void wg_barrier_after_global_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); }
-#else
 __device__ __forceinline__ void wg_barrier() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __syncthreads(); }
 // ... and the wave's own global loads / stores too: for data that goes from wave to wave of a workgroup through HBM / L2 (the waves share a CU and its vector L1, which is
 // why the memory model lets a workgroup-scope release skip vmcnt; the storing wave still has to have SENT its stores)
 __device__ __forceinline__ void wg_barrier_after_global_stores() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __syncthreads(); }
-#endif
 }  // namespace plp

@@ -65,11 +65,7 @@ struct HostPinned {
         if (n == 0) n = 16;
         // one page of slack behind the payload: a copy engine / blit kernel that fetches its source in 16-byte (or wider) pieces may
         // touch a few bytes past the last requested one, and the page after a host allocation need not be mapped
-#ifdef PLP_NO_STAGING_SLACK      // diagnostic build only (tools/build_variant.sh): the exactly-sized staging buffer of early round 2
-        hipError_t e = hipHostMalloc(&p, n, hipHostMallocDefault);
-#else
         hipError_t e = hipHostMalloc(&p, n + 4096, hipHostMallocDefault);
-#endif
         if (e == hipSuccess) bytes = n; else p = nullptr;
         return e;
     }

@@ -69,7 +69,7 @@ __device__ __forceinline__ QtShared qt_carve(uint8_t* base, int mn, int blk_word
 // level, and a 16-barrier Hillis-Steele over 256 partials had made barriers its main cost).
 // An array that lives in LDS or in HBM, decided per level (wave-uniform): every access is a DS or a GLOBAL instruction behind a scalar branch -- never a FLAT one (a
 // pointer chosen at run time, `n <= cap ? lds : hbm`, had made every access FLAT: round 6) -- and the code around it exists once (inlining the radix
-// passes and the division once per place cost 0.1 ms per step: 83 spilled SGPRs, twice the code; `tools/sessions/r06/run38.sh`).
+// passes and the division once per place cost 0.1 ms per step: 83 spilled SGPRs, twice the code; `git show 09a8f08:tools/sessions/r06/run38.sh`).
 template <typename T> struct DualArr {
     __attribute__((address_space(3))) T* l; T* g; bool in_lds;
     __device__ __forceinline__ T operator[](int i) const { T v; if (in_lds) v = l[i]; else v = g[i]; return v; }

@@ -141,15 +141,6 @@ template <bool G, bool LM = false> __device__ __forceinline__ int wg_partition(c
         const int nchp = (nch + 2) & ~1;
         Q.pA = M.pA; Q.pBx = M.pA + nchp; Q.pBi = M.pA + 2 * nchp;
         if constexpr (LM) { Q.mL = (unsigned long long*)(M.pA + 3 * nchp); Q.mR = Q.mL + nch; }   // (the caller checked that they fit)
-#if defined(PLP_SS_VADDR_GLOBAL)   // DIAGNOSTIC build only: the masks' HBM copy through GLOBAL instructions whose address sits in vector registers.  Harmless in itself; kept because with
-        // -DPLP_SOFT_BARRIERS (plp_barrier.hpp) this is a build in which the compiler deletes the LDS wait of the barrier that heads the loop over global partitions: the
-        // product-scale reproducer of the fault of rounds 4 - 6 (profiles/r06_seed_sort.md section 4; the other knobs of that hunt: profiles/r06_removed_experiment_knobs.patch)
-        if constexpr (!LM) {
-            unsigned long long v = (unsigned long long)Q.mL, w = (unsigned long long)Q.mR; asm volatile("" : "+v"(v), "+v"(w));
-            typedef __attribute__((address_space(1))) unsigned long long* gp;
-            Q.mL = (unsigned long long*)(gp)v; Q.mR = (unsigned long long*)(gp)w;
-        }
-#endif
     }
     const uint32_t e0 = a[first], ea = a[p0], eb = a[mid], ec = a[last - 1];
     const int m3 = median3_pos(ea >> kSsShift, eb >> kSsShift, ec >> kSsShift, p0, mid, last - 1);

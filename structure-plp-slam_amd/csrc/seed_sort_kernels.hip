@@ -29,22 +29,10 @@ namespace plp {
 // the STEP is what counts: 27.6 ms against 32.7 ms with 16 waves and 144 KB (profiles/r04_seed_sort.md).  Small batches (the single-frame call of
 // data/frame.cc:1146-1163): 16 waves and a 24576-entry window, the shortest time per frame.
 #define SS_NS ss_thr
-#ifndef PLP_SS_THR_WAVES
-#define PLP_SS_THR_WAVES 4
-#endif
-#ifndef PLP_SS_THR_T
-#define PLP_SS_THR_T 4096
-#endif
-#define SS_WAVES PLP_SS_THR_WAVES
-#define SS_T PLP_SS_THR_T
-#ifndef PLP_SS_THR_MINW
-#define PLP_SS_THR_MINW 4   /* at most 128 VGPRs: four workgroups of four waves per CU (5.06 against 6.06 ms alone, 27.1 against 27.7 ms in the step) */
-#endif
-#define SS_MINW PLP_SS_THR_MINW
-#ifndef PLP_SS_THR_TASK
-#define PLP_SS_THR_TASK 4096
-#endif
-#define SS_TASK PLP_SS_THR_TASK
+#define SS_WAVES 4
+#define SS_T 4096
+#define SS_MINW 4   /* at most 128 VGPRs: four workgroups of four waves per CU (5.06 against 6.06 ms alone, 27.1 against 27.7 ms in the step) */
+#define SS_TASK 4096
 #include "seed_sort_impl.inc"
 #undef SS_NS
 #undef SS_WAVES

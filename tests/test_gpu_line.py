@@ -75,6 +75,18 @@ def test_full_hd_frame():
     compare(synth.canvas(2025, 1080, 1920), grow_waves=(0,))
 
 
+def test_several_waves_give_the_oracles_lines(golden_dir):
+    """The several-waves region growing (the latency path, k_lsd_grow_mw) with 3, 5 and 8 waves and the automatic choice: the helpers only change how
+    much speculation is useful -- the main wave validates every result against the committed map -- so every setting must give the oracle's lines, bit
+    for bit.  (Round 5 tried other claim policies and a park / resume of attempts that run into an earlier seed's growing region: exact as well, no
+    faster -- profiles/r05_latency_path.md, profiles/r05_latency_path_series.patch; the protocol with parking: tests/test_spec_grow_model.py.)"""
+    n = len(compare(np.asarray(Image.open(golden_dir / "equirect1_640x480.png")), grow_waves=(0, 3, 5)))
+    n += len(compare(synth.canvas(77, 480, 640), grow_waves=(0, 8)))
+    rng = np.random.default_rng(5)
+    compare(rng.integers(0, 256, (240, 320), dtype=np.uint8), grow_waves=(0,))
+    assert n > 20
+
+
 def test_trim_gives_the_exact_orders_buffers_back_and_the_context_keeps_working():
     """plp_line_set_seed_order frees nothing (hipFree drains the device); plp_line_trim does, and the next call in the exact order allocates again"""
     img = synth.canvas(4242, 480, 640)

@@ -207,7 +207,7 @@ def test_every_barrier_is_reached_with_the_waves_lds_writes_drained():
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="no hipcc")
 def test_the_25_line_reproducer_of_the_deleted_wait_and_its_cure(tmp_path):
     """tools/experiments/soft_wait_loop_header.hip: with __syncthreads() this compiler leaves the loop header's s_barrier without its LDS wait (on the hardware: half of all thread
-    results wrong, tools/sessions/r06/run56.sh); with the hard wait of csrc/plp_barrier.hpp the barrier is reached clean (0 wrong).  The cure is asserted; the defect is reported
+    results wrong, git show 09a8f08:tools/sessions/r06/run56.sh); with the hard wait of csrc/plp_barrier.hpp the barrier is reached clean (0 wrong).  The cure is asserted; the defect is reported
     (a compiler that no longer shows it makes this test say so, not fail)."""
     import subprocess
     chk = _barrier_check()

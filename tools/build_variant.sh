@@ -1,6 +1,6 @@
 #!/bin/bash
 # Build a variant of libplp_front.so into build_exp/<name>.so for a same-box A/B (tools/ab_libs.sh).
-#   bash tools/build_variant.sh <name> "<extra hipcc flags, e.g. -DPLP_CORUN_PRIO=2>"
+#   bash tools/build_variant.sh <name> "<extra hipcc flags, e.g. -DPLP_GROW_PROF_ROUND>"
 set -e
 cd "$(dirname "$0")/.."
 name=$1; extra=$2
