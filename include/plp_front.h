@@ -506,6 +506,66 @@ plp_status plp_post_extract_model_host(plp_matcher* ctx, const plp_camera_model*
                                        int32_t rows, int32_t cols, size_t depth_step, plp_keypoint* undist, double* bearings, float* x_right,
                                        float* depths, const plp_keyline* kl, int32_t n_kl, float* kl_depths, float* kl_x_right);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Local-landmark visibility (the queries of PLP_MATCH_MODE_LANDMARKS[_LINE]): the loops over local_landmarks_ in
+ * tracking_module::search_local_landmarks / search_local_landmarks_line (src/PLPSLAM/tracking_module.cc:908-1064), for B frames at once.
+ *   points  data::frame::can_observe(lm, 0.5, reproj, x_right, pred_scale_level)          data/frame.cc:797-824
+ *           landmark::is_inside_in_orb_scale / get_{min,max}_valid_distance (0.7 x, 1.3 x) data/landmark.h:91-96, landmark.cc:297-307
+ *           landmark::predict_scale_level(float dist, frame*)                              landmark.cc:319-340
+ *   lines   data::frame::can_observe_line (both end points, the midpoint when one is out)  data/frame.cc:827-878
+ *           Line::is_inside_in_feature_scale (0.8 x, 1.2 x), Line::predict_scale_level    data/landmark_line.cc:354-387
+ *   camera::{perspective,fisheye,equirectangular}::reproject_to_image                      camera/perspective.cc:190-209, fisheye.cc:231-249
+ *                                                                                          (the undistorted perspective formula), equirectangular.cc:104-119
+ * Numeric contract: DESIGN.md section 5, D5 (f64 in the reference's order, glibc-free logf = (float)log((double)x), the x86 int cast,
+ * the stale line end points).
+ * Landmark j of problem b is slot b * m_cap + j, in local_landmarks_ order; slots j >= counts[b] are neither read nor written.
+ * skip[j] != 0 = "identifier_in_local_lm_search_ == curr_frm_.id_ || will_be_erased()" (tracking_module.cc:938-946): never valid, no can_observe.
+ * Outputs per slot j < counts[b]:
+ *   out_valid     can_observe[_line]'s result (0 for a skipped slot): is_observable_in_tracking_
+ *   out_level     pred_scale_level (scale_level_in_tracking_), written for valid slots only
+ *   points: out_reproj / out_x_right = (float) of the f64 reprojection (reproj_in_tracking_, x_right_in_tracking_; the facade's cast,
+ *           facade/PLPSLAM/match/projection.h:435-436), written for valid slots only
+ *   lines:  out_reproj / out_reproj2 = the values of the reference's temporaries reproj_sp / reproj_ep after slot j's turn, for EVERY slot:
+ *           reproject_to_image does not write its output for a point with z <= 0 (perspective, fisheye), and the temporaries are declared
+ *           once before the loop (tracking_module.cc:1010-1012), so such an end point carries the value of the most recent earlier
+ *           non-skipped slot whose matching end point had z > 0 -- valid or not -- and (0, 0) before the first one (D5 item 5).
+ *   out_num_valid[b] = number of valid slots (found_proj_candidate = out_num_valid[b] > 0; increase_num_observable per valid slot).
+ * Reprojection only (projection::match_current_and_last_frames, match/projection.cc:254-262; points only): obs_mean_normal == NULL ->
+ * valid = in the image, out_reproj / out_x_right as above, no distance or ray test, out_level not written (may be NULL), min / max ignored.
+ * The host keeps the skip flags and the writes back to the landmark objects. */
+typedef struct plp_observe_args {
+    plp_camera_model camera;        /* model, cols, rows, fx, fy, cx, cy, focal_x_baseline are read (reproject_to_image has no distortion) */
+    float img_bounds[4];            /* camera::base img_bounds_: min_x, max_x, min_y, max_y (float, camera/base.h:68-82) */
+    float ray_cos_thr;              /* points: 0.5 at tracking_module.cc:949 */
+    float log_scale_factor;         /* frame::log_scale_factor_ (points) / _log_scale_factor_lsd (lines) */
+    int32_t num_levels;             /* frame::num_scale_levels_ (points) / _num_scale_levels_lsd (lines), >= 1 */
+    int32_t B, m_cap;               /* B > 0 problems of m_cap >= 0 landmark slots */
+    const double* pose;             /* B x 15: rot_cw_ row-major, trans_cw_, cam_center_ (as the frame holds them, frame.cc:745-751) */
+    const int32_t* counts;          /* B, or NULL = m_cap everywhere */
+    const double* pos_w;            /* B x m_cap x 3 (points: get_pos_in_world) / x 6 (lines: start point, end point) */
+    const double* obs_mean_normal;  /* B x m_cap x 3 (points: get_obs_mean_normal), or NULL = reprojection only; ignored for lines */
+    const float* min_valid_dist;    /* B x m_cap: the raw members min_valid_dist_ / _min_valid_dist (float) */
+    const float* max_valid_dist;    /* B x m_cap: max_valid_dist_ / _max_valid_dist */
+    const uint8_t* skip;            /* B x m_cap, or NULL = nothing skipped */
+    float* out_reproj;              /* B x m_cap x 2 (lines: start point) */
+    float* out_reproj2;             /* lines: B x m_cap x 2 end point; ignored for points */
+    float* out_x_right;             /* points: B x m_cap or NULL; ignored for lines (the reference does not store it) */
+    int32_t* out_level;             /* B x m_cap */
+    uint8_t* out_valid;             /* B x m_cap */
+    int32_t* out_num_valid;         /* B or NULL */
+} plp_observe_args;
+/* Invalid (PLP_ERR_INVALID_ARG, checked before anything is written, m_cap == 0 included): NULL ctx / args; the camera as for
+ * plp_post_extract_model_* (unknown model, fx or fy 0, cols or rows <= 0); B <= 0, m_cap < 0, num_levels <= 0; NULL pose, pos_w,
+ * out_reproj, out_valid; points with obs_mean_normal but NULL min / max_valid_dist or out_level; lines with NULL min / max_valid_dist,
+ * out_reproj2 or out_level.  m_cap == 0: PLP_OK, out_num_valid set to 0, nothing else written.
+ * _device: every array a DEVICE pointer, asynchronous on hip_stream (the outputs go to plp_match_device as q_reproj[2], q_x_right,
+ * q_level, q_valid without a copy).  _host: HOST pointers, staged to HBM (the outputs too, so that every slot the kernel does not write
+ * keeps the caller's value), the same kernel, synchronous. */
+plp_status plp_observe_landmarks_device(plp_matcher* ctx, const plp_observe_args* args, void* hip_stream);
+plp_status plp_observe_landmarks_host(plp_matcher* ctx, const plp_observe_args* args);
+plp_status plp_observe_landmark_lines_device(plp_matcher* ctx, const plp_observe_args* args, void* hip_stream);
+plp_status plp_observe_landmark_lines_host(plp_matcher* ctx, const plp_observe_args* args);
+
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the
  * raw colour / 16-bit depth frames can go straight to HBM.  B frames, device pointers, asynchronous.

@@ -109,6 +109,10 @@ _API = [
     ("plp_post_extract_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
     ("plp_post_extract_model_device", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
     ("plp_post_extract_model_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_observe_landmarks_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_observe_landmarks_host", C.c_int, [_VP, _VP]),
+    ("plp_observe_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_observe_landmark_lines_host", C.c_int, [_VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -532,6 +536,35 @@ class camera_model(camera_model_c):
         return match_grid_c(float(b[0]), float(b[2]), float(inv_w), float(inv_h), self.NUM_GRID_COLS, self.NUM_GRID_ROWS)
 
 
+class observe_args_c(C.Structure):
+    """plp_observe_args"""
+    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("ray_cos_thr", C.c_float), ("log_scale_factor", C.c_float),
+                ("num_levels", C.c_int32), ("B", C.c_int32), ("m_cap", C.c_int32),
+                ("pose", _VP), ("counts", _VP), ("pos_w", _VP), ("obs_mean_normal", _VP), ("min_valid_dist", _VP), ("max_valid_dist", _VP), ("skip", _VP),
+                ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_level", _VP), ("out_valid", _VP), ("out_num_valid", _VP)]
+
+
+def frame_pose(rot_cw, trans_cw):
+    """One problem's pose row of plp_observe_args (15 doubles): rot_cw_ row-major, trans_cw_ and cam_center_ = -rot_cw_^T trans_cw_ formed as
+    frame::update_pose_params does (frame.cc:745-751; each coefficient a left-to-right sum of the negated column times trans_cw_)."""
+    R = [[float(v) for v in row] for row in np.asarray(rot_cw, np.float64).reshape(3, 3)]
+    t = [float(v) for v in np.asarray(trans_cw, np.float64).reshape(3)]
+    cc = [((-R[0][i]) * t[0] + (-R[1][i]) * t[1]) + (-R[2][i]) * t[2] for i in range(3)]
+    return np.array(R[0] + R[1] + R[2] + t + cc, np.float64)
+
+
+def _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, ptrs):
+    a = observe_args_c()
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    b = camera.img_bounds if img_bounds is None else img_bounds
+    a.img_bounds[:] = [float(np.float32(v)) for v in b]
+    a.ray_cos_thr, a.log_scale_factor, a.num_levels = float(ray_cos_thr), float(np.float32(log_scale_factor)), int(num_levels)
+    a.B, a.m_cap = int(B), int(m_cap)
+    for k, v in ptrs.items():
+        setattr(a, k, v)
+    return a
+
+
 class match_grid_c(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("inv_cell_width", C.c_double), ("inv_cell_height", C.c_double),
                 ("cols", C.c_int32), ("rows", C.c_int32)]
@@ -678,6 +711,81 @@ class matcher:
         if kl is not None:
             out.update(kl_depths=kd, kl_x_right=kx)
         return out
+
+    # ---- local-landmark visibility: the queries of match_frame_and_landmarks[_line] (tracking_module.cc:908-1064, plp_observe_landmark[_line]s_*)
+    def _observe_host(self, lines, camera, pose, pos_w, obs_mean_normal, min_valid_dist, max_valid_dist, skip, counts, ray_cos_thr, log_scale_factor,
+                      num_levels, img_bounds):
+        pose = np.ascontiguousarray(pose, np.float64)
+        single = pose.ndim == 1
+        pose = pose.reshape(-1, 15)
+        B = len(pose)
+        w = 6 if lines else 3
+        pw = np.ascontiguousarray(pos_w, np.float64).reshape(B, -1, w)
+        M = pw.shape[1]
+        arr = lambda v, dt, *shape: None if v is None else np.ascontiguousarray(v, dt).reshape(B, M, *shape)
+        nm = None if lines else arr(obs_mean_normal, np.float64, 3)
+        mn, mx, sk = arr(min_valid_dist, np.float32), arr(max_valid_dist, np.float32), arr(skip, np.uint8)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
+        out = dict(reproj=np.zeros((B, M, 2), np.float32), level=np.zeros((B, M), np.int32), valid=np.zeros((B, M), np.uint8), num_valid=np.zeros(B, np.int32))
+        if lines:
+            out["reproj_ep"] = np.zeros((B, M, 2), np.float32)
+        else:
+            out["x_right"] = np.zeros((B, M), np.float32)
+        P = lambda v: None if v is None else v.ctypes.data
+        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, M, dict(
+            pose=P(pose), counts=P(cn), pos_w=P(pw), obs_mean_normal=P(nm), min_valid_dist=P(mn), max_valid_dist=P(mx), skip=P(sk),
+            out_reproj=P(out["reproj"]), out_reproj2=P(out.get("reproj_ep")), out_x_right=P(out.get("x_right")), out_level=P(out["level"]),
+            out_valid=P(out["valid"]), out_num_valid=P(out["num_valid"])))
+        _check((lib().plp_observe_landmark_lines_host if lines else lib().plp_observe_landmarks_host)(self._h, C.byref(a)))
+        if lines:
+            out["reproj_sp"] = out.pop("reproj")
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def observe_landmarks(self, camera, pose, pos_w, obs_mean_normal=None, min_valid_dist=None, max_valid_dist=None, skip=None, counts=None,
+                          ray_cos_thr=0.5, log_scale_factor=None, num_levels=8, img_bounds=None):
+        """frame::can_observe over a frame's local landmarks (tracking_module.cc:929-965).  camera: camera_model (img_bounds from it unless given);
+        pose: frame_pose(...) of one frame (15,) or of B frames (B, 15); pos_w (m, 3) / (B, m, 3); obs_mean_normal None = reprojection only.
+        log_scale_factor defaults to frame::log_scale_factor_ of the scale factor 1.2f (logf as D5 defines it).  Returns dict(reproj, x_right, level, valid,
+        num_valid); the library does not write reproj / x_right / level of invalid slots, so they hold 0."""
+        lsf = np.float32(math.log(np.float32(1.2))) if log_scale_factor is None else log_scale_factor
+        return self._observe_host(False, camera, pose, pos_w, obs_mean_normal, min_valid_dist, max_valid_dist, skip, counts, ray_cos_thr, lsf,
+                                  num_levels, img_bounds)
+
+    def observe_landmark_lines(self, camera, pose, pos_w, min_valid_dist, max_valid_dist, skip=None, counts=None, log_scale_factor=None,
+                               num_levels=2, img_bounds=None):
+        """frame::can_observe_line over a frame's local line landmarks (tracking_module.cc:1004-1045).  pos_w (m, 6) / (B, m, 6): start point,
+        end point; log_scale_factor / num_levels = _log_scale_factor_lsd / _num_scale_levels_lsd (default: scale factor 2, 2 levels).
+        Returns dict(reproj_sp, reproj_ep, level, valid, num_valid); reproj_sp / reproj_ep of every slot are the reference's temporaries after it
+        (DESIGN.md section 5, D5 item 5)."""
+        lsf = np.float32(math.log(np.float32(2.0))) if log_scale_factor is None else log_scale_factor
+        return self._observe_host(True, camera, pose, pos_w, None, min_valid_dist, max_valid_dist, skip, counts, 0.0, lsf, num_levels, img_bounds)
+
+    def _observe_device(self, lines, camera, B, m_cap, pose, pos_w, out_reproj, out_valid, obs_mean_normal, min_valid_dist, max_valid_dist, skip,
+                        counts, out_reproj2, out_x_right, out_level, out_num_valid, ray_cos_thr, log_scale_factor, num_levels, img_bounds, stream):
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, dict(
+            pose=D(pose), counts=D(counts), pos_w=D(pos_w), obs_mean_normal=D(obs_mean_normal), min_valid_dist=D(min_valid_dist),
+            max_valid_dist=D(max_valid_dist), skip=D(skip), out_reproj=D(out_reproj), out_reproj2=D(out_reproj2), out_x_right=D(out_x_right),
+            out_level=D(out_level), out_valid=D(out_valid), out_num_valid=D(out_num_valid)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check((lib().plp_observe_landmark_lines_device if lines else lib().plp_observe_landmarks_device)(self._h, C.byref(a), st))
+
+    def observe_landmarks_device(self, camera, B, m_cap, pose, pos_w, out_reproj, out_valid, obs_mean_normal=None, min_valid_dist=None,
+                                 max_valid_dist=None, skip=None, counts=None, out_x_right=None, out_level=None, out_num_valid=None, ray_cos_thr=0.5,
+                                 log_scale_factor=None, num_levels=8, img_bounds=None, stream=None):
+        """plp_observe_landmarks_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        lsf = np.float32(math.log(np.float32(1.2))) if log_scale_factor is None else log_scale_factor
+        self._observe_device(False, camera, B, m_cap, pose, pos_w, out_reproj, out_valid, obs_mean_normal, min_valid_dist, max_valid_dist, skip,
+                             counts, None, out_x_right, out_level, out_num_valid, ray_cos_thr, lsf, num_levels, img_bounds, stream)
+
+    def observe_landmark_lines_device(self, camera, B, m_cap, pose, pos_w, min_valid_dist, max_valid_dist, out_reproj_sp, out_reproj_ep, out_level,
+                                      out_valid, skip=None, counts=None, out_num_valid=None, log_scale_factor=None, num_levels=2, img_bounds=None,
+                                      stream=None):
+        """plp_observe_landmark_lines_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        lsf = np.float32(math.log(np.float32(2.0))) if log_scale_factor is None else log_scale_factor
+        self._observe_device(True, camera, B, m_cap, pose, pos_w, out_reproj_sp, out_valid, None, min_valid_dist, max_valid_dist, skip, counts,
+                             out_reproj_ep, None, out_level, out_num_valid, 0.0, lsf, num_levels, img_bounds, stream)
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""

@@ -513,6 +513,97 @@ plp_status post_extract_host(plp_matcher* c, const PostArgs& cam_args, const plp
 }
 }  // namespace
 
+// ---- local-landmark visibility (include/plp_front.h: plp_observe_landmark[_line]s_*; kernels in observe_kernels.hip)
+namespace {
+plp_status observe_check(plp_matcher* c, const plp_observe_args* a, bool lines) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, false)) return s;
+    if (a->B <= 0 || a->m_cap < 0 || a->num_levels <= 0) return set_error(PLP_ERR_INVALID_ARG, "B and num_levels must be positive, m_cap non-negative");
+    if (!a->pose || !a->pos_w || !a->out_reproj || !a->out_valid) return set_error(PLP_ERR_INVALID_ARG, "pose, pos_w, out_reproj, out_valid are required");
+    const bool scale = lines || a->obs_mean_normal;
+    if (scale && (!a->min_valid_dist || !a->max_valid_dist || !a->out_level))
+        return set_error(PLP_ERR_INVALID_ARG, "min_valid_dist, max_valid_dist, out_level are required (points: unless obs_mean_normal is NULL)");
+    if (lines && !a->out_reproj2) return set_error(PLP_ERR_INVALID_ARG, "out_reproj2 is required for lines");
+    return PLP_OK;
+}
+
+ObserveArgs observe_args(const plp_observe_args* a, bool lines) {
+    ObserveArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.model = cm.model;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    A.ray_cos_thr = a->ray_cos_thr; A.log_sf = a->log_scale_factor; A.num_levels = a->num_levels; A.m_cap = a->m_cap;
+    A.pose = a->pose; A.counts = a->counts; A.pos_w = a->pos_w; A.normal = lines ? nullptr : a->obs_mean_normal;
+    const bool scale = lines || a->obs_mean_normal;
+    A.min_dist = scale ? a->min_valid_dist : nullptr; A.max_dist = scale ? a->max_valid_dist : nullptr; A.skip = a->skip;
+    A.reproj = a->out_reproj; A.reproj2 = lines ? a->out_reproj2 : nullptr; A.x_right = lines ? nullptr : a->out_x_right;
+    A.level = scale ? a->out_level : nullptr; A.valid = a->out_valid; A.num_valid = a->out_num_valid;
+    return A;
+}
+
+plp_status observe_device(plp_matcher* c, const plp_observe_args* a, bool lines, void* hip_stream) {
+    if (plp_status s = observe_check(c, a, lines)) return s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (a->m_cap == 0) {   // no landmark slot: the reference's loop does not run
+        if (a->out_num_valid) PLP_HIP(hipMemsetAsync(a->out_num_valid, 0, (size_t)a->B * 4, st));
+        return PLP_OK;
+    }
+    const ObserveArgs A = observe_args(a, lines);
+    PLP_HIP(lines ? launch_observe_lines(st, A, a->B) : launch_observe_points(st, A, a->B));
+    return PLP_OK;
+}
+
+// host pointers: every array staged into the context's slab, the device path's kernel, the outputs copied back.  The outputs go to the slab
+// FIRST, as the caller holds them: the kernel leaves slots past counts[b] and the unspecified slots alone, and copying the whole block back
+// must give the caller those slots unchanged (plp_front.h), not whatever an earlier call left in the slab.
+plp_status observe_host(plp_matcher* c, const plp_observe_args* a, bool lines) {
+    if (plp_status s = observe_check(c, a, lines)) return s;
+    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
+    if (M == 0) {
+        if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
+        return PLP_OK;
+    }
+    const ObserveArgs H = observe_args(a, lines);   // which arrays take part (host pointers)
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
+    Part parts[] = {
+        {H.pose, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0}, {H.pos_w, nullptr, BM * (lines ? 6 : 3) * 8, 0},
+        {H.normal, nullptr, BM * 3 * 8, 0}, {H.min_dist, nullptr, BM * 4, 0}, {H.max_dist, nullptr, BM * 4, 0}, {H.skip, nullptr, BM, 0},
+        {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0}, {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.level, BM * 4, 0},
+        {nullptr, H.valid, BM, 0}, {nullptr, H.num_valid, B * 4, 0}};
+    size_t tot = 0;
+    for (Part& p : parts)
+        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    PLP_HIP(c->stage.reserve(tot));
+    uint8_t* base = (uint8_t*)c->stage.p;
+    for (const Part& p : parts)
+        if (p.src || p.dst) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
+    ObserveArgs A = H;
+    A.pose = (const double*)dev(0); A.counts = (const int32_t*)dev(1); A.pos_w = (const double*)dev(2); A.normal = (const double*)dev(3);
+    A.min_dist = (const float*)dev(4); A.max_dist = (const float*)dev(5); A.skip = (const uint8_t*)dev(6);
+    A.reproj = (float*)dev(7); A.reproj2 = (float*)dev(8); A.x_right = (float*)dev(9); A.level = (int32_t*)dev(10); A.valid = (uint8_t*)dev(11);
+    A.num_valid = (int32_t*)dev(12);
+    PLP_HIP(lines ? launch_observe_lines(st, A, a->B) : launch_observe_points(st, A, a->B));
+    for (const Part& p : parts)
+        if (p.dst) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
+    PLP_HIP(hipStreamSynchronize(st));
+    return PLP_OK;
+}
+}  // namespace
+
+plp_status plp_observe_landmarks_device(plp_matcher* c, const plp_observe_args* a, void* hip_stream) { return observe_device(c, a, false, hip_stream); }
+plp_status plp_observe_landmarks_host(plp_matcher* c, const plp_observe_args* a) { return observe_host(c, a, false); }
+plp_status plp_observe_landmark_lines_device(plp_matcher* c, const plp_observe_args* a, void* hip_stream) { return observe_device(c, a, true, hip_stream); }
+plp_status plp_observe_landmark_lines_host(plp_matcher* c, const plp_observe_args* a) { return observe_host(c, a, true); }
+
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
                                            size_t src_frame_stride, int32_t channels, int32_t color_order, int32_t B, uint8_t* d_gray,
                                            size_t gray_step, size_t gray_frame_stride, void* hip_stream) {

@@ -97,6 +97,22 @@ struct PostArgs {
     float cols_f, rows_f;             // equirectangular: (float)cols_, (float)rows_ (unsigned int -> float in pt.x / cols_)
 };
 void launch_post_extract(hipStream_t st, const PostArgs& A, int B);
+
+// local-landmark visibility (observe_kernels.hip, plp_observe_landmark[_line]s_*)
+struct ObserveArgs {
+    int model;                        // plp_camera_model_type: which instantiation runs
+    double fx, fy, cx, cy, fxb;       // camera::perspective / fisheye doubles (reproject_to_image)
+    double cols_d, rows_d;            // equirectangular: cols_, rows_ (unsigned int -> double)
+    float bounds[4];                  // img_bounds_ min_x, max_x, min_y, max_y
+    float ray_cos_thr, log_sf;
+    int num_levels, m_cap;
+    const double* pose; const int32_t* counts; const double* pos_w; const double* normal;
+    const float* min_dist; const float* max_dist; const uint8_t* skip;
+    float* reproj; float* reproj2; float* x_right; int32_t* level; uint8_t* valid; int32_t* num_valid;
+};
+// both return the first error of their calls (the points launcher zeroes num_valid before its kernel adds to it)
+hipError_t launch_observe_points(hipStream_t st, const ObserveArgs& A, int B);
+hipError_t launch_observe_lines(hipStream_t st, const ObserveArgs& A, int B);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,
                     size_t dst_step, size_t dst_fs);
 void launch_to_depth(hipStream_t st, const void* src, int is_u16, int rows, int cols, size_t src_step, size_t src_fs, float scale, int B, float* dst,

@@ -1,0 +1,206 @@
+// Local-landmark visibility (plp_observe_landmarks_* / plp_observe_landmark_lines_*): the loops of tracking_module::search_local_landmarks
+// and search_local_landmarks_line (src/PLPSLAM/tracking_module.cc:908-1064) over local_landmarks_, i.e. data::frame::can_observe
+// (data/frame.cc:797-824) and can_observe_line (:827-878) with camera::*::reproject_to_image of the three models.
+// Numeric contract: DESIGN.md section 5, D5.  f64 in the reference's order (the file is compiled with -ffp-contract=off); the only
+// non-IEEE operations are ocml's f64 asin / atan2 of the equirectangular model (D4) and its f64 log behind predict_scale_level's logf (D5).
+//
+// Points: one lane per landmark, grid = (ceil(m_cap / 256), B), no LDS.
+// Lines: the reference's reproj_sp / reproj_ep temporaries are declared once before the loop and reproject_to_image leaves them alone for a
+// point behind the camera, so an end point can carry the value of an EARLIER landmark (D5 item 5).  One workgroup of four waves per problem
+// walks the landmarks in chunks of 256: the geometry of a chunk in parallel, then "the nearest writer at or below me" from a 64-bit ballot
+// within the wave, the waves' last writers through LDS, and the value carried from the previous chunks.
+#include <hip/hip_runtime.h>
+#include <limits.h>
+#include <stdint.h>
+
+#include "match_device.hpp"
+#include "plp_barrier.hpp"
+#include "plp_common.hpp"
+
+namespace plp {
+namespace {
+
+struct Reproj {
+    double u, v, xr;
+    bool wrote, in;   // wrote: reproj / x_right were assigned (z > 0, or equirectangular); in: the function's result
+};
+
+// camera::*::reproject_to_image.  P = rot_cw_ row-major (0-8), trans_cw_ (9-11), cam_center_ (12-14).
+template <int MODEL>
+__device__ __forceinline__ Reproj reproject(const ObserveArgs& A, const double* P, double x, double y, double z) {
+    Reproj r;
+    const double xc = ((P[0] * x + P[1] * y) + P[2] * z) + P[9];   // rot_cw * pos_w + trans_cw
+    const double yc = ((P[3] * x + P[4] * y) + P[5] * z) + P[10];
+    const double zc = ((P[6] * x + P[7] * y) + P[8] * z) + P[11];
+    if constexpr (MODEL == PLP_CAMERA_EQUIRECTANGULAR) {   // equirectangular.cc:104-119
+        const double sq = (xc * xc + yc * yc) + zc * zc;     // Eigen 3.3 normalized(): v / sqrt(squaredNorm), a zero vector stays zero
+        double bx = xc, by = yc, bz = zc;
+        if (sq > 0.0) {
+            const double s = sqrt(sq);
+            bx = xc / s; by = yc / s; bz = zc / s;
+        }
+        const double latitude = -asin(by);
+        const double longitude = atan2(bx, bz);
+        r.u = A.cols_d * (0.5 + longitude / (2.0 * 3.14159265358979323846));
+        r.v = A.rows_d * (0.5 - latitude / 3.14159265358979323846);
+        r.xr = 0.0;
+        r.wrote = true; r.in = true;
+        return r;
+    } else {   // perspective.cc:190-209; fisheye.cc:231-249 is the same formula
+        r.u = 0.0; r.v = 0.0; r.xr = 0.0;
+        if (zc <= 0.0) { r.wrote = false; r.in = false; return r; }
+        const double z_inv = 1.0 / zc;
+        r.u = (A.fx * xc) * z_inv + A.cx;
+        r.v = (A.fy * yc) * z_inv + A.cy;
+        r.xr = r.u - A.fxb * z_inv;
+        r.wrote = true;
+        r.in = (double)A.bounds[0] < r.u && r.u < (double)A.bounds[1] && (double)A.bounds[2] < r.v && r.v < (double)A.bounds[3];
+        return r;
+    }
+}
+
+// landmark::predict_scale_level (landmark.cc:319-340) / Line::predict_scale_level (landmark_line.cc:366-387)
+__device__ __forceinline__ int predict_level(float max_valid, float dist, float log_sf, int num_levels) {
+    const float ratio = max_valid / dist;
+    const float lg = (float)log((double)ratio);          // std::log(float) = logf, defined as (float)log((double)x) (D5 item 3)
+    const float c = ceilf(lg / log_sf);
+    // static_cast<int> of a value outside int's range (inf, NaN included) is undefined; defined as x86's cvttss2si: INT_MIN (D5 item 4)
+    const int p = (c >= -2147483648.f && c < 2147483648.f) ? (int)c : INT_MIN;
+    if (p < 0) return 0;
+    if ((unsigned)num_levels <= (unsigned)p) return num_levels - 1;
+    return p;
+}
+
+// |v| of cam_to_lm_vec, left to right
+__device__ __forceinline__ double norm3(double x, double y, double z) { return sqrt((x * x + y * y) + z * z); }
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_observe_points(ObserveArgs A) {
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = A.counts ? min(max(A.counts[b], 0), A.m_cap) : A.m_cap;
+    bool ok = false;
+    if (i < n) {
+        const size_t o = (size_t)b * A.m_cap + i;
+        if (!(A.skip && A.skip[o])) {   // frame::can_observe (frame.cc:797-824)
+            const double* P = A.pose + (size_t)15 * b;
+            const double x = A.pos_w[3 * o], y = A.pos_w[3 * o + 1], z = A.pos_w[3 * o + 2];
+            const Reproj r = reproject<MODEL>(A, P, x, y, z);
+            ok = r.in;
+            if (ok && A.normal) {
+                const double dx = x - P[12], dy = y - P[13], dz = z - P[14];
+                const double dist = norm3(dx, dy, dz);
+                const float fd = (float)dist;                                // is_inside_in_orb_scale(const float)
+                const float max_d = (float)(1.3 * (double)A.max_dist[o]);    // get_max_valid_distance (landmark.cc:303-307)
+                const float min_d = (float)(0.7 * (double)A.min_dist[o]);    // get_min_valid_distance (:297-301)
+                ok = min_d <= fd && fd <= max_d;
+                if (ok) {
+                    const double* nm = A.normal + 3 * o;
+                    const double ray_cos = ((dx * nm[0] + dy * nm[1]) + dz * nm[2]) / dist;
+                    ok = !(ray_cos < (double)A.ray_cos_thr);
+                }
+                if (ok) A.level[o] = predict_level(A.max_dist[o], fd, A.log_sf, A.num_levels);
+            }
+            if (ok) {
+                A.reproj[2 * o] = (float)r.u; A.reproj[2 * o + 1] = (float)r.v;
+                if (A.x_right) A.x_right[o] = (float)r.xr;
+            }
+        }
+        A.valid[o] = ok ? 1 : 0;
+    }
+    if (A.num_valid) {   // zeroed by the launcher
+        const unsigned long long m = __ballot(ok);
+        if ((threadIdx.x & 63) == 0 && m) atomicAdd(A.num_valid + b, (int)__popcll(m));
+    }
+}
+
+template <int MODEL>
+__global__ __launch_bounds__(256) void k_observe_lines(ObserveArgs A) {
+    __shared__ float s_last[4][4];   // per wave: its last start-point writer's (x, y), last end-point writer's (x, y)
+    __shared__ int s_has[4][2];
+    __shared__ int s_num[4];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int n = A.counts ? min(max(A.counts[b], 0), A.m_cap) : A.m_cap;
+    const double* P = A.pose + (size_t)15 * b;
+    const unsigned long long at_or_below = ~0ull >> (63 - lane);
+    float c_sx = 0.f, c_sy = 0.f, c_ex = 0.f, c_ey = 0.f;   // the temporaries before the first write: (0, 0) (D5 item 5)
+    int total = 0;
+    for (int base = 0; base < n; base += 256) {   // uniform over the workgroup
+        const int i = base + t;
+        const size_t o = (size_t)b * A.m_cap + i;
+        bool ws = false, we = false, ok = false;
+        float sx = 0.f, sy = 0.f, ex = 0.f, ey = 0.f;
+        int level = 0;
+        if (i < n && !(A.skip && A.skip[o])) {   // frame::can_observe_line (frame.cc:827-878)
+            const double* p = A.pos_w + 6 * o;
+            const double x0 = p[0], y0 = p[1], z0 = p[2], x1 = p[3], y1 = p[4], z1 = p[5];
+            const Reproj rs = reproject<MODEL>(A, P, x0, y0, z0);
+            const Reproj re = reproject<MODEL>(A, P, x1, y1, z1);
+            ws = rs.wrote; we = re.wrote;
+            sx = (float)rs.u; sy = (float)rs.v; ex = (float)re.u; ey = (float)re.v;
+            const double mx = 0.5 * (x0 + x1), my = 0.5 * (y0 + y1), mz = 0.5 * (z0 + z1);
+            ok = rs.in || re.in;
+            if (ok && !(rs.in && re.in)) ok = reproject<MODEL>(A, P, mx, my, mz).in;   // partial occlusion: the midpoint decides
+            if (ok) {
+                const float fd = (float)norm3(mx - P[12], my - P[13], mz - P[14]);     // is_inside_in_feature_scale(const float)
+                const float max_d = (float)(1.2 * (double)A.max_dist[o]);           // Line::get_max_valid_distance (landmark_line.cc:360-364)
+                const float min_d = (float)(0.8 * (double)A.min_dist[o]);           // Line::get_min_valid_distance (:354-358)
+                ok = min_d <= fd && fd <= max_d;
+                if (ok) level = predict_level(A.max_dist[o], fd, A.log_sf, A.num_levels);
+            }
+        }
+        // the temporaries after slot i's turn: the nearest writer at or below this lane in the wave, else in an earlier wave, else the carry
+        const unsigned long long ms = __ballot(ws), me = __ballot(we), mv = __ballot(ok);
+        const unsigned long long ks = ms & at_or_below, ke = me & at_or_below;
+        const int src_s = ks ? 63 - __clzll(ks) : lane, src_e = ke ? 63 - __clzll(ke) : lane;
+        float gsx = __shfl(sx, src_s), gsy = __shfl(sy, src_s), gex = __shfl(ex, src_e), gey = __shfl(ey, src_e);
+        if (lane == 63) {
+            s_last[w][0] = gsx; s_last[w][1] = gsy; s_last[w][2] = gex; s_last[w][3] = gey;
+            s_has[w][0] = ms != 0; s_has[w][1] = me != 0;
+            s_num[w] = (int)__popcll(mv);
+        }
+        wg_barrier();
+        // what precedes this wave: the last wave before it with a writer, else the carry; what follows the chunk: the same over all four
+        float psx = c_sx, psy = c_sy, pex = c_ex, pey = c_ey;
+        for (int v = 0; v < 4; ++v) {
+            if (v == w) {
+                if (!ks) { gsx = psx; gsy = psy; }
+                if (!ke) { gex = pex; gey = pey; }
+            }
+            if (s_has[v][0]) { psx = s_last[v][0]; psy = s_last[v][1]; }
+            if (s_has[v][1]) { pex = s_last[v][2]; pey = s_last[v][3]; }
+            total += s_num[v];
+        }
+        c_sx = psx; c_sy = psy; c_ex = pex; c_ey = pey;
+        if (i < n) {
+            A.reproj[2 * o] = gsx; A.reproj[2 * o + 1] = gsy;
+            A.reproj2[2 * o] = gex; A.reproj2[2 * o + 1] = gey;
+            A.valid[o] = ok ? 1 : 0;
+            if (ok) A.level[o] = level;
+        }
+        wg_barrier();   // the next chunk rewrites s_last
+    }
+    if (t == 0 && A.num_valid) A.num_valid[b] = total;
+}
+
+}  // namespace
+
+hipError_t launch_observe_points(hipStream_t st, const ObserveArgs& A, int B) {
+    if (A.num_valid) {   // the kernel adds each wave's count to it
+        const hipError_t e = hipMemsetAsync(A.num_valid, 0, (size_t)B * sizeof(int32_t), st);
+        if (e != hipSuccess) return e;
+    }
+    const dim3 grid((A.m_cap + 255) / 256, B);
+    if (A.model == PLP_CAMERA_FISHEYE) hipLaunchKernelGGL(k_observe_points<PLP_CAMERA_FISHEYE>, grid, dim3(256), 0, st, A);
+    else if (A.model == PLP_CAMERA_EQUIRECTANGULAR) hipLaunchKernelGGL(k_observe_points<PLP_CAMERA_EQUIRECTANGULAR>, grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(k_observe_points<PLP_CAMERA_PERSPECTIVE>, grid, dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_observe_lines(hipStream_t st, const ObserveArgs& A, int B) {
+    if (A.model == PLP_CAMERA_FISHEYE) hipLaunchKernelGGL(k_observe_lines<PLP_CAMERA_FISHEYE>, dim3(B), dim3(256), 0, st, A);
+    else if (A.model == PLP_CAMERA_EQUIRECTANGULAR) hipLaunchKernelGGL(k_observe_lines<PLP_CAMERA_EQUIRECTANGULAR>, dim3(B), dim3(256), 0, st, A);
+    else hipLaunchKernelGGL(k_observe_lines<PLP_CAMERA_PERSPECTIVE>, dim3(B), dim3(256), 0, st, A);
+    return hipGetLastError();
+}
+
+}  // namespace plp
