@@ -317,7 +317,7 @@ typedef struct plp_match_args {
     const uint8_t* q_has_obs;       /* B x m_cap or NULL (= all 1): landmark::has_observation() */
     const int32_t* q_counts;        /* B, or NULL */
     float margin, lowe_ratio;       /* match::base(lowe_ratio, check_orientation) */
-    int32_t direction;              /* LAST_FRAME: 0 neither, 1 assume_forward, 2 assume_backward */
+    int32_t direction;              /* LAST_FRAME: 0 neither, 1 assume_forward, 2 assume_backward (all problems; see `directions`) */
     int32_t check_orientation;
     int32_t num_levels;
     const float* scale_factors;     /* HOST pointer, num_levels floats (frame::scale_factors_) */
@@ -388,6 +388,10 @@ typedef struct plp_match_args {
      * keeps only that many targets of a frame in LDS -- more of its workgroups fit a compute unit -- and reads the targets of a frame that
      * has more from memory: results never depend on the hint. */
     int32_t t_count_hint;
+    /* LAST_FRAME / LAST_FRAME_LINE with level_window 0: the motion direction of every problem (B values, 0 neither, 1 assume_forward,
+     * 2 assume_backward; any other value = neither), in the entry's pointer space -- what plp_project_last_frame[_lines]_* write to
+     * out_direction.  NULL: `direction` applies to every problem.  Ignored by the other modes. */
+    const int32_t* directions;
 } plp_match_args;
 
 /* All array pointers in `a` are DEVICE pointers (except scale_factors); asynchronous on hip_stream. */
@@ -565,6 +569,64 @@ plp_status plp_observe_landmarks_device(plp_matcher* ctx, const plp_observe_args
 plp_status plp_observe_landmarks_host(plp_matcher* ctx, const plp_observe_args* args);
 plp_status plp_observe_landmark_lines_device(plp_matcher* ctx, const plp_observe_args* args, void* hip_stream);
 plp_status plp_observe_landmark_lines_host(plp_matcher* ctx, const plp_observe_args* args);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Last-frame queries (the queries of PLP_MATCH_MODE_LAST_FRAME[_LINE]): the loops of projection::match_current_and_last_frames
+ * (match/projection.cc:214-358) and match_current_and_last_frames_line (:361-527) in front of their searches, as called from
+ * frame_tracker::motion_based_track, for B (current frame, last frame) pairs at once:
+ *   direction  trans_lc = rot_lw (-rot_cw^T trans_cw) + trans_lw; assume_forward = trans_lc(2) > true_baseline_, assume_backward =
+ *              -trans_lc(2) > true_baseline_, both false for a monocular setup (:219-236, :366-383).  -rot_cw^T trans_cw is read as the
+ *              current pose row's cam_center_ (entries 12-14), which frame::update_pose_params forms from the same expression.
+ *   points     a slot is valid when not skipped and camera_->reproject_to_image(rot_cw, trans_cw, pos_w) is in the image (:240-262)
+ *   lines      both end points reprojected; kept when one is in the image and, if only one is, the midpoint 0.5 (sp + ep) is (:395-440)
+ * Numeric contract: DESIGN.md section 5, D5 items 1-2 (the reprojection is the one plp_observe_* computes) and D6 (the end points of a line
+ * whose out-of-image end point is behind the camera).
+ * Slot j of problem b is key point (key line) j of the last frame, b * m_cap + j; slots j >= counts[b] are neither read nor written.
+ * skip[j] != 0 = "!landmarks_[j] || outlier_flags_[j]" (_landmarks_line / _outlier_flags_line for lines): never valid, not reprojected.
+ * Outputs per slot j < counts[b], in the layout PLP_MATCH_MODE_LAST_FRAME[_LINE] reads (q_valid, q_reproj[2], q_x_right[2], q_level,
+ * q_angle; out_direction -> plp_match_args.directions), so they go to plp_match_device without a copy:
+ *   out_valid     1 where the reference goes on to the search, else 0
+ *   points: out_reproj / out_x_right = (float) of the f64 reprojection and x_right, out_level = keypts[j].octave, out_angle =
+ *           keypts[j].angle (undist_keypts_ keep the octave of keypts_), all written for valid slots only
+ *   lines:  out_reproj / out_reproj2 and out_x_right / out_x_right2 = reproj_sp / reproj_ep and x_right_sp / x_right_ep after slot j's
+ *           turn, for EVERY slot: the reference declares them inside its loop, so an end point with z <= 0 of a kept line reads
+ *           uninitialised values; the library defines them (D6) as the values of the most recent earlier non-skipped slot whose matching
+ *           end point had z > 0, (0, 0) / 0 before the first one.  out_level = keylines[j].octave, written for valid slots only.
+ *   out_direction[b] = 0 neither, 1 assume_forward, 2 assume_backward (written by both entries, also when m_cap == 0)
+ *   out_num_valid[b] = number of valid slots */
+typedef struct plp_last_frame_args {
+    plp_camera_model camera;        /* model, cols, rows, fx, fy, cx, cy, focal_x_baseline are read (as plp_observe_args) */
+    float img_bounds[4];            /* camera::base img_bounds_: min_x, max_x, min_y, max_y */
+    int32_t setup_type;             /* camera::setup_type_t of the current frame's camera: 0 monocular, 1 stereo, 2 RGB-D */
+    double true_baseline;           /* camera::base true_baseline_ (camera/base.h:144) */
+    int32_t B, m_cap;               /* B > 0 problems of m_cap >= 0 slots */
+    const int32_t* counts;          /* B: last_frm.num_keypts_ / _num_keylines, or NULL = m_cap everywhere */
+    const double* pose_curr;        /* B x 15: the current frame's pose row (plp_observe_args.pose layout) */
+    const double* pose_last;        /* B x 15: the last frame's pose row (rot_lw 0-8, trans_lw 9-11 are read) */
+    const double* pos_w;            /* B x m_cap x 3 (points: landmarks_[j]->get_pos_in_world) / x 6 (lines: start point, end point) */
+    const uint8_t* skip;            /* B x m_cap, or NULL = nothing skipped */
+    const plp_keypoint* keypts;     /* points: B x m_cap, the last frame's undist_keypts_ (octave, angle); ignored for lines */
+    const plp_keyline* keylines;    /* lines: B x m_cap, the last frame's _keylsd (octave); ignored for points */
+    float* out_reproj;              /* B x m_cap x 2 (lines: start point) */
+    float* out_reproj2;             /* lines: B x m_cap x 2 end point; ignored for points */
+    float* out_x_right;             /* B x m_cap or NULL (lines: start point) */
+    float* out_x_right2;            /* lines: B x m_cap or NULL, end point; ignored for points */
+    int32_t* out_level;             /* B x m_cap */
+    float* out_angle;               /* points: B x m_cap or NULL; ignored for lines */
+    uint8_t* out_valid;             /* B x m_cap */
+    int32_t* out_direction;         /* B */
+    int32_t* out_num_valid;         /* B or NULL */
+} plp_last_frame_args;
+/* Invalid (PLP_ERR_INVALID_ARG, checked before anything is written, m_cap == 0 included): NULL ctx / args; the camera as for
+ * plp_post_extract_model_*; setup_type outside 0..2; B <= 0, m_cap < 0; NULL pose_curr, pose_last, pos_w, out_reproj, out_level, out_valid,
+ * out_direction; points with NULL keypts; lines with NULL keylines or out_reproj2.  m_cap == 0: PLP_OK, out_direction written,
+ * out_num_valid set to 0, nothing else written.
+ * _device: every array a DEVICE pointer, asynchronous on hip_stream.  _host: HOST pointers, staged to HBM (the outputs too, so that every
+ * slot the kernel does not write keeps the caller's value), the same kernel, synchronous. */
+plp_status plp_project_last_frame_device(plp_matcher* ctx, const plp_last_frame_args* args, void* hip_stream);
+plp_status plp_project_last_frame_host(plp_matcher* ctx, const plp_last_frame_args* args);
+plp_status plp_project_last_frame_lines_device(plp_matcher* ctx, const plp_last_frame_args* args, void* hip_stream);
+plp_status plp_project_last_frame_lines_host(plp_matcher* ctx, const plp_last_frame_args* args);
 
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the

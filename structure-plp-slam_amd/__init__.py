@@ -113,6 +113,10 @@ _API = [
     ("plp_observe_landmarks_host", C.c_int, [_VP, _VP]),
     ("plp_observe_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_observe_landmark_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_project_last_frame_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_project_last_frame_host", C.c_int, [_VP, _VP]),
+    ("plp_project_last_frame_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_project_last_frame_lines_host", C.c_int, [_VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -565,6 +569,30 @@ def _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels,
     return a
 
 
+SETUP_MONOCULAR, SETUP_STEREO, SETUP_RGBD = 0, 1, 2     # camera::setup_type_t (camera/base.h:41-46)
+
+
+class last_frame_args_c(C.Structure):
+    """plp_last_frame_args"""
+    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
+                ("B", C.c_int32), ("m_cap", C.c_int32),
+                ("counts", _VP), ("pose_curr", _VP), ("pose_last", _VP), ("pos_w", _VP), ("skip", _VP), ("keypts", _VP), ("keylines", _VP),
+                ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_x_right2", _VP), ("out_level", _VP), ("out_angle", _VP),
+                ("out_valid", _VP), ("out_direction", _VP), ("out_num_valid", _VP)]
+
+
+def _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, ptrs):
+    a = last_frame_args_c()
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    b = camera.img_bounds if img_bounds is None else img_bounds
+    a.img_bounds[:] = [float(np.float32(v)) for v in b]
+    a.setup_type, a.true_baseline = int(setup_type), float(true_baseline)
+    a.B, a.m_cap = int(B), int(m_cap)
+    for k, v in ptrs.items():
+        setattr(a, k, v)
+    return a
+
+
 class match_grid_c(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("inv_cell_width", C.c_double), ("inv_cell_height", C.c_double),
                 ("cols", C.c_int32), ("rows", C.c_int32)]
@@ -582,7 +610,7 @@ class match_args_c(C.Structure):
                 ("q_group", _VP), ("t_group", _VP), ("q_reproj_d", _VP), ("inv_level_sigma_sq", _VP), ("out_query_best", _VP),
                 ("hamm_dist_thr", C.c_int32), ("level_window", C.c_int32), ("flags", C.c_int32),
                 ("q_reproj2_d", _VP), ("q_bearing", _VP), ("t_bearing", _VP), ("epipolar", _VP),
-                ("out_match", _VP), ("out_num", _VP), ("q_desc_stride", C.c_int32), ("t_count_hint", C.c_int32)]
+                ("out_match", _VP), ("out_num", _VP), ("q_desc_stride", C.c_int32), ("t_count_hint", C.c_int32), ("directions", _VP)]
 
 
 MODE_LANDMARKS, MODE_LAST_FRAME, MODE_BRUTE_FORCE, MODE_LANDMARKS_LINE, MODE_LAST_FRAME_LINE, MODE_BOW, MODE_FUSE, MODE_FUSE_LINE, MODE_TRIANGULATION = 0, 1, 2, 3, 4, 5, 6, 7, 8
@@ -646,9 +674,12 @@ class matcher:
         a.out_match, a.out_num = ptr(out_match), ptr(out_num)
         return a
 
-    def match_host(self, mode, n_cap, m_cap, fields, margin=0.0, direction=0, scale_factors=None, grid=None, B=1):
-        """fields: dict of numpy arrays named like plp_match_args members.  Returns (out_match [B,n_cap], out_num [B])."""
+    def match_host(self, mode, n_cap, m_cap, fields, margin=0.0, direction=0, scale_factors=None, grid=None, B=1, directions=None):
+        """fields: dict of numpy arrays named like plp_match_args members.  Returns (out_match [B,n_cap], out_num [B]).
+        directions: B int32 (plp_match_args.directions: LAST_FRAME[_LINE] per problem), None = `direction` for every problem."""
         fields = {k: (v if (v is None or np.isscalar(v)) else np.ascontiguousarray(v)) for k, v in fields.items()}
+        if directions is not None:
+            fields["directions"] = np.ascontiguousarray(directions, np.int32).reshape(B)
         out_match = np.zeros((B, n_cap), np.int32)
         out_num = np.zeros(B, np.int32)
         a = self._args(mode, B, n_cap, m_cap, fields, margin, direction, scale_factors, grid, out_match, out_num, lambda v: v.ctypes.data)
@@ -661,10 +692,13 @@ class matcher:
         return out_match, out_num
 
     def match_device(self, mode, n_cap, m_cap, fields, out_match, out_num, margin=0.0, direction=0, scale_factors=None, grid=None,
-                     B=1, stream=None):
-        """fields / outputs: torch tensors on the matcher's device.  Asynchronous."""
+                     B=1, stream=None, directions=None):
+        """fields / outputs: torch tensors on the matcher's device.  Asynchronous.  directions: B int32 on the device
+        (e.g. out_direction of project_last_frame[_lines]_device), None = `direction` for every problem."""
         import torch
         st = (stream or torch.cuda.current_stream(out_match.device)).cuda_stream
+        if directions is not None:
+            fields = {**fields, "directions": directions}
         a = self._args(mode, B, n_cap, m_cap, fields, margin, direction, scale_factors, grid, out_match, out_num, lambda v: v.data_ptr())
         _check(lib().plp_match_device(self._h, C.byref(a), st))
 
@@ -786,6 +820,81 @@ class matcher:
         lsf = np.float32(math.log(np.float32(2.0))) if log_scale_factor is None else log_scale_factor
         self._observe_device(True, camera, B, m_cap, pose, pos_w, out_reproj_sp, out_valid, None, min_valid_dist, max_valid_dist, skip, counts,
                              out_reproj_ep, None, out_level, out_num_valid, 0.0, lsf, num_levels, img_bounds, stream)
+
+    # ---- last-frame queries: the loops in front of match_current_and_last_frames[_line] (projection.cc:214-527, plp_project_last_frame[_lines]_*)
+    def _last_frame_host(self, lines, camera, pose_curr, pose_last, pos_w, feats, skip, counts, setup_type, true_baseline, img_bounds, out):
+        pc = np.ascontiguousarray(pose_curr, np.float64)
+        single = pc.ndim == 1
+        pc = pc.reshape(-1, 15)
+        B = len(pc)
+        pl = np.ascontiguousarray(pose_last, np.float64).reshape(B, 15)
+        w = 6 if lines else 3
+        pw = np.ascontiguousarray(pos_w, np.float64).reshape(B, -1, w)
+        M = pw.shape[1]
+        ft = np.ascontiguousarray(feats, KL_DTYPE if lines else KP_DTYPE).reshape(B, M)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(B, M)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
+        shapes = dict(reproj=((B, M, 2), np.float32), x_right=((B, M), np.float32), level=((B, M), np.int32), valid=((B, M), np.uint8),
+                      direction=((B,), np.int32), num_valid=((B,), np.int32))
+        shapes.update(dict(reproj_ep=((B, M, 2), np.float32), x_right_ep=((B, M), np.float32)) if lines else dict(angle=((B, M), np.float32)))
+        o = {}
+        for k, (shape, dt) in shapes.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+            v = None if out is None else out.get(k)
+            if v is not None:
+                if not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                    raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+                o[k] = v
+            else:
+                o[k] = np.zeros(shape, dt)
+        P = lambda v: None if v is None else v.ctypes.data
+        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, M, dict(
+            counts=P(cn), pose_curr=P(pc), pose_last=P(pl), pos_w=P(pw), skip=P(sk), keypts=None if lines else P(ft), keylines=P(ft) if lines else None,
+            out_reproj=P(o["reproj"]), out_reproj2=P(o.get("reproj_ep")), out_x_right=P(o["x_right"]), out_x_right2=P(o.get("x_right_ep")),
+            out_level=P(o["level"]), out_angle=P(o.get("angle")), out_valid=P(o["valid"]), out_direction=P(o["direction"]), out_num_valid=P(o["num_valid"])))
+        _check((lib().plp_project_last_frame_lines_host if lines else lib().plp_project_last_frame_host)(self._h, C.byref(a)))
+        if lines:
+            o["reproj_sp"], o["x_right_sp"] = o.pop("reproj"), o.pop("x_right")
+        return {k: v[0] for k, v in o.items()} if single else o
+
+    def project_last_frame(self, camera, pose_curr, pose_last, pos_w, keypts, skip=None, counts=None, setup_type=SETUP_MONOCULAR, true_baseline=0.0,
+                           img_bounds=None, out=None):
+        """The queries of match_current_and_last_frames (projection.cc:214-262) for one pair ((15,) poses) or B pairs ((B, 15)): pos_w (m, 3) /
+        (B, m, 3) = the last frame's landmark positions by key point, keypts = its undist_keypts_, skip = "!landmarks_[j] || outlier_flags_[j]".
+        Returns dict(reproj, x_right, level, angle, valid, direction, num_valid); reproj / x_right / level / angle of invalid slots are not written
+        (0, or the value of out[name] when the caller passes its own arrays)."""
+        return self._last_frame_host(False, camera, pose_curr, pose_last, pos_w, keypts, skip, counts, setup_type, true_baseline, img_bounds, out)
+
+    def project_last_frame_lines(self, camera, pose_curr, pose_last, pos_w, keylines, skip=None, counts=None, setup_type=SETUP_MONOCULAR,
+                                 true_baseline=0.0, img_bounds=None, out=None):
+        """The queries of match_current_and_last_frames_line (projection.cc:361-450): pos_w (m, 6) / (B, m, 6) start point, end point;
+        keylines = the last frame's _keylsd.  Returns dict(reproj_sp, reproj_ep, x_right_sp, x_right_ep, level, valid, direction, num_valid); the end
+        points of every slot are the reference's temporaries after it as DESIGN.md section 5 D6 defines them."""
+        return self._last_frame_host(True, camera, pose_curr, pose_last, pos_w, keylines, skip, counts, setup_type, true_baseline, img_bounds, out)
+
+    def _last_frame_device(self, lines, camera, B, m_cap, ptrs, setup_type, true_baseline, img_bounds, stream):
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, {k: D(v) for k, v in ptrs.items()})
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check((lib().plp_project_last_frame_lines_device if lines else lib().plp_project_last_frame_device)(self._h, C.byref(a), st))
+
+    def project_last_frame_device(self, camera, B, m_cap, pose_curr, pose_last, pos_w, keypts, out_reproj, out_level, out_valid, out_direction,
+                                  skip=None, counts=None, out_x_right=None, out_angle=None, out_num_valid=None, setup_type=SETUP_MONOCULAR,
+                                  true_baseline=0.0, img_bounds=None, stream=None):
+        """plp_project_last_frame_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        self._last_frame_device(False, camera, B, m_cap, dict(
+            pose_curr=pose_curr, pose_last=pose_last, pos_w=pos_w, keypts=keypts, skip=skip, counts=counts, out_reproj=out_reproj, out_x_right=out_x_right,
+            out_level=out_level, out_angle=out_angle, out_valid=out_valid, out_direction=out_direction, out_num_valid=out_num_valid),
+            setup_type, true_baseline, img_bounds, stream)
+
+    def project_last_frame_lines_device(self, camera, B, m_cap, pose_curr, pose_last, pos_w, keylines, out_reproj_sp, out_reproj_ep, out_level,
+                                        out_valid, out_direction, skip=None, counts=None, out_x_right_sp=None, out_x_right_ep=None,
+                                        out_num_valid=None, setup_type=SETUP_MONOCULAR, true_baseline=0.0, img_bounds=None, stream=None):
+        """plp_project_last_frame_lines_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        self._last_frame_device(True, camera, B, m_cap, dict(
+            pose_curr=pose_curr, pose_last=pose_last, pos_w=pos_w, keylines=keylines, skip=skip, counts=counts, out_reproj=out_reproj_sp,
+            out_reproj2=out_reproj_ep, out_x_right=out_x_right_sp, out_x_right2=out_x_right_ep, out_level=out_level, out_valid=out_valid,
+            out_direction=out_direction, out_num_valid=out_num_valid), setup_type, true_baseline, img_bounds, stream)
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""

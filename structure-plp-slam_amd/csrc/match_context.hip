@@ -95,7 +95,9 @@ plp_status run_device(plp_matcher* c, const plp_match_args* a, hipStream_t st) {
     P.q_desc = a->q_desc; P.q_has_obs = a->q_has_obs; P.q_counts = a->q_counts;
     P.t_kl = a->t_kl; P.t_kp_octave = a->t_kp_octave; P.t_x_right2 = a->t_x_right2; P.q_reproj2 = a->q_reproj2; P.q_x_right2 = a->q_x_right2;
     P.is_rgbd = a->is_rgbd; P.num_levels_lsd = a->num_levels_lsd;
-    P.margin = a->margin; P.lowe_ratio = a->lowe_ratio; P.direction = a->direction; P.check_orientation = a->check_orientation;
+    P.margin = a->margin; P.lowe_ratio = a->lowe_ratio; P.direction = a->direction;
+    P.directions = (a->mode == PLP_MATCH_MODE_LAST_FRAME || a->mode == PLP_MATCH_MODE_LAST_FRAME_LINE) ? a->directions : nullptr;
+    P.check_orientation = a->check_orientation;
     P.num_levels = a->num_levels;
     for (int i = 0; i < 16; ++i) P.scale_factors[i] = (a->scale_factors && i < a->num_levels) ? a->scale_factors[i] : 1.0f;
     P.grid_min_x = a->grid.min_x; P.grid_min_y = a->grid.min_y; P.inv_cell_w = a->grid.inv_cell_width; P.inv_cell_h = a->grid.inv_cell_height;
@@ -193,6 +195,7 @@ plp_status plp_match_host(plp_matcher* c, const plp_match_args* a) {
     const size_t o_qrd2 = add(a->q_reproj2_d, a->q_reproj2_d ? qn * 16 : 0);
     const size_t o_qb = add(a->q_bearing, a->q_bearing ? qn * 24 : 0), o_tb = add(a->t_bearing, a->t_bearing ? tn * 24 : 0);
     const size_t o_ep = add(a->epipolar, a->epipolar ? (size_t)a->B * 96 : 0);
+    const size_t o_dir = add(a->directions, a->directions ? (size_t)a->B * 4 : 0);
     const size_t o_oq = off; off += (qn * 4 + 255) / 256 * 256;
     const size_t o_om = off; off += (tn * 4 + 255) / 256 * 256;
     const size_t o_on = off; off += ((size_t)a->B * 4 + 255) / 256 * 256;
@@ -216,6 +219,7 @@ plp_status plp_match_host(plp_matcher* c, const plp_match_args* a) {
     d.q_reproj_d = (const double*)dp(a->q_reproj_d, o_qrd);
     d.q_reproj2_d = (const double*)dp(a->q_reproj2_d, o_qrd2); d.q_bearing = (const double*)dp(a->q_bearing, o_qb);
     d.t_bearing = (const double*)dp(a->t_bearing, o_tb); d.epipolar = (const double*)dp(a->epipolar, o_ep);
+    d.directions = (const int32_t*)dp(a->directions, o_dir);
     d.out_query_best = a->out_query_best ? (int32_t*)(base + o_oq) : nullptr;
     d.out_match = (int32_t*)(base + o_om); d.out_num = (int32_t*)(base + o_on);
     PLP_TRY(run_device(c, &d, st));
@@ -603,6 +607,87 @@ plp_status plp_observe_landmarks_device(plp_matcher* c, const plp_observe_args* 
 plp_status plp_observe_landmarks_host(plp_matcher* c, const plp_observe_args* a) { return observe_host(c, a, false); }
 plp_status plp_observe_landmark_lines_device(plp_matcher* c, const plp_observe_args* a, void* hip_stream) { return observe_device(c, a, true, hip_stream); }
 plp_status plp_observe_landmark_lines_host(plp_matcher* c, const plp_observe_args* a) { return observe_host(c, a, true); }
+
+// ---- last-frame queries (include/plp_front.h: plp_project_last_frame[_lines]_*; kernels in observe_kernels.hip)
+namespace {
+plp_status last_frame_check(plp_matcher* c, const plp_last_frame_args* a, bool lines) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, false)) return s;
+    if (a->setup_type < 0 || a->setup_type > 2) return set_error(PLP_ERR_INVALID_ARG, "setup_type must be 0 (monocular), 1 (stereo) or 2 (RGB-D)");
+    if (a->B <= 0 || a->m_cap < 0) return set_error(PLP_ERR_INVALID_ARG, "B must be positive, m_cap non-negative");
+    if (!a->pose_curr || !a->pose_last || !a->pos_w || !a->out_reproj || !a->out_level || !a->out_valid || !a->out_direction)
+        return set_error(PLP_ERR_INVALID_ARG, "pose_curr, pose_last, pos_w, out_reproj, out_level, out_valid, out_direction are required");
+    if (lines ? (!a->keylines || !a->out_reproj2) : !a->keypts)
+        return set_error(PLP_ERR_INVALID_ARG, lines ? "keylines and out_reproj2 are required for lines" : "keypts is required for points");
+    return PLP_OK;
+}
+
+ObserveArgs last_frame_args(const plp_last_frame_args* a, bool lines) {
+    ObserveArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.model = cm.model;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    A.m_cap = a->m_cap; A.setup_type = a->setup_type; A.true_baseline = a->true_baseline;
+    A.pose = a->pose_curr; A.pose_last = a->pose_last; A.counts = a->counts; A.pos_w = a->pos_w; A.skip = a->skip;
+    A.kps = lines ? nullptr : a->keypts; A.kl = lines ? a->keylines : nullptr;
+    A.reproj = a->out_reproj; A.reproj2 = lines ? a->out_reproj2 : nullptr; A.x_right = a->out_x_right; A.x_right2 = lines ? a->out_x_right2 : nullptr;
+    A.level = a->out_level; A.angle = lines ? nullptr : a->out_angle; A.valid = a->out_valid; A.direction = a->out_direction; A.num_valid = a->out_num_valid;
+    return A;
+}
+
+plp_status last_frame_device(plp_matcher* c, const plp_last_frame_args* a, bool lines, void* hip_stream) {
+    if (plp_status s = last_frame_check(c, a, lines)) return s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    const ObserveArgs A = last_frame_args(a, lines);
+    PLP_HIP(lines ? launch_last_frame_lines((hipStream_t)hip_stream, A, a->B) : launch_last_frame_points((hipStream_t)hip_stream, A, a->B));
+    return PLP_OK;
+}
+
+// host pointers, staged as observe_host stages them (the outputs first, so that unwritten slots come back as the caller holds them)
+plp_status last_frame_host(plp_matcher* c, const plp_last_frame_args* a, bool lines) {
+    if (plp_status s = last_frame_check(c, a, lines)) return s;
+    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
+    const ObserveArgs H = last_frame_args(a, lines);
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
+    Part parts[] = {
+        {H.pose, nullptr, B * 15 * 8, 0}, {H.pose_last, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0},
+        {H.pos_w, nullptr, BM * (lines ? 6 : 3) * 8, 0}, {H.skip, nullptr, BM, 0}, {H.kps, nullptr, BM * sizeof(plp_keypoint), 0},
+        {H.kl, nullptr, BM * sizeof(plp_keyline), 0},
+        {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0}, {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.x_right2, BM * 4, 0},
+        {nullptr, H.level, BM * 4, 0}, {nullptr, H.angle, BM * 4, 0}, {nullptr, H.valid, BM, 0}, {nullptr, H.direction, B * 4, 0},
+        {nullptr, H.num_valid, B * 4, 0}};
+    size_t tot = 0;
+    for (Part& p : parts)
+        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    PLP_HIP(c->stage.reserve(tot));
+    uint8_t* base = (uint8_t*)c->stage.p;
+    for (const Part& p : parts)
+        if ((p.src || p.dst) && p.bytes) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
+    ObserveArgs A = H;
+    A.pose = (const double*)dev(0); A.pose_last = (const double*)dev(1); A.counts = (const int32_t*)dev(2); A.pos_w = (const double*)dev(3);
+    A.skip = (const uint8_t*)dev(4); A.kps = (const plp_keypoint*)dev(5); A.kl = (const plp_keyline*)dev(6);
+    A.reproj = (float*)dev(7); A.reproj2 = (float*)dev(8); A.x_right = (float*)dev(9); A.x_right2 = (float*)dev(10); A.level = (int32_t*)dev(11);
+    A.angle = (float*)dev(12); A.valid = (uint8_t*)dev(13); A.direction = (int32_t*)dev(14); A.num_valid = (int32_t*)dev(15);
+    PLP_HIP(lines ? launch_last_frame_lines(st, A, a->B) : launch_last_frame_points(st, A, a->B));
+    for (const Part& p : parts)
+        if (p.dst && p.bytes) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
+    PLP_HIP(hipStreamSynchronize(st));
+    return PLP_OK;
+}
+}  // namespace
+
+plp_status plp_project_last_frame_device(plp_matcher* c, const plp_last_frame_args* a, void* hip_stream) { return last_frame_device(c, a, false, hip_stream); }
+plp_status plp_project_last_frame_host(plp_matcher* c, const plp_last_frame_args* a) { return last_frame_host(c, a, false); }
+plp_status plp_project_last_frame_lines_device(plp_matcher* c, const plp_last_frame_args* a, void* hip_stream) { return last_frame_device(c, a, true, hip_stream); }
+plp_status plp_project_last_frame_lines_host(plp_matcher* c, const plp_last_frame_args* a) { return last_frame_host(c, a, true); }
 
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
                                            size_t src_frame_stride, int32_t channels, int32_t color_order, int32_t B, uint8_t* d_gray,

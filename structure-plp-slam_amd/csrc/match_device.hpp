@@ -48,6 +48,7 @@ struct MatchProblem {
     // parameters
     float margin, lowe_ratio;
     int direction, check_orientation, num_levels;
+    const int32_t* directions;       // LAST_FRAME[_LINE]: per-problem direction (NULL: `direction` for all)
     float scale_factors[16];
     float grid_min_x, grid_min_y;
     double inv_cell_w, inv_cell_h;
@@ -109,10 +110,16 @@ struct ObserveArgs {
     const double* pose; const int32_t* counts; const double* pos_w; const double* normal;
     const float* min_dist; const float* max_dist; const uint8_t* skip;
     float* reproj; float* reproj2; float* x_right; int32_t* level; uint8_t* valid; int32_t* num_valid;
+    // last-frame queries (plp_project_last_frame[_lines]_*): pose = the current frame's, the last frame's features instead of the landmark tests
+    const double* pose_last; const plp_keypoint* kps; const plp_keyline* kl;
+    float* angle; float* x_right2; int32_t* direction;
+    int setup_type; double true_baseline;
 };
-// both return the first error of their calls (the points launcher zeroes num_valid before its kernel adds to it)
+// all four return the first error of their calls (the points launchers zero num_valid before their kernels add to it)
 hipError_t launch_observe_points(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_observe_lines(hipStream_t st, const ObserveArgs& A, int B);
+hipError_t launch_last_frame_points(hipStream_t st, const ObserveArgs& A, int B);
+hipError_t launch_last_frame_lines(hipStream_t st, const ObserveArgs& A, int B);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,
                     size_t dst_step, size_t dst_fs);
 void launch_to_depth(hipStream_t st, const void* src, int is_u16, int rows, int cols, size_t src_step, size_t src_fs, float scale, int B, float* dst,

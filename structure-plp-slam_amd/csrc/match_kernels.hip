@@ -84,8 +84,18 @@ __device__ __forceinline__ int fam_mode(int m) {
     else return m;
 }
 
+// assume_forward / assume_backward of the last-frame modes: plp_match_args.directions[b] when given, else the call's scalar.  b is the
+// workgroup's problem in every caller, so the value is one scalar load.  The array is read through a pointer that SAYS it is global memory:
+// written as `P.directions ? P.directions[b] : P.direction` the compiler selected between the two ADDRESSES (kernel argument, HBM) and
+// loaded through a FLAT instruction.
+__device__ __forceinline__ int query_direction(const MatchProblem& P, int b) {
+    typedef const __attribute__((address_space(1))) int32_t* g_i32;
+    return P.directions ? ((g_i32)P.directions)[b] : P.direction;
+}
+
+// dir: the problem's motion direction, query_direction(P, b) (the resolve kernels read it from LDS: see match_resolve_body)
 template <int FAM = kFamAny>
-__device__ __forceinline__ QueryCtx make_query(const MatchProblem& P, int q, int b) {
+__device__ __forceinline__ QueryCtx make_query(const MatchProblem& P, int q, int b, int dir) {
     const int mode = fam_mode<FAM>(P.mode);
     const size_t qoff = (size_t)b * P.m_cap;
     const float* reproj = P.q_reproj ? P.q_reproj + qoff * 2 : nullptr;
@@ -126,9 +136,11 @@ __device__ __forceinline__ QueryCtx make_query(const MatchProblem& P, int q, int
         if (mode == PLP_MATCH_MODE_FUSE_LINE) { c.min_level = -1; c.max_level = -1; }
         else if (mode == PLP_MATCH_MODE_LANDMARKS_LINE || P.level_window == 1) { c.min_level = lvl - 1; c.max_level = lvl; }
         else if (P.level_window == 2) { c.min_level = lvl - 1; c.max_level = lvl + 1; }
-        else if (P.direction == 1) { c.min_level = lvl; c.max_level = P.num_levels_lsd; }
-        else if (P.direction == 2) { c.min_level = 0; c.max_level = lvl + 1; }
-        else { c.min_level = lvl - 1; c.max_level = lvl + 1; }
+        else {
+            if (dir == 1) { c.min_level = lvl; c.max_level = P.num_levels_lsd; }
+            else if (dir == 2) { c.min_level = 0; c.max_level = lvl + 1; }
+            else { c.min_level = lvl - 1; c.max_level = lvl + 1; }
+        }
         c.empty = false;
         return c;
     }
@@ -143,9 +155,11 @@ __device__ __forceinline__ QueryCtx make_query(const MatchProblem& P, int q, int
     if (mode == PLP_MATCH_MODE_LANDMARKS || (mode == PLP_MATCH_MODE_LAST_FRAME && P.level_window == 1)) { c.min_level = lvl - 1; c.max_level = lvl; }
     else if (mode == PLP_MATCH_MODE_FUSE) { c.min_level = -1; c.max_level = -1; }
     else if (P.level_window == 2) { c.min_level = lvl - 1; c.max_level = lvl + 1; }
-    else if (P.direction == 1) { c.min_level = lvl; c.max_level = P.num_levels - 1; }
-    else if (P.direction == 2) { c.min_level = 0; c.max_level = lvl; }
-    else { c.min_level = lvl - 1; c.max_level = lvl + 1; }
+    else {
+        if (dir == 1) { c.min_level = lvl; c.max_level = P.num_levels - 1; }
+        else if (dir == 2) { c.min_level = 0; c.max_level = lvl; }
+        else { c.min_level = lvl - 1; c.max_level = lvl + 1; }
+    }
     // cell range of the window (common.cc:249-271)
     // float window arithmetic, double cell scale (inv_cell_width_ is a double)
     c.min_cx = max(0, floor_d((double)__fsub_rn(__fsub_rn(c.rx, P.grid_min_x), c.mg) * P.inv_cell_w));
@@ -314,7 +328,7 @@ __device__ __forceinline__ void match_topk_query(const MatchProblem& P, int b, i
     const uint8_t* t_desc = P.t_desc + (size_t)b * P.n_cap * 32;
     const float* t_xr = P.t_x_right ? P.t_x_right + (size_t)b * P.n_cap : nullptr;
     const uint8_t* t_occ = P.t_occupied ? P.t_occupied + (size_t)b * P.n_cap : nullptr;
-    const QueryCtx c = make_query<FAM>(P, q, b);
+    const QueryCtx c = make_query<FAM>(P, q, b, query_direction(P, b));
     const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + q) * 32);
     const uint4 q0 = qd[0], q1 = qd[1];
     unsigned long long top[kMatchK];
@@ -366,7 +380,7 @@ __device__ __forceinline__ void match_topk_lanes_block(const MatchProblem& P, in
     QueryCtx c{};
     uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
     if (active) {
-        c = make_query<FAM>(P, q, b);
+        c = make_query<FAM>(P, q, b, query_direction(P, b));
         const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + q) * 32);
         q0 = qd[0]; q1 = qd[1];
     }
@@ -611,6 +625,8 @@ __global__ PLP_TOPK_CELLS_BOUNDS void k_match_topk_cells(MatchProblem P, int qpb
         const uint32_t* g32 = reinterpret_cast<const uint32_t*>(gcs);
         for (int i = tid; i < (ncell + 2) / 2; i += 256) reinterpret_cast<uint32_t*>(cs)[i] = g32[i];
     }
+    __shared__ int s_dir;   // the problem's direction through LDS, as in match_resolve_body (a scalar register held across the query loop spilled)
+    if (tid == 0) s_dir = query_direction(P, b);
     wg_barrier();
     // (the staged copies are read through pointers that SAY they are LDS: written as `i < nb ? sxy[i] : ...` the compiler selected between the two POINTERS and
     // loaded through a FLAT instruction -- round 6 keeps FLAT away from LDS in every kernel, profiles/r06_seed_sort.md)
@@ -628,7 +644,7 @@ __global__ PLP_TOPK_CELLS_BOUNDS void k_match_topk_cells(MatchProblem P, int qpb
         for (int i = 0; i < kMatchK; ++i) { top[i] = 0xffffffffu; ovf[i] = 0xffffffffu; }
         int passed = 0;
         if (active) {
-            const QueryCtx c = make_query(P, q, b);
+            const QueryCtx c = make_query(P, q, b, s_dir);
             if (!c.empty) {
                 const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + q) * 32);
                 const uint4 q0 = qd[0], q1 = qd[1];
@@ -782,6 +798,7 @@ __device__ __forceinline__ void match_resolve_body(const MatchProblem& P) {
     extern __shared__ int32_t lds[];
     __shared__ int s_changed, s_num, s_hist[32], s_valid_bin[32], s_full_n, s_claim_tmp[256], s_sort_ws[48];
     __shared__ unsigned s_sort_idx[32];
+    __shared__ int s_dir;   // the problem's direction for the rare rescan, through LDS: held in a scalar register across the loops it cost 3-4 more spills
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), b = blockIdx.x;
     const int m = P.q_counts ? min(P.q_counts[b], P.m_cap) : P.m_cap;
     const int n = P.t_counts ? min(P.t_counts[b], P.n_cap) : P.n_cap;
@@ -800,6 +817,7 @@ __device__ __forceinline__ void match_resolve_body(const MatchProblem& P) {
 
     for (int t = tid; t < n; t += 256) { owner_final[t] = 0x7fffffff; out[t] = -1; }
     for (int q = tid; q < m; q += 256) claim[q] = -1;
+    if (is_last_frame_mode(mode) && tid == 0) s_dir = query_direction(P, b);   // (other modes never read it)
     wg_barrier();
 
     int32_t* full_list = P.full_list + (size_t)b * P.m_cap;   // queries whose truncated best-K list ran dry
@@ -884,7 +902,7 @@ __device__ __forceinline__ void match_resolve_body(const MatchProblem& P) {
             if (tid == 0 && P.dbg && nf) atomicAdd(&P.dbg[0], nf);
             for (int f = wv; f < nf; f += 4) {
                 const int fq = full_list[f];
-                const QueryCtx c = make_query<FAM>(P, fq, b);
+                const QueryCtx c = make_query<FAM>(P, fq, b, s_dir);
                 const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + fq) * 32);
                 const uint4 q0 = qd[0], q1 = qd[1];
                 unsigned long long k0 = ~0ull, k1 = ~0ull;
@@ -1054,7 +1072,7 @@ __global__ __launch_bounds__(256) void k_match_fuse(MatchProblem P) {
     const plp_keypoint* kps = P.t_kps + (size_t)b * P.n_cap;
     const uint8_t* t_desc = P.t_desc + (size_t)b * P.n_cap * 32;
     const float* t_xr = P.t_x_right ? P.t_x_right + (size_t)b * P.n_cap : nullptr;
-    const QueryCtx c = make_query(P, q, b);
+    const QueryCtx c = make_query(P, q, b, query_direction(P, b));
     const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + q) * 32);
     const uint4 q0 = qd[0], q1 = qd[1];
     unsigned long long best = ~0ull;
