@@ -348,7 +348,7 @@ typedef struct plp_match_args {
     const int32_t* t_group;         /* B x n_cap */
     const double* q_reproj_d;       /* B x m_cap x 2 (FUSE) */
     const float* inv_level_sigma_sq;/* HOST pointer, num_levels floats (FUSE) */
-    int32_t* out_query_best;        /* B x m_cap (FUSE, FUSE_LINE): best key point / key line per query, -1 = none */
+    int32_t* out_query_best;        /* B x m_cap (FUSE, FUSE_LINE): best key point / key line per query, -1 = none; q >= q_counts[b] not written */
     /* Variants of the same loops:
      *  - projection::match_frame_and_keyframe[_line] (projection.cc:529-645, 648-779) = LAST_FRAME[_LINE] with
      *    direction 0, t_x_right NULL / is_rgbd 0, t_occupied = "landmarks_[i] != nullptr", q_has_obs NULL and
@@ -376,7 +376,8 @@ typedef struct plp_match_args {
     const double* t_bearing;        /* B x n_cap x 3 (TRIANGULATION) */
     const double* epipolar;         /* B x 12 (TRIANGULATION) */
     /* outputs: out_match[b][t] = index of the query associated with key point t (-1 = none),
-     * out_num[b] = the matcher's return value (num_matches) */
+     * out_num[b] = the matcher's return value (num_matches).  Slots beyond a problem's count are not written and keep the caller's
+     * values, on both entries: out_match[b][t] for t >= t_counts[b], out_query_best[b][q] (fuse modes) for q >= q_counts[b]. */
     int32_t* out_match;             /* B x n_cap */
     int32_t* out_num;               /* B */
     /* Rows between two problems' blocks in q_desc (0 = m_cap).  In a batched replay the queries of frame b are the features of the
@@ -716,6 +717,15 @@ plp_status plp_landmark_descriptor_host(plp_matcher* ctx, const uint8_t* descs, 
 
 /* Diagnostics: {exact full rescans, resolve rounds, 0, 0} accumulated over all calls of this context (synchronous). */
 plp_status plp_match_debug_counters(plp_matcher* ctx, int64_t* out4);
+/* The kernels plp_match_device / plp_match_host run for a call of this shape; host code only, no context or device.  Reads mode, B, n_cap,
+ * m_cap, t_count_hint, grid.cols / grid.rows and whether t_x_right is NULL (no other pointer).  out4 = {top-k kernel, family, queries per
+ * workgroup, resolve kernel}:
+ *   top-k   1 k_match_prep + k_match_topk_cells, 2 k_match_topk_lds, 3 k_match_topk_lanes<family>, 4 k_match_topk<family>, 5 k_match_fuse
+ *   family  0 none (k_match_fuse), 1 line, 2 group (BOW, TRIANGULATION), 3 point, 4 grid (the sorted resolve after k_match_prep)
+ *   qpb     queries per workgroup of k_match_topk_cells / k_match_topk_lds, 0 for the others
+ *   resolve 1 k_match_resolve_sorted, 2 k_match_resolve_generic<family>, 0 none (fuse modes)
+ * An empty side (n_cap = 0 or m_cap = 0) runs no kernel: all four 0. */
+plp_status plp_match_debug_plan(const plp_match_args* a, int32_t* out4);
 
 /* compute_descriptor_distance_32 over all pairs (match/base.h:43-68): dist[q*nt + t], u16.
  * Device pointers, asynchronous.  (K16: input of brute-force style matchers on the host side.) */

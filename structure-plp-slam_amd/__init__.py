@@ -92,6 +92,7 @@ _API = [
     ("plp_match_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_match_host", C.c_int, [_VP, _VP]),
     ("plp_match_debug_counters", C.c_int, [_VP, _VP]),
+    ("plp_match_debug_plan", C.c_int, [_VP, _VP]),
     ("plp_match_area_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _I32, C.c_float, _I32, _VP, _VP]),
     ("plp_convert_to_grayscale_device", C.c_int, [_VP, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _I32, _I32, _I32, _VP, C.c_size_t, C.c_size_t, _VP]),
     ("plp_convert_to_true_depth_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_size_t, C.c_size_t, C.c_double, _I32, _VP, C.c_size_t, C.c_size_t, _VP]),
@@ -633,6 +634,26 @@ def make_grid(cols_px, rows_px, grid_cols=64, grid_rows=48, min_x=0.0, min_y=0.0
     return match_grid_c(min_x, min_y, float(inv_w), float(inv_h), grid_cols, grid_rows)
 
 
+MATCH_PLAN_TOPK = {0: None, 1: "cells", 2: "lds", 3: "lanes", 4: "topk", 5: "fuse"}
+MATCH_PLAN_FAMILY = {0: "any", 1: "line", 2: "group", 3: "point", 4: "grid"}
+MATCH_PLAN_RESOLVE = {0: None, 1: "sorted", 2: "generic"}
+
+
+def match_plan(mode, B, n_cap, m_cap, grid=None, t_x_right=False, t_count_hint=0):
+    """The kernels plp_match_host / plp_match_device run for a call of this shape (plp_match_debug_plan; no device needed):
+    (top-k kernel, family, queries per workgroup, resolve kernel), e.g. ("cells", "grid", 32, "sorted"); (None, "any", 0, None) for an empty side.
+    t_x_right: whether the call passes t_x_right (it sizes the LDS staging of the windowed modes)."""
+    a = match_args_c()
+    a.mode, a.B, a.n_cap, a.m_cap, a.t_count_hint = mode, B, n_cap, m_cap, int(t_count_hint)
+    keep = np.zeros(1, np.float32)
+    a.t_x_right = keep.ctypes.data if t_x_right else None
+    if grid is not None:
+        a.grid = grid
+    out = np.zeros(4, np.int32)
+    _check(lib().plp_match_debug_plan(C.byref(a), _p(out)))
+    return MATCH_PLAN_TOPK[int(out[0])], MATCH_PLAN_FAMILY[int(out[1])], int(out[2]), MATCH_PLAN_RESOLVE[int(out[3])]
+
+
 class matcher:
     """Array-form mirror of match::projection / match::robust (value-constructed with (lowe_ratio, check_orientation)
     at every call site of the reference, match/base.h:94-110)."""
@@ -674,17 +695,24 @@ class matcher:
         a.out_match, a.out_num = ptr(out_match), ptr(out_num)
         return a
 
-    def match_host(self, mode, n_cap, m_cap, fields, margin=0.0, direction=0, scale_factors=None, grid=None, B=1, directions=None):
+    def match_host(self, mode, n_cap, m_cap, fields, margin=0.0, direction=0, scale_factors=None, grid=None, B=1, directions=None,
+                   out_match=None, out_num=None, out_query_best=None):
         """fields: dict of numpy arrays named like plp_match_args members.  Returns (out_match [B,n_cap], out_num [B]).
-        directions: B int32 (plp_match_args.directions: LAST_FRAME[_LINE] per problem), None = `direction` for every problem."""
+        directions: B int32 (plp_match_args.directions: LAST_FRAME[_LINE] per problem), None = `direction` for every problem.
+        out_match / out_num / out_query_best: C-contiguous int32 arrays [B, n_cap] / [B] / [B, m_cap] the call writes into (and returns);
+        the slots beyond a problem's t_counts / q_counts keep what they hold.  None: fresh arrays."""
         fields = {k: (v if (v is None or np.isscalar(v)) else np.ascontiguousarray(v)) for k, v in fields.items()}
         if directions is not None:
             fields["directions"] = np.ascontiguousarray(directions, np.int32).reshape(B)
-        out_match = np.zeros((B, n_cap), np.int32)
-        out_num = np.zeros(B, np.int32)
+
+        def given(a, shape):
+            assert isinstance(a, np.ndarray) and a.dtype == np.int32 and a.shape == shape and a.flags.c_contiguous, (shape, a)
+            return a
+        out_match = np.zeros((B, n_cap), np.int32) if out_match is None else given(out_match, (B, n_cap))
+        out_num = np.zeros(B, np.int32) if out_num is None else given(out_num, (B,))
         a = self._args(mode, B, n_cap, m_cap, fields, margin, direction, scale_factors, grid, out_match, out_num, lambda v: v.ctypes.data)
         if mode in (MODE_FUSE, MODE_FUSE_LINE):
-            out_q = np.full((B, m_cap), -1, np.int32)
+            out_q = np.full((B, m_cap), -1, np.int32) if out_query_best is None else given(out_query_best, (B, m_cap))
             a.out_query_best = out_q.ctypes.data
             _check(lib().plp_match_host(self._h, C.byref(a)))
             return out_q

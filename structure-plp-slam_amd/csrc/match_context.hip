@@ -70,6 +70,9 @@ plp_status check_args(const plp_match_args* a) {
     return PLP_OK;
 }
 
+// targets of a frame k_match_topk_cells keeps in LDS (plp_match_args.t_count_hint)
+int lds_targets_of(const plp_match_args* a) { return a->t_count_hint > 0 ? std::min(a->t_count_hint, a->n_cap) : a->n_cap; }
+
 plp_status run_device(plp_matcher* c, const plp_match_args* a, hipStream_t st) {
     PLP_HIP(hipSetDevice(c->device));
     const size_t qn = (size_t)a->B * a->m_cap;
@@ -105,7 +108,7 @@ plp_status run_device(plp_matcher* c, const plp_match_args* a, hipStream_t st) {
     P.klist = (uint32_t*)c->klist.p; P.klist2 = (uint32_t*)c->klist2.p; P.kcount = (int32_t*)c->kcount.p; P.claim = (int32_t*)c->claim.p; P.full_list = (int32_t*)c->full_list.p;
     P.sorted = (StagedTarget*)c->sorted.p; P.sorted_xr = (float*)c->sorted_xr.p; P.cell_start = (uint16_t*)c->row_start.p; P.dbg = (int32_t*)c->dbg.p;
     P.out_match = a->out_match; P.out_num = a->out_num;
-    P.lds_targets = a->t_count_hint > 0 ? std::min(a->t_count_hint, a->n_cap) : a->n_cap;
+    P.lds_targets = lds_targets_of(a);
     launch_match(st, P, a->B);
     PLP_HIP(hipGetLastError());
     return PLP_OK;
@@ -222,8 +225,14 @@ plp_status plp_match_host(plp_matcher* c, const plp_match_args* a) {
     d.directions = (const int32_t*)dp(a->directions, o_dir);
     d.out_query_best = a->out_query_best ? (int32_t*)(base + o_oq) : nullptr;
     d.out_match = (int32_t*)(base + o_om); d.out_num = (int32_t*)(base + o_on);
+    // The kernels write only the slots below a problem's count (key points t < t_counts[b]; fuse modes: queries q < q_counts[b]); the rest of the slab
+    // holds whatever an earlier call left.  With counts given, the caller's arrays go in first so that those slots come back unchanged, as on the
+    // device entry.  Without counts every slot is written: nothing to copy.
+    const bool fuse = a->mode == PLP_MATCH_MODE_FUSE || a->mode == PLP_MATCH_MODE_FUSE_LINE;
+    if (fuse && a->q_counts) PLP_HIP(hipMemcpyAsync(base + o_oq, a->out_query_best, qn * 4, hipMemcpyHostToDevice, st));
+    if (!fuse && a->t_counts) PLP_HIP(hipMemcpyAsync(base + o_om, a->out_match, tn * 4, hipMemcpyHostToDevice, st));
     PLP_TRY(run_device(c, &d, st));
-    if (a->mode == PLP_MATCH_MODE_FUSE || a->mode == PLP_MATCH_MODE_FUSE_LINE) {
+    if (fuse) {
         PLP_HIP(hipMemcpyAsync(a->out_query_best, base + o_oq, qn * 4, hipMemcpyDeviceToHost, st));
         PLP_HIP(hipStreamSynchronize(st));
         return PLP_OK;
@@ -818,6 +827,22 @@ plp_status plp_landmark_descriptor_host(plp_matcher* c, const uint8_t* descs, co
     PLP_HIP(hipGetLastError());
     PLP_HIP(hipMemcpyAsync(best_idx, base + o_b, (size_t)L * 4, hipMemcpyDeviceToHost, st));
     PLP_HIP(hipStreamSynchronize(st));
+    return PLP_OK;
+}
+
+plp_status plp_match_debug_plan(const plp_match_args* a, int32_t* out4) {
+    if (!a || !out4) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    for (int i = 0; i < 4; ++i) out4[i] = 0;
+    if (a->mode < PLP_MATCH_MODE_LANDMARKS || a->mode > PLP_MATCH_MODE_TRIANGULATION) return set_error(PLP_ERR_INVALID_ARG, "unknown mode");
+    if (a->B <= 0 || a->n_cap < 0 || a->m_cap < 0) return set_error(PLP_ERR_INVALID_ARG, "B must be positive, n_cap and m_cap non-negative");
+    if (a->n_cap > 8192) return set_error(PLP_ERR_UNSUPPORTED, "more than 8192 key points per frame");
+    if (a->n_cap == 0 || a->m_cap == 0) return PLP_OK;   // an empty side: no kernel runs
+    MatchProblem P{};
+    P.mode = a->mode; P.n_cap = a->n_cap; P.m_cap = a->m_cap; P.t_x_right = a->t_x_right;
+    P.grid_cols = a->grid.cols; P.grid_rows = a->grid.rows;
+    P.lds_targets = lds_targets_of(a);
+    const MatchPlan pl = plan_match(P, a->B);
+    out4[0] = pl.topk; out4[1] = pl.family; out4[2] = pl.qpb; out4[3] = pl.resolve;
     return PLP_OK;
 }
 

@@ -72,6 +72,20 @@ struct MatchProblem {
 struct MihRanks { uint8_t rank[256]; };   // enumeration rank of an 8-bit flip pattern inside its popcount class (Mihasher::query)
 void launch_lbd_match_1nn(hipStream_t st, const uint8_t* q, const int32_t* q_counts, int nq_cap, const uint8_t* t, const int32_t* t_counts,
                           int nt_cap, const MihRanks& R, int32_t* out_idx, int32_t* out_dist, int B);
+// The kernels of one matcher call: a top-k kernel and a resolve kernel, chosen from the mode, B, n_cap, the LDS staging size and the grid shape.
+// plan_match() is the one place that decides; launch_match() launches what it returns and plp_match_debug_plan reports it.
+enum MatchFamily { kFamAny = 0, kFamLine = 1, kFamGroup = 2, kFamPoint = 3, kFamGrid = 4 };   // kFamGrid: the two windowed point modes after k_match_prep
+enum MatchTopk { kTopkNone = 0, kTopkCells = 1, kTopkLds = 2, kTopkLanes = 3, kTopkGeneric = 4, kTopkFuse = 5 };
+enum MatchResolve { kResolveNone = 0, kResolveSorted = 1, kResolveGeneric = 2 };
+struct MatchPlan {
+    int topk;        // MatchTopk: k_match_prep + k_match_topk_cells, k_match_topk_lds, k_match_topk_lanes<family>, k_match_topk<family>, k_match_fuse
+    int family;      // MatchFamily of the templated kernels (kFamGrid: the sorted resolve; kFamAny: k_match_fuse)
+    int qpb;         // queries per workgroup of k_match_topk_cells / k_match_topk_lds, 0 for the others
+    int resolve;     // MatchResolve: k_match_resolve_sorted, k_match_resolve_generic<family>, none (fuse modes)
+    size_t staged;   // dynamic LDS of the top-k kernel (cells, lds)
+};
+// reads P.mode, n_cap, m_cap, lds_targets, t_x_right (NULL or not), grid_cols, grid_rows
+MatchPlan plan_match(const MatchProblem& P, int B);
 void launch_match(hipStream_t st, const MatchProblem& P, int B);
 hipError_t configure_match_kernels();   // per-device kernel attributes (dynamic LDS of k_match_resolve)
 struct AreaArgs {

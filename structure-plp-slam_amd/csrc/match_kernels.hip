@@ -74,7 +74,7 @@ __device__ __forceinline__ bool is_last_frame_mode(int mode) { return mode == PL
 // every mode at once they kept all modes' pointers and gates live (81-125 scalar registers spilled, a scratch frame per wave).  An
 // instantiation reads the mode through fam_mode<FAM>(): a select over the constants of its family, so every test for another family's
 // mode folds away at compile time and that family's arguments are never loaded.  launch_match() picks the instantiation from the same value.
-enum MatchFamily { kFamAny = 0, kFamLine = 1, kFamGroup = 2, kFamPoint = 3, kFamGrid = 4 };   // kFamGrid: the two windowed point modes after k_match_prep
+// (MatchFamily: match_device.hpp)
 template <int FAM>
 __device__ __forceinline__ int fam_mode(int m) {
     if constexpr (FAM == kFamLine) return m == PLP_MATCH_MODE_LANDMARKS_LINE ? PLP_MATCH_MODE_LANDMARKS_LINE : PLP_MATCH_MODE_LAST_FRAME_LINE;
@@ -1176,41 +1176,57 @@ void launch_match_area(hipStream_t st, const AreaArgs& A) { hipLaunchKernelGGL(k
 
 static bool is_line_mode_host(int mode) { return mode == PLP_MATCH_MODE_LANDMARKS_LINE || mode == PLP_MATCH_MODE_LAST_FRAME_LINE || mode == PLP_MATCH_MODE_FUSE_LINE; }
 
-void launch_match(hipStream_t st, const MatchProblem& P, int B) {
-    if (P.mode == PLP_MATCH_MODE_FUSE || P.mode == PLP_MATCH_MODE_FUSE_LINE) { hipLaunchKernelGGL(k_match_fuse, dim3((P.m_cap + 3) / 4, B), dim3(256), 0, st, P); return; }
-    MatchProblem Q = P;
-    Q.sorted_valid = 0;
+MatchPlan plan_match(const MatchProblem& P, int B) {
+    MatchPlan pl{kTopkNone, kFamAny, 0, kResolveNone, 0};
+    if (P.mode == PLP_MATCH_MODE_FUSE || P.mode == PLP_MATCH_MODE_FUSE_LINE) { pl.topk = kTopkFuse; return pl; }
     const bool windowed = P.mode == PLP_MATCH_MODE_LANDMARKS || P.mode == PLP_MATCH_MODE_LAST_FRAME;
     const bool line = is_line_mode_host(P.mode) || P.mode == PLP_MATCH_MODE_BOW || P.mode == PLP_MATCH_MODE_TRIANGULATION;
-    const int fam = is_line_mode_host(P.mode) ? kFamLine : (P.mode == PLP_MATCH_MODE_BOW || P.mode == PLP_MATCH_MODE_TRIANGULATION) ? kFamGroup : kFamPoint;
-    const size_t staged = windowed ? (size_t)P.lds_targets * (P.t_x_right ? 16 : 12) + 2 * kCellStride : (size_t)P.n_cap * 32;
-    const dim3 qgrid((P.m_cap + kQueriesPerBlock - 1) / kQueriesPerBlock, B);
-    if (!line && windowed && staged <= 64 * 1024 && P.grid_cols <= 255 && P.grid_rows <= 255) {
-        hipLaunchKernelGGL(k_match_prep, dim3(B), dim3(256), 0, st, P);
-        Q.sorted_valid = 1;
+    pl.family = is_line_mode_host(P.mode) ? kFamLine : (P.mode == PLP_MATCH_MODE_BOW || P.mode == PLP_MATCH_MODE_TRIANGULATION) ? kFamGroup : kFamPoint;
+    pl.staged = windowed ? (size_t)P.lds_targets * (P.t_x_right ? 16 : 12) + 2 * kCellStride : (size_t)P.n_cap * 32;
+    pl.resolve = kResolveGeneric;
+    if (!line && windowed && pl.staged <= 64 * 1024 && P.grid_cols <= 255 && P.grid_rows <= 255) {
+        pl.topk = kTopkCells;
+        pl.family = kFamGrid;
+        pl.resolve = kResolveSorted;
         // queries per workgroup = queries that share one staging of the frame's targets.  Batches: 512 (alone the kernel is 3 % faster with 256 -- more
         // workgroups in flight -- but the step is 0.7 % faster with 512, six passes each: half as many stagings beside the region growers).  A single
         // frame or a few (the synchronous host-pointer entry): the CHIP is empty, so many small workgroups.
-        const int qpb = B >= 64 ? 512 : 32;   // one frame: last-frame matcher 0.40 ms with 32, 0.43 with 64, 0.46 with 256, 0.59 with 512
-        hipLaunchKernelGGL(k_match_topk_cells, dim3((P.m_cap + qpb - 1) / qpb, B), dim3(256), staged, st, P, qpb);
-    } else if (!line && !windowed && staged <= 64 * 1024) {
-        hipLaunchKernelGGL(k_match_topk_lds, qgrid, dim3(256), staged, st, P);
+        pl.qpb = B >= 64 ? 512 : 32;   // one frame: last-frame matcher 0.40 ms with 32, 0.43 with 64, 0.46 with 256, 0.59 with 512
+    } else if (!line && !windowed && pl.staged <= 64 * 1024) {
+        pl.topk = kTopkLds;
+        pl.qpb = kQueriesPerBlock;
+    } else {
+        pl.topk = (P.n_cap <= 512 && B >= 64) ? kTopkLanes : kTopkGeneric;   // lanes: small target sets, many frames
+        pl.staged = 0;
+    }
+    return pl;
+}
+
+void launch_match(hipStream_t st, const MatchProblem& P, int B) {
+    const MatchPlan pl = plan_match(P, B);
+    if (pl.topk == kTopkFuse) { hipLaunchKernelGGL(k_match_fuse, dim3((P.m_cap + 3) / 4, B), dim3(256), 0, st, P); return; }
+    MatchProblem Q = P;
+    Q.sorted_valid = pl.resolve == kResolveSorted;
+    const int fam = pl.family;
+    if (pl.topk == kTopkCells) {
+        hipLaunchKernelGGL(k_match_prep, dim3(B), dim3(256), 0, st, P);
+        hipLaunchKernelGGL(k_match_topk_cells, dim3((P.m_cap + pl.qpb - 1) / pl.qpb, B), dim3(256), pl.staged, st, P, pl.qpb);
+    } else if (pl.topk == kTopkLds) {
+        hipLaunchKernelGGL(k_match_topk_lds, dim3((P.m_cap + pl.qpb - 1) / pl.qpb, B), dim3(256), pl.staged, st, P);
+    } else if (pl.topk == kTopkLanes) {
+        const dim3 g(std::min((P.m_cap + 63) / 64, 2), B);
+        if (fam == kFamLine) hipLaunchKernelGGL(k_match_topk_lanes<kFamLine>, g, dim3(64), 0, st, P);
+        else if (fam == kFamGroup) hipLaunchKernelGGL(k_match_topk_lanes<kFamGroup>, g, dim3(64), 0, st, P);
+        else hipLaunchKernelGGL(k_match_topk_lanes<kFamPoint>, g, dim3(64), 0, st, P);
     } else {
         const int gx_full = (P.m_cap + 3) / 4, gx_min = std::max(16, (8192 + B - 1) / B);   // keep >= ~8K workgroups in flight
-        if (P.n_cap <= 512 && B >= 64) {   // small target sets, many frames
-            const dim3 g(std::min((P.m_cap + 63) / 64, 2), B);
-            if (fam == kFamLine) hipLaunchKernelGGL(k_match_topk_lanes<kFamLine>, g, dim3(64), 0, st, P);
-            else if (fam == kFamGroup) hipLaunchKernelGGL(k_match_topk_lanes<kFamGroup>, g, dim3(64), 0, st, P);
-            else hipLaunchKernelGGL(k_match_topk_lanes<kFamPoint>, g, dim3(64), 0, st, P);
-        } else {
-            const dim3 g(std::min(gx_full, gx_min), B);
-            if (fam == kFamLine) hipLaunchKernelGGL(k_match_topk<kFamLine>, g, dim3(256), 0, st, P);
-            else if (fam == kFamGroup) hipLaunchKernelGGL(k_match_topk<kFamGroup>, g, dim3(256), 0, st, P);
-            else hipLaunchKernelGGL(k_match_topk<kFamPoint>, g, dim3(256), 0, st, P);
-        }
+        const dim3 g(std::min(gx_full, gx_min), B);
+        if (fam == kFamLine) hipLaunchKernelGGL(k_match_topk<kFamLine>, g, dim3(256), 0, st, P);
+        else if (fam == kFamGroup) hipLaunchKernelGGL(k_match_topk<kFamGroup>, g, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL(k_match_topk<kFamPoint>, g, dim3(256), 0, st, P);
     }
     const size_t owners = (size_t)P.n_cap * 12;
-    if (Q.sorted_valid) hipLaunchKernelGGL(k_match_resolve_sorted, dim3(B), dim3(256), owners, st, Q);
+    if (pl.resolve == kResolveSorted) hipLaunchKernelGGL(k_match_resolve_sorted, dim3(B), dim3(256), owners, st, Q);
     else if (fam == kFamLine) hipLaunchKernelGGL(k_match_resolve_generic<kFamLine>, dim3(B), dim3(256), owners, st, Q);
     else if (fam == kFamGroup) hipLaunchKernelGGL(k_match_resolve_generic<kFamGroup>, dim3(B), dim3(256), owners, st, Q);
     else hipLaunchKernelGGL(k_match_resolve_generic<kFamPoint>, dim3(B), dim3(256), owners, st, Q);

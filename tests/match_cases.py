@@ -81,7 +81,8 @@ SF8 = (np.float32(1.2) ** np.arange(8)).astype(np.float32)
 SF_LSD = np.array([1.0, 2.0], np.float32)
 
 
-def triangulation_problem(rng, n, m, nodes, words):
+def triangulation_problem(rng, n, m, nodes, words, tr=(0.3, 0.02, 0.05)):
+    """tr: translation of key frame 2 (R = I): E_12 = [tr]_x and the epipole differ with it"""
     t, q = random_problem(rng, n, m, n_words=words)
     t_node = (t["t_desc"][:, 0].astype(np.int32) * 7 + 3) % nodes
     q_node = (q["q_desc"][:, 0].astype(np.int32) * 7 + 3) % nodes
@@ -90,7 +91,7 @@ def triangulation_problem(rng, n, m, nodes, words):
     q_has_lm = (rng.uniform(size=m) < 0.3).astype(np.uint8); t_has_lm = (rng.uniform(size=n) < 0.3).astype(np.uint8)
     q_xr = np.where(rng.uniform(size=m) < 0.3, 100.0, -1.0).astype(np.float32); t_xr = np.where(rng.uniform(size=n) < 0.3, 100.0, -1.0).astype(np.float32)
     q_oct = rng.integers(0, 8, m).astype(np.int32)
-    tr = np.array([0.3, 0.02, 0.05])
+    tr = np.asarray(tr, np.float64)
     E = np.array([[0, -tr[2], tr[1]], [tr[2], 0, -tr[0]], [-tr[1], tr[0], 0]], np.float64)
     epipole = -tr / np.linalg.norm(tr)
     pts_t = np.stack([rng.uniform(-2, 2, n), rng.uniform(-1.5, 1.5, n), rng.uniform(1, 8, n)], 1)
