@@ -16,11 +16,15 @@ constexpr int kQtMaxNodesLds = 5888;
 // up to 2 010, i.e. ONE level at K = 2 000 -- what the reference's orb_params accept and round 5 still refused (feature/orb_params.cc:40-54).
 constexpr int kQtMaxNodesLdsSmallBlock = 6040;
 
+// k_blur7: one wave blurs a strip of kBlur7W output columns (lanes 1..62, four columns each; lanes 0 and 63 only load the strip's side halo) and
+// kBlur7H output rows.
+constexpr int kBlur7W = 248, kBlur7H = 64;
+
 // Per-level constants as seen by the kernels (array of n_levels in HBM + a host copy).
 struct LevelDev {
     int w, h, pitch;        // level size, row pitch in the pyramid / blur planes
-    int blur_tiles;         // number of 128x64 blur tiles of this level
-    uint32_t blur_tiles_x_magic;   // plp_div_magic of the level's tile columns (xcd_map.hpp): a tile index -> (column, row) without a vector division
+    int blur_tiles;         // number of k_blur7 strips of this level (kBlur7W columns x kBlur7H rows each)
+    uint32_t blur_tiles_x_magic;   // plp_div_magic of the level's strip columns (xcd_map.hpp): a strip index -> (column, row) without a vector division
     size_t off;             // byte offset of the level inside one frame's plane set
     float scale;            // scale_factors_[level]
     int sel_base, sel_cap;  // slot range of this level in the per-frame selected list

@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "blur_tile.hpp"
 #include "plp_barrier.hpp"
 #include "orb_device.hpp"
 #include "plp_common.hpp"
@@ -412,24 +411,153 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 }
 
 // ------------------------------------------------------------------------------------------
-// K6  7x7 sigma-2 Gaussian, 8.8 fixed-point taps (sum 256), exact separable integer passes (blur_tile.hpp).
-// One workgroup = 128 x 64 output tile of one level of one frame; all levels in one launch.
-// grid = (tiles of all levels, B), block = 256.
+// K6  7x7 sigma-2 Gaussian, 8.8 fixed-point taps (sum 256): out = (sum_j k[j] * (sum_i k[i] * src) + 32768) >> 16, REFLECT_101.
+// Exact integer arithmetic without intermediate rounding, as in blur_tile.hpp, so the bytes are those of the tiled blur; but no LDS and no
+// barrier: every WAVE walks down a strip of kBlur7W x kBlur7H output pixels on its own.  Lane i holds the source dword at
+// x = x0 + 4 (i - 1) of each row and takes its neighbours' dwords with two DPP wave shifts, so lanes 1..62 own four output columns each
+// and lanes 0 / 63 only load the strip's side halo.  A row's four horizontal sums (v_dot4_u32_u8 against byte-shifted taps, as in
+// blur_tile_compute) go into u16 pairs of two consecutive rows; the last four pairs, eight source rows, stay in registers, and every step of
+// two source rows makes two output rows with v_dot2_u32_u16 (taps (k0,k1),(k2,k3).. for the even row, (0,k0),(k1,k2).. for the odd one).
+// The source rows of the step after next are in flight during a step.
+// Borders: rows are reflected by index (wave-uniform); at the left and right image border the lane's 12-byte window is reflected in registers
+// with v_perm_b32 (the bytes a reflected column needs always lie inside the same window), in the strips that touch a border only.
+// Until round 7 the blur was blur_tile<3>: 128 x 32 tiles staged through LDS in three phases with two workgroup barriers (40 % issue-stalled).
+// grid = (ceil(strips of all levels / 4), B), block = 256: four independent waves.
 // ------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t b7_dot2(uint32_t a, uint32_t b, uint32_t c) {
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    return __builtin_amdgcn_udot2(__builtin_bit_cast(us2, a), __builtin_bit_cast(us2, b), c, false);
+}
+
+template <bool EDGE>
+__device__ __forceinline__ void blur7_strip(const uint8_t* __restrict__ src, int sp, uint8_t* __restrict__ dst, int dp, int w, int h, int x, int y0, int y1,
+                                            const int* __restrict__ k) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t xl = (uint32_t)min(max(x, 0), (w - 1) & ~3);   // a whole dword of the row; lanes outside the image load a stand-in
+    const bool out_lane = lane >= 1 && lane <= 62 && x < w;
+    // taps: tp[e][m] = taps shifted by e bytes, four to a dword (horizontal); te / to = tap pairs of an even / odd output row (vertical)
+    uint32_t tp[4][3];
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int i = 4 * m + b - e;
+                if (i >= 0 && i < 7) v |= (uint32_t)k[i] << (8 * b);
+            }
+            tp[e][m] = v;
+        }
+    uint32_t te[4], to[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        te[j] = (uint32_t)k[2 * j] | (j < 3 ? (uint32_t)k[2 * j + 1] << 16 : 0u);
+        to[j] = (j > 0 ? (uint32_t)k[2 * j - 1] : 0u) | ((uint32_t)k[2 * j] << 16);
+    }
+    // border windows.  The lane's window W[0..11] = bytes x-4 .. x+7 (dwords l, c, r); output o reads W[o+1 .. o+7].  At the right border (n = w - x in 1..7)
+    // W'[q] = W[2n + 6 - q] for q >= n + 4: c' = perm(c, l, selc), r' = perm(r, c, selr) for n >= 5 and perm(c, l, selr) below; at x = 0, l' = (-, c3, c2, c1).
+    const int n = w - x;
+    const uint32_t selc = n == 1 ? 0x01020304u : n == 2 ? 0x03040504u : n == 3 ? 0x05060504u : 0x07060504u;
+    const uint32_t selr = n == 2 ? 0x0c0c0c02u : n == 3 ? 0x0c0c0304u : n == 4 ? 0x0c040506u : n == 5 ? 0x0c020304u : n == 6 ? 0x0c040504u : 0x07060504u;
+    const bool r_low = n >= 1 && n <= 4, left = x == 0;
+
+    auto load_row = [&](int y) -> uint32_t {   // y in [-3, h + 13] and h >= 45 (plp_orb refuses smaller levels): one reflection at most
+        const int yy = y < 0 ? -y : y >= h ? 2 * (h - 1) - y : y;
+        return *reinterpret_cast<const uint32_t*>(src + (uint32_t)(yy * sp + xl));
+    };
+    // the four horizontal sums of one source row
+    auto hsum = [&](uint32_t c, uint32_t (&a)[4]) {
+        uint32_t l = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x138, 0xf, 0xf, false);   // wave_shr:1 -- lane i - 1's dword
+        uint32_t r = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)c, 0x130, 0xf, 0xf, false);   // wave_shl:1 -- lane i + 1's dword
+        if (EDGE) {
+            const uint32_t r2 = __builtin_amdgcn_perm(r_low ? c : r, r_low ? l : c, selr);
+            const uint32_t c2 = __builtin_amdgcn_perm(c, l, selc);
+            l = left ? __builtin_amdgcn_perm(c, c, 0x0102030cu) : l;
+            c = c2; r = r2;
+        }
+        const uint32_t d[3] = {l, c, r};
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            const int s = 1 + o, q0 = s >> 2, e = s & 3;
+            uint32_t acc = 0;
+#pragma unroll
+            for (int m = 0; m < (e + 7 + 3) / 4; ++m) acc = __builtin_amdgcn_udot4(d[q0 + m], tp[e][m], acc, false);
+            a[o] = acc;
+        }
+    };
+    auto pair = [&](uint32_t ca, uint32_t cb, uint32_t (&p)[4]) {   // (row a | row b << 16) per column; a sum is at most 255 * 256
+        uint32_t ha[4], hb[4];
+        hsum(ca, ha);
+        hsum(cb, hb);
+#pragma unroll
+        for (int o = 0; o < 4; ++o) p[o] = ha[o] | (hb[o] << 16);
+    };
+
+    // P[j] = pair of source rows (r - 3 + 2 j, r - 2 + 2 j) for the output rows r, r + 1 of a step; Q = the raw rows of the next two steps
+    uint32_t P[4][4], Q[4];
+    {
+        uint32_t c[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) c[i] = load_row(y0 - 3 + i);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Q[i] = load_row(y0 + 3 + i);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) pair(c[2 * j], c[2 * j + 1], P[j]);
+    }
+    // four steps per trip: the rotation of P (period 4) and Q (period 2) is register renaming, not moves.  A trip runs whole (rows past y1 are computed and
+    // not stored, loads of rows past y1 are reflected back into the level): branches or conditional loads in it would make the renaming copies again.
+    for (int r0 = y0; r0 < y1; r0 += 8) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int r = r0 + 2 * s;
+            uint32_t* q = &Q[2 * (s & 1)];
+            const uint32_t ca = q[0], cb = q[1];
+            q[0] = load_row(r + 7); q[1] = load_row(r + 8);
+            pair(ca, cb, P[3]);
+            uint32_t ev[4], od[4];
+#pragma unroll
+            for (int o = 0; o < 4; ++o) {
+                uint32_t a = 32768u, b = 32768u;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { a = b7_dot2(P[j][o], te[j], a); b = b7_dot2(P[j][o], to[j], b); }
+                ev[o] = a; od[o] = b;
+            }
+            // byte 2 of each sum (sum <= 255 * 65536 + 32768): v_perm_b32 selects bytes of {src0, src1}, src1 = bytes 0-3
+            const uint32_t oe = __builtin_amdgcn_perm(ev[1], ev[0], 0x0c0c0602u) | __builtin_amdgcn_perm(ev[3], ev[2], 0x06020c0cu);
+            const uint32_t oo = __builtin_amdgcn_perm(od[1], od[0], 0x0c0c0602u) | __builtin_amdgcn_perm(od[3], od[2], 0x06020c0cu);
+            // rows are padded to a 64-byte pitch: the dword stays in the row
+            if (out_lane && r < y1) *reinterpret_cast<uint32_t*>(dst + (uint32_t)(__mul24(r, dp) + x)) = oe;
+            if (out_lane && r + 1 < y1) *reinterpret_cast<uint32_t*>(dst + (uint32_t)(__mul24(r + 1, dp) + x)) = oo;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+#pragma unroll
+                for (int o = 0; o < 4; ++o) P[j][o] = P[j + 1][o];
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_blur7(OrbPlanes pl, uint8_t* __restrict__ blur_base, size_t blur_frame_stride,
-                                               const LevelDev* __restrict__ lv, int n_levels, BlurTaps taps, uint32_t gx_magic) {
-    __shared__ BlurTileLds<3> S;
-    unsigned ut, uf;
-    xcd_frame_major(ut, uf, gx_magic);   // all tiles of a frame share halo rows: one L2 per frame
-    int t = (int)ut;
+                                               const LevelDev* __restrict__ lv, int n_levels, BlurTaps taps, uint32_t gx_magic, int n_strips) {
+    unsigned ub, uf;
+    xcd_frame_major(ub, uf, gx_magic);   // all strips of a frame share halo rows: one L2 per frame
+    int t = (int)ub * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (t >= n_strips) return;   // the whole wave (every lane must stay for the DPP shifts)
     const int frame = (int)uf;
     int level = 0;
     while (level + 1 < n_levels && t >= lv[level].blur_tiles) { t -= lv[level].blur_tiles; ++level; }
     const LevelDev L = lv[level];
-    const int tiles_x = (L.w + kBlurTW - 1) / kBlurTW;
-    const int trow = (int)plp_div((unsigned)t, (unsigned)tiles_x, L.blur_tiles_x_magic);
-    blur_tile<3>(S, pl.level_ptr(frame, level, L), pl.level_pitch(level, L), blur_base + (size_t)frame * blur_frame_stride + L.off, L.pitch,
-                 L.w, L.h, (t - trow * tiles_x) * kBlurTW, trow * kBlurTH, taps.k);
+    const int w = L.w, h = L.h;
+    const int strips_x = (w + kBlur7W - 1) / kBlur7W;
+    const int srow = (int)plp_div((unsigned)t, (unsigned)strips_x, L.blur_tiles_x_magic);
+    const int x0 = (t - srow * strips_x) * kBlur7W, x = x0 + 4 * ((int)(threadIdx.x & 63) - 1);
+    const int y0 = srow * kBlur7H, y1 = min(y0 + kBlur7H, h);
+    const uint8_t* src = pl.level_ptr(frame, level, L);
+    uint8_t* dst = blur_base + (size_t)frame * blur_frame_stride + L.off;
+    if (x0 == 0 || x0 + kBlur7W + 8 > w)   // (wave-uniform) the strip touches an image border
+        blur7_strip<true>(src, pl.level_pitch(level, L), dst, L.pitch, w, h, x, y0, y1, taps.k);
+    else
+        blur7_strip<false>(src, pl.level_pitch(level, L), dst, L.pitch, w, h, x, y0, y1, taps.k);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -662,7 +790,9 @@ void launch_fast(hipStream_t st, const OrbPlanes& pl, const CellDesc* d_cells, i
 void launch_blur(hipStream_t st, const OrbPlanes& pl, uint8_t* blur, size_t blur_frame_stride, const LevelDev* d_lv,
                  int n_levels, int total_tiles, int B, const BlurTaps& taps, const LevelDev* h_lv) {
     (void)h_lv;
-    hipLaunchKernelGGL(k_blur7, dim3(total_tiles, B), dim3(256), 0, st, pl, blur, blur_frame_stride, d_lv, n_levels, taps, plp_div_magic((uint32_t)total_tiles, (uint64_t)total_tiles * B));
+    const int blocks = (total_tiles + 3) / 4;   // four strips per workgroup, one per wave
+    hipLaunchKernelGGL(k_blur7, dim3(blocks, B), dim3(256), 0, st, pl, blur, blur_frame_stride, d_lv, n_levels, taps,
+                       plp_div_magic((uint32_t)blocks, (uint64_t)blocks * B), total_tiles);
 }
 
 void launch_orient_rbrief(hipStream_t st, const OrbPlanes& pl, const uint8_t* blur, size_t blur_frame_stride,
