@@ -441,7 +441,8 @@ plp_status plp_match_area_host(plp_matcher* ctx, const plp_keypoint* kps_1, cons
 
 /* cv::line_descriptor::BinaryDescriptorMatcher::match(query, train, matches) — exact 1-NN over LBD descriptors by
  * multi-index hashing (src/PLPSLAM/feature/line_descriptor/binary_descriptor_matcher.cpp:197-255, 597-818), used for the
- * stereo line association (data/frame.cc:496-533) and two-key-frame line triangulation (mapping_module.cc:481-531).
+ * stereo line association (data/frame.cc:496-533; its filter is plp_stereo_keylines_* below) and two-key-frame line triangulation
+ * (mapping_module.cc:481-531).
  * train_idx[q] = DMatch.trainIdx (among equally near train lines: the one MIH discovers first), dist[q] = DMatch.distance.
  * Nothing within Hamming distance 128 -> (-1, 256) (the reference reads uninitialised memory there). */
 plp_status plp_lbd_match_1nn_host(plp_matcher* ctx, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t* train_idx, int32_t* dist);
@@ -628,6 +629,75 @@ plp_status plp_project_last_frame_device(plp_matcher* ctx, const plp_last_frame_
 plp_status plp_project_last_frame_host(plp_matcher* ctx, const plp_last_frame_args* args);
 plp_status plp_project_last_frame_lines_device(plp_matcher* ctx, const plp_last_frame_args* args, void* hip_stream);
 plp_status plp_project_last_frame_lines_host(plp_matcher* ctx, const plp_last_frame_args* args);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Stereo key-line association: the filter every stereo data::frame constructor with lines runs on BinaryDescriptorMatcher::match's
+ * left -> right result (data/frame.cc:389-427, again at :494-533), for B frames at once.  A match of left key line j is kept when
+ *   DMatch.distance < 30 (float; the 1-NN's (-1, 256) is never kept, nor is a train index outside [0, count_right))
+ *   sqrt(serr.dot(serr)) < 200 and sqrt(eerr.dot(eerr)) < 200, serr / eerr = getStartPoint() / getEndPoint() differences (startPointX/Y,
+ *                    endPointX/Y, not the in-octave fields) as cv::Point2f, the dot x*x + y*y in float
+ *   abs((abs(a1) - abs(a2))) * 180 / 3.14 < 5: the float abs, the float product divided in f64 by 3.14 and rounded to float (DESIGN.md
+ *                    section 5, D7: the overload GCC's libstdc++ gives the unqualified call)
+ * Slot j of problem b is left key line j, b * cap_left + j; slots j >= counts_left[b] are neither read nor written.  Outputs for every
+ * slot j < counts_left[b], in the layout plp_post_extract_* and the last-frame line matcher's kl_x_right use:
+ *   out_good_match[j]    the right index of a kept match, else -1: _good_matches_stereo as a dense array
+ *   out_kl_depths[j][2]  (1.0, 1.0) for a kept match, else (-1, -1): _depths_cooresponding_to_keylines
+ *   out_kl_x_right[j][2] the same values: _stereo_x_right_cooresponding_to_keylines
+ * An empty right side (cap_right == 0 or counts_right[b] == 0) is valid: every slot -1 / (-1, -1), as the reference leaves them. */
+typedef struct plp_stereo_keylines_args {
+    int32_t B, cap_left, cap_right;     /* B > 0 frames, cap_left >= 0 left and cap_right >= 0 right key-line slots */
+    const plp_keyline* keylines_left;   /* B x cap_left: _keylsd */
+    const int32_t* counts_left;         /* B: _num_keylines, or NULL = cap_left everywhere */
+    const plp_keyline* keylines_right;  /* B x cap_right: _keylsd_right */
+    const int32_t* counts_right;        /* B, or NULL = cap_right everywhere */
+    const int32_t* train_idx;           /* B x cap_left: train_idx of plp_lbd_match_1nn_* (left = query, right = train) */
+    const int32_t* dist;                /* B x cap_left: its dist */
+    int32_t* out_good_match;            /* B x cap_left */
+    float* out_kl_depths;               /* B x cap_left x 2 */
+    float* out_kl_x_right;              /* B x cap_left x 2 */
+} plp_stereo_keylines_args;
+/* Invalid (PLP_ERR_INVALID_ARG, checked before anything is written): NULL ctx / args; B <= 0, cap_left < 0, cap_right < 0; NULL out_good_match,
+ * out_kl_depths, out_kl_x_right; NULL keylines_left when cap_left > 0; NULL keylines_right, train_idx, dist when cap_left > 0 and
+ * cap_right > 0 (with cap_right == 0 they are not read).  cap_left == 0: PLP_OK, nothing written.
+ * _device: every array a DEVICE pointer, asynchronous on hip_stream.  _host: HOST pointers, staged to HBM (the outputs too, so that every
+ * slot the kernel does not write keeps the caller's value), the same kernel, synchronous. */
+plp_status plp_stereo_keylines_device(plp_matcher* ctx, const plp_stereo_keylines_args* args, void* hip_stream);
+plp_status plp_stereo_keylines_host(plp_matcher* ctx, const plp_stereo_keylines_args* args);
+
+/* 3-D key lines: frame::triangulate_stereo_for_line(idx) (data/frame.cc:953-1123; keyframe::triangulate_stereo_for_line, keyframe.cc:647-820,
+ * is the same code with the key frame's pose) for every key line of B frames, as the initialiser (module/initializer.cc:472-530) and the key
+ * frame line triangulator (module/two_view_triangulator_line.cc:202-240) call it:
+ *   RGB-D   (setup_type 2): when 0 < depth_sp and 0 < depth_ep (kl_depths, e.g. plp_post_extract_*'s), both end points unprojected,
+ *           (x - cx) * depth * fx_inv in f64 rounded to float, fx_inv = 1.0 / fx (perspective.cc:42), then rot_wc * p + cam_center
+ *   stereo  (setup_type 1): when good_match[j] >= 0 (plp_stereo_keylines_*'s), the planes of the left line through P1 = K [I | 0] and of its
+ *           right partner through P2 = K [I | (-focal_x_baseline, 0, 0)] intersected into a Pluecker line, its end points trimmed against
+ *           the left key line, then rot_wc * p + cam_center; kept when both WORLD z > 0 (as the reference checks, :1109)
+ * Numeric contract: DESIGN.md section 5, D7 (f64 in the reference's order, every Eigen expression written out left to right; a non-finite
+ * intermediate or end point gives the zero vector).  Slot j of problem b is key line j, b * cap + j; slots j >= counts[b] are neither read
+ * nor written.  Outputs per slot j < counts[b]:
+ *   out_pos_w[j][6]  (sp, ep) in world coordinates, or Vec6_t::Zero() where the reference returns it
+ *   out_valid[j]     1 where the line was returned, 0 where the zero vector was */
+typedef struct plp_keylines_3d_args {
+    plp_camera_model camera;            /* PLP_CAMERA_PERSPECTIVE (frame.cc:957 static_casts to camera::perspective); fx, fy, cx, cy,
+                                           focal_x_baseline are read */
+    int32_t setup_type;                 /* camera::setup_type_t: 1 stereo, 2 RGB-D (monocular is the reference's assert) */
+    int32_t B, cap, cap_right;          /* B > 0 frames of cap >= 0 key-line slots; stereo: cap_right >= 0 right key-line slots */
+    const int32_t* counts;              /* B: _num_keylines, or NULL = cap everywhere */
+    const double* pose;                 /* B x 15: the plp_observe_args.pose row; rot_wc_ = its rot_cw transposed, cam_center_ = entries 12-14 */
+    const plp_keyline* keylines;        /* B x cap: _keylsd */
+    const float* kl_depths;             /* RGB-D: B x cap x 2, _depths_cooresponding_to_keylines; ignored for stereo */
+    const int32_t* good_match;          /* stereo: B x cap, plp_stereo_keylines_*'s out_good_match; ignored for RGB-D */
+    const plp_keyline* keylines_right;  /* stereo: B x cap_right, _keylsd_right */
+    const int32_t* counts_right;        /* stereo: B, or NULL = cap_right everywhere (a good_match outside [0, count) gives zero) */
+    double* out_pos_w;                  /* B x cap x 6 */
+    uint8_t* out_valid;                 /* B x cap, or NULL */
+} plp_keylines_3d_args;
+/* Invalid (checked before anything is written): NULL ctx / args; the camera as for plp_post_extract_model_* with key lines (equirectangular:
+ * PLP_ERR_UNSUPPORTED); fisheye: PLP_ERR_UNSUPPORTED; setup_type not 1 or 2, B <= 0, cap < 0, cap_right < 0; NULL pose, keylines, out_pos_w;
+ * RGB-D with NULL kl_depths; stereo with NULL good_match, or NULL keylines_right when cap_right > 0 (PLP_ERR_INVALID_ARG).  cap == 0: PLP_OK,
+ * nothing written.  _device / _host as for plp_stereo_keylines_*. */
+plp_status plp_keylines_3d_device(plp_matcher* ctx, const plp_keylines_3d_args* args, void* hip_stream);
+plp_status plp_keylines_3d_host(plp_matcher* ctx, const plp_keylines_3d_args* args);
 
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the

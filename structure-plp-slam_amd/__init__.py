@@ -118,6 +118,10 @@ _API = [
     ("plp_project_last_frame_host", C.c_int, [_VP, _VP]),
     ("plp_project_last_frame_lines_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_project_last_frame_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_stereo_keylines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_stereo_keylines_host", C.c_int, [_VP, _VP]),
+    ("plp_keylines_3d_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_keylines_3d_host", C.c_int, [_VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -594,6 +598,29 @@ def _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, pt
     return a
 
 
+class stereo_keylines_args_c(C.Structure):
+    """plp_stereo_keylines_args"""
+    _fields_ = [("B", C.c_int32), ("cap_left", C.c_int32), ("cap_right", C.c_int32),
+                ("keylines_left", _VP), ("counts_left", _VP), ("keylines_right", _VP), ("counts_right", _VP), ("train_idx", _VP), ("dist", _VP),
+                ("out_good_match", _VP), ("out_kl_depths", _VP), ("out_kl_x_right", _VP)]
+
+
+class keylines_3d_args_c(C.Structure):
+    """plp_keylines_3d_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("B", C.c_int32), ("cap", C.c_int32), ("cap_right", C.c_int32),
+                ("counts", _VP), ("pose", _VP), ("keylines", _VP), ("kl_depths", _VP), ("good_match", _VP), ("keylines_right", _VP),
+                ("counts_right", _VP), ("out_pos_w", _VP), ("out_valid", _VP)]
+
+
+def _struct(cls, fields, ptrs):
+    a = cls()
+    for k, v in fields.items():
+        setattr(a, k, v)
+    for k, v in ptrs.items():
+        setattr(a, k, v)
+    return a
+
+
 class match_grid_c(C.Structure):
     _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("inv_cell_width", C.c_double), ("inv_cell_height", C.c_double),
                 ("cols", C.c_int32), ("rows", C.c_int32)]
@@ -923,6 +950,87 @@ class matcher:
             pose_curr=pose_curr, pose_last=pose_last, pos_w=pos_w, keylines=keylines, skip=skip, counts=counts, out_reproj=out_reproj_sp,
             out_reproj2=out_reproj_ep, out_x_right=out_x_right_sp, out_x_right2=out_x_right_ep, out_level=out_level, out_valid=out_valid,
             out_direction=out_direction, out_num_valid=out_num_valid), setup_type, true_baseline, img_bounds, stream)
+
+    # ---- stereo key lines: the association of the stereo constructors (frame.cc:389-427) and triangulate_stereo_for_line (frame.cc:953-1123)
+    def stereo_keylines(self, keylines_left, keylines_right, train_idx, dist, counts_left=None, counts_right=None, out=None):
+        """The stereo constructor's filter of the 1-NN left -> right (plp_stereo_keylines_host) for one frame ((n,) key lines, (n,) train_idx /
+        dist as lbd_match_1nn returns them) or B frames ((B, cap_left) / (B, cap_right)).  Returns dict(good_match, kl_depths, kl_x_right);
+        slots at or above counts_left keep 0, or the value of out[name] when the caller passes its own arrays."""
+        kl = np.ascontiguousarray(keylines_left, KL_DTYPE)
+        single = kl.ndim == 1
+        kl = kl.reshape(1, -1) if single else kl
+        B, L = kl.shape
+        kr = np.ascontiguousarray(keylines_right, KL_DTYPE).reshape(B, -1)
+        R = kr.shape[1]
+        ti = np.ascontiguousarray(train_idx, np.int32).reshape(B, L)
+        di = np.ascontiguousarray(dist, np.int32).reshape(B, L)
+        cl = None if counts_left is None else np.ascontiguousarray(counts_left, np.int32).reshape(B)
+        cr = None if counts_right is None else np.ascontiguousarray(counts_right, np.int32).reshape(B)
+        o = {}
+        for k, shape, dt in (("good_match", (B, L), np.int32), ("kl_depths", (B, L, 2), np.float32), ("kl_x_right", (B, L, 2), np.float32)):
+            v = None if out is None else out.get(k)
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            o[k] = v if v is not None else np.zeros(shape, dt)
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(stereo_keylines_args_c, dict(B=B, cap_left=L, cap_right=R), dict(
+            keylines_left=P(kl), counts_left=P(cl), keylines_right=P(kr), counts_right=P(cr), train_idx=P(ti), dist=P(di),
+            out_good_match=o["good_match"].ctypes.data, out_kl_depths=o["kl_depths"].ctypes.data, out_kl_x_right=o["kl_x_right"].ctypes.data))
+        _check(lib().plp_stereo_keylines_host(self._h, C.byref(a)))
+        return {k: v[0] for k, v in o.items()} if single else o
+
+    def stereo_keylines_device(self, B, cap_left, cap_right, keylines_left, keylines_right, train_idx, dist, out_good_match, out_kl_depths,
+                               out_kl_x_right, counts_left=None, counts_right=None, stream=None):
+        """plp_stereo_keylines_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(stereo_keylines_args_c, dict(B=int(B), cap_left=int(cap_left), cap_right=int(cap_right)), dict(
+            keylines_left=D(keylines_left), counts_left=D(counts_left), keylines_right=D(keylines_right), counts_right=D(counts_right),
+            train_idx=D(train_idx), dist=D(dist), out_good_match=D(out_good_match), out_kl_depths=D(out_kl_depths), out_kl_x_right=D(out_kl_x_right)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_stereo_keylines_device(self._h, C.byref(a), st))
+
+    def keylines_3d(self, camera, setup_type, pose, keylines, kl_depths=None, good_match=None, keylines_right=None, counts=None, counts_right=None,
+                    out=None):
+        """triangulate_stereo_for_line for every key line (plp_keylines_3d_host) of one frame ((15,) pose, (n,) key lines) or B frames ((B, 15),
+        (B, cap)): RGB-D (SETUP_RGBD) from kl_depths (n, 2), stereo (SETUP_STEREO) from good_match (n,) and the right key lines.  camera: a
+        perspective camera_model / camera_model_c.  Returns dict(pos_w (n, 6) f64, valid (n,) u8); slots at or above counts keep 0 (or out[name])."""
+        pose = np.ascontiguousarray(pose, np.float64)
+        single = pose.ndim == 1
+        pose = pose.reshape(-1, 15)
+        B = len(pose)
+        kl = np.ascontiguousarray(keylines, KL_DTYPE).reshape(B, -1)
+        M = kl.shape[1]
+        kd = None if kl_depths is None else np.ascontiguousarray(kl_depths, np.float32).reshape(B, M, 2)
+        gm = None if good_match is None else np.ascontiguousarray(good_match, np.int32).reshape(B, M)
+        kr = None if keylines_right is None else np.ascontiguousarray(keylines_right, KL_DTYPE).reshape(B, -1)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
+        cr = None if counts_right is None else np.ascontiguousarray(counts_right, np.int32).reshape(B)
+        o = {}
+        for k, shape, dt in (("pos_w", (B, M, 6), np.float64), ("valid", (B, M), np.uint8)):
+            v = None if out is None else out.get(k)
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            o[k] = v if v is not None else np.zeros(shape, dt)
+        P = lambda v: None if v is None else v.ctypes.data
+        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=B, cap=M, cap_right=0 if kr is None else kr.shape[1]), dict(
+            counts=P(cn), pose=P(pose), keylines=P(kl), kl_depths=P(kd), good_match=P(gm), keylines_right=None if kr is None or kr.size == 0 else P(kr),
+            counts_right=P(cr), out_pos_w=o["pos_w"].ctypes.data, out_valid=o["valid"].ctypes.data))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        _check(lib().plp_keylines_3d_host(self._h, C.byref(a)))
+        return {k: v[0] for k, v in o.items()} if single else o
+
+    def keylines_3d_device(self, camera, setup_type, B, cap, pose, keylines, out_pos_w, kl_depths=None, good_match=None, keylines_right=None,
+                           cap_right=0, counts=None, counts_right=None, out_valid=None, stream=None):
+        """plp_keylines_3d_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=int(B), cap=int(cap), cap_right=int(cap_right)), dict(
+            counts=D(counts), pose=D(pose), keylines=D(keylines), kl_depths=D(kl_depths), good_match=D(good_match), keylines_right=D(keylines_right),
+            counts_right=D(counts_right), out_pos_w=D(out_pos_w), out_valid=D(out_valid)))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_keylines_3d_device(self._h, C.byref(a), st))
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""

@@ -5,7 +5,9 @@ the bench line, is replay_step.tracker_step).
   stereo_step      configs[2]  EuRoC stereo (run_euroc_slam_with_line): the stereo frame constructor, data/frame.cc:267-360:
                                ORB left || ORB right || LSD+LBD left || LSD+LBD right (frame.cc:277-281, 351-358),
                                match::stereo::compute (match/stereo.cc:45-150) -> stereo_x_right / depths,
-                               BinaryDescriptorMatcher::match left -> right on the LBD rows (frame.cc:505)
+                               BinaryDescriptorMatcher::match left -> right on the LBD rows (frame.cc:505), and with associate_lines=True
+                               the constructor's filter of that match (frame.cc:494-533, plp_stereo_keylines_device) -> good_match,
+                               kl_depths, kl_x_right
   mono_step        configs[3]  KITTI mono (run_kitti_slam_with_line): ORB || LSD+LBD, match_current_and_last_frames against frame b-1
                                (match/projection.cc:214-358, margin 20, orientation check, as frame_tracker.cc:66-87)
   rgbd_plane_step  configs[4]  ICL-NUIM RGB-D + plane masks (run_slam_planeSeg): ORB || LSD+LBD, undistort / bearings / stereo from depth
@@ -80,9 +82,14 @@ class _base:
 
 
 class stereo_step(_base):
-    def __init__(self, plp, B, K=1000, device_index=0, fxb=EUROC_FXB, tb=EUROC_TB):
+    def __init__(self, plp, B, K=1000, device_index=0, fxb=EUROC_FXB, tb=EUROC_TB, associate_lines=False):
         super().__init__(plp, B, K, device_index)
         t = self.torch
+        self.associate_lines = associate_lines
+        if associate_lines:   # _good_matches_stereo (dense), _depths_cooresponding_to_keylines, _stereo_x_right_cooresponding_to_keylines
+            self.good_match = t.empty((B, self.LCAP), dtype=t.int32, device=self.dev)
+            self.kl_depths = t.empty((B, self.LCAP, 2), dtype=t.float32, device=self.dev)
+            self.kl_x_right = t.empty((B, self.LCAP, 2), dtype=t.float32, device=self.dev)
         self.exl, self.exr = plp.orb_extractor(K, device=device_index), plp.orb_extractor(K, device=device_index)
         self.ltl, self.ltr = plp.LineFeatureTracker(device=device_index), plp.LineFeatureTracker(device=device_index)
         self.mt = plp.matcher(device=device_index)
@@ -107,6 +114,9 @@ class stereo_step(_base):
                                                     self.xr.data_ptr(), self.dep.data_ptr(), C.c_void_p(sA.cuda_stream)))
         plp._check(L.plp_lbd_match_1nn_device(self.mt._h, self.LL[1].data_ptr(), self.LL[3].data_ptr(), self.LCAP, self.LR[1].data_ptr(), self.LR[3].data_ptr(), self.LCAP,
                                               self.B, self.tidx.data_ptr(), self.tdist.data_ptr(), C.c_void_p(sC.cuda_stream)))
+        if self.associate_lines:
+            self.mt.stereo_keylines_device(self.B, self.LCAP, self.LCAP, self.LL[0], self.LR[0], self.tidx, self.tdist, self.good_match, self.kl_depths,
+                                           self.kl_x_right, counts_left=self.LL[3], counts_right=self.LR[3], stream=sC.cuda_stream)
         cur.wait_stream(sA); cur.wait_stream(sC)
 
     def status(self):

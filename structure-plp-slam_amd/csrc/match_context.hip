@@ -698,6 +698,146 @@ plp_status plp_project_last_frame_host(plp_matcher* c, const plp_last_frame_args
 plp_status plp_project_last_frame_lines_device(plp_matcher* c, const plp_last_frame_args* a, void* hip_stream) { return last_frame_device(c, a, true, hip_stream); }
 plp_status plp_project_last_frame_lines_host(plp_matcher* c, const plp_last_frame_args* a) { return last_frame_host(c, a, true); }
 
+// ---- stereo key lines (include/plp_front.h: plp_stereo_keylines_*, plp_keylines_3d_*; kernels in stereo_line_kernels.hip)
+namespace {
+plp_status stereo_keylines_check(plp_matcher* c, const plp_stereo_keylines_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (a->B <= 0 || a->cap_left < 0 || a->cap_right < 0) return set_error(PLP_ERR_INVALID_ARG, "B must be positive, cap_left and cap_right non-negative");
+    if (!a->out_good_match || !a->out_kl_depths || !a->out_kl_x_right)
+        return set_error(PLP_ERR_INVALID_ARG, "out_good_match, out_kl_depths, out_kl_x_right are required");
+    if (a->cap_left > 0 && !a->keylines_left) return set_error(PLP_ERR_INVALID_ARG, "keylines_left is required");
+    if (a->cap_left > 0 && a->cap_right > 0 && (!a->keylines_right || !a->train_idx || !a->dist))
+        return set_error(PLP_ERR_INVALID_ARG, "keylines_right, train_idx, dist are required when both sides have slots");
+    return PLP_OK;
+}
+
+StereoKeylineArgs stereo_keylines_args(const plp_stereo_keylines_args* a) {
+    StereoKeylineArgs A{};
+    A.cap_l = a->cap_left; A.cap_r = a->cap_right;
+    A.kl_l = a->keylines_left; A.counts_l = a->counts_left; A.kl_r = a->keylines_right; A.counts_r = a->counts_right;
+    A.train_idx = a->train_idx; A.dist = a->dist;
+    A.good = a->out_good_match; A.depths = a->out_kl_depths; A.x_right = a->out_kl_x_right;
+    if (A.cap_r == 0) { A.kl_r = nullptr; A.counts_r = nullptr; A.train_idx = nullptr; A.dist = nullptr; }   // not read: every slot -1
+    return A;
+}
+
+plp_status keylines_3d_check(plp_matcher* c, const plp_keylines_3d_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, true)) return s;
+    if (a->camera.model != PLP_CAMERA_PERSPECTIVE) return set_error(PLP_ERR_UNSUPPORTED, "3-D key lines need the perspective camera (frame.cc:957)");
+    if (a->setup_type != 1 && a->setup_type != 2) return set_error(PLP_ERR_INVALID_ARG, "setup_type must be 1 (stereo) or 2 (RGB-D)");
+    if (a->B <= 0 || a->cap < 0 || a->cap_right < 0) return set_error(PLP_ERR_INVALID_ARG, "B must be positive, cap and cap_right non-negative");
+    if (!a->pose || !a->keylines || !a->out_pos_w) return set_error(PLP_ERR_INVALID_ARG, "pose, keylines, out_pos_w are required");
+    if (a->setup_type == 2 && !a->kl_depths) return set_error(PLP_ERR_INVALID_ARG, "kl_depths is required for RGB-D");
+    if (a->setup_type == 1 && (!a->good_match || (a->cap_right > 0 && !a->keylines_right)))
+        return set_error(PLP_ERR_INVALID_ARG, "good_match (and keylines_right when cap_right > 0) are required for stereo");
+    return PLP_OK;
+}
+
+Keylines3dArgs keylines_3d_args(const plp_keylines_3d_args* a) {
+    Keylines3dArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.fx_inv = 1.0 / cm.fx; A.fy_inv = 1.0 / cm.fy;   // perspective.cc:42
+    A.setup_type = a->setup_type; A.cap = a->cap; A.cap_r = a->cap_right;
+    A.counts = a->counts; A.pose = a->pose; A.kl = a->keylines;
+    const bool rgbd = a->setup_type == 2;
+    A.kl_depths = rgbd ? a->kl_depths : nullptr;
+    A.good_match = rgbd ? nullptr : a->good_match;
+    A.kl_r = rgbd || a->cap_right == 0 ? nullptr : a->keylines_right;
+    A.counts_r = rgbd || a->cap_right == 0 ? nullptr : a->counts_right;
+    A.pos_w = a->out_pos_w; A.valid = a->out_valid;
+    return A;
+}
+
+// host pointers through the context's slab: inputs up, the outputs up as the caller holds them (slots past the counts keep their values), the
+// device path's kernel, the outputs back
+struct StagePart { const void* src; void* dst; size_t bytes; size_t off; };
+plp_status stage_run(plp_matcher* c, StagePart* parts, int n, uint8_t** base_out) {
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    size_t tot = 0;
+    for (int k = 0; k < n; ++k)
+        if ((parts[k].src || parts[k].dst) && parts[k].bytes) { parts[k].off = tot; tot += al(parts[k].bytes); }
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(c->stage.reserve(tot ? tot : 256));
+    uint8_t* base = (uint8_t*)c->stage.p;
+    for (int k = 0; k < n; ++k) {
+        const StagePart& p = parts[k];
+        if ((p.src || p.dst) && p.bytes) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    *base_out = base;
+    return PLP_OK;
+}
+plp_status stage_back(plp_matcher* c, const StagePart* parts, int n, uint8_t* base) {
+    for (int k = 0; k < n; ++k)
+        if (parts[k].dst && parts[k].bytes) PLP_HIP(hipMemcpyAsync(parts[k].dst, base + parts[k].off, parts[k].bytes, hipMemcpyDeviceToHost, c->stream));
+    PLP_HIP(hipStreamSynchronize(c->stream));
+    return PLP_OK;
+}
+}  // namespace
+
+plp_status plp_stereo_keylines_device(plp_matcher* c, const plp_stereo_keylines_args* a, void* hip_stream) {
+    if (plp_status s = stereo_keylines_check(c, a)) return s;
+    if (a->cap_left == 0) return PLP_OK;   // no left key line: nothing to write
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_stereo_keylines((hipStream_t)hip_stream, stereo_keylines_args(a), a->B));
+    return PLP_OK;
+}
+
+plp_status plp_stereo_keylines_host(plp_matcher* c, const plp_stereo_keylines_args* a) {
+    if (plp_status s = stereo_keylines_check(c, a)) return s;
+    if (a->cap_left == 0) return PLP_OK;
+    const size_t B = (size_t)a->B, L = (size_t)a->cap_left, R = (size_t)a->cap_right;
+    const StereoKeylineArgs H = stereo_keylines_args(a);
+    StagePart parts[] = {
+        {H.kl_l, nullptr, B * L * sizeof(plp_keyline), 0}, {H.counts_l, nullptr, B * 4, 0}, {H.kl_r, nullptr, B * R * sizeof(plp_keyline), 0},
+        {H.counts_r, nullptr, B * 4, 0}, {H.train_idx, nullptr, B * L * 4, 0}, {H.dist, nullptr, B * L * 4, 0},
+        {nullptr, H.good, B * L * 4, 0}, {nullptr, H.depths, B * L * 8, 0}, {nullptr, H.x_right, B * L * 8, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    StereoKeylineArgs A = H;
+    A.kl_l = (const plp_keyline*)dev(0); A.counts_l = (const int32_t*)dev(1); A.kl_r = (const plp_keyline*)dev(2); A.counts_r = (const int32_t*)dev(3);
+    A.train_idx = (const int32_t*)dev(4); A.dist = (const int32_t*)dev(5);
+    A.good = (int32_t*)dev(6); A.depths = (float*)dev(7); A.x_right = (float*)dev(8);
+    PLP_HIP(launch_stereo_keylines(c->stream, A, a->B));
+    return stage_back(c, parts, np, base);
+}
+
+plp_status plp_keylines_3d_device(plp_matcher* c, const plp_keylines_3d_args* a, void* hip_stream) {
+    if (plp_status s = keylines_3d_check(c, a)) return s;
+    if (a->cap == 0) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_keylines_3d((hipStream_t)hip_stream, keylines_3d_args(a), a->B));
+    return PLP_OK;
+}
+
+plp_status plp_keylines_3d_host(plp_matcher* c, const plp_keylines_3d_args* a) {
+    if (plp_status s = keylines_3d_check(c, a)) return s;
+    if (a->cap == 0) return PLP_OK;
+    const size_t B = (size_t)a->B, M = (size_t)a->cap, R = (size_t)a->cap_right;
+    const Keylines3dArgs H = keylines_3d_args(a);
+    StagePart parts[] = {
+        {H.counts, nullptr, B * 4, 0}, {H.pose, nullptr, B * 15 * 8, 0}, {H.kl, nullptr, B * M * sizeof(plp_keyline), 0},
+        {H.kl_depths, nullptr, B * M * 8, 0}, {H.good_match, nullptr, B * M * 4, 0}, {H.kl_r, nullptr, B * R * sizeof(plp_keyline), 0},
+        {H.counts_r, nullptr, B * 4, 0}, {nullptr, H.pos_w, B * M * 48, 0}, {nullptr, H.valid, B * M, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    Keylines3dArgs A = H;
+    A.counts = (const int32_t*)dev(0); A.pose = (const double*)dev(1); A.kl = (const plp_keyline*)dev(2); A.kl_depths = (const float*)dev(3);
+    A.good_match = (const int32_t*)dev(4); A.kl_r = (const plp_keyline*)dev(5); A.counts_r = (const int32_t*)dev(6);
+    A.pos_w = (double*)dev(7); A.valid = (uint8_t*)dev(8);
+    PLP_HIP(launch_keylines_3d(c->stream, A, a->B));
+    return stage_back(c, parts, np, base);
+}
+
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
                                            size_t src_frame_stride, int32_t channels, int32_t color_order, int32_t B, uint8_t* d_gray,
                                            size_t gray_step, size_t gray_frame_stride, void* hip_stream) {

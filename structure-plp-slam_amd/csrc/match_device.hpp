@@ -134,6 +134,25 @@ hipError_t launch_observe_points(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_observe_lines(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_last_frame_points(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_last_frame_lines(hipStream_t st, const ObserveArgs& A, int B);
+// stereo key-line association (plp_stereo_keylines_*, stereo_line_kernels.hip): left / right key lines, the 1-NN result (left = query)
+struct StereoKeylineArgs {
+    int cap_l, cap_r;
+    const plp_keyline* kl_l; const int32_t* counts_l; const plp_keyline* kl_r; const int32_t* counts_r;
+    const int32_t* train_idx; const int32_t* dist;
+    int32_t* good; float* depths; float* x_right;
+};
+// 3-D key lines (plp_keylines_3d_*, stereo_line_kernels.hip): camera::perspective doubles, fx_inv_ / fy_inv_ = 1.0 / fx, 1.0 / fy as the
+// constructor forms them (perspective.cc:42)
+struct Keylines3dArgs {
+    double fx, fy, cx, cy, fxb, fx_inv, fy_inv;
+    int setup_type, cap, cap_r;
+    const int32_t* counts; const double* pose; const plp_keyline* kl; const float* kl_depths;
+    const int32_t* good_match; const plp_keyline* kl_r; const int32_t* counts_r;
+    double* pos_w; uint8_t* valid;
+};
+// both return the first error of their launch
+hipError_t launch_stereo_keylines(hipStream_t st, const StereoKeylineArgs& A, int B);
+hipError_t launch_keylines_3d(hipStream_t st, const Keylines3dArgs& A, int B);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,
                     size_t dst_step, size_t dst_fs);
 void launch_to_depth(hipStream_t st, const void* src, int is_u16, int rows, int cols, size_t src_step, size_t src_fs, float scale, int B, float* dst,

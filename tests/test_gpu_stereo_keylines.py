@@ -1,0 +1,295 @@
+"""GPU parity of the stereo key-line association (plp_stereo_keylines_*) and of the 3-D key lines (plp_keylines_3d_*) against the CPU
+restatement tests/stereo_keylines_ref.py: real extractions and their 1-NN, batched and ragged problems with
+sentinel-filled outputs, host entries against device entries, RGB-D lines from the post-extract step's key-line depths, stereo lines from the
+association, and config_steps.stereo_step(associate_lines=True) frame by frame."""
+import importlib
+
+import numpy as np
+import pytest
+
+import stereo_keylines_ref as SK
+from plp import plp, synth
+
+pytestmark = pytest.mark.gpu
+cs = importlib.import_module("structure-plp-slam_amd.config_steps")
+KL = plp.KL_DTYPE
+EUROC = {"model": "perspective", "cols": 752, "rows": 480, "fx": 435.2, "fy": 435.2, "cx": 367.2, "cy": 248.4, "focal_x_baseline": cs.EUROC_FXB}
+ICL = {"model": "perspective", "cols": 640, "rows": 480, **cs.ICL_CAMERA}
+
+
+def _camera(d):
+    c = plp.camera_model_c()
+    c.model, c.cols, c.rows = plp.CAMERA_PERSPECTIVE, d["cols"], d["rows"]
+    for k in ("fx", "fy", "cx", "cy", "focal_x_baseline"):
+        setattr(c, k, float(d[k]))
+    return c
+
+
+def _dev():
+    import torch
+    return torch, torch.device("cuda", 0)
+
+
+def stereo_pair(seed, rows=480, cols=752):
+    """the scene of tests/test_gpu_stereo_lbdmatch.py: right = left seen with disparity d(y) = 8 + round(4 sin(y/60))"""
+    wide = synth.canvas(seed, rows, cols + 32)
+    left = np.ascontiguousarray(wide[:, 16:16 + cols])
+    right = np.empty_like(left)
+    for y in range(rows):
+        d = 8 + int(round(4 * np.sin(y / 60.0)))
+        right[y] = wide[y, 16 + d:16 + d + cols]
+    return left, right
+
+
+def _gates(kl_l, kl_r, idx, dist):
+    """how many matches each gate rejects first (distance, end points, angle) and how many are kept"""
+    n = [0, 0, 0, 0]
+    for j in range(len(kl_l)):
+        t = int(idx[j])
+        if not (SK.f32(dist[j]) < SK.f32(30)) or t < 0:
+            n[0] += 1
+            continue
+        a, b = kl_l[j], kl_r[t]
+        ds = SK.point_distance(SK.f32(a["startPointX"]) - SK.f32(b["startPointX"]), SK.f32(a["startPointY"]) - SK.f32(b["startPointY"]))
+        de = SK.point_distance(SK.f32(a["endPointX"]) - SK.f32(b["endPointX"]), SK.f32(a["endPointY"]) - SK.f32(b["endPointY"]))
+        if not (ds < 200 and de < 200):
+            n[1] += 1
+        elif not SK.angle_deg(a["angle"], b["angle"]) < 5:
+            n[2] += 1
+        else:
+            n[3] += 1
+    return n
+
+
+def _random_pose(rng):
+    w = rng.normal(size=3) * 0.3
+    th = np.linalg.norm(w)
+    k = w / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    R = np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx
+    c = rng.normal(size=3) + np.array([0.0, 0.0, 3.0])      # camera centres mostly above the world's z = 0
+    return SK.frame_pose(R, -R @ c)
+
+
+def _real_association(seed, perturb):
+    left, right = stereo_pair(seed)
+    lt = plp.LineFeatureTracker()
+    kl_l, lbd_l, _ = lt.extract_LSD_LBD(left)
+    kl_r, lbd_r, _ = lt.extract_LSD_LBD(right)
+    mt = plp.matcher()
+    idx, dist = mt.lbd_match_1nn(lbd_l, lbd_r)
+    kl_r = kl_r.copy()
+    if perturb:   # move every third right line by (150, 150) px (212 px) and turn the next ones by 0.1 rad: each gate has work
+        kl_r["startPointX"][::3] += 150; kl_r["startPointY"][::3] += 150; kl_r["endPointX"][::3] += 150; kl_r["endPointY"][::3] += 150
+        kl_r["angle"][1::3] += np.float32(0.1)
+    return mt, kl_l, kl_r, idx, dist
+
+
+@pytest.mark.parametrize("perturb", [False, True])
+def test_association_on_real_extractions(perturb):
+    n = np.zeros(4, int)
+    for seed in (9, 11, 13, 15):
+        mt, kl_l, kl_r, idx, dist = _real_association(seed, perturb)
+        want = SK.stereo_keylines(kl_l, kl_r, idx, dist)
+        got = mt.stereo_keylines(kl_l, kl_r, idx, dist)
+        assert np.array_equal(got["good_match"], want[0]), seed
+        assert np.array_equal(got["kl_depths"], want[1]) and np.array_equal(got["kl_x_right"], want[2]), seed
+        g = _gates(kl_l, kl_r, idx, dist)
+        assert g[3] == int((want[0] >= 0).sum())
+        n += g
+    assert n[3] >= 30 and n[0] >= 5, f"vacuous: (distance, end points, angle, kept) = {n}"
+    if perturb:
+        assert n[1] >= 5 and n[2] >= 5, f"vacuous: (distance, end points, angle, kept) = {n}"
+
+
+def _random_lines(rng, n):
+    kl = np.zeros(n, KL)
+    sx, sy = rng.uniform(0, 752, n), rng.uniform(0, 480, n)
+    ang = rng.uniform(-np.pi, np.pi, n)
+    ln = rng.uniform(20, 200, n)
+    kl["startPointX"], kl["startPointY"] = sx, sy
+    kl["endPointX"], kl["endPointY"] = sx + ln * np.cos(ang), sy + ln * np.sin(ang)
+    kl["angle"] = ang
+    kl["octave"] = rng.integers(0, 2, n)
+    return kl
+
+
+def _ragged_problem(rng, B, cap_l, cap_r):
+    """left lines, right lines = left ones moved by up to 250 px and turned by up to 0.15 rad, counts 0 .. cap (some right sides empty),
+    a 1-NN result with distances around 30 and some (-1, 256)"""
+    kl_l = np.stack([_random_lines(rng, cap_l) for _ in range(B)])
+    kl_r = np.zeros((B, cap_r), KL)
+    cl = rng.integers(0, cap_l + 1, B).astype(np.int32); cl[:3] = (0, cap_l, 1)
+    cr = rng.integers(0, cap_r + 1, B).astype(np.int32); cr[3:6] = 0; cr[1] = cap_r
+    idx = np.full((B, cap_l), -7, np.int32); dist = np.full((B, cap_l), -7, np.int32)
+    for b in range(B):
+        src = rng.permutation(cap_l)[:cap_r]                # right slot t is a copy of left line src[t]
+        kl_r[b] = kl_l[b][src]
+        for f in ("startPointX", "endPointX"):
+            kl_r[b][f] += rng.choice([0.0, 5.0, 120.0, 250.0], cap_r).astype(np.float32)
+        kl_r[b]["angle"] += rng.choice([0.0, 0.05, 0.08, 0.15], cap_r).astype(np.float32)
+        if cr[b]:
+            idx[b] = rng.integers(0, cr[b], cap_l)          # a random partner, or the copy of the line itself where it is on the right side
+            own = np.full(cap_l, -1); own[src[:cr[b]]] = np.arange(cr[b])
+            idx[b][own >= 0] = own[own >= 0]
+            dist[b] = rng.integers(20, 40, cap_l)
+            none = rng.random(cap_l) < 0.1
+            idx[b][none], dist[b][none] = -1, 256
+    return kl_l, kl_r, cl, cr, idx, dist
+
+
+def test_association_batched_ragged_and_host_equals_device():
+    torch, dev = _dev()
+    rng = np.random.default_rng(21)
+    B, cap_l, cap_r = 64, 96, 80
+    kl_l, kl_r, cl, cr, idx, dist = _ragged_problem(rng, B, cap_l, cap_r)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_good = torch.full((B, cap_l), -12345, dtype=torch.int32, device=dev)
+    d_dep = torch.full((B, cap_l, 2), 777.0, dtype=torch.float32, device=dev)
+    d_xr = torch.full((B, cap_l, 2), 555.0, dtype=torch.float32, device=dev)
+    mt = plp.matcher()
+    mt.stereo_keylines_device(B, cap_l, cap_r, T(kl_l.view(np.uint8)), T(kl_r.view(np.uint8)), T(idx), T(dist), d_good, d_dep, d_xr,
+                              counts_left=T(cl), counts_right=T(cr))
+    torch.cuda.synchronize()
+    good, dep, xr = d_good.cpu().numpy(), d_dep.cpu().numpy(), d_xr.cpu().numpy()
+    kept = 0
+    for b in range(B):
+        n = cl[b]
+        wg, wd, wx = SK.stereo_keylines(kl_l[b][:n], kl_r[b][:cr[b]], idx[b][:n], dist[b][:n])
+        assert np.array_equal(good[b][:n], wg) and np.array_equal(dep[b][:n], wd) and np.array_equal(xr[b][:n], wx), b
+        assert (good[b][n:] == -12345).all() and (dep[b][n:] == 777.0).all() and (xr[b][n:] == 555.0).all(), b
+        if cr[b] == 0:
+            assert (good[b][:n] == -1).all()
+        kept += int((wg >= 0).sum())
+    assert 200 < kept < int(cl.sum()) - 200, kept
+    # the host entry: the same kernel through HBM; the caller's arrays keep every slot at or above the counts
+    out = dict(good_match=np.full((B, cap_l), -12345, np.int32), kl_depths=np.full((B, cap_l, 2), 777.0, np.float32),
+               kl_x_right=np.full((B, cap_l, 2), 555.0, np.float32))
+    h = mt.stereo_keylines(kl_l, kl_r, idx, dist, counts_left=cl, counts_right=cr, out=out)
+    assert np.array_equal(h["good_match"], good) and np.array_equal(h["kl_depths"], dep) and np.array_equal(h["kl_x_right"], xr)
+    # one frame, empty right side, empty left side
+    g = mt.stereo_keylines(kl_l[0][:10], np.zeros(0, KL), np.full(10, -1, np.int32), np.full(10, 256, np.int32))
+    assert (g["good_match"] == -1).all() and (g["kl_depths"] == -1).all() and (g["kl_x_right"] == -1).all()
+    g = mt.stereo_keylines(np.zeros(0, KL), kl_r[0], np.zeros(0, np.int32), np.zeros(0, np.int32))
+    assert g["good_match"].shape == (0,)
+
+
+def _check_3d(got_pos, got_valid, want_pos, want_valid, what):
+    assert np.array_equal(got_valid, want_valid), what
+    assert np.array_equal(got_pos == 0, want_pos == 0), what
+    neq = int((got_pos.view(np.uint64) != want_pos.view(np.uint64)).any(-1).sum())
+    assert neq == 0, f"{what}: {neq} of {int(want_valid.sum())} kept lines not bit-equal, max |diff| {np.abs(got_pos - want_pos).max()}"
+
+
+def test_keylines_3d_rgbd_from_post_extract():
+    torch, dev = _dev()
+    B = 8
+    fr = synth.replay(4, B, 480, 640)
+    depth, seg = cs.icl_inputs(4, B)
+    depth[:, ::7, ::5] = 0.0                                     # missing depth: compute_stereo_from_depth stores 0, the 3-D step rejects it
+    st = cs.rgbd_plane_step(plp, B, 1000)
+    st.run(torch.from_numpy(fr).to(dev), torch.from_numpy(depth).to(dev), torch.from_numpy(seg).to(dev))
+    torch.cuda.synchronize(); st.status()
+    rng = np.random.default_rng(33)
+    poses = np.stack([_random_pose(rng) for _ in range(B)])
+    cap = st.LCAP
+    d_pos = torch.full((B, cap, 6), 9.5, dtype=torch.float64, device=dev)
+    d_val = torch.full((B, cap), 7, dtype=torch.uint8, device=dev)
+    cam = _camera(ICL)
+    mt = plp.matcher()
+    mt.keylines_3d_device(cam, plp.SETUP_RGBD, B, cap, torch.from_numpy(poses).to(dev), st.LB[0], d_pos, kl_depths=st.kld, counts=st.LB[3],
+                          out_valid=d_val)
+    torch.cuda.synchronize()
+    pos, val = d_pos.cpu().numpy(), d_val.cpu().numpy()
+    kl = st.LB[0].cpu().numpy().view(KL).reshape(B, cap)
+    kld, cnt = st.kld.cpu().numpy(), st.LB[3].cpu().numpy()
+    kept = zero_depth = 0
+    for b in range(B):
+        n = cnt[b]
+        wp, wv = SK.keylines_3d(ICL, SK.RGBD, poses[b], kl[b][:n], kl_depths=kld[b][:n])
+        _check_3d(pos[b][:n], val[b][:n], wp, wv, f"frame {b}")
+        assert (pos[b][n:] == 9.5).all() and (val[b][n:] == 7).all()
+        kept += int(wv.sum())
+        zero_depth += int(((kld[b][:n] == 0).any(1)).sum())
+    assert kept > 100 and zero_depth > 2, (kept, zero_depth)
+    # host entry on the same inputs
+    h = mt.keylines_3d(cam, plp.SETUP_RGBD, poses, kl, kl_depths=kld, counts=cnt, out=dict(pos_w=np.full((B, cap, 6), 9.5), valid=np.full((B, cap), 7, np.uint8)))
+    assert np.array_equal(h["pos_w"].view(np.uint64), pos.view(np.uint64)) and np.array_equal(h["valid"], val)
+
+
+@pytest.mark.parametrize("seed", [9, 13])
+def test_keylines_3d_stereo_from_the_association(seed):
+    torch, dev = _dev()
+    mt, kl_l, kl_r, idx, dist = _real_association(seed, False)
+    good = mt.stereo_keylines(kl_l, kl_r, idx, dist)["good_match"]
+    rng = np.random.default_rng(seed)
+    cam = _camera(EUROC)
+    for _ in range(3):
+        P = _random_pose(rng)
+        want_pos, want_val = SK.keylines_3d(EUROC, SK.STEREO, P, kl_l, good_match=good, kl_right=kl_r)
+        got = mt.keylines_3d(cam, plp.SETUP_STEREO, P, kl_l, good_match=good, keylines_right=kl_r)
+        _check_3d(got["pos_w"], got["valid"], want_pos, want_val, "stereo")
+        assert want_val.sum() >= 10, (int(want_val.sum()), int((good >= 0).sum()))
+    # the device entry, batched and ragged: B = 64 frames of random lines and matches
+    B, cap, cap_r = 64, 96, 80
+    kl_b, kr_b, cl, cr, idx_b, dist_b = _ragged_problem(rng, B, cap, cap_r)
+    good_b = np.stack([np.pad(SK.stereo_keylines(kl_b[b][:cl[b]], kr_b[b][:cr[b]], idx_b[b][:cl[b]], dist_b[b][:cl[b]])[0], (0, cap - cl[b]),
+                              constant_values=-1) for b in range(B)])
+    poses = np.stack([_random_pose(rng) for _ in range(B)])
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_pos = torch.full((B, cap, 6), 9.5, dtype=torch.float64, device=dev)
+    d_val = torch.full((B, cap), 7, dtype=torch.uint8, device=dev)
+    mt.keylines_3d_device(cam, plp.SETUP_STEREO, B, cap, T(poses), T(kl_b.view(np.uint8)), d_pos, good_match=T(good_b),
+                          keylines_right=T(kr_b.view(np.uint8)), cap_right=cap_r, counts=T(cl), counts_right=T(cr), out_valid=d_val)
+    torch.cuda.synchronize()
+    pos, val = d_pos.cpu().numpy(), d_val.cpu().numpy()
+    kept = 0
+    for b in range(B):
+        n = cl[b]
+        wp, wv = SK.keylines_3d(EUROC, SK.STEREO, poses[b], kl_b[b][:n], good_match=good_b[b][:n], kl_right=kr_b[b][:cr[b]])
+        _check_3d(pos[b][:n], val[b][:n], wp, wv, f"frame {b}")
+        assert (pos[b][n:] == 9.5).all() and (val[b][n:] == 7).all()
+        kept += int(wv.sum())
+    assert kept > 30, kept
+
+
+def test_invalid_arguments():
+    mt = plp.matcher()
+    kl = _random_lines(np.random.default_rng(1), 4)
+    P = SK.frame_pose(np.eye(3), np.zeros(3))
+    fish = _camera(EUROC); fish.model = plp.CAMERA_FISHEYE
+    with pytest.raises(plp.PlpError) as e:
+        mt.keylines_3d(fish, plp.SETUP_RGBD, P, kl, kl_depths=np.ones((4, 2), np.float32))
+    assert e.value.status == plp.PLP_ERR_UNSUPPORTED
+    equi = _camera(EUROC); equi.model = plp.CAMERA_EQUIRECTANGULAR
+    with pytest.raises(plp.PlpError) as e:
+        mt.keylines_3d(equi, plp.SETUP_RGBD, P, kl, kl_depths=np.ones((4, 2), np.float32))
+    assert e.value.status == plp.PLP_ERR_UNSUPPORTED
+    for setup, kw in ((plp.SETUP_MONOCULAR, dict(kl_depths=np.ones((4, 2), np.float32))), (plp.SETUP_RGBD, {}), (plp.SETUP_STEREO, {})):
+        out = dict(pos_w=np.full((4, 6), 3.0), valid=np.full(4, 9, np.uint8))
+        with pytest.raises(plp.PlpError) as e:
+            mt.keylines_3d(_camera(EUROC), setup, P, kl, out=out, **kw)
+        assert e.value.status == plp.PLP_ERR_INVALID_ARG
+        assert (out["pos_w"] == 3.0).all() and (out["valid"] == 9).all()   # nothing written
+
+
+def test_stereo_step_associate_lines():
+    torch, dev = _dev()
+    B = 8
+    wide = torch.from_numpy(synth.replay(2, B, 480, 752 + 16)).to(dev)
+    left, right = cs.stereo_pair_from_wide(wide, 752)
+    st = cs.stereo_step(plp, B, 1000, associate_lines=True)
+    st.run(left, right); st.run(left, right)
+    torch.cuda.synchronize(); st.status()
+    LL0 = st.LL[0].cpu().numpy().view(KL).reshape(B, st.LCAP); LR0 = st.LR[0].cpu().numpy().view(KL).reshape(B, st.LCAP)
+    cl, cr = st.LL[3].cpu().numpy(), st.LR[3].cpu().numpy()
+    tidx, tdist = st.tidx.cpu().numpy(), st.tdist.cpu().numpy()
+    good, dep, xr = st.good_match.cpu().numpy(), st.kl_depths.cpu().numpy(), st.kl_x_right.cpu().numpy()
+    kept = 0
+    for b in range(B):
+        n = cl[b]
+        wg, wd, wx = SK.stereo_keylines(LL0[b][:n], LR0[b][:cr[b]], tidx[b][:n], tdist[b][:n])
+        assert np.array_equal(good[b][:n], wg) and np.array_equal(dep[b][:n], wd) and np.array_equal(xr[b][:n], wx), b
+        kept += int((wg >= 0).sum())
+    assert kept > 20 * B, kept
+    assert not hasattr(cs.stereo_step(plp, 2, 1000), "good_match")      # the default step allocates and runs nothing more
