@@ -699,6 +699,105 @@ typedef struct plp_keylines_3d_args {
 plp_status plp_keylines_3d_device(plp_matcher* ctx, const plp_keylines_3d_args* args, void* hip_stream);
 plp_status plp_keylines_3d_host(plp_matcher* ctx, const plp_keylines_3d_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Key-frame pair line triangulation: what follows the 1-NN of plp_lbd_match_1nn_* in mapping_module::triangulate_line_with_two_keyframes
+ * (src/PLPSLAM/mapping_module.cc:482-601) and initializer::triangulate_line_with_two_keyframes (module/initializer.cc:585-667).
+ * Numeric contract: DESIGN.md section 5, D8; the parallel form of the sequential duplicate check: DESIGN.md section 4.
+ *
+ * keyframe::compute_median_depth(abs) (data/keyframe.cc:825-857) for F key frames, one workgroup each:
+ *   pos_c_z = ((r20 x + r21 y) + r22 z) + (double)(float)t_z   (the reference holds trans_cw_z in a float, :840), std::abs in f64 when
+ *   abs_flag, rounded to float (the std::vector<float>); out_median = element (n - 1) / 2 of the ascending order of the n valid slots'
+ *   depths (a zero is returned as +0.0), out_count = n.  n == 0, where the reference throws std::out_of_range: out_median 0.0f,
+ *   out_count 0.  Finite inputs are a precondition.  Slots j >= counts[f] are not read. */
+typedef struct plp_median_depth_args {
+    int32_t F, m_cap;               /* F > 0 key frames of 0 <= m_cap <= 8192 landmark slots */
+    int32_t abs_flag;               /* the `abs` argument (true at two_view_triangulator_line.cc:246-253) */
+    const double* pose;             /* F x 15: the plp_observe_args.pose row (entries 6-8 and 11 are read) */
+    const double* pos_w;            /* F x m_cap x 3: landmarks_[j]->get_pos_in_world(), in slot order */
+    const uint8_t* valid;           /* F x m_cap: 0 = a nullptr slot; NULL = every slot holds a landmark */
+    const int32_t* counts;          /* F: landmarks_.size(), or NULL = m_cap everywhere */
+    float* out_median;              /* F */
+    int32_t* out_count;             /* F */
+} plp_median_depth_args;
+/* Invalid (PLP_ERR_INVALID_ARG, checked before anything is written): NULL ctx / args; F <= 0, m_cap < 0; NULL pose, out_median, out_count;
+ * NULL pos_w when m_cap > 0.  m_cap > 8192: PLP_ERR_UNSUPPORTED.  m_cap == 0 is valid (every key frame: 0.0f, 0).
+ * _device: every array a DEVICE pointer, asynchronous on hip_stream.  _host: HOST pointers, staged (the outputs too), the same kernel,
+ * synchronous. */
+plp_status plp_median_depth_device(plp_matcher* ctx, const plp_median_depth_args* args, void* hip_stream);
+plp_status plp_median_depth_host(plp_matcher* ctx, const plp_median_depth_args* args);
+
+/* The loop over the matches (mapping_module.cc:502-600) with module::two_view_triangulator_line::triangulate
+ * (module/two_view_triangulator_line.cc:52-296, .h:128-151), for P pairs of key frames in G groups, over a table of F key frames.
+ * A group is one call sequence of the reference: one first key frame (cur = kf1, the query side of the 1-NN) against its neighbours
+ * (kf2, the train side) in the order the reference visits them: pairs group_offsets[g] .. group_offsets[g + 1] - 1.  Within a group every
+ * pair has the same kf1 and pairwise distinct kf2 != kf1.  Groups are independent: each starts from `occupied` as given.
+ * Per pair p and query slot j < counts[kf1], out_status says where the reference leaves the iteration, in its order of evaluation: */
+typedef enum plp_keyline_pair_status {
+    PLP_KLP_CREATED = 0,          /* triangulate returned true: the reference creates the landmark (out_match, out_pos_w) */
+    PLP_KLP_GATE_DISTANCE = 1,    /* no 1-NN, a train index outside kf2, or !(DMatch.distance < dist_thr)                 :506 */
+    PLP_KLP_GATE_ENDPOINTS = 2,   /* !(distance_s < endpoint_thr && distance_e < endpoint_thr)                            :529 */
+    PLP_KLP_GATE_ANGLE = 3,       /* !(angle < angle_thr)                                                                 :529 */
+    PLP_KLP_OCCUPIED_CUR = 4,     /* skip_occupied: cur holds a landmark at the query slot (given, or created with an earlier neighbour) :564 */
+    PLP_KLP_OCCUPIED_NGH = 5,     /* skip_occupied: ngh holds one at the train slot (given, or created by an earlier match of the pair)  :564 */
+    PLP_KLP_NO_PARALLAX = 6,      /* none of the three ways to the end points applies            two_view_triangulator_line.cc:240-243 */
+    PLP_KLP_TOO_CLOSE = 7,        /* an end point nearer than 0.3 median depths                                                :246-250 */
+    PLP_KLP_TOO_LONG = 8,         /* longer than 0.9 median depths                                                             :253-256 */
+    PLP_KLP_DEPTH = 9,            /* an end point behind one of the two cameras                                                :259-265 */
+    PLP_KLP_REPROJ_MID = 10,      /* the midpoint's reprojection error                                                         :269-270 */
+    PLP_KLP_REPROJ_END = 11,      /* an end point's distance to the key line                                                   :271-281 */
+    PLP_KLP_SCALE = 12,           /* check_scale_factors                                                                       :284-292 */
+    PLP_KLP_NON_FINITE = 13,      /* a non-finite end point or reprojection error (undefined in the -ffast-math reference): no landmark */
+    PLP_KLP_KP_DEPTH_RANGE = 14   /* depths_.at(idx) with idx >= the number of key points, where the reference throws          :90, :93 */
+} plp_keyline_pair_status;
+typedef struct plp_keyline_pairs_args {
+    plp_camera_model camera;        /* PLP_CAMERA_PERSPECTIVE (two_view_triangulator_line.cc:43 casts); fx, fy, cx, cy are read */
+    int32_t setup_type;             /* camera::setup_type_t: 0 monocular, 1 stereo, 2 RGB-D */
+    double true_baseline;           /* camera::base true_baseline_ */
+    const float* scale_factors;     /* HOST, num_levels: keyframe::scale_factors_, read at keyline.octave (:284-289) */
+    const float* level_sigma_sq;    /* HOST, num_levels: keyframe::level_sigma_sq_, read at keyline.octave (:269-278) */
+    int32_t num_levels;             /* 1 .. 16; an octave outside [0, num_levels), where the reference's at() throws, is clamped */
+    float scale_factor;             /* keyframe::scale_factor_: ratio_factor_ = 2.0f * scale_factor (:40) */
+    float rays_parallax_deg_thr;    /* 1.0 at both call sites; cos_rays_parallax_thr_ = (float)cos(thr * M_PI / 180.0) is formed on the host */
+    float dist_thr, endpoint_thr, angle_thr;   /* 50 / 400 / 20 (mapping_module.cc:506, :529), 30 / 200 / 5 (initializer.cc) */
+    int32_t skip_occupied;          /* 1: "avoid duplicate triangulation" (mapping_module.cc:564); 0: the initialiser's loop, which has no such check */
+    int32_t F, cap, kp_cap;         /* the table: F > 0 key frames of 0 <= cap <= 8192 key-line slots and kp_cap >= 0 key-point slots */
+    const plp_keyline* keylines;    /* F x cap: _keylsd */
+    const int32_t* counts;          /* F: _keylsd.size(), or NULL = cap everywhere */
+    const double* line_functions;   /* F x cap x 3: _keyline_functions (the line extractor's third output) */
+    const float* kl_x_right;        /* F x cap x 2: _stereo_x_right_cooresponding_to_keylines; .first is read, 0 <= .first = "is stereo" */
+    const float* kp_depths;         /* F x kp_cap: the KEY POINTS' depths_, which the reference indexes with a key-line index (D8 item 2) */
+    const int32_t* kp_counts;       /* F: depths_.size(), or NULL = kp_cap everywhere */
+    const double* pose;             /* F x 15: the plp_observe_args.pose row */
+    const float* median_depth;      /* F: compute_median_depth(true), e.g. plp_median_depth_*'s out_median; key frame 2's is the one read */
+    const double* lines_3d;         /* F x cap x 6: triangulate_stereo_for_line(idx) of every key line (plp_keylines_3d_*'s out_pos_w, its
+                                       zero rows included); may be NULL for a monocular setup, which never reads it */
+    const uint8_t* occupied;        /* F x cap: get_landmark_line(idx) != nullptr before the call */
+    int32_t P, G;                   /* P >= 0 pairs in G >= 0 groups */
+    const int32_t* pairs;           /* P x 2: kf1, kf2 (indices into the table) */
+    const int32_t* group_offsets;   /* G + 1, non-decreasing, inside [0, P] */
+    const int32_t* train_idx;       /* P x cap: plp_lbd_match_1nn_* with kf1 = query, kf2 = train */
+    const int32_t* dist;            /* P x cap: its dist */
+    int32_t* out_match;             /* P x cap: the train index of the landmark the reference creates, else -1 */
+    double* out_pos_w;              /* P x cap x 6: pos_w_line (sp, ep) where out_match >= 0, zero elsewhere */
+    uint8_t* out_status;            /* P x cap: a plp_keyline_pair_status */
+    uint8_t* out_occupied_cur;      /* G x cap: cur's slots after the group (`occupied` or a landmark created in the group), slots
+                                       j < counts[kf1]; feed it back as `occupied` to chain calls */
+} plp_keyline_pairs_args;
+/* Slots j >= counts[kf1] of a pair are neither read nor written; a pair outside every group gets its geometry statuses without the
+ * duplicate check.  Checked before anything is written: NULL ctx / args, the camera as for plp_post_extract_model_*, setup_type outside
+ * 0..2, num_levels outside 1..16, F <= 0, cap < 0, kp_cap < 0, P < 0, G < 0, a NULL scale_factors / level_sigma_sq, and -- when P > 0,
+ * G > 0 and cap > 0 -- a NULL keylines, line_functions, kl_x_right, pose, median_depth, occupied, pairs, group_offsets, train_idx, dist or
+ * output, a NULL kp_depths with kp_cap > 0, a NULL lines_3d with a stereo or RGB-D setup (PLP_ERR_INVALID_ARG); a camera that is not
+ * perspective, cap > 8192 or P > 2^31 / 8192 (PLP_ERR_UNSUPPORTED).  cap == 0, P == 0 or G == 0: PLP_OK, nothing written.
+ * _host additionally checks (PLP_ERR_INVALID_ARG) that group_offsets is non-decreasing inside [0, P], that every kf1 / kf2 is inside
+ * [0, F), and that the pairs of a group share kf1 and have pairwise distinct kf2 != kf1; on the _device path these are preconditions
+ * (an index outside the table is not followed: the pair is left unwritten).
+ * _device: every array but scale_factors / level_sigma_sq a DEVICE pointer; two kernels on hip_stream, no host synchronisation.
+ * _host: HOST pointers, staged (the outputs too, so that every slot the kernels do not write keeps the caller's value), the same kernels,
+ * synchronous. */
+plp_status plp_triangulate_keyline_pairs_device(plp_matcher* ctx, const plp_keyline_pairs_args* args, void* hip_stream);
+plp_status plp_triangulate_keyline_pairs_host(plp_matcher* ctx, const plp_keyline_pairs_args* args);
+
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the
  * raw colour / 16-bit depth frames can go straight to HBM.  B frames, device pointers, asynchronous.

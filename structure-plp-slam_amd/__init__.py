@@ -122,6 +122,10 @@ _API = [
     ("plp_stereo_keylines_host", C.c_int, [_VP, _VP]),
     ("plp_keylines_3d_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_keylines_3d_host", C.c_int, [_VP, _VP]),
+    ("plp_median_depth_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_median_depth_host", C.c_int, [_VP, _VP]),
+    ("plp_triangulate_keyline_pairs_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_triangulate_keyline_pairs_host", C.c_int, [_VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -612,6 +616,31 @@ class keylines_3d_args_c(C.Structure):
                 ("counts_right", _VP), ("out_pos_w", _VP), ("out_valid", _VP)]
 
 
+class median_depth_args_c(C.Structure):
+    """plp_median_depth_args"""
+    _fields_ = [("F", C.c_int32), ("m_cap", C.c_int32), ("abs_flag", C.c_int32),
+                ("pose", _VP), ("pos_w", _VP), ("valid", _VP), ("counts", _VP), ("out_median", _VP), ("out_count", _VP)]
+
+
+class keyline_pairs_args_c(C.Structure):
+    """plp_keyline_pairs_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
+                ("scale_factors", _VP), ("level_sigma_sq", _VP), ("num_levels", C.c_int32), ("scale_factor", C.c_float),
+                ("rays_parallax_deg_thr", C.c_float), ("dist_thr", C.c_float), ("endpoint_thr", C.c_float), ("angle_thr", C.c_float),
+                ("skip_occupied", C.c_int32), ("F", C.c_int32), ("cap", C.c_int32), ("kp_cap", C.c_int32),
+                ("keylines", _VP), ("counts", _VP), ("line_functions", _VP), ("kl_x_right", _VP), ("kp_depths", _VP), ("kp_counts", _VP),
+                ("pose", _VP), ("median_depth", _VP), ("lines_3d", _VP), ("occupied", _VP),
+                ("P", C.c_int32), ("G", C.c_int32), ("pairs", _VP), ("group_offsets", _VP), ("train_idx", _VP), ("dist", _VP),
+                ("out_match", _VP), ("out_pos_w", _VP), ("out_status", _VP), ("out_occupied_cur", _VP)]
+
+
+# plp_keyline_pair_status: where the reference leaves an iteration of triangulate_line_with_two_keyframes
+(KLP_CREATED, KLP_GATE_DISTANCE, KLP_GATE_ENDPOINTS, KLP_GATE_ANGLE, KLP_OCCUPIED_CUR, KLP_OCCUPIED_NGH, KLP_NO_PARALLAX, KLP_TOO_CLOSE,
+ KLP_TOO_LONG, KLP_DEPTH, KLP_REPROJ_MID, KLP_REPROJ_END, KLP_SCALE, KLP_NON_FINITE, KLP_KP_DEPTH_RANGE) = range(15)
+KLP_MAPPING = dict(dist_thr=50.0, endpoint_thr=400.0, angle_thr=20.0, skip_occupied=1)       # mapping_module.cc:506, :529, :564
+KLP_INITIALIZER = dict(dist_thr=30.0, endpoint_thr=200.0, angle_thr=5.0, skip_occupied=0)    # module/initializer.cc:585-667
+
+
 def _struct(cls, fields, ptrs):
     a = cls()
     for k, v in fields.items():
@@ -689,6 +718,7 @@ class matcher:
         h = C.c_void_p()
         _check(lib().plp_matcher_create(device, C.byref(h)))
         self._h = h
+        self.device = device
         self.lowe_ratio = lowe_ratio
         self.check_orientation = check_orientation
         self._keep = []
@@ -1031,6 +1061,146 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_keylines_3d_device(self._h, C.byref(a), st))
+
+    # ---- key-frame pair line triangulation: keyframe::compute_median_depth (keyframe.cc:825-857), triangulate_line_with_two_keyframes
+    # (mapping_module.cc:482-601) with two_view_triangulator_line::triangulate (two_view_triangulator_line.cc:52-296)
+    def median_depth(self, pose, pos_w, valid=None, counts=None, abs_flag=True):
+        """compute_median_depth(abs) (plp_median_depth_host) of one key frame ((15,) pose, (m, 3) landmark positions, (m,) valid flags) or F
+        key frames ((F, 15), (F, m_cap, 3), (F, m_cap)).  Returns (median f32, count i32); a key frame without a landmark gives (0.0, 0)."""
+        pose = np.ascontiguousarray(pose, np.float64)
+        single = pose.ndim == 1
+        pose = pose.reshape(-1, 15)
+        F = len(pose)
+        pw = np.ascontiguousarray(pos_w, np.float64).reshape(F, -1, 3)
+        M = pw.shape[1]
+        va = None if valid is None else np.ascontiguousarray(valid, np.uint8).reshape(F, M)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        med, cnt = np.zeros(F, np.float32), np.zeros(F, np.int32)
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(median_depth_args_c, dict(F=F, m_cap=M, abs_flag=int(bool(abs_flag))), dict(
+            pose=P(pose), pos_w=P(pw), valid=P(va), counts=P(cn), out_median=med.ctypes.data, out_count=cnt.ctypes.data))
+        _check(lib().plp_median_depth_host(self._h, C.byref(a)))
+        return (med[0], cnt[0]) if single else (med, cnt)
+
+    def median_depth_device(self, F, m_cap, pose, pos_w, out_median, out_count, valid=None, counts=None, abs_flag=True, stream=None):
+        """plp_median_depth_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(median_depth_args_c, dict(F=int(F), m_cap=int(m_cap), abs_flag=int(bool(abs_flag))), dict(
+            pose=D(pose), pos_w=D(pos_w), valid=D(valid), counts=D(counts), out_median=D(out_median), out_count=D(out_count)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_median_depth_device(self._h, C.byref(a), st))
+
+    @staticmethod
+    def _keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr, dist_thr,
+                              endpoint_thr, angle_thr, skip_occupied):
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        ls = np.ascontiguousarray(level_sigma_sq, np.float32)
+        if sf.shape != ls.shape or sf.ndim != 1:
+            raise PlpError(PLP_ERR_INVALID_ARG, "scale_factors and level_sigma_sq must be vectors of the same length")
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        a.setup_type, a.true_baseline = int(setup_type), float(true_baseline)
+        a.scale_factors, a.level_sigma_sq, a.num_levels = sf.ctypes.data, ls.ctypes.data, len(sf)
+        a.scale_factor = float(sf[1]) if scale_factor is None and len(sf) > 1 else float(1.0 if scale_factor is None else scale_factor)
+        a.rays_parallax_deg_thr = float(rays_parallax_deg_thr)
+        a.dist_thr, a.endpoint_thr, a.angle_thr, a.skip_occupied = float(dist_thr), float(endpoint_thr), float(angle_thr), int(bool(skip_occupied))
+        return sf, ls                                          # kept alive by the caller until the call has returned
+
+    def triangulate_keyline_pairs(self, camera, setup_type, groups, keylines, line_functions, kl_x_right, pose, median_depth, occupied,
+                                  scale_factors, level_sigma_sq, counts=None, kp_depths=None, kp_counts=None, lines_3d=None, lbd=None,
+                                  train_idx=None, dist=None, true_baseline=0.0, scale_factor=None, rays_parallax_deg_thr=1.0, dist_thr=50.0,
+                                  endpoint_thr=400.0, angle_thr=20.0, skip_occupied=True, out=None):
+        """triangulate_line_with_two_keyframes over a table of F key frames (plp_triangulate_keyline_pairs_host).  groups: a list of
+        (kf1, [kf2, ...]): cur against its neighbours in the reference's order.  Per key frame, leading dimension F: keylines (F, cap),
+        line_functions (F, cap, 3), kl_x_right (F, cap, 2), pose (F, 15), median_depth (F,), occupied (F, cap), counts (F,), kp_depths
+        (F, kp_cap) / kp_counts (F,), lines_3d (F, cap, 6) (stereo and RGB-D).  train_idx / dist (P, cap) are the 1-NN kf1 -> kf2 of every
+        pair in group order; when they are not given, lbd (F, cap, 32) is matched on the device (plp_lbd_match_1nn_device, one batch).
+        scale_factor: keyframe::scale_factor_ (default: scale_factors[1]).  The defaults are the mapping module's thresholds; KLP_INITIALIZER
+        holds the initialiser's.  Returns dict(pairs (P, 2), group_offsets (G + 1,), train_idx, dist, match (P, cap) i32, pos_w (P, cap, 6)
+        f64, status (P, cap) u8, occupied_cur (G, cap) u8); slots the kernels do not write keep 0 / -1 for match, or out[name]."""
+        kl = np.ascontiguousarray(keylines, KL_DTYPE)
+        if kl.ndim != 2:
+            raise PlpError(PLP_ERR_INVALID_ARG, "keylines must be (F, cap)")
+        F, M = kl.shape
+        pairs = np.array([(int(k1), int(k2)) for k1, ngh in groups for k2 in ngh], np.int32).reshape(-1, 2)
+        offs = np.zeros(len(groups) + 1, np.int32)
+        offs[1:] = np.cumsum([len(ngh) for _, ngh in groups])
+        Pn, G = len(pairs), len(groups)
+        if Pn and (pairs.min() < 0 or pairs.max() >= F):
+            raise PlpError(PLP_ERR_INVALID_ARG, "a group names a key frame outside the table")
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        if train_idx is None or dist is None:
+            if lbd is None:
+                raise PlpError(PLP_ERR_INVALID_ARG, "train_idx and dist, or lbd, are required")
+            train_idx, dist = self._lbd_match_pairs(np.ascontiguousarray(lbd, np.uint8).reshape(F, M, 32), cn, pairs)
+        ti = np.ascontiguousarray(train_idx, np.int32).reshape(Pn, M)
+        di = np.ascontiguousarray(dist, np.int32).reshape(Pn, M)
+        fn = np.ascontiguousarray(line_functions, np.float64).reshape(F, M, 3)
+        xr = np.ascontiguousarray(kl_x_right, np.float32).reshape(F, M, 2)
+        po = np.ascontiguousarray(pose, np.float64).reshape(F, 15)
+        md = np.ascontiguousarray(median_depth, np.float32).reshape(F)
+        oc = np.ascontiguousarray(occupied, np.uint8).reshape(F, M)
+        kd = None if kp_depths is None else np.ascontiguousarray(kp_depths, np.float32).reshape(F, -1)
+        kc = None if kp_counts is None else np.ascontiguousarray(kp_counts, np.int32).reshape(F)
+        l3 = None if lines_3d is None else np.ascontiguousarray(lines_3d, np.float64).reshape(F, M, 6)
+        o = {}
+        for k, shape, dt, fill in (("match", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 6), np.float64, 0), ("status", (Pn, M), np.uint8, 0),
+                                   ("occupied_cur", (G, M), np.uint8, 0)):
+            v = None if out is None else out.get(k)
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            o[k] = v if v is not None else np.full(shape, fill, dt)
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(keyline_pairs_args_c, dict(F=F, cap=M, kp_cap=0 if kd is None else kd.shape[1], P=Pn, G=G), dict(
+            keylines=P(kl), counts=P(cn), line_functions=P(fn), kl_x_right=P(xr), kp_depths=P(kd), kp_counts=P(kc), pose=P(po), median_depth=P(md),
+            lines_3d=P(l3), occupied=P(oc), pairs=P(pairs), group_offsets=offs.ctypes.data, train_idx=P(ti), dist=P(di),
+            out_match=P(o["match"]), out_pos_w=P(o["pos_w"]), out_status=P(o["status"]), out_occupied_cur=P(o["occupied_cur"])))
+        keep = self._keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr,
+                                          dist_thr, endpoint_thr, angle_thr, skip_occupied)
+        _check(lib().plp_triangulate_keyline_pairs_host(self._h, C.byref(a)))
+        del keep
+        return dict(pairs=pairs, group_offsets=offs, train_idx=ti, dist=di, **o)
+
+    def _lbd_match_pairs(self, lbd, counts, pairs):
+        """BinaryDescriptorMatcher::match(kf1's descriptors, kf2's) for every pair, one batched call on the device -> (train_idx, dist) (P, cap)"""
+        import torch
+        F, M, _ = lbd.shape
+        Pn = len(pairs)
+        if Pn == 0 or M == 0:
+            return np.full((Pn, M), -1, np.int32), np.full((Pn, M), 256, np.int32)
+        dev = torch.device("cuda", self.device)
+        d = torch.from_numpy(lbd).to(dev)
+        c = torch.from_numpy(np.full(F, M, np.int32) if counts is None else np.clip(counts, 0, M).astype(np.int32)).to(dev)
+        pr = torch.from_numpy(pairs.astype(np.int64)).to(dev)
+        q, t = d[pr[:, 0]].contiguous(), d[pr[:, 1]].contiguous()
+        qc, tc = c[pr[:, 0]].contiguous(), c[pr[:, 1]].contiguous()
+        idx = torch.full((Pn, M), -1, dtype=torch.int32, device=dev)
+        dist = torch.full((Pn, M), 256, dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _check(lib().plp_lbd_match_1nn_device(self._h, q.data_ptr(), qc.data_ptr(), M, t.data_ptr(), tc.data_ptr(), M, Pn, idx.data_ptr(),
+                                              dist.data_ptr(), C.c_void_p(st)))
+        torch.cuda.synchronize(dev)
+        return idx.cpu().numpy(), dist.cpu().numpy()
+
+    def triangulate_keyline_pairs_device(self, camera, setup_type, F, cap, P, G, pairs, group_offsets, train_idx, dist, keylines, line_functions,
+                                         kl_x_right, pose, median_depth, occupied, out_match, out_pos_w, out_status, out_occupied_cur,
+                                         scale_factors, level_sigma_sq, counts=None, kp_depths=None, kp_counts=None, kp_cap=0, lines_3d=None,
+                                         true_baseline=0.0, scale_factor=None, rays_parallax_deg_thr=1.0, dist_thr=50.0, endpoint_thr=400.0,
+                                         angle_thr=20.0, skip_occupied=True, stream=None):
+        """plp_triangulate_keyline_pairs_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors and
+        level_sigma_sq are host vectors); asynchronous, two kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(keyline_pairs_args_c, dict(F=int(F), cap=int(cap), kp_cap=int(kp_cap), P=int(P), G=int(G)), dict(
+            keylines=D(keylines), counts=D(counts), line_functions=D(line_functions), kl_x_right=D(kl_x_right), kp_depths=D(kp_depths),
+            kp_counts=D(kp_counts), pose=D(pose), median_depth=D(median_depth), lines_3d=D(lines_3d), occupied=D(occupied), pairs=D(pairs),
+            group_offsets=D(group_offsets), train_idx=D(train_idx), dist=D(dist), out_match=D(out_match), out_pos_w=D(out_pos_w),
+            out_status=D(out_status), out_occupied_cur=D(out_occupied_cur)))
+        keep = self._keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr,
+                                          dist_thr, endpoint_thr, angle_thr, skip_occupied)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_triangulate_keyline_pairs_device(self._h, C.byref(a), st))
+        del keep
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""

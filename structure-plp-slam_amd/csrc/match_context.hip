@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <mutex>
 #include <vector>
@@ -835,6 +836,163 @@ plp_status plp_keylines_3d_host(plp_matcher* c, const plp_keylines_3d_args* a) {
     A.good_match = (const int32_t*)dev(4); A.kl_r = (const plp_keyline*)dev(5); A.counts_r = (const int32_t*)dev(6);
     A.pos_w = (double*)dev(7); A.valid = (uint8_t*)dev(8);
     PLP_HIP(launch_keylines_3d(c->stream, A, a->B));
+    return stage_back(c, parts, np, base);
+}
+
+// ---- key-frame pair line triangulation (include/plp_front.h: plp_median_depth_*, plp_triangulate_keyline_pairs_*; keyline_pair_kernels.hip)
+namespace {
+constexpr int kKeylinePairCap = 8192;   // the matchers' envelope; the resolve kernel's two LDS arrays stay under 48 KB
+
+plp_status median_depth_check(plp_matcher* c, const plp_median_depth_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (a->F <= 0 || a->m_cap < 0) return set_error(PLP_ERR_INVALID_ARG, "F must be positive, m_cap non-negative");
+    if (!a->pose || !a->out_median || !a->out_count) return set_error(PLP_ERR_INVALID_ARG, "pose, out_median, out_count are required");
+    if (a->m_cap > 0 && !a->pos_w) return set_error(PLP_ERR_INVALID_ARG, "pos_w is required");
+    if (a->m_cap > kKeylinePairCap) return set_error(PLP_ERR_UNSUPPORTED, "m_cap above 8192");
+    return PLP_OK;
+}
+
+MedianDepthArgs median_depth_args(const plp_median_depth_args* a) {
+    MedianDepthArgs A{};
+    A.m_cap = a->m_cap; A.abs_flag = a->abs_flag ? 1 : 0;
+    A.pose = a->pose; A.pos_w = a->pos_w; A.valid = a->m_cap ? a->valid : nullptr; A.counts = a->m_cap ? a->counts : nullptr;
+    A.median = a->out_median; A.count = a->out_count;
+    return A;
+}
+
+bool keyline_pairs_empty(const plp_keyline_pairs_args* a) { return a->cap == 0 || a->P == 0 || a->G == 0; }
+
+plp_status keyline_pairs_check(plp_matcher* c, const plp_keyline_pairs_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, true)) return s;
+    if (a->camera.model != PLP_CAMERA_PERSPECTIVE)
+        return set_error(PLP_ERR_UNSUPPORTED, "the line triangulator needs the perspective camera (two_view_triangulator_line.cc:43)");
+    if (a->setup_type < 0 || a->setup_type > 2) return set_error(PLP_ERR_INVALID_ARG, "setup_type must be 0, 1 or 2");
+    if (a->num_levels < 1 || a->num_levels > 16) return set_error(PLP_ERR_INVALID_ARG, "num_levels must be 1 .. 16");
+    if (a->F <= 0 || a->cap < 0 || a->kp_cap < 0 || a->P < 0 || a->G < 0)
+        return set_error(PLP_ERR_INVALID_ARG, "F must be positive, cap, kp_cap, P and G non-negative");
+    if (!a->scale_factors || !a->level_sigma_sq) return set_error(PLP_ERR_INVALID_ARG, "scale_factors and level_sigma_sq are required");
+    if (a->cap > kKeylinePairCap) return set_error(PLP_ERR_UNSUPPORTED, "cap above 8192");
+    if (keyline_pairs_empty(a)) return PLP_OK;
+    if ((int64_t)a->P * a->cap > ((int64_t)1 << 31)) return set_error(PLP_ERR_UNSUPPORTED, "P x cap above 2^31");
+    if (!a->keylines || !a->line_functions || !a->kl_x_right || !a->pose || !a->median_depth || !a->occupied || !a->pairs || !a->group_offsets ||
+        !a->train_idx || !a->dist)
+        return set_error(PLP_ERR_INVALID_ARG, "keylines, line_functions, kl_x_right, pose, median_depth, occupied, pairs, group_offsets, train_idx, dist are required");
+    if (!a->out_match || !a->out_pos_w || !a->out_status || !a->out_occupied_cur)
+        return set_error(PLP_ERR_INVALID_ARG, "out_match, out_pos_w, out_status, out_occupied_cur are required");
+    if (a->kp_cap > 0 && !a->kp_depths) return set_error(PLP_ERR_INVALID_ARG, "kp_depths is required when kp_cap > 0");
+    if (a->setup_type != 0 && !a->lines_3d) return set_error(PLP_ERR_INVALID_ARG, "lines_3d is required for a stereo or RGB-D setup");
+    return PLP_OK;
+}
+
+// the preconditions of the _device path, checked where the lists are host memory
+plp_status keyline_pairs_check_groups(const plp_keyline_pairs_args* a) {
+    int prev = 0;
+    for (int g = 0; g <= a->G; ++g) {
+        const int o = a->group_offsets[g];
+        if (o < prev || o > a->P) return set_error(PLP_ERR_INVALID_ARG, "group_offsets must be non-decreasing inside [0, P]");
+        prev = o;
+    }
+    for (int p = 0; p < a->P; ++p)
+        for (int k = 0; k < 2; ++k)
+            if (a->pairs[2 * p + k] < 0 || a->pairs[2 * p + k] >= a->F) return set_error(PLP_ERR_INVALID_ARG, "a pair names a key frame outside the table");
+    std::vector<uint8_t> seen((size_t)a->F);
+    for (int g = 0; g < a->G; ++g) {
+        const int b = a->group_offsets[g], e = a->group_offsets[g + 1];
+        for (int p = b; p < e; ++p) {
+            const int f1 = a->pairs[2 * p], f2 = a->pairs[2 * p + 1];
+            if (f1 != a->pairs[2 * b]) return set_error(PLP_ERR_INVALID_ARG, "the pairs of a group must share kf1");
+            if (f2 == f1 || seen[f2]) return set_error(PLP_ERR_INVALID_ARG, "the pairs of a group must have pairwise distinct kf2 != kf1");
+            seen[f2] = 1;
+        }
+        for (int p = b; p < e; ++p) seen[a->pairs[2 * p + 1]] = 0;
+    }
+    return PLP_OK;
+}
+
+KeylinePairArgs keyline_pairs_args(const plp_keyline_pairs_args* a) {
+    KeylinePairArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy;
+    A.half_baseline = a->true_baseline / 2.0;
+    A.setup_type = a->setup_type; A.num_levels = a->num_levels; A.skip_occupied = a->skip_occupied ? 1 : 0;
+    A.F = a->F; A.cap = a->cap; A.kp_cap = a->kp_cap; A.P = a->P; A.G = a->G;
+    A.cos_thr = (float)std::cos(a->rays_parallax_deg_thr * M_PI / 180.0);   // two_view_triangulator_line.cc:41 into the float of .h:112
+    A.dist_thr = a->dist_thr; A.endpoint_thr = a->endpoint_thr; A.angle_thr = a->angle_thr;
+    A.ratio_factor = 2.0f * a->scale_factor;
+    for (int i = 0; i < 16; ++i) {
+        A.scale_factors[i] = i < a->num_levels ? a->scale_factors[i] : 1.0f;
+        A.level_sigma_sq[i] = i < a->num_levels ? a->level_sigma_sq[i] : 1.0f;
+    }
+    A.kl = a->keylines; A.counts = a->counts; A.line_fn = a->line_functions; A.x_right = a->kl_x_right;
+    A.kp_depths = a->kp_cap ? a->kp_depths : nullptr; A.kp_counts = a->kp_cap ? a->kp_counts : nullptr;
+    A.pose = a->pose; A.median = a->median_depth; A.lines_3d = a->setup_type != 0 ? a->lines_3d : nullptr; A.occupied = a->occupied;
+    A.pairs = a->pairs; A.group_offsets = a->group_offsets; A.train_idx = a->train_idx; A.dist = a->dist;
+    A.out_match = a->out_match; A.out_pos_w = a->out_pos_w; A.out_status = a->out_status; A.out_occ_cur = a->out_occupied_cur;
+    return A;
+}
+}  // namespace
+
+plp_status plp_median_depth_device(plp_matcher* c, const plp_median_depth_args* a, void* hip_stream) {
+    if (plp_status s = median_depth_check(c, a)) return s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_median_depth((hipStream_t)hip_stream, median_depth_args(a), a->F));
+    return PLP_OK;
+}
+
+plp_status plp_median_depth_host(plp_matcher* c, const plp_median_depth_args* a) {
+    if (plp_status s = median_depth_check(c, a)) return s;
+    const size_t F = (size_t)a->F, M = (size_t)a->m_cap;
+    const MedianDepthArgs H = median_depth_args(a);
+    StagePart parts[] = {{H.pose, nullptr, F * 15 * 8, 0}, {H.pos_w, nullptr, F * M * 24, 0}, {H.valid, nullptr, F * M, 0}, {H.counts, nullptr, F * 4, 0},
+                         {nullptr, H.median, F * 4, 0}, {nullptr, H.count, F * 4, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    MedianDepthArgs A = H;
+    A.pose = (const double*)dev(0); A.pos_w = (const double*)dev(1); A.valid = (const uint8_t*)dev(2); A.counts = (const int32_t*)dev(3);
+    A.median = (float*)dev(4); A.count = (int32_t*)dev(5);
+    PLP_HIP(launch_median_depth(c->stream, A, a->F));
+    return stage_back(c, parts, np, base);
+}
+
+plp_status plp_triangulate_keyline_pairs_device(plp_matcher* c, const plp_keyline_pairs_args* a, void* hip_stream) {
+    if (plp_status s = keyline_pairs_check(c, a)) return s;
+    if (keyline_pairs_empty(a)) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_keyline_pairs((hipStream_t)hip_stream, keyline_pairs_args(a)));
+    return PLP_OK;
+}
+
+plp_status plp_triangulate_keyline_pairs_host(plp_matcher* c, const plp_keyline_pairs_args* a) {
+    if (plp_status s = keyline_pairs_check(c, a)) return s;
+    if (keyline_pairs_empty(a)) return PLP_OK;
+    if (plp_status s = keyline_pairs_check_groups(a)) return s;
+    const size_t F = (size_t)a->F, M = (size_t)a->cap, K = (size_t)a->kp_cap, P = (size_t)a->P, G = (size_t)a->G;
+    const KeylinePairArgs H = keyline_pairs_args(a);
+    StagePart parts[] = {
+        {H.kl, nullptr, F * M * sizeof(plp_keyline), 0}, {H.counts, nullptr, F * 4, 0}, {H.line_fn, nullptr, F * M * 24, 0},
+        {H.x_right, nullptr, F * M * 8, 0}, {H.kp_depths, nullptr, F * K * 4, 0}, {H.kp_counts, nullptr, F * 4, 0}, {H.pose, nullptr, F * 15 * 8, 0},
+        {H.median, nullptr, F * 4, 0}, {H.lines_3d, nullptr, F * M * 48, 0}, {H.occupied, nullptr, F * M, 0}, {H.pairs, nullptr, P * 8, 0},
+        {H.group_offsets, nullptr, (G + 1) * 4, 0}, {H.train_idx, nullptr, P * M * 4, 0}, {H.dist, nullptr, P * M * 4, 0},
+        {nullptr, H.out_match, P * M * 4, 0}, {nullptr, H.out_pos_w, P * M * 48, 0}, {nullptr, H.out_status, P * M, 0},
+        {nullptr, H.out_occ_cur, G * M, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    KeylinePairArgs A = H;
+    A.kl = (const plp_keyline*)dev(0); A.counts = (const int32_t*)dev(1); A.line_fn = (const double*)dev(2); A.x_right = (const float*)dev(3);
+    A.kp_depths = (const float*)dev(4); A.kp_counts = (const int32_t*)dev(5); A.pose = (const double*)dev(6); A.median = (const float*)dev(7);
+    A.lines_3d = (const double*)dev(8); A.occupied = (const uint8_t*)dev(9); A.pairs = (const int32_t*)dev(10);
+    A.group_offsets = (const int32_t*)dev(11); A.train_idx = (const int32_t*)dev(12); A.dist = (const int32_t*)dev(13);
+    A.out_match = (int32_t*)dev(14); A.out_pos_w = (double*)dev(15); A.out_status = (uint8_t*)dev(16); A.out_occ_cur = (uint8_t*)dev(17);
+    PLP_HIP(launch_keyline_pairs(c->stream, A));
     return stage_back(c, parts, np, base);
 }
 

@@ -153,6 +153,29 @@ struct Keylines3dArgs {
 // both return the first error of their launch
 hipError_t launch_stereo_keylines(hipStream_t st, const StereoKeylineArgs& A, int B);
 hipError_t launch_keylines_3d(hipStream_t st, const Keylines3dArgs& A, int B);
+// key-frame pair line triangulation (plp_median_depth_* / plp_triangulate_keyline_pairs_*, keyline_pair_kernels.hip)
+struct MedianDepthArgs {
+    int m_cap, abs_flag;
+    const double* pose; const double* pos_w; const uint8_t* valid; const int32_t* counts;
+    float* median; int32_t* count;
+};
+struct KeylinePairArgs {
+    double fx, fy, cx, cy;            // camera::perspective doubles
+    double half_baseline;             // true_baseline_ / 2.0
+    int setup_type, num_levels, skip_occupied;
+    int F, cap, kp_cap, P, G;
+    float cos_thr;                    // cos_rays_parallax_thr_, the float of cos(thr * M_PI / 180.0)
+    float dist_thr, endpoint_thr, angle_thr;
+    float ratio_factor;               // 2.0f * scale_factor_
+    float scale_factors[16], level_sigma_sq[16];
+    const plp_keyline* kl; const int32_t* counts; const double* line_fn; const float* x_right; const float* kp_depths; const int32_t* kp_counts;
+    const double* pose; const float* median; const double* lines_3d; const uint8_t* occupied;
+    const int32_t* pairs; const int32_t* group_offsets; const int32_t* train_idx; const int32_t* dist;
+    int32_t* out_match; double* out_pos_w; uint8_t* out_status; uint8_t* out_occ_cur;
+};
+// both return the first error of their launches (the second: the geometry kernel, then the resolve kernel, on the same stream)
+hipError_t launch_median_depth(hipStream_t st, const MedianDepthArgs& A, int F);
+hipError_t launch_keyline_pairs(hipStream_t st, const KeylinePairArgs& A);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,
                     size_t dst_step, size_t dst_fs);
 void launch_to_depth(hipStream_t st, const void* src, int is_u16, int rows, int cols, size_t src_step, size_t src_fs, float scale, int B, float* dst,
