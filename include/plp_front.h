@@ -631,6 +631,97 @@ plp_status plp_project_last_frame_lines_device(plp_matcher* ctx, const plp_last_
 plp_status plp_project_last_frame_lines_host(plp_matcher* ctx, const plp_last_frame_args* args);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Fuse, Sim3 and relocalisation queries (the queries of PLP_MATCH_MODE_FUSE[_LINE] and of the key-frame / Sim3 variants of LAST_FRAME[_LINE]):
+ * what seven loops of the reference do per landmark in front of their search, for B (key frame or frame, landmark list) problems at once.
+ *   loop                                                               dist_mode  ray_test  line_dist_mode  search (plp_match_args)
+ *   fuse::replace_duplication              match/fuse.cc:169-236       CENTER     1         -               FUSE
+ *   fuse::replace_duplication_line         match/fuse.cc:335-420       CENTER     0         ENDPOINTS       FUSE_LINE
+ *   fuse::detect_duplication               match/fuse.cc:40-111        CENTER     1         -               FUSE, NO_CHI2 | SIGNED_LEVEL
+ *   projection::match_by_Sim3_transform    match/projection.cc:781-848 CENTER     1         -               LAST_FRAME, level_window 1, UNSIGNED_LEVEL
+ *   projection::match_keyframes_mutually   :894-993 and :1029-1087     CAMERA     0         -               FUSE, NO_CHI2 (one call per pass)
+ *   projection::match_frame_and_keyframe   :529-593                    CENTER     0         -               LAST_FRAME, level_window 2
+ *   projection::match_frame_and_keyframe_line  :648-743                CENTER     0         MIDPOINT        LAST_FRAME_LINE
+ * Per slot, in the reference's order (numeric contract: DESIGN.md section 5, D9):
+ *   1  skip[j] != 0 -> SKIPPED.  The tests at the top of each loop read host objects and stay with the caller: !lm, will_be_erased(),
+ *      is_observed_in_keyframe, valid_lms_in_keyfrm.count, already_matched.count, is_already_matched_in_keyfrm_1 / _2.
+ *   2  camera_->reproject_to_image(R, t, pos_w) with R = pose entries 0-8, t = 9-11 (camera/perspective.cc:190-209, fisheye.cc:231-249,
+ *      equirectangular.cc:104-119).  Points: not in the image -> NOT_IN_IMAGE.  Lines: both end points out -> NOT_IN_IMAGE; one out and
+ *      the midpoint 0.5 * (sp + ep) out -> MIDPOINT_OUT.
+ *   3  the distance range, an f64 comparison with the float results of get_min / max_valid_distance (points 0.7 x / 1.3 x, landmark.cc:297-307;
+ *      lines 0.8 x / 1.2 x, landmark_line.cc:354-364) widened to double: dist < min || max < dist -> DISTANCE.
+ *      dist: PLP_PROJECT_DIST_CENTER (pos_w - cam_center).norm(), cam_center = pose entries 12-14; PLP_PROJECT_DIST_CAMERA
+ *      (R pos_w + t).norm() (pos_2.norm(), projection.cc:976, 1070).  Lines: PLP_PROJECT_LINE_ENDPOINTS tests both end-point distances
+ *      (fuse.cc:398-411), PLP_PROJECT_LINE_MIDPOINT the midpoint's (projection.cc:722-730).
+ *   4  ray_test: cam_to_lm_vec.dot(obs_mean_normal) < 0.5 * dist -> RAY (fuse.cc:98, 221; projection.cc:835; no division, 0.5 a double)
+ *   5  pred_scale_level = predict_scale_level((float)dist, ...) (lines: of the midpoint distance, fuse.cc:414-416) -> KEPT
+ * Slot j of problem b is b * m_cap + j; slots j >= counts[b] are neither read nor written.  Outputs per slot j < counts[b], in the layouts
+ * plp_match_device reads (q_valid, q_reproj_d, q_reproj2_d, q_reproj, q_reproj2, q_x_right, q_x_right2, q_level), so nothing is copied or
+ * compacted between the two calls; the search's own tables (q_desc, q_angle, q_has_obs, t_occupied) stay the caller's:
+ *   out_valid     1 where the reference goes on to its search (KEPT), else 0
+ *   out_status    a plp_project_status: where the reference leaves the iteration
+ *   points: out_reproj_d = the f64 reprojection, out_reproj / out_x_right = its (float) and the (float) x_right, out_level =
+ *           pred_scale_level; all written for valid slots only
+ *   lines:  out_reproj_d / out_reproj2_d, out_reproj / out_reproj2, out_x_right / out_x_right2 = reproj_sp / reproj_ep and x_right_sp /
+ *           x_right_ep after slot j's turn, for EVERY slot: all three line loops declare them inside the loop and reproject_to_image does
+ *           not write them for z <= 0, so a kept line with an end point behind the camera reads uninitialised values (fuse.cc:364-367,
+ *           418-420; projection.cc:682-688); the library defines them as D6 does: the values of the most recent earlier non-skipped slot
+ *           whose matching end point was written, (0, 0) / 0 before the first one.  out_level is written for valid slots only.
+ *   out_num_valid[b] = number of valid slots */
+typedef enum plp_project_dist_mode { PLP_PROJECT_DIST_CENTER = 0, PLP_PROJECT_DIST_CAMERA = 1 } plp_project_dist_mode;
+typedef enum plp_project_line_dist_mode { PLP_PROJECT_LINE_ENDPOINTS = 0, PLP_PROJECT_LINE_MIDPOINT = 1 } plp_project_line_dist_mode;
+typedef enum plp_project_status {
+    PLP_PROJECT_KEPT = 0, PLP_PROJECT_SKIPPED = 1, PLP_PROJECT_NOT_IN_IMAGE = 2, PLP_PROJECT_MIDPOINT_OUT = 3, PLP_PROJECT_DISTANCE = 4,
+    PLP_PROJECT_RAY = 5
+} plp_project_status;
+typedef struct plp_project_args {
+    plp_camera_model camera;        /* model, cols, rows, fx, fy, cx, cy, focal_x_baseline are read (as plp_observe_args) */
+    float img_bounds[4];            /* camera::base img_bounds_: min_x, max_x, min_y, max_y */
+    float log_scale_factor;         /* log_scale_factor_ of the key frame / frame (points) / _log_scale_factor_lsd (lines) */
+    int32_t num_levels;             /* num_scale_levels_ (points) / _num_scale_levels_lsd (lines), >= 1 */
+    int32_t B, m_cap;               /* B > 0 problems of m_cap >= 0 landmark slots */
+    int32_t shared_landmarks;       /* != 0: pos_w, obs_mean_normal, min / max_valid_dist have m_cap rows in all and every problem reads the
+                                       same rows (the forward pass of mapping_module::fuse_landmark_duplication: the current key frame's
+                                       landmarks into every target); skip and the outputs stay B x m_cap */
+    int32_t dist_mode;              /* a plp_project_dist_mode; lines: PLP_PROJECT_DIST_CENTER */
+    int32_t ray_test;               /* points: != 0 needs obs_mean_normal and PLP_PROJECT_DIST_CENTER; lines: 0 */
+    int32_t line_dist_mode;         /* lines: a plp_project_line_dist_mode; ignored for points */
+    const double* pose;             /* B x 15: the 3 x 3 matrix handed to reproject_to_image row-major (0-8), its translation (9-11), cam_center
+                                       (12-14; not read with PLP_PROJECT_DIST_CAMERA).  Formed by the caller with the reference's own lines:
+                                       a key frame's rot_cw / trans_cw / cam_center; fuse.cc:46-50 and projection.cc:787-791 for a Sim3;
+                                       projection.cc:906-908 with :941-942 and :1035-1036 for the two mutual passes (the matrix is the scaled
+                                       s_rot_21w / s_rot_12w); :536-538 for a frame */
+    const int32_t* counts;          /* B, or NULL = m_cap everywhere */
+    const double* pos_w;            /* B x m_cap x 3 (points) / x 6 (lines: start point, end point); m_cap rows when shared_landmarks */
+    const double* obs_mean_normal;  /* points: B x m_cap x 3, or NULL without ray_test; ignored for lines */
+    const float* min_valid_dist;    /* B x m_cap: the raw members min_valid_dist_ / _min_valid_dist (float) */
+    const float* max_valid_dist;    /* B x m_cap: max_valid_dist_ / _max_valid_dist */
+    const uint8_t* skip;            /* B x m_cap, or NULL = nothing skipped */
+    double* out_reproj_d;           /* B x m_cap x 2 or NULL (lines: start point): q_reproj_d */
+    double* out_reproj2_d;          /* lines: B x m_cap x 2 with out_reproj_d, end point: q_reproj2_d; ignored for points */
+    float* out_reproj;              /* B x m_cap x 2 or NULL (lines: start point): q_reproj of the LAST_FRAME modes */
+    float* out_reproj2;             /* lines: B x m_cap x 2 with out_reproj, end point; ignored for points */
+    float* out_x_right;             /* B x m_cap or NULL (lines: start point) */
+    float* out_x_right2;            /* lines: B x m_cap or NULL, end point; ignored for points */
+    int32_t* out_level;             /* B x m_cap or NULL */
+    uint8_t* out_valid;             /* B x m_cap */
+    uint8_t* out_status;            /* B x m_cap or NULL */
+    int32_t* out_num_valid;         /* B or NULL */
+} plp_project_args;
+/* Invalid (PLP_ERR_INVALID_ARG, checked before anything is written, m_cap == 0 included): NULL ctx / args; the camera as for
+ * plp_post_extract_model_*; B <= 0, m_cap < 0, num_levels <= 0; NULL pose, pos_w, min_valid_dist, max_valid_dist, out_valid; out_reproj_d and
+ * out_reproj both NULL; dist_mode outside 0..1; points: ray_test with NULL obs_mean_normal or with PLP_PROJECT_DIST_CAMERA; lines:
+ * line_dist_mode outside 0..1, dist_mode not PLP_PROJECT_DIST_CENTER, ray_test != 0, out_reproj_d without out_reproj2_d or out_reproj without
+ * out_reproj2.  B > 65535: PLP_ERR_UNSUPPORTED.  m_cap == 0: PLP_OK, out_num_valid set to 0, nothing else written.  No launch dimension
+ * limits m_cap (points: m_cap / 256 workgroups along x; lines: one workgroup per problem walks its slots in chunks of 256).
+ * _device: every array a DEVICE pointer, asynchronous on hip_stream.  _host: HOST pointers, staged to HBM (the outputs too, so that every
+ * slot the kernel does not write keeps the caller's value), the same kernel, synchronous. */
+plp_status plp_project_landmarks_device(plp_matcher* ctx, const plp_project_args* args, void* hip_stream);   /* the five point loops above */
+plp_status plp_project_landmarks_host(plp_matcher* ctx, const plp_project_args* args);
+/* fuse::replace_duplication_line (match/fuse.cc:335-420) and projection::match_frame_and_keyframe_line (match/projection.cc:648-743) */
+plp_status plp_project_landmark_lines_device(plp_matcher* ctx, const plp_project_args* args, void* hip_stream);
+plp_status plp_project_landmark_lines_host(plp_matcher* ctx, const plp_project_args* args);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Stereo key-line association: the filter every stereo data::frame constructor with lines runs on BinaryDescriptorMatcher::match's
  * left -> right result (data/frame.cc:389-427, again at :494-533), for B frames at once.  A match of left key line j is kept when
  *   DMatch.distance < 30 (float; the 1-NN's (-1, 256) is never kept, nor is a train index outside [0, count_right))

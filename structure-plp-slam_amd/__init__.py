@@ -118,6 +118,10 @@ _API = [
     ("plp_project_last_frame_host", C.c_int, [_VP, _VP]),
     ("plp_project_last_frame_lines_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_project_last_frame_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_project_landmarks_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_project_landmarks_host", C.c_int, [_VP, _VP]),
+    ("plp_project_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_project_landmark_lines_host", C.c_int, [_VP, _VP]),
     ("plp_stereo_keylines_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_stereo_keylines_host", C.c_int, [_VP, _VP]),
     ("plp_keylines_3d_device", C.c_int, [_VP, _VP, _VP]),
@@ -602,6 +606,84 @@ def _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, pt
     return a
 
 
+class project_args_c(C.Structure):
+    """plp_project_args"""
+    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("log_scale_factor", C.c_float), ("num_levels", C.c_int32),
+                ("B", C.c_int32), ("m_cap", C.c_int32), ("shared_landmarks", C.c_int32), ("dist_mode", C.c_int32), ("ray_test", C.c_int32),
+                ("line_dist_mode", C.c_int32),
+                ("pose", _VP), ("counts", _VP), ("pos_w", _VP), ("obs_mean_normal", _VP), ("min_valid_dist", _VP), ("max_valid_dist", _VP), ("skip", _VP),
+                ("out_reproj_d", _VP), ("out_reproj2_d", _VP), ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_x_right2", _VP),
+                ("out_level", _VP), ("out_valid", _VP), ("out_status", _VP), ("out_num_valid", _VP)]
+
+
+PROJECT_DIST_CENTER, PROJECT_DIST_CAMERA = 0, 1           # plp_project_dist_mode
+PROJECT_LINE_ENDPOINTS, PROJECT_LINE_MIDPOINT = 0, 1      # plp_project_line_dist_mode
+# plp_project_status: where the reference leaves an iteration of the fuse / Sim3 / relocalisation loops
+PROJECT_KEPT, PROJECT_SKIPPED, PROJECT_NOT_IN_IMAGE, PROJECT_MIDPOINT_OUT, PROJECT_DISTANCE, PROJECT_RAY = range(6)
+
+
+def _project_args(camera, img_bounds, log_scale_factor, num_levels, B, m_cap, shared_landmarks, dist_mode, ray_test, line_dist_mode, ptrs):
+    a = project_args_c()
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    b = camera.img_bounds if img_bounds is None else img_bounds
+    a.img_bounds[:] = [float(np.float32(v)) for v in b]
+    a.log_scale_factor, a.num_levels = float(np.float32(log_scale_factor)), int(num_levels)
+    a.B, a.m_cap = int(B), int(m_cap)
+    a.shared_landmarks, a.dist_mode, a.ray_test, a.line_dist_mode = int(bool(shared_landmarks)), int(dist_mode), int(bool(ray_test)), int(line_dist_mode)
+    for k, v in ptrs.items():
+        setattr(a, k, v)
+    return a
+
+
+def _mat3(m):
+    return [[float(v) for v in row] for row in np.asarray(m, np.float64).reshape(3, 3)]
+
+
+def _vec3(v):
+    return [float(t) for t in np.asarray(v, np.float64).reshape(3)]
+
+
+def _mul33(A, Bm):
+    """Eigen's 3 x 3 product: every coefficient summed left to right over k"""
+    return [[(A[i][0] * Bm[0][j] + A[i][1] * Bm[1][j]) + A[i][2] * Bm[2][j] for j in range(3)] for i in range(3)]
+
+
+def _mul3v(A, v):
+    return [(A[i][0] * v[0] + A[i][1] * v[1]) + A[i][2] * v[2] for i in range(3)]
+
+
+def sim3_pose(Sim3_cw):
+    """The pose row of plp_project_args for a Sim3 (fuse.cc:46-50, projection.cc:787-791): s_cw = sqrt of the left-to-right dot of row 0 of
+    the scaled rotation, rot_cw = s_rot_cw / s_cw and trans_cw = Sim3_cw.block<3, 1>(0, 3) / s_cw coefficient by coefficient, cam_center =
+    -rot_cw^T trans_cw formed as frame_pose forms it."""
+    S = [[float(v) for v in row] for row in np.asarray(Sim3_cw, np.float64).reshape(4, 4)]
+    s_cw = math.sqrt((S[0][0] * S[0][0] + S[0][1] * S[0][1]) + S[0][2] * S[0][2])
+    rot = [[S[i][j] / s_cw for j in range(3)] for i in range(3)]
+    trans = [S[i][3] / s_cw for i in range(3)]
+    return frame_pose(rot, trans)
+
+
+def mutual_poses(s_12, rot_12, trans_12, rot_1w, trans_1w, rot_2w, trans_2w):
+    """The two pose rows of projection::match_keyframes_mutually (projection.cc:906-908, 941-942, 1035-1036), (2, 15): row 0 = s_rot_21w,
+    trans_21w (landmarks of key frame 1 into key frame 2), row 1 = s_rot_12w, trans_12w (landmarks of key frame 2 into key frame 1).  s_12 is
+    the reference's float; s_rot_12 = s_12 * rot_12, s_rot_21 = (1.0 / s_12) * rot_12^T, trans_21 = -s_rot_21 * trans_12; every product is
+    summed left to right over k.  Entries 12-14 (cam_center) are 0: both passes measure the distance in the camera frame
+    (PROJECT_DIST_CAMERA)."""
+    s = float(np.float32(s_12))
+    R12, R1w, R2w = _mat3(rot_12), _mat3(rot_1w), _mat3(rot_2w)
+    t12, t1w, t2w = _vec3(trans_12), _vec3(trans_1w), _vec3(trans_2w)
+    inv = 1.0 / s
+    s_rot_12 = [[s * R12[i][j] for j in range(3)] for i in range(3)]
+    s_rot_21 = [[inv * R12[j][i] for j in range(3)] for i in range(3)]
+    trans_21 = _mul3v([[-v for v in row] for row in s_rot_21], t12)
+    s_rot_21w = _mul33(s_rot_21, R1w)
+    trans_21w = [a + b for a, b in zip(_mul3v(s_rot_21, t1w), trans_21)]
+    s_rot_12w = _mul33(s_rot_12, R2w)
+    trans_12w = [a + b for a, b in zip(_mul3v(s_rot_12, t2w), t12)]
+    flat = lambda M: M[0] + M[1] + M[2]
+    return np.array([flat(s_rot_21w) + trans_21w + [0.0] * 3, flat(s_rot_12w) + trans_12w + [0.0] * 3], np.float64)
+
+
 class stereo_keylines_args_c(C.Structure):
     """plp_stereo_keylines_args"""
     _fields_ = [("B", C.c_int32), ("cap_left", C.c_int32), ("cap_right", C.c_int32),
@@ -980,6 +1062,93 @@ class matcher:
             pose_curr=pose_curr, pose_last=pose_last, pos_w=pos_w, keylines=keylines, skip=skip, counts=counts, out_reproj=out_reproj_sp,
             out_reproj2=out_reproj_ep, out_x_right=out_x_right_sp, out_x_right2=out_x_right_ep, out_level=out_level, out_valid=out_valid,
             out_direction=out_direction, out_num_valid=out_num_valid), setup_type, true_baseline, img_bounds, stream)
+
+    # ---- fuse, Sim3 and relocalisation queries: the loops in front of the searches of fuse::replace_duplication[_line], detect_duplication,
+    # match_by_Sim3_transform, match_keyframes_mutually and match_frame_and_keyframe[_line] (plp_project_landmark[_line]s_*)
+    def _project_host(self, lines, camera, pose, pos_w, obs_mean_normal, min_valid_dist, max_valid_dist, skip, counts, shared_landmarks, dist_mode,
+                      ray_test, line_dist_mode, log_scale_factor, num_levels, img_bounds):
+        pose = np.ascontiguousarray(pose, np.float64)
+        single = pose.ndim == 1
+        pose = pose.reshape(-1, 15)
+        B = len(pose)
+        w = 6 if lines else 3
+        LB = 1 if shared_landmarks else B                      # problems the landmark tables hold
+        pw = np.ascontiguousarray(pos_w, np.float64).reshape(LB, -1, w)
+        M = pw.shape[1]
+        arr = lambda v, dt, nb, *shape: None if v is None else np.ascontiguousarray(v, dt).reshape(nb, M, *shape)
+        nm = None if lines else arr(obs_mean_normal, np.float64, LB, 3)
+        mn, mx, sk = arr(min_valid_dist, np.float32, LB), arr(max_valid_dist, np.float32, LB), arr(skip, np.uint8, B)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
+        out = dict(reproj_d=np.zeros((B, M, 2), np.float64), reproj=np.zeros((B, M, 2), np.float32), x_right=np.zeros((B, M), np.float32),
+                   level=np.zeros((B, M), np.int32), valid=np.zeros((B, M), np.uint8), status=np.zeros((B, M), np.uint8), num_valid=np.zeros(B, np.int32))
+        if lines:
+            out.update(reproj_ep_d=np.zeros((B, M, 2), np.float64), reproj_ep=np.zeros((B, M, 2), np.float32), x_right_ep=np.zeros((B, M), np.float32))
+        P = lambda v: None if v is None else v.ctypes.data
+        a = _project_args(camera, img_bounds, log_scale_factor, num_levels, B, M, shared_landmarks, dist_mode, ray_test, line_dist_mode, dict(
+            pose=P(pose), counts=P(cn), pos_w=P(pw), obs_mean_normal=P(nm), min_valid_dist=P(mn), max_valid_dist=P(mx), skip=P(sk),
+            out_reproj_d=P(out["reproj_d"]), out_reproj2_d=P(out.get("reproj_ep_d")), out_reproj=P(out["reproj"]), out_reproj2=P(out.get("reproj_ep")),
+            out_x_right=P(out["x_right"]), out_x_right2=P(out.get("x_right_ep")), out_level=P(out["level"]), out_valid=P(out["valid"]),
+            out_status=P(out["status"]), out_num_valid=P(out["num_valid"])))
+        _check((lib().plp_project_landmark_lines_host if lines else lib().plp_project_landmarks_host)(self._h, C.byref(a)))
+        if lines:
+            out["reproj_sp_d"], out["reproj_sp"], out["x_right_sp"] = out.pop("reproj_d"), out.pop("reproj"), out.pop("x_right")
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def project_landmarks(self, camera, pose, pos_w, min_valid_dist, max_valid_dist, obs_mean_normal=None, skip=None, counts=None,
+                          shared_landmarks=False, dist_mode=PROJECT_DIST_CENTER, ray_test=None, log_scale_factor=None, num_levels=8, img_bounds=None):
+        """The queries of fuse::replace_duplication / detect_duplication, match_by_Sim3_transform, match_keyframes_mutually and
+        match_frame_and_keyframe (plp_project_landmarks_host) for one problem ((15,) pose) or B ((B, 15)): pose rows from frame_pose, sim3_pose or
+        mutual_poses; pos_w (m, 3) / (B, m, 3), or (m, 3) read by every problem with shared_landmarks; ray_test None = "obs_mean_normal is given".
+        Returns dict(reproj_d, reproj, x_right, level, valid, status, num_valid); reproj_d / reproj / x_right / level of invalid slots are not
+        written and hold 0."""
+        lsf = np.float32(math.log(np.float32(1.2))) if log_scale_factor is None else log_scale_factor
+        rt = (obs_mean_normal is not None) if ray_test is None else ray_test
+        return self._project_host(False, camera, pose, pos_w, obs_mean_normal, min_valid_dist, max_valid_dist, skip, counts, shared_landmarks, dist_mode,
+                                  rt, 0, lsf, num_levels, img_bounds)
+
+    def project_landmark_lines(self, camera, pose, pos_w, min_valid_dist, max_valid_dist, skip=None, counts=None, shared_landmarks=False,
+                               line_dist_mode=PROJECT_LINE_ENDPOINTS, log_scale_factor=None, num_levels=2, img_bounds=None):
+        """The queries of fuse::replace_duplication_line (PROJECT_LINE_ENDPOINTS) and match_frame_and_keyframe_line (PROJECT_LINE_MIDPOINT)
+        (plp_project_landmark_lines_host): pos_w (m, 6) / (B, m, 6) start point, end point.  Returns dict(reproj_sp_d, reproj_ep_d, reproj_sp,
+        reproj_ep, x_right_sp, x_right_ep, level, valid, status, num_valid); the end points of every slot are the reference's temporaries after it as
+        DESIGN.md section 5 D6 / D9 define them."""
+        lsf = np.float32(math.log(np.float32(2.0))) if log_scale_factor is None else log_scale_factor
+        return self._project_host(True, camera, pose, pos_w, None, min_valid_dist, max_valid_dist, skip, counts, shared_landmarks, PROJECT_DIST_CENTER,
+                                  False, line_dist_mode, lsf, num_levels, img_bounds)
+
+    def _project_device(self, lines, camera, B, m_cap, ptrs, shared_landmarks, dist_mode, ray_test, line_dist_mode, log_scale_factor, num_levels,
+                        img_bounds, stream):
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _project_args(camera, img_bounds, log_scale_factor, num_levels, B, m_cap, shared_landmarks, dist_mode, ray_test, line_dist_mode,
+                          {k: D(v) for k, v in ptrs.items()})
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check((lib().plp_project_landmark_lines_device if lines else lib().plp_project_landmarks_device)(self._h, C.byref(a), st))
+
+    def project_landmarks_device(self, camera, B, m_cap, pose, pos_w, min_valid_dist, max_valid_dist, out_valid, out_reproj_d=None, out_reproj=None,
+                                 obs_mean_normal=None, skip=None, counts=None, out_x_right=None, out_level=None, out_status=None, out_num_valid=None,
+                                 shared_landmarks=False, dist_mode=PROJECT_DIST_CENTER, ray_test=None, log_scale_factor=None, num_levels=8,
+                                 img_bounds=None, stream=None):
+        """plp_project_landmarks_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous.  The outputs
+        are the q_valid / q_reproj_d / q_reproj / q_x_right / q_level of match_device."""
+        lsf = np.float32(math.log(np.float32(1.2))) if log_scale_factor is None else log_scale_factor
+        rt = (obs_mean_normal is not None) if ray_test is None else ray_test
+        self._project_device(False, camera, B, m_cap, dict(
+            pose=pose, counts=counts, pos_w=pos_w, obs_mean_normal=obs_mean_normal, min_valid_dist=min_valid_dist, max_valid_dist=max_valid_dist,
+            skip=skip, out_reproj_d=out_reproj_d, out_reproj=out_reproj, out_x_right=out_x_right, out_level=out_level, out_valid=out_valid,
+            out_status=out_status, out_num_valid=out_num_valid), shared_landmarks, dist_mode, rt, 0, lsf, num_levels, img_bounds, stream)
+
+    def project_landmark_lines_device(self, camera, B, m_cap, pose, pos_w, min_valid_dist, max_valid_dist, out_valid, out_reproj_sp_d=None,
+                                      out_reproj_ep_d=None, out_reproj_sp=None, out_reproj_ep=None, skip=None, counts=None, out_x_right_sp=None,
+                                      out_x_right_ep=None, out_level=None, out_status=None, out_num_valid=None, shared_landmarks=False,
+                                      line_dist_mode=PROJECT_LINE_ENDPOINTS, log_scale_factor=None, num_levels=2, img_bounds=None, stream=None):
+        """plp_project_landmark_lines_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        lsf = np.float32(math.log(np.float32(2.0))) if log_scale_factor is None else log_scale_factor
+        self._project_device(True, camera, B, m_cap, dict(
+            pose=pose, counts=counts, pos_w=pos_w, min_valid_dist=min_valid_dist, max_valid_dist=max_valid_dist, skip=skip,
+            out_reproj_d=out_reproj_sp_d, out_reproj2_d=out_reproj_ep_d, out_reproj=out_reproj_sp, out_reproj2=out_reproj_ep,
+            out_x_right=out_x_right_sp, out_x_right2=out_x_right_ep, out_level=out_level, out_valid=out_valid, out_status=out_status,
+            out_num_valid=out_num_valid), shared_landmarks, PROJECT_DIST_CENTER, False, line_dist_mode, lsf, num_levels, img_bounds, stream)
 
     # ---- stereo key lines: the association of the stereo constructors (frame.cc:389-427) and triangulate_stereo_for_line (frame.cc:953-1123)
     def stereo_keylines(self, keylines_left, keylines_right, train_idx, dist, counts_left=None, counts_right=None, out=None):

@@ -699,6 +699,109 @@ plp_status plp_project_last_frame_host(plp_matcher* c, const plp_last_frame_args
 plp_status plp_project_last_frame_lines_device(plp_matcher* c, const plp_last_frame_args* a, void* hip_stream) { return last_frame_device(c, a, true, hip_stream); }
 plp_status plp_project_last_frame_lines_host(plp_matcher* c, const plp_last_frame_args* a) { return last_frame_host(c, a, true); }
 
+// ---- fuse, Sim3 and relocalisation queries (include/plp_front.h: plp_project_landmark[_line]s_*; kernels in project_kernels.hip)
+namespace {
+plp_status project_check(plp_matcher* c, const plp_project_args* a, bool lines) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, false)) return s;
+    if (a->B <= 0 || a->m_cap < 0 || a->num_levels <= 0) return set_error(PLP_ERR_INVALID_ARG, "B and num_levels must be positive, m_cap non-negative");
+    if (!a->pose || !a->pos_w || !a->min_valid_dist || !a->max_valid_dist || !a->out_valid)
+        return set_error(PLP_ERR_INVALID_ARG, "pose, pos_w, min_valid_dist, max_valid_dist, out_valid are required");
+    if (!a->out_reproj_d && !a->out_reproj) return set_error(PLP_ERR_INVALID_ARG, "one of out_reproj_d and out_reproj is required");
+    if (a->dist_mode != PLP_PROJECT_DIST_CENTER && a->dist_mode != PLP_PROJECT_DIST_CAMERA) return set_error(PLP_ERR_INVALID_ARG, "unknown dist_mode");
+    if (lines) {
+        if (a->line_dist_mode != PLP_PROJECT_LINE_ENDPOINTS && a->line_dist_mode != PLP_PROJECT_LINE_MIDPOINT)
+            return set_error(PLP_ERR_INVALID_ARG, "unknown line_dist_mode");
+        if (a->dist_mode != PLP_PROJECT_DIST_CENTER || a->ray_test) return set_error(PLP_ERR_INVALID_ARG, "lines take PLP_PROJECT_DIST_CENTER and no ray_test");
+        if ((a->out_reproj_d && !a->out_reproj2_d) || (a->out_reproj && !a->out_reproj2))
+            return set_error(PLP_ERR_INVALID_ARG, "lines need the end-point array of every start-point array (out_reproj2_d, out_reproj2)");
+    } else if (a->ray_test && (!a->obs_mean_normal || a->dist_mode != PLP_PROJECT_DIST_CENTER)) {
+        return set_error(PLP_ERR_INVALID_ARG, "ray_test needs obs_mean_normal and PLP_PROJECT_DIST_CENTER");
+    }
+    if (a->B > 65535) return set_error(PLP_ERR_UNSUPPORTED, "more than 65535 problems in one call");
+    return PLP_OK;
+}
+
+ProjectArgs project_args(const plp_project_args* a, bool lines) {
+    ProjectArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.model = cm.model;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    A.log_sf = a->log_scale_factor; A.num_levels = a->num_levels; A.m_cap = a->m_cap;
+    A.shared = a->shared_landmarks ? 1 : 0; A.dist_mode = a->dist_mode; A.ray_test = (!lines && a->ray_test) ? 1 : 0; A.line_dist_mode = a->line_dist_mode;
+    A.pose = a->pose; A.counts = a->counts; A.pos_w = a->pos_w; A.normal = (!lines && a->ray_test) ? a->obs_mean_normal : nullptr;
+    A.min_dist = a->min_valid_dist; A.max_dist = a->max_valid_dist; A.skip = a->skip;
+    A.reproj_d = a->out_reproj_d; A.reproj2_d = (lines && a->out_reproj_d) ? a->out_reproj2_d : nullptr;
+    A.reproj = a->out_reproj; A.reproj2 = (lines && a->out_reproj) ? a->out_reproj2 : nullptr;
+    A.x_right = a->out_x_right; A.x_right2 = lines ? a->out_x_right2 : nullptr;
+    A.level = a->out_level; A.valid = a->out_valid; A.status = a->out_status; A.num_valid = a->out_num_valid;
+    return A;
+}
+
+plp_status project_device(plp_matcher* c, const plp_project_args* a, bool lines, void* hip_stream) {
+    if (plp_status s = project_check(c, a, lines)) return s;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (a->m_cap == 0) {   // no landmark slot: the reference's loop does not run
+        if (a->out_num_valid) PLP_HIP(hipMemsetAsync(a->out_num_valid, 0, (size_t)a->B * 4, st));
+        return PLP_OK;
+    }
+    const ProjectArgs A = project_args(a, lines);
+    PLP_HIP(lines ? launch_project_lines(st, A, a->B) : launch_project_points(st, A, a->B));
+    return PLP_OK;
+}
+
+// host pointers, staged as observe_host stages them (the outputs first, so that unwritten slots come back as the caller holds them)
+plp_status project_host(plp_matcher* c, const plp_project_args* a, bool lines) {
+    if (plp_status s = project_check(c, a, lines)) return s;
+    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
+    if (M == 0) {
+        if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
+        return PLP_OK;
+    }
+    const ProjectArgs H = project_args(a, lines);   // which arrays take part (host pointers)
+    const size_t LM = H.shared ? M : BM;            // rows of the landmark tables
+    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
+    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
+    Part parts[] = {
+        {H.pose, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0}, {H.pos_w, nullptr, LM * (lines ? 6 : 3) * 8, 0},
+        {H.normal, nullptr, LM * 3 * 8, 0}, {H.min_dist, nullptr, LM * 4, 0}, {H.max_dist, nullptr, LM * 4, 0}, {H.skip, nullptr, BM, 0},
+        {nullptr, H.reproj_d, BM * 16, 0}, {nullptr, H.reproj2_d, BM * 16, 0}, {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0},
+        {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.x_right2, BM * 4, 0}, {nullptr, H.level, BM * 4, 0}, {nullptr, H.valid, BM, 0},
+        {nullptr, H.status, BM, 0}, {nullptr, H.num_valid, B * 4, 0}};
+    size_t tot = 0;
+    for (Part& p : parts)
+        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    PLP_HIP(c->stage.reserve(tot));
+    uint8_t* base = (uint8_t*)c->stage.p;
+    for (const Part& p : parts)
+        if (p.src || p.dst) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
+    ProjectArgs A = H;
+    A.pose = (const double*)dev(0); A.counts = (const int32_t*)dev(1); A.pos_w = (const double*)dev(2); A.normal = (const double*)dev(3);
+    A.min_dist = (const float*)dev(4); A.max_dist = (const float*)dev(5); A.skip = (const uint8_t*)dev(6);
+    A.reproj_d = (double*)dev(7); A.reproj2_d = (double*)dev(8); A.reproj = (float*)dev(9); A.reproj2 = (float*)dev(10);
+    A.x_right = (float*)dev(11); A.x_right2 = (float*)dev(12); A.level = (int32_t*)dev(13); A.valid = (uint8_t*)dev(14);
+    A.status = (uint8_t*)dev(15); A.num_valid = (int32_t*)dev(16);
+    PLP_HIP(lines ? launch_project_lines(st, A, a->B) : launch_project_points(st, A, a->B));
+    for (const Part& p : parts)
+        if (p.dst) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
+    PLP_HIP(hipStreamSynchronize(st));
+    return PLP_OK;
+}
+}  // namespace
+
+plp_status plp_project_landmarks_device(plp_matcher* c, const plp_project_args* a, void* hip_stream) { return project_device(c, a, false, hip_stream); }
+plp_status plp_project_landmarks_host(plp_matcher* c, const plp_project_args* a) { return project_host(c, a, false); }
+plp_status plp_project_landmark_lines_device(plp_matcher* c, const plp_project_args* a, void* hip_stream) { return project_device(c, a, true, hip_stream); }
+plp_status plp_project_landmark_lines_host(plp_matcher* c, const plp_project_args* a) { return project_host(c, a, true); }
+
 // ---- stereo key lines (include/plp_front.h: plp_stereo_keylines_*, plp_keylines_3d_*; kernels in stereo_line_kernels.hip)
 namespace {
 plp_status stereo_keylines_check(plp_matcher* c, const plp_stereo_keylines_args* a) {

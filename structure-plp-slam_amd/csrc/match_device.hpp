@@ -134,6 +134,24 @@ hipError_t launch_observe_points(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_observe_lines(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_last_frame_points(hipStream_t st, const ObserveArgs& A, int B);
 hipError_t launch_last_frame_lines(hipStream_t st, const ObserveArgs& A, int B);
+// fuse, Sim3 and relocalisation queries (project_kernels.hip, plp_project_landmark[_line]s_*); the camera fields are named as ObserveArgs
+// names them: reproject<MODEL> (reproject.hpp) reads either
+struct ProjectArgs {
+    int model;
+    double fx, fy, cx, cy, fxb;
+    double cols_d, rows_d;
+    float bounds[4];
+    float log_sf;
+    int num_levels, m_cap;
+    int shared, dist_mode, ray_test, line_dist_mode;
+    const double* pose; const int32_t* counts; const double* pos_w; const double* normal;
+    const float* min_dist; const float* max_dist; const uint8_t* skip;
+    double* reproj_d; double* reproj2_d; float* reproj; float* reproj2; float* x_right; float* x_right2;
+    int32_t* level; uint8_t* valid; uint8_t* status; int32_t* num_valid;
+};
+// both return the first error of their calls (the points launcher zeroes num_valid before its kernel adds to it)
+hipError_t launch_project_points(hipStream_t st, const ProjectArgs& A, int B);
+hipError_t launch_project_lines(hipStream_t st, const ProjectArgs& A, int B);
 // stereo key-line association (plp_stereo_keylines_*, stereo_line_kernels.hip): left / right key lines, the 1-NN result (left = query)
 struct StereoKeylineArgs {
     int cap_l, cap_r;
