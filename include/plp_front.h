@@ -241,6 +241,11 @@ plp_status plp_seed_introsort_debug(int32_t device, uint32_t* entries, int64_t n
 /* Host model of the LSD gradient kernel's (float)cos((double)a), (float)sin((double)a) fast path (csrc/sincos_ziv.hpp): proven[i] = 0 marks the
  * arguments for which the kernel falls back to the general f64 routine.  Returns the number of proven arguments.  No GPU needed. */
 int32_t plp_model_sincos_host(const float* a, int64_t n, float* c, float* s, uint8_t* proven);
+/* Host build of the null vector the point triangulation uses (csrc/null4.hpp): for n row-major 4 x 4 matrices
+ * A[16 i ..], out_v[4 i ..] = the column of V of the cyclic one-sided Jacobi whose column of A V has the smallest squared norm (ties: the
+ * lowest index; sign unspecified), out_sweeps[i] (may be NULL) = the sweeps that rotated, 30 = the limit was reached.  The device runs the
+ * same source.  No GPU needed.  Returns n, or -1 for a bad argument. */
+int32_t plp_model_null_vector4_host(const double* A, int32_t n, double* out_v, int32_t* out_sweeps);
 plp_status plp_line_scaled_size(const plp_line* ctx, int32_t* rows, int32_t* cols);
 /* Diagnostics of frame 0 of the last batch, 12 values.  One wave per frame: shader cycles {whole wave, region_grow, region2rect, refine},
  * regions grown, pixels grown, 0 x 6.  Several waves per frame, the main wave's view: cycles {whole, waiting for helpers, growing regions
@@ -888,6 +893,99 @@ typedef struct plp_keyline_pairs_args {
  * synchronous. */
 plp_status plp_triangulate_keyline_pairs_device(plp_matcher* ctx, const plp_keyline_pairs_args* args, void* hip_stream);
 plp_status plp_triangulate_keyline_pairs_host(plp_matcher* ctx, const plp_keyline_pairs_args* args);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Key-frame pair point triangulation: the point half of mapping_module::create_new_landmarks (src/PLPSLAM/mapping_module.cc:359-479)
+ * around PLP_MATCH_MODE_TRIANGULATION.  Numeric contract: DESIGN.md section 5, D10.
+ *
+ * In front of the matcher, per pair (kf1 = cur, kf2 = ngh) of a table of F key frames:
+ *   out_baseline = |cam_center(kf2) - cam_center(kf1)|, sqrt((dx dx + dy dy) + dz dz)                                    :382-383
+ *   out_skip     = the `continue` of :386-402: monocular (setup_type 0)  out_baseline < 0.02 * (double)median_depth[kf2],
+ *                  stereo / RGB-D  out_baseline < true_baseline
+ *   out_epipolar = the 12 doubles of plp_match_args.epipolar: E_12 = create_E_21(rot_2w, trans_2w, rot_1w, trans_1w) row-major
+ *                  (solve/essential_solver.cc:188-194, call at :429), then camera::*::reproject_to_bearing(rot_2w, trans_2w, cam_center_1)
+ *                  (match/robust.cc:50-55).  robust.cc ignores that function's return value: for perspective and fisheye with z <= 0 the
+ *                  vector is the UN-NORMALISED rot_2w cam_center_1 + trans_2w, as the reference leaves it.
+ * All three are written for every pair, skipped or not. */
+typedef struct plp_keyframe_pair_geometry_args {
+    plp_camera_model camera;        /* model is read (the epipole's normalisation) */
+    int32_t setup_type;             /* camera::setup_type_t: 0 monocular, 1 stereo, 2 RGB-D */
+    double true_baseline;           /* camera::base true_baseline_ (stereo / RGB-D gate) */
+    int32_t F, P;                   /* F > 0 key frames, P >= 0 pairs */
+    const double* pose;             /* F x 15: the plp_observe_args.pose row */
+    const float* median_depth;      /* F: compute_median_depth(true) (plp_median_depth_*'s out_median); read for a monocular setup only */
+    const int32_t* pairs;           /* P x 2: kf1, kf2 */
+    uint8_t* out_skip;              /* P */
+    double* out_epipolar;           /* P x 12 */
+    double* out_baseline;           /* P */
+} plp_keyframe_pair_geometry_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args, the camera as for plp_post_extract_model_*, setup_type
+ * outside 0..2, F <= 0, P < 0, and -- when P > 0 -- a NULL pose, pairs or output, a NULL median_depth with a monocular setup.  P == 0:
+ * PLP_OK, nothing written.  _host additionally checks that every kf1 / kf2 is inside [0, F); on the _device path that is a precondition
+ * (a pair outside the table is left unwritten).
+ * _device: DEVICE pointers, one kernel on hip_stream, no host synchronisation.  _host: HOST pointers, staged (the outputs too), the same
+ * kernel, synchronous. */
+plp_status plp_keyframe_pair_geometry_device(plp_matcher* ctx, const plp_keyframe_pair_geometry_args* args, void* hip_stream);
+plp_status plp_keyframe_pair_geometry_host(plp_matcher* ctx, const plp_keyframe_pair_geometry_args* args);
+
+/* Behind the matcher: module::two_view_triangulator::triangulate (module/two_view_triangulator.cc:45-122, .h:114-137) for every match of
+ * every pair, with solve::triangulator::triangulate (solve/triangulator.h:105-119; the null vector as D10 defines it) and
+ * keyframe::triangulate_stereo (data/keyframe.cc:589-640).  Per pair p and key point t < counts[kf2] of key frame 2, out_status says
+ * where the reference leaves the iteration, in its order of evaluation: */
+typedef enum plp_keypoint_pair_status {
+    PLP_KPP_CREATED = 0,        /* triangulate returned true: the reference creates the landmark (out_idx_1, out_pos_w)                 */
+    PLP_KPP_PAIR_SKIPPED = 1,   /* pair_skip[p]: the pair never reaches the matcher (mapping_module.cc:386-402)                         */
+    PLP_KPP_NO_MATCH = 2,       /* match_q[p][t] is -1 or outside [0, m_cap)                                                            */
+    PLP_KPP_NO_PARALLAX = 3,    /* none of the three ways to a position applies                             two_view_triangulator.cc:93-96 */
+    PLP_KPP_DEPTH = 4,          /* behind one of the two cameras (never for equirectangular)                                      :99-102 */
+    PLP_KPP_REPROJ_1 = 5,       /* check_reprojection_error in key frame 1                                                        :105-106 */
+    PLP_KPP_REPROJ_2 = 6,       /* ... in key frame 2                                                                            :107-108 */
+    PLP_KPP_SCALE = 7,          /* check_scale_factors                                                                           :114-119 */
+    PLP_KPP_NON_FINITE = 8,     /* v[3] == 0, a non-finite position or reprojection error (undefined in the -ffast-math reference): no landmark */
+    PLP_KPP_INDEX_RANGE = 9     /* idx_1 outside [0, counts[kf1]), where undist_keypts_.at(idx_1) throws                             :47 */
+} plp_keypoint_pair_status;
+typedef struct plp_keypoint_pairs_args {
+    plp_camera_model camera;        /* all three models for a monocular setup; perspective and fisheye for stereo / RGB-D */
+    int32_t setup_type;             /* 0 monocular: x_right and depths are not read (every stereo_x_right_ is -1); 1 stereo, 2 RGB-D */
+    double true_baseline;           /* camera::base true_baseline_ (the stereo parallax) */
+    const float* scale_factors;     /* HOST, num_levels: keyframe::scale_factors_, read at keypoint.octave */
+    const float* level_sigma_sq;    /* HOST, num_levels: keyframe::level_sigma_sq_ */
+    int32_t num_levels;             /* 1 .. 16; an octave outside [0, num_levels), where the reference's at() throws, is clamped */
+    float scale_factor;             /* keyframe::scale_factor_ of both key frames: ratio_factor_ = 2.0f * scale_factor */
+    float rays_parallax_deg_thr;    /* 1.0 (mapping_module.cc:436); cos_rays_parallax_thr_ = (float)cos(thr * M_PI / 180.0) is formed on the host */
+    int32_t F, cap, m_cap, P;       /* F > 0 key frames of 0 <= cap <= 8192 key-point slots; m_cap > 0 query slots per pair; P >= 0 pairs */
+    const plp_keypoint* keypts;     /* F x cap: undist_keypts_ (pt, octave) */
+    const double* bearings;         /* F x cap x 3: bearings_ */
+    const float* x_right;           /* F x cap: stereo_x_right_ (stereo / RGB-D) */
+    const float* depths;            /* F x cap: depths_ (stereo / RGB-D) */
+    const int32_t* counts;          /* F: num_keypts_, or NULL = cap everywhere */
+    const double* pose;             /* F x 15: the plp_observe_args.pose row */
+    const int32_t* pairs;           /* P x 2: kf1 (cur), kf2 (ngh) */
+    const int32_t* match_q;         /* P x cap: plp_match_* out_match of the pair's TRIANGULATION problem (the query slot per key point of
+                                       key frame 2, -1 = none); each query slot appears at most once per row */
+    const int32_t* q_feature;       /* P x m_cap: the key-point index in key frame 1 of every query slot (the BoW node order of the
+                                       matcher's queries); NULL = identity */
+    const uint8_t* pair_skip;       /* P or NULL: plp_keyframe_pair_geometry_*'s out_skip */
+    int32_t* out_idx_1;             /* P x cap: idx_1 of the match at key point t (also where the triangulation failed), -1 = NO_MATCH */
+    double* out_pos_w;              /* P x cap x 3: pos_w where CREATED, zero elsewhere */
+    uint8_t* out_status;            /* P x cap: a plp_keypoint_pair_status */
+    uint8_t* occupied_1_io;         /* P x cap or NULL, in place: the byte at idx_1 becomes 1 for every CREATED (cur_keyfrm->add_landmark :464) */
+    uint8_t* occupied_2_io;         /* P x cap or NULL, in place: the byte at t becomes 1 for every CREATED (ngh_keyfrm->add_landmark :465) */
+} plp_keypoint_pairs_args;
+/* Slots t >= counts[kf2] are neither read nor written.  A pair with pair_skip[p] != 0 gets PLP_KPP_PAIR_SKIPPED in out_status and nothing
+ * else: out_idx_1, out_pos_w and the occupancy keep the caller's values.  Every other slot gets all three outputs; occupied_*_io change
+ * only where a landmark is created.
+ * Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args, the camera as for plp_post_extract_model_*, setup_type outside
+ * 0..2, num_levels outside 1..16, F <= 0, cap < 0, m_cap <= 0, P < 0, a NULL scale_factors / level_sigma_sq, and -- when P > 0 and cap > 0 --
+ * a NULL keypts, bearings, pose, pairs, match_q or output, a NULL x_right or depths with a stereo or RGB-D setup.  A stereo or RGB-D setup
+ * with the equirectangular camera, where the reference throws (keyframe.cc:637), cap > 8192 or P x max(cap, m_cap) > 2^31: PLP_ERR_UNSUPPORTED.
+ * cap == 0 or P == 0: PLP_OK, nothing written.  _host additionally checks that every kf1 / kf2 is inside [0, F); on the _device path that
+ * is a precondition (a pair outside the table is left unwritten).
+ * _device: every array but scale_factors / level_sigma_sq a DEVICE pointer; one kernel on hip_stream, no host synchronisation.
+ * _host: HOST pointers, staged (the outputs and the occupancy too, so that every slot the kernel does not write keeps the caller's value),
+ * the same kernel, synchronous. */
+plp_status plp_triangulate_keypoint_pairs_device(plp_matcher* ctx, const plp_keypoint_pairs_args* args, void* hip_stream);
+plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* ctx, const plp_keypoint_pairs_args* args);
 
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the

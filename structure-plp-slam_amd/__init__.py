@@ -71,6 +71,7 @@ _API = [
     ("plp_model_quadtree_host", _I32, [_VP, _I32, _I32, _I32, C.c_uint32, _VP]),
     ("plp_model_sincos_host", _I32, [_VP, C.c_int64, _VP, _VP, _VP]),
     ("plp_model_index_sort_host", _I32, [_VP, _I32, _I32, _VP]),
+    ("plp_model_null_vector4_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_line_create", C.c_int, [C.c_int, _VP]),
     ("plp_line_destroy", None, [_VP]),
     ("plp_line_extract", C.c_int, [_VP, _VP, _I32, _I32, _SZ, _VP, _VP, _VP, _I32, _VP]),
@@ -130,6 +131,10 @@ _API = [
     ("plp_median_depth_host", C.c_int, [_VP, _VP]),
     ("plp_triangulate_keyline_pairs_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_triangulate_keyline_pairs_host", C.c_int, [_VP, _VP]),
+    ("plp_keyframe_pair_geometry_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_keyframe_pair_geometry_host", C.c_int, [_VP, _VP]),
+    ("plp_triangulate_keypoint_pairs_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_triangulate_keypoint_pairs_host", C.c_int, [_VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -218,6 +223,17 @@ def model_sincos(a):
     c = np.zeros(a.shape, np.float32); s = np.zeros(a.shape, np.float32); ok = np.zeros(a.shape, np.uint8)
     lib().plp_model_sincos_host(_p(a), a.size, _p(c), _p(s), _p(ok))
     return c, s, ok.astype(bool)
+
+
+def model_null_vector4(A):
+    """Host build of the null vector of the point triangulation (csrc/null4.hpp; no GPU needed).  A: (n, 4, 4) or
+    (4, 4) f64.  Returns (v (n, 4) f64, sweeps (n,) i32): the column of V with the smallest |A v|, and the sweeps that rotated (30 = limit)."""
+    A = np.ascontiguousarray(A, np.float64)
+    single = A.ndim == 2
+    A = A.reshape(-1, 16)
+    v = np.zeros((len(A), 4), np.float64); sw = np.zeros(len(A), np.int32)
+    assert lib().plp_model_null_vector4_host(_p(A), len(A), _p(v), _p(sw)) == len(A)
+    return (v[0], int(sw[0])) if single else (v, sw)
 
 
 class orb_extractor:
@@ -721,6 +737,27 @@ class keyline_pairs_args_c(C.Structure):
  KLP_TOO_LONG, KLP_DEPTH, KLP_REPROJ_MID, KLP_REPROJ_END, KLP_SCALE, KLP_NON_FINITE, KLP_KP_DEPTH_RANGE) = range(15)
 KLP_MAPPING = dict(dist_thr=50.0, endpoint_thr=400.0, angle_thr=20.0, skip_occupied=1)       # mapping_module.cc:506, :529, :564
 KLP_INITIALIZER = dict(dist_thr=30.0, endpoint_thr=200.0, angle_thr=5.0, skip_occupied=0)    # module/initializer.cc:585-667
+
+
+class pair_geometry_args_c(C.Structure):
+    """plp_keyframe_pair_geometry_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double), ("F", C.c_int32), ("P", C.c_int32),
+                ("pose", _VP), ("median_depth", _VP), ("pairs", _VP), ("out_skip", _VP), ("out_epipolar", _VP), ("out_baseline", _VP)]
+
+
+class keypoint_pairs_args_c(C.Structure):
+    """plp_keypoint_pairs_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
+                ("scale_factors", _VP), ("level_sigma_sq", _VP), ("num_levels", C.c_int32), ("scale_factor", C.c_float),
+                ("rays_parallax_deg_thr", C.c_float), ("F", C.c_int32), ("cap", C.c_int32), ("m_cap", C.c_int32), ("P", C.c_int32),
+                ("keypts", _VP), ("bearings", _VP), ("x_right", _VP), ("depths", _VP), ("counts", _VP), ("pose", _VP), ("pairs", _VP),
+                ("match_q", _VP), ("q_feature", _VP), ("pair_skip", _VP),
+                ("out_idx_1", _VP), ("out_pos_w", _VP), ("out_status", _VP), ("occupied_1_io", _VP), ("occupied_2_io", _VP)]
+
+
+# plp_keypoint_pair_status: where the reference leaves an iteration of triangulate_with_two_keyframes
+(KPP_CREATED, KPP_PAIR_SKIPPED, KPP_NO_MATCH, KPP_NO_PARALLAX, KPP_DEPTH, KPP_REPROJ_1, KPP_REPROJ_2, KPP_SCALE, KPP_NON_FINITE,
+ KPP_INDEX_RANGE) = range(10)
 
 
 def _struct(cls, fields, ptrs):
@@ -1369,6 +1406,111 @@ class matcher:
                                           dist_thr, endpoint_thr, angle_thr, skip_occupied)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_triangulate_keyline_pairs_device(self._h, C.byref(a), st))
+        del keep
+
+    def keyframe_pair_geometry(self, camera, setup_type, pose, pairs, median_depth=None, true_baseline=0.0, out=None):
+        """What create_new_landmarks computes per neighbour in front of match_for_triangulation (plp_keyframe_pair_geometry_host): pose (F, 15),
+        pairs (P, 2) = (cur, ngh), median_depth (F,) f32 (monocular).  Returns dict(skip (P,) u8, epipolar (P, 12) f64, baseline (P,) f64);
+        out: arrays to write into (slots the kernel does not write keep their values)."""
+        po = np.ascontiguousarray(pose, np.float64).reshape(-1, 15)
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        F, Pn = len(po), len(pr)
+        md = None if median_depth is None else np.ascontiguousarray(median_depth, np.float32).reshape(F)
+        o = {}
+        for k, shape, dt in (("skip", (Pn,), np.uint8), ("epipolar", (Pn, 12), np.float64), ("baseline", (Pn,), np.float64)):
+            v = None if out is None else out.get(k)
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            o[k] = v if v is not None else np.zeros(shape, dt)
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(pair_geometry_args_c, dict(F=F, P=Pn, setup_type=int(setup_type), true_baseline=float(true_baseline)), dict(
+            pose=P(po), median_depth=P(md), pairs=P(pr), out_skip=P(o["skip"]), out_epipolar=P(o["epipolar"]), out_baseline=P(o["baseline"])))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        _check(lib().plp_keyframe_pair_geometry_host(self._h, C.byref(a)))
+        return o
+
+    def keyframe_pair_geometry_device(self, camera, setup_type, F, P, pose, pairs, out_skip, out_epipolar, out_baseline, median_depth=None,
+                                      true_baseline=0.0, stream=None):
+        """plp_keyframe_pair_geometry_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(pair_geometry_args_c, dict(F=int(F), P=int(P), setup_type=int(setup_type), true_baseline=float(true_baseline)), dict(
+            pose=D(pose), median_depth=D(median_depth), pairs=D(pairs), out_skip=D(out_skip), out_epipolar=D(out_epipolar),
+            out_baseline=D(out_baseline)))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_keyframe_pair_geometry_device(self._h, C.byref(a), st))
+
+    @staticmethod
+    def _keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr):
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        ls = np.ascontiguousarray(level_sigma_sq, np.float32)
+        if sf.shape != ls.shape or sf.ndim != 1:
+            raise PlpError(PLP_ERR_INVALID_ARG, "scale_factors and level_sigma_sq must be vectors of the same length")
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        a.setup_type, a.true_baseline = int(setup_type), float(true_baseline)
+        a.scale_factors, a.level_sigma_sq, a.num_levels = sf.ctypes.data, ls.ctypes.data, len(sf)
+        a.scale_factor = float(sf[1]) if scale_factor is None and len(sf) > 1 else float(1.0 if scale_factor is None else scale_factor)
+        a.rays_parallax_deg_thr = float(rays_parallax_deg_thr)
+        return sf, ls                                          # kept alive by the caller until the call has returned
+
+    def triangulate_keypoint_pairs(self, camera, setup_type, keypts, bearings, pose, pairs, match_q, scale_factors, level_sigma_sq,
+                                   x_right=None, depths=None, counts=None, q_feature=None, m_cap=None, pair_skip=None, occupied_1=None,
+                                   occupied_2=None, true_baseline=0.0, scale_factor=None, rays_parallax_deg_thr=1.0, out=None):
+        """two_view_triangulator::triangulate for every match of every pair (plp_triangulate_keypoint_pairs_host).  Per key frame, leading
+        dimension F: keypts (F, cap) KP_DTYPE, bearings (F, cap, 3), x_right / depths (F, cap), counts (F,), pose (F, 15).  Per pair: pairs
+        (P, 2) = (cur, ngh), match_q (P, cap) = the matcher's out_match, q_feature (P, m_cap) or None = identity (then m_cap defaults to cap),
+        pair_skip (P,), occupied_1 / occupied_2 (P, cap) u8: updated IN PLACE when they are C-contiguous uint8 arrays.  Returns dict(idx_1
+        (P, cap) i32, pos_w (P, cap, 3) f64, status (P, cap) u8, occupied_1, occupied_2); slots the kernel does not write keep -1 / 0 / 0, or
+        out[name]."""
+        kp = np.ascontiguousarray(keypts, KP_DTYPE)
+        if kp.ndim != 2:
+            raise PlpError(PLP_ERR_INVALID_ARG, "keypts must be (F, cap)")
+        F, M = kp.shape
+        pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        Pn = len(pr)
+        be = np.ascontiguousarray(bearings, np.float64).reshape(F, M, 3)
+        po = np.ascontiguousarray(pose, np.float64).reshape(F, 15)
+        mq = np.ascontiguousarray(match_q, np.int32).reshape(Pn, M)
+        qf = None if q_feature is None else np.ascontiguousarray(q_feature, np.int32).reshape(Pn, -1)
+        Q = int(m_cap) if m_cap is not None else (M if qf is None else qf.shape[1])
+        xr = None if x_right is None else np.ascontiguousarray(x_right, np.float32).reshape(F, M)
+        de = None if depths is None else np.ascontiguousarray(depths, np.float32).reshape(F, M)
+        cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+        sk = None if pair_skip is None else np.ascontiguousarray(pair_skip, np.uint8).reshape(Pn)
+        o1 = None if occupied_1 is None else np.ascontiguousarray(occupied_1, np.uint8).reshape(Pn, M)
+        o2 = None if occupied_2 is None else np.ascontiguousarray(occupied_2, np.uint8).reshape(Pn, M)
+        o = {}
+        for k, shape, dt, fill in (("idx_1", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 3), np.float64, 0), ("status", (Pn, M), np.uint8, 0)):
+            v = None if out is None else out.get(k)
+            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+            o[k] = v if v is not None else np.full(shape, fill, dt)
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(keypoint_pairs_args_c, dict(F=F, cap=M, m_cap=Q, P=Pn), dict(
+            keypts=P(kp), bearings=P(be), x_right=P(xr), depths=P(de), counts=P(cn), pose=P(po), pairs=P(pr), match_q=P(mq), q_feature=P(qf),
+            pair_skip=P(sk), out_idx_1=P(o["idx_1"]), out_pos_w=P(o["pos_w"]), out_status=P(o["status"]), occupied_1_io=P(o1),
+            occupied_2_io=P(o2)))
+        keep = self._keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr)
+        _check(lib().plp_triangulate_keypoint_pairs_host(self._h, C.byref(a)))
+        del keep
+        return dict(occupied_1=o1, occupied_2=o2, **o)
+
+    def triangulate_keypoint_pairs_device(self, camera, setup_type, F, cap, m_cap, P, keypts, bearings, pose, pairs, match_q, out_idx_1,
+                                          out_pos_w, out_status, scale_factors, level_sigma_sq, x_right=None, depths=None, counts=None,
+                                          q_feature=None, pair_skip=None, occupied_1_io=None, occupied_2_io=None, true_baseline=0.0,
+                                          scale_factor=None, rays_parallax_deg_thr=1.0, stream=None):
+        """plp_triangulate_keypoint_pairs_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors
+        and level_sigma_sq are host vectors); asynchronous, one kernel on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(keypoint_pairs_args_c, dict(F=int(F), cap=int(cap), m_cap=int(m_cap), P=int(P)), dict(
+            keypts=D(keypts), bearings=D(bearings), x_right=D(x_right), depths=D(depths), counts=D(counts), pose=D(pose), pairs=D(pairs),
+            match_q=D(match_q), q_feature=D(q_feature), pair_skip=D(pair_skip), out_idx_1=D(out_idx_1), out_pos_w=D(out_pos_w),
+            out_status=D(out_status), occupied_1_io=D(occupied_1_io), occupied_2_io=D(occupied_2_io)))
+        keep = self._keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_triangulate_keypoint_pairs_device(self._h, C.byref(a), st))
         del keep
 
     def lbd_match_1nn(self, query_lbd, train_lbd):

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "line_device.hpp"
+#include "null4.hpp"
 #include "seed_sort_model.hpp"
 #include "sincos_ziv.hpp"
 #include "plp_common.hpp"
@@ -464,6 +465,17 @@ int32_t plp_model_sincos_host(const float* a, int64_t n, float* c, float* s, uin
     int32_t n_proven = 0;
     for (int64_t i = 0; i < n; ++i) { proven[i] = plp::sincos_ziv(a[i], c + i, s + i) ? 1 : 0; n_proven += proven[i]; }
     return n_proven;
+}
+
+// Host build of csrc/null4.hpp, the null vector of the point triangulation, callable without a GPU
+int32_t plp_model_null_vector4_host(const double* A, int32_t n, double* out_v, int32_t* out_sweeps) {
+    if (!A || !out_v || n < 0) return -1;
+    for (int32_t i = 0; i < n; ++i) {
+        int sweeps = 0;
+        plp::null_vector4(A + 16 * (size_t)i, out_v + 4 * (size_t)i, &sweeps);
+        if (out_sweeps) out_sweeps[i] = sweeps;
+    }
+    return n;
 }
 
 // Host model of the exact seed sort (seed_sort_model.hpp): std::__introsort_loop on entries whose key is bits 20..29, as the rank-paired

@@ -1099,6 +1099,144 @@ plp_status plp_triangulate_keyline_pairs_host(plp_matcher* c, const plp_keyline_
     return stage_back(c, parts, np, base);
 }
 
+// ---- key-frame pair point triangulation (include/plp_front.h: plp_keyframe_pair_geometry_*, plp_triangulate_keypoint_pairs_*; keypoint_pair_kernels.hip)
+namespace {
+plp_status pair_geometry_check(plp_matcher* c, const plp_keyframe_pair_geometry_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, false)) return s;
+    if (a->setup_type < 0 || a->setup_type > 2) return set_error(PLP_ERR_INVALID_ARG, "setup_type must be 0, 1 or 2");
+    if (a->F <= 0 || a->P < 0) return set_error(PLP_ERR_INVALID_ARG, "F must be positive, P non-negative");
+    if (a->P == 0) return PLP_OK;
+    if (!a->pose || !a->pairs || !a->out_skip || !a->out_epipolar || !a->out_baseline)
+        return set_error(PLP_ERR_INVALID_ARG, "pose, pairs, out_skip, out_epipolar, out_baseline are required");
+    if (a->setup_type == 0 && !a->median_depth) return set_error(PLP_ERR_INVALID_ARG, "median_depth is required for a monocular setup");
+    return PLP_OK;
+}
+
+PairGeometryArgs pair_geometry_args(const plp_keyframe_pair_geometry_args* a) {
+    PairGeometryArgs A{};
+    A.model = a->camera.model; A.setup_type = a->setup_type; A.F = a->F; A.P = a->P;
+    A.true_baseline = a->true_baseline;
+    A.pose = a->pose; A.median = a->setup_type == 0 ? a->median_depth : nullptr; A.pairs = a->pairs;
+    A.out_skip = a->out_skip; A.out_epipolar = a->out_epipolar; A.out_baseline = a->out_baseline;
+    return A;
+}
+
+plp_status check_pairs_in_table(const int32_t* pairs, int P, int F) {
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < 2; ++k)
+            if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= F) return set_error(PLP_ERR_INVALID_ARG, "a pair names a key frame outside the table");
+    return PLP_OK;
+}
+
+bool keypoint_pairs_empty(const plp_keypoint_pairs_args* a) { return a->cap == 0 || a->P == 0; }
+
+plp_status keypoint_pairs_check(plp_matcher* c, const plp_keypoint_pairs_args* a) {
+    if (!c || !a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (plp_status s = check_camera_model(&a->camera, false)) return s;
+    if (a->setup_type < 0 || a->setup_type > 2) return set_error(PLP_ERR_INVALID_ARG, "setup_type must be 0, 1 or 2");
+    if (a->setup_type != 0 && a->camera.model == PLP_CAMERA_EQUIRECTANGULAR)
+        return set_error(PLP_ERR_UNSUPPORTED, "stereo or RGB-D with the equirectangular camera is not implemented (keyframe.cc:637)");
+    if (a->num_levels < 1 || a->num_levels > 16) return set_error(PLP_ERR_INVALID_ARG, "num_levels must be 1 .. 16");
+    if (a->F <= 0 || a->cap < 0 || a->m_cap <= 0 || a->P < 0) return set_error(PLP_ERR_INVALID_ARG, "F and m_cap must be positive, cap and P non-negative");
+    if (!a->scale_factors || !a->level_sigma_sq) return set_error(PLP_ERR_INVALID_ARG, "scale_factors and level_sigma_sq are required");
+    if (a->cap > kKeylinePairCap) return set_error(PLP_ERR_UNSUPPORTED, "cap above 8192");
+    if (keypoint_pairs_empty(a)) return PLP_OK;
+    if ((int64_t)a->P * std::max(a->cap, a->m_cap) > ((int64_t)1 << 31)) return set_error(PLP_ERR_UNSUPPORTED, "P x max(cap, m_cap) above 2^31");
+    if (!a->keypts || !a->bearings || !a->pose || !a->pairs || !a->match_q) return set_error(PLP_ERR_INVALID_ARG, "keypts, bearings, pose, pairs, match_q are required");
+    if (!a->out_idx_1 || !a->out_pos_w || !a->out_status) return set_error(PLP_ERR_INVALID_ARG, "out_idx_1, out_pos_w, out_status are required");
+    if (a->setup_type != 0 && (!a->x_right || !a->depths)) return set_error(PLP_ERR_INVALID_ARG, "x_right and depths are required for a stereo or RGB-D setup");
+    return PLP_OK;
+}
+
+KeypointPairArgs keypoint_pairs_args(const plp_keypoint_pairs_args* a) {
+    KeypointPairArgs A{};
+    const plp_camera_model& cm = a->camera;
+    A.model = cm.model;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+    if (cm.model != PLP_CAMERA_EQUIRECTANGULAR) { A.fx_inv = 1.0 / cm.fx; A.fy_inv = 1.0 / cm.fy; }
+    A.half_baseline = a->true_baseline / 2.0;
+    A.setup_type = a->setup_type; A.num_levels = a->num_levels;
+    A.F = a->F; A.cap = a->cap; A.m_cap = a->m_cap; A.P = a->P;
+    A.cos_thr = (float)std::cos(a->rays_parallax_deg_thr * M_PI / 180.0);   // two_view_triangulator.cc:42 into the float of .h:110
+    A.ratio_factor = 2.0f * a->scale_factor;
+    for (int i = 0; i < 16; ++i) {
+        A.scale_factors[i] = i < a->num_levels ? a->scale_factors[i] : 1.0f;
+        A.level_sigma_sq[i] = i < a->num_levels ? a->level_sigma_sq[i] : 1.0f;
+    }
+    const bool stereo = a->setup_type != 0;
+    A.kps = a->keypts; A.bearings = a->bearings; A.x_right = stereo ? a->x_right : nullptr; A.depths = stereo ? a->depths : nullptr;
+    A.counts = a->counts; A.pose = a->pose; A.pairs = a->pairs; A.match_q = a->match_q; A.q_feature = a->q_feature; A.pair_skip = a->pair_skip;
+    A.out_idx_1 = a->out_idx_1; A.out_pos_w = a->out_pos_w; A.out_status = a->out_status; A.occ1 = a->occupied_1_io; A.occ2 = a->occupied_2_io;
+    return A;
+}
+}  // namespace
+
+plp_status plp_keyframe_pair_geometry_device(plp_matcher* c, const plp_keyframe_pair_geometry_args* a, void* hip_stream) {
+    if (plp_status s = pair_geometry_check(c, a)) return s;
+    if (a->P == 0) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_pair_geometry((hipStream_t)hip_stream, pair_geometry_args(a)));
+    return PLP_OK;
+}
+
+plp_status plp_keyframe_pair_geometry_host(plp_matcher* c, const plp_keyframe_pair_geometry_args* a) {
+    if (plp_status s = pair_geometry_check(c, a)) return s;
+    if (a->P == 0) return PLP_OK;
+    if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
+    const size_t F = (size_t)a->F, P = (size_t)a->P;
+    const PairGeometryArgs H = pair_geometry_args(a);
+    StagePart parts[] = {{H.pose, nullptr, F * 15 * 8, 0}, {H.median, nullptr, F * 4, 0}, {H.pairs, nullptr, P * 8, 0},
+                         {nullptr, H.out_skip, P, 0}, {nullptr, H.out_epipolar, P * 96, 0}, {nullptr, H.out_baseline, P * 8, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    PairGeometryArgs A = H;
+    A.pose = (const double*)dev(0); A.median = (const float*)dev(1); A.pairs = (const int32_t*)dev(2);
+    A.out_skip = (uint8_t*)dev(3); A.out_epipolar = (double*)dev(4); A.out_baseline = (double*)dev(5);
+    PLP_HIP(launch_pair_geometry(c->stream, A));
+    return stage_back(c, parts, np, base);
+}
+
+plp_status plp_triangulate_keypoint_pairs_device(plp_matcher* c, const plp_keypoint_pairs_args* a, void* hip_stream) {
+    if (plp_status s = keypoint_pairs_check(c, a)) return s;
+    if (keypoint_pairs_empty(a)) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_keypoint_pairs((hipStream_t)hip_stream, keypoint_pairs_args(a)));
+    return PLP_OK;
+}
+
+plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* c, const plp_keypoint_pairs_args* a) {
+    if (plp_status s = keypoint_pairs_check(c, a)) return s;
+    if (keypoint_pairs_empty(a)) return PLP_OK;
+    if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
+    const size_t F = (size_t)a->F, M = (size_t)a->cap, Q = (size_t)a->m_cap, P = (size_t)a->P;
+    const KeypointPairArgs H = keypoint_pairs_args(a);
+    StagePart parts[] = {
+        {H.kps, nullptr, F * M * sizeof(plp_keypoint), 0}, {H.bearings, nullptr, F * M * 24, 0}, {H.x_right, nullptr, F * M * 4, 0},
+        {H.depths, nullptr, F * M * 4, 0}, {H.counts, nullptr, F * 4, 0}, {H.pose, nullptr, F * 15 * 8, 0}, {H.pairs, nullptr, P * 8, 0},
+        {H.match_q, nullptr, P * M * 4, 0}, {H.q_feature, nullptr, P * Q * 4, 0}, {H.pair_skip, nullptr, P, 0},
+        {nullptr, H.out_idx_1, P * M * 4, 0}, {nullptr, H.out_pos_w, P * M * 24, 0}, {nullptr, H.out_status, P * M, 0},
+        {nullptr, H.occ1, P * M, 0}, {nullptr, H.occ2, P * M, 0}};
+    std::lock_guard<std::mutex> lk(c->mu);
+    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
+    uint8_t* base = nullptr;
+    if (plp_status s = stage_run(c, parts, np, &base)) return s;
+    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
+    KeypointPairArgs A = H;
+    A.kps = (const plp_keypoint*)dev(0); A.bearings = (const double*)dev(1); A.x_right = (const float*)dev(2); A.depths = (const float*)dev(3);
+    A.counts = (const int32_t*)dev(4); A.pose = (const double*)dev(5); A.pairs = (const int32_t*)dev(6); A.match_q = (const int32_t*)dev(7);
+    A.q_feature = (const int32_t*)dev(8); A.pair_skip = (const uint8_t*)dev(9);
+    A.out_idx_1 = (int32_t*)dev(10); A.out_pos_w = (double*)dev(11); A.out_status = (uint8_t*)dev(12); A.occ1 = (uint8_t*)dev(13); A.occ2 = (uint8_t*)dev(14);
+    PLP_HIP(launch_keypoint_pairs(c->stream, A));
+    return stage_back(c, parts, np, base);
+}
+
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
                                            size_t src_frame_stride, int32_t channels, int32_t color_order, int32_t B, uint8_t* d_gray,
                                            size_t gray_step, size_t gray_frame_stride, void* hip_stream) {

@@ -194,6 +194,32 @@ struct KeylinePairArgs {
 // both return the first error of their launches (the second: the geometry kernel, then the resolve kernel, on the same stream)
 hipError_t launch_median_depth(hipStream_t st, const MedianDepthArgs& A, int F);
 hipError_t launch_keyline_pairs(hipStream_t st, const KeylinePairArgs& A);
+// key-frame pair point triangulation (plp_keyframe_pair_geometry_* / plp_triangulate_keypoint_pairs_*, keypoint_pair_kernels.hip)
+struct PairGeometryArgs {
+    int model, setup_type, F, P;
+    double true_baseline;
+    const double* pose; const float* median; const int32_t* pairs;
+    uint8_t* out_skip; double* out_epipolar; double* out_baseline;
+};
+struct KeypointPairArgs {
+    int model;                        // plp_camera_model_type: which instantiation runs
+    double fx, fy, cx, cy, fxb;       // the camera fields reproject<MODEL> (reproject.hpp) reads, named as ObserveArgs names them
+    double cols_d, rows_d;
+    float bounds[4];                  // read by reproject<MODEL> for a result this step ignores: zero
+    double fx_inv, fy_inv;            // 1.0 / fx, 1.0 / fy as the constructors form them (perspective.cc:42, fisheye.cc:42)
+    double half_baseline;             // true_baseline_ / 2.0
+    int setup_type, num_levels;
+    int F, cap, m_cap, P, p0;         // p0: the first pair of this launch
+    float cos_thr;                    // cos_rays_parallax_thr_, the float of cos(thr * M_PI / 180.0)
+    float ratio_factor;               // 2.0f * scale_factor_
+    float scale_factors[16], level_sigma_sq[16];
+    const plp_keypoint* kps; const double* bearings; const float* x_right; const float* depths; const int32_t* counts;
+    const double* pose; const int32_t* pairs; const int32_t* match_q; const int32_t* q_feature; const uint8_t* pair_skip;
+    int32_t* out_idx_1; double* out_pos_w; uint8_t* out_status; uint8_t* occ1; uint8_t* occ2;
+};
+// both return the first error of their launches
+hipError_t launch_pair_geometry(hipStream_t st, const PairGeometryArgs& A);
+hipError_t launch_keypoint_pairs(hipStream_t st, const KeypointPairArgs& A);
 void launch_to_gray(hipStream_t st, const uint8_t* src, int rows, int cols, size_t src_step, size_t src_fs, int channels, int bgr, int B, uint8_t* dst,
                     size_t dst_step, size_t dst_fs);
 void launch_to_depth(hipStream_t st, const void* src, int is_u16, int rows, int cols, size_t src_step, size_t src_fs, float scale, int B, float* dst,
