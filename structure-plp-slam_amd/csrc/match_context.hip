@@ -71,6 +71,18 @@ plp_status check_args(const plp_match_args* a) {
     return PLP_OK;
 }
 
+// a kernel-argument table of 16 pyramid levels from the caller's num_levels floats (NULL: none), 1 past them
+void fill_levels(float (&dst)[16], const float* src, int num_levels) {
+    for (int i = 0; i < 16; ++i) dst[i] = (src && i < num_levels) ? src[i] : 1.0f;
+}
+
+// the camera fields reproject<MODEL> (reproject.hpp) reads, which ObserveArgs, ProjectArgs and KeypointPairArgs name alike
+template <class Args> void set_camera(Args& A, const plp_camera_model& cm) {
+    A.model = cm.model;
+    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
+    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+}
+
 // targets of a frame k_match_topk_cells keeps in LDS (plp_match_args.t_count_hint)
 int lds_targets_of(const plp_match_args* a) { return a->t_count_hint > 0 ? std::min(a->t_count_hint, a->n_cap) : a->n_cap; }
 
@@ -93,7 +105,7 @@ plp_status run_device(plp_matcher* c, const plp_match_args* a, hipStream_t st) {
     P.q_group = a->q_group; P.t_group = a->t_group; P.q_reproj_d = a->q_reproj_d; P.out_query_best = a->out_query_best;
     P.hamm_dist_thr = a->hamm_dist_thr; P.level_window = a->level_window; P.flags = a->flags;
     P.q_reproj2_d = a->q_reproj2_d; P.q_bearing = a->q_bearing; P.t_bearing = a->t_bearing; P.epipolar = a->epipolar;
-    for (int i = 0; i < 16; ++i) P.inv_level_sigma_sq[i] = (a->inv_level_sigma_sq && i < a->num_levels) ? a->inv_level_sigma_sq[i] : 1.0f;
+    fill_levels(P.inv_level_sigma_sq, a->inv_level_sigma_sq, a->num_levels);
     P.t_desc = a->t_desc; P.t_x_right = a->t_x_right; P.t_occupied = a->t_occupied; P.t_angle = a->t_angle; P.t_counts = a->t_counts;
     P.q_valid = a->q_valid; P.q_reproj = a->q_reproj; P.q_x_right = a->q_x_right; P.q_level = a->q_level; P.q_angle = a->q_angle;
     P.q_desc = a->q_desc; P.q_has_obs = a->q_has_obs; P.q_counts = a->q_counts;
@@ -103,7 +115,7 @@ plp_status run_device(plp_matcher* c, const plp_match_args* a, hipStream_t st) {
     P.directions = (a->mode == PLP_MATCH_MODE_LAST_FRAME || a->mode == PLP_MATCH_MODE_LAST_FRAME_LINE) ? a->directions : nullptr;
     P.check_orientation = a->check_orientation;
     P.num_levels = a->num_levels;
-    for (int i = 0; i < 16; ++i) P.scale_factors[i] = (a->scale_factors && i < a->num_levels) ? a->scale_factors[i] : 1.0f;
+    fill_levels(P.scale_factors, a->scale_factors, a->num_levels);
     P.grid_min_x = a->grid.min_x; P.grid_min_y = a->grid.min_y; P.inv_cell_w = a->grid.inv_cell_width; P.inv_cell_h = a->grid.inv_cell_height;
     P.grid_cols = a->grid.cols; P.grid_rows = a->grid.rows;
     P.klist = (uint32_t*)c->klist.p; P.klist2 = (uint32_t*)c->klist2.p; P.kcount = (int32_t*)c->kcount.p; P.claim = (int32_t*)c->claim.p; P.full_list = (int32_t*)c->full_list.p;
@@ -172,76 +184,26 @@ plp_status plp_match_host(plp_matcher* c, const plp_match_args* a) {
     if (a->q_desc_stride != 0 && a->q_desc_stride != a->m_cap) return set_error(PLP_ERR_UNSUPPORTED, "q_desc_stride is a device-path option (overlapping query windows of a batched replay)");
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    const size_t tn = (size_t)a->B * a->n_cap, qn = (size_t)a->B * a->m_cap;
-    // slab layout (256-byte aligned pieces)
-    struct Piece { const void* src; size_t bytes; size_t off; };
-    std::vector<Piece> in;
-    size_t off = 0;
-    auto add = [&](const void* src, size_t bytes) -> size_t {
-        const size_t o = off;
-        in.push_back({src, bytes, o});
-        off += (bytes + 255) / 256 * 256;
-        return o;
-    };
-    const size_t o_tk = add(a->t_kps, a->t_kps ? tn * sizeof(plp_keypoint) : 0), o_td = add(a->t_desc, tn * 32);
-    const size_t o_tx = add(a->t_x_right, a->t_x_right ? tn * 4 : 0), o_to = add(a->t_occupied, a->t_occupied ? tn : 0);
-    const size_t o_ta = add(a->t_angle, a->t_angle ? tn * 4 : 0), o_tc = add(a->t_counts, a->t_counts ? (size_t)a->B * 4 : 0);
-    const size_t o_qv = add(a->q_valid, a->q_valid ? qn : 0), o_qr = add(a->q_reproj, a->q_reproj ? qn * 8 : 0);
-    const size_t o_qx = add(a->q_x_right, a->q_x_right ? qn * 4 : 0), o_ql = add(a->q_level, a->q_level ? qn * 4 : 0);
-    const size_t o_qa = add(a->q_angle, a->q_angle ? qn * 4 : 0), o_qd = add(a->q_desc, qn * 32);
-    const size_t o_qh = add(a->q_has_obs, a->q_has_obs ? qn : 0), o_qc = add(a->q_counts, a->q_counts ? (size_t)a->B * 4 : 0);
-    const size_t o_kl = add(a->t_kl, a->t_kl ? tn * sizeof(plp_keyline) : 0), o_ko = add(a->t_kp_octave, a->t_kp_octave ? tn * 4 : 0);
-    const size_t o_tx2 = add(a->t_x_right2, a->t_x_right2 ? tn * 4 : 0), o_qr2 = add(a->q_reproj2, a->q_reproj2 ? qn * 8 : 0);
-    const size_t o_qx2 = add(a->q_x_right2, a->q_x_right2 ? qn * 4 : 0);
-    const size_t o_qg = add(a->q_group, a->q_group ? qn * 4 : 0), o_tg = add(a->t_group, a->t_group ? tn * 4 : 0);
-    const size_t o_qrd = add(a->q_reproj_d, a->q_reproj_d ? qn * 16 : 0);
-    const size_t o_qrd2 = add(a->q_reproj2_d, a->q_reproj2_d ? qn * 16 : 0);
-    const size_t o_qb = add(a->q_bearing, a->q_bearing ? qn * 24 : 0), o_tb = add(a->t_bearing, a->t_bearing ? tn * 24 : 0);
-    const size_t o_ep = add(a->epipolar, a->epipolar ? (size_t)a->B * 96 : 0);
-    const size_t o_dir = add(a->directions, a->directions ? (size_t)a->B * 4 : 0);
-    const size_t o_oq = off; off += (qn * 4 + 255) / 256 * 256;
-    const size_t o_om = off; off += (tn * 4 + 255) / 256 * 256;
-    const size_t o_on = off; off += ((size_t)a->B * 4 + 255) / 256 * 256;
-    PLP_HIP(c->stage.reserve(off));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    for (const Piece& p : in)
-        if (p.src && p.bytes) PLP_HIP(hipMemcpyAsync(base + p.off, p.src, p.bytes, hipMemcpyHostToDevice, st));
+    const size_t B = (size_t)a->B, tn = B * a->n_cap, qn = B * a->m_cap;
     plp_match_args d = *a;
-    auto dp = [&](const void* src, size_t o) -> const void* { return src ? base + o : nullptr; };
-    d.t_kps = (const plp_keypoint*)dp(a->t_kps, o_tk); d.t_desc = (const uint8_t*)dp(a->t_desc, o_td);
-    d.t_x_right = (const float*)dp(a->t_x_right, o_tx); d.t_occupied = (const uint8_t*)dp(a->t_occupied, o_to);
-    d.t_angle = (const float*)dp(a->t_angle, o_ta); d.t_counts = (const int32_t*)dp(a->t_counts, o_tc);
-    d.q_valid = (const uint8_t*)dp(a->q_valid, o_qv); d.q_reproj = (const float*)dp(a->q_reproj, o_qr);
-    d.q_x_right = (const float*)dp(a->q_x_right, o_qx); d.q_level = (const int32_t*)dp(a->q_level, o_ql);
-    d.q_angle = (const float*)dp(a->q_angle, o_qa); d.q_desc = (const uint8_t*)dp(a->q_desc, o_qd);
-    d.q_has_obs = (const uint8_t*)dp(a->q_has_obs, o_qh); d.q_counts = (const int32_t*)dp(a->q_counts, o_qc);
-    d.t_kl = (const plp_keyline*)dp(a->t_kl, o_kl); d.t_kp_octave = (const int32_t*)dp(a->t_kp_octave, o_ko);
-    d.t_x_right2 = (const float*)dp(a->t_x_right2, o_tx2); d.q_reproj2 = (const float*)dp(a->q_reproj2, o_qr2);
-    d.q_x_right2 = (const float*)dp(a->q_x_right2, o_qx2);
-    d.q_group = (const int32_t*)dp(a->q_group, o_qg); d.t_group = (const int32_t*)dp(a->t_group, o_tg);
-    d.q_reproj_d = (const double*)dp(a->q_reproj_d, o_qrd);
-    d.q_reproj2_d = (const double*)dp(a->q_reproj2_d, o_qrd2); d.q_bearing = (const double*)dp(a->q_bearing, o_qb);
-    d.t_bearing = (const double*)dp(a->t_bearing, o_tb); d.epipolar = (const double*)dp(a->epipolar, o_ep);
-    d.directions = (const int32_t*)dp(a->directions, o_dir);
-    d.out_query_best = a->out_query_best ? (int32_t*)(base + o_oq) : nullptr;
-    d.out_match = (int32_t*)(base + o_om); d.out_num = (int32_t*)(base + o_on);
-    // The kernels write only the slots below a problem's count (key points t < t_counts[b]; fuse modes: queries q < q_counts[b]); the rest of the slab
-    // holds whatever an earlier call left.  With counts given, the caller's arrays go in first so that those slots come back unchanged, as on the
-    // device entry.  Without counts every slot is written: nothing to copy.
-    const bool fuse = a->mode == PLP_MATCH_MODE_FUSE || a->mode == PLP_MATCH_MODE_FUSE_LINE;
-    if (fuse && a->q_counts) PLP_HIP(hipMemcpyAsync(base + o_oq, a->out_query_best, qn * 4, hipMemcpyHostToDevice, st));
-    if (!fuse && a->t_counts) PLP_HIP(hipMemcpyAsync(base + o_om, a->out_match, tn * 4, hipMemcpyHostToDevice, st));
-    PLP_TRY(run_device(c, &d, st));
-    if (fuse) {
-        PLP_HIP(hipMemcpyAsync(a->out_query_best, base + o_oq, qn * 4, hipMemcpyDeviceToHost, st));
-        PLP_HIP(hipStreamSynchronize(st));
-        return PLP_OK;
+    Stage s(c->stage, c->stream);
+    s.in(d.t_kps, tn); s.in(d.t_desc, tn * 32); s.in(d.t_x_right, tn); s.in(d.t_occupied, tn); s.in(d.t_angle, tn); s.in(d.t_counts, B);
+    s.in(d.q_valid, qn); s.in(d.q_reproj, qn * 2); s.in(d.q_x_right, qn); s.in(d.q_level, qn); s.in(d.q_angle, qn); s.in(d.q_desc, qn * 32);
+    s.in(d.q_has_obs, qn); s.in(d.q_counts, B); s.in(d.t_kl, tn); s.in(d.t_kp_octave, tn); s.in(d.t_x_right2, tn); s.in(d.q_reproj2, qn * 2);
+    s.in(d.q_x_right2, qn); s.in(d.q_group, qn); s.in(d.t_group, tn); s.in(d.q_reproj_d, qn * 2); s.in(d.q_reproj2_d, qn * 2);
+    s.in(d.q_bearing, qn * 3); s.in(d.t_bearing, tn * 3); s.in(d.epipolar, B * 12); s.in(d.directions, B);
+    // Only the mode's own result comes back; the other outputs are device-only regions (out_query_best: when the caller passes one).  Without
+    // counts every slot of the result is written: nothing to keep.  out_num is written for every problem.
+    if (a->mode == PLP_MATCH_MODE_FUSE || a->mode == PLP_MATCH_MODE_FUSE_LINE) {
+        s.out(d.out_query_best, qn, a->q_counts != nullptr);
+        s.room(d.out_match, tn); s.room(d.out_num, B);
+    } else {
+        s.room(d.out_query_best, a->out_query_best ? qn : 0);
+        s.out(d.out_match, tn, a->t_counts != nullptr); s.out(d.out_num, B, false);
     }
-    PLP_HIP(hipMemcpyAsync(a->out_match, base + o_om, tn * 4, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipMemcpyAsync(a->out_num, base + o_on, (size_t)a->B * 4, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    PLP_TRY(s.upload());
+    PLP_TRY(run_device(c, &d, c->stream));
+    return s.finish();
 }
 
 // order in which Mihasher::query enumerates the bit-flip patterns with s ones inside a b-bit substring
@@ -292,18 +254,15 @@ plp_status plp_lbd_match_1nn_host(plp_matcher* c, const uint8_t* q, int32_t nq, 
     if (nt > 65535) return set_error(PLP_ERR_UNSUPPORTED, "more than 65535 train descriptors (16-bit index in the tie-break key)");
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    const size_t bq = ((size_t)nq * 32 + 255) / 256 * 256, bt = ((size_t)nt * 32 + 255) / 256 * 256, bo = ((size_t)nq * 4 + 255) / 256 * 256;
-    PLP_HIP(c->stage.reserve(bq + bt + 2 * bo));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    PLP_HIP(hipMemcpyAsync(base, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-    PLP_HIP(hipMemcpyAsync(base + bq, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
+    const uint8_t *d_q = q, *d_t = t;   // device addresses after upload()
+    int32_t *d_train_idx = train_idx, *d_dist = dist;
+    Stage s(c->stage, c->stream);
+    s.in(d_q, (size_t)nq * 32); s.in(d_t, (size_t)nt * 32); s.out(d_train_idx, nq, false); s.out(d_dist, nq, false);
+    PLP_TRY(s.upload());
     static const MihRanks R = mih_ranks();
-    launch_lbd_match_1nn(c->stream, base, nullptr, nq, base + bq, nullptr, nt, R, (int32_t*)(base + bq + bt), (int32_t*)(base + bq + bt + bo), 1);
+    launch_lbd_match_1nn(c->stream, d_q, nullptr, nq, d_t, nullptr, nt, R, d_train_idx, d_dist, 1);
     PLP_HIP(hipGetLastError());
-    PLP_HIP(hipMemcpyAsync(train_idx, base + bq + bt, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-    PLP_HIP(hipMemcpyAsync(dist, base + bq + bt + bo, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
-    PLP_HIP(hipStreamSynchronize(c->stream));
-    return PLP_OK;
+    return s.finish();
 }
 
 plp_status plp_match_area_host(plp_matcher* c, const plp_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const plp_keypoint* kps_2,
@@ -315,34 +274,19 @@ plp_status plp_match_area_host(plp_matcher* c, const plp_keypoint* kps_1, const 
     if (!kps_1 || !desc_1 || !prev_matched_pts || n2 < 0 || (n2 > 0 && (!kps_2 || !desc_2)) || n2 > 65535) return set_error(PLP_ERR_INVALID_ARG, "bad argument");
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t n2c = std::max(n2, 1);
-    const size_t o_k1 = 0, o_d1 = o_k1 + al((size_t)n1 * sizeof(plp_keypoint)), o_k2 = o_d1 + al((size_t)n1 * 32), o_d2 = o_k2 + al(n2c * sizeof(plp_keypoint));
-    const size_t o_pp = o_d2 + al(n2c * 32), o_m = o_pp + al((size_t)n1 * 8), o_n = o_m + al((size_t)n1 * 4), o_s = o_n + 256, total = o_s + al(n2c * 8);
-    PLP_HIP(c->stage.reserve(total));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    PLP_HIP(hipMemcpyAsync(base + o_k1, kps_1, (size_t)n1 * sizeof(plp_keypoint), hipMemcpyHostToDevice, st));
-    PLP_HIP(hipMemcpyAsync(base + o_d1, desc_1, (size_t)n1 * 32, hipMemcpyHostToDevice, st));
-    if (n2) {
-        PLP_HIP(hipMemcpyAsync(base + o_k2, kps_2, (size_t)n2 * sizeof(plp_keypoint), hipMemcpyHostToDevice, st));
-        PLP_HIP(hipMemcpyAsync(base + o_d2, desc_2, (size_t)n2 * 32, hipMemcpyHostToDevice, st));
-    }
-    PLP_HIP(hipMemcpyAsync(base + o_pp, prev_matched_pts, (size_t)n1 * 8, hipMemcpyHostToDevice, st));
     AreaArgs A{};
-    A.kps1 = (const plp_keypoint*)(base + o_k1); A.desc1 = base + o_d1; A.kps2 = (const plp_keypoint*)(base + o_k2); A.desc2 = base + o_d2;
-    A.n1 = n1; A.n2 = n2;
+    A.kps1 = kps_1; A.desc1 = desc_1; A.kps2 = kps_2; A.desc2 = desc_2; A.n1 = n1; A.n2 = n2;
     A.grid_min_x = grid->min_x; A.grid_min_y = grid->min_y; A.inv_cell_w = grid->inv_cell_width; A.inv_cell_h = grid->inv_cell_height;
     A.grid_cols = grid->cols; A.grid_rows = grid->rows;
-    A.prev_pts = (float*)(base + o_pp); A.margin = (float)margin; A.lowe_ratio = lowe_ratio; A.check_orientation = check_orientation;
-    A.matched_2_in_1 = (int32_t*)(base + o_m); A.num_matches = (int32_t*)(base + o_n); A.scratch = (uint32_t*)(base + o_s);
-    launch_match_area(st, A);
+    A.prev_pts = prev_matched_pts; A.margin = (float)margin; A.lowe_ratio = lowe_ratio; A.check_orientation = check_orientation;
+    A.matched_2_in_1 = matched_2_in_1; A.num_matches = num_matches;
+    Stage s(c->stage, c->stream);   // n2 == 0: the kernel reads no key point of frame 2 and no scratch
+    s.in(A.kps1, n1); s.in(A.desc1, (size_t)n1 * 32); s.in(A.kps2, n2); s.in(A.desc2, (size_t)n2 * 32);
+    s.out(A.matched_2_in_1, n1, false); s.out(A.prev_pts, (size_t)n1 * 2); s.out(A.num_matches, 1, false); s.room(A.scratch, (size_t)n2 * 2);
+    PLP_TRY(s.upload());
+    launch_match_area(c->stream, A);
     PLP_HIP(hipGetLastError());
-    PLP_HIP(hipMemcpyAsync(matched_2_in_1, base + o_m, (size_t)n1 * 4, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipMemcpyAsync(prev_matched_pts, base + o_pp, (size_t)n1 * 8, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipMemcpyAsync(num_matches, base + o_n, 4, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    return s.finish();
 }
 
 namespace {
@@ -477,53 +421,30 @@ plp_status post_extract_host(plp_matcher* c, const PostArgs& cam_args, const plp
     if (n > 0 && (!kps || !undist)) return set_error(PLP_ERR_INVALID_ARG, "kps and undist are required");
     if (n_kl > 0 && (!kl || !depth || !kl_depths || !kl_x_right)) return set_error(PLP_ERR_INVALID_ARG, "key lines need depth and both outputs");
     if (depth && (rows <= 0 || cols <= 0 || depth_step < (size_t)cols * 4)) return set_error(PLP_ERR_INVALID_ARG, "bad depth geometry");
-    hipStream_t st;
-    {
-        std::lock_guard<std::mutex> lk(c->mu);
-        PLP_HIP(hipSetDevice(c->device));
-        st = c->stream;
-        auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-        const size_t nk = std::max(n, 1), nl = std::max(n_kl, 1);
-        const size_t o_k = 0, o_u = o_k + al(nk * sizeof(plp_keypoint)), o_b = o_u + al(nk * sizeof(plp_keypoint)), o_x = o_b + al(nk * 24),
-                     o_d = o_x + al(nk * 4), o_l = o_d + al(nk * 4), o_ld = o_l + al(nl * sizeof(plp_keyline)), o_lx = o_ld + al(nl * 8),
-                     o_img = o_lx + al(nl * 8), total = o_img + (depth ? al((size_t)rows * cols * 4) : 0);
-        PLP_HIP(c->stage.reserve(total));
-        uint8_t* base = (uint8_t*)c->stage.p;
-        if (n) PLP_HIP(hipMemcpyAsync(base + o_k, kps, (size_t)n * sizeof(plp_keypoint), hipMemcpyHostToDevice, st));
-        if (n_kl) {
-            PLP_HIP(hipMemcpyAsync(base + o_l, kl, (size_t)n_kl * sizeof(plp_keyline), hipMemcpyHostToDevice, st));
-            PLP_HIP(hipMemcpyAsync(base + o_ld, kl_depths, (size_t)n_kl * 8, hipMemcpyHostToDevice, st));     // skipped lines keep the caller's values
-            PLP_HIP(hipMemcpyAsync(base + o_lx, kl_x_right, (size_t)n_kl * 8, hipMemcpyHostToDevice, st));
-        }
-        if (depth) {   // the depth image through a page-locked buffer with slack (plp_common.hpp HostPinned): no 2-D copy reads the caller's pageable memory
-            PLP_HIP(c->pin.reserve((size_t)rows * cols * 4));
-            c->pin.pack(0, reinterpret_cast<const uint8_t*>(depth), depth_step, rows, cols * 4);
-            PLP_HIP(hipMemcpyAsync(base + o_img, c->pin.p, (size_t)rows * cols * 4, hipMemcpyHostToDevice, st));
-        }
-        PostArgs A = cam_args;
-        A.kps = n ? (const plp_keypoint*)(base + o_k) : nullptr; A.counts = nullptr; A.cap = n;
-        A.depth = depth ? (const float*)(base + o_img) : nullptr; A.depth_step = (size_t)cols * 4; A.depth_frame_stride = 0;
-        A.undist = (plp_keypoint*)(base + o_u); A.bearings = bearings ? (double*)(base + o_b) : nullptr;
-        A.x_right = (depth && x_right && depths) ? (float*)(base + o_x) : nullptr; A.depths = A.x_right ? (float*)(base + o_d) : nullptr;
-        A.kl = n_kl ? (const plp_keyline*)(base + o_l) : nullptr; A.kl_counts = nullptr; A.kl_cap = n_kl;
-        A.kl_depths = (float*)(base + o_ld); A.kl_x_right = (float*)(base + o_lx);
-        launch_post_extract(st, A, 1);
-        PLP_HIP(hipGetLastError());
-        if (n) {
-            PLP_HIP(hipMemcpyAsync(undist, base + o_u, (size_t)n * sizeof(plp_keypoint), hipMemcpyDeviceToHost, st));
-            if (bearings) PLP_HIP(hipMemcpyAsync(bearings, base + o_b, (size_t)n * 24, hipMemcpyDeviceToHost, st));
-            if (A.x_right) {
-                PLP_HIP(hipMemcpyAsync(x_right, base + o_x, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-                PLP_HIP(hipMemcpyAsync(depths, base + o_d, (size_t)n * 4, hipMemcpyDeviceToHost, st));
-            }
-        }
-        if (n_kl) {
-            PLP_HIP(hipMemcpyAsync(kl_depths, base + o_ld, (size_t)n_kl * 8, hipMemcpyDeviceToHost, st));
-            PLP_HIP(hipMemcpyAsync(kl_x_right, base + o_lx, (size_t)n_kl * 8, hipMemcpyDeviceToHost, st));
-        }
-        PLP_HIP(hipStreamSynchronize(st));
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PostArgs A = cam_args;
+    A.kps = kps; A.cap = n; A.undist = undist; A.bearings = bearings;
+    const bool stereo = depth && x_right && depths;
+    A.x_right = stereo ? x_right : nullptr; A.depths = stereo ? depths : nullptr;
+    A.kl = kl; A.kl_cap = n_kl; A.kl_depths = kl_depths; A.kl_x_right = kl_x_right;
+    A.depth_step = (size_t)cols * 4;
+    const size_t px = depth ? (size_t)rows * cols : 0;
+    Stage s(c->stage, c->stream);   // n == 0 / n_kl == 0: the kernel tests kps / kl before it touches that side's outputs
+    s.in(A.kps, n); s.out(A.undist, n, false); s.out(A.bearings, (size_t)n * 3, false); s.out(A.x_right, n, false); s.out(A.depths, n, false);
+    s.in(A.kl, n_kl); s.out(A.kl_depths, (size_t)n_kl * 2); s.out(A.kl_x_right, (size_t)n_kl * 2);   // skipped lines keep the caller's values
+    float* img = nullptr;
+    s.room(img, px);
+    PLP_TRY(s.upload());
+    A.depth = img;
+    if (depth) {   // the depth image through a page-locked buffer with slack (plp_common.hpp HostPinned): no 2-D copy reads the caller's pageable memory
+        PLP_HIP(c->pin.reserve(px * sizeof(float)));
+        c->pin.pack(0, reinterpret_cast<const uint8_t*>(depth), depth_step, rows, cols * 4);
+        PLP_HIP(hipMemcpyAsync(img, c->pin.p, px * sizeof(float), hipMemcpyHostToDevice, c->stream));
     }
-    return PLP_OK;
+    launch_post_extract(c->stream, A, 1);
+    PLP_HIP(hipGetLastError());
+    return s.finish();
 }
 }  // namespace
 
@@ -543,11 +464,8 @@ plp_status observe_check(plp_matcher* c, const plp_observe_args* a, bool lines) 
 
 ObserveArgs observe_args(const plp_observe_args* a, bool lines) {
     ObserveArgs A{};
-    const plp_camera_model& cm = a->camera;
-    A.model = cm.model;
-    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
-    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
-    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    set_camera(A, a->camera);
+    std::copy_n(a->img_bounds, 4, A.bounds);
     A.ray_cos_thr = a->ray_cos_thr; A.log_sf = a->log_scale_factor; A.num_levels = a->num_levels; A.m_cap = a->m_cap;
     A.pose = a->pose; A.counts = a->counts; A.pos_w = a->pos_w; A.normal = lines ? nullptr : a->obs_mean_normal;
     const bool scale = lines || a->obs_mean_normal;
@@ -571,9 +489,7 @@ plp_status observe_device(plp_matcher* c, const plp_observe_args* a, bool lines,
     return PLP_OK;
 }
 
-// host pointers: every array staged into the context's slab, the device path's kernel, the outputs copied back.  The outputs go to the slab
-// FIRST, as the caller holds them: the kernel leaves slots past counts[b] and the unspecified slots alone, and copying the whole block back
-// must give the caller those slots unchanged (plp_front.h), not whatever an earlier call left in the slab.
+// host pointers: every array staged through the context's slab (plp_common.hpp Stage), the device path's kernel, the outputs copied back
 plp_status observe_host(plp_matcher* c, const plp_observe_args* a, bool lines) {
     if (plp_status s = observe_check(c, a, lines)) return s;
     const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
@@ -581,35 +497,16 @@ plp_status observe_host(plp_matcher* c, const plp_observe_args* a, bool lines) {
         if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
         return PLP_OK;
     }
-    const ObserveArgs H = observe_args(a, lines);   // which arrays take part (host pointers)
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
-    Part parts[] = {
-        {H.pose, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0}, {H.pos_w, nullptr, BM * (lines ? 6 : 3) * 8, 0},
-        {H.normal, nullptr, BM * 3 * 8, 0}, {H.min_dist, nullptr, BM * 4, 0}, {H.max_dist, nullptr, BM * 4, 0}, {H.skip, nullptr, BM, 0},
-        {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0}, {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.level, BM * 4, 0},
-        {nullptr, H.valid, BM, 0}, {nullptr, H.num_valid, B * 4, 0}};
-    size_t tot = 0;
-    for (Part& p : parts)
-        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    ObserveArgs A = observe_args(a, lines);
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    PLP_HIP(c->stage.reserve(tot));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    for (const Part& p : parts)
-        if (p.src || p.dst) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
-    ObserveArgs A = H;
-    A.pose = (const double*)dev(0); A.counts = (const int32_t*)dev(1); A.pos_w = (const double*)dev(2); A.normal = (const double*)dev(3);
-    A.min_dist = (const float*)dev(4); A.max_dist = (const float*)dev(5); A.skip = (const uint8_t*)dev(6);
-    A.reproj = (float*)dev(7); A.reproj2 = (float*)dev(8); A.x_right = (float*)dev(9); A.level = (int32_t*)dev(10); A.valid = (uint8_t*)dev(11);
-    A.num_valid = (int32_t*)dev(12);
-    PLP_HIP(lines ? launch_observe_lines(st, A, a->B) : launch_observe_points(st, A, a->B));
-    for (const Part& p : parts)
-        if (p.dst) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, B * 15); s.in(A.counts, B); s.in(A.pos_w, BM * (lines ? 6 : 3)); s.in(A.normal, BM * 3);
+    s.in(A.min_dist, BM); s.in(A.max_dist, BM); s.in(A.skip, BM);
+    s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.level, BM); s.out(A.valid, BM); s.out(A.num_valid, B);
+    PLP_TRY(s.upload());
+    PLP_HIP(lines ? launch_observe_lines(c->stream, A, a->B) : launch_observe_points(c->stream, A, a->B));
+    return s.finish();
 }
 }  // namespace
 
@@ -634,11 +531,8 @@ plp_status last_frame_check(plp_matcher* c, const plp_last_frame_args* a, bool l
 
 ObserveArgs last_frame_args(const plp_last_frame_args* a, bool lines) {
     ObserveArgs A{};
-    const plp_camera_model& cm = a->camera;
-    A.model = cm.model;
-    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
-    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
-    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    set_camera(A, a->camera);
+    std::copy_n(a->img_bounds, 4, A.bounds);
     A.m_cap = a->m_cap; A.setup_type = a->setup_type; A.true_baseline = a->true_baseline;
     A.pose = a->pose_curr; A.pose_last = a->pose_last; A.counts = a->counts; A.pos_w = a->pos_w; A.skip = a->skip;
     A.kps = lines ? nullptr : a->keypts; A.kl = lines ? a->keylines : nullptr;
@@ -656,41 +550,21 @@ plp_status last_frame_device(plp_matcher* c, const plp_last_frame_args* a, bool 
     return PLP_OK;
 }
 
-// host pointers, staged as observe_host stages them (the outputs first, so that unwritten slots come back as the caller holds them)
+// m_cap == 0: nothing per slot is staged, the kernels still write every problem's direction and num_valid
 plp_status last_frame_host(plp_matcher* c, const plp_last_frame_args* a, bool lines) {
     if (plp_status s = last_frame_check(c, a, lines)) return s;
-    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
-    const ObserveArgs H = last_frame_args(a, lines);
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
-    Part parts[] = {
-        {H.pose, nullptr, B * 15 * 8, 0}, {H.pose_last, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0},
-        {H.pos_w, nullptr, BM * (lines ? 6 : 3) * 8, 0}, {H.skip, nullptr, BM, 0}, {H.kps, nullptr, BM * sizeof(plp_keypoint), 0},
-        {H.kl, nullptr, BM * sizeof(plp_keyline), 0},
-        {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0}, {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.x_right2, BM * 4, 0},
-        {nullptr, H.level, BM * 4, 0}, {nullptr, H.angle, BM * 4, 0}, {nullptr, H.valid, BM, 0}, {nullptr, H.direction, B * 4, 0},
-        {nullptr, H.num_valid, B * 4, 0}};
-    size_t tot = 0;
-    for (Part& p : parts)
-        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    const size_t B = (size_t)a->B, BM = B * a->m_cap;
+    ObserveArgs A = last_frame_args(a, lines);
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    PLP_HIP(c->stage.reserve(tot));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    for (const Part& p : parts)
-        if ((p.src || p.dst) && p.bytes) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
-    ObserveArgs A = H;
-    A.pose = (const double*)dev(0); A.pose_last = (const double*)dev(1); A.counts = (const int32_t*)dev(2); A.pos_w = (const double*)dev(3);
-    A.skip = (const uint8_t*)dev(4); A.kps = (const plp_keypoint*)dev(5); A.kl = (const plp_keyline*)dev(6);
-    A.reproj = (float*)dev(7); A.reproj2 = (float*)dev(8); A.x_right = (float*)dev(9); A.x_right2 = (float*)dev(10); A.level = (int32_t*)dev(11);
-    A.angle = (float*)dev(12); A.valid = (uint8_t*)dev(13); A.direction = (int32_t*)dev(14); A.num_valid = (int32_t*)dev(15);
-    PLP_HIP(lines ? launch_last_frame_lines(st, A, a->B) : launch_last_frame_points(st, A, a->B));
-    for (const Part& p : parts)
-        if (p.dst && p.bytes) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, B * 15); s.in(A.pose_last, B * 15); s.in(A.counts, B); s.in(A.pos_w, BM * (lines ? 6 : 3)); s.in(A.skip, BM);
+    s.in(A.kps, BM); s.in(A.kl, BM);
+    s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.x_right2, BM); s.out(A.level, BM); s.out(A.angle, BM);
+    s.out(A.valid, BM); s.out(A.direction, B); s.out(A.num_valid, B);
+    PLP_TRY(s.upload());
+    PLP_HIP(lines ? launch_last_frame_lines(c->stream, A, a->B) : launch_last_frame_points(c->stream, A, a->B));
+    return s.finish();
 }
 }  // namespace
 
@@ -724,11 +598,8 @@ plp_status project_check(plp_matcher* c, const plp_project_args* a, bool lines) 
 
 ProjectArgs project_args(const plp_project_args* a, bool lines) {
     ProjectArgs A{};
-    const plp_camera_model& cm = a->camera;
-    A.model = cm.model;
-    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
-    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
-    for (int k = 0; k < 4; ++k) A.bounds[k] = a->img_bounds[k];
+    set_camera(A, a->camera);
+    std::copy_n(a->img_bounds, 4, A.bounds);
     A.log_sf = a->log_scale_factor; A.num_levels = a->num_levels; A.m_cap = a->m_cap;
     A.shared = a->shared_landmarks ? 1 : 0; A.dist_mode = a->dist_mode; A.ray_test = (!lines && a->ray_test) ? 1 : 0; A.line_dist_mode = a->line_dist_mode;
     A.pose = a->pose; A.counts = a->counts; A.pos_w = a->pos_w; A.normal = (!lines && a->ray_test) ? a->obs_mean_normal : nullptr;
@@ -754,7 +625,6 @@ plp_status project_device(plp_matcher* c, const plp_project_args* a, bool lines,
     return PLP_OK;
 }
 
-// host pointers, staged as observe_host stages them (the outputs first, so that unwritten slots come back as the caller holds them)
 plp_status project_host(plp_matcher* c, const plp_project_args* a, bool lines) {
     if (plp_status s = project_check(c, a, lines)) return s;
     const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
@@ -762,38 +632,18 @@ plp_status project_host(plp_matcher* c, const plp_project_args* a, bool lines) {
         if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
         return PLP_OK;
     }
-    const ProjectArgs H = project_args(a, lines);   // which arrays take part (host pointers)
-    const size_t LM = H.shared ? M : BM;            // rows of the landmark tables
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    struct Part { const void* src; void* dst; size_t bytes; size_t off; };
-    Part parts[] = {
-        {H.pose, nullptr, B * 15 * 8, 0}, {H.counts, nullptr, B * 4, 0}, {H.pos_w, nullptr, LM * (lines ? 6 : 3) * 8, 0},
-        {H.normal, nullptr, LM * 3 * 8, 0}, {H.min_dist, nullptr, LM * 4, 0}, {H.max_dist, nullptr, LM * 4, 0}, {H.skip, nullptr, BM, 0},
-        {nullptr, H.reproj_d, BM * 16, 0}, {nullptr, H.reproj2_d, BM * 16, 0}, {nullptr, H.reproj, BM * 8, 0}, {nullptr, H.reproj2, BM * 8, 0},
-        {nullptr, H.x_right, BM * 4, 0}, {nullptr, H.x_right2, BM * 4, 0}, {nullptr, H.level, BM * 4, 0}, {nullptr, H.valid, BM, 0},
-        {nullptr, H.status, BM, 0}, {nullptr, H.num_valid, B * 4, 0}};
-    size_t tot = 0;
-    for (Part& p : parts)
-        if (p.src || p.dst) { p.off = tot; tot += al(p.bytes); }
+    ProjectArgs A = project_args(a, lines);
+    const size_t LM = A.shared ? M : BM;   // rows of the landmark tables
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    PLP_HIP(c->stage.reserve(tot));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    for (const Part& p : parts)
-        if (p.src || p.dst) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, st));
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) ? base + parts[k].off : nullptr; };
-    ProjectArgs A = H;
-    A.pose = (const double*)dev(0); A.counts = (const int32_t*)dev(1); A.pos_w = (const double*)dev(2); A.normal = (const double*)dev(3);
-    A.min_dist = (const float*)dev(4); A.max_dist = (const float*)dev(5); A.skip = (const uint8_t*)dev(6);
-    A.reproj_d = (double*)dev(7); A.reproj2_d = (double*)dev(8); A.reproj = (float*)dev(9); A.reproj2 = (float*)dev(10);
-    A.x_right = (float*)dev(11); A.x_right2 = (float*)dev(12); A.level = (int32_t*)dev(13); A.valid = (uint8_t*)dev(14);
-    A.status = (uint8_t*)dev(15); A.num_valid = (int32_t*)dev(16);
-    PLP_HIP(lines ? launch_project_lines(st, A, a->B) : launch_project_points(st, A, a->B));
-    for (const Part& p : parts)
-        if (p.dst) PLP_HIP(hipMemcpyAsync(p.dst, base + p.off, p.bytes, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, B * 15); s.in(A.counts, B); s.in(A.pos_w, LM * (lines ? 6 : 3)); s.in(A.normal, LM * 3);
+    s.in(A.min_dist, LM); s.in(A.max_dist, LM); s.in(A.skip, BM);
+    s.out(A.reproj_d, BM * 2); s.out(A.reproj2_d, BM * 2); s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.x_right2, BM);
+    s.out(A.level, BM); s.out(A.valid, BM); s.out(A.status, BM); s.out(A.num_valid, B);
+    PLP_TRY(s.upload());
+    PLP_HIP(lines ? launch_project_lines(c->stream, A, a->B) : launch_project_points(c->stream, A, a->B));
+    return s.finish();
 }
 }  // namespace
 
@@ -853,31 +703,6 @@ Keylines3dArgs keylines_3d_args(const plp_keylines_3d_args* a) {
     A.pos_w = a->out_pos_w; A.valid = a->out_valid;
     return A;
 }
-
-// host pointers through the context's slab: inputs up, the outputs up as the caller holds them (slots past the counts keep their values), the
-// device path's kernel, the outputs back
-struct StagePart { const void* src; void* dst; size_t bytes; size_t off; };
-plp_status stage_run(plp_matcher* c, StagePart* parts, int n, uint8_t** base_out) {
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    size_t tot = 0;
-    for (int k = 0; k < n; ++k)
-        if ((parts[k].src || parts[k].dst) && parts[k].bytes) { parts[k].off = tot; tot += al(parts[k].bytes); }
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(c->stage.reserve(tot ? tot : 256));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    for (int k = 0; k < n; ++k) {
-        const StagePart& p = parts[k];
-        if ((p.src || p.dst) && p.bytes) PLP_HIP(hipMemcpyAsync(base + p.off, p.src ? p.src : p.dst, p.bytes, hipMemcpyHostToDevice, c->stream));
-    }
-    *base_out = base;
-    return PLP_OK;
-}
-plp_status stage_back(plp_matcher* c, const StagePart* parts, int n, uint8_t* base) {
-    for (int k = 0; k < n; ++k)
-        if (parts[k].dst && parts[k].bytes) PLP_HIP(hipMemcpyAsync(parts[k].dst, base + parts[k].off, parts[k].bytes, hipMemcpyDeviceToHost, c->stream));
-    PLP_HIP(hipStreamSynchronize(c->stream));
-    return PLP_OK;
-}
 }  // namespace
 
 plp_status plp_stereo_keylines_device(plp_matcher* c, const plp_stereo_keylines_args* a, void* hip_stream) {
@@ -893,22 +718,15 @@ plp_status plp_stereo_keylines_host(plp_matcher* c, const plp_stereo_keylines_ar
     if (plp_status s = stereo_keylines_check(c, a)) return s;
     if (a->cap_left == 0) return PLP_OK;
     const size_t B = (size_t)a->B, L = (size_t)a->cap_left, R = (size_t)a->cap_right;
-    const StereoKeylineArgs H = stereo_keylines_args(a);
-    StagePart parts[] = {
-        {H.kl_l, nullptr, B * L * sizeof(plp_keyline), 0}, {H.counts_l, nullptr, B * 4, 0}, {H.kl_r, nullptr, B * R * sizeof(plp_keyline), 0},
-        {H.counts_r, nullptr, B * 4, 0}, {H.train_idx, nullptr, B * L * 4, 0}, {H.dist, nullptr, B * L * 4, 0},
-        {nullptr, H.good, B * L * 4, 0}, {nullptr, H.depths, B * L * 8, 0}, {nullptr, H.x_right, B * L * 8, 0}};
+    StereoKeylineArgs A = stereo_keylines_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    StereoKeylineArgs A = H;
-    A.kl_l = (const plp_keyline*)dev(0); A.counts_l = (const int32_t*)dev(1); A.kl_r = (const plp_keyline*)dev(2); A.counts_r = (const int32_t*)dev(3);
-    A.train_idx = (const int32_t*)dev(4); A.dist = (const int32_t*)dev(5);
-    A.good = (int32_t*)dev(6); A.depths = (float*)dev(7); A.x_right = (float*)dev(8);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.kl_l, B * L); s.in(A.counts_l, B); s.in(A.kl_r, B * R); s.in(A.counts_r, B); s.in(A.train_idx, B * L); s.in(A.dist, B * L);
+    s.out(A.good, B * L); s.out(A.depths, B * L * 2); s.out(A.x_right, B * L * 2);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_stereo_keylines(c->stream, A, a->B));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 plp_status plp_keylines_3d_device(plp_matcher* c, const plp_keylines_3d_args* a, void* hip_stream) {
@@ -924,22 +742,15 @@ plp_status plp_keylines_3d_host(plp_matcher* c, const plp_keylines_3d_args* a) {
     if (plp_status s = keylines_3d_check(c, a)) return s;
     if (a->cap == 0) return PLP_OK;
     const size_t B = (size_t)a->B, M = (size_t)a->cap, R = (size_t)a->cap_right;
-    const Keylines3dArgs H = keylines_3d_args(a);
-    StagePart parts[] = {
-        {H.counts, nullptr, B * 4, 0}, {H.pose, nullptr, B * 15 * 8, 0}, {H.kl, nullptr, B * M * sizeof(plp_keyline), 0},
-        {H.kl_depths, nullptr, B * M * 8, 0}, {H.good_match, nullptr, B * M * 4, 0}, {H.kl_r, nullptr, B * R * sizeof(plp_keyline), 0},
-        {H.counts_r, nullptr, B * 4, 0}, {nullptr, H.pos_w, B * M * 48, 0}, {nullptr, H.valid, B * M, 0}};
+    Keylines3dArgs A = keylines_3d_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    Keylines3dArgs A = H;
-    A.counts = (const int32_t*)dev(0); A.pose = (const double*)dev(1); A.kl = (const plp_keyline*)dev(2); A.kl_depths = (const float*)dev(3);
-    A.good_match = (const int32_t*)dev(4); A.kl_r = (const plp_keyline*)dev(5); A.counts_r = (const int32_t*)dev(6);
-    A.pos_w = (double*)dev(7); A.valid = (uint8_t*)dev(8);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.counts, B); s.in(A.pose, B * 15); s.in(A.kl, B * M); s.in(A.kl_depths, B * M * 2); s.in(A.good_match, B * M); s.in(A.kl_r, B * R);
+    s.in(A.counts_r, B); s.out(A.pos_w, B * M * 6); s.out(A.valid, B * M);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_keylines_3d(c->stream, A, a->B));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 // ---- key-frame pair line triangulation (include/plp_front.h: plp_median_depth_*, plp_triangulate_keyline_pairs_*; keyline_pair_kernels.hip)
@@ -988,6 +799,13 @@ plp_status keyline_pairs_check(plp_matcher* c, const plp_keyline_pairs_args* a) 
     return PLP_OK;
 }
 
+plp_status check_pairs_in_table(const int32_t* pairs, int P, int F) {
+    for (int p = 0; p < P; ++p)
+        for (int k = 0; k < 2; ++k)
+            if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= F) return set_error(PLP_ERR_INVALID_ARG, "a pair names a key frame outside the table");
+    return PLP_OK;
+}
+
 // the preconditions of the _device path, checked where the lists are host memory
 plp_status keyline_pairs_check_groups(const plp_keyline_pairs_args* a) {
     int prev = 0;
@@ -996,9 +814,7 @@ plp_status keyline_pairs_check_groups(const plp_keyline_pairs_args* a) {
         if (o < prev || o > a->P) return set_error(PLP_ERR_INVALID_ARG, "group_offsets must be non-decreasing inside [0, P]");
         prev = o;
     }
-    for (int p = 0; p < a->P; ++p)
-        for (int k = 0; k < 2; ++k)
-            if (a->pairs[2 * p + k] < 0 || a->pairs[2 * p + k] >= a->F) return set_error(PLP_ERR_INVALID_ARG, "a pair names a key frame outside the table");
+    PLP_TRY(check_pairs_in_table(a->pairs, a->P, a->F));
     std::vector<uint8_t> seen((size_t)a->F);
     for (int g = 0; g < a->G; ++g) {
         const int b = a->group_offsets[g], e = a->group_offsets[g + 1];
@@ -1023,10 +839,8 @@ KeylinePairArgs keyline_pairs_args(const plp_keyline_pairs_args* a) {
     A.cos_thr = (float)std::cos(a->rays_parallax_deg_thr * M_PI / 180.0);   // two_view_triangulator_line.cc:41 into the float of .h:112
     A.dist_thr = a->dist_thr; A.endpoint_thr = a->endpoint_thr; A.angle_thr = a->angle_thr;
     A.ratio_factor = 2.0f * a->scale_factor;
-    for (int i = 0; i < 16; ++i) {
-        A.scale_factors[i] = i < a->num_levels ? a->scale_factors[i] : 1.0f;
-        A.level_sigma_sq[i] = i < a->num_levels ? a->level_sigma_sq[i] : 1.0f;
-    }
+    fill_levels(A.scale_factors, a->scale_factors, a->num_levels);
+    fill_levels(A.level_sigma_sq, a->level_sigma_sq, a->num_levels);
     A.kl = a->keylines; A.counts = a->counts; A.line_fn = a->line_functions; A.x_right = a->kl_x_right;
     A.kp_depths = a->kp_cap ? a->kp_depths : nullptr; A.kp_counts = a->kp_cap ? a->kp_counts : nullptr;
     A.pose = a->pose; A.median = a->median_depth; A.lines_3d = a->setup_type != 0 ? a->lines_3d : nullptr; A.occupied = a->occupied;
@@ -1047,19 +861,14 @@ plp_status plp_median_depth_device(plp_matcher* c, const plp_median_depth_args* 
 plp_status plp_median_depth_host(plp_matcher* c, const plp_median_depth_args* a) {
     if (plp_status s = median_depth_check(c, a)) return s;
     const size_t F = (size_t)a->F, M = (size_t)a->m_cap;
-    const MedianDepthArgs H = median_depth_args(a);
-    StagePart parts[] = {{H.pose, nullptr, F * 15 * 8, 0}, {H.pos_w, nullptr, F * M * 24, 0}, {H.valid, nullptr, F * M, 0}, {H.counts, nullptr, F * 4, 0},
-                         {nullptr, H.median, F * 4, 0}, {nullptr, H.count, F * 4, 0}};
+    MedianDepthArgs A = median_depth_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    MedianDepthArgs A = H;
-    A.pose = (const double*)dev(0); A.pos_w = (const double*)dev(1); A.valid = (const uint8_t*)dev(2); A.counts = (const int32_t*)dev(3);
-    A.median = (float*)dev(4); A.count = (int32_t*)dev(5);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, F * 15); s.in(A.pos_w, F * M * 3); s.in(A.valid, F * M); s.in(A.counts, F); s.out(A.median, F); s.out(A.count, F);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_median_depth(c->stream, A, a->F));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 plp_status plp_triangulate_keyline_pairs_device(plp_matcher* c, const plp_keyline_pairs_args* a, void* hip_stream) {
@@ -1076,27 +885,17 @@ plp_status plp_triangulate_keyline_pairs_host(plp_matcher* c, const plp_keyline_
     if (keyline_pairs_empty(a)) return PLP_OK;
     if (plp_status s = keyline_pairs_check_groups(a)) return s;
     const size_t F = (size_t)a->F, M = (size_t)a->cap, K = (size_t)a->kp_cap, P = (size_t)a->P, G = (size_t)a->G;
-    const KeylinePairArgs H = keyline_pairs_args(a);
-    StagePart parts[] = {
-        {H.kl, nullptr, F * M * sizeof(plp_keyline), 0}, {H.counts, nullptr, F * 4, 0}, {H.line_fn, nullptr, F * M * 24, 0},
-        {H.x_right, nullptr, F * M * 8, 0}, {H.kp_depths, nullptr, F * K * 4, 0}, {H.kp_counts, nullptr, F * 4, 0}, {H.pose, nullptr, F * 15 * 8, 0},
-        {H.median, nullptr, F * 4, 0}, {H.lines_3d, nullptr, F * M * 48, 0}, {H.occupied, nullptr, F * M, 0}, {H.pairs, nullptr, P * 8, 0},
-        {H.group_offsets, nullptr, (G + 1) * 4, 0}, {H.train_idx, nullptr, P * M * 4, 0}, {H.dist, nullptr, P * M * 4, 0},
-        {nullptr, H.out_match, P * M * 4, 0}, {nullptr, H.out_pos_w, P * M * 48, 0}, {nullptr, H.out_status, P * M, 0},
-        {nullptr, H.out_occ_cur, G * M, 0}};
+    KeylinePairArgs A = keyline_pairs_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    KeylinePairArgs A = H;
-    A.kl = (const plp_keyline*)dev(0); A.counts = (const int32_t*)dev(1); A.line_fn = (const double*)dev(2); A.x_right = (const float*)dev(3);
-    A.kp_depths = (const float*)dev(4); A.kp_counts = (const int32_t*)dev(5); A.pose = (const double*)dev(6); A.median = (const float*)dev(7);
-    A.lines_3d = (const double*)dev(8); A.occupied = (const uint8_t*)dev(9); A.pairs = (const int32_t*)dev(10);
-    A.group_offsets = (const int32_t*)dev(11); A.train_idx = (const int32_t*)dev(12); A.dist = (const int32_t*)dev(13);
-    A.out_match = (int32_t*)dev(14); A.out_pos_w = (double*)dev(15); A.out_status = (uint8_t*)dev(16); A.out_occ_cur = (uint8_t*)dev(17);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.kl, F * M); s.in(A.counts, F); s.in(A.line_fn, F * M * 3); s.in(A.x_right, F * M * 2); s.in(A.kp_depths, F * K); s.in(A.kp_counts, F);
+    s.in(A.pose, F * 15); s.in(A.median, F); s.in(A.lines_3d, F * M * 6); s.in(A.occupied, F * M); s.in(A.pairs, P * 2); s.in(A.group_offsets, G + 1);
+    s.in(A.train_idx, P * M); s.in(A.dist, P * M);
+    s.out(A.out_match, P * M); s.out(A.out_pos_w, P * M * 6); s.out(A.out_status, P * M); s.out(A.out_occ_cur, G * M);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_keyline_pairs(c->stream, A));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 // ---- key-frame pair point triangulation (include/plp_front.h: plp_keyframe_pair_geometry_*, plp_triangulate_keypoint_pairs_*; keypoint_pair_kernels.hip)
@@ -1122,13 +921,6 @@ PairGeometryArgs pair_geometry_args(const plp_keyframe_pair_geometry_args* a) {
     return A;
 }
 
-plp_status check_pairs_in_table(const int32_t* pairs, int P, int F) {
-    for (int p = 0; p < P; ++p)
-        for (int k = 0; k < 2; ++k)
-            if (pairs[2 * p + k] < 0 || pairs[2 * p + k] >= F) return set_error(PLP_ERR_INVALID_ARG, "a pair names a key frame outside the table");
-    return PLP_OK;
-}
-
 bool keypoint_pairs_empty(const plp_keypoint_pairs_args* a) { return a->cap == 0 || a->P == 0; }
 
 plp_status keypoint_pairs_check(plp_matcher* c, const plp_keypoint_pairs_args* a) {
@@ -1152,19 +944,15 @@ plp_status keypoint_pairs_check(plp_matcher* c, const plp_keypoint_pairs_args* a
 KeypointPairArgs keypoint_pairs_args(const plp_keypoint_pairs_args* a) {
     KeypointPairArgs A{};
     const plp_camera_model& cm = a->camera;
-    A.model = cm.model;
-    A.fx = cm.fx; A.fy = cm.fy; A.cx = cm.cx; A.cy = cm.cy; A.fxb = cm.focal_x_baseline;
-    A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
+    set_camera(A, cm);
     if (cm.model != PLP_CAMERA_EQUIRECTANGULAR) { A.fx_inv = 1.0 / cm.fx; A.fy_inv = 1.0 / cm.fy; }
     A.half_baseline = a->true_baseline / 2.0;
     A.setup_type = a->setup_type; A.num_levels = a->num_levels;
     A.F = a->F; A.cap = a->cap; A.m_cap = a->m_cap; A.P = a->P;
     A.cos_thr = (float)std::cos(a->rays_parallax_deg_thr * M_PI / 180.0);   // two_view_triangulator.cc:42 into the float of .h:110
     A.ratio_factor = 2.0f * a->scale_factor;
-    for (int i = 0; i < 16; ++i) {
-        A.scale_factors[i] = i < a->num_levels ? a->scale_factors[i] : 1.0f;
-        A.level_sigma_sq[i] = i < a->num_levels ? a->level_sigma_sq[i] : 1.0f;
-    }
+    fill_levels(A.scale_factors, a->scale_factors, a->num_levels);
+    fill_levels(A.level_sigma_sq, a->level_sigma_sq, a->num_levels);
     const bool stereo = a->setup_type != 0;
     A.kps = a->keypts; A.bearings = a->bearings; A.x_right = stereo ? a->x_right : nullptr; A.depths = stereo ? a->depths : nullptr;
     A.counts = a->counts; A.pose = a->pose; A.pairs = a->pairs; A.match_q = a->match_q; A.q_feature = a->q_feature; A.pair_skip = a->pair_skip;
@@ -1187,19 +975,14 @@ plp_status plp_keyframe_pair_geometry_host(plp_matcher* c, const plp_keyframe_pa
     if (a->P == 0) return PLP_OK;
     if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
     const size_t F = (size_t)a->F, P = (size_t)a->P;
-    const PairGeometryArgs H = pair_geometry_args(a);
-    StagePart parts[] = {{H.pose, nullptr, F * 15 * 8, 0}, {H.median, nullptr, F * 4, 0}, {H.pairs, nullptr, P * 8, 0},
-                         {nullptr, H.out_skip, P, 0}, {nullptr, H.out_epipolar, P * 96, 0}, {nullptr, H.out_baseline, P * 8, 0}};
+    PairGeometryArgs A = pair_geometry_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    PairGeometryArgs A = H;
-    A.pose = (const double*)dev(0); A.median = (const float*)dev(1); A.pairs = (const int32_t*)dev(2);
-    A.out_skip = (uint8_t*)dev(3); A.out_epipolar = (double*)dev(4); A.out_baseline = (double*)dev(5);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, F * 15); s.in(A.median, F); s.in(A.pairs, P * 2); s.out(A.out_skip, P); s.out(A.out_epipolar, P * 12); s.out(A.out_baseline, P);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_pair_geometry(c->stream, A));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 plp_status plp_triangulate_keypoint_pairs_device(plp_matcher* c, const plp_keypoint_pairs_args* a, void* hip_stream) {
@@ -1216,25 +999,16 @@ plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* c, const plp_keypoin
     if (keypoint_pairs_empty(a)) return PLP_OK;
     if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
     const size_t F = (size_t)a->F, M = (size_t)a->cap, Q = (size_t)a->m_cap, P = (size_t)a->P;
-    const KeypointPairArgs H = keypoint_pairs_args(a);
-    StagePart parts[] = {
-        {H.kps, nullptr, F * M * sizeof(plp_keypoint), 0}, {H.bearings, nullptr, F * M * 24, 0}, {H.x_right, nullptr, F * M * 4, 0},
-        {H.depths, nullptr, F * M * 4, 0}, {H.counts, nullptr, F * 4, 0}, {H.pose, nullptr, F * 15 * 8, 0}, {H.pairs, nullptr, P * 8, 0},
-        {H.match_q, nullptr, P * M * 4, 0}, {H.q_feature, nullptr, P * Q * 4, 0}, {H.pair_skip, nullptr, P, 0},
-        {nullptr, H.out_idx_1, P * M * 4, 0}, {nullptr, H.out_pos_w, P * M * 24, 0}, {nullptr, H.out_status, P * M, 0},
-        {nullptr, H.occ1, P * M, 0}, {nullptr, H.occ2, P * M, 0}};
+    KeypointPairArgs A = keypoint_pairs_args(a);
     std::lock_guard<std::mutex> lk(c->mu);
-    const int np = (int)(sizeof(parts) / sizeof(parts[0]));
-    uint8_t* base = nullptr;
-    if (plp_status s = stage_run(c, parts, np, &base)) return s;
-    auto dev = [&](int k) -> void* { return (parts[k].src || parts[k].dst) && parts[k].bytes ? base + parts[k].off : nullptr; };
-    KeypointPairArgs A = H;
-    A.kps = (const plp_keypoint*)dev(0); A.bearings = (const double*)dev(1); A.x_right = (const float*)dev(2); A.depths = (const float*)dev(3);
-    A.counts = (const int32_t*)dev(4); A.pose = (const double*)dev(5); A.pairs = (const int32_t*)dev(6); A.match_q = (const int32_t*)dev(7);
-    A.q_feature = (const int32_t*)dev(8); A.pair_skip = (const uint8_t*)dev(9);
-    A.out_idx_1 = (int32_t*)dev(10); A.out_pos_w = (double*)dev(11); A.out_status = (uint8_t*)dev(12); A.occ1 = (uint8_t*)dev(13); A.occ2 = (uint8_t*)dev(14);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.kps, F * M); s.in(A.bearings, F * M * 3); s.in(A.x_right, F * M); s.in(A.depths, F * M); s.in(A.counts, F); s.in(A.pose, F * 15);
+    s.in(A.pairs, P * 2); s.in(A.match_q, P * M); s.in(A.q_feature, P * Q); s.in(A.pair_skip, P);
+    s.out(A.out_idx_1, P * M); s.out(A.out_pos_w, P * M * 3); s.out(A.out_status, P * M); s.out(A.occ1, P * M); s.out(A.occ2, P * M);
+    PLP_TRY(s.upload());
     PLP_HIP(launch_keypoint_pairs(c->stream, A));
-    return stage_back(c, parts, np, base);
+    return s.finish();
 }
 
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
@@ -1355,18 +1129,15 @@ plp_status plp_landmark_descriptor_host(plp_matcher* c, const uint8_t* descs, co
         if (offsets[l + 1] < offsets[l] || offsets[l + 1] - offsets[l] > 1024) return set_error(PLP_ERR_UNSUPPORTED, "offsets must ascend, at most 1024 rows per landmark");
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    auto al = [](size_t v) { return (v + 255) / 256 * 256; };
-    const size_t o_d = 0, o_o = al((size_t)std::max<int64_t>(total, 1) * 32), o_b = o_o + al((size_t)(L + 1) * 4), tot = o_b + al((size_t)L * 4);
-    PLP_HIP(c->stage.reserve(tot));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    if (total) PLP_HIP(hipMemcpyAsync(base + o_d, descs, (size_t)total * 32, hipMemcpyHostToDevice, st));
-    PLP_HIP(hipMemcpyAsync(base + o_o, offsets, (size_t)(L + 1) * 4, hipMemcpyHostToDevice, st));
-    launch_landmark_descriptor(st, base + o_d, (const int32_t*)(base + o_o), L, (int32_t*)(base + o_b));
+    const uint8_t* d_descs = descs;   // device addresses after upload()
+    const int32_t* d_offsets = offsets;
+    int32_t* d_best_idx = best_idx;
+    Stage s(c->stage, c->stream);   // no row at all: the kernel reads no descriptor
+    s.in(d_descs, (size_t)total * 32); s.in(d_offsets, (size_t)L + 1); s.out(d_best_idx, L, false);
+    PLP_TRY(s.upload());
+    launch_landmark_descriptor(c->stream, d_descs, d_offsets, L, d_best_idx);
     PLP_HIP(hipGetLastError());
-    PLP_HIP(hipMemcpyAsync(best_idx, base + o_b, (size_t)L * 4, hipMemcpyDeviceToHost, st));
-    PLP_HIP(hipStreamSynchronize(st));
-    return PLP_OK;
+    return s.finish();
 }
 
 plp_status plp_match_debug_plan(const plp_match_args* a, int32_t* out4) {
@@ -1410,16 +1181,14 @@ plp_status plp_hamming_matrix_host(plp_matcher* c, const uint8_t* q, int32_t nq,
     if (nq <= 0 || nt <= 0) return PLP_OK;
     std::lock_guard<std::mutex> lk(c->mu);
     PLP_HIP(hipSetDevice(c->device));
-    const size_t bq = ((size_t)nq * 32 + 255) / 256 * 256, bt = ((size_t)nt * 32 + 255) / 256 * 256;
-    PLP_HIP(c->stage.reserve(bq + bt + (size_t)nq * nt * 2));
-    uint8_t* base = (uint8_t*)c->stage.p;
-    PLP_HIP(hipMemcpyAsync(base, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-    PLP_HIP(hipMemcpyAsync(base + bq, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
-    launch_hamming_matrix(c->stream, base, nq, base + bq, nt, (uint16_t*)(base + bq + bt));
+    const uint8_t *d_q = q, *d_t = t;   // device addresses after upload()
+    uint16_t* d_dist = dist;
+    Stage s(c->stage, c->stream);
+    s.in(d_q, (size_t)nq * 32); s.in(d_t, (size_t)nt * 32); s.out(d_dist, (size_t)nq * nt, false);
+    PLP_TRY(s.upload());
+    launch_hamming_matrix(c->stream, d_q, nq, d_t, nt, d_dist);
     PLP_HIP(hipGetLastError());
-    PLP_HIP(hipMemcpyAsync(dist, base + bq + bt, (size_t)nq * nt * 2, hipMemcpyDeviceToHost, c->stream));
-    PLP_HIP(hipStreamSynchronize(c->stream));
-    return PLP_OK;
+    return s.finish();
 }
 
 // Host model of the bin ranking inside the matchers' orientation check (csrc/libstdcxx_sort.hpp), callable without a GPU: the

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 #include "../../include/plp_front.h"
 
@@ -75,6 +76,50 @@ struct HostPinned {
         if (step == (size_t)cols) memcpy(d, src, (size_t)rows * cols);
         else for (int y = 0; y < rows; ++y) memcpy(d + (size_t)y * cols, src + (size_t)y * step, (size_t)cols);
     }
+};
+
+// The arrays of one host-pointer entry, staged through a context's slab.  Every array is declared once, by reference to the pointer field
+// of the kernel-argument struct that holds its HOST address, with its element count (bytes = count * sizeof(T)):
+//   in    uploaded;
+//   out   downloaded by finish().  keep: uploaded first, as the caller holds it.  The kernels write only the slots they compute (below a
+//         problem's count, not skipped), and finish() copies the whole block back, so the unwritten slots must hold the caller's values, as
+//         on the device entry (plp_front.h), not what an earlier call left in the slab.  keep = false is for an array every slot of which
+//         the kernel writes;
+//   room  a device-only region (scratch, an image packed elsewhere); the pointer's old value is ignored.
+// upload() lays the arrays out in the order declared, 256-byte aligned, reserves the slab, rewrites every declared pointer to its device
+// address and issues the host-to-device copies.  A NULL pointer or a count of 0 is not staged: the kernel sees NULL for it.
+// finish() issues the device-to-host copies and waits for the stream.  The slab must not be reserved again in between.
+// Nothing checks that every pointer field of an argument struct was declared: a field left out reaches the kernel as the caller's HOST
+// address.  After upload() a declared pointer is a device address, whatever its name: host code must not dereference it.
+class Stage {
+public:
+    Stage(DevBuf& slab, hipStream_t st) : slab_(slab), st_(st) { parts_.reserve(32); }
+    template <class T> void in(const T*& p, size_t count) { parts_.push_back({&p, p, nullptr, p ? count * sizeof(T) : 0, 0}); }
+    template <class T> void out(T*& p, size_t count, bool keep = true) { parts_.push_back({&p, keep ? p : nullptr, p, p ? count * sizeof(T) : 0, 0}); }
+    template <class T> void room(T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }
+    plp_status upload() {
+        size_t tot = 0;
+        for (Part& p : parts_) { p.off = tot; tot += (p.bytes + 255) / 256 * 256; }
+        PLP_HIP(slab_.reserve(tot));
+        for (const Part& p : parts_) {
+            void* d = p.bytes ? static_cast<uint8_t*>(slab_.p) + p.off : nullptr;
+            memcpy(p.field, &d, sizeof d);   // the field is a `T*` or `const T*` object: same representation
+            if (d && p.src) PLP_HIP(hipMemcpyAsync(d, p.src, p.bytes, hipMemcpyHostToDevice, st_));
+        }
+        return PLP_OK;
+    }
+    plp_status finish() {
+        for (const Part& p : parts_)
+            if (p.bytes && p.dst) PLP_HIP(hipMemcpyAsync(p.dst, static_cast<uint8_t*>(slab_.p) + p.off, p.bytes, hipMemcpyDeviceToHost, st_));
+        PLP_HIP(hipStreamSynchronize(st_));
+        return PLP_OK;
+    }
+
+private:
+    struct Part { void* field; const void* src; void* dst; size_t bytes; size_t off; };   // src: uploaded from; dst: downloaded to
+    DevBuf& slab_;
+    hipStream_t st_;
+    std::vector<Part> parts_;
 };
 
 }  // namespace plp
