@@ -31,29 +31,40 @@ def compare(img, grow_waves=(0, 1, 3)):
     return kl
 
 
-def compare_one(img, ora, waves, order=plp.SEED_ORDER_STABLE):
+def compare_one(img, ora, waves, order=plp.SEED_ORDER_STABLE, what="", need_lines=False):
     lt = plp.LineFeatureTracker()
     lt.set_grow_waves(waves)
     lt.set_seed_order(order)
     kl, lbd, fn = lt.extract_LSD_LBD(img)
-    assert np.array_equal(lt.debug_read(lt.DBG_SCALED), ora.scaled), "11-tap blur + x0.5 INTER_LINEAR_EXACT"
-    assert np.array_equal(lt.debug_read(lt.DBG_ORDER), ora.order[defined_seed(ora.scaled)[ora.order]]), "seed order (pixels with a defined angle: the others never start a region)"
-    raw = lt.debug_read(lt.DBG_RAW)
-    assert raw.shape == ora.raw.shape, (raw.shape, ora.raw.shape)
-    assert np.abs(raw - ora.raw).max(initial=0) <= 1e-4, "LSD segment end points"
-    assert np.array_equal(raw, ora.raw), "LSD segments (identical in practice)"
-    akl = lt.debug_read(lt.DBG_ALL_KL)
-    assert np.array_equal(akl, ora.all_kl), "KeyLine records"
-    if len(ora.all_kl):
-        n = img.shape[0] * img.shape[1]
-        assert np.array_equal(lt.debug_read(lt.DBG_SOBEL_DX)[:n].reshape(img.shape), ora.dx), "Sobel dx"
-        assert np.array_equal(lt.debug_read(lt.DBG_SOBEL_DY)[:n].reshape(img.shape), ora.dy), "Sobel dy"
-    albd = lt.debug_read(lt.DBG_ALL_LBD)
-    ham = np.unpackbits(albd ^ ora.all_lbd, axis=1).sum(1) if len(albd) else np.zeros(0)
-    assert ham.sum() == 0, f"LBD bits differ: hamming distances {ham[ham > 0]}"
-    assert np.array_equal(kl, ora.keylsd) and np.array_equal(lbd, ora.lbd)
-    assert np.array_equal(fn, ora.linefn)
+    compare_stages(lt, ora, img.shape, kl, lbd, fn, what=what, need_lines=need_lines)
     return kl
+
+
+def compare_stages(lt, ora, shape, kl, lbd, fn, frame=0, what="", need_lines=False):
+    """the stage planes and lists `lt` holds for frame `frame` of its last call, and that frame's results (kl, lbd, fn), against the oracle `ora` of the
+    same image and seed order; `what` starts every failure message (tests/test_gpu_line_passes.py: the shape and the setting).  The Sobel planes exist on
+    both sides only when there are key lines (the oracle returns early otherwise, as the reference does): need_lines=True makes their absence a failure."""
+    assert np.array_equal(lt.debug_read(lt.DBG_SCALED, frame), ora.scaled), what + "11-tap blur + x0.5 INTER_LINEAR_EXACT"
+    assert np.array_equal(lt.debug_read(lt.DBG_ORDER, frame), ora.order[defined_seed(ora.scaled)[ora.order]]), what + "seed order (pixels with a defined angle: the others never start a region)"
+    raw = lt.debug_read(lt.DBG_RAW, frame)
+    assert raw.shape == ora.raw.shape, what + f"number of LSD segments {raw.shape}, oracle {ora.raw.shape}"
+    assert np.abs(raw - ora.raw).max(initial=0) <= 1e-4, what + "LSD segment end points"
+    assert np.array_equal(raw, ora.raw), what + "LSD segments (identical in practice)"
+    akl = lt.debug_read(lt.DBG_ALL_KL, frame)
+    assert np.array_equal(akl, ora.all_kl), what + "KeyLine records"
+    if need_lines:
+        assert len(ora.all_kl) > 0, what + "the oracle has no key line: its Sobel planes are empty"
+    if len(ora.all_kl):
+        n = shape[0] * shape[1]
+        assert np.array_equal(lt.debug_read(lt.DBG_SOBEL_DX, frame)[:n].reshape(shape), ora.dx), what + "Sobel dx"
+        assert np.array_equal(lt.debug_read(lt.DBG_SOBEL_DY, frame)[:n].reshape(shape), ora.dy), what + "Sobel dy"
+    albd = lt.debug_read(lt.DBG_ALL_LBD, frame)
+    assert albd.shape == ora.all_lbd.shape, what + f"number of LBD rows {albd.shape}, oracle {ora.all_lbd.shape}"
+    ham = np.unpackbits(albd ^ ora.all_lbd, axis=1).sum(1) if len(albd) else np.zeros(0)
+    assert ham.sum() == 0, what + f"LBD bits differ: hamming distances {ham[ham > 0]}"
+    assert np.array_equal(kl, ora.keylsd), what + "kept key lines"
+    assert np.array_equal(lbd, ora.lbd), what + "kept LBD rows"
+    assert np.array_equal(fn, ora.linefn), what + "line functions"
 
 
 def test_line_front_matches_oracle_on_fixture_frames(golden_dir):
