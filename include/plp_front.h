@@ -987,6 +987,79 @@ typedef struct plp_keypoint_pairs_args {
 plp_status plp_triangulate_keypoint_pairs_device(plp_matcher* ctx, const plp_keypoint_pairs_args* args, void* hip_stream);
 plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* ctx, const plp_keypoint_pairs_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Landmark normals and valid distance ranges: landmark::update_normal_and_depth (src/PLPSLAM/data/landmark.cc:249-295) and
+ * Line::update_information (data/landmark_line.cc:311-352) for L landmarks at once, over a table of F key frames -- what the reference
+ * runs beside compute_descriptor (plp_landmark_descriptor_*) wherever landmark geometry changes: after triangulation, fusion
+ * (mapping_module.cc:619-650), every bundle adjustment and a map load.  The outputs are the tables plp_observe_args / plp_project_args
+ * read as obs_mean_normal, min_valid_dist and max_valid_dist.  Numeric contract: DESIGN.md section 5, D11.
+ *
+ * Landmark l owns the observations obs_offsets[l] .. obs_offsets[l + 1] - 1 of obs_kf / obs_idx (key frame, feature index), in the
+ * iteration order of the caller's observations_ map; no limit on their number.  Points (landmark.cc):
+ *   mean_normal = the left-to-right sum, in list order, of (pos_w - cam_center[obs_kf]).normalized() over EVERY observation (erased key
+ *                 frames included, unlike compute_descriptor), then normalized(); normalized() = v / sqrt((x x + y y) + z z), a zero
+ *                 vector stays zero                                                                                            :272-281, :293
+ *   max         = (float)(|pos_w - cam_center[ref_kf]| * (double)scale_factors[octave]), octave = that of key point obs_idx of the
+ *                 observation whose obs_kf == ref_kf (a precondition: at most one; the first is taken)                     :283-286, :291
+ *   min         = max / scale_factors[num_levels - 1], float / float                                                               :292
+ * Lines (landmark_line.cc), no normal:
+ *   distance    = |0.5 * (sp + ep) - cam_center[ref_kf]|                                                                       :336-342
+ *   level       = keylines[ref_kf][idx].octave, idx = the reference key frame's observation, or 0 when ref_kf is not among the
+ *                 observations (observations[ref_kf] is operator[])                                                                :343
+ *   max         = (float)(distance * (double)scale_factors_lsd[level])                                                       :344, :349
+ *   min         = max / scale_factors[num_levels_lsd - 1]: the ORB table indexed with the LSD level count, as the reference has it   :350
+ * out_status is written for every l < L; the value outputs only where it is PLP_LG_UPDATED (elsewhere they keep the caller's values,
+ * as the reference leaves its members).  The status says where the reference leaves the function, in its order of evaluation: skipped,
+ * no observations, a key frame outside the table (the loop over the observations and ref_keyfrm->get_cam_center() follow those pointers),
+ * the reference key frame not observed, its feature index out of range, its octave out of range. */
+typedef enum plp_landmark_geometry_status {
+    PLP_LG_UPDATED = 0,           /* the value outputs were written                                                                       */
+    PLP_LG_SKIPPED = 1,           /* skip[l]: will_be_erased_, the early return of landmark.cc:257-260 / landmark_line.cc:324-325         */
+    PLP_LG_NO_OBSERVATIONS = 2,   /* an empty list                                                    landmark.cc:266-269 / landmark_line.cc:333-334 */
+    PLP_LG_REF_NOT_OBSERVED = 3,  /* points only: ref_kf is not among the observations, observations.at(ref_keyfrm) throws (:285)         */
+    PLP_LG_INDEX_RANGE = 4,       /* ref_kf or an obs_kf outside [0, F), or the reference key frame's feature index outside
+                                     [0, counts[ref_kf]), where undist_keypts_.at() throws                                                 */
+    PLP_LG_OCTAVE_RANGE = 5       /* the octave outside [0, num_levels) (lines: [0, num_levels_lsd)), where scale_factors_.at() throws    */
+} plp_landmark_geometry_status;
+typedef struct plp_landmark_geometry_args {
+    int32_t F, cap;                 /* the table: F > 0 key frames of cap >= 0 key-point (lines: key-line) slots */
+    const double* pose;             /* F x 15: the plp_observe_args.pose row; only entries 12-14, cam_center_, are read */
+    const int32_t* counts;          /* F: num_keypts_ (lines: _keylsd.size()), or NULL = cap everywhere */
+    const plp_keypoint* keypts;     /* points: F x cap, undist_keypts_; only octave is read.  Ignored for lines */
+    const plp_keyline* keylines;    /* lines: F x cap, _keylsd; only octave is read.  Ignored for points */
+    const float* scale_factors;     /* HOST, num_levels: keyframe::scale_factors_ */
+    int32_t num_levels;             /* 1 .. 16: num_scale_levels_ */
+    const float* scale_factors_lsd; /* lines: HOST, num_levels_lsd: _scale_factors_lsd.  Ignored for points */
+    int32_t num_levels_lsd;         /* lines: 1 .. num_levels: _num_scale_levels_lsd.  Ignored for points */
+    int32_t L;                      /* L >= 0 landmarks */
+    const double* pos_w;            /* points: L x 3, pos_w_; lines: L x 6, _pos_w = (sp, ep) */
+    const int32_t* ref_kf;          /* L: ref_keyfrm_ as a row of the table */
+    const uint8_t* skip;            /* L, or NULL = none: will_be_erased_ */
+    const int32_t* obs_offsets;     /* L + 1, non-decreasing from 0 */
+    const int32_t* obs_kf;          /* obs_offsets[L]: the key frame of every observation, a row of the table */
+    const int32_t* obs_idx;         /* obs_offsets[L]: its feature index in that key frame */
+    double* out_mean_normal;        /* points: L x 3, mean_normal_.  Ignored for lines */
+    float* out_min_valid_dist;      /* L: the raw member min_valid_dist_ / _min_valid_dist (not the 0.7 / 0.8 getter) */
+    float* out_max_valid_dist;      /* L: max_valid_dist_ / _max_valid_dist (not the 1.3 / 1.2 getter) */
+    uint8_t* out_status;            /* L: a plp_landmark_geometry_status */
+} plp_landmark_geometry_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; F <= 0, cap < 0, L < 0; num_levels outside 1..16 or a NULL
+ * scale_factors; lines: num_levels_lsd outside 1..16, above num_levels (the reference would read past scale_factors_) or a NULL
+ * scale_factors_lsd; and -- when L > 0 -- a NULL pose, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_min_valid_dist,
+ * out_max_valid_dist or out_status, a NULL keypts / out_mean_normal (points) or keylines (lines) -- keypts / keylines may be NULL when
+ * cap == 0.  L == 0: PLP_OK, nothing written.  _host additionally checks that obs_offsets starts at 0 and is non-decreasing
+ * (PLP_ERR_INVALID_ARG) and ends at most at 2^31 - 257 (PLP_ERR_UNSUPPORTED); on the _device path these are preconditions.
+ * _device: every array but the two scale tables a DEVICE pointer; one kernel on hip_stream, no host synchronisation.
+ * _host: HOST pointers, staged (the outputs too, so that every slot the kernel does not write keeps the caller's value), the same
+ * kernel, synchronous. */
+plp_status plp_landmark_geometry_device(plp_matcher* ctx, const plp_landmark_geometry_args* args, void* hip_stream);
+plp_status plp_landmark_geometry_host(plp_matcher* ctx, const plp_landmark_geometry_args* args);
+plp_status plp_landmark_line_geometry_device(plp_matcher* ctx, const plp_landmark_geometry_args* args, void* hip_stream);
+plp_status plp_landmark_line_geometry_host(plp_matcher* ctx, const plp_landmark_geometry_args* args);
+/* Host build of the same source (csrc/landmark_geometry.hpp), HOST pointers, one landmark after the other: lines == 0 the point entry,
+ * else the line entry.  The same checks as the _host entries (no ctx).  No GPU needed.  Returns L, or -1 for a bad argument. */
+int32_t plp_model_landmark_geometry_host(const plp_landmark_geometry_args* args, int32_t lines);
+
 /* Input side: util::convert_to_grayscale (src/PLPSLAM/util/image_converter.cc:33-75, cv::cvtColor
  * RGB/BGR[A] -> gray on CV_8U) and util::convert_to_true_depth (:77-80, convertTo(CV_32F, 1 / depthmap_factor)), so that the
  * raw colour / 16-bit depth frames can go straight to HBM.  B frames, device pointers, asynchronous.

@@ -135,6 +135,11 @@ _API = [
     ("plp_keyframe_pair_geometry_host", C.c_int, [_VP, _VP]),
     ("plp_triangulate_keypoint_pairs_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_triangulate_keypoint_pairs_host", C.c_int, [_VP, _VP]),
+    ("plp_landmark_geometry_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_landmark_geometry_host", C.c_int, [_VP, _VP]),
+    ("plp_landmark_line_geometry_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_landmark_line_geometry_host", C.c_int, [_VP, _VP]),
+    ("plp_model_landmark_geometry_host", _I32, [_VP, _I32]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -223,6 +228,56 @@ def model_sincos(a):
     c = np.zeros(a.shape, np.float32); s = np.zeros(a.shape, np.float32); ok = np.zeros(a.shape, np.uint8)
     lib().plp_model_sincos_host(_p(a), a.size, _p(c), _p(s), _p(ok))
     return c, s, ok.astype(bool)
+
+
+def _landmark_geometry_host(call, lines, pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip, counts,
+                            out):
+    """the numpy side of plp_landmark[_line]_geometry_host and plp_model_landmark_geometry_host: call(args struct) runs the entry"""
+    po = np.ascontiguousarray(pose, np.float64).reshape(-1, 15)
+    F = len(po)
+    ft = np.ascontiguousarray(feats, KL_DTYPE if lines else KP_DTYPE).reshape(F, -1)
+    M = ft.shape[1]
+    pw = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 6 if lines else 3)
+    L = len(pw)
+    rk = np.ascontiguousarray(ref_kf, np.int32).reshape(L)
+    oo = np.ascontiguousarray(obs_offsets, np.int32).reshape(L + 1)
+    ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1)
+    oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+    if len(ok) != len(oi) or (L and int(oo[L]) > len(ok)):
+        raise PlpError(PLP_ERR_INVALID_ARG, "obs_kf and obs_idx must hold obs_offsets[L] entries each")
+    if L and len(ok) == 0:
+        ok, oi = np.zeros(1, np.int32), np.zeros(1, np.int32)            # lists without an entry: the arrays are still required
+    sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(L)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+    sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+    sl = np.ascontiguousarray(scale_factors_lsd, np.float32).reshape(-1) if lines else None
+    shapes = dict(min_dist=((L,), np.float32), max_dist=((L,), np.float32), status=((L,), np.uint8))
+    if not lines:
+        shapes["normal"] = ((L, 3), np.float64)
+    o = {}
+    for k, (shape, dt) in shapes.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
+        o[k] = v if v is not None else np.zeros(shape, dt)
+    P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(landmark_geometry_args_c, dict(F=F, cap=M, L=L, num_levels=len(sf), num_levels_lsd=len(sl) if lines else 0), dict(
+        pose=P(po), counts=P(cn), keypts=None if lines else P(ft), keylines=P(ft) if lines else None, scale_factors=P(sf), scale_factors_lsd=P(sl),
+        pos_w=P(pw), ref_kf=P(rk), skip=P(sk), obs_offsets=P(oo), obs_kf=P(ok), obs_idx=P(oi), out_mean_normal=P(o.get("normal")),
+        out_min_valid_dist=P(o["min_dist"]), out_max_valid_dist=P(o["max_dist"]), out_status=P(o["status"])))
+    call(a)
+    return o
+
+
+def model_landmark_geometry(pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd=None, skip=None, counts=None,
+                            lines=False, out=None):
+    """Host build of landmark::update_normal_and_depth / Line::update_information (csrc/landmark_geometry.hpp, DESIGN.md section 5, D11; no GPU
+    needed): the arguments and the result of matcher.landmark_geometry (lines: matcher.landmark_line_geometry)."""
+    def call(a):
+        if lib().plp_model_landmark_geometry_host(C.byref(a), int(bool(lines))) != a.L:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _landmark_geometry_host(call, bool(lines), pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip,
+                                   counts, out)
 
 
 def model_null_vector4(A):
@@ -758,6 +813,18 @@ class keypoint_pairs_args_c(C.Structure):
 # plp_keypoint_pair_status: where the reference leaves an iteration of triangulate_with_two_keyframes
 (KPP_CREATED, KPP_PAIR_SKIPPED, KPP_NO_MATCH, KPP_NO_PARALLAX, KPP_DEPTH, KPP_REPROJ_1, KPP_REPROJ_2, KPP_SCALE, KPP_NON_FINITE,
  KPP_INDEX_RANGE) = range(10)
+
+
+class landmark_geometry_args_c(C.Structure):
+    """plp_landmark_geometry_args"""
+    _fields_ = [("F", C.c_int32), ("cap", C.c_int32), ("pose", _VP), ("counts", _VP), ("keypts", _VP), ("keylines", _VP),
+                ("scale_factors", _VP), ("num_levels", C.c_int32), ("scale_factors_lsd", _VP), ("num_levels_lsd", C.c_int32), ("L", C.c_int32),
+                ("pos_w", _VP), ("ref_kf", _VP), ("skip", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("obs_idx", _VP),
+                ("out_mean_normal", _VP), ("out_min_valid_dist", _VP), ("out_max_valid_dist", _VP), ("out_status", _VP)]
+
+
+# plp_landmark_geometry_status: where landmark::update_normal_and_depth / Line::update_information leave a landmark
+LG_UPDATED, LG_SKIPPED, LG_NO_OBSERVATIONS, LG_REF_NOT_OBSERVED, LG_INDEX_RANGE, LG_OCTAVE_RANGE = range(6)
 
 
 def _struct(cls, fields, ptrs):
@@ -1512,6 +1579,56 @@ class matcher:
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_triangulate_keypoint_pairs_device(self._h, C.byref(a), st))
         del keep
+
+    def landmark_geometry(self, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, skip=None, counts=None, out=None):
+        """landmark::update_normal_and_depth for L landmarks (plp_landmark_geometry_host): pose (F, 15), keypts (F, cap) KP_DTYPE, pos_w (L, 3),
+        ref_kf (L,), skip (L,) u8 or None, the ragged observations obs_offsets (L + 1,) / obs_kf / obs_idx, scale_factors (num_levels,) f32.
+        Returns dict(normal (L, 3) f64, min_dist / max_dist (L,) f32: the raw members, status (L,) u8: LG_*); the values are written where
+        status is LG_UPDATED, elsewhere they keep 0 or out[name]."""
+        call = lambda a: _check(lib().plp_landmark_geometry_host(self._h, C.byref(a)))
+        return _landmark_geometry_host(call, False, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, None, skip, counts, out)
+
+    def landmark_line_geometry(self, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip=None,
+                               counts=None, out=None):
+        """Line::update_information for L line landmarks (plp_landmark_line_geometry_host): keylines (F, cap) KL_DTYPE, pos_w (L, 6),
+        scale_factors the ORB table, scale_factors_lsd (num_levels_lsd,) the LSD table.  Returns dict(min_dist, max_dist, status)."""
+        call = lambda a: _check(lib().plp_landmark_line_geometry_host(self._h, C.byref(a)))
+        return _landmark_geometry_host(call, True, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip,
+                                       counts, out)
+
+    def _landmark_geometry_device(self, lines, F, cap, L, pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_mean_normal, out_min_valid_dist,
+                                  out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip, counts, stream):
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        sl = np.ascontiguousarray(scale_factors_lsd, np.float32).reshape(-1) if lines else None    # both live until the call has returned
+        a = _struct(landmark_geometry_args_c, dict(F=int(F), cap=int(cap), L=int(L), num_levels=len(sf), num_levels_lsd=len(sl) if lines else 0), dict(
+            pose=D(pose), counts=D(counts), keypts=None if lines else D(feats), keylines=D(feats) if lines else None, scale_factors=sf.ctypes.data,
+            scale_factors_lsd=sl.ctypes.data if lines else None, pos_w=D(pos_w), ref_kf=D(ref_kf), skip=D(skip), obs_offsets=D(obs_offsets),
+            obs_kf=D(obs_kf), obs_idx=D(obs_idx), out_mean_normal=D(out_mean_normal), out_min_valid_dist=D(out_min_valid_dist),
+            out_max_valid_dist=D(out_max_valid_dist), out_status=D(out_status)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check((lib().plp_landmark_line_geometry_device if lines else lib().plp_landmark_geometry_device)(self._h, C.byref(a), st))
+
+    def landmark_geometry_device(self, F, cap, L, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_mean_normal, out_min_valid_dist,
+                                 out_max_valid_dist, out_status, scale_factors, skip=None, counts=None, stream=None):
+        """plp_landmark_geometry_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors is a host
+        vector); asynchronous, one kernel on the stream"""
+        self._landmark_geometry_device(False, F, cap, L, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_mean_normal, out_min_valid_dist,
+                                       out_max_valid_dist, out_status, scale_factors, None, skip, counts, stream)
+
+    def landmark_line_geometry_device(self, F, cap, L, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_min_valid_dist,
+                                      out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip=None, counts=None, stream=None):
+        """plp_landmark_line_geometry_device: as landmark_geometry_device, with the LSD scale table beside the ORB one and no normal"""
+        self._landmark_geometry_device(True, F, cap, L, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, None, out_min_valid_dist,
+                                       out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip, counts, stream)
+
+    def landmark_descriptors_device(self, descs, offsets, L, out_best_idx, stream=None):
+        """plp_landmark_descriptor_device: descs [total, 32] u8, offsets [L + 1] i32, out_best_idx [L] i32 on the matcher's device; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_landmark_descriptor_device(self._h, D(descs), D(offsets), int(L), D(out_best_idx), st))
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""

@@ -19,8 +19,9 @@ robust.cc:73-108 walks the feature vector in); the step derives that order from 
 q_feature.  Gathering the query arrays is torch indexing on the stream; the geometry, the search and the triangulation are the library's
 kernels.
 
-What stays on the host: `new data::landmark`, add_observation, compute_descriptor, update_normal_and_depth, map_db_->add_landmark and
-local_map_cleaner_->add_fresh_landmark (:459-477), which build map objects from the (idx_1, idx_2, pos_w) triples the step returns; and the
+What stays on the host: `new data::landmark`, add_observation, map_db_->add_landmark and local_map_cleaner_->add_fresh_landmark (:459-477),
+which build map objects from the (idx_1, idx_2, pos_w) triples the step returns (compute_descriptor and update_normal_and_depth of the new
+landmarks: landmark_refresh_step.py); and the
 `1 < i && keyframe_is_queued()` abort (:374), which a caller honours by passing fewer neighbours.
 
 Tables are torch tensors on the step's device, F key frames of `cap` key-point slots:

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <vector>
 
+#include "landmark_geometry.hpp"
 #include "libstdcxx_sort.hpp"
 #include "match_device.hpp"
 #include "plp_common.hpp"
@@ -1009,6 +1010,108 @@ plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* c, const plp_keypoin
     PLP_TRY(s.upload());
     PLP_HIP(launch_keypoint_pairs(c->stream, A));
     return s.finish();
+}
+
+// ---- landmark normals and valid distance ranges (include/plp_front.h: plp_landmark[_line]_geometry_*; landmark_geometry_kernels.hip)
+namespace {
+plp_status landmark_geometry_check(const plp_landmark_geometry_args* a, bool lines) {
+    if (!a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (a->F <= 0 || a->cap < 0 || a->L < 0) return set_error(PLP_ERR_INVALID_ARG, "F must be positive, cap and L non-negative");
+    if (a->num_levels < 1 || a->num_levels > 16 || !a->scale_factors) return set_error(PLP_ERR_INVALID_ARG, "num_levels must be 1 .. 16, scale_factors is required");
+    if (lines && (a->num_levels_lsd < 1 || a->num_levels_lsd > 16 || a->num_levels_lsd > a->num_levels || !a->scale_factors_lsd))
+        return set_error(PLP_ERR_INVALID_ARG, "num_levels_lsd must be 1 .. min(16, num_levels), scale_factors_lsd is required");
+    if (a->L == 0) return PLP_OK;
+    if (!a->pose || !a->pos_w || !a->ref_kf || !a->obs_offsets || !a->obs_kf || !a->obs_idx)
+        return set_error(PLP_ERR_INVALID_ARG, "pose, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx are required");
+    if (!a->out_min_valid_dist || !a->out_max_valid_dist || !a->out_status || (!lines && !a->out_mean_normal))
+        return set_error(PLP_ERR_INVALID_ARG, "out_min_valid_dist, out_max_valid_dist, out_status (points: out_mean_normal) are required");
+    if (a->cap > 0 && !(lines ? (const void*)a->keylines : (const void*)a->keypts)) return set_error(PLP_ERR_INVALID_ARG, "keypts (lines: keylines) is required");
+    return PLP_OK;
+}
+
+// the host entries' view of the lists (HOST pointers)
+plp_status landmark_geometry_check_offsets(const plp_landmark_geometry_args* a) {
+    if (a->obs_offsets[0] != 0) return set_error(PLP_ERR_INVALID_ARG, "obs_offsets must start at 0");
+    for (int l = 0; l < a->L; ++l)
+        if (a->obs_offsets[l + 1] < a->obs_offsets[l]) return set_error(PLP_ERR_INVALID_ARG, "obs_offsets must not decrease");
+    if (a->obs_offsets[a->L] > INT32_MAX - 256) return set_error(PLP_ERR_UNSUPPORTED, "more than 2^31 - 257 observations");
+    return PLP_OK;
+}
+
+LandmarkGeometryArgs landmark_geometry_args(const plp_landmark_geometry_args* a, bool lines) {
+    LandmarkGeometryArgs A{};
+    A.F = a->F; A.cap = a->cap; A.L = a->L; A.num_levels = a->num_levels; A.num_levels_lsd = lines ? a->num_levels_lsd : 1;
+    fill_levels(A.scale_factors, a->scale_factors, a->num_levels);
+    fill_levels(A.scale_factors_lsd, lines ? a->scale_factors_lsd : nullptr, A.num_levels_lsd);
+    A.pose = a->pose; A.counts = a->counts; A.kps = lines ? nullptr : a->keypts; A.kl = lines ? a->keylines : nullptr;
+    A.pos_w = a->pos_w; A.ref_kf = a->ref_kf; A.skip = a->skip; A.obs_offsets = a->obs_offsets; A.obs_kf = a->obs_kf; A.obs_idx = a->obs_idx;
+    A.normal = lines ? nullptr : a->out_mean_normal; A.min_dist = a->out_min_valid_dist; A.max_dist = a->out_max_valid_dist; A.status = a->out_status;
+    return A;
+}
+
+plp_status landmark_geometry_device(plp_matcher* c, const plp_landmark_geometry_args* a, void* hip_stream, bool lines) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = landmark_geometry_check(a, lines)) return s;
+    if (a->L == 0) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    const LandmarkGeometryArgs A = landmark_geometry_args(a, lines);
+    PLP_HIP(lines ? launch_landmark_geometry_lines((hipStream_t)hip_stream, A) : launch_landmark_geometry_points((hipStream_t)hip_stream, A));
+    return PLP_OK;
+}
+
+plp_status landmark_geometry_host(plp_matcher* c, const plp_landmark_geometry_args* a, bool lines) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = landmark_geometry_check(a, lines)) return s;
+    if (a->L == 0) return PLP_OK;
+    if (plp_status s = landmark_geometry_check_offsets(a)) return s;
+    const size_t F = (size_t)a->F, M = (size_t)a->cap, L = (size_t)a->L, T = (size_t)a->obs_offsets[a->L];
+    LandmarkGeometryArgs A = landmark_geometry_args(a, lines);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.pose, F * 15); s.in(A.counts, F); s.in(A.kps, F * M); s.in(A.kl, F * M); s.in(A.pos_w, L * (lines ? 6 : 3)); s.in(A.ref_kf, L); s.in(A.skip, L);
+    s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T);
+    s.out(A.normal, L * 3); s.out(A.min_dist, L); s.out(A.max_dist, L); s.out(A.status, L);
+    PLP_TRY(s.upload());
+    PLP_HIP(lines ? launch_landmark_geometry_lines(c->stream, A) : launch_landmark_geometry_points(c->stream, A));
+    return s.finish();
+}
+}  // namespace
+
+plp_status plp_landmark_geometry_device(plp_matcher* c, const plp_landmark_geometry_args* a, void* hip_stream) {
+    return landmark_geometry_device(c, a, hip_stream, false);
+}
+plp_status plp_landmark_geometry_host(plp_matcher* c, const plp_landmark_geometry_args* a) { return landmark_geometry_host(c, a, false); }
+plp_status plp_landmark_line_geometry_device(plp_matcher* c, const plp_landmark_geometry_args* a, void* hip_stream) {
+    return landmark_geometry_device(c, a, hip_stream, true);
+}
+plp_status plp_landmark_line_geometry_host(plp_matcher* c, const plp_landmark_geometry_args* a) { return landmark_geometry_host(c, a, true); }
+
+// the host build of landmark_geometry.hpp: the loops of the two kernels, one landmark after the other (no HIP call)
+int32_t plp_model_landmark_geometry_host(const plp_landmark_geometry_args* a, int32_t lines) {
+    if (landmark_geometry_check(a, lines != 0) != PLP_OK) return -1;
+    if (a->L == 0) return 0;
+    if (landmark_geometry_check_offsets(a) != PLP_OK) return -1;
+    const LandmarkGeometryArgs A = landmark_geometry_args(a, lines != 0);
+    for (int l = 0; l < A.L; ++l) {
+        if (lines) { A.status[l] = lg_line(A, l); continue; }
+        const int beg = A.obs_offsets[l], end = A.obs_offsets[l + 1], ref = A.ref_kf[l];
+        const double* p = A.pos_w + (size_t)3 * l;
+        double sx = 0.0, sy = 0.0, sz = 0.0;
+        int found = -1;
+        bool bad = false;
+        for (int o = beg; o < end; ++o) {
+            const int kf = A.obs_kf[o];
+            if ((unsigned)kf >= (unsigned)A.F) { bad = true; continue; }
+            const double* cc = A.pose + (size_t)15 * kf + 12;
+            const LgVec3 u = lg_normalized(p[0] - cc[0], p[1] - cc[1], p[2] - cc[2]);
+            sx = sx + u.x; sy = sy + u.y; sz = sz + u.z;
+            if (found < 0 && kf == ref) found = o;
+        }
+        A.status[l] = lg_point_finish(A, l, end - beg, sx, sy, sz, found, bad);
+    }
+    return A.L;
 }
 
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
