@@ -128,7 +128,8 @@ plp_status plp_orb_pyramid_host(plp_orb* ctx, int32_t frame, int32_t level, uint
  * per left key point the best right key point in its row band (Hamming < 75, octave +-1, disparity in [0, fx*b/b)),
  * 11x11 L1 patch slide on the pyramid level + parabola, 2x-median correlation rejection.  The image pyramids are the
  * ones `left` / `right` built in their last extract call (the reference passes orb_extractor::image_pyramid_).
- * Outputs: n_l floats each, -1 where no stereo match. */
+ * Outputs: n_l floats each, -1 where no stereo match.  More than 65535 key points on either side are refused with
+ * PLP_ERR_INVALID_ARG, as a `cap` above 65535 is by the batched entry (the kernel packs the right index into 16 bits). */
 plp_status plp_stereo_compute(plp_orb* left, plp_orb* right, const plp_keypoint* kps_l, int32_t n_l, const plp_keypoint* kps_r, int32_t n_r,
                               const uint8_t* desc_l, const uint8_t* desc_r, float focal_x_baseline, float true_baseline,
                               float* stereo_x_right, float* depths);

@@ -531,6 +531,7 @@ plp_status plp_stereo_compute(plp_orb* left, plp_orb* right, const plp_keypoint*
     if (!left || !right || !stereo_x_right || !depths) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (n_l <= 0) return PLP_OK;
     if (n_r < 0 || (n_r > 0 && (!kps_r || !desc_r)) || !kps_l || !desc_l) return set_error(PLP_ERR_INVALID_ARG, "bad argument");
+    if (n_l > 65535 || n_r > 65535) return set_error(PLP_ERR_INVALID_ARG, "more than 65535 key points (k_stereo_match packs the right index into 16 bits)");   // = the batched entry's cap check
     std::lock_guard<std::mutex> lk(left->mu);
     PLP_HIP(hipSetDevice(left->device));
     hipStream_t st = left->stream;
