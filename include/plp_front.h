@@ -1138,6 +1138,97 @@ plp_status plp_bow_transform_device(plp_bow_vocab* vocab, const uint8_t* d_desc,
 plp_status plp_bow_transform_host(plp_bow_vocab* vocab, const uint8_t* desc, int32_t n, int32_t levelsup, uint32_t* word_id, uint32_t* node_id,
                                   uint32_t* bow_word, double* bow_value, int32_t* n_bow, uint32_t* fv_node, uint32_t* fv_feat, int32_t* n_fv);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Place recognition: data::bow_database::acquire_loop_candidates (src/PLPSLAM/data/bow_database.cc:97-168) and
+ * acquire_relocalization_candidates (:170-236) with their helpers set_candidates_sharing_words (:247-287), compute_scores (:289-311),
+ * align_scores_and_keyframes (:313-331) and align_total_scores_and_keyframes (:333-378), for Q queries against one database of N rows --
+ * what module/relocalizer.cc:60 and module/loop_detector.cc:66-127 ask.  Numeric contract: DESIGN.md section 5, D12.
+ *
+ * The database is N BowVectors in the layout plp_bow_transform_device writes (row k: db_n[k] words, ascending, at db_word / db_value
+ * + k * stride), the queries Q more with a stride of their own.  The reference's inverted index, its unordered sets and maps become masks
+ * and arrays over the rows; nothing it returns depends on their iteration order.  Per query q (row k = key frame k):
+ *   common[k]   = |words(q) AND words(k)| for an alive row, 0 for a dead one (never added, or erased)            num_common_words_ :258-284
+ *   candidate   = common[k] > 0 && !reject[q][k]                                                                 init_candidates_ :276-279
+ *   max_common  = max of common over candidates; thr = (unsigned)(0.8f * (float)max_common), an f32 product               :119-127
+ *   score[k]    = (float)L1Scoring::score(query, row k) for candidates with thr < common[k]                               :294-308
+ *   kept[k]     = candidate && thr < common[k] && min_score[q] <= score[k]                                                :318-328
+ *   total[k]    = score[k] + score[c] (f32 adds, in covisibility order) over the c of covis[k] that are candidates with thr < common[c]
+ *                 -- kept or not, a row naming itself included; best_kf[k] = k, or the c whose score is the first to exceed the best so
+ *                 far; best_total = max(min_score[q], total[k] over kept k)                                               :337-375
+ *   final[best_kf[k]] = 1 for kept k with 0.75f * best_total < total[k]                                                   :153-165
+ * The score: DBoW2's L1Scoring (the ORB vocabulary's L1_NORM).  DBoW2 is not in the reference tree; the score is restated from the published
+ * algorithm, as the transform is -- parity unpinned (csrc/bow_score.hpp: one f64 accumulator over the common words in ascending order).
+ * scoring: the vocabulary's DBoW2 ScoringType; 0 (L1_NORM) is implemented, 1 .. 5 return PLP_ERR_UNSUPPORTED. */
+typedef enum plp_bow_query_status {
+    PLP_BOW_CANDIDATES = 0,       /* final holds the candidates                                                                    */
+    PLP_BOW_NO_COMMON_WORDS = 1,  /* no candidate shares a word: the return of bow_database.cc:111 / :180                          */
+    PLP_BOW_NO_SCORE = 2,         /* no score computed (:134 / :203).  Unreachable when max_common >= 1 -- the candidate that holds
+                                     the maximum is above thr -- and kept because the reference has the branch                     */
+    PLP_BOW_BELOW_MIN_SCORE = 3   /* nothing reaches min_score (:140 / :209)                                                        */
+} plp_bow_query_status;
+typedef struct plp_bow_query_args {
+    int32_t scoring;                /* DBoW2 ScoringType of the vocabulary: 0 = L1_NORM */
+    uint32_t n_words;               /* every word id is below n_words: a promise of the caller, used as an upper bound only (ids at or above it
+                                       count as not shared).  Up to 1,310,720 the count runs over a bitmap of the query in LDS, above over
+                                       the query's sorted words: the results are the same */
+    int32_t N, stride;              /* the database: N >= 0 rows of stride slots, 1 <= stride <= 8192 */
+    const uint32_t* db_word;        /* N x stride, ascending within a row */
+    const double* db_value;         /* N x stride */
+    const int32_t* db_n;            /* N: words of a row, taken as min(max(n, 0), stride) */
+    const uint8_t* db_alive;        /* N, or NULL = all alive */
+    int32_t Q, q_stride;            /* the queries: Q >= 0 rows of q_stride slots, 1 <= q_stride <= 8192 */
+    const uint32_t* q_word;
+    const double* q_value;
+    const int32_t* q_n;             /* a query with n = 0 gets status 1 */
+    const uint8_t* reject;          /* Q x N, or NULL = none: the query's connected key frames and the query itself (:107-108) */
+    const float* min_score;         /* Q, a DEVICE array on the _device entry, or NULL = 0.0f for every query (relocalisation, :209, :217) */
+    int32_t covis_cap;              /* 0 .. 16 slots of a covisibility row */
+    const int32_t* covis;           /* N x covis_cap: get_top_n_covisibilities(10) of row k, in that order; an entry outside [0, N) is passed over */
+    const int32_t* n_covis;         /* N: entries of a row, taken as min(max(n, 0), covis_cap); NULL = none */
+    /* outputs, [Q][N] unless noted; any may be NULL */
+    uint32_t* out_common;           /* 0 where nothing is shared or the row is dead */
+    float* out_score;               /* -1.0f where not computed */
+    float* out_total;               /* -1.0f where not kept */
+    int32_t* out_best_kf;           /* -1 where not kept */
+    uint8_t* out_final;             /* every byte written; all 0 unless status is 0 */
+    int32_t* out_n_final;           /* [Q]: set bytes of final */
+    uint32_t* out_max_common;       /* [Q] */
+    float* out_best_total;          /* [Q]: min_score where status is not 0 */
+    uint8_t* out_status;            /* [Q]: a plp_bow_query_status */
+} plp_bow_query_args;
+/* Checked before anything is written: NULL ctx / args, N < 0, Q < 0, a stride outside 1 .. 8192, covis_cap outside 0 .. 16, n_words == 0
+ * (PLP_ERR_INVALID_ARG); scoring outside 0 .. 5 (PLP_ERR_INVALID_ARG), 1 .. 5 (PLP_ERR_UNSUPPORTED); with N > 0 a NULL db_word / db_value /
+ * db_n, with Q > 0 a NULL q_word / q_value / q_n, with covis_cap > 0 and a non-NULL n_covis a NULL covis (PLP_ERR_INVALID_ARG).  Q == 0: PLP_OK,
+ * nothing written.  N == 0: PLP_OK, out_n_final and out_max_common zeroed, out_best_total = min_score, out_status = 1.
+ * _device: DEVICE pointers; four kernels on hip_stream and no host synchronisation (outputs passed as NULL live in a scratch buffer of the
+ * context, which grows on the first call of a size).  _host: HOST pointers, staged, the same kernels, synchronous. */
+plp_status plp_bow_query_device(plp_matcher* ctx, const plp_bow_query_args* args, void* hip_stream);
+plp_status plp_bow_query_host(plp_matcher* ctx, const plp_bow_query_args* args);
+
+/* Single scores with the same function: out_score[p] = (float)score(row a_row[p] of table A, row b_row[p] of table B), A's values as the
+ * first argument.  loop_detector::compute_min_score_in_covisibilities (module/loop_detector.cc:238-266) is the minimum of these over the
+ * covisibilities of a key frame and 1.0f; the will_be_erased filter (:248) and that minimum stay with the caller.  A row index outside its
+ * table gives -1.0f.  Checks as above (strides, scoring, NULL arrays when P > 0 or a table has rows); P == 0: PLP_OK, nothing written. */
+typedef struct plp_bow_score_pairs_args {
+    int32_t scoring;
+    int32_t NA, stride_a;           /* table A: NA rows */
+    const uint32_t* a_word;
+    const double* a_value;
+    const int32_t* a_n;
+    int32_t NB, stride_b;           /* table B (may be table A) */
+    const uint32_t* b_word;
+    const double* b_value;
+    const int32_t* b_n;
+    int32_t P;
+    const int32_t* a_row;           /* P */
+    const int32_t* b_row;           /* P */
+    float* out_score;               /* P */
+} plp_bow_score_pairs_args;
+plp_status plp_bow_score_pairs_device(plp_matcher* ctx, const plp_bow_score_pairs_args* args, void* hip_stream);
+plp_status plp_bow_score_pairs_host(plp_matcher* ctx, const plp_bow_score_pairs_args* args);
+/* Host build of the score (csrc/bow_score.hpp), HOST pointers, before the narrowing to float.  No GPU and no context needed. */
+double plp_model_bow_score_host(const uint32_t* wa, const double* va, int32_t na, const uint32_t* wb, const double* vb, int32_t nb);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

@@ -104,6 +104,11 @@ _API = [
     ("plp_bow_vocab_destroy", None, [_VP]),
     ("plp_bow_transform_device", C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_bow_transform_host", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_bow_query_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_bow_query_host", C.c_int, [_VP, _VP]),
+    ("plp_bow_score_pairs_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_bow_score_pairs_host", C.c_int, [_VP, _VP]),
+    ("plp_model_bow_score_host", C.c_double, [_VP, _VP, _I32, _VP, _VP, _I32]),
     ("plp_color_vote_device", C.c_int, [_VP, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
     ("plp_landmark_descriptor_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),
     ("plp_landmark_descriptor_host", C.c_int, [_VP, _VP, _VP, _I32, _VP]),
@@ -278,6 +283,17 @@ def model_landmark_geometry(pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs
             raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
     return _landmark_geometry_host(call, bool(lines), pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip,
                                    counts, out)
+
+
+def model_bow_score(wa, va, wb, vb):
+    """Host build of the BowVector score (csrc/bow_score.hpp, DESIGN.md section 5, D12; no GPU needed): DBoW2's L1Scoring::score of two vectors
+    given as ascending word ids and values, as f64 before the narrowing to float.  Restated from the published algorithm, parity unpinned."""
+    wa = np.ascontiguousarray(wa, np.uint32).reshape(-1); va = np.ascontiguousarray(va, np.float64).reshape(-1)
+    wb = np.ascontiguousarray(wb, np.uint32).reshape(-1); vb = np.ascontiguousarray(vb, np.float64).reshape(-1)
+    if len(wa) != len(va) or len(wb) != len(vb):
+        raise PlpError(PLP_ERR_INVALID_ARG, "words and values must have the same length")
+    P = lambda v: v.ctypes.data if v.size else None
+    return float(lib().plp_model_bow_score_host(P(wa), P(va), len(wa), P(wb), P(vb), len(wb)))
 
 
 def model_null_vector4(A):
@@ -825,6 +841,30 @@ class landmark_geometry_args_c(C.Structure):
 
 # plp_landmark_geometry_status: where landmark::update_normal_and_depth / Line::update_information leave a landmark
 LG_UPDATED, LG_SKIPPED, LG_NO_OBSERVATIONS, LG_REF_NOT_OBSERVED, LG_INDEX_RANGE, LG_OCTAVE_RANGE = range(6)
+
+
+class bow_query_args_c(C.Structure):
+    """plp_bow_query_args"""
+    _fields_ = [("scoring", C.c_int32), ("n_words", C.c_uint32), ("N", C.c_int32), ("stride", C.c_int32), ("db_word", _VP), ("db_value", _VP),
+                ("db_n", _VP), ("db_alive", _VP), ("Q", C.c_int32), ("q_stride", C.c_int32), ("q_word", _VP), ("q_value", _VP), ("q_n", _VP),
+                ("reject", _VP), ("min_score", _VP), ("covis_cap", C.c_int32), ("covis", _VP), ("n_covis", _VP), ("out_common", _VP),
+                ("out_score", _VP), ("out_total", _VP), ("out_best_kf", _VP), ("out_final", _VP), ("out_n_final", _VP), ("out_max_common", _VP),
+                ("out_best_total", _VP), ("out_status", _VP)]
+
+
+class bow_score_pairs_args_c(C.Structure):
+    """plp_bow_score_pairs_args"""
+    _fields_ = [("scoring", C.c_int32), ("NA", C.c_int32), ("stride_a", C.c_int32), ("a_word", _VP), ("a_value", _VP), ("a_n", _VP),
+                ("NB", C.c_int32), ("stride_b", C.c_int32), ("b_word", _VP), ("b_value", _VP), ("b_n", _VP), ("P", C.c_int32), ("a_row", _VP),
+                ("b_row", _VP), ("out_score", _VP)]
+
+
+# plp_bow_query_status: where acquire_loop_candidates / acquire_relocalization_candidates leave a query
+BOW_CANDIDATES, BOW_NO_COMMON_WORDS, BOW_NO_SCORE, BOW_BELOW_MIN_SCORE = range(4)
+BOW_BITMAP_WORDS = 1310720          # up to this n_words the count kernel tests bits of an LDS bitmap, above it bisects the query's words
+# the outputs of plp_bow_query_*: name -> (per row?, dtype)
+BOW_QUERY_OUTPUTS = dict(common=(True, np.uint32), score=(True, np.float32), total=(True, np.float32), best_kf=(True, np.int32), final=(True, np.uint8),
+                         n_final=(False, np.int32), max_common=(False, np.uint32), best_total=(False, np.float32), status=(False, np.uint8))
 
 
 def _struct(cls, fields, ptrs):
@@ -1623,6 +1663,74 @@ class matcher:
         self._landmark_geometry_device(True, F, cap, L, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, None, out_min_valid_dist,
                                        out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip, counts, stream)
 
+    def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
+                  scoring=0, outputs=None):
+        """data::bow_database::acquire_loop_candidates / acquire_relocalization_candidates for Q queries (plp_bow_query_host): db_word (N, stride)
+        u32 ascending per row, db_value (N, stride) f64, db_n (N,), db_alive (N,) u8 or None; q_word / q_value (Q, q_stride), q_n (Q,); reject
+        (Q, N) u8 or None; min_score (Q,) f32 or None = 0; covis (N, covis_cap) i32 with n_covis (N,), or None.  Returns a dict of the outputs
+        named in `outputs` (default: all of BOW_QUERY_OUTPUTS): common, score, total, best_kf, final (Q, N); n_final, max_common, best_total,
+        status (Q,)."""
+        dw = np.ascontiguousarray(db_word, np.uint32); dv = np.ascontiguousarray(db_value, np.float64)
+        qw = np.ascontiguousarray(q_word, np.uint32); qv = np.ascontiguousarray(q_value, np.float64)
+        if dw.ndim != 2 or qw.ndim != 2 or dv.shape != dw.shape or qv.shape != qw.shape:
+            raise PlpError(PLP_ERR_INVALID_ARG, "db_word / db_value must be (N, stride) and q_word / q_value (Q, q_stride)")
+        (N, stride), (Q, q_stride) = dw.shape, qw.shape
+        dn = np.ascontiguousarray(db_n, np.int32).reshape(N); qn = np.ascontiguousarray(q_n, np.int32).reshape(Q)
+        al = None if db_alive is None else np.ascontiguousarray(db_alive, np.uint8).reshape(N)
+        rj = None if reject is None else np.ascontiguousarray(reject, np.uint8).reshape(Q, N)
+        ms = None if min_score is None else np.ascontiguousarray(min_score, np.float32).reshape(Q)
+        cv = None if covis is None else np.ascontiguousarray(covis, np.int32)
+        if cv is not None and (cv.ndim != 2 or cv.shape[0] != N):
+            raise PlpError(PLP_ERR_INVALID_ARG, "covis must be (N, covis_cap)")
+        nc = None if covis is None else np.ascontiguousarray(n_covis, np.int32).reshape(N)
+        o = {k: np.zeros((Q, N) if rows else (Q,), dt) for k, (rows, dt) in BOW_QUERY_OUTPUTS.items() if outputs is None or k in outputs}
+        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        a = _struct(bow_query_args_c, dict(scoring=int(scoring), n_words=int(n_words), N=N, stride=stride, Q=Q, q_stride=q_stride,
+                                           covis_cap=0 if cv is None else cv.shape[1]),
+                    dict(db_word=P(dw), db_value=P(dv), db_n=P(dn), db_alive=P(al), q_word=P(qw), q_value=P(qv), q_n=P(qn), reject=P(rj), min_score=P(ms),
+                         covis=P(cv), n_covis=P(nc), **{"out_" + k: P(v) for k, v in o.items()}))
+        _check(lib().plp_bow_query_host(self._h, C.byref(a)))
+        return o
+
+    def bow_query_device(self, n_words, N, stride, db_word, db_value, db_n, Q, q_stride, q_word, q_value, q_n, out, db_alive=None, reject=None,
+                         min_score=None, covis_cap=0, covis=None, n_covis=None, scoring=0, stream=None):
+        """plp_bow_query_device: every array a device pointer (int) or a torch tensor on the matcher's device -- min_score too; `out` maps names of
+        BOW_QUERY_OUTPUTS to tensors (the others are not written); asynchronous, four kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(bow_query_args_c, dict(scoring=int(scoring), n_words=int(n_words), N=int(N), stride=int(stride), Q=int(Q), q_stride=int(q_stride),
+                                           covis_cap=int(covis_cap)),
+                    dict(db_word=D(db_word), db_value=D(db_value), db_n=D(db_n), db_alive=D(db_alive), q_word=D(q_word), q_value=D(q_value), q_n=D(q_n),
+                         reject=D(reject), min_score=D(min_score), covis=D(covis), n_covis=D(n_covis), **{"out_" + k: D(v) for k, v in out.items()}))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_bow_query_device(self._h, C.byref(a), st))
+
+    def bow_score_pairs(self, a_word, a_value, a_n, b_word, b_value, b_n, a_row, b_row, scoring=0):
+        """plp_bow_score_pairs_host: (float)score(row a_row[p] of table A, row b_row[p] of table B), (P,) f32; tables as in bow_query"""
+        aw = np.ascontiguousarray(a_word, np.uint32); av = np.ascontiguousarray(a_value, np.float64)
+        bw = np.ascontiguousarray(b_word, np.uint32); bv = np.ascontiguousarray(b_value, np.float64)
+        if aw.ndim != 2 or bw.ndim != 2 or av.shape != aw.shape or bv.shape != bw.shape:
+            raise PlpError(PLP_ERR_INVALID_ARG, "the tables must be (rows, stride)")
+        an = np.ascontiguousarray(a_n, np.int32).reshape(aw.shape[0]); bn = np.ascontiguousarray(b_n, np.int32).reshape(bw.shape[0])
+        ar = np.ascontiguousarray(a_row, np.int32).reshape(-1); br = np.ascontiguousarray(b_row, np.int32).reshape(len(ar))
+        out = np.zeros(len(ar), np.float32)
+        P = lambda v: None if v.size == 0 else v.ctypes.data
+        a = _struct(bow_score_pairs_args_c, dict(scoring=int(scoring), NA=aw.shape[0], stride_a=aw.shape[1], NB=bw.shape[0], stride_b=bw.shape[1], P=len(ar)),
+                    dict(a_word=P(aw), a_value=P(av), a_n=P(an), b_word=P(bw), b_value=P(bv), b_n=P(bn), a_row=P(ar), b_row=P(br), out_score=P(out)))
+        _check(lib().plp_bow_score_pairs_host(self._h, C.byref(a)))
+        return out
+
+    def bow_score_pairs_device(self, NA, stride_a, a_word, a_value, a_n, NB, stride_b, b_word, b_value, b_n, P, a_row, b_row, out_score, scoring=0,
+                               stream=None):
+        """plp_bow_score_pairs_device: device pointers (int) or torch tensors; asynchronous, one kernel on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(bow_score_pairs_args_c, dict(scoring=int(scoring), NA=int(NA), stride_a=int(stride_a), NB=int(NB), stride_b=int(stride_b), P=int(P)),
+                    dict(a_word=D(a_word), a_value=D(a_value), a_n=D(a_n), b_word=D(b_word), b_value=D(b_value), b_n=D(b_n), a_row=D(a_row),
+                         b_row=D(b_row), out_score=D(out_score)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_bow_score_pairs_device(self._h, C.byref(a), st))
+
     def landmark_descriptors_device(self, descs, offsets, L, out_best_idx, stream=None):
         """plp_landmark_descriptor_device: descs [total, 32] u8, offsets [L + 1] i32, out_best_idx [L] i32 on the matcher's device; asynchronous"""
         import torch
@@ -1870,3 +1978,153 @@ class bow_vocabulary:
         for nd, fi in zip(fn[:nf.value].tolist(), ff[:nf.value].tolist()):
             feat_vec.setdefault(nd, []).append(fi)
         return bow_vec, feat_vec, word[:n].copy(), node[:n].copy()
+
+
+# ------------------------------------------------------------------------------------------------
+class bow_database:
+    """Mirror of data::bow_database (src/PLPSLAM/data/bow_database.cc) on the device: a table of BowVectors, one row per key frame, in the layout
+    bow_vocabulary.transform_device writes, and the two candidate queries over it (plp_bow_query_device).  The caller binds key-frame ids to rows
+    (INTEGRATION.md section 3).  The score is DBoW2's L1 score restated from the published algorithm: parity unpinned.
+
+    n_words: an upper bound of every word id (the vocabulary's word count); stride: slots of a row (the cap of the transform, or tighter);
+    covis_cap: slots of a covisibility row (get_top_n_covisibilities(10) -> 10).  The tables grow by doubling."""
+
+    def __init__(self, n_words, stride, covis_cap=10, scoring=L1_NORM, capacity=64, device=0):
+        import torch
+        if scoring != L1_NORM:
+            raise PlpError(PLP_ERR_UNSUPPORTED, "only L1_NORM scoring is implemented")
+        if not (1 <= stride <= 8192 and 0 <= covis_cap <= 16 and n_words > 0):
+            raise PlpError(PLP_ERR_INVALID_ARG, "stride must be 1 .. 8192, covis_cap 0 .. 16, n_words positive")
+        self.torch, self.dev, self.device = torch, torch.device("cuda", device), device
+        self.n_words, self.stride, self.covis_cap, self.scoring = int(n_words), int(stride), int(covis_cap), int(scoring)
+        self.N = 0                                 # rows in use: 1 + the highest row ever added
+        self.mt = matcher(device=device)
+        self._alloc(max(int(capacity), 1))
+
+    def _alloc(self, cap):
+        torch = self.torch
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.dev)
+        new = dict(word=z((cap, self.stride), torch.int32), value=z((cap, self.stride), torch.float64), n=z((cap,), torch.int32),
+                   alive=z((cap,), torch.uint8), covis=z((cap, max(self.covis_cap, 1)), torch.int32), n_covis=z((cap,), torch.int32))
+        old = getattr(self, "t", None)
+        if old is not None:
+            for k, v in old.items():
+                new[k][:v.shape[0]].copy_(v)
+        self.t, self.capacity = new, cap
+
+    def _stream(self, stream):
+        return stream or self.torch.cuda.current_stream(self.dev)
+
+    def add_keyframe(self, row, bow_word, bow_value, n_bow, stream=None):
+        """bow_database::add_keyframe (:24-40): row <- one BowVector.  bow_word / bow_value: 1-D device tensors (a row of transform_device's
+        bow_word / bow_value; the first min(len, stride) slots are copied), n_bow: its count, a device tensor of one element or an int, of which at
+        most `stride` are used.  Device copies on the stream."""
+        torch = self.torch
+        row = int(row)
+        with torch.cuda.stream(self._stream(stream)):
+            if row >= self.capacity:
+                cap = self.capacity
+                while cap <= row:
+                    cap *= 2
+                self._alloc(cap)
+            m = min(int(bow_word.shape[0]), self.stride)
+            self.t["word"][row, :m].copy_(bow_word[:m].view(torch.int32) if bow_word.dtype != torch.int32 else bow_word[:m])
+            self.t["value"][row, :m].copy_(bow_value[:m])
+            if isinstance(n_bow, int):
+                self.t["n"][row:row + 1].fill_(min(n_bow, m))
+            else:
+                self.t["n"][row:row + 1].copy_(n_bow.reshape(1).clamp(max=m))
+            self.t["alive"][row:row + 1].fill_(1)
+        self.N = max(self.N, row + 1)
+
+    def erase_keyframe(self, row, stream=None):
+        """bow_database::erase_keyframe (:42-66): the row shares no word with anything from now on"""
+        if 0 <= int(row) < self.N:
+            with self.torch.cuda.stream(self._stream(stream)):
+                self.t["alive"][int(row):int(row) + 1].fill_(0)
+
+    def clear(self, stream=None):
+        """bow_database::clear (:68-77)"""
+        with self.torch.cuda.stream(self._stream(stream)):
+            self.t["alive"].zero_()
+            self.t["n_covis"].zero_()
+        self.N = 0
+
+    def set_covisibilities(self, row, rows, stream=None):
+        """the key frame's get_top_n_covisibilities(10), as database rows in that order: a list of ints or a device i32 tensor"""
+        torch = self.torch
+        row, n = int(row), len(rows)
+        if not (0 <= row < self.capacity) or n > self.covis_cap:
+            raise PlpError(PLP_ERR_INVALID_ARG, "row outside the table or more than covis_cap covisibilities")
+        with torch.cuda.stream(self._stream(stream)):
+            if n:
+                src = rows if isinstance(rows, torch.Tensor) else torch.tensor([int(r) for r in rows], dtype=torch.int32).to(self.dev)
+                self.t["covis"][row, :n].copy_(src)
+            self.t["n_covis"][row:row + 1].fill_(n)
+
+    def _query_device(self, q_word, q_value, q_n, min_score, reject, stream, outputs):
+        torch = self.torch
+        if q_word.dim() == 1:
+            q_word, q_value, q_n = q_word.unsqueeze(0), q_value.unsqueeze(0), q_n.reshape(1)
+        Q, qs = q_word.shape
+        if not (q_word.is_contiguous() and q_value.is_contiguous()):
+            raise PlpError(PLP_ERR_INVALID_ARG, "q_word and q_value must be contiguous (Q, q_stride) tensors")
+        st = self._stream(stream)
+        tt = {np.uint32: torch.int32, np.float32: torch.float32, np.int32: torch.int32, np.uint8: torch.uint8}
+        with torch.cuda.stream(st):
+            out = {k: torch.empty((Q, self.N) if rows else (Q,), dtype=tt[dt], device=self.dev) for k, (rows, dt) in BOW_QUERY_OUTPUTS.items()
+                   if outputs is None or k in outputs}
+        t = self.t
+        self.mt.bow_query_device(self.n_words, self.N, self.stride, t["word"], t["value"], t["n"], Q, qs, q_word, q_value, q_n, out, db_alive=t["alive"],
+                                 reject=reject, min_score=min_score, covis_cap=self.covis_cap, covis=t["covis"] if self.covis_cap else None,
+                                 n_covis=t["n_covis"] if self.covis_cap else None, scoring=self.scoring, stream=st)
+        return out
+
+    def acquire_loop_candidates_device(self, q_word, q_value, q_n, min_score, reject=None, stream=None, outputs=None):
+        """bow_database::acquire_loop_candidates (:97-168) for Q query key frames: q_word / q_value (Q, q_stride) and q_n (Q,) device tensors (or one
+        query, 1-D), min_score (Q,) f32 DEVICE tensor (score_pairs_device -> torch minimum: it never visits the host), reject (Q, N) u8 device tensor
+        -- the query's connected key frames and the query itself -- or None.  Returns the device tensors of BOW_QUERY_OUTPUTS (u32 as i32);
+        `final` is the candidate mask over the rows.  Asynchronous."""
+        if reject is not None and tuple(reject.shape)[-1] != self.N:
+            raise PlpError(PLP_ERR_INVALID_ARG, "reject must be (Q, N) for the N rows in use")
+        return self._query_device(q_word, q_value, q_n, min_score, reject, stream, outputs)
+
+    def acquire_relocalization_candidates_device(self, q_word, q_value, q_n, stream=None, outputs=None):
+        """bow_database::acquire_relocalization_candidates (:170-236): no rejected key frames, min_score 0"""
+        return self._query_device(q_word, q_value, q_n, None, None, stream, outputs)
+
+    def _rows(self, out, single):
+        self.torch.cuda.current_stream(self.dev).synchronize()
+        final = out["final"].cpu().numpy()
+        lists = [np.flatnonzero(f).tolist() for f in final]
+        return lists[0] if single else lists
+
+    def acquire_loop_candidates(self, q_word, q_value, q_n, min_score, reject=None):
+        """host form: the sorted list of candidate rows (a list per query for 2-D queries); min_score a float, a sequence or a device tensor"""
+        torch = self.torch
+        single = q_word.dim() == 1
+        if not isinstance(min_score, torch.Tensor):
+            min_score = torch.tensor(np.asarray(min_score, np.float32).reshape(-1)).to(self.dev)
+        return self._rows(self.acquire_loop_candidates_device(q_word, q_value, q_n, min_score, reject, outputs=("final",)), single)
+
+    def acquire_relocalization_candidates(self, q_word, q_value, q_n):
+        return self._rows(self.acquire_relocalization_candidates_device(q_word, q_value, q_n, outputs=("final",)), q_word.dim() == 1)
+
+    def score_pairs_device(self, a_rows, b_rows, stream=None):
+        """(float)bow_vocab_->score(row a, row b) for device i32 tensors of rows of this database: (P,) f32 device tensor.  The minimum of these over
+        a key frame's covisibilities and 1.0f is loop_detector::compute_min_score_in_covisibilities (module/loop_detector.cc:238-266)."""
+        torch = self.torch
+        P = int(a_rows.shape[0])
+        st = self._stream(stream)
+        with torch.cuda.stream(st):
+            out = torch.empty((P,), dtype=torch.float32, device=self.dev)
+        t = self.t
+        self.mt.bow_score_pairs_device(self.N, self.stride, t["word"], t["value"], t["n"], self.N, self.stride, t["word"], t["value"], t["n"], P, a_rows,
+                                       b_rows, out, scoring=self.scoring, stream=st)
+        return out
+
+    def score(self, a, b):
+        """bow_vocab_->score(bow_vec of row a, bow_vec of row b) as the float the reference keeps"""
+        torch = self.torch
+        rows = torch.tensor([[int(a)], [int(b)]], dtype=torch.int32).to(self.dev)
+        return float(self.score_pairs_device(rows[0], rows[1]).cpu()[0])

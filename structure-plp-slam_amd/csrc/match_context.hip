@@ -7,6 +7,8 @@
 #include <mutex>
 #include <vector>
 
+#include "bow_database.hpp"
+#include "bow_score.hpp"
 #include "landmark_geometry.hpp"
 #include "libstdcxx_sort.hpp"
 #include "match_device.hpp"
@@ -19,6 +21,7 @@ struct plp_matcher {
     hipStream_t stream = nullptr;
     DevBuf klist, klist2, kcount, claim, full_list, sorted, sorted_xr, row_start, dbg;  // scratch of the device path
     DevBuf stage;                            // one slab for the host-pointer path
+    DevBuf bow_scratch;                      // plp_bow_query_device: the per-row arrays the caller did not ask for
     HostPinned pin;                          // page-locked staging of host images (post-extract depth)
     std::mutex mu;
 };
@@ -1112,6 +1115,148 @@ int32_t plp_model_landmark_geometry_host(const plp_landmark_geometry_args* a, in
         A.status[l] = lg_point_finish(A, l, end - beg, sx, sy, sz, found, bad);
     }
     return A.L;
+}
+
+// ---- place recognition (include/plp_front.h: plp_bow_query_*, plp_bow_score_pairs_*; bow_database_kernels.hip)
+namespace {
+plp_status bow_scoring_check(int32_t scoring) {
+    if (scoring < 0 || scoring > 5) return set_error(PLP_ERR_INVALID_ARG, "scoring must be a DBoW2 ScoringType, 0 .. 5");
+    if (scoring != 0) return set_error(PLP_ERR_UNSUPPORTED, "only L1_NORM scoring (0) is implemented");
+    return PLP_OK;
+}
+
+plp_status bow_query_check(const plp_bow_query_args* a) {
+    if (!a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (a->N < 0 || a->Q < 0) return set_error(PLP_ERR_INVALID_ARG, "N and Q must not be negative");
+    if (a->stride < 1 || a->stride > 8192 || a->q_stride < 1 || a->q_stride > 8192) return set_error(PLP_ERR_INVALID_ARG, "stride and q_stride must be 1 .. 8192");
+    if (a->covis_cap < 0 || a->covis_cap > 16) return set_error(PLP_ERR_INVALID_ARG, "covis_cap must be 0 .. 16");
+    if (a->n_words == 0) return set_error(PLP_ERR_INVALID_ARG, "n_words must be positive");
+    if (plp_status s = bow_scoring_check(a->scoring)) return s;
+    if (a->Q > 65535) return set_error(PLP_ERR_UNSUPPORTED, "more than 65535 queries in one call");
+    if (a->N > 0 && (!a->db_word || !a->db_value || !a->db_n)) return set_error(PLP_ERR_INVALID_ARG, "db_word, db_value, db_n are required");
+    if (a->Q > 0 && (!a->q_word || !a->q_value || !a->q_n)) return set_error(PLP_ERR_INVALID_ARG, "q_word, q_value, q_n are required");
+    if (a->N > 0 && a->covis_cap > 0 && a->n_covis && !a->covis) return set_error(PLP_ERR_INVALID_ARG, "covis is required beside n_covis");
+    return PLP_OK;
+}
+
+BowQueryArgs bow_query_args(const plp_bow_query_args* a) {
+    BowQueryArgs A{};
+    A.n_words = a->n_words; A.N = a->N; A.stride = a->stride; A.Q = a->Q; A.q_stride = a->q_stride; A.covis_cap = a->covis_cap;
+    A.db_word = a->db_word; A.db_value = a->db_value; A.db_n = a->db_n; A.db_alive = a->db_alive;
+    A.q_word = a->q_word; A.q_value = a->q_value; A.q_n = a->q_n; A.reject = a->reject; A.min_score = a->min_score;
+    A.covis = a->covis; A.n_covis = a->covis_cap > 0 ? a->n_covis : nullptr;
+    A.common = a->out_common; A.score = a->out_score; A.total = a->out_total; A.best_kf = a->out_best_kf; A.final_mask = a->out_final;
+    A.max_common = a->out_max_common; A.n_final = a->out_n_final; A.best_total = a->out_best_total; A.status = a->out_status;
+    return A;
+}
+
+plp_status bow_pairs_check(const plp_bow_score_pairs_args* a) {
+    if (!a) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
+    if (a->NA < 0 || a->NB < 0 || a->P < 0) return set_error(PLP_ERR_INVALID_ARG, "NA, NB and P must not be negative");
+    if (a->stride_a < 1 || a->stride_a > 8192 || a->stride_b < 1 || a->stride_b > 8192) return set_error(PLP_ERR_INVALID_ARG, "stride_a and stride_b must be 1 .. 8192");
+    if (plp_status s = bow_scoring_check(a->scoring)) return s;
+    if (a->NA > 0 && (!a->a_word || !a->a_value || !a->a_n)) return set_error(PLP_ERR_INVALID_ARG, "a_word, a_value, a_n are required");
+    if (a->NB > 0 && (!a->b_word || !a->b_value || !a->b_n)) return set_error(PLP_ERR_INVALID_ARG, "b_word, b_value, b_n are required");
+    if (a->P > 0 && (!a->a_row || !a->b_row || !a->out_score)) return set_error(PLP_ERR_INVALID_ARG, "a_row, b_row, out_score are required");
+    return PLP_OK;
+}
+
+BowPairsArgs bow_pairs_args(const plp_bow_score_pairs_args* a) {
+    BowPairsArgs A{};
+    A.NA = a->NA; A.stride_a = a->stride_a; A.NB = a->NB; A.stride_b = a->stride_b; A.P = a->P;
+    A.a_word = a->a_word; A.a_value = a->a_value; A.a_n = a->a_n; A.b_word = a->b_word; A.b_value = a->b_value; A.b_n = a->b_n;
+    A.a_row = a->a_row; A.b_row = a->b_row; A.out_score = a->out_score;
+    return A;
+}
+}  // namespace
+
+plp_status plp_bow_query_device(plp_matcher* c, const plp_bow_query_args* a, void* hip_stream) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = bow_query_check(a)) return s;
+    if (a->Q == 0) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    BowQueryArgs A = bow_query_args(a);
+    // the per-row arrays the kernels hand to each other live in the context where the caller passed NULL
+    const size_t QN = (size_t)a->Q * (size_t)a->N, al = 256;
+    const size_t b4 = (QN * 4 + al - 1) / al * al, b1 = (QN + al - 1) / al * al, bq = ((size_t)a->Q * 4 + al - 1) / al * al;
+    size_t need = 0;
+    if (!A.common) need += b4;
+    if (!A.score) need += b4;
+    if (!A.total) need += b4;
+    if (!A.best_kf) need += b4;
+    if (!A.final_mask) need += b1;
+    if (!A.max_common) need += bq;
+    if (need) {
+        PLP_HIP(c->bow_scratch.reserve(need));
+        uint8_t* p = static_cast<uint8_t*>(c->bow_scratch.p);
+        if (!A.common) { A.common = reinterpret_cast<uint32_t*>(p); p += b4; }
+        if (!A.score) { A.score = reinterpret_cast<float*>(p); p += b4; }
+        if (!A.total) { A.total = reinterpret_cast<float*>(p); p += b4; }
+        if (!A.best_kf) { A.best_kf = reinterpret_cast<int32_t*>(p); p += b4; }
+        if (!A.final_mask) { A.final_mask = p; p += b1; }
+        if (!A.max_common) { A.max_common = reinterpret_cast<uint32_t*>(p); p += bq; }
+    }
+    PLP_HIP(launch_bow_query((hipStream_t)hip_stream, A));
+    return PLP_OK;
+}
+
+plp_status plp_bow_query_host(plp_matcher* c, const plp_bow_query_args* a) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = bow_query_check(a)) return s;
+    if (a->Q == 0) return PLP_OK;
+    const size_t N = (size_t)a->N, Q = (size_t)a->Q, QN = Q * N;
+    BowQueryArgs A = bow_query_args(a);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.db_word, N * a->stride); s.in(A.db_value, N * a->stride); s.in(A.db_n, N); s.in(A.db_alive, N);
+    s.in(A.q_word, Q * a->q_stride); s.in(A.q_value, Q * a->q_stride); s.in(A.q_n, Q); s.in(A.reject, QN); s.in(A.min_score, Q);
+    s.in(A.covis, N * a->covis_cap); s.in(A.n_covis, N);
+    // every slot of every output is written: keep = false; an output the caller left out is a device-only region
+    if (A.common) s.out(A.common, QN, false); else s.room(A.common, QN);
+    if (A.score) s.out(A.score, QN, false); else s.room(A.score, QN);
+    if (A.total) s.out(A.total, QN, false); else s.room(A.total, QN);
+    if (A.best_kf) s.out(A.best_kf, QN, false); else s.room(A.best_kf, QN);
+    if (A.final_mask) s.out(A.final_mask, QN, false); else s.room(A.final_mask, QN);
+    if (A.max_common) s.out(A.max_common, Q, false); else s.room(A.max_common, Q);
+    s.out(A.n_final, Q, false); s.out(A.best_total, Q, false); s.out(A.status, Q, false);
+    PLP_TRY(s.upload());
+    PLP_HIP(launch_bow_query(c->stream, A));
+    return s.finish();
+}
+
+plp_status plp_bow_score_pairs_device(plp_matcher* c, const plp_bow_score_pairs_args* a, void* hip_stream) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = bow_pairs_check(a)) return s;
+    if (a->P == 0) return PLP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    PLP_HIP(launch_bow_score_pairs((hipStream_t)hip_stream, bow_pairs_args(a)));
+    return PLP_OK;
+}
+
+plp_status plp_bow_score_pairs_host(plp_matcher* c, const plp_bow_score_pairs_args* a) {
+    if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
+    if (plp_status s = bow_pairs_check(a)) return s;
+    if (a->P == 0) return PLP_OK;
+    BowPairsArgs A = bow_pairs_args(a);
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    Stage s(c->stage, c->stream);
+    s.in(A.a_word, (size_t)a->NA * a->stride_a); s.in(A.a_value, (size_t)a->NA * a->stride_a); s.in(A.a_n, (size_t)a->NA);
+    s.in(A.b_word, (size_t)a->NB * a->stride_b); s.in(A.b_value, (size_t)a->NB * a->stride_b); s.in(A.b_n, (size_t)a->NB);
+    s.in(A.a_row, (size_t)a->P); s.in(A.b_row, (size_t)a->P);
+    s.out(A.out_score, (size_t)a->P, false);
+    PLP_TRY(s.upload());
+    PLP_HIP(launch_bow_score_pairs(c->stream, A));
+    return s.finish();
+}
+
+// the host build of bow_score.hpp (no HIP call)
+double plp_model_bow_score_host(const uint32_t* wa, const double* va, int32_t na, const uint32_t* wb, const double* vb, int32_t nb) {
+    if (na < 0 || nb < 0 || (na > 0 && (!wa || !va)) || (nb > 0 && (!wb || !vb))) return -1.0;
+    return bow_l1_score(wa, va, na, wb, vb, nb);
 }
 
 plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src, int32_t rows, int32_t cols, size_t src_step,
