@@ -1229,6 +1229,99 @@ plp_status plp_bow_score_pairs_host(plp_matcher* ctx, const plp_bow_score_pairs_
 /* Host build of the score (csrc/bow_score.hpp), HOST pointers, before the narrowing to float.  No GPU and no context needed. */
 double plp_model_bow_score_host(const uint32_t* wa, const double* va, int32_t na, const uint32_t* wb, const double* vb, int32_t nb);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Loop candidates: solve::sim3_solver (src/PLPSLAM/solve/sim3_solver.cc), constructor and find_via_ransac, for P problems at once -- a
+ * problem is one pair (current key frame 1, candidate key frame 2) of loop_detector::select_loop_candidate_via_Sim3
+ * (module/loop_detector.cc:334-410): `sim3_solver solver(cur, candidate, matches, fix_scale, 20); solver.find_via_ransac(200);`.
+ * Numeric contract: DESIGN.md section 5, D13 (the eigenvector of Horn's matrix by a written-down Jacobi in place of Eigen::EigenSolver,
+ * f64 in the reference's order, the sample generator, points the camera does not reproject).
+ *
+ * The constructor's loop over the key points of key frame 1 (:70-115) is given in slot form, [P][n_cap], slot = idx1:
+ *   valid       1 where the loop reaches :96, 0 where one of its four `continue`s fires: no match (:72), a NULL landmark (:80), a landmark
+ *               that will_be_erased (:84), lm_2 not observed in key frame 2 (:91).  These read objects: the caller computes the byte
+ *   pos_w_1/2   lm_1 / lm_2 ->get_pos_in_world()                                                                     :108, :111
+ *   octave_1/2  undist_keypts_.at(idx1).octave of key frame 1, undist_keypts_.at(idx2).octave of key frame 2          :96-100
+ * Common point k is the k-th valid slot in slot order (the order of common_pts_in_keyfrm_1_): that is what a sample index means.
+ * The camera-frame points rot_cw * pos_w + trans_cw (:109, :112), their reprojections into their own images (:117-118) and the thresholds
+ * 9.21034f * level_sigma_sq[octave] (a float product, :67, :102-103) are formed by the library.
+ *
+ * find_via_ransac (:121-191) runs `iters` hypotheses.  Hypothesis i takes the common points samples[p][i][0..2] (:149-154), compute_Sim3
+ * (:193-288) and count_inliers (:290-325).  samples == NULL: the library draws them from `seed` (the reference draws from
+ * std::random_device, util/random_array.cc:37-44: there is no order to reproduce; the generator is D13's, the same on host and device).
+ * A caller's sample with an index outside [0, num_common) or a repeated index gives a hypothesis with 0 inliers.  The best hypothesis is
+ * the reference's: strictly more inliers win (:168), so among equal counts the LOWEST iteration wins.
+ * Outputs per problem:
+ *   out_status       a plp_sim3_status
+ *   out_num_common   num_common_pts_
+ *   out_rot_12 (9, row-major) / out_trans_12 (3) / out_scale_12   get_best_rotation_12 / translation_12 / scale_12; zero unless PLP_SIM3_OK (:181-183)
+ *   out_num_inliers  max_num_inliers (0 for PLP_SIM3_TOO_FEW_POINTS)
+ *   out_best_iter    the iteration that gave it; -1 unless PLP_SIM3_OK, or when no hypothesis had an inlier
+ *   out_inliers      optional, [P][n_cap] in slot order: the inlier flags of the best hypothesis (0 for a slot that is no common point;
+ *                    all 0 unless PLP_SIM3_OK); slots at or above counts[p] keep the caller's values
+ *   out_hyp_inliers  optional, [P][iters]: num_inliers of every hypothesis (0 for PLP_SIM3_TOO_FEW_POINTS, where the loop does not run)
+ * An octave outside [0, num_levels) (where level_sigma_sq_.at() throws) and a common point behind its own camera (perspective, fisheye;
+ * the reference leaves its reprojected_1_ / reprojected_2_ entry uninitialised, :352-356) make a common point that keeps its rank and is
+ * no inlier of any hypothesis; a point the other camera does not reproject under a hypothesis (:336-340) is no inlier of it (D13). */
+typedef enum plp_sim3_status {
+    PLP_SIM3_OK = 0,               /* solution_is_valid_                                                                       :188 */
+    PLP_SIM3_TOO_FEW_POINTS = 1,   /* num_common_pts_ < 3 || num_common_pts_ < min_num_inliers_                                 :130 */
+    PLP_SIM3_TOO_FEW_INLIERS = 2   /* max_num_inliers < min_num_inliers_                                                       :177 */
+} plp_sim3_status;
+typedef struct plp_sim3_ransac_args {
+    plp_camera_model camera;        /* keyfrm->camera_ of both key frames (:338, :354): model, cols, rows, fx, fy, cx, cy are read */
+    int32_t P, n_cap;               /* P >= 0 problems of n_cap >= 0 slots (keyfrm_1_lms.size(), :70), n_cap <= 8192 */
+    int32_t fix_scale;              /* fix_scale_ (:263): scale_21 = 1.0f */
+    int32_t min_num_inliers;        /* min_num_inliers_ (:130, :177), >= 0; 20 at loop_detector.cc:370 */
+    int32_t iters;                  /* max_num_iter (:145), >= 1; 200 at loop_detector.cc:371 */
+    uint64_t seed;                  /* samples == NULL: the generator's seed */
+    const float* level_sigma_sq_1;  /* HOST, num_levels: keyfrm_1_->level_sigma_sq_ (:99) */
+    const float* level_sigma_sq_2;  /* HOST, num_levels: keyfrm_2_->level_sigma_sq_ (:100) */
+    int32_t num_levels;             /* 1 .. 16 */
+    const int32_t* counts;          /* P: slots in use, or NULL = n_cap everywhere */
+    const uint8_t* valid;           /* P x n_cap (:72-94) */
+    const double* pos_w_1;          /* P x n_cap x 3 (:108) */
+    const double* pos_w_2;          /* P x n_cap x 3 (:111) */
+    const int32_t* octave_1;        /* P x n_cap (:96, :99) */
+    const int32_t* octave_2;        /* P x n_cap (:97, :100) */
+    const double* pose_1;           /* P x 15: the plp_observe_args.pose row of key frame 1; entries 0-11, rot_cw and trans_cw, are read (:50-51) */
+    const double* pose_2;           /* P x 15: key frame 2 (:52-53) */
+    const int32_t* samples;         /* P x iters x 3 indices of common points (:149), or NULL = drawn from seed */
+    uint8_t* out_status;            /* P */
+    int32_t* out_num_common;        /* P */
+    double* out_rot_12;             /* P x 9 (:171) */
+    double* out_trans_12;           /* P x 3 (:172) */
+    float* out_scale_12;            /* P (:173) */
+    int32_t* out_num_inliers;       /* P (:170) */
+    int32_t* out_best_iter;         /* P */
+    uint8_t* out_inliers;           /* P x n_cap, or NULL */
+    int32_t* out_hyp_inliers;       /* P x iters, or NULL */
+} plp_sim3_ransac_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; the camera as for plp_post_extract_model_* (unknown model, fx
+ * or fy 0, cols or rows <= 0); P < 0, n_cap < 0, iters < 1, min_num_inliers < 0; num_levels outside 1 .. 16 or a NULL level_sigma_sq_1 /
+ * level_sigma_sq_2; and -- when P > 0 and n_cap > 0 -- a NULL valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, out_status,
+ * out_num_common, out_rot_12, out_trans_12, out_scale_12, out_num_inliers or out_best_iter.  n_cap > 8192 or P > 65535: PLP_ERR_UNSUPPORTED.
+ * P == 0 or n_cap == 0: PLP_OK, nothing written.
+ * _device: every array but the two sigma tables a DEVICE pointer; three kernels on hip_stream, no host synchronisation; bad samples are
+ * never an error.  The kernels hand the hypotheses to one another through buffers the context owns (38 doubles per hypothesis), so the
+ * calls of one context must be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (the outputs too, so that every slot the kernel does not write keeps the caller's value),
+ * the same kernel, synchronous. */
+plp_status plp_sim3_ransac_device(plp_matcher* ctx, const plp_sim3_ransac_args* args, void* hip_stream);
+plp_status plp_sim3_ransac_host(plp_matcher* ctx, const plp_sim3_ransac_args* args);
+/* Host builds of the same source (csrc/sim3.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_sim3_ransac_host: the entry above, one problem and one hypothesis after the other; the same checks.  Returns P, or -1 for a
+ * bad argument (plp_last_error() names it).
+ * plp_model_horn_sim3_host: sim3_solver::compute_Sim3 (:193-288) for n pairs of row-major 3 x 3 point matrices (column c = sample c):
+ * out_rot_12 / out_rot_21 n x 9, out_trans_12 / out_trans_21 n x 3, out_scale_12 / out_scale_21 n floats, out_sweeps n (may be NULL).
+ * plp_model_sym_eig4_max_host: the unit eigenvector of the largest eigenvalue of n symmetric 4 x 4 matrices (row-major; the upper
+ * triangle is read), ties to the lowest column, sign unspecified; out_sweeps = sweeps that rotated, 30 = the limit.  Both return n. */
+int32_t plp_model_sim3_ransac_host(const plp_sim3_ransac_args* args);
+int32_t plp_model_horn_sim3_host(const double* pts_1, const double* pts_2, int32_t n, int32_t fix_scale, double* out_rot_12, double* out_trans_12,
+                                 float* out_scale_12, double* out_rot_21, double* out_trans_21, float* out_scale_21, int32_t* out_sweeps);
+int32_t plp_model_sym_eig4_max_host(const double* N, int32_t n, double* out_v, int32_t* out_sweeps);
+/* The samples the entries draw for problem p, iterations iter0 .. iter0 + n_iters - 1, of num_common >= 3 common points (D13's generator):
+ * out n_iters x 3.  Returns n_iters, or -1 for a bad argument. */
+int32_t plp_model_sim3_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_common, int32_t* out);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

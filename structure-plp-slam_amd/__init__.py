@@ -145,6 +145,12 @@ _API = [
     ("plp_landmark_line_geometry_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_landmark_line_geometry_host", C.c_int, [_VP, _VP]),
     ("plp_model_landmark_geometry_host", _I32, [_VP, _I32]),
+    ("plp_sim3_ransac_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_sim3_ransac_host", C.c_int, [_VP, _VP]),
+    ("plp_model_sim3_ransac_host", _I32, [_VP]),
+    ("plp_model_horn_sim3_host", _I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_model_sym_eig4_max_host", _I32, [_VP, _I32, _VP, _VP]),
+    ("plp_model_sim3_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -305,6 +311,138 @@ def model_null_vector4(A):
     v = np.zeros((len(A), 4), np.float64); sw = np.zeros(len(A), np.int32)
     assert lib().plp_model_null_vector4_host(_p(A), len(A), _p(v), _p(sw)) == len(A)
     return (v[0], int(sw[0])) if single else (v, sw)
+
+
+def model_sym_eig4_max(N):
+    """Host build of the eigenvector Horn's method needs (csrc/sim3.hpp; no GPU needed).  N: (n, 4, 4) or (4, 4) f64,
+    symmetric (the upper triangle is read).  Returns (v (n, 4) f64, sweeps (n,) i32): the unit eigenvector of the largest eigenvalue (ties: the
+    lowest column; sign unspecified) and the sweeps that rotated (30 = limit)."""
+    N = np.ascontiguousarray(N, np.float64)
+    single = N.ndim == 2
+    N = N.reshape(-1, 16)
+    v = np.zeros((len(N), 4), np.float64); sw = np.zeros(len(N), np.int32)
+    P = lambda a: a.ctypes.data if a.size else None
+    assert lib().plp_model_sym_eig4_max_host(P(N), len(N), P(v), P(sw)) == len(N)
+    return (v[0], int(sw[0])) if single else (v, sw)
+
+
+def model_horn_sim3(pts_1, pts_2, fix_scale=False):
+    """Host build of sim3_solver::compute_Sim3 (solve/sim3_solver.cc:193-288; csrc/sim3.hpp, D13; no GPU needed).  pts_1 / pts_2: (n, 3, 3) or
+    (3, 3) f64, column c = sample c.  Returns dict(rot_12, rot_21 (n, 3, 3) f64, trans_12, trans_21 (n, 3) f64, scale_12, scale_21 (n,) f32,
+    sweeps (n,) i32); without the leading axis for a single pair."""
+    a = np.ascontiguousarray(pts_1, np.float64); b = np.ascontiguousarray(pts_2, np.float64)
+    single = a.ndim == 2
+    a = a.reshape(-1, 9); b = b.reshape(-1, 9)
+    if len(a) != len(b):
+        raise PlpError(PLP_ERR_INVALID_ARG, "pts_1 and pts_2 must hold the same number of 3 x 3 matrices")
+    n = len(a)
+    o = dict(rot_12=np.zeros((n, 3, 3)), trans_12=np.zeros((n, 3)), scale_12=np.zeros(n, np.float32), rot_21=np.zeros((n, 3, 3)), trans_21=np.zeros((n, 3)),
+             scale_21=np.zeros(n, np.float32), sweeps=np.zeros(n, np.int32))
+    P = lambda v: v.ctypes.data if v.size else None
+    assert lib().plp_model_horn_sim3_host(P(a), P(b), n, int(bool(fix_scale)), P(o["rot_12"]), P(o["trans_12"]), P(o["scale_12"]), P(o["rot_21"]),
+                                          P(o["trans_21"]), P(o["scale_21"]), P(o["sweeps"])) == n
+    return {k: v[0] for k, v in o.items()} if single else o
+
+
+def model_sim3_draw(seed, p, iters, num_common, iter0=0):
+    """The samples plp_sim3_ransac_* draw for problem p when the caller passes none (D13's generator; no GPU needed): (iters, 3) i32"""
+    out = np.zeros((int(iters), 3), np.int32)
+    if lib().plp_model_sim3_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_common), out.ctypes.data if out.size else None) != int(iters):
+        raise PlpError(PLP_ERR_INVALID_ARG, "num_common must be at least 3, iters non-negative")
+    return out
+
+
+# plp_sim3_status: where sim3_solver::find_via_ransac leaves a problem
+SIM3_OK, SIM3_TOO_FEW_POINTS, SIM3_TOO_FEW_INLIERS = range(3)
+# the outputs of plp_sim3_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
+SIM3_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_common=(lambda M, I: (), np.int32, False), rot_12=(lambda M, I: (3, 3), np.float64, False),
+                    trans_12=(lambda M, I: (3,), np.float64, False), scale_12=(lambda M, I: (), np.float32, False),
+                    num_inliers=(lambda M, I: (), np.int32, False), best_iter=(lambda M, I: (), np.int32, False),
+                    inliers=(lambda M, I: (M,), np.uint8, True), hyp_inliers=(lambda M, I: (I,), np.int32, True))
+
+
+def _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters, fix_scale,
+                      min_num_inliers, samples, seed, counts, outputs, out):
+    """the numpy side of plp_sim3_ransac_host and plp_model_sim3_ransac_host: call(args struct) runs the entry"""
+    va = np.ascontiguousarray(valid, np.uint8)
+    if va.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "valid must be (P, n_cap)")
+    P_, M = va.shape
+    w1 = np.ascontiguousarray(pos_w_1, np.float64).reshape(P_, M, 3); w2 = np.ascontiguousarray(pos_w_2, np.float64).reshape(P_, M, 3)
+    o1 = np.ascontiguousarray(octave_1, np.int32).reshape(P_, M); o2 = np.ascontiguousarray(octave_2, np.int32).reshape(P_, M)
+    p1 = np.ascontiguousarray(pose_1, np.float64).reshape(P_, 15); p2 = np.ascontiguousarray(pose_2, np.float64).reshape(P_, 15)
+    s1 = np.ascontiguousarray(level_sigma_sq_1, np.float32).reshape(-1); s2 = np.ascontiguousarray(level_sigma_sq_2, np.float32).reshape(-1)
+    if len(s1) != len(s2):
+        raise PlpError(PLP_ERR_INVALID_ARG, "level_sigma_sq_1 and level_sigma_sq_2 must have the same length")
+    I = int(iters)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(P_, I, 3)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
+    o = {}
+    for k, (shape, dt, optional) in SIM3_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (P_,) + shape(M, max(I, 0))
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(sim3_ransac_args_c, dict(P=P_, n_cap=M, fix_scale=int(bool(fix_scale)), min_num_inliers=int(min_num_inliers), iters=I,
+                                         seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(s1)), dict(
+        level_sigma_sq_1=Pt(s1), level_sigma_sq_2=Pt(s2), counts=Pt(cn), valid=Pt(va), pos_w_1=Pt(w1), pos_w_2=Pt(w2), octave_1=Pt(o1), octave_2=Pt(o2),
+        pose_1=Pt(p1), pose_2=Pt(p2), samples=Pt(sm), out_status=Pt(o["status"]), out_num_common=Pt(o["num_common"]), out_rot_12=Pt(o["rot_12"]),
+        out_trans_12=Pt(o["trans_12"]), out_scale_12=Pt(o["scale_12"]), out_num_inliers=Pt(o["num_inliers"]), out_best_iter=Pt(o["best_iter"]),
+        out_inliers=Pt(o.get("inliers")), out_hyp_inliers=Pt(o.get("hyp_inliers"))))
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    call(a)
+    return o
+
+
+def model_sim3_ransac(camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters=200, fix_scale=False,
+                      min_num_inliers=20, samples=None, seed=0, counts=None, outputs=None, out=None):
+    """Host build of solve::sim3_solver's constructor and find_via_ransac (csrc/sim3.hpp, DESIGN.md section 5, D13; no GPU needed): the arguments
+    and the result of matcher.sim3_ransac."""
+    def call(a):
+        if lib().plp_model_sim3_ransac_host(C.byref(a)) != a.P:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters, fix_scale,
+                             min_num_inliers, samples, seed, counts, outputs, out)
+
+
+class sim3_solver:
+    """Mirror of solve::sim3_solver (solve/sim3_solver.h) over the flattened lists of its constructor's loop (include/plp_front.h,
+    plp_sim3_ransac_args): valid / pos_w_1 / pos_w_2 / octave_1 / octave_2 per key point of key frame 1, the two pose rows and sigma tables.
+    mt: a matcher (the GPU entry), or None = the host build.  samples / seed: as matcher.sim3_ransac."""
+
+    def __init__(self, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, fix_scale=False,
+                 min_num_inliers=20, mt=None, samples=None, seed=0):
+        n = len(np.asarray(valid).reshape(-1))
+        self._in = (camera, np.asarray(valid).reshape(1, n), np.asarray(pos_w_1).reshape(1, n, 3), np.asarray(pos_w_2).reshape(1, n, 3),
+                    np.asarray(octave_1).reshape(1, n), np.asarray(octave_2).reshape(1, n), np.asarray(pose_1).reshape(1, 15), np.asarray(pose_2).reshape(1, 15),
+                    level_sigma_sq_1, level_sigma_sq_2)
+        self._kw = dict(fix_scale=fix_scale, min_num_inliers=min_num_inliers, samples=samples, seed=seed)
+        self._mt = mt
+        self._r = None
+
+    def find_via_ransac(self, max_num_iter):
+        fn = model_sim3_ransac if self._mt is None else self._mt.sim3_ransac
+        self._r = fn(*self._in, iters=int(max_num_iter), **self._kw)
+
+    def solution_is_valid(self):
+        return self._r is not None and int(self._r["status"][0]) == SIM3_OK
+
+    def get_best_rotation_12(self):
+        return self._r["rot_12"][0].copy()
+
+    def get_best_translation_12(self):
+        return self._r["trans_12"][0].copy()
+
+    def get_best_scale_12(self):
+        return float(self._r["scale_12"][0])
+
+    def get_inliers(self):
+        """the inlier flags of the best hypothesis per key point of key frame 1 (not in the reference's surface: count_inliers' vector)"""
+        return self._r["inliers"][0].astype(bool)
 
 
 class orb_extractor:
@@ -841,6 +979,15 @@ class landmark_geometry_args_c(C.Structure):
 
 # plp_landmark_geometry_status: where landmark::update_normal_and_depth / Line::update_information leave a landmark
 LG_UPDATED, LG_SKIPPED, LG_NO_OBSERVATIONS, LG_REF_NOT_OBSERVED, LG_INDEX_RANGE, LG_OCTAVE_RANGE = range(6)
+
+
+class sim3_ransac_args_c(C.Structure):
+    """plp_sim3_ransac_args"""
+    _fields_ = [("camera", camera_model_c), ("P", C.c_int32), ("n_cap", C.c_int32), ("fix_scale", C.c_int32), ("min_num_inliers", C.c_int32),
+                ("iters", C.c_int32), ("seed", C.c_uint64), ("level_sigma_sq_1", _VP), ("level_sigma_sq_2", _VP), ("num_levels", C.c_int32),
+                ("counts", _VP), ("valid", _VP), ("pos_w_1", _VP), ("pos_w_2", _VP), ("octave_1", _VP), ("octave_2", _VP), ("pose_1", _VP), ("pose_2", _VP),
+                ("samples", _VP), ("out_status", _VP), ("out_num_common", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
+                ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -1662,6 +1809,37 @@ class matcher:
         """plp_landmark_line_geometry_device: as landmark_geometry_device, with the LSD scale table beside the ORB one and no normal"""
         self._landmark_geometry_device(True, F, cap, L, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, None, out_min_valid_dist,
                                        out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip, counts, stream)
+
+    def sim3_ransac(self, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters=200,
+                    fix_scale=False, min_num_inliers=20, samples=None, seed=0, counts=None, outputs=None, out=None):
+        """solve::sim3_solver's constructor and find_via_ransac for P problems (plp_sim3_ransac_host): valid (P, n_cap) u8, pos_w_1 / pos_w_2
+        (P, n_cap, 3), octave_1 / octave_2 (P, n_cap), pose_1 / pose_2 (P, 15), the two sigma tables (num_levels,) f32, samples (P, iters, 3)
+        indices of common points or None = drawn from seed, counts (P,) or None.  Returns dict(status (P,) u8: SIM3_*, num_common, rot_12
+        (P, 3, 3), trans_12 (P, 3), scale_12 (P,) f32, num_inliers, best_iter, inliers (P, n_cap) u8, hyp_inliers (P, iters)); `outputs` names
+        the optional ones wanted (default both); out[name]: the caller's array."""
+        call = lambda a: _check(lib().plp_sim3_ransac_host(self._h, C.byref(a)))
+        return _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters,
+                                 fix_scale, min_num_inliers, samples, seed, counts, outputs, out)
+
+    def sim3_ransac_device(self, camera, P, n_cap, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, out,
+                           iters=200, fix_scale=False, min_num_inliers=20, samples=None, seed=0, counts=None, stream=None):
+        """plp_sim3_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device (the sigma tables are host
+        vectors); out: dict of the device outputs named as in SIM3_OUTPUTS (inliers / hyp_inliers may be absent); asynchronous, three kernels
+        on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        s1 = np.ascontiguousarray(level_sigma_sq_1, np.float32).reshape(-1)
+        s2 = np.ascontiguousarray(level_sigma_sq_2, np.float32).reshape(-1)        # both live until the call has returned
+        a = _struct(sim3_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), fix_scale=int(bool(fix_scale)), min_num_inliers=int(min_num_inliers),
+                                             iters=int(iters), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=min(len(s1), len(s2))), dict(
+            level_sigma_sq_1=s1.ctypes.data if len(s1) else None, level_sigma_sq_2=s2.ctypes.data if len(s2) else None, counts=D(counts), valid=D(valid),
+            pos_w_1=D(pos_w_1), pos_w_2=D(pos_w_2), octave_1=D(octave_1), octave_2=D(octave_2), pose_1=D(pose_1), pose_2=D(pose_2), samples=D(samples),
+            out_status=D(out.get("status")), out_num_common=D(out.get("num_common")), out_rot_12=D(out.get("rot_12")), out_trans_12=D(out.get("trans_12")),
+            out_scale_12=D(out.get("scale_12")), out_num_inliers=D(out.get("num_inliers")), out_best_iter=D(out.get("best_iter")),
+            out_inliers=D(out.get("inliers")), out_hyp_inliers=D(out.get("hyp_inliers"))))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_sim3_ransac_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):

@@ -1,4 +1,4 @@
-// Device helpers shared by observe_kernels.hip and project_kernels.hip: camera::*::reproject_to_image of the three models,
+// Device helpers shared by observe_kernels.hip, project_kernels.hip and sim3.hpp (which builds reproject<MODEL> for the host too): camera::*::reproject_to_image of the three models,
 // predict_scale_level, the norm of cam_to_lm_vec and the carried end-point temporaries of the line loops.
 // Every translation unit that includes this file is compiled with -ffp-contract=off; the helpers have internal linkage.
 #pragma once
@@ -20,7 +20,7 @@ struct Reproj {
 // camera::*::reproject_to_image.  P = rot_cw_ row-major (0-8), trans_cw_ (9-11), cam_center_ (12-14).  A: ObserveArgs or ProjectArgs (the
 // camera fields model-independent code reads: fx, fy, cx, cy, fxb, cols_d, rows_d, bounds).
 template <int MODEL, class Args>
-__device__ __forceinline__ Reproj reproject(const Args& A, const double* P, double x, double y, double z) {
+__host__ __device__ __forceinline__ Reproj reproject(const Args& A, const double* P, double x, double y, double z) {
     Reproj r;
     const double xc = ((P[0] * x + P[1] * y) + P[2] * z) + P[9];   // rot_cw * pos_w + trans_cw
     const double yc = ((P[3] * x + P[4] * y) + P[5] * z) + P[10];
