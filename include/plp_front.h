@@ -1322,6 +1322,102 @@ int32_t plp_model_sym_eig4_max_host(const double* N, int32_t n, double* out_v, i
  * out n_iters x 3.  Returns n_iters, or -1 for a bad argument. */
 int32_t plp_model_sim3_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_common, int32_t* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Relocalisation: solve::pnp_solver (src/PLPSLAM/solve/pnp_solver.cc), constructor and find_via_ransac, for P problems at once -- a problem
+ * is one candidate key frame of module::relocalizer::relocalize (module/relocalizer.cc:70-99):
+ * `setup_pnp_solver(valid_indices, bearings, keypts, matched_landmarks, scale_factors)->find_via_ransac(30)`.
+ * Numeric contract: DESIGN.md section 5, D14 (the four Eigen::JacobiSVD uses by one written-down one-sided Jacobi, f64 in the reference's
+ * order, the sample generator, what the reference leaves undefined).
+ *
+ * extract_valid_indices + setup_pnp_solver (relocalizer.cc:254-291) are given in slot form, [P][n_cap], slot = key point of the frame:
+ *   valid     1 where extract_valid_indices keeps the index: a landmark was matched (:261) that will not be erased (:265)
+ *   bearing   curr_frm.bearings_.at(idx)                                                               relocalizer.cc:281, pnp_solver.cc:39
+ *   pos_w     matched_landmarks.at(idx)->get_pos_in_world()                                            relocalizer.cc:287
+ *   octave    curr_frm.keypts_.at(idx).octave                                                          relocalizer.cc:282, pnp_solver.cc:50
+ * Match k is the k-th valid slot in slot order (the order of valid_indices): that is what a sample index means.  There is no camera: the
+ * solver sees bearings only (pnp_solver.h:166: fx_ = fy_ = 1, cx_ = cy_ = 0), which covers all three camera models.
+ * max_cos_errors_ (:47-51) is util::cos((float)(scale_factors[octave] * (1.0 * M_PI / 180.0))), a float per level formed by the library.
+ *
+ * find_via_ransac (:70-153) runs `iters` hypotheses.  Hypothesis i adds the matches samples[p][i][0..3] in that order (:103-108; signs_[0]
+ * and pcs_[2] belong to the first), compute_pose (:230-290) and check_inliers (:155-181).  samples == NULL: the library draws them from
+ * `seed` (the reference draws from std::random_device and shuffles, util/random_array.cc:37-88: there is no order to reproduce; the
+ * generator is D14's, the same on host and device).  A caller's sample with an index outside [0, num_matches) or a repeated index, and a
+ * sample whose four bearings all have z == 0 (add_correspondence skips them, :206; the reference then divides by zero correspondences),
+ * give a hypothesis with 0 inliers.  The best hypothesis is the reference's: strictly more inliers win (:117), so among equal counts the
+ * LOWEST iteration wins.  recompute (:136-152): compute_pose once more over all inliers of the best hypothesis in match order; when every
+ * inlier has bearing z == 0 the best hypothesis' pose stays.
+ * Outputs per problem:
+ *   out_status       a plp_pnp_status
+ *   out_num_matches  num_matches_
+ *   out_rot_cw (9, row-major) / out_trans_cw (3)   get_best_rotation / get_best_translation; zero unless PLP_PNP_OK
+ *   out_num_inliers  max_num_inliers (0 for PLP_PNP_TOO_FEW_MATCHES)
+ *   out_best_iter    the iteration that gave it; -1 unless PLP_PNP_OK
+ *   out_inliers      optional, [P][n_cap] in slot order: get_inlier_flags() of the best hypothesis, which recompute does not change (0 for a
+ *                    slot that is no match; all 0 unless PLP_PNP_OK); slots at or above counts[p] keep the caller's values
+ *   out_hyp_inliers  optional, [P][iters]: num_inliers of every hypothesis (0 for PLP_PNP_TOO_FEW_MATCHES, where the loop does not run)
+ * An octave outside [0, num_levels) (where scale_factors.at() throws, :50) makes a match that keeps its rank and is no inlier of any
+ * hypothesis; sampled, it is a correspondence like any other (its threshold is not read there). */
+typedef enum plp_pnp_status {
+    PLP_PNP_OK = 0,                /* solution_is_valid_                                                                       :128 */
+    PLP_PNP_TOO_FEW_MATCHES = 1,   /* num_matches_ < 4 || num_matches_ < min_num_inliers_                                       :76 */
+    PLP_PNP_TOO_FEW_INLIERS = 2    /* !(max_num_inliers > min_num_inliers_): strict, unlike plp_sim3_status                     :126 */
+} plp_pnp_status;
+typedef struct plp_pnp_ransac_args {
+    int32_t P, n_cap;               /* P >= 0 problems of n_cap >= 0 slots (curr_frm.num_keypts_), n_cap <= 8192 */
+    int32_t min_num_inliers;        /* min_num_inliers_ (:76, :126), >= 0; 10 by the constructor's default (pnp_solver.h) */
+    int32_t iters;                  /* max_num_iter (:96), >= 1; 30 at relocalizer.cc:93 */
+    int32_t recompute;              /* :131-152; true by find_via_ransac's default */
+    uint64_t seed;                  /* samples == NULL: the generator's seed */
+    const float* scale_factors;     /* HOST, num_levels: curr_frm.scale_factors_ (:50) */
+    int32_t num_levels;             /* 1 .. 16 */
+    const int32_t* counts;          /* P: slots in use, or NULL = n_cap everywhere */
+    const uint8_t* valid;           /* P x n_cap (relocalizer.cc:258-270) */
+    const double* bearing;          /* P x n_cap x 3 (:105) */
+    const double* pos_w;            /* P x n_cap x 3 (:106) */
+    const int32_t* octave;          /* P x n_cap (:50) */
+    const int32_t* samples;         /* P x iters x 4 indices of matches (:99), or NULL = drawn from seed */
+    uint8_t* out_status;            /* P */
+    int32_t* out_num_matches;       /* P */
+    double* out_rot_cw;             /* P x 9 (:120, :152) */
+    double* out_trans_cw;           /* P x 3 (:121, :152) */
+    int32_t* out_num_inliers;       /* P (:119) */
+    int32_t* out_best_iter;         /* P */
+    uint8_t* out_inliers;           /* P x n_cap, or NULL (:122) */
+    int32_t* out_hyp_inliers;       /* P x iters, or NULL */
+} plp_pnp_ransac_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; P < 0, n_cap < 0, iters < 1, min_num_inliers < 0; num_levels
+ * outside 1 .. 16 or a NULL scale_factors; and -- when P > 0 and n_cap > 0 -- a NULL valid, bearing, pos_w, octave, out_status,
+ * out_num_matches, out_rot_cw, out_trans_cw, out_num_inliers or out_best_iter.  n_cap > 8192 or P > 65535: PLP_ERR_UNSUPPORTED.
+ * P == 0 or n_cap == 0: PLP_OK, nothing written.
+ * _device: every array but scale_factors a DEVICE pointer; five kernels on hip_stream, no host synchronisation; bad samples are never an
+ * error.  The kernels hand the ranks, the hypotheses and the refit's correspondences to one another through buffers the context owns, so
+ * the calls of one context must be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (the
+ * outputs too, so that every slot the kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_pnp_ransac_device(plp_matcher* ctx, const plp_pnp_ransac_args* args, void* hip_stream);
+plp_status plp_pnp_ransac_host(plp_matcher* ctx, const plp_pnp_ransac_args* args);
+/* Host builds of the same source (csrc/pnp.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_pnp_ransac_host: the entry above, one problem and one hypothesis after the other; the same checks.  Returns P, or -1 for a bad
+ * argument (plp_last_error() names it).
+ * plp_model_epnp_host: compute_pose (:230-290) for n lists of correspondences: list i holds pos_w / bearing rows offsets[i] .. offsets[i+1]
+ * (add_correspondence skips bearing z == 0).  out_rot n x 9, out_trans n x 3, out_err n (the reprojection error returned), out_N n (the
+ * chosen approximation 1 .. 3), out_sweeps n x 8 (may be NULL; PW0tPW0, MtM, the three least-squares systems, the three Abt).  A list
+ * without a correspondence left gives zeros and N = 0.  Returns n.
+ * plp_model_sym_jacobi_host: uses 1 and 2 of D14 for n symmetric dim x dim matrices (row-major), dim = 3 or 12: out_vals n x dim singular
+ * values descending, out_ut n x dim x dim (row r = the vector of out_vals[r]), out_sweeps n (may be NULL; 60 = the limit).
+ * plp_model_lstsq6_host: use 3 for n systems A (6 x k row-major) x = b, k = 3, 4 or 5: out_x n x k.
+ * plp_model_rot_from_abt_host: use 4 for n 3 x 3 matrices (row-major): out_rot n x 9.  All return n, or -1 for a bad argument. */
+int32_t plp_model_pnp_ransac_host(const plp_pnp_ransac_args* args);
+int32_t plp_model_epnp_host(const double* pos_w, const double* bearing, const int32_t* offsets, int32_t n, double* out_rot, double* out_trans,
+                            double* out_err, int32_t* out_N, int32_t* out_sweeps);
+int32_t plp_model_sym_jacobi_host(const double* A, int32_t dim, int32_t n, double* out_vals, double* out_ut, int32_t* out_sweeps);
+int32_t plp_model_lstsq6_host(const double* A, const double* b, int32_t k, int32_t n, double* out_x, int32_t* out_sweeps);
+int32_t plp_model_rot_from_abt_host(const double* Abt, int32_t n, double* out_rot, int32_t* out_sweeps);
+/* The samples the entries draw for problem p, iterations iter0 .. iter0 + n_iters - 1, of num_matches >= 4 matches (D14's generator):
+ * out n_iters x 4.  Returns n_iters, or -1 for a bad argument. */
+int32_t plp_model_pnp_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_matches, int32_t* out);
+/* max_cos_errors_ per level (:47-51) for num_levels scale factors: out num_levels floats.  Returns num_levels, or -1. */
+int32_t plp_model_pnp_thresholds_host(const float* scale_factors, int32_t num_levels, float* out);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

@@ -151,6 +151,15 @@ _API = [
     ("plp_model_horn_sim3_host", _I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_model_sym_eig4_max_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_model_sim3_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
+    ("plp_pnp_ransac_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_pnp_ransac_host", C.c_int, [_VP, _VP]),
+    ("plp_model_pnp_ransac_host", _I32, [_VP]),
+    ("plp_model_epnp_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_model_sym_jacobi_host", _I32, [_VP, _I32, _I32, _VP, _VP, _VP]),
+    ("plp_model_lstsq6_host", _I32, [_VP, _VP, _I32, _I32, _VP, _VP]),
+    ("plp_model_rot_from_abt_host", _I32, [_VP, _I32, _VP, _VP]),
+    ("plp_model_pnp_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
+    ("plp_model_pnp_thresholds_host", _I32, [_VP, _I32, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -443,6 +452,174 @@ class sim3_solver:
     def get_inliers(self):
         """the inlier flags of the best hypothesis per key point of key frame 1 (not in the reference's surface: count_inliers' vector)"""
         return self._r["inliers"][0].astype(bool)
+
+
+def model_sym_jacobi(A):
+    """Host build of uses 1 and 2 of DESIGN.md section 5, D14 (csrc/pnp.hpp; no GPU needed): the one-sided Jacobi on symmetric positive
+    semi-definite matrices.  A: (n, d, d) or (d, d) f64, d = 3 or 12.  Returns (vals (n, d) singular values descending, ut (n, d, d): row r =
+    the vector of vals[r], sweeps (n,) i32: the sweeps that rotated, 60 = limit)."""
+    A = np.ascontiguousarray(A, np.float64)
+    single = A.ndim == 2
+    d = A.shape[-1]
+    A = A.reshape(-1, d * d)
+    n = len(A)
+    vals = np.zeros((n, d)); ut = np.zeros((n, d, d)); sw = np.zeros(n, np.int32)
+    P = lambda a: a.ctypes.data if a.size else None
+    if lib().plp_model_sym_jacobi_host(P(A), d, n, P(vals), P(ut), P(sw)) != n:
+        raise PlpError(PLP_ERR_INVALID_ARG, "A must be (n, 3, 3) or (n, 12, 12)")
+    return (vals[0], ut[0], int(sw[0])) if single else (vals, ut, sw)
+
+
+def model_lstsq6(A, b):
+    """Host build of use 3 of D14 (csrc/pnp.hpp; no GPU needed): the minimum-norm least-squares solution of 6 x k systems, k = 3, 4, 5.
+    A: (n, 6, k) or (6, k), b: (n, 6) or (6,).  Returns (x (n, k), sweeps (n,))."""
+    A = np.ascontiguousarray(A, np.float64); b = np.ascontiguousarray(b, np.float64)
+    single = A.ndim == 2
+    k = A.shape[-1]
+    A = A.reshape(-1, 6 * k); b = b.reshape(-1, 6)
+    n = len(A)
+    x = np.zeros((n, k)); sw = np.zeros(n, np.int32)
+    P = lambda a: a.ctypes.data if a.size else None
+    if len(b) != n or lib().plp_model_lstsq6_host(P(A), P(b), k, n, P(x), P(sw)) != n:
+        raise PlpError(PLP_ERR_INVALID_ARG, "A must be (n, 6, k) with k = 3, 4, 5 and b (n, 6)")
+    return (x[0], int(sw[0])) if single else (x, sw)
+
+
+def model_rot_from_abt(Abt):
+    """Host build of use 4 of D14 (csrc/pnp.hpp; no GPU needed): R = U V^T of 3 x 3 matrices with the det < 0 flip of estimate_R_and_t
+    (solve/pnp_solver.cc:487-514).  Abt: (n, 3, 3) or (3, 3).  Returns (R (n, 3, 3), sweeps (n,))."""
+    A = np.ascontiguousarray(Abt, np.float64)
+    single = A.ndim == 2
+    A = A.reshape(-1, 9)
+    n = len(A)
+    R = np.zeros((n, 3, 3)); sw = np.zeros(n, np.int32)
+    P = lambda a: a.ctypes.data if a.size else None
+    assert lib().plp_model_rot_from_abt_host(P(A), n, P(R), P(sw)) == n
+    return (R[0], int(sw[0])) if single else (R, sw)
+
+
+def model_epnp(pos_w, bearing, offsets=None):
+    """Host build of pnp_solver::compute_pose (solve/pnp_solver.cc:230-290; csrc/pnp.hpp, D14; no GPU needed) for lists of correspondences:
+    pos_w / bearing (m, 3) f64, list i = rows offsets[i] .. offsets[i+1] (None: one list of all rows).  Returns dict(rot (n, 3, 3), trans
+    (n, 3), err (n,): the reprojection error, N (n,) i32: the chosen approximation 1 .. 3 (0: no correspondence left), sweeps (n, 8) i32);
+    without the leading axis for offsets None."""
+    w = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3); b = np.ascontiguousarray(bearing, np.float64).reshape(-1, 3)
+    if len(w) != len(b):
+        raise PlpError(PLP_ERR_INVALID_ARG, "pos_w and bearing must hold the same number of rows")
+    single = offsets is None
+    off = np.array([0, len(w)], np.int32) if single else np.ascontiguousarray(offsets, np.int32).reshape(-1)
+    n = len(off) - 1
+    if n < 0 or (n and int(off[-1]) > len(w)):
+        raise PlpError(PLP_ERR_INVALID_ARG, "offsets must be ascending within the rows")
+    o = dict(rot=np.zeros((n, 3, 3)), trans=np.zeros((n, 3)), err=np.zeros(n), N=np.zeros(n, np.int32), sweeps=np.zeros((n, 8), np.int32))
+    P = lambda a: a.ctypes.data if a.size else None
+    if lib().plp_model_epnp_host(P(w), P(b), P(off), n, P(o["rot"]), P(o["trans"]), P(o["err"]), P(o["N"]), P(o["sweeps"])) != n:
+        raise PlpError(PLP_ERR_INVALID_ARG, "offsets must be ascending within the rows")
+    return {k: v[0] for k, v in o.items()} if single else o
+
+
+def model_pnp_draw(seed, p, iters, num_matches, iter0=0):
+    """The samples plp_pnp_ransac_* draw for problem p when the caller passes none (D14's generator; no GPU needed): (iters, 4) i32"""
+    out = np.zeros((int(iters), 4), np.int32)
+    if lib().plp_model_pnp_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_matches), out.ctypes.data if out.size else None) != int(iters):
+        raise PlpError(PLP_ERR_INVALID_ARG, "num_matches must be at least 4, iters non-negative")
+    return out
+
+
+def model_pnp_thresholds(scale_factors):
+    """max_cos_errors_ per level (solve/pnp_solver.cc:47-51): util::cos((float)(scale_factors[l] * (1.0 * M_PI / 180.0))), f32 (no GPU needed)"""
+    sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+    out = np.zeros(len(sf), np.float32)
+    assert lib().plp_model_pnp_thresholds_host(sf.ctypes.data if len(sf) else None, len(sf), out.ctypes.data if len(sf) else None) == len(sf)
+    return out
+
+
+# plp_pnp_status: where pnp_solver::find_via_ransac leaves a problem
+PNP_OK, PNP_TOO_FEW_MATCHES, PNP_TOO_FEW_INLIERS = range(3)
+# the outputs of plp_pnp_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
+PNP_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_matches=(lambda M, I: (), np.int32, False), rot_cw=(lambda M, I: (3, 3), np.float64, False),
+                   trans_cw=(lambda M, I: (3,), np.float64, False), num_inliers=(lambda M, I: (), np.int32, False),
+                   best_iter=(lambda M, I: (), np.int32, False), inliers=(lambda M, I: (M,), np.uint8, True), hyp_inliers=(lambda M, I: (I,), np.int32, True))
+
+
+def _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples, seed, counts, outputs, out):
+    """the numpy side of plp_pnp_ransac_host and plp_model_pnp_ransac_host: call(args struct) runs the entry"""
+    va = np.ascontiguousarray(valid, np.uint8)
+    if va.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "valid must be (P, n_cap)")
+    P_, M = va.shape
+    be = np.ascontiguousarray(bearing, np.float64).reshape(P_, M, 3); pw = np.ascontiguousarray(pos_w, np.float64).reshape(P_, M, 3)
+    oc = np.ascontiguousarray(octave, np.int32).reshape(P_, M)
+    sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+    I = int(iters)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(P_, I, 4)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
+    o = {}
+    for k, (shape, dt, optional) in PNP_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (P_,) + shape(M, max(I, 0))
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(pnp_ransac_args_c, dict(P=P_, n_cap=M, min_num_inliers=int(min_num_inliers), iters=I, recompute=int(bool(recompute)),
+                                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(sf)), dict(
+        scale_factors=Pt(sf), counts=Pt(cn), valid=Pt(va), bearing=Pt(be), pos_w=Pt(pw), octave=Pt(oc), samples=Pt(sm), out_status=Pt(o["status"]),
+        out_num_matches=Pt(o["num_matches"]), out_rot_cw=Pt(o["rot_cw"]), out_trans_cw=Pt(o["trans_cw"]), out_num_inliers=Pt(o["num_inliers"]),
+        out_best_iter=Pt(o["best_iter"]), out_inliers=Pt(o.get("inliers")), out_hyp_inliers=Pt(o.get("hyp_inliers"))))
+    call(a)
+    return o
+
+
+def model_pnp_ransac(valid, bearing, pos_w, octave, scale_factors, iters=30, min_num_inliers=10, recompute=True, samples=None, seed=0, counts=None,
+                     outputs=None, out=None):
+    """Host build of solve::pnp_solver's constructor and find_via_ransac (csrc/pnp.hpp, DESIGN.md section 5, D14; no GPU needed): the arguments
+    and the result of matcher.pnp_ransac."""
+    def call(a):
+        if lib().plp_model_pnp_ransac_host(C.byref(a)) != a.P:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples, seed, counts, outputs, out)
+
+
+class pnp_solver:
+    """Mirror of solve::pnp_solver (solve/pnp_solver.h): valid_bearings (n, 3), valid_keypts_octaves (n,) -- the octave is all the constructor
+    reads of a key point --, valid_landmarks (n, 3), scale_factors.  mt: a matcher (the GPU entry), or None = the host build.  samples / seed:
+    as matcher.pnp_ransac."""
+
+    def __init__(self, valid_bearings, valid_keypts_octaves, valid_landmarks, scale_factors, min_num_inliers=10, mt=None, samples=None, seed=0):
+        b = np.ascontiguousarray(valid_bearings, np.float64).reshape(-1, 3)
+        n = len(b)
+        self._n = n
+        self._in = (np.ones((1, max(n, 1)), np.uint8), b.reshape(1, n, 3) if n else np.zeros((1, 1, 3)),
+                    np.ascontiguousarray(valid_landmarks, np.float64).reshape(1, n, 3) if n else np.zeros((1, 1, 3)),
+                    np.ascontiguousarray(valid_keypts_octaves, np.int32).reshape(1, n) if n else np.zeros((1, 1), np.int32), scale_factors)
+        self._kw = dict(min_num_inliers=min_num_inliers, samples=samples, seed=seed, counts=np.array([n], np.int32))
+        self._mt = mt
+        self._r = None
+
+    def find_via_ransac(self, max_num_iter, recompute=True):
+        fn = model_pnp_ransac if self._mt is None else self._mt.pnp_ransac
+        self._r = fn(*self._in, iters=int(max_num_iter), recompute=recompute, **self._kw)
+
+    def solution_is_valid(self):
+        return self._r is not None and int(self._r["status"][0]) == PNP_OK
+
+    def get_best_rotation(self):
+        return self._r["rot_cw"][0].copy()
+
+    def get_best_translation(self):
+        return self._r["trans_cw"][0].copy()
+
+    def get_best_cam_pose(self):
+        T = np.eye(4)
+        T[:3, :3] = self._r["rot_cw"][0]
+        T[:3, 3] = self._r["trans_cw"][0]
+        return T
+
+    def get_inlier_flags(self):
+        return self._r["inliers"][0, :self._n].astype(bool)
 
 
 class orb_extractor:
@@ -987,6 +1164,14 @@ class sim3_ransac_args_c(C.Structure):
                 ("iters", C.c_int32), ("seed", C.c_uint64), ("level_sigma_sq_1", _VP), ("level_sigma_sq_2", _VP), ("num_levels", C.c_int32),
                 ("counts", _VP), ("valid", _VP), ("pos_w_1", _VP), ("pos_w_2", _VP), ("octave_1", _VP), ("octave_2", _VP), ("pose_1", _VP), ("pose_2", _VP),
                 ("samples", _VP), ("out_status", _VP), ("out_num_common", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
+                ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
+
+
+class pnp_ransac_args_c(C.Structure):
+    """plp_pnp_ransac_args"""
+    _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("min_num_inliers", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32),
+                ("seed", C.c_uint64), ("scale_factors", _VP), ("num_levels", C.c_int32), ("counts", _VP), ("valid", _VP), ("bearing", _VP), ("pos_w", _VP),
+                ("octave", _VP), ("samples", _VP), ("out_status", _VP), ("out_num_matches", _VP), ("out_rot_cw", _VP), ("out_trans_cw", _VP),
                 ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
 
 
@@ -1840,6 +2025,31 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_sim3_ransac_device(self._h, C.byref(a), st))
+
+    def pnp_ransac(self, valid, bearing, pos_w, octave, scale_factors, iters=30, min_num_inliers=10, recompute=True, samples=None, seed=0, counts=None,
+                   outputs=None, out=None):
+        """solve::pnp_solver's constructor and find_via_ransac for P problems (plp_pnp_ransac_host): valid (P, n_cap) u8, bearing / pos_w
+        (P, n_cap, 3) f64, octave (P, n_cap), scale_factors (num_levels,) f32, samples (P, iters, 4) indices of matches or None = drawn from
+        seed, counts (P,) or None.  Returns dict(status (P,) u8: PNP_*, num_matches, rot_cw (P, 3, 3), trans_cw (P, 3), num_inliers, best_iter,
+        inliers (P, n_cap) u8, hyp_inliers (P, iters)); `outputs` names the optional ones wanted (default both); out[name]: the caller's array."""
+        call = lambda a: _check(lib().plp_pnp_ransac_host(self._h, C.byref(a)))
+        return _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples, seed, counts, outputs, out)
+
+    def pnp_ransac_device(self, P, n_cap, valid, bearing, pos_w, octave, scale_factors, out, iters=30, min_num_inliers=10, recompute=True, samples=None,
+                          seed=0, counts=None, stream=None):
+        """plp_pnp_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors is a host vector);
+        out: dict of the device outputs named as in PNP_OUTPUTS (inliers / hyp_inliers may be absent); asynchronous, five kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)           # lives until the call has returned
+        a = _struct(pnp_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), min_num_inliers=int(min_num_inliers), iters=int(iters),
+                                            recompute=int(bool(recompute)), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(sf)), dict(
+            scale_factors=sf.ctypes.data if len(sf) else None, counts=D(counts), valid=D(valid), bearing=D(bearing), pos_w=D(pos_w), octave=D(octave),
+            samples=D(samples), out_status=D(out.get("status")), out_num_matches=D(out.get("num_matches")), out_rot_cw=D(out.get("rot_cw")),
+            out_trans_cw=D(out.get("trans_cw")), out_num_inliers=D(out.get("num_inliers")), out_best_iter=D(out.get("best_iter")),
+            out_inliers=D(out.get("inliers")), out_hyp_inliers=D(out.get("hyp_inliers"))))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_pnp_ransac_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):
