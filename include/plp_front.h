@@ -1422,7 +1422,9 @@ int32_t plp_model_pnp_thresholds_host(const float* scale_factors, int32_t num_le
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to
  * offsets[l]) whose median Hamming distance to all rows of the landmark -- itself included, rank (unsigned)(0.5 * (n - 1)) --
- * is smallest, first such row; -1 for a landmark without rows.  At most 1024 rows per landmark. */
+ * is smallest, first such row; -1 for a landmark without rows.  At most 1024 rows per landmark: _host checks it (and that the offsets
+ * ascend) and returns PLP_ERR_UNSUPPORTED with nothing written; _device cannot see the offsets and takes any n, but its kernel packs the
+ * row into 16 bits of the key it minimises, so on the device entry the limit is the caller's to keep. */
 plp_status plp_landmark_descriptor_device(plp_matcher* ctx, const uint8_t* d_descs, const int32_t* d_offsets, int32_t L, int32_t* d_best_idx,
                                           void* hip_stream);
 plp_status plp_landmark_descriptor_host(plp_matcher* ctx, const uint8_t* descs, const int32_t* offsets, int32_t L, int32_t* best_idx);
