@@ -1418,6 +1418,100 @@ int32_t plp_model_pnp_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t
 /* max_cos_errors_ per level (:47-51) for num_levels scale factors: out num_levels floats.  Returns num_levels, or -1. */
 int32_t plp_model_pnp_thresholds_host(const float* scale_factors, int32_t num_levels, float* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Per-frame pose optimisation: optimize::pose_optimizer::optimize (src/PLPSLAM/optimize/pose_optimizer.cc:53-229) and
+ * optimize::pose_optimizer_extended_line::optimize (optimize/pose_optimizer_extended_line.cc:62-305) for B frames at once, in slot form --
+ * what the tracker runs after the last-frame match (module/frame_tracker.cc:83-96), after the local-map match (tracking_module.cc:750-759)
+ * and up to three times per relocalisation candidate (module/relocalizer.cc:118, 164-168, 209-213).  l_cap == 0 is pose_optimizer, l_cap > 0
+ * the extended optimiser.  Numeric contract: DESIGN.md section 5, D15 (the vertex, the edges, sin / cos, the order of the sums, the 6 x 6
+ * Cholesky, g2o's Levenberg-Marquardt, what the reference leaves undefined); g2o is not linked.
+ *
+ * Slot = key point (key line) of the frame, [B][n_cap] ([B][l_cap]):
+ *   valid        1 where frm.landmarks_.at(idx) is set and will not be erased                          :126-134 / :135-143
+ *   undist       frm.undist_keypts_ (pt and octave are read)                                           :140-142
+ *   x_right      frm.stereo_x_right_; NULL = every key point monocular (-1)                            :141
+ *   pos_w        lm->get_pos_in_world()
+ *   line_valid, keylines (startPoint, endPoint, octave), pos_w_lines (Pluecker, 6)                      pose_optimizer_extended_line.cc:173-202
+ * A valid slot whose octave is outside [0, num_levels) (where inv_level_sigma_sq_.at() throws) is no observation: it is not counted and
+ * its flag is left alone.  The edges are the perspective ones for PLP_CAMERA_PERSPECTIVE and PLP_CAMERA_FISHEYE
+ * (pose_opt_edge_wrapper.h:127-217); PLP_CAMERA_EQUIRECTANGULAR is PLP_ERR_UNSUPPORTED (D15: its atan2 / asin cannot be held bit for bit).
+ * An edge is two- or three-dimensional by x_right < 0 per key point; the Huber delta is sqrt(chi_sq_2D) for setup_type 0, else
+ * sqrt(chi_sq_3D), per frame (:144), and sqrt(chi_sq_2D) for lines.
+ * Outputs per frame:
+ *   out_status        a plp_pose_opt_status
+ *   out_pose          15 doubles: rot_cw (row-major), trans_cw, cam_center as frame::update_pose_params forms it; for
+ *                     PLP_POSE_OPT_TOO_FEW_OBS the first 12 are the input's
+ *   out_num_init_obs  num_init_obs
+ *   out_num_valid     the function's return value, num_init_obs - num_bad_obs; 0 for PLP_POSE_OPT_TOO_FEW_OBS
+ *   out_outlier       [B][n_cap]: frm.outlier_flags_; only observation slots are written
+ *   out_outlier_lines [B][l_cap]: frm._outlier_flags_line; written only when num_init_obs >= 5 (:161-165), observation slots only
+ *   out_trial_info    optional, [B][num_trials][4]: iterations run, rejected steps, num_bad_obs, why optimize() ended (1 all iterations,
+ *                     2 the ten tries were used up, 3 rho == 0); a trial not run: 0 0 0 0
+ *   out_trial_chi2    optional, [B][num_trials][2]: the robust chi2 of the kept estimate and lambda at the trial's end; not run: 0 0 */
+typedef enum plp_pose_opt_status {
+    PLP_POSE_OPT_OK = 0,
+    PLP_POSE_OPT_TOO_FEW_OBS = 1     /* num_init_obs < 5: nothing optimised (:153 / :162) */
+} plp_pose_opt_status;
+typedef struct plp_pose_optimize_args {
+    plp_camera_model camera;            /* model, fx, fy, cx, cy, focal_x_baseline are read */
+    int32_t setup_type;                 /* camera::setup_type_t: 0 monocular, 1 stereo, 2 RGB-D */
+    int32_t B, n_cap, l_cap;            /* B >= 0 frames; n_cap, l_cap in 0 .. 8192; l_cap == 0: no line edges */
+    int32_t num_trials, num_each_iter;  /* >= 1; 4 and 10 by the constructors' defaults */
+    int32_t pose_stride;                /* doubles between two rows of pose_in, >= 12 (15 for plp.frame_pose rows) */
+    const float* inv_level_sigma_sq;    /* HOST, num_levels: frm.inv_level_sigma_sq_ */
+    int32_t num_levels;                 /* 1 .. 16 */
+    const float* inv_level_sigma_sq_lsd;/* HOST, num_levels_lsd: frm._inv_level_sigma_sq_lsd; may be NULL when l_cap == 0 */
+    int32_t num_levels_lsd;             /* 1 .. 16 when l_cap > 0 */
+    const double* pose_in;              /* B rows: rot_cw row-major (9), trans_cw (3); the rest of a row is not read */
+    const int32_t* counts;              /* B: point slots in use, or NULL = n_cap */
+    const int32_t* line_counts;         /* B: line slots in use, or NULL = l_cap */
+    const uint8_t* valid;               /* B x n_cap */
+    const plp_keypoint* undist;         /* B x n_cap */
+    const float* x_right;               /* B x n_cap, or NULL */
+    const double* pos_w;                /* B x n_cap x 3 */
+    const uint8_t* line_valid;          /* B x l_cap */
+    const plp_keyline* keylines;        /* B x l_cap */
+    const double* pos_w_lines;          /* B x l_cap x 6 */
+    uint8_t* out_status;                /* B */
+    double* out_pose;                   /* B x 15 */
+    int32_t* out_num_init_obs;          /* B */
+    int32_t* out_num_valid;             /* B */
+    uint8_t* out_outlier;               /* B x n_cap */
+    uint8_t* out_outlier_lines;         /* B x l_cap */
+    int32_t* out_trial_info;            /* B x num_trials x 4, or NULL */
+    double* out_trial_chi2;             /* B x num_trials x 2, or NULL */
+} plp_pose_optimize_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; an unknown camera model or setup_type; fx or fy 0; B, n_cap or
+ * l_cap negative; num_trials or num_each_iter < 1; pose_stride < 12; num_levels outside 1 .. 16 or a NULL inv_level_sigma_sq; with l_cap > 0
+ * num_levels_lsd outside 1 .. 16 or a NULL inv_level_sigma_sq_lsd; and -- when B > 0 -- a NULL pose_in, out_status, out_pose,
+ * out_num_init_obs or out_num_valid, with n_cap > 0 a NULL valid, undist, pos_w or out_outlier, with l_cap > 0 a NULL line_valid, keylines,
+ * pos_w_lines or out_outlier_lines.  The equirectangular camera, n_cap or l_cap > 8192, B > 65535: PLP_ERR_UNSUPPORTED.  B == 0: PLP_OK,
+ * nothing written.
+ * _device: every array but the two sigma tables a DEVICE pointer; two kernels on hip_stream, the whole trial loop inside the second, no host
+ * synchronisation.  The kernels hand the ranks and the edges' last chi2 on through buffers the context owns, so the calls of one context must
+ * be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (the flag outputs too, so that every slot
+ * the kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_pose_optimize_device(plp_matcher* ctx, const plp_pose_optimize_args* args, void* hip_stream);
+plp_status plp_pose_optimize_host(plp_matcher* ctx, const plp_pose_optimize_args* args);
+/* Host builds of the same source (csrc/pose_opt.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_pose_optimize_host: the entry above, one frame and one edge after the other; the same checks.  Returns B, or the negated
+ * plp_status of a refused call (-PLP_ERR_INVALID_ARG, -PLP_ERR_UNSUPPORTED; plp_last_error() names the reason).
+ * plp_model_pose_linearize_host: one linearisation at the poses pose_in of the inputs in `args` (its outputs are not touched): the edges of
+ * the observation slots whose `active` (B x n_cap; NULL = all) / `active_lines` (B x l_cap; NULL = all) byte is non-zero, Huber kernels on
+ * (robust != 0) or off.  out_sums B x 28: H upper triangle row-major (21), b (6), robust chi2; out_chi2 B x n_cap and out_chi2_lines
+ * B x l_cap (either may be NULL): the chi2 of every active edge, other slots keep their values.  Returns as the entry above.
+ * plp_model_se3_exp_host: out = SE3Quat::exp(update) * est (shot_vertex::oplusImpl) for n pairs; update n x 6 (omega, upsilon), est and out
+ * n x 7 (qx qy qz qw tx ty tz).
+ * plp_model_chol6_host: (H + lambda I) x = b for n systems; H n x 21 (upper triangle row-major), b n x 6, lambda n, out_x n x 6, out_ok n
+ * (0 = a pivot was not positive and finite; x is then zero).
+ * plp_model_pose_sincos_host: D15's sin and cos of n doubles.  All three return n, or -1 for a bad argument. */
+int32_t plp_model_pose_optimize_host(const plp_pose_optimize_args* args);
+int32_t plp_model_pose_linearize_host(const plp_pose_optimize_args* args, int32_t robust, const uint8_t* active, const uint8_t* active_lines,
+                                      double* out_sums, double* out_chi2, double* out_chi2_lines);
+int32_t plp_model_se3_exp_host(const double* update, const double* est, int32_t n, double* out);
+int32_t plp_model_chol6_host(const double* H, const double* b, const double* lambda, int32_t n, double* out_x, int32_t* out_ok);
+int32_t plp_model_pose_sincos_host(const double* x, int32_t n, double* out_sin, double* out_cos);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

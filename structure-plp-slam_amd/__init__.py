@@ -160,6 +160,13 @@ _API = [
     ("plp_model_rot_from_abt_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_model_pnp_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
     ("plp_model_pnp_thresholds_host", _I32, [_VP, _I32, _VP]),
+    ("plp_pose_optimize_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_pose_optimize_host", C.c_int, [_VP, _VP]),
+    ("plp_model_pose_optimize_host", _I32, [_VP]),
+    ("plp_model_pose_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_model_se3_exp_host", _I32, [_VP, _VP, _I32, _VP]),
+    ("plp_model_chol6_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_model_pose_sincos_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -620,6 +627,155 @@ class pnp_solver:
 
     def get_inlier_flags(self):
         return self._r["inliers"][0, :self._n].astype(bool)
+
+
+# plp_pose_opt_status: where pose_optimizer::optimize leaves a frame
+POSE_OPT_OK, POSE_OPT_TOO_FEW_OBS = range(2)
+# why a trial's optimize() ended (trial_info[..., 3]); 0 = the trial was not run
+POSE_OPT_END_ITERATIONS, POSE_OPT_END_TRIES, POSE_OPT_END_RHO_ZERO = 1, 2, 3
+# the outputs of plp_pose_optimize_*: name -> (shape per frame given (n_cap, l_cap, num_trials), dtype, optional)
+POSE_OPT_OUTPUTS = dict(status=(lambda N, L, T: (), np.uint8, False), pose=(lambda N, L, T: (15,), np.float64, False),
+                        num_init_obs=(lambda N, L, T: (), np.int32, False), num_valid=(lambda N, L, T: (), np.int32, False),
+                        outlier=(lambda N, L, T: (N,), np.uint8, False), outlier_lines=(lambda N, L, T: (L,), np.uint8, False),
+                        trial_info=(lambda N, L, T: (T, 4), np.int32, True), trial_chi2=(lambda N, L, T: (T, 2), np.float64, True))
+
+
+def _pose_optimize_inputs(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials, num_each_iter):
+    """the input half of a plp_pose_optimize_args from numpy arrays: (args struct, the arrays it points to, B, n_cap, l_cap)"""
+    va = np.ascontiguousarray(valid, np.uint8)
+    if va.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "valid must be (B, n_cap)")
+    B, N = va.shape
+    po = np.ascontiguousarray(pose_in, np.float64)
+    if po.ndim != 2 or po.shape[0] != B or po.shape[1] < 12:
+        raise PlpError(PLP_ERR_INVALID_ARG, "pose_in must be (B, 12 or more)")
+    kp = np.ascontiguousarray(undist, KP_DTYPE).reshape(B, N); pw = np.ascontiguousarray(pos_w, np.float64).reshape(B, N, 3)
+    xr = None if x_right is None else np.ascontiguousarray(x_right, np.float32).reshape(B, N)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
+    sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)
+    L = 0; lv = kl = lw = lc = sl = None
+    if lines is not None:
+        lv = np.ascontiguousarray(lines["valid"], np.uint8).reshape(B, -1)
+        L = lv.shape[1]
+        kl = np.ascontiguousarray(lines["keylines"], KL_DTYPE).reshape(B, L); lw = np.ascontiguousarray(lines["pos_w"], np.float64).reshape(B, L, 6)
+        lc = None if lines.get("counts") is None else np.ascontiguousarray(lines["counts"], np.int32).reshape(B)
+        sl = np.ascontiguousarray(lines["inv_level_sigma_sq_lsd"], np.float32).reshape(-1)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(pose_optimize_args_c, dict(setup_type=int(setup_type), B=B, n_cap=N, l_cap=L, num_trials=int(num_trials), num_each_iter=int(num_each_iter),
+                                           pose_stride=po.shape[1], num_levels=len(sg), num_levels_lsd=0 if sl is None else len(sl)), dict(
+        inv_level_sigma_sq=Pt(sg), inv_level_sigma_sq_lsd=Pt(sl), pose_in=Pt(po), counts=Pt(cn), line_counts=Pt(lc), valid=Pt(va), undist=Pt(kp), x_right=Pt(xr),
+        pos_w=Pt(pw), line_valid=Pt(lv), keylines=Pt(kl), pos_w_lines=Pt(lw)))
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    return a, (va, po, kp, pw, xr, cn, sg, lv, kl, lw, lc, sl), B, N, L
+
+
+def _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials, num_each_iter,
+                        outputs, out):
+    """the numpy side of plp_pose_optimize_host and plp_model_pose_optimize_host: call(args struct) runs the entry"""
+    a, keep, B, N, L = _pose_optimize_inputs(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
+                                             num_each_iter)
+    o = {}
+    for k, (shape, dt, optional) in POSE_OPT_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (B,) + shape(N, L, max(int(num_trials), 0))
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    for k in POSE_OPT_OUTPUTS:
+        setattr(a, "out_" + k, Pt(o.get(k)))
+    call(a)
+    return o
+
+
+def model_pose_optimize(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, num_trials=4,
+                        num_each_iter=10, outputs=None, out=None):
+    """Host build of optimize::pose_optimizer[_extended_line]::optimize (csrc/pose_opt.hpp, DESIGN.md section 5, D15; no GPU needed): the arguments
+    and the result of matcher.pose_optimize."""
+    def call(a):
+        r = lib().plp_model_pose_optimize_host(C.byref(a))
+        if r != a.B:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
+                               num_each_iter, outputs, out)
+
+
+def model_pose_linearize(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, robust=True,
+                         active=None, active_lines=None):
+    """Host build of one linearisation of D15 at the poses pose_in (no GPU needed): the edges of the observation slots whose `active` /
+    `active_lines` byte is set (None = all), Huber kernels on or off.  Returns dict(H (B, 21) upper triangle row-major, b (B, 6), chi2 (B,) the
+    robust sum, edge_chi2 (B, n_cap), edge_chi2_lines (B, l_cap); NaN where no edge was evaluated)."""
+    a, keep, B, N, L = _pose_optimize_inputs(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, 1, 1)
+    ac = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(B, N)
+    al = None if active_lines is None else np.ascontiguousarray(active_lines, np.uint8).reshape(B, L)
+    sums = np.zeros((B, 28)); ec = np.full((B, N), np.nan); el = np.full((B, L), np.nan)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    # the checks of the entry want its required outputs
+    dummy = _pose_optimize_host(lambda a_: None, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, 1, 1, None, None)
+    for k in ("status", "pose", "num_init_obs", "num_valid", "outlier", "outlier_lines"):
+        setattr(a, "out_" + k, Pt(dummy[k]))
+    r = lib().plp_model_pose_linearize_host(C.byref(a), int(bool(robust)), Pt(ac), Pt(al), Pt(sums), Pt(ec), Pt(el))
+    if r != B:
+        raise PlpError(-r, lib().plp_last_error().decode())
+    return dict(H=sums[:, :21].copy(), b=sums[:, 21:27].copy(), chi2=sums[:, 27].copy(), edge_chi2=ec, edge_chi2_lines=el)
+
+
+def model_se3_exp(update, est):
+    """Host build of shot_vertex::oplusImpl (D15 item 1; no GPU needed): SE3Quat::exp(update) * est for n pairs; update (n, 6) = (omega, upsilon),
+    est (n, 7) = (qx, qy, qz, qw, tx, ty, tz).  Returns (n, 7)."""
+    u = np.ascontiguousarray(update, np.float64).reshape(-1, 6); e = np.ascontiguousarray(est, np.float64).reshape(-1, 7)
+    assert len(u) == len(e)
+    o = np.zeros_like(e)
+    if lib().plp_model_se3_exp_host(_p(u), _p(e), len(u), _p(o)) != len(u):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_se3_exp_host")
+    return o
+
+
+def model_chol6(H, b, lam):
+    """Host build of D15 item 4 (no GPU needed): (H + lambda I) x = b for n systems; H (n, 21) upper triangle row-major, b (n, 6), lam (n,).
+    Returns (x (n, 6), ok (n,) bool); x is zero where a pivot was not positive and finite."""
+    H = np.ascontiguousarray(H, np.float64).reshape(-1, 21); b = np.ascontiguousarray(b, np.float64).reshape(-1, 6)
+    lam = np.ascontiguousarray(lam, np.float64).reshape(-1)
+    assert len(H) == len(b) == len(lam)
+    x = np.zeros_like(b); ok = np.zeros(len(H), np.int32)
+    if lib().plp_model_chol6_host(_p(H), _p(b), _p(lam), len(H), _p(x), _p(ok)) != len(H):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_chol6_host")
+    return x, ok.astype(bool)
+
+
+def model_pose_sincos(x):
+    """Host build of D15's sin and cos (csrc/pose_opt.hpp pose_sincos; no GPU needed; model_sincos is the line extractor's f32 pair): (sin, cos) f64"""
+    x = np.ascontiguousarray(x, np.float64)
+    s = np.zeros(x.shape); c = np.zeros(x.shape)
+    if lib().plp_model_pose_sincos_host(_p(x), x.size, _p(s), _p(c)) != x.size:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_sincos_host")
+    return s, c
+
+
+class pose_optimizer:
+    """Mirror of optimize::pose_optimizer and optimize::pose_optimizer_extended_line (optimize/pose_optimizer.h): optimize() takes one frame's
+    arrays and returns (num_valid, result dict of that frame); mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, num_trials=4, num_each_iter=10, mt=None):
+        self.num_trials, self.num_each_iter, self._mt = int(num_trials), int(num_each_iter), mt
+
+    def optimize(self, camera, setup_type, cam_pose_cw, valid, undist_keypts, pos_w, inv_level_sigma_sq, x_right=None, lines=None):
+        """cam_pose_cw: 4 x 4 (or a 12 / 15-double pose row); valid (n,), undist_keypts (n,) KP_DTYPE, pos_w (n, 3); lines: None or dict(valid (l,),
+        keylines (l,) KL_DTYPE, pos_w (l, 6), inv_level_sigma_sq_lsd).  Returns (the reference's return value, dict(status, pose (15,), cam_pose_cw
+        4 x 4, num_init_obs, outlier (n,), outlier_lines (l,), trial_info, trial_chi2))."""
+        T = np.asarray(cam_pose_cw, np.float64)
+        row = np.concatenate([T[:3, :3].reshape(9), T[:3, 3]]) if T.shape == (4, 4) else T.reshape(-1)[:12]
+        n = len(np.asarray(valid).reshape(-1))
+        ln = None if lines is None else dict(lines, valid=np.asarray(lines["valid"]).reshape(1, -1))
+        fn = model_pose_optimize if self._mt is None else self._mt.pose_optimize
+        r = fn(camera, setup_type, row.reshape(1, 12), np.asarray(valid).reshape(1, n), undist_keypts, pos_w, inv_level_sigma_sq, x_right=x_right, lines=ln,
+               num_trials=self.num_trials, num_each_iter=self.num_each_iter)
+        o = {k: v[0] for k, v in r.items()}
+        M = np.eye(4); M[:3, :3] = o["pose"][:9].reshape(3, 3); M[:3, 3] = o["pose"][9:12]
+        o["cam_pose_cw"] = M
+        return int(o["num_valid"]), o
 
 
 class orb_extractor:
@@ -1173,6 +1329,16 @@ class pnp_ransac_args_c(C.Structure):
                 ("seed", C.c_uint64), ("scale_factors", _VP), ("num_levels", C.c_int32), ("counts", _VP), ("valid", _VP), ("bearing", _VP), ("pos_w", _VP),
                 ("octave", _VP), ("samples", _VP), ("out_status", _VP), ("out_num_matches", _VP), ("out_rot_cw", _VP), ("out_trans_cw", _VP),
                 ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
+
+
+class pose_optimize_args_c(C.Structure):
+    """plp_pose_optimize_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("B", C.c_int32), ("n_cap", C.c_int32), ("l_cap", C.c_int32),
+                ("num_trials", C.c_int32), ("num_each_iter", C.c_int32), ("pose_stride", C.c_int32), ("inv_level_sigma_sq", _VP), ("num_levels", C.c_int32),
+                ("inv_level_sigma_sq_lsd", _VP), ("num_levels_lsd", C.c_int32), ("pose_in", _VP), ("counts", _VP), ("line_counts", _VP), ("valid", _VP),
+                ("undist", _VP), ("x_right", _VP), ("pos_w", _VP), ("line_valid", _VP), ("keylines", _VP), ("pos_w_lines", _VP), ("out_status", _VP),
+                ("out_pose", _VP), ("out_num_init_obs", _VP), ("out_num_valid", _VP), ("out_outlier", _VP), ("out_outlier_lines", _VP),
+                ("out_trial_info", _VP), ("out_trial_chi2", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -2050,6 +2216,41 @@ class matcher:
             out_inliers=D(out.get("inliers")), out_hyp_inliers=D(out.get("hyp_inliers"))))
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_pnp_ransac_device(self._h, C.byref(a), st))
+
+    def pose_optimize(self, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, num_trials=4,
+                      num_each_iter=10, outputs=None, out=None):
+        """optimize::pose_optimizer::optimize (lines None) / pose_optimizer_extended_line::optimize for B frames (plp_pose_optimize_host): camera a
+        camera_model, setup_type 0 / 1 / 2, pose_in (B, >= 12) rot_cw row-major + trans_cw (frame_pose rows), valid (B, n_cap) u8, undist (B, n_cap)
+        KP_DTYPE, pos_w (B, n_cap, 3), inv_level_sigma_sq (num_levels,) f32, x_right (B, n_cap) f32 or None = monocular key points, counts (B,) or
+        None; lines: dict(valid (B, l_cap), keylines KL_DTYPE, pos_w (B, l_cap, 6) Pluecker, inv_level_sigma_sq_lsd, counts or None).  Returns
+        dict(status (B,) u8: POSE_OPT_*, pose (B, 15), num_init_obs, num_valid, outlier (B, n_cap) u8, outlier_lines (B, l_cap), trial_info
+        (B, num_trials, 4), trial_chi2 (B, num_trials, 2)); `outputs` names the optional ones wanted (default both); out[name]: the caller's array
+        (slots the reference does not write keep their values)."""
+        call = lambda a: _check(lib().plp_pose_optimize_host(self._h, C.byref(a)))
+        return _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
+                                   num_each_iter, outputs, out)
+
+    def pose_optimize_device(self, camera, setup_type, B, n_cap, pose_in, valid, undist, pos_w, inv_level_sigma_sq, out, x_right=None, counts=None,
+                             l_cap=0, line_valid=None, keylines=None, pos_w_lines=None, inv_level_sigma_sq_lsd=None, line_counts=None, num_trials=4,
+                             num_each_iter=10, pose_stride=15, stream=None):
+        """plp_pose_optimize_device: every array a device pointer (int) or a torch tensor on the matcher's device (the two sigma tables are host
+        vectors); out: dict of the device outputs named as in POSE_OPT_OUTPUTS (trial_info / trial_chi2 may be absent, outlier_lines when l_cap
+        is 0); asynchronous, two kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)           # live until the call has returned
+        sl = None if inv_level_sigma_sq_lsd is None else np.ascontiguousarray(inv_level_sigma_sq_lsd, np.float32).reshape(-1)
+        a = _struct(pose_optimize_args_c, dict(setup_type=int(setup_type), B=int(B), n_cap=int(n_cap), l_cap=int(l_cap), num_trials=int(num_trials),
+                                               num_each_iter=int(num_each_iter), pose_stride=int(pose_stride), num_levels=len(sg),
+                                               num_levels_lsd=0 if sl is None else len(sl)), dict(
+            inv_level_sigma_sq=sg.ctypes.data if len(sg) else None, inv_level_sigma_sq_lsd=None if sl is None or not len(sl) else sl.ctypes.data,
+            pose_in=D(pose_in), counts=D(counts), line_counts=D(line_counts), valid=D(valid), undist=D(undist), x_right=D(x_right), pos_w=D(pos_w),
+            line_valid=D(line_valid), keylines=D(keylines), pos_w_lines=D(pos_w_lines)))
+        for k in POSE_OPT_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_pose_optimize_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):

@@ -12,7 +12,8 @@ For B frames whose features are already in HBM (extractor outputs plus the post-
 The projections write their outputs in the layout the matcher reads, so nothing is copied between a projection and its matcher.  The
 current frame's `landmarks_` are cleared before call 1 (frame_tracker.cc:61): calls 1 and 2 see no occupied key point.  Calls 3 and 4 see
 the key points / key lines the last-frame calls matched to a landmark with an observation (what `landmarks_[idx] && has_observation()` reads
-there) unless the caller passes its own arrays (e.g. after removing the pose optimiser's outliers).  Pose optimisation itself, the widened
+there) unless the caller passes its own arrays (e.g. after removing the pose optimiser's outliers).  Pose optimisation lives in
+pose_optimization_step.py (tracked_pose_step: run_last_frame, plp_pose_optimize_device, run_local, plp_pose_optimize_device again); the widened
 second search of motion_based_track and the host's writes back to the landmark objects are not part of the step.
 
 Tables are torch tensors on the step's device, one row per frame:
@@ -75,20 +76,39 @@ class posed_tracker_step:
         Returns dict(m1, n1, m2, n2, m3, n3, m4, n4): out_match [B, n_cap] / out_num [B] of the four calls (LAST_FRAME, LANDMARKS, LAST_FRAME_LINE,
         LANDMARKS_LINE), and the intermediate query arrays under q1 ... q4.  Nothing is synchronised; the returned tensors are the step's own
         buffers, rewritten by the next run."""
-        torch, plp, cam = self.torch, self.plp, self.camera
+        torch = self.torch
         st = stream or torch.cuda.current_stream(self.dev)
-        pose = pose_pred if pose is None else pose
-        B, cap = frame["kps"].shape[0], frame["kps"].shape[1]
-        lcap = frame["kl"].shape[1]
-        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        out = self.run_last_frame(frame, last, pose_pred, stream=st)
+        # what calls 3 and 4 see as occupied: curr_frm.landmarks_[idx] && has_observation() after the last-frame calls
+        with torch.cuda.stream(st):
+            if t_occupied is None:
+                t_occupied = self._occupied(out["m1"], frame["counts"], last.get("has_obs"))
+            if t_occupied_lines is None:
+                t_occupied_lines = self._occupied(out["m3"], frame["kl_counts"], last.get("has_obs_lines"))
+        out.update(self.run_local(frame, local, pose_pred if pose is None else pose, t_occupied, t_occupied_lines, stream=st))
+        return out
+
+    def _targets(self, frame, st, last_frame=True):
+        torch = self.torch
         t = dict(t_kps=frame["kps"], t_desc=frame["desc"], t_counts=frame["counts"], t_x_right=frame.get("x_right"))
         kxr = frame.get("kl_x_right")
         tl = dict(t_kl=frame["kl"], t_desc=frame["lbd"], t_counts=frame["kl_counts"])
-        rgbd = self.setup_type == plp.SETUP_RGBD
         tl_last = dict(tl)
-        if kxr is not None:   # _stereo_x_right_cooresponding_to_keylines first / second as the two arrays LAST_FRAME_LINE's RGB-D gate reads
+        if kxr is not None and last_frame:   # _stereo_x_right_cooresponding_to_keylines first / second as the two arrays LAST_FRAME_LINE's RGB-D gate reads
             with torch.cuda.stream(st):
                 tl_last["t_x_right"], tl_last["t_x_right2"] = kxr[..., 0].contiguous(), kxr[..., 1].contiguous()
+        return t, tl, tl_last
+
+    def run_last_frame(self, frame, last, pose_pred, stream=None):
+        """Calls 1 and 2 of run() alone (a pose optimiser may sit between them and calls 3 and 4: pose_optimization_step.py): dict(m1, n1, q1,
+        direction, m3, n3, q3, direction_lines)."""
+        torch, plp, cam = self.torch, self.plp, self.camera
+        st = stream or torch.cuda.current_stream(self.dev)
+        B, cap = frame["kps"].shape[0], frame["kps"].shape[1]
+        lcap = frame["kl"].shape[1]
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        t, tl, tl_last = self._targets(frame, st)
+        rgbd = self.setup_type == plp.SETUP_RGBD
         out = {}
 
         # 1  last frame, points
@@ -121,12 +141,17 @@ class posed_tracker_step:
                                        B=B, stream=st, directions=d3)
         out.update(m3=m3, n3=n3, q3=q3, direction_lines=d3)
 
-        # what calls 3 and 4 see as occupied: curr_frm.landmarks_[idx] && has_observation() after the last-frame calls
-        with torch.cuda.stream(st):
-            if t_occupied is None:
-                t_occupied = self._occupied(m1, frame["counts"], last.get("has_obs"))
-            if t_occupied_lines is None:
-                t_occupied_lines = self._occupied(m3, frame["kl_counts"], last.get("has_obs_lines"))
+        return out
+
+    def run_local(self, frame, local, pose, t_occupied, t_occupied_lines, stream=None):
+        """Calls 3 and 4 of run() alone, with the occupancy they see given: dict(m2, n2, q2, t_occupied, m4, n4, q4, t_occupied_lines)."""
+        torch, plp, cam = self.torch, self.plp, self.camera
+        st = stream or torch.cuda.current_stream(self.dev)
+        B, cap = frame["kps"].shape[0], frame["kps"].shape[1]
+        lcap = frame["kl"].shape[1]
+        i32, f32, u8 = torch.int32, torch.float32, torch.uint8
+        t, tl, _ = self._targets(frame, st, False)
+        out = {}
 
         # 3  local landmarks, points
         L = local["pos_w"].shape[1]
