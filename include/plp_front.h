@@ -1512,6 +1512,98 @@ int32_t plp_model_se3_exp_host(const double* update, const double* est, int32_t 
 int32_t plp_model_chol6_host(const double* H, const double* b, const double* lambda, int32_t n, double* out_x, int32_t* out_ok);
 int32_t plp_model_pose_sincos_host(const double* x, int32_t n, double* out_sin, double* out_cos);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Sim3 refinement of loop candidates: optimize::transform_optimizer::optimize (src/PLPSLAM/optimize/transform_optimizer.cc:47-197) for P
+ * problems at once, in slot form -- what loop_detector::select_loop_candidate_via_Sim3 runs per candidate between the mutual projection
+ * match and its `num_optimized_inliers < 20` decision (module/loop_detector.cc:389-396).  A problem is one pair: the current key frame (1)
+ * and a candidate (2).  Numeric contract: DESIGN.md section 5, D16 (the Sim3 vertex, exp, the two reprojection edges per match with g2o's
+ * numeric Jacobian, the order of the sums, the 7 x 7 Cholesky, the two rounds) on top of D15; g2o is not linked.
+ *
+ * Slot = key point idx1 of key frame 1, [P][n_cap]:
+ *   valid        1 where matched_lms_in_keyfrm_2.at(idx1) is set, lm_1 and lm_2 exist, neither will be erased and
+ *                lm_2->get_index_in_keyframe(keyfrm_2) >= 0                                              :95-118
+ *   pos_w_1/_2   lm_1 / lm_2 ->get_pos_in_world()
+ *   undist_1/_2  keyfrm_1->undist_keypts_.at(idx1) / keyfrm_2->undist_keypts_.at(idx2) (pt and octave are read)
+ * A valid slot with either octave outside [0, num_levels) (where inv_level_sigma_sq_.at() throws) is no observation: it is not counted and
+ * its out_kept byte is left alone.  The edges are the perspective ones for PLP_CAMERA_PERSPECTIVE and PLP_CAMERA_FISHEYE
+ * (mutual_reproj_edge_wrapper.h:106-256); PLP_CAMERA_EQUIRECTANGULAR is PLP_ERR_UNSUPPORTED (D15's reason).
+ * Outputs per problem:
+ *   out_status        a plp_transform_opt_status
+ *   out_num_valid     num_valid_matches
+ *   out_num_inliers   the function's return value; 0 for PLP_TRANSFORM_OPT_TOO_FEW_INLIERS
+ *   out_rot_12 (9, row-major), out_trans_12 (3), out_scale_12 (double): g2o_Sim3_12 after the call; for
+ *                     PLP_TRANSFORM_OPT_TOO_FEW_INLIERS the input's values (the Sim3 is not written back)
+ *   out_world_to_1    optional, 13 doubles: g2o_Sim3_12 * Sim3(rot_2w, trans_2w, 1.0) as rot (9), trans (3), scale (loop_detector.cc:404),
+ *                     formed from the returned Sim3 for either status
+ *   out_kept          [P][n_cap]: 1 where matched_lms_in_keyfrm_2.at(idx1) is still set after the call (the drops of round 1 stand on the
+ *                     early return); only observation slots are written
+ *   out_round_info    optional, [P][2][4] per round: iterations run, rejected steps, matches dropped, why optimize() ended (1 all
+ *                     iterations, 2 the ten tries were used up, 3 rho == 0); a round not run: 0 0 0 0
+ *   out_round_chi2    optional, [P][2][2]: the robust chi2 of the kept estimate and lambda at the round's end; not run: 0 0 */
+typedef enum plp_transform_opt_status {
+    PLP_TRANSFORM_OPT_OK = 0,
+    PLP_TRANSFORM_OPT_TOO_FEW_INLIERS = 1     /* fewer than 10 matches left after round 1 (:156), or no match at all */
+} plp_transform_opt_status;
+typedef struct plp_transform_optimize_args {
+    plp_camera_model camera;            /* model, fx, fy, cx, cy are read; both key frames share it */
+    int32_t fix_scale;                  /* transform_optimizer's fix_scale_ */
+    int32_t num_iter;                   /* >= 1; 10 by the constructor's default */
+    float chi_sq;                       /* > 0; 10 at loop_detector.cc:391 */
+    int32_t P, n_cap;                   /* P >= 0 problems; n_cap in 0 .. 8192 */
+    const float* inv_level_sigma_sq_1;  /* HOST, num_levels: keyfrm_1->inv_level_sigma_sq_ */
+    const float* inv_level_sigma_sq_2;  /* HOST, num_levels: keyfrm_2->inv_level_sigma_sq_ */
+    int32_t num_levels;                 /* 1 .. 16 */
+    const int32_t* counts;              /* P: slots in use, or NULL = n_cap */
+    const uint8_t* valid;               /* P x n_cap */
+    const double* pos_w_1;              /* P x n_cap x 3 */
+    const double* pos_w_2;              /* P x n_cap x 3 */
+    const plp_keypoint* undist_1;       /* P x n_cap */
+    const plp_keypoint* undist_2;       /* P x n_cap */
+    const double* pose_1;               /* P rows of 15: rot_1w row-major (9), trans_1w (3); the rest is not read */
+    const double* pose_2;               /* P rows of 15: rot_2w, trans_2w */
+    const double* rot_12;               /* P x 9 */
+    const double* trans_12;             /* P x 3 */
+    const float* scale_12;              /* P: the solver's float (loop_detector.cc:382) */
+    uint8_t* out_status;                /* P */
+    int32_t* out_num_valid;             /* P */
+    int32_t* out_num_inliers;           /* P */
+    double* out_rot_12;                 /* P x 9 */
+    double* out_trans_12;               /* P x 3 */
+    double* out_scale_12;               /* P */
+    double* out_world_to_1;             /* P x 13, or NULL */
+    uint8_t* out_kept;                  /* P x n_cap */
+    int32_t* out_round_info;            /* P x 2 x 4, or NULL */
+    double* out_round_chi2;             /* P x 2 x 2, or NULL */
+} plp_transform_optimize_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; an unknown camera model; fx or fy 0, or fx, fy, cx or cy not finite; P or
+ * n_cap negative; num_iter < 1; chi_sq not positive; num_levels outside 1 .. 16 or a NULL sigma table; and -- when P > 0 -- a NULL pose_1, pose_2, rot_12,
+ * trans_12, scale_12, out_status, out_num_valid, out_num_inliers, out_rot_12, out_trans_12 or out_scale_12, with n_cap > 0 a NULL valid,
+ * pos_w_1, pos_w_2, undist_1, undist_2 or out_kept.  The equirectangular camera, n_cap > 8192, P > 65535: PLP_ERR_UNSUPPORTED.  P == 0:
+ * PLP_OK, nothing written.
+ * _device: every array but the two sigma tables a DEVICE pointer; three kernels on hip_stream, both rounds inside the second, no host
+ * synchronisation.  The kernels hand the ranks, the edges' constants and last chi2 and the outcome on through buffers the context owns, so the calls of one context must
+ * be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (out_kept too, so that every slot the
+ * kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_transform_optimize_device(plp_matcher* ctx, const plp_transform_optimize_args* args, void* hip_stream);
+plp_status plp_transform_optimize_host(plp_matcher* ctx, const plp_transform_optimize_args* args);
+/* Host builds of the same source (csrc/transform_opt.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_transform_optimize_host: the entry above, one problem and one edge after the other; the same checks.  Returns P, or the negated
+ * plp_status of a refused call.
+ * plp_model_transform_linearize_host: one linearisation at the Sim3 of the inputs in `args` (its output pointers are neither written nor checked: they
+ * may all be NULL; the checks of the inputs are the entry's): the two edges of
+ * every observation slot whose `active` byte (P x n_cap; NULL = all) is non-zero.  out_sums P x 36: H upper triangle row-major (28), b (7),
+ * robust chi2; out_chi2 P x n_cap x 2 (may be NULL): forward and backward chi2 of every active match, other slots keep their values.
+ * plp_model_sim3_exp_host: out = Sim3(update) * est (transform_vertex::oplusImpl) for n pairs; update n x 7 (omega, upsilon, sigma), est and
+ * out n x 8 (qx qy qz qw tx ty tz s); fix_scale != 0 takes sigma as 0.
+ * plp_model_chol7_host: (H + lambda I) x = b for n systems; H n x 28 (upper triangle row-major), b n x 7, lambda n, out_x n x 7, out_ok n
+ * (0 = a pivot was not positive and finite; x is then zero).
+ * plp_model_pose_exp_host: D16's exp of n doubles (NaN outside [-700, 700]).  The last three return n, or -1 for a bad argument. */
+int32_t plp_model_transform_optimize_host(const plp_transform_optimize_args* args);
+int32_t plp_model_transform_linearize_host(const plp_transform_optimize_args* args, const uint8_t* active, double* out_sums, double* out_chi2);
+int32_t plp_model_sim3_exp_host(const double* update, const double* est, int32_t fix_scale, int32_t n, double* out);
+int32_t plp_model_chol7_host(const double* H, const double* b, const double* lambda, int32_t n, double* out_x, int32_t* out_ok);
+int32_t plp_model_pose_exp_host(const double* x, int32_t n, double* out);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

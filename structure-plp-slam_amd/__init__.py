@@ -167,6 +167,13 @@ _API = [
     ("plp_model_se3_exp_host", _I32, [_VP, _VP, _I32, _VP]),
     ("plp_model_chol6_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
     ("plp_model_pose_sincos_host", _I32, [_VP, _I32, _VP, _VP]),
+    ("plp_transform_optimize_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_transform_optimize_host", C.c_int, [_VP, _VP]),
+    ("plp_model_transform_optimize_host", _I32, [_VP]),
+    ("plp_model_transform_linearize_host", _I32, [_VP, _VP, _VP, _VP]),
+    ("plp_model_sim3_exp_host", _I32, [_VP, _VP, _I32, _I32, _VP]),
+    ("plp_model_chol7_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_model_pose_exp_host", _I32, [_VP, _I32, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -778,6 +785,143 @@ class pose_optimizer:
         return int(o["num_valid"]), o
 
 
+# plp_transform_opt_status: where transform_optimizer::optimize leaves a problem
+TRANSFORM_OPT_OK, TRANSFORM_OPT_TOO_FEW_INLIERS = range(2)
+# the outputs of plp_transform_optimize_*: name -> (shape per problem given n_cap, dtype, optional); round_info[..., 3] is a POSE_OPT_END_*
+TRANSFORM_OPT_OUTPUTS = dict(status=(lambda N: (), np.uint8, False), num_valid=(lambda N: (), np.int32, False), num_inliers=(lambda N: (), np.int32, False),
+                             rot_12=(lambda N: (9,), np.float64, False), trans_12=(lambda N: (3,), np.float64, False), scale_12=(lambda N: (), np.float64, False),
+                             world_to_1=(lambda N: (13,), np.float64, True), kept=(lambda N: (N,), np.uint8, False),
+                             round_info=(lambda N: (2, 4), np.int32, True), round_chi2=(lambda N: (2, 2), np.float64, True))
+
+
+def _transform_optimize_inputs(camera, fix_scale, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12, inv_level_sigma_sq_1,
+                               inv_level_sigma_sq_2, counts, num_iter, chi_sq):
+    """the input half of a plp_transform_optimize_args from numpy arrays: (args struct, the arrays it points to, P, n_cap)"""
+    va = np.ascontiguousarray(valid, np.uint8)
+    if va.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "valid must be (P, n_cap)")
+    P, N = va.shape
+    w1 = np.ascontiguousarray(pos_w_1, np.float64).reshape(P, N, 3); w2 = np.ascontiguousarray(pos_w_2, np.float64).reshape(P, N, 3)
+    k1 = np.ascontiguousarray(undist_1, KP_DTYPE).reshape(P, N); k2 = np.ascontiguousarray(undist_2, KP_DTYPE).reshape(P, N)
+    p1 = np.ascontiguousarray(pose_1, np.float64).reshape(P, 15); p2 = np.ascontiguousarray(pose_2, np.float64).reshape(P, 15)
+    r = np.ascontiguousarray(rot_12, np.float64).reshape(P, 9); t = np.ascontiguousarray(trans_12, np.float64).reshape(P, 3)
+    sc = np.ascontiguousarray(scale_12, np.float32).reshape(P)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P)
+    s1 = np.ascontiguousarray(inv_level_sigma_sq_1, np.float32).reshape(-1); s2 = np.ascontiguousarray(inv_level_sigma_sq_2, np.float32).reshape(-1)
+    if len(s1) != len(s2):
+        raise PlpError(PLP_ERR_INVALID_ARG, "the two sigma tables must have one length")
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(transform_optimize_args_c, dict(fix_scale=int(bool(fix_scale)), num_iter=int(num_iter), chi_sq=float(chi_sq), P=P, n_cap=N, num_levels=len(s1)), dict(
+        inv_level_sigma_sq_1=Pt(s1), inv_level_sigma_sq_2=Pt(s2), counts=Pt(cn), valid=Pt(va), pos_w_1=Pt(w1), pos_w_2=Pt(w2), undist_1=Pt(k1), undist_2=Pt(k2),
+        pose_1=Pt(p1), pose_2=Pt(p2), rot_12=Pt(r), trans_12=Pt(t), scale_12=Pt(sc)))
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    return a, (va, w1, w2, k1, k2, p1, p2, r, t, sc, cn, s1, s2), P, N
+
+
+def _transform_optimize_host(call, inputs, outputs, out):
+    """the numpy side of plp_transform_optimize_host and plp_model_transform_optimize_host: call(args struct) runs the entry"""
+    a, keep, P, N = _transform_optimize_inputs(**inputs)
+    o = {}
+    for k, (shape, dt, optional) in TRANSFORM_OPT_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (P,) + shape(N)
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    for k in TRANSFORM_OPT_OUTPUTS:
+        setattr(a, "out_" + k, Pt(o.get(k)))
+    call(a)
+    return o
+
+
+def model_transform_optimize(camera, fix_scale, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12, inv_level_sigma_sq_1,
+                             inv_level_sigma_sq_2, counts=None, num_iter=10, chi_sq=10.0, outputs=None, out=None):
+    """Host build of optimize::transform_optimizer::optimize (csrc/transform_opt.hpp, DESIGN.md section 5, D16; no GPU needed): the arguments and
+    the result of matcher.transform_optimize."""
+    def call(a):
+        r = lib().plp_model_transform_optimize_host(C.byref(a))
+        if r != a.P:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    inputs = dict(camera=camera, fix_scale=fix_scale, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1,
+                  pose_2=pose_2, rot_12=rot_12, trans_12=trans_12, scale_12=scale_12, inv_level_sigma_sq_1=inv_level_sigma_sq_1,
+                  inv_level_sigma_sq_2=inv_level_sigma_sq_2, counts=counts, num_iter=num_iter, chi_sq=chi_sq)
+    return _transform_optimize_host(call, inputs, outputs, out)
+
+
+def model_transform_linearize(camera, fix_scale, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12, inv_level_sigma_sq_1,
+                              inv_level_sigma_sq_2, counts=None, chi_sq=10.0, active=None):
+    """Host build of one linearisation of D16 at the Sim3 (rot_12, trans_12, scale_12) (no GPU needed): the two edges of every observation slot whose
+    `active` byte is set (None = all).  Returns dict(H (P, 28) upper triangle row-major, b (P, 7), chi2 (P,) the robust sum, edge_chi2 (P, n_cap, 2)
+    forward / backward; NaN where no edge was evaluated)."""
+    inputs = dict(camera=camera, fix_scale=fix_scale, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1,
+                  pose_2=pose_2, rot_12=rot_12, trans_12=trans_12, scale_12=scale_12, inv_level_sigma_sq_1=inv_level_sigma_sq_1,
+                  inv_level_sigma_sq_2=inv_level_sigma_sq_2, counts=counts, num_iter=1, chi_sq=chi_sq)
+    a, keep, P, N = _transform_optimize_inputs(**inputs)
+    ac = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(P, N)
+    sums = np.zeros((P, 36)); ec = np.full((P, N, 2), np.nan)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    r = lib().plp_model_transform_linearize_host(C.byref(a), Pt(ac), Pt(sums), Pt(ec))
+    if r != P:
+        raise PlpError(-r, lib().plp_last_error().decode())
+    return dict(H=sums[:, :28].copy(), b=sums[:, 28:35].copy(), chi2=sums[:, 35].copy(), edge_chi2=ec)
+
+
+def model_sim3_exp(update, est, fix_scale=False):
+    """Host build of transform_vertex::oplusImpl (D16; no GPU needed): Sim3(update) * est for n pairs; update (n, 7) = (omega, upsilon, sigma), est
+    (n, 8) = (qx, qy, qz, qw, tx, ty, tz, s).  Returns (n, 8)."""
+    u = np.ascontiguousarray(update, np.float64).reshape(-1, 7); e = np.ascontiguousarray(est, np.float64).reshape(-1, 8)
+    assert len(u) == len(e)
+    o = np.zeros_like(e)
+    if lib().plp_model_sim3_exp_host(_p(u), _p(e), int(bool(fix_scale)), len(u), _p(o)) != len(u):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_sim3_exp_host")
+    return o
+
+
+def model_chol7(H, b, lam):
+    """Host build of the 7 x 7 solve of D16 (no GPU needed): (H + lambda I) x = b for n systems; H (n, 28) upper triangle row-major, b (n, 7), lam (n,).
+    Returns (x (n, 7), ok (n,) bool); x is zero where a pivot was not positive and finite."""
+    H = np.ascontiguousarray(H, np.float64).reshape(-1, 28); b = np.ascontiguousarray(b, np.float64).reshape(-1, 7)
+    lam = np.ascontiguousarray(lam, np.float64).reshape(-1)
+    assert len(H) == len(b) == len(lam)
+    x = np.zeros_like(b); ok = np.zeros(len(H), np.int32)
+    if lib().plp_model_chol7_host(_p(H), _p(b), _p(lam), len(H), _p(x), _p(ok)) != len(H):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_chol7_host")
+    return x, ok.astype(bool)
+
+
+def model_pose_exp(x):
+    """Host build of D16's exp (csrc/transform_opt.hpp pose_exp; no GPU needed): f64, NaN outside [-700, 700]"""
+    x = np.ascontiguousarray(x, np.float64)
+    o = np.zeros(x.shape)
+    if lib().plp_model_pose_exp_host(_p(x), x.size, _p(o)) != x.size:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_exp_host")
+    return o
+
+
+class transform_optimizer:
+    """Mirror of optimize::transform_optimizer (optimize/transform_optimizer.h): optimize() takes one pair's arrays and returns (num_inliers, result
+    dict of that pair); mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, fix_scale, num_iter=10, mt=None):
+        self.fix_scale, self.num_iter, self._mt = bool(fix_scale), int(num_iter), mt
+
+    def optimize(self, camera, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12, inv_level_sigma_sq_1,
+                 inv_level_sigma_sq_2, chi_sq=10.0):
+        """valid (n,): the slots that pass the four `continue`s of :95-118; pos_w_1 / pos_w_2 (n, 3), undist_1 / undist_2 (n,) KP_DTYPE, pose_1 / pose_2 15-double
+        pose rows, (rot_12 3 x 3, trans_12, scale_12) the g2o::Sim3 to refine.  Returns (the reference's return value, dict(status, num_valid, rot_12 (9,),
+        trans_12, scale_12, world_to_1 (13,), kept (n,): matched_lms_in_keyfrm_2 still set, round_info, round_chi2))."""
+        n = len(np.asarray(valid).reshape(-1))
+        fn = model_transform_optimize if self._mt is None else self._mt.transform_optimize
+        r = fn(camera, self.fix_scale, np.asarray(valid).reshape(1, n), pos_w_1, pos_w_2, undist_1, undist_2, np.asarray(pose_1, np.float64).reshape(1, 15),
+               np.asarray(pose_2, np.float64).reshape(1, 15), np.asarray(rot_12, np.float64).reshape(1, 9), np.asarray(trans_12, np.float64).reshape(1, 3),
+               np.asarray(scale_12, np.float32).reshape(1), inv_level_sigma_sq_1, inv_level_sigma_sq_2, num_iter=self.num_iter, chi_sq=chi_sq)
+        o = {k: v[0] for k, v in r.items()}
+        return int(o["num_inliers"]), o
+
+
 class orb_extractor:
     """Mirror of feature::orb_extractor (src/PLPSLAM/feature/orb_extractor.h:38-176) over the C ABI."""
 
@@ -1339,6 +1483,15 @@ class pose_optimize_args_c(C.Structure):
                 ("undist", _VP), ("x_right", _VP), ("pos_w", _VP), ("line_valid", _VP), ("keylines", _VP), ("pos_w_lines", _VP), ("out_status", _VP),
                 ("out_pose", _VP), ("out_num_init_obs", _VP), ("out_num_valid", _VP), ("out_outlier", _VP), ("out_outlier_lines", _VP),
                 ("out_trial_info", _VP), ("out_trial_chi2", _VP)]
+
+
+class transform_optimize_args_c(C.Structure):
+    """plp_transform_optimize_args"""
+    _fields_ = [("camera", camera_model_c), ("fix_scale", C.c_int32), ("num_iter", C.c_int32), ("chi_sq", C.c_float), ("P", C.c_int32), ("n_cap", C.c_int32),
+                ("inv_level_sigma_sq_1", _VP), ("inv_level_sigma_sq_2", _VP), ("num_levels", C.c_int32), ("counts", _VP), ("valid", _VP), ("pos_w_1", _VP),
+                ("pos_w_2", _VP), ("undist_1", _VP), ("undist_2", _VP), ("pose_1", _VP), ("pose_2", _VP), ("rot_12", _VP), ("trans_12", _VP), ("scale_12", _VP),
+                ("out_status", _VP), ("out_num_valid", _VP), ("out_num_inliers", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
+                ("out_world_to_1", _VP), ("out_kept", _VP), ("out_round_info", _VP), ("out_round_chi2", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -2251,6 +2404,41 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_pose_optimize_device(self._h, C.byref(a), st))
+
+    def transform_optimize(self, camera, fix_scale, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12,
+                           inv_level_sigma_sq_1, inv_level_sigma_sq_2, counts=None, num_iter=10, chi_sq=10.0, outputs=None, out=None):
+        """optimize::transform_optimizer::optimize for P pairs (plp_transform_optimize_host): camera a camera_model, valid (P, n_cap) u8, pos_w_1 / pos_w_2
+        (P, n_cap, 3), undist_1 / undist_2 (P, n_cap) KP_DTYPE, pose_1 / pose_2 (P, 15) pose rows, rot_12 (P, 9), trans_12 (P, 3), scale_12 (P,) f32, the two
+        sigma tables (num_levels,) f32, counts (P,) or None.  Returns dict(status (P,) u8: TRANSFORM_OPT_*, num_valid, num_inliers, rot_12, trans_12,
+        scale_12 (P,) f64, world_to_1 (P, 13), kept (P, n_cap) u8, round_info (P, 2, 4), round_chi2 (P, 2, 2)); `outputs` names the optional ones wanted
+        (default all); out[name]: the caller's array (slots the reference does not write keep their values)."""
+        call = lambda a: _check(lib().plp_transform_optimize_host(self._h, C.byref(a)))
+        inputs = dict(camera=camera, fix_scale=fix_scale, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1,
+                      pose_2=pose_2, rot_12=rot_12, trans_12=trans_12, scale_12=scale_12, inv_level_sigma_sq_1=inv_level_sigma_sq_1,
+                      inv_level_sigma_sq_2=inv_level_sigma_sq_2, counts=counts, num_iter=num_iter, chi_sq=chi_sq)
+        return _transform_optimize_host(call, inputs, outputs, out)
+
+    def transform_optimize_device(self, camera, fix_scale, P, n_cap, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12,
+                                  inv_level_sigma_sq_1, inv_level_sigma_sq_2, out, counts=None, num_iter=10, chi_sq=10.0, stream=None):
+        """plp_transform_optimize_device: every array a device pointer (int) or a torch tensor on the matcher's device (the two sigma tables are host
+        vectors); out: dict of the device outputs named as in TRANSFORM_OPT_OUTPUTS (world_to_1 / round_info / round_chi2 may be absent); asynchronous,
+        three kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        s1 = np.ascontiguousarray(inv_level_sigma_sq_1, np.float32).reshape(-1)         # live until the call has returned
+        s2 = np.ascontiguousarray(inv_level_sigma_sq_2, np.float32).reshape(-1)
+        if len(s1) != len(s2):
+            raise PlpError(PLP_ERR_INVALID_ARG, "the two sigma tables must have one length")
+        a = _struct(transform_optimize_args_c, dict(fix_scale=int(bool(fix_scale)), num_iter=int(num_iter), chi_sq=float(chi_sq), P=int(P), n_cap=int(n_cap),
+                                                    num_levels=len(s1)), dict(
+            inv_level_sigma_sq_1=s1.ctypes.data if len(s1) else None, inv_level_sigma_sq_2=s2.ctypes.data if len(s2) else None, counts=D(counts), valid=D(valid),
+            pos_w_1=D(pos_w_1), pos_w_2=D(pos_w_2), undist_1=D(undist_1), undist_2=D(undist_2), pose_1=D(pose_1), pose_2=D(pose_2), rot_12=D(rot_12),
+            trans_12=D(trans_12), scale_12=D(scale_12)))
+        for k in TRANSFORM_OPT_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_transform_optimize_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):
