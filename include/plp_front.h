@@ -1604,6 +1604,111 @@ int32_t plp_model_sim3_exp_host(const double* update, const double* est, int32_t
 int32_t plp_model_chol7_host(const double* H, const double* b, const double* lambda, int32_t n, double* out_x, int32_t* out_ok);
 int32_t plp_model_pose_exp_host(const double* x, int32_t n, double* out);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Local bundle adjustment: optimize::local_bundle_adjuster::optimize (src/PLPSLAM/optimize/local_bundle_adjuster.cc:62-410) for G problems
+ * at once over shared map tables -- what mapping_module runs for every new key frame (mapping_module.cc:251-261).  From the tables to the
+ * optimised poses, positions and outlier observations without the host.  Numeric contract: DESIGN.md section 5, D17 (the sets, the orders,
+ * the binary edge's two Jacobian blocks, the ordered sums, the Schur complement, the Cholesky of the reduced system, the two rounds) on top
+ * of D15; g2o is not linked.  force_stop_flag is not modelled (NULL); covisibility selection is the caller's (kf_local).
+ *
+ * Key-frame table, F rows:
+ *   pose          rot_cw row-major (9), trans_cw (3) per row; pose_stride doubles between rows
+ *   kf_erased     keyframe::will_be_erased()                                                            :85, :139, :250
+ *   kf_is_origin  id_ == 0: a local key frame that is held constant                                     :198
+ *   undist        undist_keypts_ (pt and octave are read), kp_stride slots per row; x_right: stereo_x_right_, NULL = all monocular (-1)
+ *   counts        key points per key frame, NULL = kp_stride
+ * Landmark table, L rows, with the observation lists in the layout of plp_landmark_geometry_args:
+ *   pos_w, lm_erased (will_be_erased(), :107), obs_offsets (L + 1), obs_kf, obs_idx (T = obs_offsets[L] entries)
+ * Per problem: kf_local [G][F], the current key frame and the covisibilities the caller chose (:73-91).
+ * Sets (:72-158): a key frame is local iff kf_local and not erased; a landmark is local iff not erased and a local key frame is among its
+ * observations; a key frame is fixed iff it is not local, not erased and observes a local landmark.  One edge per observation of a local
+ * landmark by a key frame that is not erased; an observation whose obs_kf is outside [0, F), whose obs_idx is outside [0, counts[kf]) or
+ * whose octave is outside [0, num_levels) is not an edge (where the reference follows a null pointer or .at() throws).  Order: key frames
+ * and landmarks in table order, edges in landmark order, then list order (a declared deviation: the reference's orders come from
+ * unordered_map iteration).
+ * Outputs per problem; slots that are not written keep the caller's values:
+ *   out_status      a plp_local_ba_status
+ *   out_kf_role     [G][F] a plp_local_ba_kf_role; out_lm_role [G][L]: 1 = local
+ *   out_pose        [G][F][15]: set_cam_pose's result as plp_pose_optimize_args.out_pose, for PLP_LOCAL_BA_KF_FREE rows only
+ *   out_pos_w       [G][L][3]: local landmarks only
+ *   out_outlier     [G][T]: step [7]'s verdict (:345-369), one byte per observation entry, edges only
+ *   out_round_info  optional, [G][2][4] per round: iterations run, rejected steps, edges moved to level 1 (round 1 only), why optimize()
+ *                   ended (1 all iterations, 2 the ten tries were used up, 3 rho == 0; 0 = the round had no level-0 edge)
+ *   out_round_chi2  optional, [G][2][2]: the robust chi2 of the kept estimate and lambda at the round's end */
+typedef enum plp_local_ba_status {
+    PLP_LOCAL_BA_OK = 0,
+    PLP_LOCAL_BA_NO_EDGES = 1,        /* nothing to optimise: out_pose is the input's (with its cam_center), out_pos_w the input's            */
+    PLP_LOCAL_BA_TOO_MANY_FREE = 2    /* _device only: more than 64 free key frames; nothing but out_status is written for the problem       */
+} plp_local_ba_status;
+typedef enum plp_local_ba_kf_role {
+    PLP_LOCAL_BA_KF_NONE = 0,
+    PLP_LOCAL_BA_KF_FREE = 1,         /* local and optimised                                                                                 */
+    PLP_LOCAL_BA_KF_ORIGIN = 2,       /* local with kf_is_origin: a constant vertex                                                          */
+    PLP_LOCAL_BA_KF_FIXED = 3         /* observes a local landmark: a constant vertex                                                        */
+} plp_local_ba_kf_role;
+typedef struct plp_local_ba_args {
+    plp_camera_model camera;            /* model, fx, fy, cx, cy, focal_x_baseline are read */
+    int32_t setup_type;                 /* camera::setup_type_t: 0 monocular, 1 stereo, 2 RGB-D: the Huber delta (:259-261) */
+    int32_t num_first_iter, num_second_iter;   /* >= 1; 5 and 10 by the constructor's defaults */
+    int32_t G, F, L, T;                 /* G >= 0 problems; F <= 1024 key frames; L, T <= 2^18; G <= 256, G * T and G * L <= 2^22 */
+    int32_t kp_stride, pose_stride;     /* slots between two rows of undist / x_right; doubles between two pose rows, >= 12 */
+    const float* inv_level_sigma_sq;    /* HOST, num_levels */
+    int32_t num_levels;                 /* 1 .. 16 */
+    const double* pose;                 /* F rows */
+    const uint8_t* kf_erased;           /* F, or NULL = none */
+    const uint8_t* kf_is_origin;        /* F, or NULL = none */
+    const plp_keypoint* undist;         /* F x kp_stride */
+    const float* x_right;               /* F x kp_stride, or NULL */
+    const int32_t* counts;              /* F, or NULL */
+    const double* pos_w;                /* L x 3 */
+    const uint8_t* lm_erased;           /* L, or NULL = none */
+    const int32_t* obs_offsets;         /* L + 1 */
+    const int32_t* obs_kf;              /* T */
+    const int32_t* obs_idx;             /* T */
+    const uint8_t* kf_local;            /* G x F */
+    uint8_t* out_status;                /* G */
+    uint8_t* out_kf_role;               /* G x F */
+    uint8_t* out_lm_role;               /* G x L */
+    double* out_pose;                   /* G x F x 15 */
+    double* out_pos_w;                  /* G x L x 3 */
+    uint8_t* out_outlier;               /* G x T */
+    int32_t* out_round_info;            /* G x 2 x 4, or NULL */
+    double* out_round_chi2;             /* G x 2 x 2, or NULL */
+} plp_local_ba_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; an unknown camera model or setup_type; fx or fy 0 or a
+ * non-finite fx, fy, cx, cy; G, F, L, T or kp_stride negative; an iteration count < 1; pose_stride < 12; num_levels outside 1 .. 16 or a
+ * NULL sigma table; and -- when G > 0 -- a NULL kf_local (F > 0), pose, undist (F > 0 and kp_stride > 0), pos_w (L > 0), obs_offsets,
+ * obs_kf, obs_idx (T > 0) or a NULL required output of non-zero size.  The equirectangular camera, F > 1024, L or T > 2^18, G > 256,
+ * G * T or G * L > 2^22: PLP_ERR_UNSUPPORTED (the context holds G (78 T + 25 L + 14 F + 384^2) doubles of state between the kernels).  G == 0: PLP_OK, nothing written.  _host and the host builds also check that obs_offsets rises from 0 to
+ * T (PLP_ERR_INVALID_ARG) and that no problem has more than 64 free key frames (PLP_ERR_UNSUPPORTED), before anything is written; on the
+ * _device path the first is a precondition (the kernels cut every run to the list) and the second a per-problem status.
+ * _device: every array but the sigma table a DEVICE pointer; three kernels on hip_stream (the sets and edges; both rounds; the outputs), one
+ * workgroup per problem, no host synchronisation.  The kernels hand their state on through buffers the context owns, so the calls of one
+ * context must be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (the outputs too, so that
+ * every slot the kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_local_ba_device(plp_matcher* ctx, const plp_local_ba_args* args, void* hip_stream);
+plp_status plp_local_ba_host(plp_matcher* ctx, const plp_local_ba_args* args);
+/* Host builds of the same source (csrc/local_ba.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_local_ba_host: the entry above with a team of one lane; the same checks.  Returns G, or the negated plp_status of a refused call.
+ * plp_model_local_ba_linearize_host: one linearisation of problem 0 (G must be 1) at the inputs' estimates with every edge at level 0, Huber
+ * kernels on (robust != 0) or off; the output pointers of `args` are neither read nor checked.  out_free_kf [64]: the table rows of the
+ * active free key frames in order (-1 behind them); out_hpp [64][27]: every active pose's H upper triangle row-major (21) and b (6);
+ * out_hll [L][9]: every active landmark's H (00 01 02 11 12 22) and b (3); out_w [T][18]: H_pl of every edge with an active free pose, 6 x 3
+ * row-major; out_chi2 [1]: the robust chi2; out_edge_chi2 [T]: the chi2 of every edge.  Slots without a value keep the caller's.  Any of
+ * them may be NULL.  Returns the number of active free poses, or the negated status.
+ * plp_model_local_ba_solve_host: one damped Schur solve from given blocks: P <= 64 poses (hpp P x 27 as above), M landmarks (hll M x 9),
+ * E edges in landmark order with e_pose (0 .. P - 1, or -1 for a constant pose), e_lm (non-decreasing, 0 .. M - 1) and w (E x 18).  A pose
+ * or a landmark without an edge is not in the system (its x is 0).  out_xp P x 6, out_xl M x 3; returns 1 = solved, 0 = a pivot or a
+ * 3 x 3 inverse failed (every x is then 0), -1 = a bad argument.
+ * plp_model_inv3_host: the closed cofactor inverse of n symmetric 3 x 3 matrices (n x 6: 00 01 02 11 12 22), out n x 6, out_ok n
+ * (0 = a coefficient of the inverse is not finite).  Returns n, or -1. */
+int32_t plp_model_local_ba_host(const plp_local_ba_args* args);
+int32_t plp_model_local_ba_linearize_host(const plp_local_ba_args* args, int32_t robust, int32_t* out_free_kf, double* out_hpp, double* out_hll,
+                                          double* out_w, double* out_chi2, double* out_edge_chi2);
+int32_t plp_model_local_ba_solve_host(int32_t P, int32_t M, int32_t E, const double* hpp, const double* hll, const int32_t* e_pose,
+                                      const int32_t* e_lm, const double* w, double lambda, double* out_xp, double* out_xl);
+int32_t plp_model_inv3_host(const double* a, int32_t n, double* out, int32_t* out_ok);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

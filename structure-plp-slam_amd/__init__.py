@@ -174,6 +174,12 @@ _API = [
     ("plp_model_sim3_exp_host", _I32, [_VP, _VP, _I32, _I32, _VP]),
     ("plp_model_chol7_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
     ("plp_model_pose_exp_host", _I32, [_VP, _I32, _VP]),
+    ("plp_local_ba_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_local_ba_host", C.c_int, [_VP, _VP]),
+    ("plp_model_local_ba_host", _I32, [_VP]),
+    ("plp_model_local_ba_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_model_local_ba_solve_host", _I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, C.c_double, _VP, _VP]),
+    ("plp_model_inv3_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
@@ -922,6 +928,147 @@ class transform_optimizer:
         return int(o["num_inliers"]), o
 
 
+# plp_local_ba_status / plp_local_ba_kf_role
+LOCAL_BA_OK, LOCAL_BA_NO_EDGES, LOCAL_BA_TOO_MANY_FREE = range(3)
+LOCAL_BA_KF_NONE, LOCAL_BA_KF_FREE, LOCAL_BA_KF_ORIGIN, LOCAL_BA_KF_FIXED = range(4)
+LOCAL_BA_MAX_FREE = 64
+# the outputs of plp_local_ba_*: name -> (shape per problem given (F, L, T), dtype, optional); round_info[..., 3] is a POSE_OPT_END_* (0: round not run)
+LOCAL_BA_OUTPUTS = dict(status=(lambda F, L, T: (), np.uint8, False), kf_role=(lambda F, L, T: (F,), np.uint8, False), lm_role=(lambda F, L, T: (L,), np.uint8, False),
+                        pose=(lambda F, L, T: (F, 15), np.float64, False), pos_w=(lambda F, L, T: (L, 3), np.float64, False),
+                        outlier=(lambda F, L, T: (T,), np.uint8, False), round_info=(lambda F, L, T: (2, 4), np.int32, True),
+                        round_chi2=(lambda F, L, T: (2, 2), np.float64, True))
+
+
+def _local_ba_inputs(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts, kf_erased, kf_is_origin,
+                     lm_erased, num_first_iter, num_second_iter):
+    """the input half of a plp_local_ba_args from numpy arrays: (args struct, the arrays it points to, G, F, L, T).  pose (F, pose_stride >= 12); undist / x_right
+    (F, kp_stride): the row widths are the strides of the struct."""
+    po = np.ascontiguousarray(pose, np.float64)
+    if po.ndim != 2 or po.shape[1] < 12:
+        raise PlpError(PLP_ERR_INVALID_ARG, "pose must be (F, pose_stride >= 12)")
+    F = po.shape[0]
+    ku = np.ascontiguousarray(undist, KP_DTYPE)
+    ku = ku.reshape(F, -1) if F else ku.reshape(0, 0)
+    K = ku.shape[1]
+    xr = None if x_right is None else np.ascontiguousarray(x_right, np.float32).reshape(F, K)
+    pw = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3)
+    L = len(pw)
+    oo = np.ascontiguousarray(obs_offsets, np.int32).reshape(-1); ok = np.ascontiguousarray(obs_kf, np.int32).reshape(-1); oi = np.ascontiguousarray(obs_idx, np.int32).reshape(-1)
+    if len(oo) != L + 1 or len(ok) != len(oi):
+        raise PlpError(PLP_ERR_INVALID_ARG, "obs_offsets must have L + 1 entries, obs_kf and obs_idx one length")
+    T = len(ok)
+    kl = np.ascontiguousarray(kf_local, np.uint8).reshape(-1, F) if F else np.zeros((np.asarray(kf_local).shape[0], 0), np.uint8)
+    G = kl.shape[0]
+    u8 = lambda v, n: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(n)
+    ke, ko, le = u8(kf_erased, F), u8(kf_is_origin, F), u8(lm_erased, L)
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
+    sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(local_ba_args_c, dict(setup_type=int(setup_type), num_first_iter=int(num_first_iter), num_second_iter=int(num_second_iter), G=G, F=F, L=L, T=T,
+                                      kp_stride=int(K), pose_stride=po.shape[1], num_levels=len(sg)), dict(
+        inv_level_sigma_sq=Pt(sg), pose=Pt(po), kf_erased=Pt(ke), kf_is_origin=Pt(ko), undist=Pt(ku), x_right=Pt(xr), counts=Pt(cn), pos_w=Pt(pw), lm_erased=Pt(le),
+        obs_offsets=Pt(oo), obs_kf=Pt(ok), obs_idx=Pt(oi), kf_local=Pt(kl)))
+    a.camera = camera_model_c.from_buffer_copy(camera)
+    return a, (po, ku, xr, pw, oo, ok, oi, kl, ke, ko, le, cn, sg), G, F, L, T
+
+
+def _local_ba_host(call, inputs, outputs, out):
+    """the numpy side of plp_local_ba_host and plp_model_local_ba_host: call(args struct) runs the entry"""
+    a, keep, G, F, L, T = _local_ba_inputs(**inputs)
+    o = {}
+    for k, (shape, dt, optional) in LOCAL_BA_OUTPUTS.items():     # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (G,) + shape(F, L, T)
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    for k in LOCAL_BA_OUTPUTS:
+        setattr(a, "out_" + k, Pt(o.get(k)))
+    call(a)
+    return o
+
+
+def _local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts, kf_erased, kf_is_origin,
+                 lm_erased, num_first_iter, num_second_iter):
+    return dict(camera=camera, setup_type=setup_type, pose=pose, undist=undist, pos_w=pos_w, obs_offsets=obs_offsets, obs_kf=obs_kf, obs_idx=obs_idx,
+                kf_local=kf_local, inv_level_sigma_sq=inv_level_sigma_sq, x_right=x_right, counts=counts, kf_erased=kf_erased, kf_is_origin=kf_is_origin,
+                lm_erased=lm_erased, num_first_iter=num_first_iter, num_second_iter=num_second_iter)
+
+
+def model_local_ba(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
+                   kf_erased=None, kf_is_origin=None, lm_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
+    """Host build of optimize::local_bundle_adjuster::optimize (csrc/local_ba.hpp, DESIGN.md section 5, D17; no GPU needed): the arguments and the
+    result of matcher.local_ba."""
+    def call(a):
+        r = lib().plp_model_local_ba_host(C.byref(a))
+        if r != a.G:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _local_ba_host(call, _local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts,
+                                             kf_erased, kf_is_origin, lm_erased, num_first_iter, num_second_iter), outputs, out)
+
+
+def model_local_ba_linearize(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
+                             kf_erased=None, kf_is_origin=None, lm_erased=None, robust=True):
+    """Host build of one linearisation of D17 at the inputs' estimates, every edge at level 0 (no GPU needed); kf_local (F,) or (1, F).  Returns
+    dict(free_kf (P,) table rows of the active free key frames, Hpp (P, 21) upper triangle row-major, bp (P, 6), Hll (L, 6) (00 01 02 11 12 22) and bl (L, 3),
+    NaN for a landmark without an edge, W (T, 6, 3) NaN where the edge has no active free pose, chi2 the robust sum, edge_chi2 (T,) NaN where no edge)."""
+    a, keep, G, F, L, T = _local_ba_inputs(**_local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq,
+                                                          x_right, counts, kf_erased, kf_is_origin, lm_erased, 1, 1))
+    fk = np.full(LOCAL_BA_MAX_FREE, -1, np.int32); hpp = np.full((LOCAL_BA_MAX_FREE, 27), np.nan); hll = np.full((L, 9), np.nan); w = np.full((T, 18), np.nan)
+    chi = np.zeros(1); ec = np.full(T, np.nan)
+    Pt = lambda v: None if v.size == 0 else v.ctypes.data
+    r = lib().plp_model_local_ba_linearize_host(C.byref(a), int(bool(robust)), Pt(fk), Pt(hpp), Pt(hll), Pt(w), Pt(chi), Pt(ec))
+    if r < 0:
+        raise PlpError(-r, lib().plp_last_error().decode())
+    return dict(free_kf=fk[:r].copy(), Hpp=hpp[:r, :21].copy(), bp=hpp[:r, 21:].copy(), Hll=hll[:, :6].copy(), bl=hll[:, 6:].copy(), W=w.reshape(T, 6, 3),
+                chi2=float(chi[0]), edge_chi2=ec)
+
+
+def model_local_ba_solve(Hpp, bp, Hll, bl, e_pose, e_lm, W, lam):
+    """Host build of one damped Schur solve of D17 (no GPU needed): Hpp (P, 21), bp (P, 6), Hll (M, 6), bl (M, 3), edges in landmark order with e_pose (E,)
+    (-1: a constant pose), e_lm (E,) and W (E, 6, 3).  Returns (x_p (P, 6), x_l (M, 3), ok)."""
+    hp = np.concatenate([np.asarray(Hpp, np.float64).reshape(-1, 21), np.asarray(bp, np.float64).reshape(-1, 6)], axis=1).copy()
+    hl = np.concatenate([np.asarray(Hll, np.float64).reshape(-1, 6), np.asarray(bl, np.float64).reshape(-1, 3)], axis=1).copy()
+    ep = np.ascontiguousarray(e_pose, np.int32).reshape(-1); el = np.ascontiguousarray(e_lm, np.int32).reshape(-1)
+    w = np.ascontiguousarray(W, np.float64).reshape(len(ep), 18)
+    xp = np.zeros((len(hp), 6)); xl = np.zeros((len(hl), 3))
+    Pt = lambda v: None if v.size == 0 else v.ctypes.data
+    r = lib().plp_model_local_ba_solve_host(len(hp), len(hl), len(ep), Pt(hp), Pt(hl), Pt(ep), Pt(el), Pt(w), float(lam), Pt(xp), Pt(xl))
+    if r < 0:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_local_ba_solve_host")
+    return xp, xl, bool(r)
+
+
+def model_inv3(a):
+    """Host build of D17's closed 3 x 3 inverse (no GPU needed): a (n, 6) symmetric (00 01 02 11 12 22).  Returns (inverse (n, 6), ok (n,) bool)."""
+    a = np.ascontiguousarray(a, np.float64).reshape(-1, 6)
+    o = np.zeros_like(a); ok = np.zeros(len(a), np.int32)
+    if lib().plp_model_inv3_host(_p(a), len(a), _p(o), _p(ok)) != len(a):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_inv3_host")
+    return o, ok.astype(bool)
+
+
+class local_bundle_adjuster:
+    """Mirror of optimize::local_bundle_adjuster (optimize/local_bundle_adjuster.h): optimize() takes the map tables and one problem's kf_local and
+    returns that problem's result dict; mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, num_first_iter=5, num_second_iter=10, mt=None):
+        self.num_first_iter, self.num_second_iter, self._mt = int(num_first_iter), int(num_second_iter), mt
+
+    def optimize(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
+                 kf_erased=None, kf_is_origin=None, lm_erased=None):
+        """kf_local (F,): the current key frame and its covisibilities (:73-91).  Returns dict(status, kf_role (F,), lm_role (L,), pose (F, 15), pos_w (L, 3),
+        outlier (T,), round_info, round_chi2); rows the adjuster does not write are zero."""
+        fn = model_local_ba if self._mt is None else self._mt.local_ba
+        r = fn(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, np.asarray(kf_local, np.uint8).reshape(1, -1), inv_level_sigma_sq,
+               x_right=x_right, counts=counts, kf_erased=kf_erased, kf_is_origin=kf_is_origin, lm_erased=lm_erased, num_first_iter=self.num_first_iter,
+               num_second_iter=self.num_second_iter)
+        return {k: v[0] for k, v in r.items()}
+
+
 class orb_extractor:
     """Mirror of feature::orb_extractor (src/PLPSLAM/feature/orb_extractor.h:38-176) over the C ABI."""
 
@@ -1492,6 +1639,16 @@ class transform_optimize_args_c(C.Structure):
                 ("pos_w_2", _VP), ("undist_1", _VP), ("undist_2", _VP), ("pose_1", _VP), ("pose_2", _VP), ("rot_12", _VP), ("trans_12", _VP), ("scale_12", _VP),
                 ("out_status", _VP), ("out_num_valid", _VP), ("out_num_inliers", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
                 ("out_world_to_1", _VP), ("out_kept", _VP), ("out_round_info", _VP), ("out_round_chi2", _VP)]
+
+
+class local_ba_args_c(C.Structure):
+    """plp_local_ba_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("num_first_iter", C.c_int32), ("num_second_iter", C.c_int32), ("G", C.c_int32),
+                ("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("kp_stride", C.c_int32), ("pose_stride", C.c_int32), ("inv_level_sigma_sq", _VP),
+                ("num_levels", C.c_int32), ("pose", _VP), ("kf_erased", _VP), ("kf_is_origin", _VP), ("undist", _VP), ("x_right", _VP), ("counts", _VP),
+                ("pos_w", _VP), ("lm_erased", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("obs_idx", _VP), ("kf_local", _VP), ("out_status", _VP),
+                ("out_kf_role", _VP), ("out_lm_role", _VP), ("out_pose", _VP), ("out_pos_w", _VP), ("out_outlier", _VP), ("out_round_info", _VP),
+                ("out_round_chi2", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -2439,6 +2596,37 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_transform_optimize_device(self._h, C.byref(a), st))
+
+    def local_ba(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
+                 kf_erased=None, kf_is_origin=None, lm_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
+        """optimize::local_bundle_adjuster::optimize for G problems over shared map tables (plp_local_ba_host; DESIGN.md section 5, D17): camera a
+        camera_model, pose (F, >= 12), undist (F, kp_stride) KP_DTYPE, x_right (F, kp_stride) f32 or None, counts (F,) or None, pos_w (L, 3), the
+        observation lists obs_offsets (L + 1,), obs_kf / obs_idx (T,), kf_local (G, F) u8, the sigma table (num_levels,) f32, kf_erased / kf_is_origin (F,)
+        and lm_erased (L,) u8 or None.  Returns dict(status (G,) u8: LOCAL_BA_*, kf_role (G, F), lm_role (G, L), pose (G, F, 15), pos_w (G, L, 3),
+        outlier (G, T), round_info (G, 2, 4), round_chi2 (G, 2, 2)); `outputs` names the optional ones wanted (default all); out[name]: the caller's
+        array (slots the adjuster does not write keep their values)."""
+        call = lambda a: _check(lib().plp_local_ba_host(self._h, C.byref(a)))
+        return _local_ba_host(call, _local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right,
+                                                 counts, kf_erased, kf_is_origin, lm_erased, num_first_iter, num_second_iter), outputs, out)
+
+    def local_ba_device(self, camera, setup_type, G, F, L, T, kp_stride, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, out,
+                        x_right=None, counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None, pose_stride=15, num_first_iter=5, num_second_iter=10,
+                        stream=None):
+        """plp_local_ba_device: every array a device pointer (int) or a torch tensor on the matcher's device (the sigma table is a host vector); out: dict
+        of the device outputs named as in LOCAL_BA_OUTPUTS (round_info / round_chi2 may be absent); asynchronous, three kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)             # live until the call has returned
+        a = _struct(local_ba_args_c, dict(setup_type=int(setup_type), num_first_iter=int(num_first_iter), num_second_iter=int(num_second_iter), G=int(G), F=int(F),
+                                          L=int(L), T=int(T), kp_stride=int(kp_stride), pose_stride=int(pose_stride), num_levels=len(sg)), dict(
+            inv_level_sigma_sq=sg.ctypes.data if len(sg) else None, pose=D(pose), kf_erased=D(kf_erased), kf_is_origin=D(kf_is_origin), undist=D(undist),
+            x_right=D(x_right), counts=D(counts), pos_w=D(pos_w), lm_erased=D(lm_erased), obs_offsets=D(obs_offsets), obs_kf=D(obs_kf), obs_idx=D(obs_idx),
+            kf_local=D(kf_local)))
+        for k in LOCAL_BA_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_local_ba_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):
