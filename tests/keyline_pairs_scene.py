@@ -95,8 +95,11 @@ def nn_brute(q, t):
     return idx, dist
 
 
-def make_scene(seed, setup_type, F=12, n_seg=44, n_long=4, perturb=0.3, extra_horizontal=False, few_keypoints=True, occupied_rate=0.08):
-    """-> dict(cam, kfs: the restatement's key-frame dicts, seg: per key frame the segment of every slot, segments, lbd: per key frame (n, 32))"""
+def make_scene(seed, setup_type, F=12, n_seg=44, n_long=4, perturb=0.3, extra_horizontal=False, few_keypoints=True, occupied_rate=0.08, cap=CAP,
+               counts=None, n_keypoints=None):
+    """-> dict(cam, kfs: the restatement's key-frame dicts, seg: per key frame the segment of every slot, segments, lbd: per key frame (n, 32)).
+    cap: the slots of the table the scene is made for; counts: per key frame the largest number of key lines (None: cap); n_keypoints: a
+    dict key frame -> the number of its key points (the others: 40 more than key lines)."""
     rng = np.random.default_rng(seed)
     segs = _segments(rng, n_seg, n_long)
     if extra_horizontal:                                        # exactly horizontal in key frame 0: reprojected l1 == 0 (NON_FINITE)
@@ -138,7 +141,7 @@ def make_scene(seed, setup_type, F=12, n_seg=44, n_long=4, perturb=0.3, extra_ho
                     for bit in flips:
                         code[bit // 8] ^= np.uint8(1 << (bit % 8))
                     rows.append((i, ends[0], ends[1], ends[2], ends[3], za, zb, code))
-        order = rng.permutation(len(rows))[:CAP]
+        order = rng.permutation(len(rows))[:cap if counts is None else min(int(counts[k]), cap)]
         rows = [rows[o] for o in order]
         n = len(rows)
         octs = rng.integers(0, 3, n)
@@ -171,6 +174,8 @@ def make_scene(seed, setup_type, F=12, n_seg=44, n_long=4, perturb=0.3, extra_ho
         n_kp = n + 40
         if few_keypoints and k == 4:
             n_kp = max(n - 9, 0)                                # fewer key points than key lines: depths_.at(idx) throws for the last slots
+        if n_keypoints is not None and k in n_keypoints:
+            n_kp = int(n_keypoints[k])
         kp_depths = rng.uniform(2.0, 10.0, n_kp).astype(np.float32)
         if k % 3 == 0 and n_kp > 6:
             kp_depths[3:6] = kp_depths[2]                       # equal depths: both stereo cosines from bit-identical inputs
@@ -205,15 +210,15 @@ def match_all(scene, groups):
     return [[nn_brute(scene["lbd"][kf1], scene["lbd"][kf2]) for kf2 in ngh] for kf1, ngh in groups]
 
 
-def run_ref(scene, groups, matches, gates, gaps=None, info=None, occupied=None):
-    """the restatement over every group -> (match, pos_w, status) in the (P, CAP) layout with the sentinels in the slots it does not write,
-    occupied_cur (G, CAP); info: per pair the restatement's notes"""
+def run_ref(scene, groups, matches, gates, gaps=None, info=None, occupied=None, cap=CAP):
+    """the restatement over every group -> (match, pos_w, status) in the (P, cap) layout with the sentinels in the slots it does not write,
+    occupied_cur (G, cap); info: per pair the restatement's notes"""
     sf, ls = scale_tables()
     P = sum(len(n) for _, n in groups)
-    om = np.full((P, CAP), SENT_I32, np.int32)
-    op = np.full((P, CAP, 6), SENT_F64, np.float64)
-    os_ = np.full((P, CAP), SENT_U8, np.uint8)
-    oc = np.full((len(groups), CAP), SENT_U8, np.uint8)
+    om = np.full((P, cap), SENT_I32, np.int32)
+    op = np.full((P, cap, 6), SENT_F64, np.float64)
+    os_ = np.full((P, cap), SENT_U8, np.uint8)
+    oc = np.full((len(groups), cap), SENT_U8, np.uint8)
     kfs = scene["kfs"]
     if occupied is not None:
         kfs = [dict(kf, occupied=occupied[k][:len(kf["keylines"])]) for k, kf in enumerate(kfs)]
@@ -232,14 +237,14 @@ def run_ref(scene, groups, matches, gates, gaps=None, info=None, occupied=None):
     return om, op, os_, oc
 
 
-def table(scene, occupied=None):
-    """the key-frame table as the (F, CAP, ...) arrays of plp_keyline_pairs_args; slots past the counts hold values that must not be read"""
+def table(scene, occupied=None, cap=CAP):
+    """the key-frame table as the (F, cap, ...) arrays of plp_keyline_pairs_args; slots past the counts hold values that must not be read"""
     F, kfs = scene["F"], scene["kfs"]
     kp_cap = max(len(kf["kp_depths"]) for kf in kfs)
-    t = dict(keylines=np.zeros((F, CAP), plp.KL_DTYPE), counts=np.zeros(F, np.int32), line_functions=np.full((F, CAP, 3), np.nan),
-             kl_x_right=np.full((F, CAP, 2), 5.0, np.float32), kp_depths=np.full((F, kp_cap), np.nan, np.float32), kp_counts=np.zeros(F, np.int32),
-             pose=np.zeros((F, 15)), median_depth=np.zeros(F, np.float32), occupied=np.ones((F, CAP), np.uint8),
-             lines_3d=None if scene["setup_type"] == KP.MONOCULAR else np.full((F, CAP, 6), np.nan), lbd=np.zeros((F, CAP, 32), np.uint8))
+    t = dict(keylines=np.zeros((F, cap), plp.KL_DTYPE), counts=np.zeros(F, np.int32), line_functions=np.full((F, cap, 3), np.nan),
+             kl_x_right=np.full((F, cap, 2), 5.0, np.float32), kp_depths=np.full((F, kp_cap), np.nan, np.float32), kp_counts=np.zeros(F, np.int32),
+             pose=np.zeros((F, 15)), median_depth=np.zeros(F, np.float32), occupied=np.ones((F, cap), np.uint8),
+             lines_3d=None if scene["setup_type"] == KP.MONOCULAR else np.full((F, cap, 6), np.nan), lbd=np.zeros((F, cap, 32), np.uint8))
     t["keylines"]["startPointX"] = np.nan
     for k, kf in enumerate(kfs):
         n = len(kf["keylines"])
@@ -254,10 +259,10 @@ def table(scene, occupied=None):
     return t
 
 
-def flat_matches(groups, matches):
-    """(train_idx, dist) as (P, CAP) arrays; slots past cur's count hold an index that would be out of bounds if it were followed"""
+def flat_matches(groups, matches, cap=CAP):
+    """(train_idx, dist) as (P, cap) arrays; slots past cur's count hold an index that would be out of bounds if it were followed"""
     P = sum(len(n) for _, n in groups)
-    ti, di = np.full((P, CAP), 1 << 20, np.int32), np.zeros((P, CAP), np.int32)
+    ti, di = np.full((P, cap), 1 << 20, np.int32), np.zeros((P, cap), np.int32)
     p = 0
     for g, (_, ngh) in enumerate(groups):
         for k in range(len(ngh)):
@@ -286,3 +291,177 @@ def scene_case(name):
         ref = run_ref(scene, groups, matches, gates, gaps, info)
         _cache[name] = (scene, groups, matches, gates, ref, gaps, info)
     return _cache[name]
+
+
+# ------------------------------------------------------------------------------------------ above one workgroup of slots (256 query slots)
+# The scenes of tests/test_gpu_pair_kernels_wide.py; what they are named for is asserted on the restatement in tests/test_pair_kernels_wide_cpu.py.
+WIDE_CAP = 300                                                  # two trips of the resolve kernel's loops, the second with 44 slots
+LIMIT_CAP = 8192                                                # the largest capacity the entries accept: 40 960 B of dynamic LDS
+NO_GATES_CHECK = dict(KP.MAPPING_GATES, skip_occupied=0)        # the mapping thresholds without the duplicate check
+_SLOT_FIELDS = ("keylines", "line_functions", "kl_x_right", "kl_depths", "lines_3d", "occupied")
+
+
+def _reindex(scene, k, index):
+    """key frame k's key lines become the old ones at `index` (monocular scenes: nothing refers to a slot by its number)"""
+    assert scene["setup_type"] == KP.MONOCULAR
+    kf = scene["kfs"][k]
+    for f in _SLOT_FIELDS:
+        if kf[f] is not None:
+            kf[f] = kf[f][index].copy()
+    scene["lbd"][k] = scene["lbd"][k][index].copy()
+    scene["seg"][k] = [scene["seg"][k][i] for i in index]
+
+
+def copy_slot(scene, k, src, dst):
+    index = np.arange(len(scene["kfs"][k]["keylines"]))
+    index[dst] = src
+    _reindex(scene, k, index)
+
+
+def swap_slots(scene, k, a, b):
+    index = np.arange(len(scene["kfs"][k]["keylines"]))
+    index[[a, b]] = index[[b, a]]
+    _reindex(scene, k, index)
+
+
+def tile_key_frame(scene, k, count):
+    """repeat key frame k's key lines in turn until it has `count` of them"""
+    _reindex(scene, k, np.arange(count) % len(scene["kfs"][k]["keylines"]))
+
+
+def created_alone(scene, kf1, kf2, j, t, gates=KP.MAPPING_GATES, dist=7):
+    """does query slot j of kf1 with train index t of kf2 pass the three gates and become a landmark when nothing is occupied?"""
+    a, b = scene["kfs"][kf1], scene["kfs"][kf2]
+    if KP.gate(a["keylines"][j], b["keylines"][t], dist, gates["dist_thr"], gates["endpoint_thr"], gates["angle_thr"]) != KP.CREATED:
+        return False
+    sf, ls = scale_tables()
+    return KP.triangulate(scene["cam"], scene["setup_type"], TRUE_BASELINE, sf, ls, SCALE_FACTOR, KP.cos_parallax_thr(1.0), a, b, j, t)[0] == KP.CREATED
+
+
+def plant_shared_train(scene, cur, neighbours, query_slots, train_slots, dist=7):
+    """Key lines whose query slots share one train index: a segment that cur and every neighbour see, and that is triangulated into a landmark
+    with each of them, is put into every slot of query_slots of cur (copies of one key line) and into slot train_slots[k] of neighbours[k].
+    -> matches of the group (the brute-force 1-NN of the scene after the move; the planted queries name the planted train index with
+    distance `dist`, every other query that named it is left without a match)"""
+    segs = [scene["seg"][k] for k in neighbours]
+    for j, s in enumerate(scene["seg"][cur]):
+        if j in query_slots or not all(s in sg for sg in segs):
+            continue
+        ts = [sg.index(s) for sg in segs]
+        if any(t in train_slots for t in ts) or not all(created_alone(scene, cur, k, j, t, dist=dist) for k, t in zip(neighbours, ts)):
+            continue
+        for q in query_slots:
+            copy_slot(scene, cur, j, q)
+        for k, t, to in zip(neighbours, ts, train_slots):
+            swap_slots(scene, k, t, to)
+        break
+    else:
+        raise AssertionError("no segment of this scene is triangulated with every neighbour")
+    matches = []
+    for k, to in zip(neighbours, train_slots):
+        ti, di = nn_brute(scene["lbd"][cur], scene["lbd"][k])
+        ti[ti == to], di[ti == to] = -1, 256
+        ti[list(query_slots)], di[list(query_slots)] = to, dist
+        matches.append((ti, di))
+    return matches
+
+
+_wide = {}
+
+
+def wide_counts_case():
+    """L1: cur key frames with 255, 256, 257 and 300 key lines, neighbours with 70 and with 300, groups of three pairs (RGB-D)
+    -> (scene, groups, matches)"""
+    if "counts" not in _wide:
+        scene = make_scene(70, KP.RGBD, F=10, n_seg=640, n_long=4, cap=WIDE_CAP, counts=(255, 70, 256, 300, 257, 70, 300, 300, 300, 0))
+        assert [len(kf["keylines"]) for kf in scene["kfs"]] == [255, 70, 256, 300, 257, 70, 300, 300, 300, 0]
+        groups = [(0, [1, 3, 6]), (2, [3, 5, 7]), (4, [5, 6, 1]), (6, [7, 1, 3])]
+        _wide["counts"] = (scene, groups, match_all(scene, groups))
+    return _wide["counts"]
+
+
+SHARED_QUERIES, SHARED_TRAIN = (10, 266, 290), (260, 280)        # three query slots on both sides of 256, the train index per neighbour
+SHARED_CASES = ("free", "cur occupied", "train occupied")
+
+
+def shared_train_case():
+    """L2: one group (0, [2, 4]) of full key frames (monocular, nothing occupied); query slots SHARED_QUERIES of key frame 0 are copies of one
+    key line whose partner is slot SHARED_TRAIN[k] of neighbour k -> (scene, groups, matches, occupancy per case of SHARED_CASES)"""
+    if "shared" not in _wide:
+        scene = make_scene(71, KP.MONOCULAR, F=7, n_seg=640, cap=WIDE_CAP, counts=(WIDE_CAP,) * 6 + (0,), occupied_rate=0.0)
+        groups = [(0, [2, 4])]
+        assert all(len(scene["kfs"][k]["keylines"]) == WIDE_CAP for k in (0, 2, 4))
+        matches = [plant_shared_train(scene, 0, groups[0][1], SHARED_QUERIES, SHARED_TRAIN)]
+        free = [np.zeros(len(kf["keylines"]), np.uint8) for kf in scene["kfs"]]
+        occ = {"free": free, "cur occupied": [o.copy() for o in free], "train occupied": [o.copy() for o in free]}
+        occ["cur occupied"][0][SHARED_QUERIES[0]] = 1
+        occ["train occupied"][2][SHARED_TRAIN[0]] = 1
+        _wide["shared"] = (scene, groups, matches, occ)
+    return _wide["shared"]
+
+
+KP_COUNT = 260
+
+
+def kp_depth_case():
+    """L3: stereo; key frame 0 has WIDE_CAP key lines and KP_COUNT key points, its neighbours have more key points than key lines
+    -> (scene, groups, matches)"""
+    if "kp" not in _wide:
+        scene = make_scene(72, KP.STEREO, F=7, n_seg=640, cap=WIDE_CAP, counts=(WIDE_CAP, 250, 250, 250, 250, 250, 0), few_keypoints=False,
+                           n_keypoints={0: KP_COUNT})
+        assert len(scene["kfs"][0]["keylines"]) == WIDE_CAP and len(scene["kfs"][0]["kp_depths"]) == KP_COUNT
+        groups = [(0, [2, 4, 1])]
+        _wide["kp"] = (scene, groups, match_all(scene, groups))
+    return _wide["kp"]
+
+
+def limit_case():
+    """L4: cap = LIMIT_CAP; a small monocular scene whose key frames 0 and 2 are repeated up to the capacity, one group (0, [2, 4]).  The
+    small scene's 1-NN for its own slots, no match (the distance gate) for the repeated ones; planted: query LIMIT_CAP - 1 (a copy of a
+    query that is created) and train index 8100 (a copy of the partner of another) -> (scene, groups, matches, planted)"""
+    if "limit" not in _wide:
+        scene = make_scene(73, KP.MONOCULAR, F=7, occupied_rate=0.0)
+        groups = [(0, [2, 4])]
+        base = match_all(scene, groups)[0]
+        nb = len(scene["kfs"][0]["keylines"])
+        made = [(j, int(base[0][0][j])) for j in range(nb) if base[0][0][j] >= 0 and created_alone(scene, 0, 2, j, int(base[0][0][j]), dist=base[0][1][j])]
+        made = [(j, t) for j, t in made if [tt for _, tt in made].count(t) == 1]
+        (j1, t1), (j2, t2) = made[0], made[1]
+        tile_key_frame(scene, 0, LIMIT_CAP)
+        tile_key_frame(scene, 2, LIMIT_CAP)
+        last, far = LIMIT_CAP - 1, 8100
+        copy_slot(scene, 0, j1, last)
+        copy_slot(scene, 2, t2, far)
+        matches = []
+        for ti, di in base:
+            a, b = np.full(LIMIT_CAP, -1, np.int32), np.full(LIMIT_CAP, 256, np.int32)
+            a[:nb], b[:nb] = ti, di
+            matches.append((a, b))
+        ti, di = matches[0]
+        ti[last], di[last] = t1, di[j1]
+        ti[j1], di[j1] = -1, 256                                # its copy at the last slot takes its place
+        ti[j2] = far
+        _wide["limit"] = (scene, groups, [matches], dict(created=[(0, last, t1), (0, j2, far)]))
+    return _wide["limit"]
+
+
+def wide_reference(case, gates_name="mapping", occupancy=None):
+    """the restatement on a wide case, once per process -> dict(ref = (match, pos_w, status, occupied_cur), gaps, info)"""
+    key = ("ref", case, gates_name, occupancy)
+    if key not in _wide:
+        gates = dict(mapping=KP.MAPPING_GATES, unchecked=NO_GATES_CHECK)[gates_name]
+        gaps, info = [], []
+        if case == "counts":
+            scene, groups, matches = wide_counts_case()
+            ref = run_ref(scene, groups, matches, gates, gaps, info, cap=WIDE_CAP)
+        elif case == "shared":
+            scene, groups, matches, occ = shared_train_case()
+            ref = run_ref(scene, groups, matches, gates, gaps, info, occupied=occ[occupancy], cap=WIDE_CAP)
+        elif case == "kp":
+            scene, groups, matches = kp_depth_case()
+            ref = run_ref(scene, groups, matches, gates, gaps, info, cap=WIDE_CAP)
+        else:
+            scene, groups, matches, _ = limit_case()
+            ref = run_ref(scene, groups, matches, gates, gaps, info, cap=LIMIT_CAP)
+        _wide[key] = dict(ref=ref, gaps=gaps, info=info)
+    return _wide[key]

@@ -1,7 +1,9 @@
 """GPU parity of the key-frame pair line triangulation (plp_median_depth_* / plp_triangulate_keyline_pairs_*) against the CPU restatement
 tests/keyline_pairs_ref.py: scenes with ground truth (tests/keyline_pairs_scene.py; that they reach every status
 and hold no near tie of the parallax comparisons is asserted without a GPU in tests/test_keyline_pairs_cpu.py), batched groups with
-sentinel-filled outputs, directed cases, chained calls, host entries against device entries, argument validation, the median depth."""
+sentinel-filled outputs, directed cases, chained calls, host entries against device entries, argument validation, the median depth.  The
+triangulation cases here run a capacity of 64 query slots, less than one workgroup (256) of the geometry kernel and one trip of the resolve
+kernel's loops; more than one, duplicates across trips and the capacity limit of 8192 are in tests/test_gpu_pair_kernels_wide.py."""
 import ctypes as C
 
 import numpy as np

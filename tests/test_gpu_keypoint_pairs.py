@@ -2,7 +2,9 @@
 restatement tests/keypoint_pairs_ref.py, bit for bit: scenes with ground truth for every setup and camera
 (tests/keypoint_pairs_scene.py; that they reach every status and keep a gap in every comparison the device decides with its own cos /
 atan2 / asin is asserted without a GPU in tests/test_keypoint_pairs_cpu.py), sentinel-filled outputs, ragged counts, a capacity that is
-not a multiple of 64, empty key frames, P = 0, host entries against device entries, argument validation."""
+not a multiple of 64, empty key frames, P = 0, host entries against device entries, argument validation.  Every case here runs a capacity
+of 80 slots, less than one workgroup of the triangulation kernel (256 slots of key frame 2); counts around and above a workgroup, the
+packing layouts and the capacity limit of 8192 are in tests/test_gpu_pair_kernels_wide.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,7 +1,8 @@
 """GPU parity of the stereo key-line association (plp_stereo_keylines_*) and of the 3-D key lines (plp_keylines_3d_*) against the CPU
 restatement tests/stereo_keylines_ref.py: real extractions and their 1-NN, batched and ragged problems with
 sentinel-filled outputs, host entries against device entries, RGB-D lines from the post-extract step's key-line depths, stereo lines from the
-association, and config_steps.stereo_step(associate_lines=True) frame by frame."""
+association, and config_steps.stereo_step(associate_lines=True) frame by frame.  The batched problems here have 96 left and 80 right slots,
+less than one workgroup of 256 key lines; left counts around and above one workgroup are in tests/test_gpu_pair_kernels_wide.py."""
 import importlib
 
 import numpy as np
