@@ -1709,6 +1709,102 @@ int32_t plp_model_local_ba_solve_host(int32_t P, int32_t M, int32_t E, const dou
                                       const int32_t* e_lm, const double* w, double lambda, double* out_xp, double* out_xl);
 int32_t plp_model_inv3_host(const double* a, int32_t n, double* out, int32_t* out_ok);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The local map of B frames over one map snapshot: module::local_map_updater (src/PLPSLAM/module/local_map_updater.cc:60-273) as
+ * tracking_module::update_local_map runs it (tracking_module.cc:837-906), and the landmarks search_local_landmarks[_line] skips because the
+ * frame holds them (tracking_module.cc:911-946).  Integers only; contract: DESIGN.md section 5, D18 (the literal parts, and the orders
+ * the reference leaves to an unordered_map and a std::set of pointers, which D18 defines: ascending key-frame row, the caller's child order).
+ *
+ * Map snapshot, shared by the B frames:
+ *   kf_erased            keyframe::will_be_erased()                                                       local_map_updater.cc:122, :156
+ *   kf_covis             [F][10] graph_node_->get_top_n_covisibilities(10) in its order, -1 behind the last              :179
+ *   kf_parent            [F] get_spanning_parent(), -1 = none                                                            :199
+ *   kf_children_offsets  [F + 1] into kf_children [C]: get_spanning_children() in the caller's order                     :189
+ *   kf_lm                [F][cap] keyfrm->get_landmarks(): the landmark row of key point idx, -1 = none                  :213
+ *   kf_counts            [F] key points per key frame, NULL = cap
+ *   kf_lm_lines          [F][lcap] keyfrm->get_landmarks_line(), with kf_kl_counts; NULL = _b_use_line_tracking is off   :248, tracking_module.cc:898
+ *   obs_offsets, obs_kf  lm->get_observations() in plp_landmark_geometry_args' layout; the key-frame rows only        :101-105
+ *   lm_erased            [L] landmark::will_be_erased(), NULL = none; lm_erased_lines [LL] likewise       :221, :256, tracking_module.cc:847, :864
+ * Per frame:
+ *   frm_lm               [B][frm_stride] curr_frm_.landmarks_ as landmark rows, -1 = none; fcap slots of a row are read  :33, :94-100
+ *   frm_counts           [B] num_keypts_, NULL = fcap                                                                    :34
+ *   frm_lm_lines         [B][frm_stride_lines] curr_frm_._landmarks_line, flcap slots read, with frm_kl_counts; NULL = the frame holds no line
+ * A row outside its table (frm_lm, kf_lm, obs_kf, kf_covis, kf_parent, kf_children and the line tables) counts as absent; a count is cut to
+ * [0, its cap]; an observation run is cut to [0, T].
+ * Outputs per frame; slots that are not written keep the caller's values:
+ *   out_status        a plp_local_map_status
+ *   out_num_first     first local key frames (:110-141); out_num_kf: first + second (:84-85), the true length even above k_cap
+ *   out_local_kf      [B][k_cap] the local key frames in order, rows [0, min(out_num_kf, k_cap))
+ *   out_first_weight  optional, [B][k_cap]: the weight of a first local key frame (:104), 0 for a second one
+ *   out_nearest_kf    nearest_covisibility_ (:133-137), -1 = none (no key frame voted, or every one that did is erased)
+ *   out_num_lm        local landmarks (:206-238), the true length even above m_cap; 0 after PLP_LOCAL_MAP_KF_OVERFLOW
+ *   out_local_lm      [B][m_cap] rows [0, min(out_num_lm, m_cap)); out_held [B][m_cap]: 1 = a non-empty slot of the frame holds the landmark
+ *                     (identifier_in_local_lm_search_ == curr_frm_.id_, tracking_module.cc:925, :939)
+ *   out_num_lines, out_local_lines [B][ml_cap], out_held_lines [B][ml_cap]: the same for lines (:241-273, tracking_module.cc:994-1011),
+ *                     written only when kf_lm_lines is given */
+typedef enum plp_local_map_status {
+    PLP_LOCAL_MAP_OK = 0,
+    PLP_LOCAL_MAP_NO_KEYFRAMES = 1,   /* no weight at all: acquire_local_map() returns false (:78-81) and the tracker keeps its previous local map; every
+                                         count is 0, out_nearest_kf -1, no list row is written                                                        */
+    PLP_LOCAL_MAP_KF_OVERFLOW = 2,    /* out_num_kf > k_cap: rows [0, k_cap) of out_local_kf are written, the landmark lists are not (their counts are 0) */
+    PLP_LOCAL_MAP_LM_OVERFLOW = 3,    /* out_num_lm > m_cap: rows [0, m_cap) are written; the line list is complete unless it overflows too               */
+    PLP_LOCAL_MAP_LINE_OVERFLOW = 4   /* out_num_lines > ml_cap (and the point list fits): rows [0, ml_cap) are written                                   */
+} plp_local_map_status;
+typedef struct plp_local_map_args {
+    int32_t B, F, C, L, LL, T;          /* B <= 65535 frames; F <= 8192 key frames (the weights of a frame are an LDS table); C children entries; L, LL landmark rows; T observation entries */
+    int32_t cap, lcap;                  /* slots per row of kf_lm / kf_lm_lines, <= 8192 */
+    int32_t fcap, flcap;                /* slots read per row of frm_lm / frm_lm_lines, <= 8192 */
+    int32_t frm_stride, frm_stride_lines;   /* slots between two rows of frm_lm / frm_lm_lines; 0 = fcap / flcap */
+    int32_t max_num_local_keyfrms;      /* tracking_module.cc:873 passes 60 */
+    int32_t k_cap, m_cap, ml_cap;       /* rows per frame of the three output lists; k_cap * max(cap, lcap) < 2^31 */
+    int64_t workspace_bytes;            /* the mark table (L + L / 32 words per frame, LL likewise) is kept for as many frames at a time as fit this
+                                           many bytes, at least one; 0 = 256 MiB.  The frames are done in chunks of that many. */
+    const uint8_t* kf_erased;           /* F, or NULL = none */
+    const int32_t* kf_covis;            /* F x 10 */
+    const int32_t* kf_parent;           /* F */
+    const int32_t* kf_children_offsets; /* F + 1 */
+    const int32_t* kf_children;         /* C */
+    const int32_t* kf_lm;               /* F x cap */
+    const int32_t* kf_counts;           /* F, or NULL */
+    const int32_t* kf_lm_lines;         /* F x lcap, or NULL = no lines */
+    const int32_t* kf_kl_counts;        /* F, or NULL */
+    const int32_t* obs_offsets;         /* L + 1 */
+    const int32_t* obs_kf;              /* T */
+    const uint8_t* lm_erased;           /* L, or NULL = none */
+    const uint8_t* lm_erased_lines;     /* LL, or NULL = none */
+    const int32_t* frm_lm;              /* B x frm_stride */
+    const int32_t* frm_counts;          /* B, or NULL */
+    const int32_t* frm_lm_lines;        /* B x frm_stride_lines, or NULL */
+    const int32_t* frm_kl_counts;       /* B, or NULL */
+    uint8_t* out_status;                /* B */
+    int32_t* out_num_first;             /* B */
+    int32_t* out_num_kf;                /* B */
+    int32_t* out_local_kf;              /* B x k_cap */
+    int32_t* out_first_weight;          /* B x k_cap, or NULL */
+    int32_t* out_nearest_kf;            /* B */
+    int32_t* out_num_lm;                /* B */
+    int32_t* out_local_lm;              /* B x m_cap */
+    uint8_t* out_held;                  /* B x m_cap */
+    int32_t* out_num_lines;             /* B; the three line outputs are required iff kf_lm_lines is given */
+    int32_t* out_local_lines;           /* B x ml_cap */
+    uint8_t* out_held_lines;            /* B x ml_cap */
+} plp_local_map_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; a negative B, F, C, L, LL, T, cap, lcap, fcap, flcap, stride,
+ * max_num_local_keyfrms or workspace_bytes; k_cap, m_cap or ml_cap < 0; a stride below its fcap / flcap (when not 0); and -- when B > 0 -- a
+ * NULL kf_covis, kf_parent (F > 0), kf_children_offsets, kf_children (C > 0), kf_lm (F > 0 and cap > 0), obs_offsets, obs_kf (T > 0), frm_lm
+ * (fcap > 0), or a NULL required output of non-zero size.  F > 8192, cap, lcap, fcap or flcap > 8192, B > 65535, k_cap * max(cap, lcap) >=
+ * 2^31: PLP_ERR_UNSUPPORTED.  B == 0: PLP_OK, nothing written.  _host and the host build also check that obs_offsets rises from 0 to T and
+ * kf_children_offsets from 0 to C (PLP_ERR_INVALID_ARG); on the _device path that is a precondition (the kernels cut every run to its list).
+ * _device: every array a DEVICE pointer; k_local_map_keyframes once (a workgroup per frame), then per chunk of frames the clear of the mark
+ * table, k_local_map_mark and k_local_map_compact for the points and again for the lines, all on hip_stream; the number of chunks follows
+ * from the shapes, so nothing is synchronised.  The mark table is the context's: the calls of one context must be ordered on the device.
+ * _host: HOST pointers, staged (the outputs too, so that every slot the kernels do not write keeps the caller's value), synchronous. */
+plp_status plp_local_map_device(plp_matcher* ctx, const plp_local_map_args* args, void* hip_stream);
+plp_status plp_local_map_host(plp_matcher* ctx, const plp_local_map_args* args);
+/* Host build of the same source (csrc/local_map.hpp) with a team of one lane, HOST pointers, no GPU and no context needed; the same checks.
+ * Returns B, or the negated plp_status of a refused call. */
+int32_t plp_model_local_map_host(const plp_local_map_args* args);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

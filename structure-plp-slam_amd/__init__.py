@@ -177,6 +177,9 @@ _API = [
     ("plp_local_ba_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_local_ba_host", C.c_int, [_VP, _VP]),
     ("plp_model_local_ba_host", _I32, [_VP]),
+    ("plp_local_map_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_local_map_host", C.c_int, [_VP, _VP]),
+    ("plp_model_local_map_host", _I32, [_VP]),
     ("plp_model_local_ba_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_model_local_ba_solve_host", _I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, C.c_double, _VP, _VP]),
     ("plp_model_inv3_host", _I32, [_VP, _I32, _VP, _VP]),
@@ -1069,6 +1072,146 @@ class local_bundle_adjuster:
         return {k: v[0] for k, v in r.items()}
 
 
+# plp_local_map_status
+LOCAL_MAP_OK, LOCAL_MAP_NO_KEYFRAMES, LOCAL_MAP_KF_OVERFLOW, LOCAL_MAP_LM_OVERFLOW, LOCAL_MAP_LINE_OVERFLOW = range(5)
+LOCAL_MAP_MAX_KF = 8192             # F: the weights of a frame are an LDS table of that many counters
+LOCAL_MAP_MAX_SLOTS = 8192          # cap, lcap, fcap, flcap
+LOCAL_MAP_MAX_FRAMES = 65535        # B
+LOCAL_MAP_INPUTS = ("kf_erased", "kf_covis", "kf_parent", "kf_children_offsets", "kf_children", "kf_lm", "kf_counts", "kf_lm_lines", "kf_kl_counts",
+                    "obs_offsets", "obs_kf", "lm_erased", "lm_erased_lines", "frm_lm", "frm_counts", "frm_lm_lines", "frm_kl_counts")
+# the outputs of plp_local_map_*: name -> (which of k_cap / m_cap / ml_cap is its row length or None, dtype, optional, line side only)
+LOCAL_MAP_OUTPUTS = dict(status=(None, np.uint8, False, False), num_first=(None, np.int32, False, False), num_kf=(None, np.int32, False, False),
+                         local_kf=("k_cap", np.int32, False, False), first_weight=("k_cap", np.int32, True, False),
+                         nearest_kf=(None, np.int32, False, False), num_lm=(None, np.int32, False, False), local_lm=("m_cap", np.int32, False, False),
+                         held=("m_cap", np.uint8, False, False), num_lines=(None, np.int32, False, True),
+                         local_lines=("ml_cap", np.int32, False, True), held_lines=("ml_cap", np.uint8, False, True))
+
+
+def _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased, kf_counts,
+                    kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines, frm_kl_counts, max_num_local_keyfrms, workspace_bytes,
+                    fcap, flcap, outputs, out):
+    """the numpy side of plp_local_map_host and plp_model_local_map_host: call(args struct) runs the entry.  The row widths of kf_lm, kf_lm_lines,
+    frm_lm and frm_lm_lines are cap, lcap and the two frame strides; fcap / flcap (default: the stride) are the slots read of a frame's row."""
+    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    kp = i32(kf_parent).reshape(-1)
+    F = len(kp)
+    rows = lambda v, n: None if v is None else (i32(v).reshape(n, -1) if n else np.zeros((0, 0), np.int32))
+    kc = rows(kf_covis, F)
+    if F and kc.shape[1] != 10:
+        raise PlpError(PLP_ERR_INVALID_ARG, "kf_covis must be (F, 10)")
+    co, ch = i32(kf_children_offsets).reshape(-1), i32(kf_children).reshape(-1)
+    kl, kll = rows(kf_lm, F), rows(kf_lm_lines, F)
+    oo, ok = i32(obs_offsets).reshape(-1), i32(obs_kf).reshape(-1)
+    fl = i32(frm_lm)
+    if fl.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "frm_lm must be (B, stride)")
+    B = fl.shape[0]
+    fll = None if frm_lm_lines is None else i32(frm_lm_lines).reshape(B, -1)
+    if len(co) != F + 1 or len(oo) < 1:
+        raise PlpError(PLP_ERR_INVALID_ARG, "kf_children_offsets must have F + 1 entries, obs_offsets L + 1")
+    L = len(oo) - 1
+    le, lel = u8(lm_erased), u8(lm_erased_lines)
+    LL = int(LL) if LL is not None else (len(lel) if lel is not None else 0)
+    ke, kcn, kkc, fc, fkc = u8(kf_erased), i32(kf_counts), i32(kf_kl_counts), i32(frm_counts), i32(frm_kl_counts)
+    for name, v, n in (("kf_erased", ke, F), ("kf_counts", kcn, F), ("kf_kl_counts", kkc, F), ("lm_erased", le, L), ("lm_erased_lines", lel, LL),
+                       ("frm_counts", fc, B), ("frm_kl_counts", fkc, B)):
+        if v is not None and v.size != n:
+            raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
+    caps = dict(k_cap=int(k_cap), m_cap=int(m_cap), ml_cap=int(ml_cap))
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    lines = kll is not None
+    a = _struct(local_map_args_c, dict(B=B, F=F, C=len(ch), L=L, LL=LL, T=len(ok), cap=kl.shape[1], lcap=kll.shape[1] if lines else 0,
+                                       fcap=fl.shape[1] if fcap is None else int(fcap), flcap=(fll.shape[1] if fll is not None else 0) if flcap is None else int(flcap),
+                                       frm_stride=fl.shape[1], frm_stride_lines=fll.shape[1] if fll is not None else 0,
+                                       max_num_local_keyfrms=int(max_num_local_keyfrms), workspace_bytes=int(workspace_bytes), **caps), dict(
+        kf_erased=Pt(ke), kf_covis=Pt(kc), kf_parent=Pt(kp), kf_children_offsets=Pt(co), kf_children=Pt(ch), kf_lm=Pt(kl), kf_counts=Pt(kcn),
+        kf_kl_counts=Pt(kkc), obs_offsets=Pt(oo), obs_kf=Pt(ok), lm_erased=Pt(le), lm_erased_lines=Pt(lel), frm_lm=Pt(fl), frm_counts=Pt(fc),
+        frm_lm_lines=Pt(fll), frm_kl_counts=Pt(fkc)))
+    if lines:      # a table without a slot is still "line tracking is on": the pointer only has to be non-NULL
+        a.kf_lm_lines = kll.ctypes.data if kll.size else kp.ctypes.data if kp.size else co.ctypes.data
+    o = {}
+    for k, (cap_name, dt, optional, line_side) in LOCAL_MAP_OUTPUTS.items():   # the caller's arrays are the outputs when given (unwritten slots keep their values)
+        if (line_side and not lines) or (optional and outputs is not None and k not in outputs):
+            continue
+        full = (B,) if cap_name is None else (B, max(caps[cap_name], 0))      # a negative cap is the library's to refuse
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+        setattr(a, "out_" + k, Pt(o[k]))
+    call(a)
+    return o
+
+
+def model_local_map(kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap=0, kf_erased=None,
+                    kf_counts=None, kf_lm_lines=None, kf_kl_counts=None, lm_erased=None, lm_erased_lines=None, LL=None, frm_counts=None, frm_lm_lines=None,
+                    frm_kl_counts=None, max_num_local_keyfrms=60, workspace_bytes=0, fcap=None, flcap=None, outputs=None, out=None):
+    """Host build of module::local_map_updater for B frames (csrc/local_map.hpp, DESIGN.md section 5, D18; no GPU needed): the arguments and the
+    result of matcher.local_map."""
+    def call(a):
+        r = lib().plp_model_local_map_host(C.byref(a))
+        if r != a.B:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased,
+                           kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines, frm_kl_counts,
+                           max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
+
+
+def kf_landmarks_from_observations(obs_offsets, obs_kf, obs_idx, F, cap):
+    """kf_lm [F, cap] i32 from the observation lists (torch tensors on one device): slot (obs_kf[t], obs_idx[t]) takes the landmark whose run holds
+    entry t, every other slot -1.  For callers whose keyframe landmarks_ and landmark observations_ agree (one landmark per slot); entries outside
+    the table are left out.  Static shapes, no synchronisation."""
+    import torch
+    T, dev = obs_kf.shape[0], obs_kf.device
+    out = torch.full((F * cap + 1,), -1, dtype=torch.int32, device=dev)
+    if T == 0 or F * cap == 0:
+        return out[:F * cap].view(F, cap)
+    lm = torch.searchsorted(obs_offsets[1:].to(torch.int64).contiguous(), torch.arange(T, device=dev), right=True)
+    kf, ix = obs_kf.to(torch.int64), obs_idx.to(torch.int64)
+    inside = (kf >= 0) & (kf < F) & (ix >= 0) & (ix < cap)
+    out.index_copy_(0, torch.where(inside, kf * cap + ix, torch.full_like(kf, F * cap)), lm.to(torch.int32))
+    out[F * cap] = -1
+    return out[:F * cap].view(F, cap)
+
+
+class local_map_updater:
+    """Mirror of module::local_map_updater (module/local_map_updater.h) for one frame: acquire_local_map() takes the map tables (a dict with the
+    keys of LOCAL_MAP_INPUTS but the frm_* ones) and the frame's landmarks_ as rows; mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, max_num_local_keyfrms=60, mt=None):
+        self.max_num_local_keyfrms, self._mt, self._r = int(max_num_local_keyfrms), mt, None
+
+    def acquire_local_map(self, tables, frm_lm, frm_lm_lines=None, k_cap=None, m_cap=None, ml_cap=None, LL=None):
+        """True iff a key frame voted (:60-66).  The caps default to what always fits: F key frames, L landmarks, LL lines."""
+        F, L = len(np.asarray(tables["kf_parent"]).reshape(-1)), len(np.asarray(tables["obs_offsets"]).reshape(-1)) - 1
+        lel = tables.get("lm_erased_lines")
+        LL = int(LL) if LL is not None else (len(lel) if lel is not None else 0)
+        fn = model_local_map if self._mt is None else self._mt.local_map
+        opt = {k: tables.get(k) for k in ("kf_erased", "kf_counts", "kf_lm_lines", "kf_kl_counts", "lm_erased", "lm_erased_lines")}
+        r = fn(tables["kf_covis"], tables["kf_parent"], tables["kf_children_offsets"], tables["kf_children"], tables["kf_lm"], tables["obs_offsets"],
+               tables["obs_kf"], np.asarray(frm_lm, np.int32).reshape(1, -1), F if k_cap is None else k_cap, L if m_cap is None else m_cap,
+               LL if ml_cap is None else ml_cap, LL=LL, frm_lm_lines=None if frm_lm_lines is None else np.asarray(frm_lm_lines, np.int32).reshape(1, -1),
+               max_num_local_keyfrms=self.max_num_local_keyfrms, **opt)
+        self._r = {k: v[0] for k, v in r.items()}
+        return int(self._r["status"]) != LOCAL_MAP_NO_KEYFRAMES
+
+    def get_local_keyframes(self):
+        return self._r["local_kf"][:min(int(self._r["num_kf"]), len(self._r["local_kf"]))].copy()
+
+    def get_local_landmarks(self):
+        return self._r["local_lm"][:min(int(self._r["num_lm"]), len(self._r["local_lm"]))].copy()
+
+    def get_local_landmarks_line(self):
+        if "num_lines" not in self._r:
+            return np.zeros(0, np.int32)
+        return self._r["local_lines"][:min(int(self._r["num_lines"]), len(self._r["local_lines"]))].copy()
+
+    def get_nearest_covisibility(self):
+        """the key-frame row, or -1 where the reference's member is indeterminate (D18)"""
+        return int(self._r["nearest_kf"])
+
+
 class orb_extractor:
     """Mirror of feature::orb_extractor (src/PLPSLAM/feature/orb_extractor.h:38-176) over the C ABI."""
 
@@ -1649,6 +1792,18 @@ class local_ba_args_c(C.Structure):
                 ("pos_w", _VP), ("lm_erased", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("obs_idx", _VP), ("kf_local", _VP), ("out_status", _VP),
                 ("out_kf_role", _VP), ("out_lm_role", _VP), ("out_pose", _VP), ("out_pos_w", _VP), ("out_outlier", _VP), ("out_round_info", _VP),
                 ("out_round_chi2", _VP)]
+
+
+class local_map_args_c(C.Structure):
+    """plp_local_map_args"""
+    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("LL", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32),
+                ("lcap", C.c_int32), ("fcap", C.c_int32), ("flcap", C.c_int32), ("frm_stride", C.c_int32), ("frm_stride_lines", C.c_int32),
+                ("max_num_local_keyfrms", C.c_int32), ("k_cap", C.c_int32), ("m_cap", C.c_int32), ("ml_cap", C.c_int32), ("workspace_bytes", C.c_int64),
+                ("kf_erased", _VP), ("kf_covis", _VP), ("kf_parent", _VP), ("kf_children_offsets", _VP), ("kf_children", _VP), ("kf_lm", _VP),
+                ("kf_counts", _VP), ("kf_lm_lines", _VP), ("kf_kl_counts", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("lm_erased", _VP),
+                ("lm_erased_lines", _VP), ("frm_lm", _VP), ("frm_counts", _VP), ("frm_lm_lines", _VP), ("frm_kl_counts", _VP), ("out_status", _VP),
+                ("out_num_first", _VP), ("out_num_kf", _VP), ("out_local_kf", _VP), ("out_first_weight", _VP), ("out_nearest_kf", _VP),
+                ("out_num_lm", _VP), ("out_local_lm", _VP), ("out_held", _VP), ("out_num_lines", _VP), ("out_local_lines", _VP), ("out_held_lines", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -2627,6 +2782,33 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_local_ba_device(self._h, C.byref(a), st))
+
+    def local_map(self, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap=0, kf_erased=None,
+                  kf_counts=None, kf_lm_lines=None, kf_kl_counts=None, lm_erased=None, lm_erased_lines=None, LL=None, frm_counts=None, frm_lm_lines=None,
+                  frm_kl_counts=None, max_num_local_keyfrms=60, workspace_bytes=0, fcap=None, flcap=None, outputs=None, out=None):
+        """module::local_map_updater for B frames over one map snapshot (plp_local_map_host; DESIGN.md section 5, D18): kf_covis (F, 10), kf_parent (F,),
+        kf_children_offsets (F + 1,), kf_children (C,), kf_lm (F, cap), the observation lists obs_offsets (L + 1,), obs_kf (T,), frm_lm (B, stride), all
+        i32 with -1 for none; kf_lm_lines (F, lcap) with LL line rows and frm_lm_lines (B, stride) or None; the erased flags u8 and the counts i32 or
+        None.  Returns dict(status (B,) u8: LOCAL_MAP_*, num_first, num_kf, nearest_kf, num_lm (B,), local_kf, first_weight (B, k_cap), local_lm, held
+        (B, m_cap) and, with lines, num_lines, local_lines, held_lines); `outputs` names the optional ones wanted (default all); out[name]: the caller's
+        array (slots the updater does not write keep their values)."""
+        call = lambda a: _check(lib().plp_local_map_host(self._h, C.byref(a)))
+        return _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased,
+                               kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines, frm_kl_counts,
+                               max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
+
+    def local_map_device(self, dims, tables, out, max_num_local_keyfrms=60, workspace_bytes=0, stream=None):
+        """plp_local_map_device: dims a dict of the struct's sizes (B, F, C, L, LL, T, cap, lcap, fcap, flcap, k_cap, m_cap, ml_cap and optionally
+        frm_stride, frm_stride_lines); tables a dict of LOCAL_MAP_INPUTS and out a dict of LOCAL_MAP_OUTPUTS, each a device pointer (int), a torch
+        tensor on the matcher's device or absent / None; asynchronous on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(local_map_args_c, dict({k: int(v) for k, v in dims.items()}, max_num_local_keyfrms=int(max_num_local_keyfrms),
+                                           workspace_bytes=int(workspace_bytes)), {k: D(tables.get(k)) for k in LOCAL_MAP_INPUTS})
+        for k in LOCAL_MAP_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_local_map_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):

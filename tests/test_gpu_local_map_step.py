@@ -1,0 +1,182 @@
+"""local_map_step end to end on the device (structure-plp-slam_amd/local_map_step.py): the map's tables and the frames' landmark slots in, the
+`local` dict of posed_step.py out, row by row against gathers done in numpy from the lists of the restatement tests/local_map_ref.py; then that
+dict fed to posed_tracker_step.run_local on the small posed scene the pose-optimisation step's test uses, against the same call fed the
+numpy-built tables."""
+import importlib
+
+import numpy as np
+import pytest
+
+import last_frame_ref as LF
+import local_map_ref as R
+from plp import plp
+from test_gpu_landmark_observe import random_pose, yaml_of
+from test_gpu_last_frame import _last_pose, _world
+from test_gpu_pose_optimization_step import plucker
+
+pytestmark = pytest.mark.gpu
+i32, u8 = np.int32, np.uint8
+POINT_KEYS = ("pos_w", "normal", "min_dist", "max_dist", "desc")
+LINE_KEYS = ("pos_w_lines", "min_dist_lines", "max_dist_lines", "desc_lines", "plucker_lines")
+
+
+def build_map(rng, worlds, F, fcap, flcap, lcap):
+    """one map from the frames' local landmarks: frame b's rows are block b of the tables; observations, key-frame slots, covisibilities and a
+    spanning tree at random"""
+    lo = [w[2] for w in worlds]
+    lm = {k: np.concatenate([d[k] for d in lo]) for k in POINT_KEYS + LINE_KEYS + ("skip", "skip_lines")}
+    L, LL, B = len(lm["pos_w"]), len(lm["pos_w_lines"]), len(worlds)
+    per, per_l = L // B, LL // B
+    off, kfs, idx, used = [0], [], [], np.zeros(F, i32)
+    for l in range(L):
+        for kf in (6 * (l // per) + rng.choice(6, int(rng.integers(0, 4)), replace=False)).tolist():   # block b votes for key frames 6 b .. 6 b + 5
+            kfs.append(kf); idx.append(int(used[kf])); used[kf] += 1
+        off.append(len(kfs))
+    off_l = np.concatenate([[0], np.cumsum(rng.integers(0, 3, LL))]).astype(i32)
+    kf_lm_lines = rng.integers(-1, LL, (F, lcap)).astype(i32)
+    kf_covis = np.full((F, 10), -1, i32)
+    for f in range(F):
+        n = int(rng.integers(1, 6))
+        kf_covis[f, :n] = rng.choice(F, n, replace=False)
+    kf_parent = np.array([-1] + [int(rng.integers(0, f)) for f in range(1, F)], i32)
+    kids = [np.flatnonzero(kf_parent == f) for f in range(F)]
+    sc = dict(cap=int(used.max()), lcap=lcap, fcap=fcap, flcap=flcap, LL=LL, max_kf=8,
+              kf_erased=(np.arange(F) == 2).astype(u8), kf_covis=kf_covis, kf_parent=kf_parent,
+              kf_children_offsets=np.concatenate([[0], np.cumsum([len(k) for k in kids])]).astype(i32), kf_children=np.concatenate(kids).astype(i32),
+              kf_counts=used.copy(), kf_lm_lines=kf_lm_lines, kf_kl_counts=rng.integers(1, lcap + 1, F).astype(i32),
+              obs_offsets=np.array(off, i32), obs_kf=np.array(kfs, i32), obs_idx=np.array(idx, i32), lm_erased=lm["skip"], lm_erased_lines=lm["skip_lines"],
+              frm_counts=rng.integers(fcap // 2, fcap + 1, B).astype(i32), frm_kl_counts=rng.integers(1, flcap + 1, B).astype(i32))
+    sc["frm_lm"] = np.stack([np.where(rng.random(fcap) < 0.7, b * per + rng.integers(0, per, fcap), -1) for b in range(B)]).astype(i32)
+    sc["frm_lm_lines"] = np.stack([np.where(rng.random(flcap) < 0.7, b * per_l + rng.integers(0, per_l, flcap), -1) for b in range(B)]).astype(i32)
+    sc["kf_lm"] = np.full((F, sc["cap"]), -1, i32)
+    for l in range(L):
+        for o in range(off[l], off[l + 1]):
+            sc["kf_lm"][kfs[o], idx[o]] = l
+    lm["obs_offsets_lines"] = off_l
+    return sc, lm
+
+
+def test_the_step_equals_the_restatement_and_feeds_run_local():
+    import torch
+    setup, tb = LF.RGBD, 0.05
+    cm = plp.camera_model(yaml_of("fr1"))
+    rng = np.random.default_rng(1801)
+    B, cap, lcap_f, m, ml, L, LL, F = 2, 640, 96, 100, 20, 160, 30, 14
+    P = np.stack([random_pose(rng, False) for _ in range(B)])
+    worlds = [_world(rng, cm, setup, P[b], _last_pose(rng, P[b], tb), cap, lcap_f, m, ml, L, LL) for b in range(B)]
+    for _, _, lo in worlds:
+        lo["plucker_lines"] = plucker(lo["pos_w_lines"])
+    sc, lm = build_map(np.random.default_rng(1802), worlds, F, 64, 12, 9)
+    res = R.run_scene(sc, sc["max_kf"])
+    assert all(r["found"] and r["second"] and 20 < len(r["local_lm"]) and len(r["local_lines"]) > 3 for r in res)
+    assert any(sum(r["held"]) > 0 for r in res) and any(sum(r["held_lines"]) > 0 for r in res)
+    dev = torch.device("cuda:0")
+
+    def T(a):
+        a = np.ascontiguousarray(a)
+        if a.dtype.fields is not None:
+            a = a.view(np.uint8).reshape(a.shape + (-1,))
+        return torch.from_numpy(a).to(dev)
+    N = lambda t: t.cpu().numpy()
+    keyframes = {k: T(sc[k]) for k in ("kf_erased", "kf_covis", "kf_parent", "kf_children_offsets", "kf_children", "kf_lm_lines")}
+    keyframes.update(counts=T(sc["kf_counts"]), kl_counts=T(sc["kf_kl_counts"]))
+    landmarks = {k: T(v) for k, v in lm.items()}
+    landmarks.update(obs_offsets=T(sc["obs_offsets"]), obs_kf=T(sc["obs_kf"]))
+    # the helper: where landmarks_ and observations_ agree, kf_lm is the scatter of the observation lists
+    keyframes["kf_lm"] = plp.kf_landmarks_from_observations(landmarks["obs_offsets"], landmarks["obs_kf"], T(sc["obs_idx"]), F, sc["cap"])
+    assert np.array_equal(N(keyframes["kf_lm"]), sc["kf_lm"])
+    prev = np.array([5, 6], i32)
+    frames = dict(frm_lm=T(sc["frm_lm"]), frm_counts=T(sc["frm_counts"]), frm_lm_lines=T(sc["frm_lm_lines"]), frm_kl_counts=T(sc["frm_kl_counts"]), ref_kf=T(prev))
+    before = {k: v.clone() for k, v in {**keyframes, **landmarks, **frames}.items()}
+    m_cap, ml_cap = 1 + max(len(r["local_lm"]) for r in res), 2 + max(len(r["local_lines"]) for r in res)
+    step = importlib.import_module("structure-plp-slam_amd.local_map_step").local_map_step(plp, k_cap=F, m_cap=m_cap, ml_cap=ml_cap,
+                                                                                            max_num_local_keyfrms=sc["max_kf"])
+    out = step.run(keyframes, landmarks, frames)
+    torch.cuda.synchronize()
+    for k, v in before.items():
+        assert torch.equal(v, {**keyframes, **landmarks, **frames}[k]), k
+
+    # row by row against numpy gathers from the restatement's lists
+    want = R.expected(res, F, m_cap, ml_cap, True)
+    for k in want:
+        sel = want[k] != R.SENTINEL[k]
+        assert np.array_equal(N(out[k])[sel], want[k][sel]), k
+    assert np.array_equal(N(out["ref_kf"]), [r["nearest"] if r["nearest"] >= 0 else prev[b] for b, r in enumerate(res)])
+    local = out["local"]
+    mine = {}
+    for sfx, keys, lst, held, cap_ in (("", POINT_KEYS, "local_lm", "held", m_cap), ("_lines", LINE_KEYS, "local_lines", "held_lines", ml_cap)):
+        off = lm["obs_offsets_lines"] if sfx else sc["obs_offsets"]
+        erased = lm["skip" + sfx]
+        cnt = np.array([len(r[lst]) for r in res], i32)
+        assert np.array_equal(N(local["counts" + sfx]), cnt)
+        mine["counts" + sfx] = cnt
+        for k in keys:
+            mine[k] = np.zeros((B, cap_) + lm[k].shape[1:], lm[k].dtype)
+        mine["has_obs" + sfx], mine["skip" + sfx] = np.zeros((B, cap_), u8), np.ones((B, cap_), u8)
+        for b, r in enumerate(res):
+            rows = np.array(r[lst], np.int64)
+            n = len(rows)
+            for k in keys:
+                mine[k][b, :n] = lm[k][rows]
+                assert N(local[k])[b, :n].tobytes() == mine[k][b, :n].tobytes(), (k, b)
+            mine["has_obs" + sfx][b, :n] = off[rows + 1] > off[rows]
+            mine["skip" + sfx][b, :n] = np.array(r[held], u8) | erased[rows]
+            assert np.array_equal(N(local["has_obs" + sfx])[b, :n], mine["has_obs" + sfx][b, :n]) and (N(local["skip" + sfx])[b, n:] == 1).all()
+            assert np.array_equal(N(local["skip" + sfx])[b, :n], mine["skip" + sfx][b, :n]), b
+
+    # the dict feeds run_local: the same call with the numpy-built tables gives the same matches and queries
+    posed = importlib.import_module("structure-plp-slam_amd.posed_step")
+    stack = lambda k: T(np.stack([np.asarray(w[0][k]) for w in worlds]))
+    frame = {k: stack(k) for k in worlds[0][0]}
+    frame["counts"], frame["kl_counts"] = frame["counts"].to(torch.int32), frame["kl_counts"].to(torch.int32)
+    occ, occ_l = torch.zeros((B, cap), dtype=torch.uint8, device=dev), torch.zeros((B, lcap_f), dtype=torch.uint8, device=dev)
+    runs = []
+    for tables in (local, {k: T(v) for k, v in mine.items()}):
+        ps = posed.posed_tracker_step(plp, cm, setup, true_baseline=tb)
+        o = ps.run_local(frame, tables, T(P), occ, occ_l)
+        torch.cuda.synchronize()
+        runs.append({k: N(o[k]).copy() for k in ("m2", "n2", "m4", "n4")} | {"q2v": N(o["q2"]["q_valid"]).copy(), "q4v": N(o["q4"]["q_valid"]).copy()})
+    a, b_ = runs
+    assert np.array_equal(a["n2"], b_["n2"]) and np.array_equal(a["n4"], b_["n4"]) and a["n2"].min() > 5
+    for b in range(B):
+        n, nl = int(worlds[b][0]["counts"]), int(worlds[b][0]["kl_counts"])
+        assert np.array_equal(a["m2"][b, :n], b_["m2"][b, :n]) and np.array_equal(a["m4"][b, :nl], b_["m4"][b, :nl]), b
+        c, cl = int(mine["counts"][b]), int(mine["counts_lines"][b])
+        assert np.array_equal(a["q2v"][b, :c], b_["q2v"][b, :c]) and np.array_equal(a["q4v"][b, :cl], b_["q4v"][b, :cl]), b
+
+
+def test_ref_kf_keeps_the_previous_value_and_overflow_empties_the_dict():
+    """ref_kf is `nearest`, or the caller's previous value where no key frame voted or every one that did is erased (tracking_module.cc:877-892);
+    a frame whose key-frame list overflows has counts of 0"""
+    import torch
+    import local_map_scene as S
+    sc = S.scene("f130")
+    res = R.run_scene(sc, sc["max_kf"])
+    assert not res[3]["found"] and res[4]["found"] and res[4]["nearest"] == -1
+    rng = np.random.default_rng(1802)
+    F, L, LL, B = len(sc["kf_parent"]), len(sc["obs_offsets"]) - 1, sc["LL"], sc["frm_lm"].shape[0]
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    keyframes = {k: T(sc[k]) for k in ("kf_erased", "kf_covis", "kf_parent", "kf_children_offsets", "kf_children", "kf_lm", "kf_lm_lines")}
+    keyframes.update(counts=T(sc["kf_counts"]), kl_counts=T(sc["kf_kl_counts"]))
+    landmarks = dict(pos_w=T(rng.random((L, 3))), normal=T(rng.random((L, 3))), min_dist=T(rng.random(L).astype(np.float32)),
+                     max_dist=T(rng.random(L).astype(np.float32)), desc=T(rng.integers(0, 256, (L, 32), dtype=u8)), skip=T(sc["lm_erased"]),
+                     obs_offsets=T(sc["obs_offsets"]), obs_kf=T(sc["obs_kf"]), pos_w_lines=T(rng.random((LL, 6))),
+                     min_dist_lines=T(rng.random(LL).astype(np.float32)), max_dist_lines=T(rng.random(LL).astype(np.float32)),
+                     desc_lines=T(rng.integers(0, 256, (LL, 32), dtype=u8)), skip_lines=T(sc["lm_erased_lines"]),
+                     obs_offsets_lines=T(np.arange(LL + 1, dtype=i32)))
+    prev = np.arange(100, 100 + B, dtype=i32)
+    frames = dict(frm_lm=T(sc["frm_lm"][:, :sc["fcap"]]), frm_counts=T(sc["frm_counts"]), frm_lm_lines=T(sc["frm_lm_lines"][:, :sc["flcap"]]),
+                  frm_kl_counts=T(sc["frm_kl_counts"]), ref_kf=T(prev))
+    k_cap = len(res[1]["first"]) + len(res[1]["second"])            # frame 1 fits exactly, frame 0 (more first key frames than that) does not
+    assert len(res[0]["first"]) > k_cap
+    step = importlib.import_module("structure-plp-slam_amd.local_map_step").local_map_step(plp, k_cap=k_cap, m_cap=L, ml_cap=LL, max_num_local_keyfrms=sc["max_kf"])
+    out = step.run(keyframes, landmarks, frames)
+    torch.cuda.synchronize()
+    want = R.expected(res, k_cap, L, LL, True)
+    N = lambda t: t.cpu().numpy()
+    assert np.array_equal(N(out["status"]), want["status"]) and want["status"][0] == R.KF_OVERFLOW and want["status"][3] == R.NO_KEYFRAMES
+    assert np.array_equal(N(out["ref_kf"]), [r["nearest"] if r["found"] and r["nearest"] >= 0 else prev[b] for b, r in enumerate(res)])
+    assert N(out["ref_kf"])[3] == prev[3] and N(out["ref_kf"])[4] == prev[4] and N(out["ref_kf"])[0] == res[0]["nearest"]
+    counts = [0 if s in (R.NO_KEYFRAMES, R.KF_OVERFLOW) else len(r["local_lm"]) for r, s in zip(res, want["status"])]
+    assert np.array_equal(N(out["local"]["counts"]), counts) and counts[0] == 0 and counts[1] > 0
+    assert (N(out["local"]["skip"])[0] == 1).all() and (N(out["local"]["skip"])[3] == 1).all()
