@@ -1,8 +1,8 @@
 // optimize::local_bundle_adjuster::optimize (optimize/local_bundle_adjuster.cc:62-410), one definition for host and device (plp_local_ba_* /
 // plp_model_local_ba*_host, include/plp_front.h) on top of pose_opt.hpp (D15): the sets and roles from the map tables,
 // the binary reprojection edge with both Jacobian blocks, the ordered sums of the blocks, the Schur complement on the landmarks, the Cholesky of
-// the reduced system, g2o's Levenberg-Marquardt and the two rounds.  f64 with IEEE + - * / sqrt only, in the order written; translation units
-// that include this file are compiled with -ffp-contract=off.
+// the reduced system and the two rounds; g2o's Levenberg-Marquardt accept / reject step and end rule are levenberg.hpp's.  f64 with IEEE
+// + - * / sqrt only, in the order written; translation units that include this file are compiled with -ffp-contract=off.
 //
 // The steps are written once over a team `P` of lanes (P::NT lanes in waves of P::WS): the kernels run them with a workgroup of 512, the host
 // build with a team of one, for which every barrier is empty and every strided loop is the plain loop.  No sum depends on the team's size: each
@@ -132,7 +132,7 @@ __host__ __device__ __forceinline__ bool la_inv3(const double* a, double* o) {
     const double id = 1.0 / det;
     o[0] = c00 * id; o[1] = c01 * id; o[2] = c02 * id; o[3] = c11 * id; o[4] = c12 * id; o[5] = c22 * id;
     bool ok = true;
-    _Pragma("unroll") for (int i = 0; i < 6; ++i) ok = ok && o[i] >= -kPoseDblMax && o[i] <= kPoseDblMax;
+    _Pragma("unroll") for (int i = 0; i < 6; ++i) ok = ok && o[i] >= -kLevDblMax && o[i] <= kLevDblMax;
     return ok;
 }
 
@@ -365,7 +365,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_edge_pa
 // ---- the sums of a pass: every active landmark's robust chi2 (and its block when lin) over its level-0 edges in list order, every active
 // pose's 27 sums over its edges in edge order
 template <class P, class AA> __host__ __device__ __forceinline__ void la_sums(const AA& A, const LaView& V, LaShared& sh, P& par, bool lin) {
-    const int L = A.L, T = A.T;
+    const int L = A.L;
     for (int l = par.tid(); l < L; l += P::NT) {
         if (!V.lm_act()[l]) continue;
         int lo, hi;
@@ -439,7 +439,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
         const int p = it / n, q = it % n;
         double v = 0.0;
         if (q >= p && q / 6 == p / 6) {
-            v = la_p(V, p / 6, pose_h_index(p % 6, q % 6));
+            v = la_p(V, p / 6, lev_h_index<6>(p % 6, q % 6));
             if (p == q) v = v + lambda;
         }
         V.S()[(size_t)p * kLaN + q] = v;
@@ -496,7 +496,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
                 s = s - ljk * ljk;
                 if (p > j) v = v - V.S()[(size_t)k * kLaN + p] * ljk;
             }
-            if (!(s > 0.0) || s > kPoseDblMax) { sh.ok = 0; continue; }
+            if (!(s > 0.0) || s > kLevDblMax) { sh.ok = 0; continue; }
             const double d = __builtin_sqrt(s);
             if (p == j) sh.dl[j] = d;
             else V.S()[(size_t)j * kLaN + p] = v / d;
@@ -647,7 +647,7 @@ template <class P> __host__ __device__ __forceinline__ void la_solve(const LaArg
                     double m = 0.0;                          // computeLambdaInit over every active vertex, at iteration 0
                     for (int a = 0; a < sh.nfa; ++a)
                         _Pragma("unroll") for (int j = 0; j < 6; ++j) {
-                            const double d = __builtin_fabs(la_p(V, a, pose_h_index(j, j)));
+                            const double d = __builtin_fabs(la_p(V, a, lev_h_index<6>(j, j)));
                             m = d > m ? d : m;
                         }
                     sh.acc = m;
@@ -666,29 +666,10 @@ template <class P> __host__ __device__ __forceinline__ void la_solve(const LaArg
             par.barrier();
             la_scale(D, V, sh, par);
             if (tid == 0) {
-                const double temp_chi = sh.ok ? temp_sum : kPoseDblMax;
-                const double scale = sh.acc + 1e-3;
-                sh.rho = (sh.current_chi - temp_chi) / scale;
-                const bool finite = temp_chi >= -kPoseDblMax && temp_chi <= kPoseDblMax;
-                if (sh.rho > 0.0 && finite) {
-                    const double v = 2.0 * sh.rho - 1.0;
-                    double alpha = 1.0 - (v * v) * v;
-                    alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-                    const double f = alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
-                    sh.lambda = sh.lambda * f;
-                    sh.ni = 2.0;
-                    sh.current_chi = temp_chi;
-                    sh.cur = 1 - sh.cur;                     // the tried estimates are kept
-                } else {
-                    sh.lambda = sh.lambda * sh.ni;
-                    sh.ni = sh.ni * 2.0;
-                    sh.rejected += 1;
-                }
-                sh.qmax += 1;
-                sh.go_on = (sh.rho < 0.0 && sh.qmax < kPoseMaxTries) ? 1 : 0;
+                lev_decide(sh, sh.ok != 0, temp_sum, sh.acc, [&sh] { sh.cur = 1 - sh.cur; }, [] {});   // kept: the tried estimates become the kept ones
                 if (!sh.go_on) {
                     sh.iterations += 1;
-                    sh.end = sh.qmax == kPoseMaxTries ? kPoseEndTries : sh.rho == 0.0 ? kPoseEndRhoZero : 0;
+                    sh.end = lev_end(sh);
                 }
             }
             par.barrier();
@@ -718,7 +699,7 @@ template <class P> __host__ __device__ __forceinline__ void la_solve(const LaArg
         par.barrier_g();
         if (tid == 0) {
             int32_t* ri = V.hdr() + kLaHInfo + 4 * round;
-            ri[0] = sh.iterations; ri[1] = sh.rejected; ri[2] = sh.drops; ri[3] = sh.end ? sh.end : sh.iterations ? kPoseEndIterations : 0;
+            ri[0] = sh.iterations; ri[1] = sh.rejected; ri[2] = sh.drops; ri[3] = sh.end ? sh.end : sh.iterations ? kLevEndIterations : 0;
             V.hd()[2 * round] = sh.current_chi; V.hd()[2 * round + 1] = sh.lambda;
             V.hdr()[kLaHCur] = sh.cur;
         }

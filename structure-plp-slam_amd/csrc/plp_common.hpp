@@ -97,6 +97,7 @@ public:
     template <class T> void in(const T*& p, size_t count) { parts_.push_back({&p, p, nullptr, p ? count * sizeof(T) : 0, 0}); }
     template <class T> void out(T*& p, size_t count, bool keep = true) { parts_.push_back({&p, keep ? p : nullptr, p, p ? count * sizeof(T) : 0, 0}); }
     template <class T> void room(T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }
+    template <class T> void room(DevBuf&, T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }   // a solver's *_rooms() (matcher_context.hpp): the slab serves, not the context's buffer
     plp_status upload() {
         size_t tot = 0;
         for (Part& p : parts_) { p.off = tot; tot += (p.bytes + 255) / 256 * 256; }

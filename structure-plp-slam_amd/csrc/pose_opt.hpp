@@ -1,7 +1,7 @@
 // optimize::pose_optimizer / pose_optimizer_extended_line (optimize/pose_optimizer.cc:53-229, pose_optimizer_extended_line.cc:62-305), one
 // definition of the arithmetic for host and device (plp_pose_optimize_* / plp_model_pose_*_host, include/plp_front.h):
-// the vertex (g2o::SE3Quat as shot_vertex holds it), the three edges, the Huber kernel, the 28 per-edge terms of the quadratic form, the 6 x 6
-// Cholesky and the Levenberg-Marquardt bookkeeping.  f64 with IEEE + - * / sqrt only, in the order written, floats where the reference holds
+// the vertex (g2o::SE3Quat as shot_vertex holds it), the three edges, the Huber kernel, the 28 per-edge terms of the quadratic form; the 6 x 6
+// Cholesky and the Levenberg-Marquardt bookkeeping are levenberg.hpp's.  f64 with IEEE + - * / sqrt only, in the order written, floats where the reference holds
 // floats; translation units that include this file are compiled with -ffp-contract=off.  sin / cos are pose_sincos() below, not a library's.
 //
 // Everything works on memory the caller names (PoseWork, the term rows): on the device that is LDS, reached with run-time indices, so that no
@@ -11,20 +11,16 @@
 #include <stdint.h>
 
 #include "../../include/plp_front.h"
+#include "levenberg.hpp"
 
 namespace plp {
 
 constexpr int kPoseMaxSlots = 8192;      // n_cap / l_cap limit of the entries (a rank fits 16 bits)
 constexpr int kPoseTerms = 28;           // per edge: H upper triangle row-major (21), b (6), robust chi2 (1)
-constexpr int kPoseMaxTries = 10;        // g2o's maxTrialsAfterFailure
 constexpr int kPoseMinObs = 5;           // :153 / :162, :218 / :264
 constexpr float kPoseChiSq2D = 5.99146f;
 constexpr float kPoseChiSq3D = 7.81473f;
 constexpr double kPoseNumericDelta = 1e-9;   // g2o's numeric Jacobian of a unary edge
-constexpr double kPoseDblMax = 1.7976931348623157e308;
-
-// why a trial's optimize() ended (out_trial_info[..][3]); 0 = the trial was not run
-enum { kPoseEndIterations = 1, kPoseEndTries = 2, kPoseEndRhoZero = 3 };
 
 // ---- sin and cos (D15 item 1): k = floor(x 2/pi + 1/2), r = (x - k P1) - k P2 (P1 = the first 33 bits of pi/2, so k P1 is exact for |k| < 2^20),
 // fdlibm's kernel polynomials on |r| <= pi/4 evaluated by Horner without fma, quadrant from k mod 4.  |x| > 2^20 or not finite: both NaN.
@@ -310,7 +306,7 @@ __host__ __device__ __forceinline__ double pose_line_terms(const double* est, co
     return chi2;
 }
 
-// ---- the 6 x 6 solve and the Levenberg-Marquardt state of one frame
+// ---- the Levenberg-Marquardt state of one frame (levenberg.hpp at N = 6)
 struct PoseWork {
     double est[7], bak[7];
     double pert[84];
@@ -321,87 +317,12 @@ struct PoseWork {
     int32_t ok2, qmax, iterations, rejected, go_on, end;
 };
 
-__host__ __device__ __forceinline__ int pose_h_index(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }   // i <= j
-
-// (H + lambda I) x = b by Cholesky; false = a pivot that is not positive and finite (x is then zero)
-__host__ __device__ __forceinline__ bool pose_chol6(const double* H21, const double* b, double lambda, double* Lf, double* y, double* x) {
-    for (int i = 0; i < 6; ++i) x[i] = 0.0;
-    for (int j = 0; j < 6; ++j) {
-        double s = H21[pose_h_index(j, j)] + lambda;
-        for (int k = 0; k < j; ++k) s = s - Lf[6 * j + k] * Lf[6 * j + k];
-        if (!(s > 0.0) || s > kPoseDblMax) return false;
-        const double d = __builtin_sqrt(s);
-        Lf[6 * j + j] = d;
-        for (int i = j + 1; i < 6; ++i) {
-            double v = H21[pose_h_index(j, i)];
-            for (int k = 0; k < j; ++k) v = v - Lf[6 * i + k] * Lf[6 * j + k];
-            Lf[6 * i + j] = v / d;
-        }
-    }
-    for (int i = 0; i < 6; ++i) {
-        double v = b[i];
-        for (int k = 0; k < i; ++k) v = v - Lf[6 * i + k] * y[k];
-        y[i] = v / Lf[6 * i + i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-        for (int k = i + 1; k < 6; ++k) v = v - Lf[6 * k + i] * x[k];
-        x[i] = v / Lf[6 * i + i];
-    }
-    return true;
-}
-
-// OptimizationAlgorithmLevenberg::solve after buildSystem: W.sum holds the linearisation at W.est
-__host__ __device__ __forceinline__ void pose_lm_begin(PoseWork& W, int iteration) {
-    W.current_chi = W.sum[27];
-    if (iteration == 0) {                       // computeLambdaInit: tau max |H_jj|
-        double m = 0.0;
-        for (int j = 0; j < 6; ++j) {
-            const double d = __builtin_fabs(W.sum[pose_h_index(j, j)]);
-            m = d > m ? d : m;
-        }
-        W.lambda = 1e-5 * m;
-        W.ni = 2.0;
-    }
-    W.qmax = 0;
-    W.rho = 0.0;
-}
 // push, solve, update: W.est becomes the tried estimate
 __host__ __device__ __forceinline__ void pose_lm_try(PoseWork& W) {
     for (int i = 0; i < 7; ++i) W.bak[i] = W.est[i];
-    W.ok2 = pose_chol6(W.sum, W.sum + 21, W.lambda, W.Lf, W.y, W.x) ? 1 : 0;
+    W.ok2 = lev_chol<6>(W.sum, W.sum + 21, W.lambda, W.Lf, W.y, W.x) ? 1 : 0;
     pose_oplus(W.x, W.bak, W.est);
 }
-// the decision after the errors at the tried estimate were summed to temp_sum; sets go_on (the do-while repeats)
-__host__ __device__ __forceinline__ void pose_lm_decide(PoseWork& W, double temp_sum) {
-    const double temp_chi = W.ok2 ? temp_sum : kPoseDblMax;
-    double scale = 0.0;
-    for (int j = 0; j < 6; ++j) scale = scale + W.x[j] * (W.lambda * W.x[j] + W.sum[21 + j]);
-    scale = scale + 1e-3;
-    W.rho = (W.current_chi - temp_chi) / scale;
-    const bool finite = temp_chi >= -kPoseDblMax && temp_chi <= kPoseDblMax;
-    if (W.rho > 0.0 && finite) {
-        const double v = 2.0 * W.rho - 1.0;
-        double alpha = 1.0 - (v * v) * v;
-        alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-        const double f = alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
-        W.lambda = W.lambda * f;
-        W.ni = 2.0;
-        W.current_chi = temp_chi;
-    } else {
-        W.lambda = W.lambda * W.ni;
-        W.ni = W.ni * 2.0;
-        for (int i = 0; i < 7; ++i) W.est[i] = W.bak[i];
-        W.rejected += 1;
-    }
-    W.qmax += 1;
-    W.go_on = (W.rho < 0.0 && W.qmax < kPoseMaxTries) ? 1 : 0;
-}
-// after the do-while: whether the iteration returns Terminate
-__host__ __device__ __forceinline__ int pose_lm_end(const PoseWork& W) {
-    return W.qmax == kPoseMaxTries ? kPoseEndTries : W.rho == 0.0 ? kPoseEndRhoZero : 0;
-}
-
 // whether trial `trial` of num_trials runs with the Huber kernels: they are removed after trial num_trials - 2 (unsigned: never for num_trials < 2)
 __host__ __device__ __forceinline__ bool pose_trial_robust(int trial, int num_trials) { return num_trials < 2 || trial <= num_trials - 2; }
 

@@ -214,15 +214,15 @@ __global__ __launch_bounds__(256) void k_pose_optimize(PoseArgs A) {
             if (lin) {
                 if (tid < kPoseTerms) W.sum[tid] = acc;
                 wg_barrier();
-                if (tid == 0) { pose_lm_begin(W, it); pose_lm_try(W); }
+                if (tid == 0) { lev_begin<6>(W, it); pose_lm_try(W); }
                 wg_barrier();
                 lin = false;
                 continue;
             }
             if (tid == 0) {
-                pose_lm_decide(W, acc);
+                lev_decide_vertex<6, 7>(W, acc);
                 if (W.go_on) pose_lm_try(W);
-                else { W.iterations += 1; W.end = pose_lm_end(W); }
+                else { W.iterations += 1; W.end = lev_end(W); }
             }
             wg_barrier();
             if (W.go_on) continue;
@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void k_pose_optimize(PoseArgs A) {
         if (tid == 0) {
             if (A.out_trial_info) {
                 int32_t* ti = A.out_trial_info + ((size_t)T * b + trial) * 4;
-                ti[0] = W.iterations; ti[1] = W.rejected; ti[2] = num_bad; ti[3] = W.end ? W.end : kPoseEndIterations;
+                ti[0] = W.iterations; ti[1] = W.rejected; ti[2] = num_bad; ti[3] = W.end ? W.end : kLevEndIterations;
             }
             if (A.out_trial_chi2) {
                 double* tc = A.out_trial_chi2 + ((size_t)T * b + trial) * 2;

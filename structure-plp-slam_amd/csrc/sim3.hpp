@@ -205,7 +205,7 @@ __host__ __device__ __forceinline__ void sim3_draw(uint64_t seed, int p, int ite
     }
 }
 
-// the camera fields reproject<MODEL> reads (set_camera, match_context.hip) and what every problem of a call shares
+// the camera fields reproject<MODEL> reads (set_camera, matcher_context.hpp) and what every problem of a call shares
 struct Sim3Args {
     int model;
     double fx, fy, cx, cy, fxb, cols_d, rows_d;

@@ -1,10 +1,9 @@
 // optimize::transform_optimizer::optimize (optimize/transform_optimizer.cc:47-197), one definition of the arithmetic for host and device
 // (plp_transform_optimize_* / plp_model_transform_*_host, include/plp_front.h): the vertex (g2o::Sim3 as
 // transform_vertex holds it), the forward and backward reprojection edges with g2o's numeric Jacobian, the 36 per-edge terms of the quadratic
-// form, the 7 x 7 Cholesky, the Levenberg-Marquardt bookkeeping and exp.  Everything D15 fixes is pose_opt.hpp's and is used from there: the
-// quaternion arithmetic, pose_sincos, Huber, the order of the operations.  The 7 x 7 solve and the LM state are copies of the 6 x 6 ones at
-// n = 7, so that pose_opt.hpp and the code compiled from it stay as they are.  Translation units that include this file are compiled with
-// -ffp-contract=off.
+// form and exp.  Everything D15 fixes is pose_opt.hpp's and is used from there: the quaternion arithmetic, pose_sincos, Huber, the order of
+// the operations.  The 7 x 7 Cholesky and the Levenberg-Marquardt bookkeeping are levenberg.hpp's at N = 7.  Translation units that include
+// this file are compiled with -ffp-contract=off.
 //
 // As in pose_opt.hpp everything works on memory the caller names (TfWork, the term rows): LDS on the device, the stack on the host.
 #pragma once
@@ -198,7 +197,7 @@ __host__ __device__ __forceinline__ double tf_edge_terms(const double* sims, con
     return chi2;
 }
 
-// ---- the 7 x 7 solve and the Levenberg-Marquardt state of one problem (pose_opt.hpp's at n = 7)
+// ---- the Levenberg-Marquardt state of one problem (levenberg.hpp at N = 7)
 struct TfWork {
     double est[8], bak[8];
     double sims[8 * kTfSims], invs[8 * kTfSims];   // of the last linearisation; entry 14 of both follows every tried estimate
@@ -209,56 +208,10 @@ struct TfWork {
     int32_t ok2, qmax, iterations, rejected, go_on, end;
 };
 
-__host__ __device__ __forceinline__ int tf_h_index(int i, int j) { return i * kTfDim - (i * (i - 1)) / 2 + (j - i); }   // i <= j
-
-// (H + lambda I) x = b by Cholesky; false = a pivot that is not positive and finite (x is then zero)
-__host__ __device__ __forceinline__ bool tf_chol7(const double* H28, const double* b, double lambda, double* Lf, double* y, double* x) {
-    const int n = kTfDim;
-    for (int i = 0; i < n; ++i) x[i] = 0.0;
-    for (int j = 0; j < n; ++j) {
-        double s = H28[tf_h_index(j, j)] + lambda;
-        for (int k = 0; k < j; ++k) s = s - Lf[n * j + k] * Lf[n * j + k];
-        if (!(s > 0.0) || s > kPoseDblMax) return false;
-        const double d = __builtin_sqrt(s);
-        Lf[n * j + j] = d;
-        for (int i = j + 1; i < n; ++i) {
-            double v = H28[tf_h_index(j, i)];
-            for (int k = 0; k < j; ++k) v = v - Lf[n * i + k] * Lf[n * j + k];
-            Lf[n * i + j] = v / d;
-        }
-    }
-    for (int i = 0; i < n; ++i) {
-        double v = b[i];
-        for (int k = 0; k < i; ++k) v = v - Lf[n * i + k] * y[k];
-        y[i] = v / Lf[n * i + i];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-        double v = y[i];
-        for (int k = i + 1; k < n; ++k) v = v - Lf[n * k + i] * x[k];
-        x[i] = v / Lf[n * i + i];
-    }
-    return true;
-}
-
-// OptimizationAlgorithmLevenberg::solve after buildSystem: W.sum holds the linearisation at W.est
-__host__ __device__ __forceinline__ void tf_lm_begin(TfWork& W, int iteration) {
-    W.current_chi = W.sum[35];
-    if (iteration == 0) {                       // computeLambdaInit: tau max |H_jj|
-        double m = 0.0;
-        for (int j = 0; j < kTfDim; ++j) {
-            const double d = __builtin_fabs(W.sum[tf_h_index(j, j)]);
-            m = d > m ? d : m;
-        }
-        W.lambda = 1e-5 * m;
-        W.ni = 2.0;
-    }
-    W.qmax = 0;
-    W.rho = 0.0;
-}
 // push and solve: W.x is the step to try from W.bak
 __host__ __device__ __forceinline__ void tf_lm_solve(TfWork& W) {
     for (int i = 0; i < 8; ++i) W.bak[i] = W.est[i];
-    W.ok2 = tf_chol7(W.sum, W.sum + 28, W.lambda, W.Lf, W.y, W.x) ? 1 : 0;
+    W.ok2 = lev_chol<kTfDim>(W.sum, W.sum + 28, W.lambda, W.Lf, W.y, W.x) ? 1 : 0;
 }
 // update: W.est becomes the tried estimate, entry 14 of sims / invs the tried estimate and its inverse
 // (the host build's: see tf_perturb)
@@ -267,36 +220,6 @@ __host__ __device__ __forceinline__ void tf_lm_update(TfWork& W, bool fix_scale)
     tf_inverse(W.sims + 8 * 14, W.invs + 8 * 14);
     for (int i = 0; i < 8; ++i) W.est[i] = W.sims[8 * 14 + i];
 }
-// the decision after the errors at the tried estimate were summed to temp_sum; sets go_on (the do-while repeats)
-__host__ __device__ __forceinline__ void tf_lm_decide(TfWork& W, double temp_sum) {
-    const double temp_chi = W.ok2 ? temp_sum : kPoseDblMax;
-    double scale = 0.0;
-    for (int j = 0; j < kTfDim; ++j) scale = scale + W.x[j] * (W.lambda * W.x[j] + W.sum[28 + j]);
-    scale = scale + 1e-3;
-    W.rho = (W.current_chi - temp_chi) / scale;
-    const bool finite = temp_chi >= -kPoseDblMax && temp_chi <= kPoseDblMax;
-    if (W.rho > 0.0 && finite) {
-        const double v = 2.0 * W.rho - 1.0;
-        double alpha = 1.0 - (v * v) * v;
-        alpha = alpha < 2.0 / 3.0 ? alpha : 2.0 / 3.0;
-        const double f = alpha > 1.0 / 3.0 ? alpha : 1.0 / 3.0;
-        W.lambda = W.lambda * f;
-        W.ni = 2.0;
-        W.current_chi = temp_chi;
-    } else {
-        W.lambda = W.lambda * W.ni;
-        W.ni = W.ni * 2.0;
-        for (int i = 0; i < 8; ++i) W.est[i] = W.bak[i];
-        W.rejected += 1;
-    }
-    W.qmax += 1;
-    W.go_on = (W.rho < 0.0 && W.qmax < kPoseMaxTries) ? 1 : 0;
-}
-// after the do-while: whether the iteration returns Terminate
-__host__ __device__ __forceinline__ int tf_lm_end(const TfWork& W) {
-    return W.qmax == kPoseMaxTries ? kPoseEndTries : W.rho == 0.0 ? kPoseEndRhoZero : 0;
-}
-
 // iterations of round `round` (0, 1)
 __host__ __device__ __forceinline__ int tf_round_iters(int round, int num_iter) { return round == 0 ? kTfFirstIters : num_iter; }
 // round 1 (:139-153): the match stays iff both chi2 are below chi_sq (a NaN drops it); round 2 (:176-183): it is dropped iff chi_sq is below one

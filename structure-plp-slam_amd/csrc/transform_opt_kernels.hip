@@ -188,10 +188,10 @@ __global__ __launch_bounds__(256) void k_transform_optimize(TfArgs A) {
                 wg_barrier();
             }
             if (tid == 0) {
-                if (lin) { tf_lm_begin(W, it); W.go_on = 1; }
-                else tf_lm_decide(W, acc);
+                if (lin) { lev_begin<kTfDim>(W, it); W.go_on = 1; }
+                else lev_decide_vertex<kTfDim, 8>(W, acc);
                 if (W.go_on) tf_lm_solve(W);
-                else { W.iterations += 1; W.end = tf_lm_end(W); }
+                else { W.iterations += 1; W.end = lev_end(W); }
             }
             wg_barrier();
             lin = false;
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(256) void k_transform_optimize(TfArgs A) {
         left -= drops;
         if (tid == 0) {
             int32_t* ri = A.ctx_n + kTfCtxInts * p + 3 + 4 * round;
-            ri[0] = W.iterations; ri[1] = W.rejected; ri[2] = drops; ri[3] = W.end ? W.end : kPoseEndIterations;
+            ri[0] = W.iterations; ri[1] = W.rejected; ri[2] = drops; ri[3] = W.end ? W.end : kLevEndIterations;
             double* rc = A.ctx_chi2 + 2 * (size_t)A.P * A.n_cap + kTfCtxDoubles * (size_t)p + 8 + 2 * round;
             rc[0] = W.current_chi; rc[1] = W.lambda;
         }

@@ -53,14 +53,14 @@ int main() {
     for (int it = 0; it < 5; ++it) {
         for (int i = 0; i < kTfSims; ++i) { tf_perturb(W->est, i, false, W->sims + 8 * i); tf_inverse(W->sims + 8 * i, W->invs + 8 * i); }
         pass(true, W->sum);
-        tf_lm_begin(*W, it);
+        lev_begin<kTfDim>(*W, it);
         do {
             tf_lm_solve(*W);
             tf_lm_update(*W, false);
             pass(false, sums.get());
-            tf_lm_decide(*W, sums[35]);
+            lev_decide_vertex<kTfDim, 8>(*W, sums[35]);
         } while (W->go_on);
-        if (tf_lm_end(*W)) break;
+        if (lev_end(*W)) break;
     }
     // the edge arguments of the pieces
     const double xs[] = {0.0, 700.0, -700.0, 700.5, -1e300, 1e-300, NAN, INFINITY, -INFINITY};
@@ -80,8 +80,8 @@ int main() {
     std::unique_ptr<double[]> H(new double[28]), b(new double[7]), Lf(new double[49]), y(new double[7]), x(new double[7]);
     for (int i = 0; i < 28; ++i) H[i] = 0.0;
     for (int i = 0; i < 7; ++i) b[i] = 1.0;
-    const bool ok0 = tf_chol7(H.get(), b.get(), 0.0, Lf.get(), y.get(), x.get());      // no information: fails
-    const bool ok1 = tf_chol7(H.get(), b.get(), 0.5, Lf.get(), y.get(), x.get());      // lambda alone: x = b / lambda
+    const bool ok0 = lev_chol<kTfDim>(H.get(), b.get(), 0.0, Lf.get(), y.get(), x.get());      // no information: fails
+    const bool ok1 = lev_chol<kTfDim>(H.get(), b.get(), 0.5, Lf.get(), y.get(), x.get());      // lambda alone: x = b / lambda
     const bool good = !ok0 && ok1 && std::fabs(x[6] - 2.0) < 1e-12 && acc == 5.0 && std::fabs(W->est[7] - st) < 1e-5 && std::fabs(W->est[4] - tt[0]) < 1e-5;
     std::printf("scale %.9f trans %.6f %.6f %.6f rejected %d, solves %d %d x6 %g, NaN of exp %g: %s\n", W->est[7], W->est[4], W->est[5], W->est[6], W->rejected,
                 (int)ok0, (int)ok1, x[6], acc, good ? "ok" : "FAILED");
