@@ -8,8 +8,9 @@
 //
 //   k_match_prep        per frame: free in-grid targets counting-sorted by (grid column, grid row, index) = the visiting
 //                       order of data::get_keypoints_in_cell (common.cc:241-313), 16-byte records + cell starts
-//   k_match_topk_cells  windowed modes, main path: 16 lanes per query walk the window's grid columns staged in LDS
-//                       (12-byte records), keep the K = 8 best by (distance, visiting order)
+//   k_match_topk_cells  windowed modes, main path: one lane per query walks the window's grid columns staged in LDS
+//                       (12-byte records), the wave fetches the found candidates' descriptors slot by slot; keeps the
+//                       K = 8 best by (distance, visiting order) and the next 8
 //   k_match_topk_lds    brute-force mode: the target descriptors staged in LDS, one wave per query
 //   k_match_topk        generic path (line modes, BoW / triangulation groups, frames beyond the LDS budget): one wave per
 //                       query scans all targets through candidate_key(); waves stride over a frame's queries
@@ -551,10 +552,11 @@ __global__ __launch_bounds__(256) void k_match_prep(MatchProblem P) {
     for (int i = tid; i <= ncell; i += 256) P.cell_start[(size_t)b * kCellStride + i] = start[min(i, 4096)];
 }
 
-// candidates a lane collects before it fetches their descriptors = descriptor fetches in flight per lane.  6: 97 VGPRs, one wave per SIMD beside
-// two region growers; 3: 72, two; 1: 54, three -- and alone the kernel is FASTER with one (the four matcher calls 3.84 -> 3.52 ms): its occupancy,
-// not its memory-level parallelism per lane, is what it runs on.  profiles/r03_scheduling_experiments.md
-constexpr int kLaneCand = 1;
+// k_match_topk_cells: candidate positions a lane holds (two per register) before its wave stops walking and fetches descriptors.  The wave stops as
+// soon as ONE lane is full, so no lane ever waits inside the walk; a lane with more candidates than this just makes the wave fetch once more.
+// Measured (profiles/r20_match_dense_gather.md, builds that still kept the walk's state in scratch): the four matcher calls 3.33 / 3.15 / 3.06 ms with
+// 2 / 4 / 8, against 3.17 ms for a fetch per candidate; 8 is four registers and the kernel stays at 60.  As built here: 2.34 ms.
+constexpr int kLanePend = 8;
 #define PLP_TOPK_CELLS_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 8)))
 
 // 16-lane (DPP row) reductions: four queries share a wave
@@ -574,13 +576,20 @@ __device__ __forceinline__ int row16_sum_i32(int v) {
 }
 
 // Main path of the point projection matchers.  The workgroup copies the frame's sorted targets (16 B each), their
-// stereo coordinates and the cell index into LDS once and reuses them for kQueriesPerBlock queries.  A query is served
-// by ONE lane, which walks the grid columns of its window (each column one contiguous range of the sorted array, so only the
-// window's cells are touched) and keeps its 8 best keys (distance << 16 | position in visiting order) in registers.  A window at
-// the low pyramid levels is 4-5 columns with about five candidates: the earlier 16-lanes-per-query version left two thirds of
-// its lanes idle and spent more instructions merging the lanes' lists (8 DPP row minima per query) than finding candidates.
+// stereo coordinates and the cell index into LDS once and reuses them for qpb queries.  A query is OWNED by one lane, which
+// keeps its 8 best keys (distance << 16 | position in visiting order) and the next 8 in registers; a wave serves 64 queries
+// per pass, in two phases that repeat until every lane has walked its whole window:
+//   walk    LDS only.  All lanes step together; a step opens the lane's next grid column (one contiguous range of the sorted array)
+//           or tests one position of the open column against the gates (level, margin, stereo) and keeps it if it passes.  It is
+//           ONE loop over the positions of all columns, so the wave runs as long as its longest lane, not the sum over columns of
+//           the longest range, and it ends when one lane holds kLanePend positions or no lane has a position left.
+//   fetch   slot by slot: every lane that has a position in slot j takes that target's index from the staged copy and its 32-byte
+//           descriptor from memory -- slot j + 1's gather is issued before slot j's key is used -- and inserts the key into its
+//           lists.  A wave makes one dependent memory round trip per slot in use, not one per walk iteration in which ANY lane
+//           found a candidate (139 per pass before, 39 now, at 7 candidates per query in the bench's last-frame call).
+// Keys are unique within a query, so both lists and the count depend on the candidate SET only, not on the order they are met in.
 // Consecutive queries sit on the same pyramid level (key points are stored by level), so the lanes of a wave run similar trip counts.
-// grid = (ceil(m_cap / kQueriesPerBlock), B), block = 256, dynamic LDS = n_cap * 20 + 2 * kCellStride bytes.
+// grid = (ceil(m_cap / qpb), B), block = 256, dynamic LDS = lds_targets * (12 or 16) + 2 * kCellStride bytes.
 __global__ PLP_TOPK_CELLS_BOUNDS void k_match_topk_cells(MatchProblem P, int qpb) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     unsigned uqb, ub;
@@ -602,7 +611,6 @@ __global__ PLP_TOPK_CELLS_BOUNDS void k_match_topk_cells(MatchProblem P, int qpb
     uint32_t* sto = reinterpret_cast<uint32_t*>(smem + (size_t)nb * 8);
     float* sxr = reinterpret_cast<float*>(smem + (size_t)nb * 12);
     uint16_t* cs = reinterpret_cast<uint16_t*>(smem + (size_t)nb * (has_xr ? 16 : 12));
-    __shared__ uint16_t s_cand[256 * kLaneCand];
     const uint4* g_sorted = reinterpret_cast<const uint4*>(P.sorted + (size_t)b * P.n_cap);   // {x, y, octave | cell, index}
     const float* g_sorted_xr = P.sorted_xr + (size_t)b * P.n_cap;
     {
@@ -637,73 +645,103 @@ __global__ PLP_TOPK_CELLS_BOUNDS void k_match_topk_cells(MatchProblem P, int qpb
     auto t_xr = [&](int i) -> float { return i < nb ? sxr_l[i] : g_sorted_xr[i]; };
     const uint8_t* q_valid = P.q_valid ? P.q_valid + (size_t)b * P.m_cap : nullptr;
     const int q_end = min(m, q_begin + qpb);
-    for (int q = q_begin + tid; q < q_end; q += 256) {
-        const bool active = !(q_valid && !q_valid[q]);
+    static_assert(kLanePend % 2 == 0, "two positions per register");
+    const int lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // Every lane of a wave stays in this loop, with or without a query of its own: the walk's end is decided by the wave.
+    for (int q_wave = q_begin + 64 * wv; q_wave < q_end; q_wave += 256) {
+        const int q = q_wave + lane;
+        const bool in_range = q < q_end;
+        const bool active = in_range && !(q_valid && !q_valid[q]);
         uint32_t top[kMatchK], ovf[kMatchK];   // the 8 best keys, and the next 8: what falls out of (or never reaches) the first list
 #pragma unroll
         for (int i = 0; i < kMatchK; ++i) { top[i] = 0xffffffffu; ovf[i] = 0xffffffffu; }
+        auto insert = [&](uint32_t key) {
+            if (key < top[kMatchK - 1]) {
+                const uint32_t out = top[kMatchK - 1];
+                top[kMatchK - 1] = key;
+#pragma unroll
+                for (int e = kMatchK - 1; e > 0; --e) { const uint32_t lo = min(top[e], top[e - 1]), hi = max(top[e], top[e - 1]); top[e - 1] = lo; top[e] = hi; }
+                key = out;
+            }
+            if (key < ovf[kMatchK - 1]) {
+                ovf[kMatchK - 1] = key;
+#pragma unroll
+                for (int e = kMatchK - 1; e > 0; --e) { const uint32_t lo = min(ovf[e], ovf[e - 1]), hi = max(ovf[e], ovf[e - 1]); ovf[e - 1] = lo; ovf[e] = hi; }
+            }
+        };
         int passed = 0;
+        // the walk's state: the next column to open, the open column's remaining range [i, i1).  A lane without a window starts finished.
+        // (cell bounds are at most 254 and a staged octave is 8 bits -- plan_match(), k_match_prep -- so the window is two registers: next column | last column << 8 |
+        // first row << 16 | last row << 24, and lowest level | highest level << 16, clamped to what an octave can be; "no upper bound" is 255)
+        float rx = 0.f, ry = 0.f, mg = 0.f, qxr = 0.f;
+        uint32_t win = 1u, lvls = 255u << 16;
+        int i = 0, i1 = 0;
+        uint4 q0 = make_uint4(0u, 0u, 0u, 0u), q1 = q0;
         if (active) {
             const QueryCtx c = make_query(P, q, b, s_dir);
             if (!c.empty) {
                 const uint4* qd = reinterpret_cast<const uint4*>(P.q_desc + ((size_t)b * P.q_desc_stride + q) * 32);
-                const uint4 q0 = qd[0], q1 = qd[1];
-                const bool check_level = (0 < c.min_level) || (0 <= c.max_level);
-                // Two phases so that the descriptor gathers of a lane are in flight together: (1) walk the column
-                // ranges and note the positions that pass the geometric tests (up to kLaneCand in an LDS slot of this
-                // thread), (2) fetch their descriptors, (3) distances and the best-8 insertion.  A lane that finds more
-                // candidates drains its slot and goes on.
-                uint16_t* my = s_cand + tid * kLaneCand;
-                int nc = 0;
-                auto drain = [&]() {
-                    uint4 d0[kLaneCand], d1[kLaneCand];
-#pragma unroll
-                    for (int k = 0; k < kLaneCand; ++k)
-                        if (k < nc) {
-                            const uint4* d = reinterpret_cast<const uint4*>(t_desc + 32 * (size_t)(t_to(my[k]) & 0xffffu));
-                            d0[k] = d[0]; d1[k] = d[1];
-                        }
-#pragma unroll
-                    for (int k = 0; k < kLaneCand; ++k)
-                        if (k < nc) {
-                            uint32_t key = (hamming256(q0, q1, d0[k], d1[k]) << 16) | (uint32_t)my[k];
-                            if (key < top[kMatchK - 1]) {
-                                const uint32_t out = top[kMatchK - 1];
-                                top[kMatchK - 1] = key;
-#pragma unroll
-                                for (int e = kMatchK - 1; e > 0; --e) { const uint32_t lo = min(top[e], top[e - 1]), hi = max(top[e], top[e - 1]); top[e - 1] = lo; top[e] = hi; }
-                                key = out;
-                            }
-                            if (key < ovf[kMatchK - 1]) {
-                                ovf[kMatchK - 1] = key;
-#pragma unroll
-                                for (int e = kMatchK - 1; e > 0; --e) { const uint32_t lo = min(ovf[e], ovf[e - 1]), hi = max(ovf[e], ovf[e - 1]); ovf[e - 1] = lo; ovf[e] = hi; }
-                            }
-                        }
-                    passed += nc;
-                    nc = 0;
-                };
-                for (int col = c.min_cx; col <= c.max_cx; ++col) {
-                    const int i0 = cs[col * rows + c.min_cy], i1 = cs[col * rows + c.max_cy + 1];
-                    for (int i = i0; i < i1; ++i) {
-                        const float2 sp = t_xy(i);
-                        if (check_level) {
-                            const int oct = (int)(t_to(i) >> 16);
-                            if (oct < c.min_level) continue;
-                            if (0 <= c.max_level && c.max_level < oct) continue;
-                        }
-                        if (!(fabsf(__fsub_rn(sp.x, c.rx)) < c.mg && fabsf(__fsub_rn(sp.y, c.ry)) < c.mg)) continue;
-                        if (has_xr) {
-                            const float xr = t_xr(i);
-                            if (0 < xr && c.mg < fabsf(__fsub_rn(c.xr, xr))) continue;
-                        }
-                        my[nc++] = (uint16_t)i;
-                        if (nc == kLaneCand) drain();
-                    }
-                }
-                drain();
+                q0 = qd[0]; q1 = qd[1];
+                rx = c.rx; ry = c.ry; mg = c.mg; qxr = c.xr;
+                win = (uint32_t)c.min_cx | ((uint32_t)c.max_cx << 8) | ((uint32_t)c.min_cy << 16) | ((uint32_t)c.max_cy << 24);
+                lvls = (uint32_t)min(max(c.min_level, 0), 256) | ((c.max_level < 0 ? 255u : (uint32_t)min(c.max_level, 255)) << 16);
             }
         }
+        bool wave_more;
+        do {
+            // walk: until this lane holds kLanePend positions or has no position left
+            uint32_t pend[kLanePend / 2];
+#pragma unroll
+            for (int k = 0; k < kLanePend / 2; ++k) pend[k] = 0u;
+            int nc = 0;
+            // all lanes step together until one of them is full or none has a position left: no lane waits for another inside the walk
+            for (;;) {
+                if (i >= i1) {   // open the next column
+                    const int col = (int)(win & 0xffu);
+                    if (col <= (int)((win >> 8) & 0xffu)) {
+                        i = cs[col * rows + (int)((win >> 16) & 0xffu)]; i1 = cs[col * rows + (int)(win >> 24) + 1];
+                        ++win;   // (a last column of 254 at most: no carry)
+                    }
+                } else {         // test one position
+                    const int p = i++;
+                    const float2 sp = t_xy(p);
+                    const uint32_t oct = t_to(p) >> 16;
+                    bool ok = (lvls & 0xffffu) <= oct && oct <= (lvls >> 16) && fabsf(__fsub_rn(sp.x, rx)) < mg && fabsf(__fsub_rn(sp.y, ry)) < mg;
+                    if (ok && has_xr) {
+                        const float xr = t_xr(p);
+                        ok = !(0 < xr && mg < fabsf(__fsub_rn(qxr, xr)));
+                    }
+                    if (ok) {
+                        const uint32_t v = (uint32_t)p << (16 * (nc & 1));
+#pragma unroll
+                        for (int k = 0; k < kLanePend / 2; ++k) pend[k] |= (nc >> 1) == k ? v : 0u;
+                        ++nc;
+                    }
+                }
+                wave_more = __builtin_amdgcn_ballot_w64(i < i1 || (win & 0xffu) <= ((win >> 8) & 0xffu)) != 0ull;
+                if (!wave_more || __builtin_amdgcn_ballot_w64(nc == kLanePend) != 0ull) break;
+            }
+            // fetch + insert: slot by slot, every lane its own candidate; the next slot's gather is issued before this slot's key is used
+            auto slot_pos = [&](int j) -> int { return (int)((pend[j >> 1] >> (16 * (j & 1))) & 0xffffu); };
+            auto gather = [&](int j, uint4& a0, uint4& a1) {
+                if (j < nc) {
+                    const uint4* d = reinterpret_cast<const uint4*>(t_desc + 32 * (size_t)(t_to(slot_pos(j)) & 0xffffu));
+                    a0 = d[0]; a1 = d[1];
+                }
+            };
+            uint4 a0 = make_uint4(0u, 0u, 0u, 0u), a1 = a0;
+            gather(0, a0, a1);
+#pragma unroll
+            for (int j = 0; j < kLanePend; ++j) {
+                if (__builtin_amdgcn_ballot_w64(j < nc) == 0ull) break;
+                uint4 b0 = a0, b1 = a1;
+                if (j + 1 < kLanePend) gather(j + 1, b0, b1);
+                if (j < nc) insert((hamming256(q0, q1, a0, a1) << 16) | (uint32_t)slot_pos(j));
+                a0 = b0; a1 = b1;
+            }
+            passed += nc;
+        } while (wave_more);
+        if (!in_range) continue;
         uint32_t e[kMatchK];
 #pragma unroll
         for (int k = 0; k < kMatchK; ++k) {
