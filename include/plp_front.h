@@ -1101,6 +1101,128 @@ plp_status plp_color_vote_device(plp_matcher* ctx, const uint8_t* d_mask, int32_
                                  size_t mask_frame_stride, const plp_keypoint* d_undist, const uint8_t* d_valid, const int32_t* d_counts,
                                  int32_t cap, int32_t B, int32_t check_3x3_window, int32_t* d_labels, void* hip_stream);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Plane fitting: Planar_Mapping_module's RANSAC (src/PLPSLAM/planar_mapping_module.cc) for P planes at once.  `mode` selects
+ *   PLP_PLANE_CREATE  estimate_plane_sequential_RANSAC (:412-591) with the gate in front of it in create_new_plane (:359)
+ *   PLP_PLANE_UPDATE  update_plane_via_RANSAC (:593-733)
+ * estimate_plane_sequential_Graph_cut_RANSAC (:1006-) needs a third-party library and is not offered.
+ * Numeric contract: DESIGN.md section 5, D19 (slot order, the samples, estimate_plane_SVD as a written-down algorithm, the shape of
+ * every sum), reformulation: DESIGN.md section 4.
+ *
+ * A plane's landmarks are given in slot form, [P][n_cap]; a slot is one entry of plane->get_landmarks() (`lms`), counts[p] = lms.size():
+ *   pos_w   get_pos_in_world()
+ *   flags   bit 0 (PLP_PLANE_LM_ERASED) will_be_erased(), bit 1 (PLP_PLANE_LM_OWNED) get_Owning_Plane() != nullptr; these read objects:
+ *           the caller computes the byte
+ * A slot is eligible for a sample when it is not erased (CREATE, :452) or not erased and owned (UPDATE, :623-628); a sample index is a
+ * RANK among the eligible slots in slot order.  A hypothesis has m samples, with replacement: points_per_ransac (CREATE) or the smallest
+ * m with !((double)m < (double)counts[p] * 0.8) (UPDATE, :620).  samples == NULL: rank k of iteration i is drawn from `seed` (D19 item 2;
+ * plp_model_plane_draw_host).  A caller's rank outside [0, n_eligible) makes the hypothesis's residual DBL_MAX and its equation 0, and
+ * its refit is not tried.
+ * Every iteration computes [1] the fit of its samples, [2] the non-erased slots closer to it than dist_thresh[p], [3] -- when the gate
+ * holds (CREATE: inlier_ratio > inliers_ratio_thr && inliers >= points_per_ransac, inlier_ratio = double(inliers) / double(counts[p]);
+ * UPDATE: inliers >= points_per_ransac) -- the fit of those inliers and its error.  The loop over them is the reference's, literally:
+ * best_error = min(best_error, residual) BEFORE `error < best_error` is tested; the plane gets every iteration's sample fit
+ * unconditionally and its refit when accepted; CREATE breaks on error < error_thresh[p], UPDATE never.  So the plane ends with the
+ * equation of the LAST iteration that ran, and step [4] keeps the slots of best_inliers_list that are closer than dist_thresh[p] to THAT.
+ * Outputs per problem (the plane's state as the function leaves it):
+ *   out_status       a plp_plane_status
+ *   out_flags        PLP_PLANE_FLAG_INVALID: set_invalid() was called (:604, :724); PLP_PLANE_FLAG_NEED_REFINEMENT: set_need_refinement()
+ *                    (:700); PLP_PLANE_FLAG_GATED: create_new_plane dropped the plane at :359
+ *   out_equation[4] / out_best_error   get_equation() / get_best_error().  Where the function returns before its loop (TOO_FEW_POINTS,
+ *                    NO_ELIGIBLE) they are equation_in / best_error_in (UPDATE) or keep the caller's values (CREATE)
+ *   out_best_iter    the iteration whose inlier list is best_inliers_list, -1 when !best_found;  out_last_iter  the last that ran (-1: none)
+ *   out_num_inliers / out_inliers [P][n_cap]   step [4]: plane_best_inlier_map_points.size() and its membership byte per slot, where step
+ *                    [4] ran (OK, TOO_FEW_LEFT), else 0; slots at or above counts[p] keep the caller's values
+ *   out_hyp_residual / out_hyp_inliers / out_hyp_error   optional, [P][iters]: every hypothesis's residual, inliers_list.size() and refit
+ *                    error (DBL_MAX where the refit was not tried), whether or not the loop reached it; 0 / 0 / DBL_MAX where the function
+ *                    returned before its loop */
+typedef enum plp_plane_mode { PLP_PLANE_CREATE = 0, PLP_PLANE_UPDATE = 1 } plp_plane_mode;
+typedef enum plp_plane_status {
+    PLP_PLANE_OK = 0,
+    PLP_PLANE_TOO_FEW_POINTS = 1,         /* :359 (with PLP_PLANE_FLAG_GATED), :423-436, :597-606 */
+    PLP_PLANE_NO_ELIGIBLE = 2,            /* no slot may be sampled: the reference's while loop (:449, :620) would not end */
+    PLP_PLANE_NOT_FOUND = 3,              /* !best_found                                                       :545, :698 */
+    PLP_PLANE_ERROR_ABOVE_THRESHOLD = 4,  /* best_error > _final_error_thresh                                  :554, :698 */
+    PLP_PLANE_TOO_FEW_LEFT = 5            /* UPDATE: step [4] kept fewer than points_per_ransac                       :722 */
+} plp_plane_status;
+enum { PLP_PLANE_LM_ERASED = 1, PLP_PLANE_LM_OWNED = 2 };
+enum { PLP_PLANE_FLAG_INVALID = 1, PLP_PLANE_FLAG_NEED_REFINEMENT = 2, PLP_PLANE_FLAG_GATED = 4 };
+typedef struct plp_plane_ransac_args {
+    int32_t mode;                      /* a plp_plane_mode */
+    int32_t P, n_cap;                  /* P >= 0 planes of n_cap >= 0 slots, n_cap <= 8192, P <= 65535 */
+    int32_t points_per_ransac;         /* POINTS_PER_RANSAC, >= 1 */
+    int32_t min_points_before_ransac;  /* MIN_NUMBER_POINTS_BEFORE_RANSAC (:359), >= 0; CREATE */
+    int32_t iters;                     /* _iterationsCount, 1 .. 1024 */
+    double inliers_ratio_thr;          /* _inliers_ratio_thr (:498); CREATE */
+    uint64_t seed;                     /* samples == NULL: the generator's seed */
+    int32_t m_cap;                     /* samples != NULL: ranks per hypothesis in `samples`; at least the largest m a problem can have:
+                                          points_per_ransac (CREATE), the m of n_cap (UPDATE) */
+    const int32_t* counts;             /* P: lms.size(), or NULL = n_cap everywhere */
+    const double* pos_w;               /* P x n_cap x 3 */
+    const uint8_t* flags;              /* P x n_cap: PLP_PLANE_LM_* */
+    const double* dist_thresh;         /* P: _planar_distance_thresh */
+    const double* error_thresh;        /* P: _final_error_thresh */
+    const double* best_error_in;       /* P: plane->get_best_error() before the call (:609); UPDATE */
+    const double* equation_in;         /* P x 4: the plane's equation before the call; UPDATE */
+    const int32_t* samples;            /* P x iters x m_cap ranks, or NULL = drawn from seed */
+    uint8_t* out_status;               /* P */
+    uint8_t* out_flags;                /* P */
+    double* out_equation;              /* P x 4 */
+    double* out_best_error;            /* P */
+    int32_t* out_best_iter;            /* P */
+    int32_t* out_last_iter;            /* P */
+    int32_t* out_num_inliers;          /* P */
+    uint8_t* out_inliers;              /* P x n_cap */
+    double* out_hyp_residual;          /* P x iters, or NULL */
+    int32_t* out_hyp_inliers;          /* P x iters, or NULL */
+    double* out_hyp_error;             /* P x iters, or NULL */
+} plp_plane_ransac_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; an unknown mode; P < 0, n_cap < 0, iters < 1,
+ * points_per_ransac < 1, min_points_before_ransac < 0; samples != NULL with m_cap below the largest m; and -- when P > 0 and n_cap > 0 -- a
+ * NULL pos_w, flags, dist_thresh, error_thresh, (UPDATE) best_error_in, equation_in, or a NULL required output (out_status .. out_inliers).
+ * n_cap > 8192, P > 65535 or iters > 1024: PLP_ERR_UNSUPPORTED.  P == 0 or n_cap == 0: PLP_OK, nothing written.
+ * _device: every array a DEVICE pointer (the thresholds too: one derived from plp_median_depth_device needs no host round trip); two
+ * kernels on hip_stream, no host synchronisation; bad samples are never an error.  The kernels hand the hypotheses to one another through
+ * a buffer the context owns (12 doubles per hypothesis), so the calls of one context must be ordered on the device: one stream, or events
+ * between streams.  _host: HOST pointers, staged (the outputs too, so that every slot the kernels do not write keeps the caller's value),
+ * the same kernels, synchronous. */
+plp_status plp_plane_ransac_device(plp_matcher* ctx, const plp_plane_ransac_args* args, void* hip_stream);
+plp_status plp_plane_ransac_host(plp_matcher* ctx, const plp_plane_ransac_args* args);
+/* Host builds of the same source (csrc/plane_fit.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_plane_ransac_host: the entry above, one problem, one hypothesis and one partial sum after the other; the same checks.
+ * Returns P, or -1 for a bad argument (plp_last_error() names it).
+ * plp_model_plane_fit_host: estimate_plane_SVD (:735-771, D19 item 3) for n index lists into one point table pos_w (n_points x 3): list l
+ * is indices[offsets[l] .. offsets[l+1]).  out_equation n x 4, out_residual n, out_sweeps n (may be NULL: the Jacobi sweeps that rotated).
+ * An empty list or an index outside [0, n_points) gives equation 0 and residual DBL_MAX.  Returns n, or -1.
+ * plp_model_plane_draw_host: the ranks the entries draw for problem p, iterations iter0 .. iter0 + n_iters - 1, m per iteration, among
+ * n_eligible >= 1 eligible slots: out n_iters x m.  Returns n_iters, or -1. */
+int32_t plp_model_plane_ransac_host(const plp_plane_ransac_args* args);
+int32_t plp_model_plane_fit_host(const double* pos_w, int32_t n_points, const int32_t* indices, const int32_t* offsets, int32_t n,
+                                 double* out_equation, double* out_residual, int32_t* out_sweeps);
+int32_t plp_model_plane_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t m, int32_t n_eligible, int32_t* out);
+
+/* Planar_Mapping_module::refine_points (:954-1004) over a landmark list: landmark i of plane row lm_plane[i] (-1: none) is skipped when
+ * the plane is not active (active[pl] == 0: !is_valid() || need_refinement() || get_num_landmarks() < POINTS_PER_RANSAC, :960-962; the
+ * caller computes the byte), when it is erased or not owned (flags as above, :970); else dist_old = calculate_distance(pos_w) -- already
+ * a fabs -- and, when it is > 0, pos_w - normalized(n) * dist_old replaces pos_w if its distance is < dist_thresh[0] and < dist_old
+ * (:977-989; a point on the negative side moves away and is rejected).  Operation order: D19.  out_changed[i] = 1 where pos_w[i] was
+ * written, else 0 (every i < M is written).  M == 0: PLP_OK, nothing written.  PLP_ERR_INVALID_ARG: NULL ctx / args, M < 0, NP < 0, or
+ * -- when M > 0 -- a NULL pos_w, lm_plane, flags, dist_thresh, out_changed, or (NP > 0) equation, active.
+ * _device: DEVICE pointers, one kernel, asynchronous; _host: HOST pointers, staged, synchronous; plp_model_*: the host build. */
+typedef struct plp_plane_refine_args {
+    int32_t M, NP;
+    double* pos_w;                     /* M x 3, updated in place */
+    const int32_t* lm_plane;           /* M */
+    const uint8_t* flags;              /* M: PLP_PLANE_LM_* */
+    const double* equation;            /* NP x 4 */
+    const uint8_t* active;             /* NP */
+    const double* dist_thresh;         /* 1: _planar_distance_thresh */
+    uint8_t* out_changed;              /* M */
+} plp_plane_refine_args;
+plp_status plp_plane_refine_points_device(plp_matcher* ctx, const plp_plane_refine_args* args, void* hip_stream);
+plp_status plp_plane_refine_points_host(plp_matcher* ctx, const plp_plane_refine_args* args);
+int32_t plp_model_plane_refine_points_host(const plp_plane_refine_args* args);
+
 /* Bag-of-words transform: data::frame::compute_bow / data::keyframe::compute_bow
  * (src/PLPSLAM/data/frame.cc:785-795) = bow_vocab_->transform(to_desc_vec(descriptors_), bow_vec_, bow_feat_vec_, 4) of
  * DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (data/bow_vocabulary.h:22; the USE_DBOW2 build).  DBoW2 and the

@@ -192,6 +192,14 @@ _API = [
     ("plp_replay_point_queries_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_pack_rows_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     ("plp_replay_line_queries_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_plane_ransac_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_plane_ransac_host", C.c_int, [_VP, _VP]),
+    ("plp_model_plane_ransac_host", _I32, [_VP]),
+    ("plp_model_plane_fit_host", _I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP]),
+    ("plp_model_plane_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _I32, _VP]),
+    ("plp_plane_refine_points_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_plane_refine_points_host", C.c_int, [_VP, _VP]),
+    ("plp_model_plane_refine_points_host", _I32, [_VP]),
 ]
 
 
@@ -475,6 +483,171 @@ class sim3_solver:
     def get_inliers(self):
         """the inlier flags of the best hypothesis per key point of key frame 1 (not in the reference's surface: count_inliers' vector)"""
         return self._r["inliers"][0].astype(bool)
+
+
+# plp_plane_mode, plp_plane_status, the landmark byte and out_flags of plp_plane_ransac_* (include/plp_front.h)
+PLANE_CREATE, PLANE_UPDATE = range(2)
+PLANE_OK, PLANE_TOO_FEW_POINTS, PLANE_NO_ELIGIBLE, PLANE_NOT_FOUND, PLANE_ERROR_ABOVE_THRESHOLD, PLANE_TOO_FEW_LEFT = range(6)
+PLANE_LM_ERASED, PLANE_LM_OWNED = 1, 2
+PLANE_FLAG_INVALID, PLANE_FLAG_NEED_REFINEMENT, PLANE_FLAG_GATED = 1, 2, 4
+# the outputs of plp_plane_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
+PLANE_RANSAC_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), flags=(lambda M, I: (), np.uint8, False),
+                            equation=(lambda M, I: (4,), np.float64, False), best_error=(lambda M, I: (), np.float64, False),
+                            best_iter=(lambda M, I: (), np.int32, False), last_iter=(lambda M, I: (), np.int32, False),
+                            num_inliers=(lambda M, I: (), np.int32, False), inliers=(lambda M, I: (M,), np.uint8, False),
+                            hyp_residual=(lambda M, I: (I,), np.float64, True), hyp_inliers=(lambda M, I: (I,), np.int32, True),
+                            hyp_error=(lambda M, I: (I,), np.float64, True))
+
+
+def plane_sample_size(mode, n, points_per_ransac):
+    """the samples of one hypothesis: POINTS_PER_RANSAC (CREATE), the smallest m with !(m < n * 0.8) (UPDATE, planar_mapping_module.cc:620)"""
+    if int(mode) == PLANE_CREATE:
+        return int(points_per_ransac)
+    m = int(float(n) * 0.8)
+    while float(m) < float(n) * 0.8:
+        m += 1
+    return m
+
+
+def _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac, min_points_before_ransac, iters, inliers_ratio_thr,
+                       best_error_in, equation_in, samples, seed, counts, outputs, out):
+    """the numpy side of plp_plane_ransac_host and plp_model_plane_ransac_host: call(args struct) runs the entry"""
+    fl = np.ascontiguousarray(flags, np.uint8)
+    if fl.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "flags must be (P, n_cap)")
+    P_, M = fl.shape
+    pw = np.ascontiguousarray(pos_w, np.float64).reshape(P_, M, 3)
+    vec = lambda v, w=(): None if v is None else np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (P_,) + w))
+    dt_, et_, be, eq = vec(dist_thresh), vec(error_thresh), vec(best_error_in), vec(equation_in, (4,))
+    I = int(iters)
+    sm = None if samples is None else np.ascontiguousarray(samples, np.int32)
+    if sm is not None and (sm.ndim != 3 or sm.shape[:2] != (P_, I)):
+        raise PlpError(PLP_ERR_INVALID_ARG, "samples must be (P, iters, m_cap)")
+    cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
+    o = {}
+    for k, (shape, dt, optional) in PLANE_RANSAC_OUTPUTS.items():   # the caller's arrays are the outputs when given (what the library does not write keeps its value)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (P_,) + shape(M, max(I, 0))
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(plane_ransac_args_c, dict(mode=int(mode), P=P_, n_cap=M, points_per_ransac=int(points_per_ransac),
+                                          min_points_before_ransac=int(min_points_before_ransac), iters=I, inliers_ratio_thr=float(inliers_ratio_thr),
+                                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=0 if sm is None else sm.shape[2]), dict(
+        counts=Pt(cn), pos_w=Pt(pw), flags=Pt(fl), dist_thresh=Pt(dt_), error_thresh=Pt(et_), best_error_in=Pt(be), equation_in=Pt(eq), samples=Pt(sm),
+        **{"out_" + k: Pt(o.get(k)) for k in PLANE_RANSAC_OUTPUTS}))
+    call(a)
+    return o
+
+
+def model_plane_ransac(mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac=18, min_points_before_ransac=12, iters=50, inliers_ratio_thr=0.7,
+                       best_error_in=None, equation_in=None, samples=None, seed=0, counts=None, outputs=None, out=None):
+    """Host build of Planar_Mapping_module's RANSAC (csrc/plane_fit.hpp; no GPU needed): the arguments and the result
+    of matcher.plane_ransac."""
+    def call(a):
+        if lib().plp_model_plane_ransac_host(C.byref(a)) != a.P:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac, min_points_before_ransac, iters, inliers_ratio_thr,
+                              best_error_in, equation_in, samples, seed, counts, outputs, out)
+
+
+def model_plane_fit(pos_w, lists):
+    """Host build of estimate_plane_SVD (planar_mapping_module.cc:735-771 as D19 item 3 writes it down; no GPU needed).  pos_w: (n_points, 3) f64,
+    lists: index lists into it.  Returns (equation (n, 4), residual (n,), sweeps (n,) i32: the Jacobi sweeps that rotated)."""
+    pw = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3)
+    lists = [np.asarray(l, np.int32).reshape(-1) for l in lists]
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(l) for l in lists])
+    idx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
+    n = len(lists)
+    eq = np.zeros((n, 4)); res = np.zeros(n); sw = np.zeros(n, np.int32)
+    Pt = lambda v: v.ctypes.data if v.size else None
+    if lib().plp_model_plane_fit_host(Pt(pw), len(pw), Pt(idx), Pt(off), n, Pt(eq), Pt(res), Pt(sw)) != n:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_plane_fit_host")
+    return eq, res, sw
+
+
+def model_plane_draw(seed, p, iters, m, n_eligible, iter0=0):
+    """The ranks plp_plane_ransac_* draw for problem p when the caller passes none (D19 item 2; no GPU needed): (iters, m) i32"""
+    out = np.zeros((int(iters), int(m)), np.int32)
+    if lib().plp_model_plane_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(m), int(n_eligible),
+                                       out.ctypes.data if out.size else None) != int(iters):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_plane_draw_host: n_eligible must be at least 1")
+    return out
+
+
+def _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh):
+    """the numpy side of plp_plane_refine_points_host and its host build; returns (pos_w (M, 3), the new positions, changed (M,) u8)"""
+    pw = np.array(pos_w, np.float64, order="C").reshape(-1, 3)
+    M = len(pw)
+    lp = np.ascontiguousarray(lm_plane, np.int32).reshape(M); fl = np.ascontiguousarray(flags, np.uint8).reshape(M)
+    eq = np.ascontiguousarray(equation, np.float64).reshape(-1, 4); ac = np.ascontiguousarray(active, np.uint8).reshape(len(eq))
+    th = np.array([dist_thresh], np.float64)
+    ch = np.zeros(M, np.uint8)
+    Pt = lambda v: v.ctypes.data if v.size else None
+    call(_struct(plane_refine_args_c, dict(M=M, NP=len(eq)), dict(pos_w=Pt(pw), lm_plane=Pt(lp), flags=Pt(fl), equation=Pt(eq), active=Pt(ac),
+                                                                  dist_thresh=Pt(th), out_changed=Pt(ch))))
+    return pw, ch
+
+
+def model_plane_refine_points(pos_w, lm_plane, flags, equation, active, dist_thresh):
+    """Host build of Planar_Mapping_module::refine_points (csrc/plane_fit.hpp, D19; no GPU needed): the arguments and result of
+    matcher.plane_refine_points."""
+    def call(a):
+        if lib().plp_model_plane_refine_points_host(C.byref(a)) != a.M:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh)
+
+
+class planar_mapper:
+    """Mirror of Planar_Mapping_module's plane fitting (planar_mapping_module.h) under the yaml's names: cfg maps "Threshold.iterationsCount",
+    "Threshold.inliers_ratio_thr", "Threshold.min_number_points_before_ransac", "Threshold.point_per_ransac", "Threshold.plane_distance_correction"
+    and "Threshold.final_error_correction" (load_configuration, :1162-1184; "Threshold.use_graph_cut" must be absent or false: that estimator
+    needs a third-party library and is not offered).  mt: a matcher (the GPU entry), or None = the host build.  A plane is its landmark list:
+    pos_w (n, 3), flags (n,) PLANE_LM_* bytes."""
+
+    def __init__(self, cfg, mt=None, seed=0):
+        if cfg.get("Threshold.use_graph_cut", False):
+            raise PlpError(PLP_ERR_UNSUPPORTED, "Threshold.use_graph_cut: estimate_plane_sequential_Graph_cut_RANSAC is not offered")
+        self._iters = int(cfg["Threshold.iterationsCount"])
+        self._ratio = float(cfg["Threshold.inliers_ratio_thr"])
+        self._min_points = int(cfg["Threshold.min_number_points_before_ransac"])
+        self._ppr = int(cfg["Threshold.point_per_ransac"])
+        self._dist_corr = float(cfg["Threshold.plane_distance_correction"])
+        self._err_corr = float(cfg["Threshold.final_error_correction"])
+        self._mt, self._seed = mt, seed
+        self.set_map_scale(1.0)
+
+    def set_map_scale(self, map_scale):
+        """estimate_map_scale (:130-183): _planar_distance_thresh and _final_error_thresh follow the scale"""
+        self._map_scale = float(map_scale)
+        self.planar_distance_thresh = self._dist_corr * self._map_scale
+        self.final_error_thresh = self._err_corr * self._map_scale
+
+    def _run(self, mode, pos_w, flags, samples, **kw):
+        fl = np.asarray(flags, np.uint8).reshape(1, -1)
+        fn = model_plane_ransac if self._mt is None else self._mt.plane_ransac
+        r = fn(mode, np.asarray(pos_w, np.float64).reshape(1, fl.shape[1], 3), fl, self.planar_distance_thresh, self.final_error_thresh,
+               points_per_ransac=self._ppr, min_points_before_ransac=self._min_points, iters=self._iters, inliers_ratio_thr=self._ratio,
+               samples=None if samples is None else np.asarray(samples, np.int32)[None], seed=self._seed, **kw)
+        return {k: v[0] for k, v in r.items()}
+
+    def estimate_plane_sequential_RANSAC(self, pos_w, flags, samples=None):
+        """create_new_plane's gate (:359) and estimate_plane_sequential_RANSAC (:412-591): the outputs of one problem; it returned true where
+        status == PLANE_OK"""
+        return self._run(PLANE_CREATE, pos_w, flags, samples)
+
+    def update_plane_via_RANSAC(self, pos_w, flags, equation, best_error, samples=None):
+        """update_plane_via_RANSAC (:593-733) of a plane with this equation and best error"""
+        return self._run(PLANE_UPDATE, pos_w, flags, samples, equation_in=np.asarray(equation, np.float64).reshape(1, 4), best_error_in=[best_error])
+
+    def refine_points(self, pos_w, lm_plane, flags, equation, active):
+        """refine_points (:954-1004): (the new pos_w, changed)"""
+        fn = model_plane_refine_points if self._mt is None else self._mt.plane_refine_points
+        return fn(pos_w, lm_plane, flags, equation, active, self.planar_distance_thresh)
 
 
 def model_sym_jacobi(A):
@@ -1757,6 +1930,21 @@ class sim3_ransac_args_c(C.Structure):
                 ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
 
 
+class plane_ransac_args_c(C.Structure):
+    """plp_plane_ransac_args"""
+    _fields_ = [("mode", C.c_int32), ("P", C.c_int32), ("n_cap", C.c_int32), ("points_per_ransac", C.c_int32), ("min_points_before_ransac", C.c_int32),
+                ("iters", C.c_int32), ("inliers_ratio_thr", C.c_double), ("seed", C.c_uint64), ("m_cap", C.c_int32), ("counts", _VP), ("pos_w", _VP),
+                ("flags", _VP), ("dist_thresh", _VP), ("error_thresh", _VP), ("best_error_in", _VP), ("equation_in", _VP), ("samples", _VP),
+                ("out_status", _VP), ("out_flags", _VP), ("out_equation", _VP), ("out_best_error", _VP), ("out_best_iter", _VP), ("out_last_iter", _VP),
+                ("out_num_inliers", _VP), ("out_inliers", _VP), ("out_hyp_residual", _VP), ("out_hyp_inliers", _VP), ("out_hyp_error", _VP)]
+
+
+class plane_refine_args_c(C.Structure):
+    """plp_plane_refine_args"""
+    _fields_ = [("M", C.c_int32), ("NP", C.c_int32), ("pos_w", _VP), ("lm_plane", _VP), ("flags", _VP), ("equation", _VP), ("active", _VP),
+                ("dist_thresh", _VP), ("out_changed", _VP)]
+
+
 class pnp_ransac_args_c(C.Structure):
     """plp_pnp_ransac_args"""
     _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("min_num_inliers", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32),
@@ -2656,6 +2844,51 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_sim3_ransac_device(self._h, C.byref(a), st))
+
+    def plane_ransac(self, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac=18, min_points_before_ransac=12, iters=50,
+                     inliers_ratio_thr=0.7, best_error_in=None, equation_in=None, samples=None, seed=0, counts=None, outputs=None, out=None):
+        """Planar_Mapping_module's RANSAC for P planes (plp_plane_ransac_host): mode PLANE_CREATE (estimate_plane_sequential_RANSAC behind
+        create_new_plane's gate) or PLANE_UPDATE (update_plane_via_RANSAC); pos_w (P, n_cap, 3) f64, flags (P, n_cap) u8 of PLANE_LM_*,
+        dist_thresh / error_thresh a number or (P,), best_error_in (P,) / equation_in (P, 4) for UPDATE, samples (P, iters, m_cap) ranks among
+        the eligible slots or None = drawn from seed, counts (P,) or None.  Returns dict(status (P,) u8: PLANE_*, flags: PLANE_FLAG_*, equation
+        (P, 4), best_error, best_iter, last_iter, num_inliers, inliers (P, n_cap) u8, hyp_residual / hyp_inliers / hyp_error (P, iters));
+        `outputs` names the optional ones wanted (default all); out[name]: the caller's array."""
+        call = lambda a: _check(lib().plp_plane_ransac_host(self._h, C.byref(a)))
+        return _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac, min_points_before_ransac, iters,
+                                  inliers_ratio_thr, best_error_in, equation_in, samples, seed, counts, outputs, out)
+
+    def plane_ransac_device(self, mode, P, n_cap, pos_w, flags, dist_thresh, error_thresh, out, points_per_ransac=18, min_points_before_ransac=12,
+                            iters=50, inliers_ratio_thr=0.7, best_error_in=None, equation_in=None, samples=None, m_cap=0, seed=0, counts=None,
+                            stream=None):
+        """plp_plane_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device, the thresholds (P,) f64
+        included; out: dict of the device outputs named as in PLANE_RANSAC_OUTPUTS (the hyp_* ones may be absent); asynchronous, two kernels
+        on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(plane_ransac_args_c, dict(mode=int(mode), P=int(P), n_cap=int(n_cap), points_per_ransac=int(points_per_ransac),
+                                              min_points_before_ransac=int(min_points_before_ransac), iters=int(iters),
+                                              inliers_ratio_thr=float(inliers_ratio_thr), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=int(m_cap)), dict(
+            counts=D(counts), pos_w=D(pos_w), flags=D(flags), dist_thresh=D(dist_thresh), error_thresh=D(error_thresh), best_error_in=D(best_error_in),
+            equation_in=D(equation_in), samples=D(samples), **{"out_" + k: D(out.get(k)) for k in PLANE_RANSAC_OUTPUTS}))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_plane_ransac_device(self._h, C.byref(a), st))
+
+    def plane_refine_points(self, pos_w, lm_plane, flags, equation, active, dist_thresh):
+        """Planar_Mapping_module::refine_points over a landmark list (plp_plane_refine_points_host): pos_w (M, 3) f64, lm_plane (M,) plane
+        rows or -1, flags (M,) u8 of PLANE_LM_*, equation (NP, 4), active (NP,) u8, dist_thresh a number.  Returns (the new pos_w, changed
+        (M,) u8)."""
+        call = lambda a: _check(lib().plp_plane_refine_points_host(self._h, C.byref(a)))
+        return _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh)
+
+    def plane_refine_points_device(self, M, NP, pos_w, lm_plane, flags, equation, active, dist_thresh, out_changed, stream=None):
+        """plp_plane_refine_points_device: device pointers (int) or torch tensors, dist_thresh one f64 on the device; pos_w is updated in
+        place; asynchronous, one kernel on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(plane_refine_args_c, dict(M=int(M), NP=int(NP)), dict(pos_w=D(pos_w), lm_plane=D(lm_plane), flags=D(flags), equation=D(equation),
+                                                                          active=D(active), dist_thresh=D(dist_thresh), out_changed=D(out_changed)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_plane_refine_points_device(self._h, C.byref(a), st))
 
     def pnp_ransac(self, valid, bearing, pos_w, octave, scale_factors, iters=30, min_num_inliers=10, recompute=True, samples=None, seed=0, counts=None,
                    outputs=None, out=None):
