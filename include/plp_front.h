@@ -1927,6 +1927,148 @@ plp_status plp_local_map_host(plp_matcher* ctx, const plp_local_map_args* args);
  * Returns B, or the negated plp_status of a refused call. */
 int32_t plp_model_local_map_host(const plp_local_map_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Map culling: module::local_map_cleaner (src/PLPSLAM/module/local_map_cleaner.cc:51-320), the two map-only calls of the mapping loop
+ * (mapping_module.cc:204-284).  Integers and the two float comparisons of the text; contract: DESIGN.md section 5, D20.
+ *
+ * plp_cull_keyframes_*: remove_redundant_keyframes (:201-240) with count_redundant_observations (:242-320) for G problems over one map
+ * snapshot.  A problem is one current key frame with its get_covisibilities() list, in the reference's order and at full length.  The loop
+ * is sequential because prepare_for_erasing() of a removed key frame (keyframe.cc:872-926) erases its observations, which lowers
+ * num_observations() of its landmarks and discards those left with at most 2 (landmark.cc:99-136); D20 gives that effect in closed form
+ * over the set of key frames removed so far, and the entry computes exactly that.  The problems are independent readings of the snapshot.
+ *
+ * Map snapshot, shared by the G problems (the tables plp_local_ba_args and plp_local_map_args name alike):
+ *   kf_lm            [F][cap] keyfrm->get_landmarks(): the landmark row of key point idx, -1 = none                          :251-258
+ *   kf_counts        [F] key points per key frame, NULL = cap
+ *   undist           [F][kp_stride] undist_keypts_; only `octave` is read                                                    :280, :298
+ *   x_right          [F][kp_stride] stereo_x_right_; NULL = monocular, every observation weighs 1            landmark.cc:89-96, :108-115
+ *   depths           [F][kp_stride] depths_ and depth_thr [F] depth_thr_; read only when !is_monocular                       :265-269
+ *   kf_id            [F] id_                                                                                                 :215, :220
+ *   kf_erased        [F] will_be_erased(), NULL = none.  The text has no test of it, so the entry never reads it: an erased covisibility is
+ *                    counted and decided like any other.  The field keeps the snapshot's tables together.
+ *   kf_cannot_erase  [F] cannot_be_erased_, NULL = none: prepare_for_erasing() returns early                         keyframe.cc:880-884
+ *   obs_offsets, obs_kf, obs_idx   lm->get_observations() in plp_landmark_geometry_args' layout; they must agree with kf_lm (slot
+ *                    (obs_kf[t], obs_idx[t]) holds the landmark whose run holds t), as observations_ and landmarks_ do
+ *   lm_erased        [L] landmark::will_be_erased(), NULL = none                                                             :259
+ *   lm_num_obs       [L] num_observations_ before the call; NULL = the sum over the observation list of 2 where x_right >= 0 and 1
+ *                    otherwise (landmark.cc:84-97)
+ * Problems:
+ *   cur_kf           [G] the row of cur_keyfrm
+ *   covis_offsets    [G + 1] into covis [Cv]: the rows of cur_keyfrm->graph_node_->get_covisibilities()                      :211
+ *   origin_id        origin_keyfrm_id_ (:215); is_monocular: is_monocular_ (:266)
+ * A row outside its table (cur_kf, covis, kf_lm, obs_kf, obs_idx against cap) counts as absent; a count is cut to [0, cap]; a run of
+ * obs_offsets is cut to [0, T] and one of covis_offsets to [0, Cv].
+ * Outputs; slots that are not written keep the caller's values:
+ *   out_num_removed    [G] the return value (:239): PLP_CULL_KF_REMOVED and PLP_CULL_KF_REMOVED_HELD entries
+ *   out_decision       [Cv] a plp_cull_keyframe_decision per entry
+ *   out_num_valid, out_num_redundant   [Cv] num_valid_obs and num_redundant_obs as counted at that entry's turn (:229); not written for
+ *                      a skipped entry
+ *   out_kf_removed     optional, [G][F]: 1 = the problem's loop called prepare_for_erasing() on the key frame and it took effect
+ *   out_lm_erased      optional, [G][L]: 1 = the point landmark will_be_erased() at the end of the problem's loop: lm_erased, or
+ *                      discarded by erase_observation (landmark.cc:125-134).  With these two a caller that keeps the tables on the device
+ *                      never walks the cascade. */
+typedef enum plp_cull_keyframe_decision {
+    PLP_CULL_KF_SKIP_ORIGIN = 0,     /* id_ == origin_keyfrm_id_ (:215-218)                                                                  */
+    PLP_CULL_KF_SKIP_WINDOW = 1,     /* id_c <= id_cur && id_cur <= id_c + 2 in unsigned 32-bit arithmetic (:220-223)                        */
+    PLP_CULL_KF_KEPT = 2,            /* !(0.9f <= (float)num_redundant / num_valid); 0 / 0 is NaN and keeps it (:232)                        */
+    PLP_CULL_KF_REMOVED = 3,         /* counted, and prepare_for_erasing() took effect: later entries see the map without it                 */
+    PLP_CULL_KF_REMOVED_HELD = 4,    /* counted in num_removed (:234), but cannot_be_erased_ left the map untouched                          */
+    PLP_CULL_KF_ABSENT = 5           /* the entry's row, or the problem's cur_kf, is outside [0, F): not counted, nothing else written       */
+} plp_cull_keyframe_decision;
+typedef struct plp_cull_keyframes_args {
+    int32_t F, L, T;                    /* F <= 8192 key frames (the removed set is an LDS bitmap); L landmark rows; T observation entries */
+    int32_t cap, kp_stride;             /* slots per row of kf_lm, <= 8192; slots between two rows of undist, x_right and depths, 0 = cap */
+    int32_t G, Cv;                      /* G <= 65535 problems; Cv entries of covis */
+    uint32_t origin_id;
+    int32_t is_monocular;
+    const int32_t* kf_lm;               /* F x cap */
+    const int32_t* kf_counts;           /* F, or NULL */
+    const plp_keypoint* undist;         /* F x kp_stride */
+    const float* x_right;               /* F x kp_stride, or NULL */
+    const float* depths;                /* F x kp_stride; required iff !is_monocular */
+    const float* depth_thr;             /* F; required iff !is_monocular */
+    const uint32_t* kf_id;              /* F */
+    const uint8_t* kf_erased;           /* F, or NULL; never read */
+    const uint8_t* kf_cannot_erase;     /* F, or NULL */
+    const int32_t* obs_offsets;         /* L + 1 */
+    const int32_t* obs_kf;              /* T */
+    const int32_t* obs_idx;             /* T */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const uint32_t* lm_num_obs;         /* L, or NULL */
+    const int32_t* cur_kf;              /* G */
+    const int32_t* covis_offsets;       /* G + 1 */
+    const int32_t* covis;               /* Cv */
+    int32_t* out_num_removed;           /* G */
+    uint8_t* out_decision;              /* Cv */
+    int32_t* out_num_valid;             /* Cv */
+    int32_t* out_num_redundant;         /* Cv */
+    uint8_t* out_kf_removed;            /* G x F, or NULL */
+    uint8_t* out_lm_erased;             /* G x L, or NULL */
+} plp_cull_keyframes_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; a negative F, L, T, cap, kp_stride, G or Cv; a kp_stride
+ * below cap (when not 0); and -- when G > 0 -- a NULL cur_kf, covis_offsets, covis (Cv > 0), kf_id (F > 0), kf_lm or undist (F > 0 and
+ * cap > 0), obs_offsets, obs_kf or obs_idx (T > 0), depths (F > 0 and cap > 0) or depth_thr (F > 0) when !is_monocular, out_num_removed, or
+ * out_decision, out_num_valid or out_num_redundant (Cv > 0).  F > 8192, cap > 8192 or G > 65535: PLP_ERR_UNSUPPORTED.  G == 0: PLP_OK,
+ * nothing written.  _host and the host build also check that obs_offsets rises from 0 to T and covis_offsets from 0 to Cv
+ * (PLP_ERR_INVALID_ARG); on the _device path that is a precondition (the kernels cut every run to its list).
+ * _device: every array a DEVICE pointer; k_cull_count (a workgroup per entry: the counts against the snapshot), k_cull_replay (a workgroup
+ * per problem: the loop in order, recounting once a key frame is removed) and, with an optional mask, k_cull_dead_landmarks, all on hip_stream,
+ * nothing synchronised.  The counts and the removed sets pass through buffers the context owns: the calls of one context must be ordered on
+ * the device.  _host: HOST pointers, staged (the outputs too, so that every slot the kernels do not write keeps the caller's value),
+ * synchronous. */
+plp_status plp_cull_keyframes_device(plp_matcher* ctx, const plp_cull_keyframes_args* args, void* hip_stream);
+plp_status plp_cull_keyframes_host(plp_matcher* ctx, const plp_cull_keyframes_args* args);
+/* Host build of the same source (csrc/map_cull.hpp) with a team of one lane, HOST pointers, no GPU and no context needed; the same checks.
+ * Returns G, or the negated plp_status of a refused call. */
+int32_t plp_model_cull_keyframes_host(const plp_cull_keyframes_args* args);
+
+/* plp_cull_landmarks_*: remove_redundant_landmarks (:51-131) or remove_redundant_landmarks_line (:133-199) for R fresh lists in ragged
+ * form; points and lines are two calls with their own tables (or, where the rows share one table, two lists of one call).
+ *   fresh_offsets    [R + 1] into fresh [N]: fresh_landmarks_ / _fresh_landmarks_line as landmark rows, in list order      :66, :148
+ *   lm_erased        [L] will_be_erased(), NULL = none                                                                      :73, :155
+ *   num_observed, num_observable   [L] the two terms of get_observed_ratio(): (float)num_observed / num_observable, compared < 0.3f;
+ *                    0 / 0 and x / 0 behave as IEEE float does (NaN is not below, +inf is not below)          :79, :161, landmark.cc:453-457
+ *   first_kf_id      [L] first_keyfrm_id_; num_obs [L] num_observations()                                                   :92, :105
+ *   owning_plane     [L] get_Owning_Plane() != nullptr, NULL = none (the line list passes NULL)                             :83, :96
+ *   cur_kf_id        [R] cur_keyfrm_id; num_obs_thr [R]: 2 or 3 by is_monocular_ for points (:55), 3 for lines (:137)
+ * The id tests are unsigned 32-bit: 2 + first_kf_id <= cur_kf_id and 3 + first_kf_id <= cur_kf_id.  A row outside [0, L) leaves the buffer
+ * as an erased one does (PLP_CULL_DROP).  A run of fresh_offsets is cut to [0, N].  Entries are independent.
+ * Outputs (out_fresh must not overlap fresh):
+ *   out_state        [N] a plp_cull_landmark_state per entry
+ *   out_num_removed  [R] the return value: PLP_CULL_ERASE entries (:119, :187)
+ *   out_num_fresh    [R] the length of the list afterwards; out_fresh [N]: its entries, the PLP_CULL_HOLD ones in order, from
+ *                    fresh_offsets[r] on; the slots behind them keep the caller's values */
+typedef enum plp_cull_landmark_state {
+    PLP_CULL_HOLD = 0,               /* NotClear: stays in the buffer                                      */
+    PLP_CULL_DROP = 1,               /* Valid: leaves the buffer only                                      */
+    PLP_CULL_ERASE = 2               /* Invalid: counted, prepare_for_erasing(), leaves the buffer         */
+} plp_cull_landmark_state;
+typedef struct plp_cull_landmarks_args {
+    int32_t R, N, L;                    /* lists, entries of fresh, landmark rows */
+    const int32_t* fresh_offsets;       /* R + 1 */
+    const int32_t* fresh;               /* N */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const uint32_t* num_observed;       /* L */
+    const uint32_t* num_observable;     /* L */
+    const uint32_t* first_kf_id;        /* L */
+    const uint32_t* num_obs;            /* L */
+    const uint8_t* owning_plane;        /* L, or NULL */
+    const uint32_t* cur_kf_id;          /* R */
+    const uint32_t* num_obs_thr;        /* R */
+    uint8_t* out_state;                 /* N */
+    int32_t* out_num_removed;           /* R */
+    int32_t* out_num_fresh;             /* R */
+    int32_t* out_fresh;                 /* N */
+} plp_cull_landmarks_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; a negative R, N or L; and -- when R > 0 -- a NULL
+ * fresh_offsets, cur_kf_id, num_obs_thr, out_num_removed or out_num_fresh, a NULL fresh, out_state or out_fresh (N > 0), a NULL
+ * num_observed, num_observable, first_kf_id or num_obs (L > 0).  R == 0: PLP_OK, nothing written.  _host and the host build also check that
+ * fresh_offsets rises from 0 to N.  _device: DEVICE pointers, k_cull_landmark_states (a workgroup per list) on hip_stream.  _host: HOST
+ * pointers, staged, synchronous.  plp_model_cull_landmarks_host: the host build; returns R, or the negated plp_status. */
+plp_status plp_cull_landmarks_device(plp_matcher* ctx, const plp_cull_landmarks_args* args, void* hip_stream);
+plp_status plp_cull_landmarks_host(plp_matcher* ctx, const plp_cull_landmarks_args* args);
+int32_t plp_model_cull_landmarks_host(const plp_cull_landmarks_args* args);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

@@ -200,6 +200,12 @@ _API = [
     ("plp_plane_refine_points_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_plane_refine_points_host", C.c_int, [_VP, _VP]),
     ("plp_model_plane_refine_points_host", _I32, [_VP]),
+    ("plp_cull_keyframes_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_cull_keyframes_host", C.c_int, [_VP, _VP]),
+    ("plp_model_cull_keyframes_host", _I32, [_VP]),
+    ("plp_cull_landmarks_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_cull_landmarks_host", C.c_int, [_VP, _VP]),
+    ("plp_model_cull_landmarks_host", _I32, [_VP]),
 ]
 
 
@@ -1385,6 +1391,171 @@ class local_map_updater:
         return int(self._r["nearest_kf"])
 
 
+# plp_cull_keyframe_decision and plp_cull_landmark_state
+CULL_KF_SKIP_ORIGIN, CULL_KF_SKIP_WINDOW, CULL_KF_KEPT, CULL_KF_REMOVED, CULL_KF_REMOVED_HELD, CULL_KF_ABSENT = range(6)
+CULL_HOLD, CULL_DROP, CULL_ERASE = range(3)
+CULL_MAX_KF = 8192                  # F: the removed set of a problem is an LDS bitmap
+CULL_MAX_SLOTS = 8192               # cap
+CULL_MAX_PROBLEMS = 65535           # G
+CULL_KEYFRAMES_INPUTS = ("kf_lm", "kf_counts", "undist", "x_right", "depths", "depth_thr", "kf_id", "kf_erased", "kf_cannot_erase", "obs_offsets",
+                         "obs_kf", "obs_idx", "lm_erased", "lm_num_obs", "cur_kf", "covis_offsets", "covis")
+# the outputs of plp_cull_keyframes_*: name -> (shape from (G, Cv, F, L), dtype, optional)
+CULL_KEYFRAMES_OUTPUTS = dict(num_removed=(lambda G, Cv, F, L: (G,), np.int32, False), decision=(lambda G, Cv, F, L: (Cv,), np.uint8, False),
+                              num_valid=(lambda G, Cv, F, L: (Cv,), np.int32, False), num_redundant=(lambda G, Cv, F, L: (Cv,), np.int32, False),
+                              kf_removed=(lambda G, Cv, F, L: (G, F), np.uint8, True), lm_erased=(lambda G, Cv, F, L: (G, L), np.uint8, True))
+CULL_LANDMARKS_INPUTS = ("fresh_offsets", "fresh", "lm_erased", "num_observed", "num_observable", "first_kf_id", "num_obs", "owning_plane",
+                         "cur_kf_id", "num_obs_thr")
+# the outputs of plp_cull_landmarks_*: name -> (per entry (N) or per list (R), dtype)
+CULL_LANDMARKS_OUTPUTS = dict(state=("N", np.uint8), num_removed=("R", np.int32), num_fresh=("R", np.int32), fresh=("N", np.int32))
+
+
+def _cull_out(spec_items, out, a):
+    """the output arrays of a culling entry: the caller's where given (unwritten slots keep their values), zeros otherwise"""
+    o = {}
+    for k, full, dt in spec_items:
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+        setattr(a, "out_" + k, o[k].ctypes.data if o[k].size else None)
+    return o
+
+
+def _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id, is_monocular, kf_counts,
+                         x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out):
+    """the numpy side of plp_cull_keyframes_host and plp_model_cull_keyframes_host: call(args struct) runs the entry.  The row widths of kf_lm and
+    of undist (with x_right and depths) are cap and kp_stride."""
+    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+    u32 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint32).reshape(-1)
+    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    kid = u32(kf_id)
+    F = len(kid)
+    kl = i32(kf_lm).reshape(F, -1) if F else np.zeros((0, 0), np.int32)
+    un = np.ascontiguousarray(undist)
+    if un.dtype != KP_DTYPE:
+        un = np.ascontiguousarray(un, np.uint8).reshape(F, -1).view(KP_DTYPE)
+    un = un.reshape(F, -1) if F else np.zeros((0, 0), KP_DTYPE)
+    cap, stride = kl.shape[1], un.shape[1]
+    f32 = lambda v, shape: None if v is None else np.ascontiguousarray(v, np.float32).reshape(shape)
+    xr, dp, dt_ = f32(x_right, (F, stride)), f32(depths, (F, stride)), f32(depth_thr, (F,))
+    oo, ok, oi = i32(obs_offsets).reshape(-1), i32(obs_kf).reshape(-1), i32(obs_idx).reshape(-1)
+    ck, co, cv = i32(cur_kf).reshape(-1), i32(covis_offsets).reshape(-1), i32(covis).reshape(-1)
+    if len(oo) < 1 or len(co) != len(ck) + 1 or len(oi) != len(ok):
+        raise PlpError(PLP_ERR_INVALID_ARG, "obs_offsets must have L + 1 entries, covis_offsets G + 1, obs_idx as many as obs_kf")
+    L, G, Cv = len(oo) - 1, len(ck), len(cv)
+    kcn, ke, kce, le, ln = i32(kf_counts), u8(kf_erased), u8(kf_cannot_erase), u8(lm_erased), u32(lm_num_obs)
+    for name, v, n in (("kf_counts", kcn, F), ("kf_erased", ke, F), ("kf_cannot_erase", kce, F), ("lm_erased", le, L), ("lm_num_obs", ln, L)):
+        if v is not None and v.size != n:
+            raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(cull_keyframes_args_c, dict(F=F, L=L, T=len(ok), cap=cap, kp_stride=stride, G=G, Cv=Cv, origin_id=int(origin_id),
+                                            is_monocular=int(bool(is_monocular))),
+                dict(kf_lm=Pt(kl), kf_counts=Pt(kcn), undist=Pt(un), x_right=Pt(xr), depths=Pt(dp), depth_thr=Pt(dt_), kf_id=Pt(kid), kf_erased=Pt(ke),
+                     kf_cannot_erase=Pt(kce), obs_offsets=Pt(oo), obs_kf=Pt(ok), obs_idx=Pt(oi), lm_erased=Pt(le), lm_num_obs=Pt(ln), cur_kf=Pt(ck),
+                     covis_offsets=Pt(co), covis=Pt(cv)))
+    o = _cull_out([(k, shape(G, Cv, F, L), dt) for k, (shape, dt, optional) in CULL_KEYFRAMES_OUTPUTS.items()
+                   if not (optional and outputs is not None and k not in outputs)], out, a)
+    call(a)
+    return o
+
+
+def model_cull_keyframes(kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id=0, is_monocular=True,
+                         kf_counts=None, x_right=None, depths=None, depth_thr=None, kf_erased=None, kf_cannot_erase=None, lm_erased=None,
+                         lm_num_obs=None, outputs=None, out=None):
+    """Host build of local_map_cleaner::remove_redundant_keyframes for G problems (csrc/map_cull.hpp, DESIGN.md section 5, D20; no GPU needed): the
+    arguments and the result of matcher.cull_keyframes."""
+    def call(a):
+        r = lib().plp_model_cull_keyframes_host(C.byref(a))
+        if r != a.G:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id, is_monocular,
+                                kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out)
+
+
+def _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased, owning_plane,
+                         out):
+    """the numpy side of plp_cull_landmarks_host and plp_model_cull_landmarks_host"""
+    i32 = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
+    u32 = lambda v: np.ascontiguousarray(v, np.uint32).reshape(-1)
+    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    fo, fr = i32(fresh_offsets), i32(fresh)
+    nd, nb, fk, no, ck, th = u32(num_observed), u32(num_observable), u32(first_kf_id), u32(num_obs), u32(cur_kf_id), u32(num_obs_thr)
+    L, R, N = len(nd), len(ck), len(fr)
+    le, pl = u8(lm_erased), u8(owning_plane)
+    if len(fo) != R + 1 or len(th) != R or any(len(v) != L for v in (nb, fk, no)) or any(v is not None and len(v) != L for v in (le, pl)):
+        raise PlpError(PLP_ERR_INVALID_ARG, "fresh_offsets must have R + 1 entries, num_obs_thr R, every landmark table L")
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(cull_landmarks_args_c, dict(R=R, N=N, L=L),
+                dict(fresh_offsets=Pt(fo), fresh=Pt(fr), lm_erased=Pt(le), num_observed=Pt(nd), num_observable=Pt(nb), first_kf_id=Pt(fk), num_obs=Pt(no),
+                     owning_plane=Pt(pl), cur_kf_id=Pt(ck), num_obs_thr=Pt(th)))
+    o = _cull_out([(k, (N,) if per == "N" else (R,), dt) for k, (per, dt) in CULL_LANDMARKS_OUTPUTS.items()], out, a)
+    call(a)
+    return o
+
+
+def model_cull_landmarks(fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased=None,
+                         owning_plane=None, out=None):
+    """Host build of local_map_cleaner::remove_redundant_landmarks[_line] for R fresh lists (csrc/map_cull.hpp, D20; no GPU needed): the arguments
+    and the result of matcher.cull_landmarks."""
+    def call(a):
+        r = lib().plp_model_cull_landmarks_host(C.byref(a))
+        if r != a.R:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased,
+                                owning_plane, out)
+
+
+class local_map_cleaner:
+    """Mirror of module::local_map_cleaner (module/local_map_cleaner.h) over table rows: the fresh buffers hold landmark rows, the key frames are
+    rows of the map tables the calls take.  mt: a matcher (the GPU entries), or None = the host build."""
+
+    def __init__(self, is_monocular, mt=None):
+        self.is_monocular, self._mt, self.origin_keyfrm_id = bool(is_monocular), mt, 0
+        self.reset()
+
+    def set_origin_keyframe_id(self, id_):
+        self.origin_keyfrm_id = int(id_)
+
+    def add_fresh_landmark(self, lm):
+        self.fresh_landmarks.append(int(lm))
+
+    def add_fresh_landmark_line(self, lm_line):
+        self.fresh_landmarks_line.append(int(lm_line))
+
+    def reset(self):
+        self.fresh_landmarks, self.fresh_landmarks_line, self.last = [], [], None
+
+    def _landmarks(self, fresh, cur_keyfrm_id, thr, tables, plane):
+        fn = model_cull_landmarks if self._mt is None else self._mt.cull_landmarks
+        r = fn([0, len(fresh)], fresh, tables["num_observed"], tables["num_observable"], tables["first_kf_id"], tables["num_obs"], [cur_keyfrm_id], [thr],
+               lm_erased=tables.get("lm_erased"), owning_plane=tables.get("owning_plane") if plane else None)
+        self.last = r
+        return [int(v) for v in r["fresh"][:int(r["num_fresh"][0])]], int(r["num_removed"][0])
+
+    def remove_redundant_landmarks(self, cur_keyfrm_id, tables):
+        """tables: a dict of the per-row tables of CULL_LANDMARKS_INPUTS for the point landmarks.  Returns num_removed; self.last["state"] names
+        what became of every entry (CULL_ERASE: the caller runs prepare_for_erasing() on it), fresh_landmarks keeps the HOLD ones."""
+        self.fresh_landmarks, n = self._landmarks(self.fresh_landmarks, cur_keyfrm_id, 2 if self.is_monocular else 3, tables, True)
+        return n
+
+    def remove_redundant_landmarks_line(self, cur_keyfrm_id, tables):
+        """the same for the line buffer, whose threshold is 3 and whose landmarks own no plane"""
+        self.fresh_landmarks_line, n = self._landmarks(self.fresh_landmarks_line, cur_keyfrm_id, 3, tables, False)
+        return n
+
+    def remove_redundant_keyframes(self, cur_row, covisibilities, tables):
+        """cur_row: the table row of cur_keyfrm; covisibilities: the rows of its get_covisibilities(), in order; tables: a dict with the keys of
+        CULL_KEYFRAMES_INPUTS but the problem's.  Returns num_removed; self.last holds the outputs of CULL_KEYFRAMES_OUTPUTS (decision: which rows
+        the caller runs prepare_for_erasing() on; kf_removed, lm_erased: the map afterwards)."""
+        fn = model_cull_keyframes if self._mt is None else self._mt.cull_keyframes
+        cv = np.asarray(covisibilities, np.int32).reshape(-1)
+        opt = {k: tables.get(k) for k in ("kf_counts", "x_right", "depths", "depth_thr", "kf_erased", "kf_cannot_erase", "lm_erased", "lm_num_obs")}
+        r = fn(tables["kf_lm"], tables["undist"], tables["kf_id"], tables["obs_offsets"], tables["obs_kf"], tables["obs_idx"], [int(cur_row)], [0, len(cv)],
+               cv, origin_id=self.origin_keyfrm_id, is_monocular=self.is_monocular, **opt)
+        self.last = r
+        return int(r["num_removed"][0])
+
+
 class orb_extractor:
     """Mirror of feature::orb_extractor (src/PLPSLAM/feature/orb_extractor.h:38-176) over the C ABI."""
 
@@ -1992,6 +2163,23 @@ class local_map_args_c(C.Structure):
                 ("lm_erased_lines", _VP), ("frm_lm", _VP), ("frm_counts", _VP), ("frm_lm_lines", _VP), ("frm_kl_counts", _VP), ("out_status", _VP),
                 ("out_num_first", _VP), ("out_num_kf", _VP), ("out_local_kf", _VP), ("out_first_weight", _VP), ("out_nearest_kf", _VP),
                 ("out_num_lm", _VP), ("out_local_lm", _VP), ("out_held", _VP), ("out_num_lines", _VP), ("out_local_lines", _VP), ("out_held_lines", _VP)]
+
+
+class cull_keyframes_args_c(C.Structure):
+    """plp_cull_keyframes_args"""
+    _fields_ = [("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32), ("kp_stride", C.c_int32), ("G", C.c_int32), ("Cv", C.c_int32),
+                ("origin_id", C.c_uint32), ("is_monocular", C.c_int32), ("kf_lm", _VP), ("kf_counts", _VP), ("undist", _VP), ("x_right", _VP),
+                ("depths", _VP), ("depth_thr", _VP), ("kf_id", _VP), ("kf_erased", _VP), ("kf_cannot_erase", _VP), ("obs_offsets", _VP), ("obs_kf", _VP),
+                ("obs_idx", _VP), ("lm_erased", _VP), ("lm_num_obs", _VP), ("cur_kf", _VP), ("covis_offsets", _VP), ("covis", _VP),
+                ("out_num_removed", _VP), ("out_decision", _VP), ("out_num_valid", _VP), ("out_num_redundant", _VP), ("out_kf_removed", _VP),
+                ("out_lm_erased", _VP)]
+
+
+class cull_landmarks_args_c(C.Structure):
+    """plp_cull_landmarks_args"""
+    _fields_ = [("R", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("fresh_offsets", _VP), ("fresh", _VP), ("lm_erased", _VP), ("num_observed", _VP),
+                ("num_observable", _VP), ("first_kf_id", _VP), ("num_obs", _VP), ("owning_plane", _VP), ("cur_kf_id", _VP), ("num_obs_thr", _VP),
+                ("out_state", _VP), ("out_num_removed", _VP), ("out_num_fresh", _VP), ("out_fresh", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -3042,6 +3230,52 @@ class matcher:
             setattr(a, "out_" + k, D(out.get(k)))
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_local_map_device(self._h, C.byref(a), st))
+
+    def cull_keyframes(self, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id=0, is_monocular=True,
+                       kf_counts=None, x_right=None, depths=None, depth_thr=None, kf_erased=None, kf_cannot_erase=None, lm_erased=None, lm_num_obs=None,
+                       outputs=None, out=None):
+        """local_map_cleaner::remove_redundant_keyframes for G problems over one map snapshot (plp_cull_keyframes_host; DESIGN.md section 5, D20):
+        kf_lm (F, cap) i32, undist (F, kp_stride) KP_DTYPE, kf_id (F,) u32, the observation lists obs_offsets (L + 1,), obs_kf, obs_idx (T,), cur_kf
+        (G,) rows, covis_offsets (G + 1,) into covis (Cv,) rows; x_right / depths (F, kp_stride) f32, depth_thr (F,) f32, the byte tables and lm_num_obs
+        (L,) u32 or None.  Returns dict(num_removed (G,), decision (Cv,) u8: CULL_KF_*, num_valid, num_redundant (Cv,), kf_removed (G, F), lm_erased
+        (G, L)); `outputs` names the optional ones wanted (default all); out[name]: the caller's array (unwritten slots keep their values)."""
+        call = lambda a: _check(lib().plp_cull_keyframes_host(self._h, C.byref(a)))
+        return _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id, is_monocular,
+                                    kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out)
+
+    def cull_keyframes_device(self, dims, tables, out, origin_id=0, is_monocular=True, stream=None):
+        """plp_cull_keyframes_device: dims a dict of the struct's sizes (F, L, T, cap, G, Cv and optionally kp_stride); tables a dict of
+        CULL_KEYFRAMES_INPUTS and out a dict of CULL_KEYFRAMES_OUTPUTS, each a device pointer (int), a torch tensor on the matcher's device or
+        absent / None; asynchronous on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(cull_keyframes_args_c, dict({k: int(v) for k, v in dims.items()}, origin_id=int(origin_id), is_monocular=int(bool(is_monocular))),
+                    {k: D(tables.get(k)) for k in CULL_KEYFRAMES_INPUTS})
+        for k in CULL_KEYFRAMES_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_cull_keyframes_device(self._h, C.byref(a), st))
+
+    def cull_landmarks(self, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased=None,
+                       owning_plane=None, out=None):
+        """local_map_cleaner::remove_redundant_landmarks[_line] for R fresh lists (plp_cull_landmarks_host; D20): fresh_offsets (R + 1,) into fresh
+        (N,) landmark rows; num_observed, num_observable, first_kf_id, num_obs (L,) u32; cur_kf_id, num_obs_thr (R,) u32; lm_erased, owning_plane (L,)
+        u8 or None.  Returns dict(state (N,) u8: CULL_HOLD / CULL_DROP / CULL_ERASE, num_removed, num_fresh (R,), fresh (N,): the HOLD entries of
+        list r in order from fresh_offsets[r] on)."""
+        call = lambda a: _check(lib().plp_cull_landmarks_host(self._h, C.byref(a)))
+        return _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased,
+                                    owning_plane, out)
+
+    def cull_landmarks_device(self, dims, tables, out, stream=None):
+        """plp_cull_landmarks_device: dims dict(R, N, L); tables a dict of CULL_LANDMARKS_INPUTS and out a dict of CULL_LANDMARKS_OUTPUTS, device
+        pointers (int) or torch tensors; asynchronous, one kernel on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(cull_landmarks_args_c, {k: int(v) for k, v in dims.items()}, {k: D(tables.get(k)) for k in CULL_LANDMARKS_INPUTS})
+        for k in CULL_LANDMARKS_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_cull_landmarks_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):
