@@ -115,6 +115,7 @@ plp_status build(plp_line* c, int rows, int cols) {
     {
         double u = (7 * 3 - 1) / 2, sg = (7 * 2 + 1) / 2, inv = -1 / (2 * sg * sg);
         for (int i = 0; i < 21; ++i) { const double d = i - u; c->w.l[i] = (float)std::exp(d * d * inv); }
+        for (int i = 0; i < 21; ++i) c->w.l2[i] = c->w.l[i] * c->w.l[i];   // the second moments weigh with the f32 square (one rounding, as on the device)
         u = (9 * 7 - 1) / 2; sg = u; inv = -1 / (2 * sg * sg);
         for (int i = 0; i < 63; ++i) { const double d = i - u; c->w.g[i] = (float)std::exp(d * d * inv); }
     }
@@ -153,13 +154,13 @@ plp_status ensure(plp_line* c, int B) {
         PLP_HIP(c->raw.reserve(sizeof(float4) * kLineCap * B)); PLP_HIP(c->n_raw.reserve(4 * (size_t)B));
         PLP_HIP(c->dx.reserve(dxy_frame_entries(P.W, P.H) * 4 * B));
         PLP_HIP(c->all_kl.reserve(sizeof(plp_keyline) * kLineCap * B)); PLP_HIP(c->all_kl_dir.reserve(sizeof(float2) * kLineCap * B)); PLP_HIP(c->all_lbd.reserve((size_t)32 * kLineCap * B));
-        PLP_HIP(c->n_all.reserve(4 * (size_t)B)); PLP_HIP(c->status.reserve(16)); PLP_HIP(c->prof.reserve(128)); PLP_HIP(c->grow_stats.reserve(16 * (size_t)B));
+        PLP_HIP(c->n_all.reserve(8 * (size_t)B));   /* counts, then k_lbd's tickets */ PLP_HIP(c->status.reserve(16)); PLP_HIP(c->prof.reserve(128)); PLP_HIP(c->grow_stats.reserve(16 * (size_t)B));
         P.blur11 = (uint8_t*)c->blur11.p; P.scaled = (uint8_t*)c->scaled.p;
         P.pix = (LsdPix*)c->pix.p; P.g2 = (uint32_t*)c->g2.p; P.n_order = (int32_t*)c->n_order.p;
         P.blockmax = (uint32_t*)c->maxgrad.p; P.undef = (unsigned long long*)c->undef.p;
         P.order = (uint32_t*)c->order.p; P.reg = (uint32_t*)c->reg.p; P.raw = (float4*)c->raw.p; P.n_raw = (int32_t*)c->n_raw.p;
         P.dxy = (short2*)c->dx.p; P.all_kl = (plp_keyline*)c->all_kl.p; P.all_kl_dir = (float2*)c->all_kl_dir.p; P.all_lbd = (uint8_t*)c->all_lbd.p;
-        P.n_all = (int32_t*)c->n_all.p; P.status = (int32_t*)c->status.p; P.prof = (long long*)c->prof.p; P.grow_stats = (int32_t*)c->grow_stats.p;
+        P.n_all = (int32_t*)c->n_all.p; P.lbd_ticket = P.n_all + B; P.status = (int32_t*)c->status.p; P.prof = (long long*)c->prof.p; P.grow_stats = (int32_t*)c->grow_stats.p;
         c->capB = B;
     }
     P.reg_frame_stride = B <= kLsdMwMaxFrames ? 2 * n : n;

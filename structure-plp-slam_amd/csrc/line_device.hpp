@@ -57,6 +57,7 @@ struct LinePlanes {
     short2* dxy;              // Sobel 3x3, (dx, dy) per pixel, in tiles of 8 x 4 pixels = one 128-byte line (dxy_index)  [B][dxy_frame_entries(W, H)]
     plp_keyline* all_kl; uint8_t* all_lbd; int32_t* n_all;   // before the length filter  [B][kLineCap]
     float2* all_kl_dir;                                       // (cos, sin) of all_kl[.].angle as floats: the LBD's line direction
+    int32_t* lbd_ticket;                                      // next line of the frame no wave of k_lbd has taken yet (k_keylines zeroes it)  [B]
     int32_t* status;
     int half_exact;           // 1: every INTER_LINEAR_EXACT table entry is (2d, 128): blur11 and the x0.5 resize run as one kernel
     int32_t* grow_stats;      // per frame {regions grown, pixels accepted, exact (in-band) decisions of the angle test, 0}: the USED map's history in three numbers  [B][4]
@@ -87,7 +88,7 @@ constexpr double kLsdBandMinPrec = 0.01, kLsdBandMaxPrec = 1.5;
 
 struct ResizeExactTab { const int16_t *xo, *xc, *yo, *yc; };   // offsets + 8.8 weights (-1/-2: border sample)
 struct BlurTapsN { int k[11]; };
-struct LbdWeightsDev { float g[63], l[21]; };
+struct LbdWeightsDev { float g[63], l[21], l2[21]; };   // global weight per band row; local weight per row of a band and its two neighbours, and its f32 square
 
 // Seed order of a reference built with libstdc++ (seed_sort_kernels.hip): `ent` = [B][(sw-1)(sh-1)] entries, `ws` = [B][ws_stride] scratch
 struct SeedSortBufs { uint32_t* ent; uint32_t* ws; size_t ws_stride; };

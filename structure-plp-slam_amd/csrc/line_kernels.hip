@@ -1607,7 +1607,7 @@ __global__ __launch_bounds__(64) void k_keylines(LinePlanes P, LsdParams lp) {
         }
         run += __popcll(bal);
     }
-    if (lane == 0) P.n_all[b] = run;
+    if (lane == 0) { P.n_all[b] = run; P.lbd_ticket[b] = 0; }   // (k_lbd's waves draw the frame's lines from the ticket)
 }
 
 // ------------------------------------------------------------------------------------------ blur5 + Sobel
@@ -1670,131 +1670,222 @@ __constant__ int c_comb[32][2] = {{0, 1}, {0, 2}, {0, 3}, {0, 4}, {0, 5}, {0, 6}
                                   {2, 3}, {2, 4}, {2, 5}, {2, 6}, {2, 7}, {2, 8}, {3, 4}, {3, 5}, {3, 6}, {3, 7}, {3, 8},
                                   {4, 5}, {4, 6}, {4, 7}, {4, 8}, {5, 6}, {5, 7}, {5, 8}, {6, 7}, {6, 8}, {7, 8}};
 
-// grid = (2, B), block = 256: one wave per line, 8 lines of a frame in flight (more waves thrash L1/L2: every wave
-// keeps 63 image rows live).
+// grid = (3, B), block = 256: one wave per line, 12 lines of a frame in flight (more waves thrash L1/L2: every wave
+// keeps 63 image rows live).  A wave draws its next line from the frame's ticket (P.lbd_ticket, zeroed by k_keylines): the lines of a frame
+// run from 61 to several hundred samples, and a fixed stride left the waves of a frame with unequal shares.
 constexpr int kLbdU = 8;   // band steps whose gathers are in flight together (per lane = band row)
+
+// One band sample: the two derivatives of a pixel (s16 pair) projected on the line direction and its normal, accumulated by sign.
+// max(g, 0) / min(g, 0) instead of a branch on the sign: the accumulators start at +0 and only grow, and adding a zero of either sign to
+// such a value (or subtracting one from it) returns it unchanged, so every accumulator sees the same sequence of roundings.
+__device__ __forceinline__ void lbd_accumulate(uint32_t v, float dL0, float dL1, float& pgdL, float& ngdL, float& pgdO, float& ngdO) {
+    const float fx = (float)(short)(v & 0xffffu), fy = (float)(short)(v >> 16);
+    const float gDL = __fadd_rn(__fmul_rn(fx, dL0), __fmul_rn(fy, dL1));
+    const float gDO = __fadd_rn(__fmul_rn(fx, -dL1), __fmul_rn(fy, dL0));
+    pgdL = __fadd_rn(pgdL, fmaxf(gDL, 0.0f)); ngdL = __fsub_rn(ngdL, fminf(gDL, 0.0f));
+    pgdO = __fadd_rn(pgdO, fmaxf(gDO, 0.0f)); ngdO = __fsub_rn(ngdO, fminf(gDO, 0.0f));
+}
+
+// Byte offset of the sample at (sx, sy) in the frame's tiled Sobel plane (dxy_index * 4: the largest frame the
+// region grower admits has about 2.1 M pixels, a plane of 8.4 MB, and both factors of the 24-bit multiply stay below 2^18).
+// kInside: the caller has shown 0.5 <= sx, sy and that the rounded position lies in the image.  For s >= 0.5 roundf(s) is
+// trunc(s + 0.5f): in [0.5, 1) the sum lies in [1, 1.5] and truncates to 1; from 1 on s and 0.5 are multiples of ulp(s) and the sum stays
+// in the binade of s (exact) or reaches the next power of two 2^k from [2^k - 0.5, 2^k), where every rounding of it still truncates to 2^k.
+template <bool kInside>
+__device__ __forceinline__ uint32_t lbd_sample_offset(float sx, float sy, short imageWidth, short imageHeight, uint32_t tile_row_bytes) {
+    uint32_t x, y;
+    if (kInside) {
+        x = (uint32_t)(int)__fadd_rn(sx, 0.5f);
+        y = (uint32_t)(int)__fadd_rn(sy, 0.5f);
+    } else {
+        short t = (short)roundf(sx);
+        x = (uint32_t)((t < 0) ? 0 : (t > imageWidth) ? imageWidth : t);
+        t = (short)roundf(sy);
+        y = (uint32_t)((t < 0) ? 0 : (t > imageHeight) ? imageHeight : t);
+    }
+    // ((y >> 2) tiles_x + (x >> 3)) 128 + (y & 3) 32 + (x & 7) 4, with x & 7 = x - (x & ~7) and y & 3 = y - 4 (y >> 2): seven instructions instead of nine
+    return __umul24(x & ~7u, 12u) + (x << 2) + __umul24(y >> 2, tile_row_bytes - 128u) + (y << 5);
+}
+
+// kLbdU steps of every band row: addresses first, the gathers in flight together, then the strictly ordered accumulation of the first `n` of them
+// (kTail: n < kLbdU, the last trip of a line; the steps past the line's end are addressed -- clamped -- and fetched, not accumulated).
+template <bool kInside, bool kTail>
+__device__ __forceinline__ void lbd_trip(const char* __restrict__ dxyBytes, float& sCorX, float& sCorY, float dL0, float dL1, short imageWidth,
+                                         short imageHeight, uint32_t tile_row_bytes, int n, float& pgdL, float& ngdL, float& pgdO, float& ngdO) {
+    static_assert(!(kInside && kTail), "the steps past a line's end may leave the image: the tail trip clamps");
+    uint32_t off[kLbdU];
+#pragma unroll
+    for (int u = 0; u < kLbdU; ++u) {
+        off[u] = lbd_sample_offset<kInside>(sCorX, sCorY, imageWidth, imageHeight, tile_row_bytes);
+        sCorX = __fadd_rn(sCorX, dL0);
+        sCorY = __fadd_rn(sCorY, dL1);
+    }
+    uint32_t vxy[kLbdU];
+#pragma unroll
+    for (int u = 0; u < kLbdU; ++u) vxy[u] = *reinterpret_cast<const uint32_t*>(dxyBytes + off[u]);
+#pragma unroll
+    for (int u = 0; u < kLbdU; ++u)
+        if (!kTail || u < n) lbd_accumulate(vxy[u], dL0, dL1, pgdL, ngdL, pgdO, ngdO);
+}
+
+constexpr int kLbdPad = 7;   // zero rows before and after the 63 band rows in LDS: the bands at both ends sum 21 rows like the others
 __global__ __launch_bounds__(256) void k_lbd(LinePlanes P, LbdWeightsDev W) {
-    __shared__ float s_row[4][63][8];   // per row: pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2 (after the global weight)
-    __shared__ float s_des[4][72], s_des2[4][72], s_norm[4][4];
+    __shared__ float s_row[4][63 + 2 * kLbdPad][8];   // per row: pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2 (after the global weight)
+    __shared__ __attribute__((aligned(16))) float s_des[4][72], s_des2[4][72], s_sq[4][72];
+    __shared__ float s_norm[4][4];
+    __shared__ float s_coef[2][21];   // W.l and W.l2: a lane reads the row its component needs (a select between the two per lane would be kept in 21 registers across the line loop)
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), b = blockIdx.y;   // (wave-uniform, and said so: the line's record and addresses are scalar)
     const int n_lines = P.n_all[b];
-    for (int li = blockIdx.x * 4 + wv; li < n_lines; li += gridDim.x * 4) {   // a few resident waves walk the frame's lines
-    const plp_keyline kl = P.all_kl[(size_t)b * kLineCap + li];
-    const short2* dxyImg = P.dxy + (size_t)b * dxy_frame_entries(P.W, P.H);
-    const int tiles8 = (P.W + 7) / 8;
+    const char* dxyBytes = reinterpret_cast<const char*>(P.dxy + (size_t)b * dxy_frame_entries(P.W, P.H));
+    const uint32_t tile_row_bytes = (uint32_t)((P.W + 7) / 8) * 128u;
     const short imageWidth = (short)(P.W - 1), imageHeight = (short)(P.H - 1);
+    auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); };
+    if (lane < 2 * kLbdPad) {
+        float* z = s_row[wv][lane < kLbdPad ? lane : 63 + lane];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) z[k] = 0.0f;
+    }
+    if (threadIdx.x < 21) { s_coef[0][threadIdx.x] = W.l[threadIdx.x]; s_coef[1][threadIdx.x] = W.l2[threadIdx.x]; }
+    wg_barrier();
+    for (;;) {   // a few resident waves walk the frame's lines
+    int li = 0;
+    if (lane == 0) li = atomicAdd(&P.lbd_ticket[b], 1);
+    li = __builtin_amdgcn_readfirstlane(li);
+    if (li >= n_lines) break;
+    const plp_keyline kl = P.all_kl[(size_t)b * kLineCap + li];
     const short lengthOfLSP = (short)kl.numOfPixels;
     const short halfWidth = (short)((lengthOfLSP - 1) / 2), halfHeight = 31;
     const float midX = (float)(0.5 * (double)__fadd_rn(kl.sPointInOctaveX, kl.ePointInOctaveX));
     const float midY = (float)(0.5 * (double)__fadd_rn(kl.sPointInOctaveY, kl.ePointInOctaveY));
     const float2 dir = P.all_kl_dir[(size_t)b * kLineCap + li];   // ((float)cos((double)kl.angle), (float)sin((double)kl.angle)), from k_keylines
     const float dL0 = dir.x, dL1 = dir.y;
-    const float dO0 = -dL1, dO1 = dL0;
+    // start corner of row 0; the reference steps it row by row (sCorX0 -= dL1; sCorY0 += dL0)
+    const float cornerX = __fadd_rn(__fadd_rn(__fmul_rn(-dL0, (float)halfWidth), __fmul_rn(dL1, (float)halfHeight)), midX);
+    const float cornerY = __fadd_rn(__fsub_rn(__fmul_rn(-dL1, (float)halfWidth), __fmul_rn(dL0, (float)halfHeight)), midY);
+    // Does the whole band lie inside the image?  Every sample is a convex combination of the band's four corners; the sampled positions are
+    // sums of up to 62 + length f32 additions, each off by at most half an ulp of a coordinate below W + H, so they stay within `drift` of
+    // the exact ones (the bound is taken four times over, which also covers the roundings of the corners computed here).  A band that passes
+    // needs no clamp, and all its coordinates are >= 1: lbd_sample_offset<true>.
+    bool inside;
+    {
+        const float drift = (float)(62 + lengthOfLSP) * (float)(P.W + P.H) * 0x1p-22f;
+        const float ex = (float)(lengthOfLSP - 1) * dL0, ey = (float)(lengthOfLSP - 1) * dL1, rx = -62.0f * dL1, ry = 62.0f * dL0;
+        const float x_lo = cornerX + fminf(ex, 0.0f) + fminf(rx, 0.0f), x_hi = cornerX + fmaxf(ex, 0.0f) + fmaxf(rx, 0.0f);
+        const float y_lo = cornerY + fminf(ey, 0.0f) + fminf(ry, 0.0f), y_hi = cornerY + fmaxf(ey, 0.0f) + fmaxf(ry, 0.0f);
+        const bool in = x_lo >= 1.0f + drift && y_lo >= 1.0f + drift && x_hi <= (float)(P.W - 2) - drift && y_hi <= (float)(P.H - 2) - drift;
+        inside = __builtin_amdgcn_readfirstlane((int)in) != 0;
+    }
     if (lane < 63) {
-        // start corner of row hID = lane: the reference steps it row by row (sCorX0 -= dL1; sCorY0 += dL0)
-        float sCorX0 = __fadd_rn(__fadd_rn(__fmul_rn(-dL0, (float)halfWidth), __fmul_rn(dL1, (float)halfHeight)), midX);
-        float sCorY0 = __fadd_rn(__fsub_rn(__fmul_rn(-dL1, (float)halfWidth), __fmul_rn(dL0, (float)halfHeight)), midY);
-        for (int r = 0; r < lane; ++r) { sCorX0 = __fsub_rn(sCorX0, dL1); sCorY0 = __fadd_rn(sCorY0, dL0); }
-        float sCorX = sCorX0, sCorY = sCorY0;
+        float sCorX = cornerX, sCorY = cornerY;
+        for (int r = 0; r < lane; ++r) { sCorX = __fsub_rn(sCorX, dL1); sCorY = __fadd_rn(sCorY, dL0); }
         float pgdL = 0, ngdL = 0, pgdO = 0, ngdO = 0;
-        // the gathers do not depend on the running sums: addresses of 8 steps first, 16 loads in flight, then the
-        // strictly ordered accumulation
-        for (int w0 = 0; w0 < lengthOfLSP; w0 += kLbdU) {
-            int off[kLbdU];
-#pragma unroll
-            for (int u = 0; u < kLbdU; ++u) {
-                short t = (short)roundf(sCorX);
-                const short xCor = (t < 0) ? 0 : (t > imageWidth) ? imageWidth : t;
-                t = (short)roundf(sCorY);
-                const short yCor = (t < 0) ? 0 : (t > imageHeight) ? imageHeight : t;
-                off[u] = dxy_index(xCor, yCor, tiles8);
-                sCorX = __fadd_rn(sCorX, dL0);
-                sCorY = __fadd_rn(sCorY, dL1);
-            }
-            short2 vxy[kLbdU];
-#pragma unroll
-            for (int u = 0; u < kLbdU; ++u) vxy[u] = dxyImg[off[u]];
-#pragma unroll
-            for (int u = 0; u < kLbdU; ++u) {
-                if (w0 + u < lengthOfLSP) {
-                    const float fx = (float)vxy[u].x, fy = (float)vxy[u].y;
-                    const float gDL = __fadd_rn(__fmul_rn(fx, dL0), __fmul_rn(fy, dL1));
-                    const float gDO = __fadd_rn(__fmul_rn(fx, dO0), __fmul_rn(fy, dO1));
-                    if (gDL > 0) pgdL = __fadd_rn(pgdL, gDL); else ngdL = __fsub_rn(ngdL, gDL);
-                    if (gDO > 0) pgdO = __fadd_rn(pgdO, gDO); else ngdO = __fsub_rn(ngdO, gDO);
-                }
-            }
-        }
+        // the gathers do not depend on the running sums: addresses of 8 steps first, 8 loads in flight, then the strictly ordered
+        // accumulation.  Full trips carry no length test; the last, partial trip is peeled.
+        int w0 = 0;
+        if (inside)
+            for (; w0 + kLbdU <= lengthOfLSP; w0 += kLbdU)
+                lbd_trip<true, false>(dxyBytes, sCorX, sCorY, dL0, dL1, imageWidth, imageHeight, tile_row_bytes, kLbdU, pgdL, ngdL, pgdO, ngdO);
+        else
+            for (; w0 + kLbdU <= lengthOfLSP; w0 += kLbdU)
+                lbd_trip<false, false>(dxyBytes, sCorX, sCorY, dL0, dL1, imageWidth, imageHeight, tile_row_bytes, kLbdU, pgdL, ngdL, pgdO, ngdO);
+        if (w0 < lengthOfLSP)
+            lbd_trip<false, true>(dxyBytes, sCorX, sCorY, dL0, dL1, imageWidth, imageHeight, tile_row_bytes, lengthOfLSP - w0, pgdL, ngdL, pgdO, ngdO);
         const float cg = W.g[lane];
         pgdL = __fmul_rn(cg, pgdL); ngdL = __fmul_rn(cg, ngdL); pgdO = __fmul_rn(cg, pgdO); ngdO = __fmul_rn(cg, ngdO);
-        float* r = s_row[wv][lane];
+        float* r = s_row[wv][kLbdPad + lane];
         r[0] = pgdL; r[1] = ngdL; r[2] = __fmul_rn(pgdL, pgdL); r[3] = __fmul_rn(ngdL, ngdL);
         r[4] = pgdO; r[5] = ngdO; r[6] = __fmul_rn(pgdO, pgdO); r[7] = __fmul_rn(ngdO, ngdO);
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
+    // (the lane index of the per-line part is made opaque here: the compiler otherwise computes every LDS address of this part once per kernel and keeps some
+    // thirty of them in registers across the sample loops, whose own needs then pass the 64 registers that eight waves per SIMD allow)
+    int el = lane;
+    asm volatile("" : "+v"(el));
     // band sums: lane = (band, component); contributions arrive in row order hID (neighbour-below band first,
-    // own rows, then neighbour-above band), exactly the order of the reference's accumulation
-    for (int item = lane; item < 72; item += 64) {
-        const int band = item >> 3, comp = item & 7;
-        const bool sq = (comp == 2 || comp == 3 || comp == 6 || comp == 7);
-        float acc = 0;
-        for (int hID = max(0, (band - 1) * 7); hID < min(63, (band + 2) * 7); ++hID) {
-            const int rb = hID / 7;
-            const float c = rb == band ? W.l[hID % 7 + 7] : (rb == band + 1 ? W.l[hID % 7 + 14] : W.l[hID % 7]);
-            const float v = s_row[wv][hID][comp];
-            acc = sq ? __fadd_rn(acc, __fmul_rn(__fmul_rn(c, c), v)) : __fadd_rn(acc, __fmul_rn(c, v));
+    // own rows, then neighbour-above band), exactly the order of the reference's accumulation.  Row hID of band `band` carries the local
+    // weight W.l[hID - 7 (band - 1)] (its square for the second moments: W.l2, from the host): 21 steps for every band, those of the bands at
+    // both ends over the zero rows, whose +0 terms leave the non-negative sums as they are.  Band 8 (items 64..71) runs beside it as a
+    // second chain; lanes 0..7 keep it.
+    {
+        const int band = el >> 3, comp = el & 7;
+        const float* cf = s_coef[(comp >> 1) & 1];   // the squared weights for components 2, 3, 6, 7
+        const float* ra = &s_row[wv][band * 7][comp];
+        const float* rb = &s_row[wv][8 * 7][comp];
+        float acc = 0, acc8 = 0;
+#pragma unroll 1
+        for (int j0 = 0; j0 < 21; j0 += 7) {   // seven rows' reads in flight, not all 21 (registers)
+#pragma unroll
+            for (int j = 0; j < 7; ++j) {
+                const float c = cf[j0 + j];
+                acc = __fadd_rn(acc, __fmul_rn(c, ra[(j0 + j) * 8]));
+                acc8 = __fadd_rn(acc8, __fmul_rn(c, rb[(j0 + j) * 8]));
+            }
         }
-        // mean / std per band (components reordered to the descriptor layout below)
-        s_des[wv][item] = acc;
+        s_des[wv][el] = acc;
+        if (el < 8) s_des[wv][64 + el] = acc8;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_wave_barrier();
-    // mean / std per band, the two-stage normalisation and the binary string.  Element-wise work is spread over the
-    // lanes; the three sums whose order matters (tempM, tempS, temp) are chained by lane 0 over LDS values.
+    // mean / std per band, the two-stage normalisation and the binary string.  Element-wise work, the squares of the three ordered sums
+    // (tempM, tempS, temp) included, is spread over the lanes; the sums themselves are chained in registers by the lanes that own them,
+    // over terms fetched from LDS with wide reads issued together.
     float* des = s_des2[wv];
-    auto wave_sync = [] { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup"); __builtin_amdgcn_wave_barrier(); };
-    if (lane < 36) {
-        const int band = lane >> 2, k = lane & 3;
+    float* dsq = s_sq[wv];
+    if (el < 36) {
+        const int band = el >> 2, k = el & 3;
         const float invN = (band == 0 || band == 8) ? (float)(1.0 / (7 * 2.0)) : (float)(1.0 / (7 * 3.0));
         const float* sb = &s_des[wv][band * 8];   // pgdL, ngdL, pgdL2, ngdL2, pgdO, ngdO, pgdO2, ngdO2
         const int mi = (k < 2) ? k : k + 2, qi = mi + 2;   // mean from 0,1,4,5; second moment from 2,3,6,7
         const float temp = __fmul_rn(sb[mi], invN);
+        const float dev = sqrtf(__fsub_rn(__fmul_rn(sb[qi], invN), __fmul_rn(temp, temp)));
         des[band * 8 + k] = temp;
-        des[band * 8 + 4 + k] = sqrtf(__fsub_rn(__fmul_rn(sb[qi], invN), __fmul_rn(temp, temp)));
+        des[band * 8 + 4 + k] = dev;
+        dsq[band * 8 + k] = __fmul_rn(temp, temp);
+        dsq[band * 8 + 4 + k] = __fmul_rn(dev, dev);
     }
     wave_sync();
-    if (lane == 0) {
-        float tempM = 0, tempS = 0;
-        for (int band = 0; band < 9; ++band) {
-            const float* v = des + 8 * band;
-            for (int k = 0; k < 4; ++k) tempM = __fadd_rn(tempM, __fmul_rn(v[k], v[k]));
-            for (int k = 4; k < 8; ++k) tempS = __fadd_rn(tempS, __fmul_rn(v[k], v[k]));
+    if (el < 2) {   // lane 0: tempM over the means, lane 1: tempS over the deviations, band by band
+        float acc = 0;
+#pragma unroll 1
+        for (int b0 = 0; b0 < 9; b0 += 3) {   // three bands' terms per round trip (registers)
+            float4 t[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) t[q] = *reinterpret_cast<const float4*>(dsq + 8 * (b0 + q) + 4 * el);
+#pragma unroll
+            for (int q = 0; q < 3; ++q) acc = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(acc, t[q].x), t[q].y), t[q].z), t[q].w);
         }
-        s_norm[wv][0] = __fdiv_rn(1.0f, sqrtf(tempM));
-        s_norm[wv][1] = __fdiv_rn(1.0f, sqrtf(tempS));
+        s_norm[wv][el] = __fdiv_rn(1.0f, sqrtf(acc));
     }
     wave_sync();
-    for (int i = lane; i < 72; i += 64) {
+    for (int i = el; i < 72; i += 64) {
         float v = __fmul_rn(des[i], s_norm[wv][(i >> 2) & 1]);
         if ((double)v > 0.4) v = (float)0.4;
         des[i] = v;
+        dsq[i] = __fmul_rn(v, v);
     }
     wave_sync();
-    if (lane == 0) {
+    if (el == 0) {
         float temp = 0;
-        for (int i = 0; i < 72; ++i) temp = __fadd_rn(temp, __fmul_rn(des[i], des[i]));
+#pragma unroll 1
+        for (int i0 = 0; i0 < 72; i0 += 24) {   // 24 terms per round trip (registers)
+            float4 t[6];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) t[q] = *reinterpret_cast<const float4*>(dsq + i0 + 4 * q);
+#pragma unroll
+            for (int q = 0; q < 6; ++q) temp = __fadd_rn(__fadd_rn(__fadd_rn(__fadd_rn(temp, t[q].x), t[q].y), t[q].z), t[q].w);
+        }
         s_norm[wv][2] = __fdiv_rn(1.0f, sqrtf(temp));
     }
     wave_sync();
-    for (int i = lane; i < 72; i += 64) des[i] = __fmul_rn(des[i], s_norm[wv][2]);
+    for (int i = el; i < 72; i += 64) des[i] = __fmul_rn(des[i], s_norm[wv][2]);
     wave_sync();
-    if (lane < 32) {
-        const float* f1 = des + 8 * c_comb[lane][0];
-        const float* f2 = des + 8 * c_comb[lane][1];
+    if (el < 32) {
+        const float* f1 = des + 8 * c_comb[el][0];
+        const float* f2 = des + 8 * c_comb[el][1];
         unsigned r = 0;
         for (int i = 0; i < 8; ++i) r += (f1[i] > f2[i]) ? (1u << i) : 0u;
-        P.all_lbd[((size_t)b * kLineCap + li) * 32 + lane] = (uint8_t)r;
+        P.all_lbd[((size_t)b * kLineCap + li) * 32 + el] = (uint8_t)r;
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
     __builtin_amdgcn_wave_barrier();
@@ -1897,10 +1988,10 @@ void launch_line_front(hipStream_t st, const LinePlanes& P, const LsdParams& lp,
     mark(5);
     if (!sobel_first) hipLaunchKernelGGL(k_blur_sobel, dim3(sobel_tiles, B), dim3(256), 0, st, P.img, P.img_frame_stride, P.img_pitch, P.dxy, P.W, P.H, t5, sobel_td);
     mark(6);
-    // few resident waves per frame: their 63-row working sets have to stay in L1 / L2.  Workgroups of four waves per frame, kernel alone / step: 1: 1.41 ms /
-    // 87.4 k frames/s, 2: 1.37 / 88.0 k, 3: 1.30 / 86.7 k, 4: 1.40 / 87.5 k, 8: 1.64 / 86.8 k, 16: 1.78 / 86.8 k (sessions 35, 36; the step numbers are within
-    // their run-to-run spread of each other below 8)
-    const int lbd_blocks = B >= 64 ? 2 : 16;   // a single frame (plp_line_extract): the chip is empty, one wave per line
+    // few resident waves per frame: their 63-row working sets have to stay in L1 / L2.  Workgroups of four waves per frame, kernel alone, with the lines drawn
+    // from the frame's ticket: 1: 1.11 ms, 2: 1.05, 3: 0.98, 4: 1.02 (with a fixed stride: 2: 1.11, 3: 1.04); the step is the same within its run-to-run spread
+    // for all of them (profiles/r23_lbd.md)
+    const int lbd_blocks = B >= 64 ? 3 : 16;   // a single frame (plp_line_extract): the chip is empty, one wave per line
     hipLaunchKernelGGL(k_lbd, dim3(lbd_blocks, B), dim3(256), 0, st, P, w);
     mark(7);
     hipLaunchKernelGGL(k_line_finalize, dim3(B), dim3(64), 0, st, P, lp, out_kl, out_lbd, out_fn, cap, out_counts);
