@@ -227,6 +227,10 @@ plp_status plp_line_debug_read(plp_line* ctx, plp_line_debug_id what, int32_t fr
  * src/PLPSLAM/match/angle_checker.h:165-176; the kernels reproduce libstdc++'s algorithm so that ties fall as in a reference built with
  * GCC): idx = the indices 0..n-1, n <= 64, in that order.  depth_limit < 0 = the library's recursion budget.  No GPU needed. */
 int32_t plp_model_index_sort_host(const int32_t* sizes, int32_t n, int32_t depth_limit, uint32_t* idx);
+/* Host model of the sort the quadtree kernel runs on levels of a few hundred candidates (csrc/quadtree_model.hpp qt_rank): perm[r] = the index of the
+ * entry of rank r by (keys[i] >> shift, i), i.e. a stable sort by the shifted key.  The shifted keys must be below 2^31.  No GPU needed.  Returns n, or -1
+ * for a bad argument. */
+int32_t plp_model_quadtree_rank_sort_host(const uint32_t* keys, int32_t n, int32_t shift, uint32_t* perm);
 /* Host model of the exact seed sort (csrc/seed_sort_model.hpp): std::__introsort_loop, in place, on n entries whose sort key is bits 20..29
  * (larger first), computed as the rank-paired partitions the kernel runs; depth_limit < 0 = the library's 2 * floor(log2 n).  skip_key > 0:
  * parts that can only hold keys below it are left as they are, as the kernel leaves the undefined pixels of a frame (they are sorted along

@@ -69,6 +69,7 @@ _API = [
     ("plp_orb_pyramid_host", C.c_int, [_VP, _I32, _I32, _VP, _SZ]),
     ("plp_orb_debug_read", C.c_int, [_VP, C.c_int, _I32, _I32, _VP, _SZ, _VP]),
     ("plp_model_quadtree_host", _I32, [_VP, _I32, _I32, _I32, C.c_uint32, _VP]),
+    ("plp_model_quadtree_rank_sort_host", _I32, [_VP, _I32, _I32, _VP]),
     ("plp_model_sincos_host", _I32, [_VP, C.c_int64, _VP, _VP, _VP]),
     ("plp_model_index_sort_host", _I32, [_VP, _I32, _I32, _VP]),
     ("plp_model_null_vector4_host", _I32, [_VP, _I32, _VP, _VP]),
@@ -249,6 +250,14 @@ def model_quadtree(xys, level_w, level_h, quota):
     out = np.zeros(max(len(xys), 1), np.int32)
     m = lib().plp_model_quadtree_host(_p(xys), len(xys), level_w, level_h, quota, _p(out))
     return out[:m].copy()
+
+
+def model_quadtree_rank_sort(keys, shift=0):
+    """Host model of the quadtree kernel's rank sort of small levels (no GPU needed): the indices of `keys` in the order of a stable sort by keys >> shift"""
+    k = np.ascontiguousarray(keys, np.uint32)
+    perm = np.zeros(max(len(k), 1), np.uint32)
+    assert lib().plp_model_quadtree_rank_sort_host(_p(k), len(k), int(shift), _p(perm)) == len(k)
+    return perm[:len(k)].copy()
 
 
 SEED_ORDER_STABLE, SEED_ORDER_LIBSTDCXX = 0, 1          # plp_seed_order (include/plp_front.h)

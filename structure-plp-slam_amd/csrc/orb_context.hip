@@ -20,6 +20,8 @@ void launch_quadtree(hipStream_t st, const LevelDev* d_lv, int n_levels, int n_c
                      const int32_t* cell_count, int32_t* sel, int32_t* sel_count, int total_sel_cap, uint32_t* qt_scratch,
                      size_t qt_scratch_frame_stride, int32_t* status, int B, int max_quota);
 size_t quadtree_scratch_bytes_per_frame(const LevelDev* h_lv, int n_levels);
+size_t quadtree_lds_bytes(int max_quota);   // dynamic LDS of one k_quadtree workgroup for that largest per-level quota
+hipError_t quadtree_configure();            // raises k_quadtree's dynamic-LDS limit to 160 KB on the current device
 }
 
 using namespace plp;
@@ -42,6 +44,7 @@ struct plp_orb {
     DevBuf pyr, blur, l0copy, cell_cand, cell_count, sel, sel_count, status, qt_scratch, d_mask;
     size_t l0copy_frame_stride = 0, qt_frame_stride = 0;
     int max_quota = 0;
+    bool qt_big_lds_ok = false;   // k_quadtree may take more than 64 KB of dynamic LDS on this context's device (quadtree_configure at creation)
     // single-frame host API staging
     DevBuf s_kps, s_desc, s_counts;
     DevBuf stereo_corr, stereo_stage;
@@ -143,6 +146,8 @@ plp_status build_geometry_impl(plp_orb* c, int rows, int cols) {
     }
     if (3 * c->max_quota + 8 > kQtMaxNodesLds && max_cells > 1024)   // a quota above 1960 halves the kernel's cell-prefix block (quadtree_kernel.hip kQtBlkWordsSmall)
         return set_error(PLP_ERR_UNSUPPORTED, "frame/keypoint budget exceeds the quadtree kernel limits (a quota above 1960 per level needs levels of at most 1024 cells)");
+    if (!c->qt_big_lds_ok && quadtree_lds_bytes(c->max_quota) > 64 * 1024)
+        return set_error(PLP_ERR_UNSUPPORTED, "frame/keypoint budget exceeds the quadtree kernel limits (this device refused more than 64 KB of LDS per workgroup: quota per level <= 729)");
     PLP_HIP(c->d_lv.upload(c->h_lv.data(), sizeof(LevelDev) * nl, c->stream));
     PLP_HIP(c->d_cells.upload(c->geo.cells.data(), sizeof(CellDesc) * c->geo.cells.size(), c->stream));
     // resize tables: 8 int16 arrays back to back
@@ -284,6 +289,8 @@ plp_status plp_orb_create(const plp_orb_params* params, int device, plp_orb** ou
     c->rects.assign(params->mask_rects, params->mask_rects + 4 * (size_t)params->n_mask_rects);
     c->p.mask_rects = nullptr;
     c->device = device;
+    c->qt_big_lds_ok = quadtree_configure() == hipSuccess;   // per context, for the context's device (as grow_configure() in line_context.hip); checked in build_geometry_impl
+    (void)hipGetLastError();
     if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return set_error(PLP_ERR_HIP, "hipStreamCreate failed"); }
     reinitialize(c);
     *out = c;
@@ -570,6 +577,14 @@ int32_t plp_model_quadtree_host(const int32_t* xys, int32_t n, int32_t level_w, 
     std::vector<int> pick = quadtree_select(cs.data(), n, g.lv[0], quota);
     for (size_t i = 0; i < pick.size(); ++i) out_idx[i] = pick[i];
     return (int32_t)pick.size();
+}
+
+// Host model of the rank sort of the quadtree kernel's small levels (qt_rank_sort_host), callable without a GPU (tests/test_quadtree_rank_model.py).
+int32_t plp_model_quadtree_rank_sort_host(const uint32_t* keys, int32_t n, int32_t shift, uint32_t* perm) {
+    if (n < 0 || shift < 0 || shift > 31 || (n > 0 && (!keys || !perm))) return -1;
+    for (int i = 0; i < n; ++i) if ((keys[i] >> shift) >= 0x80000000u) return -1;   // tree keys are below 2^31
+    qt_rank_sort_host(keys, n, shift, perm);
+    return n;
 }
 
 }  // extern "C"

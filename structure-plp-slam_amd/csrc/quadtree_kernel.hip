@@ -3,7 +3,8 @@
 // Restates distribute_keypoints_via_tree (reference src/PLPSLAM/feature/orb_extractor.cc:468-685)
 // in the sort-based form proven equivalent on the host in quadtree_model.hpp:
 //   1. gather the level's per-cell candidate lists in reference order (cell row, cell col, row-major)
-//   2. one tree key per candidate (initial node + 2 bits per split), LSD radix sort by key
+//   2. one tree key per candidate (initial node + 2 bits per split), stable sort by key: by rank inside LDS for levels of at most kQtSmallN
+//      candidates (which never touch the HBM scratch), LSD radix sort over the scratch for larger ones
 //   3. every node = a range of the sorted array; whole-list split passes and the "fullest first"
 //      fill phase run data-parallel over node records with prefix sums giving the list order
 //   4. per node: maximum score, ties to the smallest candidate index
@@ -23,6 +24,17 @@ constexpr int kQtMaxNodes = kQtMaxNodesLds;   // hard upper bound of the node ar
 // segments, then the sorted-key cache (blk_words keys); larger levels use the HBM scratch.  blk_words = 2048 (8 KB: 256 segments = 16384 candidates in LDS) -- or 1024
 // for a per-level quota above 1960 (round 6: the 4 KB that buys fit the node arrays of one level at K = 2000, the reference's single-level configuration).
 constexpr int kQtBlkWords = 2048, kQtBlkWordsSmall = 1024;
+// Levels of at most kQtSmallN candidates (every level of a 640 x 480 frame at K = 1000: 126 - 440) are gathered by element, sorted by RANK in LDS and selected from LDS:
+// no pass over the HBM scratch, one barrier for the sort (profiles/r24_quadtree.md).  While it sorts, a level keeps three words per candidate (sort key, full key, packed
+// candidate) in the space of the node arrays, which are idle until the initial nodes are written -- at least 256 * 26 bytes of them -- and afterwards ten bytes per
+// candidate (sorted key, packed candidate, u16 index) in the 4 * blk_words bytes of the block: qt_small_limit().
+#if defined(PLP_QT_PROF) && defined(PLP_QT_PROF_SMALL_N)
+constexpr int kQtSmallN = PLP_QT_PROF_SMALL_N;   // the diagnostic build only: 0 sends every level down the large path
+#else
+constexpr int kQtSmallN = 512;
+#endif
+static_assert(kQtSmallN % 4 == 0 && 3 * 4 * kQtSmallN <= 256 * 26, "the rank sort's three arrays alias the node arrays of the smallest max_nodes (256)");
+__host__ __device__ constexpr int qt_small_limit(int blk_words) { return 2 * blk_words / 5 < kQtSmallN ? 2 * blk_words / 5 : kQtSmallN; }
 
 // LDS of one workgroup, carved from dynamic shared memory: the node arrays are sized by the largest per-level quota
 // (a list never holds more than 3 * quota + 3 nodes), so that 2-3 workgroups fit a CU for the usual K = 1000..2000
@@ -167,6 +179,36 @@ template <class KeyArr> __device__ __forceinline__ int dev_split(const KeyArr& K
     return (o1 > s) + (o2 > o1) + (o3 > o2) + (e > o3);
 }
 
+// Phase clocks of a diagnostic build (-DPLP_QT_PROF, tools/quadtree_phases.py; never the shipped library): thread 0 of every workgroup adds its shader-clock
+// ticks per phase {gather, sort, sorted-key copy, initial nodes, phase 1, phase 2, selection} to its level's row of g_qt_prof, then the number of workgroups, of
+// candidates, of phase-1 and phase-2 passes, the largest population of a final node (a maximum), the final nodes and the workgroups that took the small path.
+#ifdef PLP_QT_PROF
+__device__ unsigned long long g_qt_prof[kMaxLevels][16];
+#define QT_PROF_TICK(k) (qt_t[k] = clock64())
+#define QT_PROF_COUNT(v) (++v)
+#define QT_PROF_REPORT()                                                                                                  \
+    do {                                                                                                                  \
+        if (tid == 0) {                                                                                                   \
+            int pop = 0;                                                                                                  \
+            for (int i = 0; i < m_out; ++i) pop = max(pop, (int)S.ne(cur)[i] - (int)S.ns(cur)[i]);                        \
+            unsigned long long* P = g_qt_prof[level];                                                                     \
+            for (int k = 0; k < 7; ++k) atomicAdd(&P[k], (unsigned long long)(qt_t[k + 1] - qt_t[k]));                    \
+            atomicAdd(&P[7], 1ull); atomicAdd(&P[8], (unsigned long long)n); atomicAdd(&P[9], (unsigned long long)qt_np1); \
+            atomicAdd(&P[10], (unsigned long long)qt_np2); atomicMax(&P[11], (unsigned long long)pop);                    \
+            atomicAdd(&P[12], (unsigned long long)m); atomicAdd(&P[13], (unsigned long long)small);                       \
+        }                                                                                                                 \
+    } while (0)
+extern "C" int plp_debug_quadtree_phases(unsigned long long* out, int reset) {
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_qt_prof), sizeof(g_qt_prof)) != hipSuccess) return 1;
+    if (reset) { static const unsigned long long zero[kMaxLevels][16] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_qt_prof), zero, sizeof(zero)) != hipSuccess) return 1; }
+    return 0;
+}
+#else
+#define QT_PROF_TICK(k) ((void)0)
+#define QT_PROF_COUNT(v) ((void)0)
+#define QT_PROF_REPORT() ((void)0)
+#endif
+
 __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ lv, int n_cells_total,
                                                   const uint32_t* __restrict__ cell_cand, const int32_t* __restrict__ cell_count,
                                                   int32_t* __restrict__ sel, int32_t* __restrict__ sel_count, int total_sel_cap,
@@ -179,6 +221,11 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
     const int level = blockIdx.x, frame = blockIdx.y;
     const LevelDev L = lv[level];
     const int N = L.quota;
+#ifdef PLP_QT_PROF
+    long long qt_t[8];
+    int qt_np1 = 0, qt_np2 = 0;
+#endif
+    QT_PROF_TICK(0);
     uint32_t* cand = reinterpret_cast<uint32_t*>(scratch + (size_t)frame * scratch_frame_stride + L.qt_off);
     uint32_t* key = cand + L.qt_cap;
     uint32_t* idxA = key + L.qt_cap;
@@ -191,74 +238,109 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
     const int32_t* cc = cell_count + (size_t)frame * n_cells_total + L.cell_base;
     for (int c = tid; c < L.n_cells; c += 256) S.big[c] = (uint32_t)cc[c];
     wg_barrier();
-    int n = (int)block_scan_excl(S.big, L.n_cells, S.partial);
+    int n = __builtin_amdgcn_readfirstlane((int)block_scan_excl(S.big, L.n_cells, S.partial));
     if (n > L.qt_cap) { if (tid == 0) atomicOr(status, 2); n = L.qt_cap; }
-    for (int c = wv; c < L.n_cells; c += 4) {
-        const int base = (int)S.big[c], cnt = cc[c];
-        const uint32_t* src = cell_cand + ((size_t)frame * n_cells_total + L.cell_base + c) * kCellCap;
-        for (int j = lane; j < cnt; j += 64) {
-            const int dst = base + j;
-            if (dst < n) {
-                const uint32_t pk = src[j];
-                cand[dst] = pk;
-                key[dst] = dev_qt_key((int)(pk & 0xfff), (int)((pk >> 12) & 0xfff), L);
-            }
-        }
-    }
-    wg_barrier();
     if (n == 0) { if (tid == 0) *out_cnt = 0; return; }
-
-    // ---- 2. LSD radix sort (4 bits per pass) of candidate indices by key bits [sort_lo, sort_hi)
-    const int nseg = (n + 63) >> 6;
+    // one scalar branch per workgroup: the small path keeps the level in LDS from here on and never touches cand / key / idxA / idxB
+    const bool small = n <= qt_small_limit(blk_words);
+    uint32_t* const spk = S.big + n;                                  // small path: packed candidates in key order ...
+    uint16_t* const sid = reinterpret_cast<uint16_t*>(S.big + 2 * n);   // ... and their indices in reference order, behind the sorted keys S.big[0, n)
     uint32_t* src = idxA;
     uint32_t* dst = idxB;
-    bool first = true;
-    // The radix counters live in LDS, or -- levels with more than blk_words / 8 segments -- in HBM: a DualArr (DS or GLOBAL instructions behind a scalar branch)
-    const DualArr<uint16_t> CNT = dual_arr(S.cnt, cnt_hbm, nseg <= kQtSegLds);
-    for (int shift = L.sort_lo; shift < L.sort_hi; shift += 4) {
-        for (int seg = wv; seg < nseg; seg += 4) {
-            const int i = seg * 64 + lane;
-            unsigned d = 16;
-            if (i < n) d = (key[first ? (uint32_t)i : src[i]] >> shift) & 15u;
-            uint32_t mine = 0;
-#pragma unroll
-            for (unsigned v = 0; v < 16; ++v) {
-                const unsigned long long bal = __ballot(d == v);
-                if ((unsigned)lane == v) mine = (uint32_t)__popcll(bal);
+    if (small) {
+        // by element: the candidate's cell from the LDS prefix (the last cell whose prefix is <= i), then ONE global load
+        uint32_t* const uk = S.pk;            // key >> sort_lo, what the radix passes compare; padded to a multiple of four with 0xffffffff
+        uint32_t* const fk = uk + kQtSmallN;  // full keys
+        uint32_t* const upk = fk + kQtSmallN; // packed candidates
+        for (int i = tid; i < n; i += 256) {
+            int lo = 0, hi = L.n_cells;
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (S.big[mid] <= (uint32_t)i) lo = mid + 1; else hi = mid; }
+            const int c = lo - 1;
+            const uint32_t pk = cell_cand[((size_t)frame * n_cells_total + L.cell_base + c) * kCellCap + ((uint32_t)i - S.big[c])];
+            const uint32_t k = dev_qt_key((int)(pk & 0xfff), (int)((pk >> 12) & 0xfff), L);
+            uk[i] = k >> L.sort_lo; fk[i] = k; upk[i] = pk;
+        }
+        if (tid < 4 && n + tid < ((n + 3) & ~3)) uk[n + tid] = 0xffffffffu;
+        wg_barrier();
+        QT_PROF_TICK(1);
+        // ---- 2s. sort by rank (qt_rank, quadtree_model.hpp): the stable order the radix passes produce, from broadcast reads of all keys, four per ds_read_b128
+        const int n4 = (n + 3) & ~3;
+        const auto load4 = [uk](int j) { const uint4 q = *reinterpret_cast<const uint4*>(uk + j); return QtKey4{q.x, q.y, q.z, q.w}; };
+        for (int i0 = __builtin_amdgcn_readfirstlane(wv) * 64; i0 < n; i0 += 256) {
+            const int i = i0 + lane;
+            const uint32_t rank = qt_rank(load4, n4, i0, i, uk[min(i, n - 1)]);
+            if (i < n) { S.big[rank] = fk[i]; spk[rank] = upk[i]; sid[rank] = (uint16_t)i; }   // the block's cell prefix is dead: every wave is past the gather's barrier
+        }
+        QT_PROF_TICK(2);
+    } else {
+        // one wave per cell, through the HBM scratch
+        for (int c = wv; c < L.n_cells; c += 4) {
+            const int base = (int)S.big[c], cnt = cc[c];
+            const uint32_t* cell = cell_cand + ((size_t)frame * n_cells_total + L.cell_base + c) * kCellCap;
+            for (int j = lane; j < cnt; j += 64) {
+                const int at = base + j;
+                if (at < n) {
+                    const uint32_t pk = cell[j];
+                    cand[at] = pk;
+                    key[at] = dev_qt_key((int)(pk & 0xfff), (int)((pk >> 12) & 0xfff), L);
+                }
             }
-            if (lane < 16) CNT.set(lane * nseg + seg, (uint16_t)mine);
         }
         wg_barrier();
-        block_scan_excl_arr<uint16_t>(CNT, 16 * nseg, S.partial);
-        for (int seg = wv; seg < nseg; seg += 4) {
-            const int i = seg * 64 + lane;
-            unsigned d = 16;
-            uint32_t id = 0;
-            if (i < n) { id = first ? (uint32_t)i : src[i]; d = (key[id] >> shift) & 15u; }
-            // the lanes holding the same digit as this one (d = 16: the lanes past the end), from one ballot per BIT of d; selecting the
-            // lane's own of sixteen per-value ballots had cost 30 registers for their copies (the kernel's register peak)
-            unsigned long long mybal = ~0ull;
+        QT_PROF_TICK(1);
+
+        // ---- 2. LSD radix sort (4 bits per pass) of candidate indices by key bits [sort_lo, sort_hi)
+        const int nseg = (n + 63) >> 6;
+        bool first = true;
+        // The radix counters live in LDS, or -- levels with more than blk_words / 8 segments -- in HBM: a DualArr (DS or GLOBAL instructions behind a scalar branch)
+        const DualArr<uint16_t> CNT = dual_arr(S.cnt, cnt_hbm, nseg <= kQtSegLds);
+        for (int shift = L.sort_lo; shift < L.sort_hi; shift += 4) {
+            for (int seg = wv; seg < nseg; seg += 4) {
+                const int i = seg * 64 + lane;
+                unsigned d = 16;
+                if (i < n) d = (key[first ? (uint32_t)i : src[i]] >> shift) & 15u;
+                uint32_t mine = 0;
 #pragma unroll
-            for (unsigned bit = 0; bit < 5; ++bit) {
-                const bool one = (d >> bit) & 1u;
-                const unsigned long long bal = __ballot(one);
-                mybal &= one ? bal : ~bal;
+                for (unsigned v = 0; v < 16; ++v) {
+                    const unsigned long long bal = __ballot(d == v);
+                    if ((unsigned)lane == v) mine = (uint32_t)__popcll(bal);
+                }
+                if (lane < 16) CNT.set(lane * nseg + seg, (uint16_t)mine);
             }
-            if (i < n) dst[(uint32_t)CNT[d * nseg + seg] + (uint32_t)__popcll(mybal & ((1ull << lane) - 1ull))] = id;
+            wg_barrier();
+            block_scan_excl_arr<uint16_t>(CNT, 16 * nseg, S.partial);
+            for (int seg = wv; seg < nseg; seg += 4) {
+                const int i = seg * 64 + lane;
+                unsigned d = 16;
+                uint32_t id = 0;
+                if (i < n) { id = first ? (uint32_t)i : src[i]; d = (key[id] >> shift) & 15u; }
+                // the lanes holding the same digit as this one (d = 16: the lanes past the end), from one ballot per BIT of d; selecting the
+                // lane's own of sixteen per-value ballots had cost 30 registers for their copies (the kernel's register peak)
+                unsigned long long mybal = ~0ull;
+#pragma unroll
+                for (unsigned bit = 0; bit < 5; ++bit) {
+                    const bool one = (d >> bit) & 1u;
+                    const unsigned long long bal = __ballot(one);
+                    mybal &= one ? bal : ~bal;
+                }
+                if (i < n) dst[(uint32_t)CNT[d * nseg + seg] + (uint32_t)__popcll(mybal & ((1ull << lane) - 1ull))] = id;
+            }
+            wg_barrier();
+            uint32_t* t = src; src = dst; dst = t;
+            first = false;
         }
-        wg_barrier();
-        uint32_t* t = src; src = dst; dst = t;
-        first = false;
-    }
-    // src now holds candidate indices in key order (identity if no pass ran); dst <- sorted keys
-    for (int i = tid; i < n; i += 256) {
-        const uint32_t id = first ? (uint32_t)i : src[i];
-        if (first) src[i] = id;
-        const uint32_t k = key[id];
-        dst[i] = k;
-        if (n <= kQtKeyCache) S.big[i] = k;
+        QT_PROF_TICK(2);
+        // src now holds candidate indices in key order (identity if no pass ran); dst <- sorted keys
+        for (int i = tid; i < n; i += 256) {
+            const uint32_t id = first ? (uint32_t)i : src[i];
+            if (first) src[i] = id;
+            const uint32_t k = key[id];
+            dst[i] = k;
+            if (n <= kQtKeyCache) S.big[i] = k;
+        }
     }
     wg_barrier();
+    QT_PROF_TICK(3);
     const uint32_t* sidx = src;
     // The sorted keys are read from their LDS copy when it exists, from the HBM scratch otherwise: a DualArr again
     const DualArr<uint32_t> K = dual_arr(S.big, dst, n <= kQtKeyCache);
@@ -274,17 +356,20 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
             S.ns(0)[m] = (uint16_t)s; S.ne(0)[m] = (uint16_t)lo; S.nd(0)[m] = 0; S.nleaf(0)[m] = (lo - s == 1);
             ++m; s = lo;
         }
-        S.misc[0] = m;
+        S.misc[0] = m; S.misc[1] = 0; S.misc[3] = 0;
     }
     wg_barrier();
+    QT_PROF_TICK(4);
     int m = S.misc[0];
     bool filled = false, failed = false;
 
-    // ---- 3b. phase 1: split every non-leaf entry, children to the front in reverse creation order
+    // ---- 3b. phase 1: split every non-leaf entry, children to the front in reverse creation order.  The pool size (children with more than one point) is counted
+    // in misc[1] and misc[3] by turns: a pass resets the NEXT pass's counter behind its first barrier -- every thread has read that counter's last value before it got
+    // there, and three more barriers follow before the next pass adds to it -- so neither the reset nor the end of the loop needs a barrier of its own
+    int pslot = 1;
     while (true) {
+        QT_PROF_COUNT(qt_np1);
         const int prev = m;
-        if (tid == 0) S.misc[1] = 0;   // pool size (children with more than one point)
-        wg_barrier();
         for (int i = tid; i < m; i += 256) {
             if (S.nleaf(cur)[i]) { S.pk[i] = 1u << 16; continue; }
             int o1, o2, o3;
@@ -293,9 +378,10 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
             S.b1[i] = (uint16_t)o1; S.b2[i] = (uint16_t)o2; S.b3[i] = (uint16_t)o3;
             S.pk[i] = (uint32_t)k;
             const int big = (o1 - s > 1) + (o2 - o1 > 1) + (o3 - o2 > 1) + (e - o3 > 1);
-            if (big) atomicAdd(&S.misc[1], big);
+            if (big) atomicAdd(&S.misc[pslot], big);
         }
         wg_barrier();
+        if (tid == 0) S.misc[pslot ^ 2] = 0;
         const uint32_t tot = block_scan_excl(S.pk, m, S.partial);
         const int T = (int)(tot & 0xffff), kept = (int)(tot >> 16);
         const int m_new = T + kept;
@@ -322,34 +408,36 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
         }
         wg_barrier();
         cur = nxt; m = m_new;
-        const int pool = S.misc[1];
+        const int pool = S.misc[pslot];
+        pslot ^= 2;
         if (N <= m || m == prev) { filled = true; break; }
         if (N < m + pool) break;
-        wg_barrier();
     }
 
     // ---- 3c. phase 2: split the fullest entries first until the quota is reached
+    QT_PROF_TICK(5);
     while (!filled && !failed) {
+        QT_PROF_COUNT(qt_np2);
         const int prev = m;
         // pool = entries with more than one point, in list order (ordered compaction)
         for (int i = tid; i < m; i += 256) S.pk[i] = (uint32_t)(S.ne(cur)[i] - S.ns(cur)[i] > 1);
         wg_barrier();
-        const int p = (int)block_scan_excl(S.pk, m, S.partial);
-        for (int i = tid; i < m; i += 256)
-            if (S.ne(cur)[i] - S.ns(cur)[i] > 1) S.pool_pos[S.pk[i]] = (uint16_t)i;
+        const int p = __builtin_amdgcn_readfirstlane((int)block_scan_excl(S.pk, m, S.partial));
+        // ... with each pool entry's order key beside it (b1 and b2, one u32 array while no split is pending): the ranking below reads ONE broadcast word per
+        // comparison instead of pool_pos -> ne, ns
+        uint32_t* const pkey = reinterpret_cast<uint32_t*>(S.b1);
+        for (int i = tid; i < m; i += 256) {
+            const int cnt = S.ne(cur)[i] - S.ns(cur)[i];
+            if (cnt > 1) { const uint32_t a = S.pk[i]; S.pool_pos[a] = (uint16_t)i; pkey[a] = ((uint32_t)cnt << 12) | (uint32_t)(4095 - min(i, 4095)); }
+        }
         wg_barrier();
         if (p == 0) break;   // nothing left to split
         // order: count descending, then list position ascending (== creation descending)
         for (int a = tid; a < p; a += 256) {
-            const int ia = S.pool_pos[a];
-            const uint32_t ka = ((uint32_t)(S.ne(cur)[ia] - S.ns(cur)[ia]) << 12) | (uint32_t)(4095 - min(ia, 4095));
+            const uint32_t ka = pkey[a];
             int rank = 0;
-            for (int b = 0; b < p; ++b) {
-                const int ib = S.pool_pos[b];
-                const uint32_t kb = ((uint32_t)(S.ne(cur)[ib] - S.ns(cur)[ib]) << 12) | (uint32_t)(4095 - min(ib, 4095));
-                rank += kb > ka;
-            }
-            S.pool_sorted[rank] = (uint16_t)ia;
+            for (int b = 0; b < p; ++b) rank += pkey[b] > ka;
+            S.pool_sorted[rank] = S.pool_pos[a];
         }
         wg_barrier();
         // split in sorted order; inclusive gain prefix decides where the quota is met
@@ -422,24 +510,41 @@ __global__ __launch_bounds__(256) void k_quadtree(const LevelDev* __restrict__ l
         return;
     }
     // ---- 4. best candidate per node: max score, then smallest candidate index
+    QT_PROF_TICK(6);
     const int m_out = min(m, L.sel_cap);
     if (m > L.sel_cap && tid == 0) atomicOr(status, 2);
-    for (int i = tid; i < m_out; i += 256) {
-        const int s = S.ns(cur)[i], e = S.ne(cur)[i];
-        if (s >= n || e > n || s >= e) { atomicOr(status, 8); out_sel[i] = 0; continue; }   // cannot happen: node ranges partition [0, n)
-        uint32_t best_id = sidx[s];
-        if (best_id >= (uint32_t)n) { atomicOr(status, 8); best_id = (uint32_t)(n - 1); }   // cannot happen: the sort permutes [0, n)
-        uint32_t best_pk = cand[best_id];
-        for (int t = s + 1; t < e; ++t) {
-            uint32_t id = sidx[t];
-            if (id >= (uint32_t)n) { atomicOr(status, 8); id = (uint32_t)(n - 1); }
-            const uint32_t pk = cand[id];
-            const uint32_t sa = pk >> 24, sb = best_pk >> 24;
-            if (sa > sb || (sa == sb && id < best_id)) { best_id = id; best_pk = pk; }
+    if (small) {   // the same walk over the LDS copies (a loop of its own: one loop over a pointer chosen at run time would be FLAT accesses)
+        for (int i = tid; i < m_out; i += 256) {
+            const int s = S.ns(cur)[i], e = S.ne(cur)[i];
+            if (s >= n || e > n || s >= e) { atomicOr(status, 8); out_sel[i] = 0; continue; }   // cannot happen: node ranges partition [0, n)
+            uint32_t best_id = sid[s], best_pk = spk[s];
+            for (int t = s + 1; t < e; ++t) {
+                const uint32_t id = sid[t], pk = spk[t];
+                const uint32_t sa = pk >> 24, sb = best_pk >> 24;
+                if (sa > sb || (sa == sb && id < best_id)) { best_id = id; best_pk = pk; }
+            }
+            out_sel[i] = (int32_t)best_pk;
         }
-        out_sel[i] = (int32_t)best_pk;
+    } else {
+        for (int i = tid; i < m_out; i += 256) {
+            const int s = S.ns(cur)[i], e = S.ne(cur)[i];
+            if (s >= n || e > n || s >= e) { atomicOr(status, 8); out_sel[i] = 0; continue; }   // cannot happen: node ranges partition [0, n)
+            uint32_t best_id = sidx[s];
+            if (best_id >= (uint32_t)n) { atomicOr(status, 8); best_id = (uint32_t)(n - 1); }   // cannot happen: the sort permutes [0, n)
+            uint32_t best_pk = cand[best_id];
+            for (int t = s + 1; t < e; ++t) {
+                uint32_t id = sidx[t];
+                if (id >= (uint32_t)n) { atomicOr(status, 8); id = (uint32_t)(n - 1); }
+                const uint32_t pk = cand[id];
+                const uint32_t sa = pk >> 24, sb = best_pk >> 24;
+                if (sa > sb || (sa == sb && id < best_id)) { best_id = id; best_pk = pk; }
+            }
+            out_sel[i] = (int32_t)best_pk;
+        }
     }
     if (tid == 0) *out_cnt = m_out;
+    QT_PROF_TICK(7);
+    QT_PROF_REPORT();
 }
 
 size_t quadtree_scratch_bytes_per_frame(const LevelDev* h_lv, int n_levels) {
@@ -448,16 +553,29 @@ size_t quadtree_scratch_bytes_per_frame(const LevelDev* h_lv, int n_levels) {
     return (end + 255) / 256 * 256;
 }
 
+// node arrays for 3 * quota + 8 entries (the bound of the lists, see QtShared), rounded to 8: at K = 1000 (quota 217) 25.5 KB, so that THREE
+// workgroups fit the 77 KB two region-growing workgroups leave on a CU (rounded to a power of two it was 34.9 KB: two)
+static void qt_layout(int max_quota, int& mn, int& blk) {
+    const int want = std::max(256, (3 * max_quota + 8 + 7) / 8 * 8);
+    const bool small_blk = want > kQtMaxNodes;                    // a quota above 1960 (plp_orb_create has checked that it fits with the smaller block and that no level has more cells than it holds)
+    mn = std::min(small_blk ? kQtMaxNodesLdsSmallBlock : kQtMaxNodes, want); blk = small_blk ? kQtBlkWordsSmall : kQtBlkWords;
+}
+size_t quadtree_lds_bytes(int max_quota) {
+    int mn, blk;
+    qt_layout(max_quota, mn, blk);
+    return qt_lds_bytes(mn, blk);
+}
+// More than 64 KB of dynamic LDS (a per-level quota of 730 or more) needs the function's limit raised on the device that launches it: every ORB context does so for
+// its own device when it is created and refuses such a quota where that failed (orb_context.hip).
+hipError_t quadtree_configure() {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_quadtree), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+
 void launch_quadtree(hipStream_t st, const LevelDev* d_lv, int n_levels, int n_cells_total, const uint32_t* cell_cand,
                      const int32_t* cell_count, int32_t* sel, int32_t* sel_count, int total_sel_cap, uint32_t* qt_scratch,
                      size_t qt_scratch_frame_stride, int32_t* status, int B, int max_quota) {
-    // node arrays for 3 * quota + 8 entries (the bound of the lists, see QtShared), rounded to 8: at K = 1000 (quota 217) 25.5 KB, so that THREE
-    // workgroups fit the 77 KB two region-growing workgroups leave on a CU (rounded to a power of two it was 34.9 KB: two)
-    const int want = std::max(256, (3 * max_quota + 8 + 7) / 8 * 8);
-    const bool small_blk = want > kQtMaxNodes;                    // a quota above 1960 (plp_orb_create has checked that it fits with the smaller block and that no level has more cells than it holds)
-    const int mn = std::min(small_blk ? kQtMaxNodesLdsSmallBlock : kQtMaxNodes, want), blk = small_blk ? kQtBlkWordsSmall : kQtBlkWords;
-    static bool attr_set = false;
-    if (!attr_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_quadtree), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr_set = true; }
+    int mn, blk;
+    qt_layout(max_quota, mn, blk);
     hipLaunchKernelGGL(k_quadtree, dim3(n_levels, B), dim3(256), qt_lds_bytes(mn, blk), st, d_lv, n_cells_total, cell_cand, cell_count, sel,
                        sel_count, total_sel_cap, reinterpret_cast<uint8_t*>(qt_scratch), qt_scratch_frame_stride, status, mn, blk);
 }

@@ -43,6 +43,45 @@ inline uint32_t qt_key(int x, int y, const LevelGeom& L) {
     return key;   // node index above 26 digit bits
 }
 
+// The small levels' sort (k_quadtree, n <= kQtSmallN): entry i goes to its RANK, the number of entries j with (key_j, j) < (key_i, i) -- the order of a stable sort by
+// key.  One wave ranks the 64 consecutive entries [i0, i0 + 64) against all keys, four at a time: an entry in front of the wave's own 64 counts when key_j <= key_i, one
+// behind them when key_j < key_i, and only the own 64 are told apart by index.  Keys are below 2^31 (key_i + 1 does not wrap) and the array is padded to n4, a multiple
+// of four, with 0xffffffff, which never counts.  load4(j) returns keys j .. j + 3, j a multiple of four.  Shared by the kernel (LDS reads) and the host model.
+struct QtKey4 { uint32_t x, y, z, w; };
+#ifdef __HIPCC__
+#define PLP_QT_HD __host__ __device__ __forceinline__
+#else
+#define PLP_QT_HD inline
+#endif
+template <class Load4> PLP_QT_HD uint32_t qt_rank(const Load4& load4, int n4, int i0, int i, uint32_t ki) {
+    const uint32_t kle = ki + 1;
+    const int own_end = i0 + 64 < n4 ? i0 + 64 : n4;
+    uint32_t rank = 0;
+    for (int j = 0; j < i0; j += 4) {
+        const QtKey4 q = load4(j);
+        rank += (uint32_t)(q.x < kle) + (uint32_t)(q.y < kle) + (uint32_t)(q.z < kle) + (uint32_t)(q.w < kle);
+    }
+    for (int j = i0; j < own_end; j += 4) {
+        const QtKey4 q = load4(j);
+        rank += (uint32_t)(q.x < (j < i ? kle : ki)) + (uint32_t)(q.y < (j + 1 < i ? kle : ki)) + (uint32_t)(q.z < (j + 2 < i ? kle : ki)) +
+                (uint32_t)(q.w < (j + 3 < i ? kle : ki));
+    }
+    for (int j = own_end; j < n4; j += 4) {
+        const QtKey4 q = load4(j);
+        rank += (uint32_t)(q.x < ki) + (uint32_t)(q.y < ki) + (uint32_t)(q.z < ki) + (uint32_t)(q.w < ki);
+    }
+    return rank;
+}
+// host statement of that sort as the kernel runs it: perm[rank] = i for the keys `key >> shift`; equals std::stable_sort by that value for any input
+inline void qt_rank_sort_host(const uint32_t* key, int n, int shift, uint32_t* perm) {
+    const int n4 = (n + 3) & ~3;
+    std::vector<uint32_t> uk((size_t)n4, 0xffffffffu);
+    for (int i = 0; i < n; ++i) uk[i] = key[i] >> shift;
+    const auto load4 = [&](int j) { return QtKey4{uk[j], uk[j + 1], uk[j + 2], uk[j + 3]}; };
+    for (int i0 = 0; i0 < n; i0 += 64)
+        for (int i = i0; i < std::min(i0 + 64, n); ++i) perm[qt_rank(load4, n4, i0, i, uk[i])] = (uint32_t)i;
+}
+
 struct QtNode { int s, e, depth; bool leaf; };
 
 // digit of sorted element i at split number `depth` (0 = first split)
