@@ -2073,6 +2073,116 @@ plp_status plp_cull_landmarks_device(plp_matcher* ctx, const plp_cull_landmarks_
 plp_status plp_cull_landmarks_host(plp_matcher* ctx, const plp_cull_landmarks_args* args);
 int32_t plp_model_cull_landmarks_host(const plp_cull_landmarks_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The covisibility graph: data::graph_node (src/PLPSLAM/data/graph_node.cc:36-285) kept as tables.  Integers only; contract: DESIGN.md
+ * section 5, D21.  Key-frame rows stand in for keyframe*: where the text orders by pointer, rows order it, ascending.
+ *
+ * plp_covisibility_update_*: update_connections() (:92-193) of the G key frames of `owners`, as if called one after another in list order
+ * over one snapshot of kf_lm and the observation lists.  The loop is sequential only through add_connection (:36-59) and the assignment of
+ * :180; D21 gives every key frame's final state in closed form (its base, then the overlays of the owners that name it), and the entry
+ * computes exactly that.
+ *
+ * Map snapshot, read only (the tables plp_local_map_args and plp_cull_keyframes_args name alike):
+ *   kf_lm            [F][cap] owner_keyfrm_->get_landmarks(): the landmark row of key point idx, -1 = none                    :94-102
+ *   kf_counts        [F] key points per key frame, NULL = cap
+ *   obs_offsets, obs_kf   lm->get_observations() in plp_landmark_geometry_args' layout                                       :108-120
+ *   lm_erased        [L] landmark::will_be_erased(), NULL = none                                                             :103
+ *   kf_id            [F] id_; only `!= 0` is read                                                                            :184
+ * A landmark row outside [0, L) counts as absent, a count is cut to [0, cap], a run of obs_offsets to [0, T], an observation whose key
+ * frame is outside [0, F) is not counted.  A landmark that sits in two slots counts twice.  The text has no test of a key frame's
+ * will_be_erased(), so there is none.
+ * State, updated in place, a row per key frame:
+ *   kf_conn, kf_conn_w   [F][conn_cap] connected_keyfrms_and_weights_ in ascending row; kf_n_conn [F] its length
+ *   kf_covis, kf_covis_w [F][covis_cap] ordered_covisibilities_ / ordered_weights_ in list order: descending (weight, row) (:165, :208);
+ *                    kf_n_covis [F] its length.  A row that is written is written whole: -1 / 0 behind the last entry of either list.
+ *                    The first 10 columns of kf_covis are plp_local_map_args' kf_covis
+ *   kf_parent        [F] spanning_parent_ (plp_local_map_args' kf_parent); kf_parent_unset [F] spanning_parent_is_not_set_           :184-191
+ * A state row outside [0, F) is dropped when its row is rewritten.  Weights stay below 2^31.
+ * Problem:
+ *   owners           [G] rows, in call order
+ * Outputs; out_status is required, NULL = not wanted for the others:
+ *   out_status       [G] a plp_covisibility_status
+ *   out_nearest      [G] nearest_covisibility (:139-143): the largest row among the maximal weights; -1 unless OK / OVERFLOW
+ *   out_max_weight   [G] max_weight; 0 unless OK / OVERFLOW
+ *   out_touched      [F] 0 = the row's state was not written, 1 = written, 2 = not valid any more (see PLP_COVIS_OVERFLOW) */
+typedef enum plp_covisibility_status {
+    PLP_COVIS_OK = 0,
+    PLP_COVIS_NO_SHARED = 1,         /* keyfrm_weights.empty() (:123-126): the call returned, nothing of the owner changed, not even its connected map */
+    PLP_COVIS_ROW_ABSENT = 2,        /* the owner is outside [0, F)                                                                                   */
+    PLP_COVIS_DUPLICATE = 3,         /* the owner appeared earlier in the list: not processed (the _host entry and the host build refuse such a list) */
+    PLP_COVIS_OVERFLOW = 4           /* the owner's row outgrew conn_cap or covis_cap: kf_n_conn / kf_n_covis carry the length (above the cap), the
+                                        row is written up to its cap in its order and out_touched is 2: the caller restores the row, grows the table
+                                        and calls again.  A row that only received connections and outgrew a cap has out_touched 2 as well; so has a
+                                        row for which an owner cut at conn_cap could not tell whether it connects to it                              */
+} plp_covisibility_status;
+typedef struct plp_covisibility_update_args {
+    int32_t F, L, T;                    /* F <= 8192 key frames (the weights of an owner are an LDS table); L landmark rows; T observation entries */
+    int32_t cap;                        /* slots per row of kf_lm, <= 8192 */
+    int32_t conn_cap, covis_cap;        /* slots per row of kf_conn and of kf_covis, <= 8192 */
+    int32_t G;                          /* owners, <= 8192 */
+    const int32_t* kf_lm;               /* F x cap */
+    const int32_t* kf_counts;           /* F, or NULL */
+    const int32_t* obs_offsets;         /* L + 1 */
+    const int32_t* obs_kf;              /* T */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const uint32_t* kf_id;              /* F */
+    int32_t* kf_conn;                   /* F x conn_cap */
+    int32_t* kf_conn_w;                 /* F x conn_cap */
+    int32_t* kf_n_conn;                 /* F */
+    int32_t* kf_covis;                  /* F x covis_cap */
+    int32_t* kf_covis_w;                /* F x covis_cap */
+    int32_t* kf_n_covis;                /* F */
+    int32_t* kf_parent;                 /* F */
+    uint8_t* kf_parent_unset;           /* F */
+    const int32_t* owners;              /* G */
+    uint8_t* out_status;                /* G */
+    int32_t* out_nearest;               /* G, or NULL */
+    int32_t* out_max_weight;            /* G, or NULL */
+    uint8_t* out_touched;               /* F, or NULL */
+} plp_covisibility_update_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; a negative F, L, T, cap, conn_cap, covis_cap or G; a NULL
+ * kf_n_conn or kf_n_covis (F > 0), kf_conn or kf_conn_w (F > 0 and conn_cap > 0), kf_covis or kf_covis_w (F > 0 and covis_cap > 0); and --
+ * when G > 0 -- a NULL owners, out_status, kf_id, kf_parent or kf_parent_unset (F > 0), kf_lm (F > 0 and cap > 0), obs_offsets or obs_kf
+ * (T > 0).  F, cap, conn_cap, covis_cap or G above 8192: PLP_ERR_UNSUPPORTED.  G == 0: PLP_OK, nothing written.  F == 0: every owner is
+ * PLP_COVIS_ROW_ABSENT.  _host and the host build also check that obs_offsets rises from 0 to T and that no owner appears twice
+ * (PLP_ERR_INVALID_ARG); on the _device path the first is a precondition (the kernels cut every run to its list) and the second a status.
+ * _device: every array a DEVICE pointer; k_covis_count (a workgroup per owner: the weights, nearest, the pairs, the owner's own lists into
+ * the context's scratch) and k_covis_apply (a workgroup per key frame: the overlays, the row), all on hip_stream, nothing synchronised.  The
+ * scratch grows on the first call of a size; the calls of one context must be ordered on the device.  _host: HOST pointers, staged (the
+ * state and the outputs both ways), synchronous. */
+plp_status plp_covisibility_update_device(plp_matcher* ctx, const plp_covisibility_update_args* args, void* hip_stream);
+plp_status plp_covisibility_update_host(plp_matcher* ctx, const plp_covisibility_update_args* args);
+/* Host build of the same source (csrc/covisibility.hpp) with a team of one lane, HOST pointers, no GPU and no context needed; the same
+ * checks.  Returns G, or the negated plp_status of a refused call. */
+int32_t plp_model_covisibility_update_host(const plp_covisibility_update_args* args);
+
+/* plp_covisibility_erase_*: erase_all_connections() (:79-90) of every key frame k with erased[k] != 0, in any order (the result does not
+ * depend on it): a surviving key frame j loses every such k that holds j in its connected map at the start of the call and that j holds
+ * (erase_connection, :61-77), and rebuilds its ordered list from ALL of its connected map if it lost one (update_covisibility_orders,
+ * :195-219); a stale k that j holds without k holding j stays, as in the text.  The erased rows end empty.  The parents are not touched
+ * (keyframe::prepare_for_erasing mends the spanning tree, keyframe.cc:886-909).
+ *   out_status       [F] PLP_COVIS_OK, or PLP_COVIS_OVERFLOW where the rebuilt list outgrew covis_cap (kf_n_covis carries the true length)
+ *   out_touched      [F] as above */
+typedef struct plp_covisibility_erase_args {
+    int32_t F;                          /* <= 8192 */
+    int32_t conn_cap, covis_cap;        /* <= 8192 */
+    int32_t* kf_conn;                   /* F x conn_cap */
+    int32_t* kf_conn_w;                 /* F x conn_cap */
+    int32_t* kf_n_conn;                 /* F */
+    int32_t* kf_covis;                  /* F x covis_cap */
+    int32_t* kf_covis_w;                /* F x covis_cap */
+    int32_t* kf_n_covis;                /* F */
+    const uint8_t* erased;              /* F */
+    uint8_t* out_status;                /* F */
+    uint8_t* out_touched;               /* F, or NULL */
+} plp_covisibility_erase_args;
+/* Checks as above; F == 0: PLP_OK, nothing written.  _device: k_covis_erase twice on hip_stream (a workgroup per key frame: the surviving
+ * rows, which read the erased ones, then the erased rows), no scratch.  plp_model_covisibility_erase_host returns F, or the negated
+ * plp_status. */
+plp_status plp_covisibility_erase_device(plp_matcher* ctx, const plp_covisibility_erase_args* args, void* hip_stream);
+plp_status plp_covisibility_erase_host(plp_matcher* ctx, const plp_covisibility_erase_args* args);
+int32_t plp_model_covisibility_erase_host(const plp_covisibility_erase_args* args);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

@@ -207,6 +207,12 @@ _API = [
     ("plp_cull_landmarks_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_cull_landmarks_host", C.c_int, [_VP, _VP]),
     ("plp_model_cull_landmarks_host", _I32, [_VP]),
+    ("plp_covisibility_update_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_covisibility_update_host", C.c_int, [_VP, _VP]),
+    ("plp_model_covisibility_update_host", _I32, [_VP]),
+    ("plp_covisibility_erase_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_covisibility_erase_host", C.c_int, [_VP, _VP]),
+    ("plp_model_covisibility_erase_host", _I32, [_VP]),
 ]
 
 
@@ -1565,6 +1571,217 @@ class local_map_cleaner:
         return int(r["num_removed"][0])
 
 
+# plp_covisibility_status
+COVIS_OK, COVIS_NO_SHARED, COVIS_ROW_ABSENT, COVIS_DUPLICATE, COVIS_OVERFLOW = range(5)
+COVIS_MAX_KF = 8192                 # F, G, conn_cap, covis_cap: the weights of an owner are an LDS table
+COVIS_MAX_SLOTS = 8192              # cap
+COVIS_WEIGHT_THR = 15               # weight_thr_
+COVISIBILITY_INPUTS = ("kf_lm", "kf_counts", "obs_offsets", "obs_kf", "lm_erased", "kf_id", "owners")
+# the state tables of plp_covisibility_*: name -> (row length from (conn_cap, covis_cap) or None, dtype, what an empty row holds)
+COVISIBILITY_STATE = dict(kf_conn=(lambda cc, vc: cc, np.int32, -1), kf_conn_w=(lambda cc, vc: cc, np.int32, 0), kf_n_conn=(None, np.int32, 0),
+                          kf_covis=(lambda cc, vc: vc, np.int32, -1), kf_covis_w=(lambda cc, vc: vc, np.int32, 0), kf_n_covis=(None, np.int32, 0),
+                          kf_parent=(None, np.int32, -1), kf_parent_unset=(None, np.uint8, 1))
+COVISIBILITY_ERASE_STATE = ("kf_conn", "kf_conn_w", "kf_n_conn", "kf_covis", "kf_covis_w", "kf_n_covis")
+# the outputs of plp_covisibility_update_*: name -> (per owner (G) or per key frame (F), dtype, optional); plp_covisibility_erase_* has status
+# and touched, both per key frame
+COVISIBILITY_OUTPUTS = dict(status=("G", np.uint8, False), nearest=("G", np.int32, True), max_weight=("G", np.int32, True),
+                            touched=("F", np.uint8, True))
+
+
+def covisibility_state(F, conn_cap, covis_cap):
+    """the state tables of F key frames without a connection, as numpy arrays"""
+    return {k: np.full((F,) if row is None else (F, row(conn_cap, covis_cap)), fill, dt) for k, (row, dt, fill) in COVISIBILITY_STATE.items()}
+
+
+def _covisibility_state_ptrs(state, names, F):
+    """the caller's state tables as they are (the entry updates them in place): checked, and their pointers with the two caps"""
+    for k in names:
+        row, dt, _ = COVISIBILITY_STATE[k]
+        v = state.get(k)
+        if not (isinstance(v, np.ndarray) and v.dtype == dt and v.flags.c_contiguous and v.flags.writeable and v.shape[0] == F
+                and v.ndim == (1 if row is None else 2)):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"state[{k!r}] must be a writeable C-contiguous {np.dtype(dt).name} array with a row per key frame")
+    cc, vc = state["kf_conn"].shape[1], state["kf_covis"].shape[1]
+    if state["kf_conn_w"].shape[1] != cc or state["kf_covis_w"].shape[1] != vc:
+        raise PlpError(PLP_ERR_INVALID_ARG, "kf_conn_w and kf_covis_w must have the row lengths of kf_conn and kf_covis")
+    return cc, vc, {k: (state[k].ctypes.data if state[k].size else None) for k in names}
+
+
+def _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out):
+    """the numpy side of plp_covisibility_update_host and plp_model_covisibility_update_host: call(args struct) runs the entry"""
+    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+    kid = np.ascontiguousarray(kf_id, np.uint32).reshape(-1)
+    F = len(kid)
+    kl = i32(kf_lm).reshape(F, -1) if F else np.zeros((0, 0), np.int32)
+    oo, ok, ow = i32(obs_offsets).reshape(-1), i32(obs_kf).reshape(-1), i32(owners).reshape(-1)
+    if len(oo) < 1:
+        raise PlpError(PLP_ERR_INVALID_ARG, "obs_offsets must have L + 1 entries")
+    L, G = len(oo) - 1, len(ow)
+    kcn = None if kf_counts is None else i32(kf_counts).reshape(-1)
+    le = None if lm_erased is None else np.ascontiguousarray(lm_erased, np.uint8).reshape(-1)
+    for name, v, n in (("kf_counts", kcn, F), ("lm_erased", le, L)):
+        if v is not None and v.size != n:
+            raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
+    cc, vc, sp = _covisibility_state_ptrs(state, COVISIBILITY_STATE, F)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(covisibility_update_args_c, dict(F=F, L=L, T=len(ok), cap=kl.shape[1], conn_cap=cc, covis_cap=vc, G=G),
+                dict(sp, kf_lm=Pt(kl), kf_counts=Pt(kcn), obs_offsets=Pt(oo), obs_kf=Pt(ok), lm_erased=Pt(le), kf_id=Pt(kid), owners=Pt(ow)))
+    o = _cull_out([(k, (G,) if per == "G" else (F,), dt) for k, (per, dt, optional) in COVISIBILITY_OUTPUTS.items()
+                   if not (optional and outputs is not None and k not in outputs)], out, a)
+    call(a)
+    return o
+
+
+def _covisibility_erase_host(call, state, erased, out):
+    """the numpy side of plp_covisibility_erase_host and plp_model_covisibility_erase_host"""
+    er = np.ascontiguousarray(erased, np.uint8).reshape(-1)
+    F = len(er)
+    cc, vc, sp = _covisibility_state_ptrs(state, COVISIBILITY_ERASE_STATE, F)
+    a = _struct(covisibility_erase_args_c, dict(F=F, conn_cap=cc, covis_cap=vc), dict(sp, erased=er.ctypes.data if F else None))
+    o = _cull_out([("status", (F,), np.uint8), ("touched", (F,), np.uint8)], out, a)
+    call(a)
+    return o
+
+
+def model_covisibility_update(kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts=None, lm_erased=None, outputs=None, out=None):
+    """Host build of graph_node::update_connections for a list of owners (csrc/covisibility.hpp, DESIGN.md section 5, D21; no GPU needed): the
+    arguments and the result of matcher.covisibility_update."""
+    def call(a):
+        r = lib().plp_model_covisibility_update_host(C.byref(a))
+        if r != a.G:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out)
+
+
+def model_covisibility_erase(state, erased, out=None):
+    """Host build of graph_node::erase_all_connections for a set of key frames (csrc/covisibility.hpp, D21; no GPU needed): the arguments and the
+    result of matcher.covisibility_erase."""
+    def call(a):
+        r = lib().plp_model_covisibility_erase_host(C.byref(a))
+        if r != a.F:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _covisibility_erase_host(call, state, erased, out)
+
+
+class covisibility_graph:
+    """Mirror of data::graph_node (data/graph_node.h) for all F key frames of a map, over table rows: the connected maps, the ordered lists, the
+    spanning parents.  mt: a matcher -- the tables live on its device as torch tensors and the calls are the _device entries -- or None = numpy
+    tables and the host build.  After an OVERFLOW the touched rows are restored from the copy taken before the call, the cap that was outgrown
+    is doubled and the call runs again."""
+
+    def __init__(self, F, conn_cap=32, covis_cap=32, mt=None, device_index=0):
+        self._mt, self.F = mt, int(F)
+        st = covisibility_state(self.F, conn_cap, covis_cap)
+        if mt is not None:
+            import torch
+            self._dev = torch.device("cuda", device_index)
+            st = {k: torch.from_numpy(v).to(self._dev) for k, v in st.items()}
+        self.state, self.last = st, None
+
+    def _np(self, v):
+        return v if isinstance(v, np.ndarray) else v.cpu().numpy()
+
+    def _grow(self, conn, covis):
+        """double the row length of the connected tables and / or of the ordered tables"""
+        for k, (row, dt, fill) in COVISIBILITY_STATE.items():
+            if row is None or not (conn if k.startswith("kf_conn") else covis):
+                continue
+            old = self.state[k]
+            if isinstance(old, np.ndarray):
+                new = np.full((self.F, max(2 * old.shape[1], 1)), fill, dt)
+            else:
+                new = old.new_full((self.F, max(2 * old.shape[1], 1)), fill)
+            new[:, :old.shape[1]] = old
+            self.state[k] = new
+
+    def _run(self, names, call):
+        """call(state) -> the outputs; the overflow protocol around it"""
+        while True:
+            keep = {k: (self.state[k].copy() if isinstance(self.state[k], np.ndarray) else self.state[k].clone()) for k in names}
+            cc, vc = self.state["kf_conn"].shape[1], self.state["kf_covis"].shape[1]
+            out = {k: self._np(v) for k, v in call(self.state).items()}
+            if not (out["touched"] == 2).any():
+                self.last = out
+                return out
+            rows = np.flatnonzero(out["touched"])
+            n_conn, n_covis = self._np(self.state["kf_n_conn"]), self._np(self.state["kf_n_covis"])
+            conn = bool((n_conn[rows] > cc).any())
+            covis = bool((n_covis[rows] > vc).any())
+            for k in names:                                  # the call was one transaction: every row it wrote goes back
+                self.state[k][rows] = keep[k][rows]
+            self._grow(conn or not covis, covis)
+
+    def update_connections(self, rows, kf_lm, obs_offsets, obs_kf, kf_id, kf_counts=None, lm_erased=None):
+        """update_connections() of the key frames `rows`, one after another in list order, over one map snapshot (numpy arrays, or torch tensors
+        on the matcher's device).  Returns the statuses (G,); self.last holds every output."""
+        owners = np.asarray(rows, np.int32).reshape(-1)
+        if self._mt is None:
+            call = lambda st: model_covisibility_update(kf_lm, obs_offsets, obs_kf, kf_id, st, owners, kf_counts, lm_erased)
+        else:
+            import torch
+            dev = lambda v, dt: None if v is None else (v if torch.is_tensor(v) else torch.from_numpy(np.ascontiguousarray(v, dt)).to(self._dev))
+            t = dict(kf_lm=dev(kf_lm, np.int32), kf_counts=dev(kf_counts, np.int32), obs_offsets=dev(obs_offsets, np.int32), obs_kf=dev(obs_kf, np.int32),
+                     lm_erased=dev(lm_erased, np.uint8), kf_id=dev(np.asarray(kf_id).astype(np.uint32).view(np.int32) if not torch.is_tensor(kf_id) else kf_id, np.int32),
+                     owners=dev(owners, np.int32))
+            dims = dict(F=self.F, L=t["obs_offsets"].shape[0] - 1, T=t["obs_kf"].shape[0], cap=t["kf_lm"].shape[1] if self.F else 0, G=len(owners))
+
+            def call(st):
+                out = dict(status=torch.zeros(len(owners), dtype=torch.uint8, device=self._dev), nearest=torch.zeros(len(owners), dtype=torch.int32, device=self._dev),
+                           max_weight=torch.zeros(len(owners), dtype=torch.int32, device=self._dev), touched=torch.zeros(self.F, dtype=torch.uint8, device=self._dev))
+                self._mt.covisibility_update_device(dict(dims, conn_cap=st["kf_conn"].shape[1], covis_cap=st["kf_covis"].shape[1]), dict(t, **st), out)
+                return out
+        return self._run(tuple(COVISIBILITY_STATE), call)["status"]
+
+    def erase_all_connections(self, rows_or_mask):
+        """erase_all_connections() of the key frames named by a list of rows or by a mask of F bytes"""
+        m = np.asarray(rows_or_mask)
+        if not (m.dtype in (np.uint8, np.bool_) and m.shape == (self.F,)):
+            rows, m = m.astype(np.int64).reshape(-1), np.zeros(self.F, np.uint8)
+            m[rows] = 1
+        m = m.astype(np.uint8)
+        if self._mt is None:
+            call = lambda st: model_covisibility_erase(st, m)
+        else:
+            import torch
+            md = torch.from_numpy(m).to(self._dev)
+
+            def call(st):
+                out = dict(status=torch.zeros(self.F, dtype=torch.uint8, device=self._dev), touched=torch.zeros(self.F, dtype=torch.uint8, device=self._dev))
+                self._mt.covisibility_erase_device(dict(F=self.F, conn_cap=st["kf_conn"].shape[1], covis_cap=st["kf_covis"].shape[1]), dict(st, erased=md), out)
+                return out
+        return self._run(COVISIBILITY_ERASE_STATE, call)["status"]
+
+    def _ordered(self, row):
+        n = int(self.state["kf_n_covis"][row])
+        return self._np(self.state["kf_covis"][row, :n]), self._np(self.state["kf_covis_w"][row, :n])
+
+    def get_covisibilities(self, row):
+        return [int(v) for v in self._ordered(row)[0]]
+
+    def get_top_n_covisibilities(self, row, n):
+        return self.get_covisibilities(row)[:int(n)]
+
+    def get_covisibilities_over_weight(self, row, weight):
+        """the prefix whose weights are at least `weight` -- and the empty list when every entry qualifies, as the text returns (:262-266)"""
+        rows, w = self._ordered(row)
+        num = int((w >= int(weight)).sum())
+        return [] if num == len(w) else [int(v) for v in rows[:num]]
+
+    def get_connected_keyframes(self, row):
+        n = int(self.state["kf_n_conn"][row])
+        return {int(v) for v in self._np(self.state["kf_conn"][row, :n])}
+
+    def get_weight(self, a, b):
+        """the weight key frame a holds for key frame b, 0 when it holds none"""
+        n = int(self.state["kf_n_conn"][a])
+        rows, w = self._np(self.state["kf_conn"][a, :n]), self._np(self.state["kf_conn_w"][a, :n])
+        at = np.flatnonzero(rows == int(b))
+        return int(w[at[0]]) if len(at) else 0
+
+    def get_spanning_parent(self, row):
+        return int(self.state["kf_parent"][row])
+
+
 class orb_extractor:
     """Mirror of feature::orb_extractor (src/PLPSLAM/feature/orb_extractor.h:38-176) over the C ABI."""
 
@@ -2189,6 +2406,21 @@ class cull_landmarks_args_c(C.Structure):
     _fields_ = [("R", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("fresh_offsets", _VP), ("fresh", _VP), ("lm_erased", _VP), ("num_observed", _VP),
                 ("num_observable", _VP), ("first_kf_id", _VP), ("num_obs", _VP), ("owning_plane", _VP), ("cur_kf_id", _VP), ("num_obs_thr", _VP),
                 ("out_state", _VP), ("out_num_removed", _VP), ("out_num_fresh", _VP), ("out_fresh", _VP)]
+
+
+class covisibility_update_args_c(C.Structure):
+    """plp_covisibility_update_args"""
+    _fields_ = [("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32), ("conn_cap", C.c_int32), ("covis_cap", C.c_int32),
+                ("G", C.c_int32), ("kf_lm", _VP), ("kf_counts", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("lm_erased", _VP), ("kf_id", _VP),
+                ("kf_conn", _VP), ("kf_conn_w", _VP), ("kf_n_conn", _VP), ("kf_covis", _VP), ("kf_covis_w", _VP), ("kf_n_covis", _VP),
+                ("kf_parent", _VP), ("kf_parent_unset", _VP), ("owners", _VP), ("out_status", _VP), ("out_nearest", _VP), ("out_max_weight", _VP),
+                ("out_touched", _VP)]
+
+
+class covisibility_erase_args_c(C.Structure):
+    """plp_covisibility_erase_args"""
+    _fields_ = [("F", C.c_int32), ("conn_cap", C.c_int32), ("covis_cap", C.c_int32), ("kf_conn", _VP), ("kf_conn_w", _VP), ("kf_n_conn", _VP),
+                ("kf_covis", _VP), ("kf_covis_w", _VP), ("kf_n_covis", _VP), ("erased", _VP), ("out_status", _VP), ("out_touched", _VP)]
 
 
 class bow_query_args_c(C.Structure):
@@ -3285,6 +3517,47 @@ class matcher:
             setattr(a, "out_" + k, D(out.get(k)))
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_cull_landmarks_device(self._h, C.byref(a), st))
+
+    def covisibility_update(self, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts=None, lm_erased=None, outputs=None, out=None):
+        """graph_node::update_connections of the key frames `owners` (G,), as if one after another in list order, over one map snapshot
+        (plp_covisibility_update_host): kf_lm (F, cap) i32, the observation lists obs_offsets (L + 1,), obs_kf (T,), kf_id
+        (F,) u32; kf_counts (F,) i32 and lm_erased (L,) u8 or None.  state: a dict of the numpy tables of COVISIBILITY_STATE (covisibility_state()
+        makes empty ones), updated in place.  Returns dict(status (G,) u8: COVIS_*, nearest, max_weight (G,), touched (F,) u8); `outputs` names
+        the optional ones wanted (default all); out[name]: the caller's array (unwritten slots keep their values).  A list that names a key
+        frame twice is refused."""
+        call = lambda a: _check(lib().plp_covisibility_update_host(self._h, C.byref(a)))
+        return _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out)
+
+    def covisibility_update_device(self, dims, tables, out, stream=None):
+        """plp_covisibility_update_device: dims a dict of the struct's sizes (F, L, T, cap, conn_cap, covis_cap, G); tables a dict of
+        COVISIBILITY_INPUTS and COVISIBILITY_STATE (updated in place) and out a dict of COVISIBILITY_OUTPUTS, each a device pointer (int), a torch
+        tensor on the matcher's device or absent / None; asynchronous on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(covisibility_update_args_c, {k: int(v) for k, v in dims.items()},
+                    {k: D(tables.get(k)) for k in COVISIBILITY_INPUTS + tuple(COVISIBILITY_STATE)})
+        for k in COVISIBILITY_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_covisibility_update_device(self._h, C.byref(a), st))
+
+    def covisibility_erase(self, state, erased, out=None):
+        """graph_node::erase_all_connections of every key frame with erased[k] != 0 (plp_covisibility_erase_host; D21): state as for
+        covisibility_update (the six connection tables), erased (F,) u8.  Returns dict(status (F,) u8, touched (F,) u8)."""
+        call = lambda a: _check(lib().plp_covisibility_erase_host(self._h, C.byref(a)))
+        return _covisibility_erase_host(call, state, erased, out)
+
+    def covisibility_erase_device(self, dims, tables, out, stream=None):
+        """plp_covisibility_erase_device: dims dict(F, conn_cap, covis_cap); tables the six connection tables and `erased`, out dict(status,
+        touched), device pointers (int) or torch tensors; asynchronous, two launches on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(covisibility_erase_args_c, {k: int(v) for k, v in dims.items()},
+                    {k: D(tables.get(k)) for k in COVISIBILITY_ERASE_STATE + ("erased",)})
+        for k in ("status", "touched"):
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_covisibility_erase_device(self._h, C.byref(a), st))
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):

@@ -9,9 +9,9 @@ search_local_landmarks[_line], module::local_map_updater (module/local_map_updat
   2  torch, on the stream   gathers of static shape [B, m_cap] / [B, ml_cap] from the shared landmark tables into the `local` dict of posed_step.py;
                             ref_keyfrm_ = nearest where there is one (:888-892)
 
-No .item(), no copy to the host, no boolean-mask indexing.  What stays on the host: the covisibility graph and the spanning tree themselves
-(graph_node::update_connections; the caller uploads kf_covis, kf_parent and the children lists), map_db_->set_local_landmarks, and the writes to the
-landmark objects around the search (is_observable_in_tracking_, increase_num_observable).
+No .item(), no copy to the host, no boolean-mask indexing.  kf_covis, kf_parent and the children lists are covisibility_step's views of the graph
+(graph_node::update_connections on the device, D21), or the caller's upload.  What stays on the host: map_db_->set_local_landmarks, and the writes
+to the landmark objects around the search (is_observable_in_tracking_, increase_num_observable).
 
 Tables are torch tensors on the step's device, named as landmark_refresh_step names them where it has them:
   key frames  kf_erased [F] u8, kf_covis [F, 10] i32 (get_top_n_covisibilities(10), -1 padded), kf_parent [F] i32, kf_children_offsets [F + 1] i32,

@@ -7,8 +7,9 @@ DESIGN.md section 5, D20), on the tables local_ba_step, local_map_step and landm
                   into `kf_erased` and out_lm_erased into `skip` in place: the tables the next local_map_step or landmark_refresh_step call reads
 
 Several lists or problems are independent readings of one snapshot: their masks are returned and nothing is written back.  No .item(), no copy
-to the host, no boolean-mask indexing.  What stays on the host is what prepare_for_erasing() does to objects: erase_all_connections,
-recover_spanning_connections, replace_reference_keyframe and the databases, for the rows the decisions name, in list order.
+to the host, no boolean-mask indexing.  erase_all_connections of the removed key frames is covisibility_step.erase over kf_removed (D21), and the
+covisibility list of a problem is that step's view of the owner's row.  What stays on the host is the rest of what prepare_for_erasing() does to
+objects: recover_spanning_connections, replace_reference_keyframe and the databases, for the rows the decisions name, in list order.
 
 Tables are torch tensors on the step's device, named as the other steps name them:
   key frames  kps [F, kp_stride, 28] u8 (undist_keypts_ as plp_keypoint), counts [F] i32 or absent, kf_lm [F, cap] i32, kf_erased [F] u8 (updated in
