@@ -23,6 +23,16 @@ g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -DUSE_DBOW2 -w
     "$R/feature/line_descriptor/binary_descriptor_custom.cpp" "$R/feature/line_descriptor/binary_descriptor_matcher.cpp" \
     "$HERE/ref_driver2.cpp" -o "$HERE/_ref/libplpref2.so"
 echo "ref_build: built $HERE/_ref/libplpref2.so"
+# The covisibility graph and the map cleaner of the reference, unmodified, against the stand-ins of keyframe / landmark / Line in
+# ref_shadow_map (ahead of every other include path; ref_shadow is not on it) and the spdlog shim: a third library.  The driver alone is
+# compiled without access control, so that it can preset and read graph_node's private tables; the reference's text is left as it is.
+g++ -O2 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-access-control -w \
+    -I"$HERE/ref_shadow_map" -I"$HERE/ref_shim" -I"$REF/src" -I"$HERE/../include" \
+    -c "$HERE/ref_driver3.cpp" -o "$HERE/_ref/ref_driver3.o"
+g++ -O2 -std=c++17 -fPIC -shared -ffp-contract=off -fno-fast-math -w \
+    -I"$HERE/ref_shadow_map" -I"$HERE/ref_shim" -I"$REF/src" \
+    "$R/data/graph_node.cc" "$R/module/local_map_cleaner.cc" "$HERE/_ref/ref_driver3.o" -o "$HERE/_ref/libplpref3.so"
+echo "ref_build: built $HERE/_ref/libplpref3.so"
 # the shipped C++ facade, compiled like a reference translation unit and linked to the product library
 PKG="$HERE/../structure-plp-slam_amd"
 if [ -f "$PKG/libplp_front.so" ]; then

@@ -73,7 +73,7 @@ class Builder:
             self.landmark([(k, 3), ("H0", 0)])
 
 
-def keyframe_scene(F, setup, seed, problems, lm_num_obs=False, outside=False):
+def keyframe_scene(F, setup, seed, problems, lm_num_obs=False, outside=False, wrap=False):
     cap = 260
     b = Builder(F, cap, setup, seed)
     rng = b.rng
@@ -116,6 +116,9 @@ def keyframe_scene(F, setup, seed, problems, lm_num_obs=False, outside=False):
     kf_id = (10 + 3 * np.arange(F)).astype(np.uint32)
     for n, v in (("CUR", CUR_ID), ("CUR2", 2000), ("ORIGIN", ORIGIN_ID), ("W_AT", CUR_ID), ("W_M2", CUR_ID - 2), ("W_M3", CUR_ID - 3), ("W_P1", CUR_ID + 1)):
         kf_id[b.name[n]] = v
+    if wrap:                                                          # the window test at the top of the unsigned range: W_M2's id + 2 wraps to 0
+        for n, v in (("CUR", 2 ** 32 - 1), ("W_AT", 2 ** 32 - 1), ("W_M2", 2 ** 32 - 2), ("W_M3", 2 ** 32 - 3), ("W_P1", 0)):
+            kf_id[b.name[n]] = v
     kf_erased = np.zeros(F, np.uint8); kf_erased[e] = 1
     cannot = np.zeros(F, np.uint8); cannot[b.name["HELD"]] = 1
     lm_erased = (rng.integers(0, 25, L) == 0).astype(np.uint8)
@@ -188,10 +191,23 @@ def _several(b, rng):
             (b.F, ["Z", "K910"]), ("CUR2", ["K910", "Z", "HELD", "FLIP_RK", "FLIP_KR"] + [int(v) for v in rng.permutation(b.base)[:70]])]
 
 
+def _several_inside(b, rng):
+    """_several with every row inside the table: what a build of the reference, which follows pointers, can be handed whole"""
+    return [(c, [v for v in lst if b.name.get(v, v) in range(b.F)]) for c, lst in _several(b, rng) if b.name.get(c, c) in range(b.F)]
+
+
+def _short(b, rng):
+    return [("CUR", _main_list(b, rng, 12))]
+
+
+# stereo97c is stereo97 without a row outside a table; wrap65 has the ids of the window's key frames at the top of the unsigned range: W_M2 is
+# 2^32 - 2 against a current key frame of 2^32 - 1, so `id + 2` wraps to 0 and the entry is counted and removed (signed arithmetic would skip it)
 _SPECS = dict(mono97=dict(F=97, setup=0, seed=11, problems=_one),
               mono65=dict(F=65, setup=0, seed=12, problems=_several, lm_num_obs=True),
               stereo97=dict(F=97, setup=1, seed=13, problems=_several, outside=True),
-              rgbd65=dict(F=65, setup=2, seed=14, problems=_one, lm_num_obs=True))
+              rgbd65=dict(F=65, setup=2, seed=14, problems=_one, lm_num_obs=True),
+              stereo97c=dict(F=97, setup=1, seed=13, problems=_several_inside),
+              wrap65=dict(F=65, setup=0, seed=15, problems=_short, wrap=True))
 SCENES = tuple(_SPECS)
 _cache = {}
 

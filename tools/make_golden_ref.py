@@ -8,7 +8,11 @@ Also (oracle/_ref/libplpref2.so = the reference's matcher / line / LBD / MIH / s
   tests/golden/ref_match.npz   random problems for every array-form matcher (tests/match_cases.py) with the REFERENCE'S answers
   tests/golden/ref_line.npz    LineFeatureTracker::extract_LSD_LBD of the reference build on the fixture frames and two synthetic ones
   tests/golden/ref_stereo.npz  match::stereo::compute of the reference build on two synthetic stereo pairs
-    python tools/make_golden_ref.py
+Also (oracle/_ref/libplpref3.so = the reference's data/graph_node.cc and module/local_map_cleaner.cc, oracle/ref_driver3.cpp):
+  tests/golden/ref_map.npz     the covisibility graph and map culling of the reference build on the seeded scenes of tests/covisibility_scene.py
+                               and tests/map_cull_scene.py: answers only (integer arrays) and a digest of each scene's input tables
+    python tools/make_golden_ref.py          every file
+    python tools/make_golden_ref.py map      ref_map.npz alone
 """
 import pathlib
 import sys
@@ -106,7 +110,26 @@ def golden_line_and_stereo():
     np.savez_compressed(ROOT / "tests" / "golden" / "ref_stereo.npz", **out)
 
 
+def golden_map():
+    """what tests/ref_map_lib.py records, narrowed to the smallest integer type that holds each array"""
+    import ref_map_lib as M
+    out = {}
+    for k, v in M.record_all().items():
+        v = np.asarray(v)
+        for dt in (np.int8, np.int16, np.int32):
+            if v.dtype.kind == "i" and v.size and np.iinfo(dt).min <= v.min() and v.max() <= np.iinfo(dt).max:
+                v = v.astype(dt)
+                break
+        out[k] = v
+    path = ROOT / "tests" / "golden" / "ref_map.npz"
+    np.savez_compressed(path, **out)
+    print("ref_map.npz:", len(out), "arrays,", path.stat().st_size, "bytes")
+
+
 def main():
+    if sys.argv[1:] == ["map"]:
+        return golden_map()
+    golden_map()
     golden_match()
     golden_line_and_stereo()
     out = {}
