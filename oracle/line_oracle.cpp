@@ -175,6 +175,7 @@ struct LineResult {
     Image scaled;
     std::vector<int> order_xy;
     std::vector<int16_t> dx, dy;
+    LsdCensus census;                        // filled by extract_lsd_lbd(..., with_census = true) only
 };
 
 inline void check_extremes(std::array<float, 4>& e, int w, int h) {   // LSDDetector_custom.cpp:76-102
@@ -188,13 +189,14 @@ inline void check_extremes(std::array<float, 4>& e, int w, int h) {   // LSDDete
     if (e[3] >= h) e[3] = (float)h - 1.0f;
 }
 
-inline LineResult extract_lsd_lbd(const Image& img, bool stable_order) {
+inline LineResult extract_lsd_lbd(const Image& img, bool stable_order, bool with_census = false) {
     LineResult R;
     // (i) cv::remap with the K*K^-1 map is the identity for a perspective camera
     const Image& img_temp = img;
     LsdOptions opts;
     const double min_length = 0.125 * std::min(img_temp.cols, img_temp.rows);   // line_extractor.cc:122, line_extractor.h:103
     Lsd lsd(opts, stable_order);
+    if (with_census) lsd.set_census(&R.census);
     R.raw = lsd.detect(img_temp);
     R.scaled = lsd.scaled;
     R.order_xy = lsd.order_xy;
@@ -263,6 +265,31 @@ void* oracle_line_extract(const uint8_t* img, int rows, int cols, long step, int
     auto* h = new OracleLineHandle();
     h->R = extract_lsd_lbd(im, stable_order != 0);
     return h;
+}
+// the same run with the census of region growing and refinement attached (lsd_restated.hpp LsdCensus); every other output is what oracle_line_extract gives
+void* oracle_line_extract_census(const uint8_t* img, int rows, int cols, long step, int stable_order) {
+    Image im(rows, cols);
+    for (int y = 0; y < rows; ++y) std::memcpy(im.row(y), img + (size_t)y * step, cols);
+    auto* h = new OracleLineHandle();
+    h->R = extract_lsd_lbd(im, stable_order != 0, true);
+    return h;
+}
+// frame3 = regions_grown, pixels_first, regions_upto8; the row counts of the two tables of oracle_line_census
+void oracle_line_census_counts(void* h, long long* frame3, int* n_regions, int* n_passes) {
+    const LsdCensus& c = ((OracleLineHandle*)h)->R.census;
+    frame3[0] = c.regions_grown; frame3[1] = c.pixels_first; frame3[2] = c.regions_upto8;
+    *n_regions = (int)c.n_first.size(); *n_passes = (int)c.pass_region.size();
+}
+// regions7: [7][n_regions] = n_first, frontier_max, frontier_max7, refined, n_regrown, kept, n_passes; tau: [n_regions];
+// passes4: [4][n_passes] = pass_region, n_before, n_kept, n_moves
+void oracle_line_census(void* h, int* regions7, double* tau, int* passes4) {
+    const LsdCensus& c = ((OracleLineHandle*)h)->R.census;
+    const size_t nr = c.n_first.size(), np = c.pass_region.size();
+    const std::vector<int>* rc[7] = {&c.n_first, &c.frontier_max, &c.frontier_max7, &c.refined, &c.n_regrown, &c.kept, &c.n_passes};
+    for (int k = 0; k < 7 && nr; ++k) std::memcpy(regions7 + k * nr, rc[k]->data(), nr * sizeof(int));
+    if (nr) std::memcpy(tau, c.tau.data(), nr * sizeof(double));
+    const std::vector<int>* pc[4] = {&c.pass_region, &c.n_before, &c.n_kept, &c.n_moves};
+    for (int k = 0; k < 4 && np; ++k) std::memcpy(passes4 + k * np, pc[k]->data(), np * sizeof(int));
 }
 void oracle_line_free(void* h) { delete (OracleLineHandle*)h; }
 int oracle_line_count(void* h, int which) {   // 0 kept, 1 all (before filter), 2 raw LSD segments

@@ -70,9 +70,24 @@ struct LsdOptions {   // line_extractor.cc:113-122
     int n_bins = 1024;
 };
 
+// What region growing and refinement did on one frame: counters only, filled when a census is attached (Lsd::set_census), for the tests that
+// must know which branches of the device growers a frame reaches (tests/test_lsd_grow_cpu.py).  Without one the class runs as it always did:
+// one untaken branch per region, nothing inside the per-pixel loops.
+struct LsdCensus {
+    long long regions_grown = 0;    // first growths started (seeds that were unused and had an angle)
+    long long pixels_first = 0;     // the sum of their sizes
+    long long regions_upto8 = 0;    // first growths of at most 8 points (what the several-waves grower keeps inside a result entry)
+    // one row per region whose first growth reached min_reg_size
+    std::vector<int> n_first, frontier_max, frontier_max7, refined, n_regrown, kept, n_passes;
+    std::vector<double> tau;        // of refined regions (0 otherwise; can be NaN)
+    // one row per shrink pass of reduce_region_radius, in region order: pass_region indexes the rows above
+    std::vector<int> pass_region, n_before, n_kept, n_moves;
+};
+
 class Lsd {
 public:
     explicit Lsd(const LsdOptions& o, bool stable) : o_(o), stable_(stable) {}
+    void set_census(LsdCensus* c) { census_ = c; }
     std::vector<std::array<float, 4>> detect(const Image& image);
     Image scaled;          // kept for stage parity
     std::vector<int> order_xy;   // seed order (y * w + x)
@@ -84,6 +99,7 @@ private:
     struct Rect { double x1, y1, x2, y2, width, x, y, theta, dx, dy, prec, p; };
 
     void ll_angle(double threshold, unsigned n_bins);
+    template <bool kCensus = false>
     void region_grow(int sx, int sy, std::vector<RegionPoint>& reg, double& reg_angle, double prec);
     void region2rect(const std::vector<RegionPoint>& reg, double reg_angle, double prec, double p, Rect& rec) const;
     double get_theta(const std::vector<RegionPoint>& reg, double x, double y, double reg_angle, double prec) const;
@@ -119,6 +135,8 @@ private:
     std::vector<uint8_t> used_;
     struct NormPoint { int x, y, norm; };
     std::vector<NormPoint> ordered_;
+    LsdCensus* census_ = nullptr;
+    int front_max_ = 0, front_max7_ = 0;   // of the region being grown, first growth and regrowth together (census only)
 };
 
 inline void Lsd::ll_angle(double threshold, unsigned n_bins) {
@@ -152,6 +170,7 @@ inline void Lsd::ll_angle(double threshold, unsigned n_bins) {
     else std::sort(ordered_.begin(), ordered_.end(), cmp);
 }
 
+template <bool kCensus>
 inline void Lsd::region_grow(int sx, int sy, std::vector<RegionPoint>& reg, double& reg_angle, double prec) {
     reg.clear();
     reg_angle = angles_[(size_t)sy * w_ + sx];
@@ -160,6 +179,11 @@ inline void Lsd::region_grow(int sx, int sy, std::vector<RegionPoint>& reg, doub
     float sumdy = float(std::sin(reg_angle));
     used_[(size_t)sy * w_ + sx] = 1;
     for (size_t i = 0; i < reg.size(); ++i) {
+        if (kCensus) {   // the frontier: points listed and not yet visited, as the loop reaches point i
+            const int front = (int)(reg.size() - i);
+            if (front > front_max_) front_max_ = front;
+            if (i % 7 == 0 && front > front_max7_) front_max7_ = front;   // 7 = the points the device growers visit per batch: they look at the frontier there only
+        }
         const int px = reg[i].x, py = reg[i].y;
         const int xx_min = std::max(px - 1, 0), xx_max = std::min(px + 1, w_ - 1);
         const int yy_min = std::max(py - 1, 0), yy_max = std::min(py + 1, h_ - 1);
@@ -227,6 +251,16 @@ inline bool Lsd::reduce_region_radius(std::vector<RegionPoint>& reg, double reg_
     double radSq = radSq1 > radSq2 ? radSq1 : radSq2;
     while (density < density_th) {
         radSq *= 0.75 * 0.75;
+        if (census_) {   // before the pass moves anything: the far positions below the kept count are the ones a kept point is moved into
+            const int nb = (int)reg.size();
+            int far = 0;
+            for (int i = 0; i < nb; ++i) far += dist_sq(xc, yc, double(reg[i].x), double(reg[i].y)) > radSq;
+            int moves = 0;
+            for (int i = 0; i < nb - far; ++i) moves += dist_sq(xc, yc, double(reg[i].x), double(reg[i].y)) > radSq;
+            census_->pass_region.push_back((int)census_->n_first.size() - 1);
+            census_->n_before.push_back(nb); census_->n_kept.push_back(nb - far); census_->n_moves.push_back(moves);
+            ++census_->n_passes.back();
+        }
         for (size_t i = 0; i < reg.size(); ++i) {
             if (dist_sq(xc, yc, double(reg[i].x), double(reg[i].y)) > radSq) {
                 used_[(size_t)reg[i].y * w_ + reg[i].x] = 0;
@@ -261,7 +295,10 @@ inline bool Lsd::refine(std::vector<RegionPoint>& reg, double reg_angle, double 
     const double mean_angle = sum / double(n);
     const double tau = 2.0 * std::sqrt((s_sum - 2.0 * mean_angle * sum) / double(n) + mean_angle * mean_angle);
     const int sx = reg[0].x, sy = reg[0].y;
-    region_grow(sx, sy, reg, reg_angle, tau);
+    if (census_) {
+        region_grow<true>(sx, sy, reg, reg_angle, tau);
+        census_->refined.back() = 1; census_->tau.back() = tau; census_->n_regrown.back() = (int)reg.size();
+    } else region_grow(sx, sy, reg, reg_angle, tau);
     if (reg.size() < 2) return false;
     region2rect(reg, reg_angle, prec, p, rec);
     density = double(reg.size()) / (dist(rec.x1, rec.y1, rec.x2, rec.y2) * rec.width);
@@ -291,11 +328,23 @@ inline std::vector<std::array<float, 4>> Lsd::detect(const Image& image) {
         order_xy.push_back(op.y * w_ + op.x);
         if (used_[(size_t)op.y * w_ + op.x] == 0 && angles_[(size_t)op.y * w_ + op.x] != NOTDEF) {
             double reg_angle;
-            region_grow(op.x, op.y, reg, reg_angle, prec);
+            if (census_) {
+                front_max_ = front_max7_ = 0;
+                region_grow<true>(op.x, op.y, reg, reg_angle, prec);
+                ++census_->regions_grown; census_->pixels_first += (long long)reg.size(); census_->regions_upto8 += reg.size() <= 8;
+                if (reg.size() >= min_reg_size) {
+                    for (auto* v : {&census_->n_first, &census_->frontier_max, &census_->frontier_max7, &census_->refined, &census_->n_regrown, &census_->kept, &census_->n_passes})
+                        v->push_back(0);
+                    census_->tau.push_back(0.0);
+                    census_->n_first.back() = (int)reg.size();
+                }
+            } else region_grow(op.x, op.y, reg, reg_angle, prec);
             if (reg.size() < min_reg_size) continue;
             Rect rec;
             region2rect(reg, reg_angle, prec, p, rec);
-            if (o_.refine > 0 && !refine(reg, reg_angle, prec, p, rec, o_.density_th)) continue;
+            const bool keep = !(o_.refine > 0) || refine(reg, reg_angle, prec, p, rec, o_.density_th);
+            if (census_) { census_->frontier_max.back() = front_max_; census_->frontier_max7.back() = front_max7_; census_->kept.back() = keep; }
+            if (!keep) continue;
             rec.x1 += 0.5; rec.y1 += 0.5; rec.x2 += 0.5; rec.y2 += 0.5;
             if (o_.scale != 1) { rec.x1 /= o_.scale; rec.y1 /= o_.scale; rec.x2 /= o_.scale; rec.y2 /= o_.scale; rec.width /= o_.scale; }
             lines.push_back({float(rec.x1), float(rec.y1), float(rec.x2), float(rec.y2)});

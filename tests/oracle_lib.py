@@ -178,6 +178,10 @@ def _load():
         L.oracle_front_time_frames.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint, C.c_int, C.c_float, C.c_void_p]
         L.oracle_line_extract.restype = C.c_void_p
         L.oracle_line_extract.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int]
+        L.oracle_line_extract_census.restype = C.c_void_p
+        L.oracle_line_extract_census.argtypes = L.oracle_line_extract.argtypes
+        L.oracle_line_census_counts.argtypes = [C.c_void_p] * 4
+        L.oracle_line_census.argtypes = [C.c_void_p] * 4
         L.oracle_line_free.argtypes = [C.c_void_p]
         L.oracle_line_count.argtypes = [C.c_void_p, C.c_int]
         L.oracle_line_get.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
@@ -381,17 +385,40 @@ KL_DTYPE = np.dtype([("angle", "<f4"), ("class_id", "<i4"), ("octave", "<i4"), (
                      ("lineLength", "<f4"), ("numOfPixels", "<i4")])
 
 
+class LineCensus:
+    """what region growing and refinement did on one frame (oracle/lsd_restated.hpp LsdCensus).  Frame counters: regions_grown, pixels_first,
+    regions_upto8.  One entry per region whose first growth reached min_reg_size: n_first, frontier_max, frontier_max7, refined, n_regrown, kept,
+    n_passes, tau.  One entry per shrink pass: pass_region (index into the region arrays), n_before, n_kept, n_moves."""
+    REGION_COLS = ("n_first", "frontier_max", "frontier_max7", "refined", "n_regrown", "kept", "n_passes")
+    PASS_COLS = ("pass_region", "n_before", "n_kept", "n_moves")
+
+    def __init__(self, L, h):
+        frame = np.zeros(3, np.int64)
+        nr, npass = C.c_int(), C.c_int()
+        L.oracle_line_census_counts(h, _p(frame), C.byref(nr), C.byref(npass))
+        self.regions_grown, self.pixels_first, self.regions_upto8 = (int(v) for v in frame)
+        reg = np.zeros((len(self.REGION_COLS), nr.value), np.int32); pas = np.zeros((len(self.PASS_COLS), npass.value), np.int32)
+        self.tau = np.zeros(nr.value, np.float64)
+        L.oracle_line_census(h, _p(reg), _p(self.tau), _p(pas))
+        for k, v in zip(self.REGION_COLS, reg):
+            setattr(self, k, v)
+        for k, v in zip(self.PASS_COLS, pas):
+            setattr(self, k, v)
+
+
 class LineOracle:
     """one extract_LSD_LBD run of the oracle with its stage outputs"""
 
-    def __init__(self, img, stable_order=False):
+    def __init__(self, img, stable_order=False, census=False):
         """stable_order=False (default): seeds visited in the order std::sort leaves, as OpenCV's lsd.cpp does it (a reference built with this C++
-        library); True: bin descending then row-major, the library's PLP_SEED_ORDER_STABLE mode (definition D1 of rounds 1-3)"""
+        library); True: bin descending then row-major, the library's PLP_SEED_ORDER_STABLE mode (definition D1 of rounds 1-3).
+        census=True: the same run with counters attached; self.census is a LineCensus (None otherwise)"""
         img = np.ascontiguousarray(img, np.uint8)
         self.shape = img.shape
         L = lib()
-        h = L.oracle_line_extract(_p(img), img.shape[0], img.shape[1], img.strides[0], int(stable_order))
+        h = (L.oracle_line_extract_census if census else L.oracle_line_extract)(_p(img), img.shape[0], img.shape[1], img.strides[0], int(stable_order))
         try:
+            self.census = LineCensus(L, h) if census else None
             n = L.oracle_line_count(h, 0); na = L.oracle_line_count(h, 1); nr = L.oracle_line_count(h, 2)
             self.keylsd = np.zeros(n, KL_DTYPE); self.lbd = np.zeros((n, 32), np.uint8); self.linefn = np.zeros((n, 3), np.float64)
             L.oracle_line_get(h, 0, _p(self.keylsd), _p(self.lbd), _p(self.linefn), None)
