@@ -2183,6 +2183,131 @@ plp_status plp_covisibility_erase_device(plp_matcher* ctx, const plp_covisibilit
 plp_status plp_covisibility_erase_host(plp_matcher* ctx, const plp_covisibility_erase_args* args);
 int32_t plp_model_covisibility_erase_host(const plp_covisibility_erase_args* args);
 
+/* ---- Loop closing: optimize::graph_optimizer::optimize (src/PLPSLAM/optimize/graph_optimizer.cc:53-350; csrc/pose_graph.hpp, DESIGN.md
+ * section 5, D22) for G problems over one key-frame table and its graph tables (D21's layout).  A Sim3 is 8 doubles: the quaternion x y z w
+ * (never normalised), the translation, the scale.
+ *
+ * Vertices (:85-129): every row with kf_erased == 0, ascending row (rows ascending in kf_id reproduce g2o's index mapping).  The estimate is
+ * the problem's pre_corrected Sim3 of the row if listed, else Sim3(rot_cw, trans_cw, 1.0) of its pose row.  loop_kf is fixed.
+ * Edges (:131-298), in insertion order, which is the order of every sum:
+ *   [3.1] the problem's loop connections (lc_owner, lc_target) in list order -- the reference walks a std::map of std::sets in pointer order;
+ *         ascending (owner, target) is this library's order and the caller's to keep -- unless get_weight(owner, target) on kf_conn /
+ *         kf_conn_w (0: not connected) is below 100 and the pair is not (curr_kf, loop_kf); type PLP_POSE_GRAPH_EDGE_LOOP_CONNECTION   :154-181
+ *   [3.2] for every row k ascending: the parent edge (:196-217; id(k) <= id(parent) leaves the key frame altogether, as the text's
+ *         `continue` does), the loop edges kf_loop[kf_loop_offsets[k] .. kf_loop_offsets[k + 1]) with id(k) > id(other) (:222-243), the
+ *         covisibilities of get_covisibilities_over_weight(100) -- the empty list when every entry reaches the weight -- that have a parent,
+ *         are neither the parent nor a child (kf_parent[c] == k) nor a loop edge nor erased, with id(k) > id(c) and no edge of that pair yet
+ *         (:248-297).  The relative pose Sim3_21 uses the problem's non_corrected Sim3 of a row where listed, else the vertex's initial one.
+ *   An edge with an erased end, a row outside the table or both ends the same row is not inserted.  kf_id must be unique; the rows of
+ *   kf_covis and kf_loop hold a key frame once.
+ * A vertex without an edge is not in the system and keeps its estimate.  The error of an edge is (Sim3_21 * v1 * v2^-1).log() (g2o's
+ * Sim3::log restated, log and acos without a library), the information the identity, no robust kernel; the Jacobians are g2o's central
+ * differences through the vertex's update Sim3(x) * est (sigma = 0 under fix_scale).  Up to 50 Levenberg-Marquardt iterations
+ * (csrc/levenberg.hpp); the linear system is solved by a block skyline Cholesky in vertex order (this replaces LinearSolverCSparse: the same
+ * solution, other rounding).  Parity against a g2o build is unpinned: the definition is csrc/pose_graph.hpp = tests/pose_graph_ref.py.
+ *
+ * Outputs (:307-328), written for the rows that are vertices only:
+ *   out_status       [G] plp_pose_graph_status; anything but OK / NO_EDGES: only out_status and out_num_edges are written
+ *   out_num_edges    [G] the edges (TOO_MANY_EDGES: the number that would be needed)
+ *   out_edges        [G][edge_cap][3] id1 row, id2 row, plp_pose_graph_edge_type, the first out_num_edges entries
+ *   out_sim3_cw      [G][F][8] Sim3s_cw, the initial estimates            :100, :110
+ *   out_corrected_wc [G][F][8] the inverse of the final estimate          :327
+ *   out_pose         [G][F][15] rot_cw (the quaternion's toRotationMatrix), trans_cw = t / (double)(float)s, the camera centre   :319-325
+ *   out_info         [G][4] iterations, rejected steps, why it ended (1 iterations, 2 tries, 3 rho == 0; 0 = not run), vertices in the system
+ *   out_chi2         [G][2] chi2 and lambda at the end */
+typedef enum plp_pose_graph_status {
+    PLP_POSE_GRAPH_OK = 0,
+    PLP_POSE_GRAPH_NO_EDGES = 1,             /* nothing to optimise: the outputs carry the initial estimates */
+    PLP_POSE_GRAPH_ENVELOPE_TOO_LARGE = 2,   /* the skyline needs more than env_cap blocks */
+    PLP_POSE_GRAPH_TOO_MANY_EDGES = 3,       /* more than edge_cap edges */
+    PLP_POSE_GRAPH_BAD_LOOP_KF = 4           /* loop_kf is no vertex */
+} plp_pose_graph_status;
+typedef enum plp_pose_graph_edge_type {
+    PLP_POSE_GRAPH_EDGE_LOOP_CONNECTION = 1, PLP_POSE_GRAPH_EDGE_PARENT = 2, PLP_POSE_GRAPH_EDGE_LOOP = 3, PLP_POSE_GRAPH_EDGE_COVIS = 4
+} plp_pose_graph_edge_type;
+typedef struct plp_pose_graph_args {
+    int32_t G;                          /* <= 16 */
+    int32_t F;                          /* <= 1024 */
+    int32_t pose_stride;                /* >= 12 */
+    int32_t conn_cap, covis_cap;        /* <= 65536 */
+    int32_t edge_cap;                   /* edges per problem, 1 .. 16384 */
+    int32_t env_cap;                    /* 7 x 7 blocks of a problem's skyline, 1 .. 65536 */
+    int32_t max_iter;                   /* 50 in the reference */
+    const double* pose;                 /* F x pose_stride */
+    const uint8_t* kf_erased;           /* F, or NULL */
+    const int32_t* kf_id;               /* F */
+    const int32_t* kf_parent;           /* F */
+    const int32_t* kf_conn;             /* F x conn_cap */
+    const int32_t* kf_conn_w;           /* F x conn_cap */
+    const int32_t* kf_n_conn;           /* F */
+    const int32_t* kf_covis;            /* F x covis_cap */
+    const int32_t* kf_covis_w;          /* F x covis_cap */
+    const int32_t* kf_n_covis;          /* F */
+    const int32_t* kf_loop_offsets;     /* F + 1, or NULL: no loop edges */
+    const int32_t* kf_loop;             /* kf_loop_offsets[F] */
+    const int32_t* loop_kf;             /* G */
+    const int32_t* curr_kf;             /* G */
+    const uint8_t* fix_scale;           /* G, or NULL: free scale */
+    const int32_t* pre_offsets;         /* G + 1, or NULL */
+    const int32_t* pre_row;
+    const double* pre_sim3;             /* x 8 */
+    const int32_t* non_offsets;         /* G + 1, or NULL */
+    const int32_t* non_row;
+    const double* non_sim3;             /* x 8 */
+    const int32_t* lc_offsets;          /* G + 1, or NULL */
+    const int32_t* lc_owner;
+    const int32_t* lc_target;
+    uint8_t* out_status;                /* G */
+    int32_t* out_num_edges;             /* G, or NULL */
+    int32_t* out_edges;                 /* G x edge_cap x 3, or NULL */
+    double* out_sim3_cw;                /* G x F x 8, or NULL */
+    double* out_corrected_wc;           /* G x F x 8, or NULL */
+    double* out_pose;                   /* G x F x 15, or NULL */
+    int32_t* out_info;                  /* G x 4, or NULL */
+    double* out_chi2;                   /* G x 2, or NULL */
+} plp_pose_graph_args;
+/* PLP_ERR_INVALID_ARG: a NULL args, negative sizes, pose_stride < 12, max_iter < 0, edge_cap or env_cap < 1, a missing required array.
+ * PLP_ERR_UNSUPPORTED, before anything is written: G > 16, F > 1024, edge_cap > 16384, env_cap > 65536, conn_cap or covis_cap > 65536 --
+ * the state of a call is G (122 edge_cap + 98 env_cap + 60 F) doubles, at most 1.1 GB.  _host also checks that the offset lists ascend.
+ * G == 0: PLP_OK.  _device: DEVICE pointers; k_pg_prepare, k_pg_solve (every iteration without the host) and k_pg_finish, one workgroup of
+ * 512 per problem, on hip_stream, nothing synchronised; the state lives in the context.  _host: HOST pointers, staged, synchronous. */
+plp_status plp_pose_graph_optimize_device(plp_matcher* ctx, const plp_pose_graph_args* args, void* hip_stream);
+plp_status plp_pose_graph_optimize_host(plp_matcher* ctx, const plp_pose_graph_args* args);
+/* Host builds of the same source with a team of one lane, HOST pointers, no GPU and no context needed; the same checks.  Return G, or the
+ * negated plp_status.  _edges_ stops after the edge list (:131-298): out_status, out_num_edges, out_edges and out_sim3_cw only. */
+int32_t plp_model_pose_graph_optimize_host(const plp_pose_graph_args* args);
+int32_t plp_model_pose_graph_edges_host(const plp_pose_graph_args* args);
+/* g2o's Sim3::log of n Sim3 (n x 8 -> n x 7: omega, upsilon, sigma), and its two scalar functions: log on 1e-300 <= x <= 1e300, acos on
+ * -1 <= x <= 1, NaN outside (D22).  Return n, -1 for a refused call. */
+int32_t plp_model_sim3_log_host(const double* sim3, int32_t n, double* out7);
+int32_t plp_model_pose_log_host(const double* x, int32_t n, double* out);
+int32_t plp_model_pose_acos_host(const double* x, int32_t n, double* out);
+/* D22's block skyline solve of (H + lambda I) x = b on a given system of n <= 1024 vertices: first[i] <= i the first column block of row
+ * block i, env the blocks first[i] .. i of every row block in order, each row block as seven scalar rows of 7 (i - first[i] + 1) (the upper
+ * part of a diagonal block is not read), b (7 n).  Returns 1, 0 when a pivot is not positive and finite (x is then zero), -1 refused. */
+int32_t plp_model_block_chol7_host(int32_t n, const int32_t* first, const double* env, const double* b, double lambda, double* out_x);
+
+/* The landmark half of graph_optimizer::optimize (:331-350): out_pos_w[l] = corrected_Sim3_wc[ref].map(Sim3_cw[ref].map(pos_w[l])) with
+ * ref = ref_kf[l], the row the caller resolves (ref_keyfrm_id_in_loop_fusion_ when the landmark's loop_fusion_identifier_ is the current key
+ * frame's, else its reference key frame, :338-340); sim3_cw / corrected_wc are one problem's out_sim3_cw / out_corrected_wc (F x 8).
+ * out_pos_w may be pos_w.  out_status [L]: plp_correct_landmark_status; only a corrected landmark's position is written. */
+typedef enum plp_correct_landmark_status { PLP_CORRECT_LM_OK = 0, PLP_CORRECT_LM_ERASED = 1, PLP_CORRECT_LM_NO_VERTEX = 2 } plp_correct_landmark_status;
+typedef struct plp_correct_landmarks_args {
+    int32_t L, F;                       /* F <= 1024 */
+    const double* pos_w;                /* L x 3 */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const int32_t* ref_kf;              /* L */
+    const uint8_t* kf_erased;           /* F, or NULL */
+    const double* sim3_cw;              /* F x 8 */
+    const double* corrected_wc;         /* F x 8 */
+    double* out_pos_w;                  /* L x 3 */
+    uint8_t* out_status;                /* L */
+} plp_correct_landmarks_args;
+/* _device: DEVICE pointers, one lane per landmark (k_pg_correct_landmarks), asynchronous.  _host: HOST pointers, staged, synchronous. */
+plp_status plp_correct_landmarks_device(plp_matcher* ctx, const plp_correct_landmarks_args* args, void* hip_stream);
+plp_status plp_correct_landmarks_host(plp_matcher* ctx, const plp_correct_landmarks_args* args);
+int32_t plp_model_correct_landmarks_host(const plp_correct_landmarks_args* args);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

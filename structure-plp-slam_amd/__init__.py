@@ -213,6 +213,17 @@ _API = [
     ("plp_covisibility_erase_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_covisibility_erase_host", C.c_int, [_VP, _VP]),
     ("plp_model_covisibility_erase_host", _I32, [_VP]),
+    ("plp_pose_graph_optimize_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_pose_graph_optimize_host", C.c_int, [_VP, _VP]),
+    ("plp_model_pose_graph_optimize_host", _I32, [_VP]),
+    ("plp_model_pose_graph_edges_host", _I32, [_VP]),
+    ("plp_model_sim3_log_host", _I32, [_VP, _I32, _VP]),
+    ("plp_model_pose_log_host", _I32, [_VP, _I32, _VP]),
+    ("plp_model_pose_acos_host", _I32, [_VP, _I32, _VP]),
+    ("plp_model_block_chol7_host", _I32, [_I32, _VP, _VP, _VP, C.c_double, _VP]),
+    ("plp_correct_landmarks_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_correct_landmarks_host", C.c_int, [_VP, _VP]),
+    ("plp_model_correct_landmarks_host", _I32, [_VP]),
 ]
 
 
@@ -1263,6 +1274,201 @@ class local_bundle_adjuster:
         r = fn(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, np.asarray(kf_local, np.uint8).reshape(1, -1), inv_level_sigma_sq,
                x_right=x_right, counts=counts, kf_erased=kf_erased, kf_is_origin=kf_is_origin, lm_erased=lm_erased, num_first_iter=self.num_first_iter,
                num_second_iter=self.num_second_iter)
+        return {k: v[0] for k, v in r.items()}
+
+
+# plp_pose_graph_status / plp_pose_graph_edge_type / plp_correct_landmark_status
+POSE_GRAPH_OK, POSE_GRAPH_NO_EDGES, POSE_GRAPH_ENVELOPE_TOO_LARGE, POSE_GRAPH_TOO_MANY_EDGES, POSE_GRAPH_BAD_LOOP_KF = range(5)
+POSE_GRAPH_EDGE_LOOP_CONNECTION, POSE_GRAPH_EDGE_PARENT, POSE_GRAPH_EDGE_LOOP, POSE_GRAPH_EDGE_COVIS = range(1, 5)
+CORRECT_LM_OK, CORRECT_LM_ERASED, CORRECT_LM_NO_VERTEX = range(3)
+POSE_GRAPH_MAX_KF, POSE_GRAPH_MAX_EDGES, POSE_GRAPH_MAX_ENV, POSE_GRAPH_MAX_PROBLEMS = 1024, 1 << 14, 1 << 16, 16
+# the outputs of plp_pose_graph_optimize_*: name -> (shape per problem given (F, edge_cap), dtype, optional)
+POSE_GRAPH_OUTPUTS = dict(status=(lambda F, E: (), np.uint8, False), num_edges=(lambda F, E: (), np.int32, True), edges=(lambda F, E: (E, 3), np.int32, True),
+                          sim3_cw=(lambda F, E: (F, 8), np.float64, True), corrected_wc=(lambda F, E: (F, 8), np.float64, True),
+                          pose=(lambda F, E: (F, 15), np.float64, True), info=(lambda F, E: (4,), np.int32, True), chi2=(lambda F, E: (2,), np.float64, True))
+POSE_GRAPH_TABLES = ("pose", "kf_erased", "kf_id", "kf_parent", "kf_conn", "kf_conn_w", "kf_n_conn", "kf_covis", "kf_covis_w", "kf_n_covis", "kf_loop_offsets",
+                     "kf_loop")
+
+
+def _sim3_list(problems, key):
+    """the CSR of a per-problem {row: Sim3} mapping, rows ascending: (offsets (G + 1,), rows, sims (n, 8))"""
+    off, rows, sims = [0], [], []
+    for pr in problems:
+        for r, v in sorted((pr.get(key) or {}).items()):
+            rows.append(int(r)); sims.append(np.asarray(v, np.float64).reshape(8))
+        off.append(len(rows))
+    return np.asarray(off, np.int32), np.asarray(rows, np.int32), np.asarray(sims, np.float64).reshape(-1, 8)
+
+
+def pose_graph_problems(problems):
+    """The per-problem arrays of a plp_pose_graph_args from a list of dicts(loop_kf, curr_kf, fix_scale=False, pre_corrected={row: Sim3}, non_corrected={row:
+    Sim3}, loop_connections={owner row: set of rows}): the mappings become lists in ascending row, the library's order."""
+    lc_off, lo, lt = [0], [], []
+    for pr in problems:
+        for a, targets in sorted((pr.get("loop_connections") or {}).items()):
+            for b in sorted(targets):
+                lo.append(int(a)); lt.append(int(b))
+        lc_off.append(len(lo))
+    po, pr_, ps = _sim3_list(problems, "pre_corrected")
+    no, nr, ns = _sim3_list(problems, "non_corrected")
+    return dict(loop_kf=np.asarray([p["loop_kf"] for p in problems], np.int32), curr_kf=np.asarray([p["curr_kf"] for p in problems], np.int32),
+                fix_scale=np.asarray([bool(p.get("fix_scale")) for p in problems], np.uint8), pre_offsets=po, pre_row=pr_, pre_sim3=ps, non_offsets=no, non_row=nr,
+                non_sim3=ns, lc_offsets=np.asarray(lc_off, np.int32), lc_owner=np.asarray(lo, np.int32), lc_target=np.asarray(lt, np.int32))
+
+
+def _pose_graph_inputs(tables, problems, edge_cap, env_cap, max_iter):
+    """the input half of a plp_pose_graph_args from numpy arrays: (args struct, the arrays it points to, G, F)"""
+    po = np.ascontiguousarray(tables["pose"], np.float64)
+    if po.ndim != 2:
+        raise PlpError(PLP_ERR_INVALID_ARG, "pose must be (F, pose_stride)")
+    F = po.shape[0]
+    i32 = lambda v, shape: np.ascontiguousarray(v, np.int32).reshape(shape)
+    t = dict(pose=po, kf_erased=None if tables.get("kf_erased") is None else np.ascontiguousarray(tables["kf_erased"], np.uint8).reshape(F),
+             kf_id=i32(tables["kf_id"] if tables.get("kf_id") is not None else np.arange(F), F), kf_parent=i32(tables["kf_parent"], F),
+             kf_conn=i32(tables["kf_conn"], (F, -1)) if F else np.zeros((0, 0), np.int32), kf_n_conn=i32(tables["kf_n_conn"], F),
+             kf_covis=i32(tables["kf_covis"], (F, -1)) if F else np.zeros((0, 0), np.int32), kf_n_covis=i32(tables["kf_n_covis"], F))
+    t["kf_conn_w"] = i32(tables["kf_conn_w"], t["kf_conn"].shape); t["kf_covis_w"] = i32(tables["kf_covis_w"], t["kf_covis"].shape)
+    if tables.get("kf_loop_offsets") is not None:
+        t["kf_loop_offsets"] = i32(tables["kf_loop_offsets"], F + 1); t["kf_loop"] = i32(tables["kf_loop"], -1)
+        if len(t["kf_loop"]) == 0:
+            t["kf_loop"] = np.zeros(1, np.int32)
+    pr = problems if isinstance(problems, dict) else pose_graph_problems(problems)
+    pr = {k: np.ascontiguousarray(v) for k, v in pr.items()}
+    for k in ("pre_row", "pre_sim3", "non_row", "non_sim3", "lc_owner", "lc_target"):          # lists without an entry: the arrays are still required
+        if pr[k].size == 0:
+            pr[k] = np.zeros(8, pr[k].dtype)
+    G = len(pr["loop_kf"])
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(pose_graph_args_c, dict(G=G, F=F, pose_stride=po.shape[1], conn_cap=t["kf_conn"].shape[1], covis_cap=t["kf_covis"].shape[1], edge_cap=int(edge_cap),
+                                        env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: Pt(v) for k, v in t.items()}, **{k: Pt(v) for k, v in pr.items()}})
+    return a, (t, pr), G, F
+
+
+def _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out):
+    """the numpy side of plp_pose_graph_optimize_host and the host builds: call(args struct) runs the entry"""
+    a, keep, G, F = _pose_graph_inputs(tables, problems, edge_cap, env_cap, max_iter)
+    o = {}
+    for k, (shape, dt, optional) in POSE_GRAPH_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
+        if optional and outputs is not None and k not in outputs:
+            continue
+        full = (G,) + shape(F, int(edge_cap))
+        v = None if out is None else out.get(k)
+        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
+            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
+        o[k] = v if v is not None else np.zeros(full, dt)
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    for k in POSE_GRAPH_OUTPUTS:
+        setattr(a, "out_" + k, Pt(o.get(k)))
+    call(a)
+    return o
+
+
+def model_pose_graph_optimize(tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV, max_iter=50, outputs=None, out=None):
+    """Host build of optimize::graph_optimizer::optimize (csrc/pose_graph.hpp, DESIGN.md section 5, D22; no GPU needed): the arguments and the result
+    of matcher.pose_graph_optimize."""
+    def call(a):
+        r = lib().plp_model_pose_graph_optimize_host(C.byref(a))
+        if r != a.G:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out)
+
+
+def model_pose_graph_edges(tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, out=None):
+    """Host build of D22's vertices and edge list alone (:85-298; no GPU needed): dict(status, num_edges, edges (G, edge_cap, 3), sim3_cw (G, F, 8))"""
+    def call(a):
+        r = lib().plp_model_pose_graph_edges_host(C.byref(a))
+        if r != a.G:
+            raise PlpError(-r, lib().plp_last_error().decode())
+    return _pose_graph_host(call, tables, problems, edge_cap, 1, 0, ("num_edges", "edges", "sim3_cw"), out)
+
+
+def model_sim3_log(sim3):
+    """Host build of g2o's Sim3::log as D22 restates it (no GPU needed): sim3 (n, 8) or (8,) -> (n, 7) or (7,): omega, upsilon, sigma"""
+    a = np.ascontiguousarray(sim3, np.float64)
+    single = a.ndim == 1
+    a = a.reshape(-1, 8)
+    o = np.zeros((len(a), 7))
+    if lib().plp_model_sim3_log_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_sim3_log_host")
+    return o[0] if single else o
+
+
+def model_pose_log(x):
+    """Host build of D22's log (no GPU needed): NaN outside 1e-300 <= x <= 1e300"""
+    a = np.ascontiguousarray(x, np.float64).reshape(-1)
+    o = np.zeros_like(a)
+    if lib().plp_model_pose_log_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_log_host")
+    return o
+
+
+def model_pose_acos(x):
+    """Host build of D22's acos (no GPU needed): NaN outside -1 <= x <= 1"""
+    a = np.ascontiguousarray(x, np.float64).reshape(-1)
+    o = np.zeros_like(a)
+    if lib().plp_model_pose_acos_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_acos_host")
+    return o
+
+
+def pose_graph_envelope(H, first):
+    """The skyline of a dense symmetric (7 n, 7 n) matrix in D22's layout: row block i holds the column blocks first[i] .. i as seven rows of 7 (i - first[i] + 1)"""
+    H = np.asarray(H, np.float64)
+    return np.concatenate([H[7 * i:7 * i + 7, 7 * int(f):7 * i + 7].reshape(-1) for i, f in enumerate(first)]) if len(first) else np.zeros(0)
+
+
+def model_block_chol7(H, first, b, lam):
+    """Host build of D22's block skyline solve (no GPU needed): (H + lam I) x = b for a dense symmetric H whose row block i is zero before column block
+    first[i].  Returns (x (7 n,), ok)."""
+    fi = np.ascontiguousarray(first, np.int32).reshape(-1)
+    env = pose_graph_envelope(H, fi); bb = np.ascontiguousarray(b, np.float64).reshape(-1)
+    x = np.zeros(7 * len(fi))
+    P = lambda v: v.ctypes.data if v.size else None
+    r = lib().plp_model_block_chol7_host(len(fi), P(fi), P(env), P(bb), float(lam), P(x))
+    if r < 0:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_block_chol7_host")
+    return x, bool(r)
+
+
+def _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out):
+    pw = np.ascontiguousarray(pos_w, np.float64).reshape(-1, 3); L = len(pw)
+    cw = np.ascontiguousarray(sim3_cw, np.float64).reshape(-1, 8); wc = np.ascontiguousarray(corrected_wc, np.float64).reshape(-1, 8); F = len(cw)
+    rk = np.ascontiguousarray(ref_kf, np.int32).reshape(L)
+    le = None if lm_erased is None else np.ascontiguousarray(lm_erased, np.uint8).reshape(L)
+    ke = None if kf_erased is None else np.ascontiguousarray(kf_erased, np.uint8).reshape(F)
+    o = dict(pos_w=(out or {}).get("pos_w"), status=(out or {}).get("status"))
+    o["pos_w"] = np.zeros((L, 3)) if o["pos_w"] is None else o["pos_w"]
+    o["status"] = np.zeros(L, np.uint8) if o["status"] is None else o["status"]
+    if o["pos_w"].shape != (L, 3) or o["pos_w"].dtype != np.float64 or o["status"].shape != (L,) or o["status"].dtype != np.uint8:
+        raise PlpError(PLP_ERR_INVALID_ARG, "out['pos_w'] must be (L, 3) f64, out['status'] (L,) u8")
+    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    a = _struct(correct_landmarks_args_c, dict(L=L, F=F), dict(pos_w=Pt(pw), lm_erased=Pt(le), ref_kf=Pt(rk), kf_erased=Pt(ke), sim3_cw=Pt(cw), corrected_wc=Pt(wc),
+                                                              out_pos_w=Pt(o["pos_w"]), out_status=Pt(o["status"])))
+    call(a)
+    return o
+
+
+def model_correct_landmarks(pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased=None, kf_erased=None, out=None):
+    """Host build of the landmark half of graph_optimizer::optimize (:331-350; no GPU needed): the arguments and the result of matcher.correct_landmarks"""
+    def call(a):
+        if lib().plp_model_correct_landmarks_host(C.byref(a)) != a.L:
+            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
+    return _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
+
+
+class graph_optimizer:
+    """Mirror of optimize::graph_optimizer (optimize/graph_optimizer.h): the map is the key-frame and graph tables (POSE_GRAPH_TABLES), optimize() takes the
+    rows of the loop and the current key frame and the three mappings of the reference by row; mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, tables, fix_scale, mt=None, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV):
+        self.tables, self.fix_scale, self._mt, self.edge_cap, self.env_cap = tables, bool(fix_scale), mt, int(edge_cap), int(env_cap)
+
+    def optimize(self, loop_kf, curr_kf, non_corrected, pre_corrected, loop_connections):
+        """non_corrected / pre_corrected: {row: Sim3 (8,)}, loop_connections: {row: set of rows}.  Returns dict(status, num_edges, edges, sim3_cw (F, 8),
+        corrected_wc (F, 8), pose (F, 15), info, chi2); rows that are no vertices are zero."""
+        fn = model_pose_graph_optimize if self._mt is None else self._mt.pose_graph_optimize
+        r = fn(self.tables, [dict(loop_kf=loop_kf, curr_kf=curr_kf, fix_scale=self.fix_scale, non_corrected=non_corrected, pre_corrected=pre_corrected,
+                                  loop_connections=loop_connections)], edge_cap=self.edge_cap, env_cap=self.env_cap)
         return {k: v[0] for k, v in r.items()}
 
 
@@ -2379,6 +2585,20 @@ class local_ba_args_c(C.Structure):
                 ("out_round_chi2", _VP)]
 
 
+class pose_graph_args_c(C.Structure):
+    """plp_pose_graph_args"""
+    _fields_ = [(k, C.c_int32) for k in ("G", "F", "pose_stride", "conn_cap", "covis_cap", "edge_cap", "env_cap", "max_iter")] + [(k, _VP) for k in (
+        "pose", "kf_erased", "kf_id", "kf_parent", "kf_conn", "kf_conn_w", "kf_n_conn", "kf_covis", "kf_covis_w", "kf_n_covis", "kf_loop_offsets", "kf_loop",
+        "loop_kf", "curr_kf", "fix_scale", "pre_offsets", "pre_row", "pre_sim3", "non_offsets", "non_row", "non_sim3", "lc_offsets", "lc_owner", "lc_target",
+        "out_status", "out_num_edges", "out_edges", "out_sim3_cw", "out_corrected_wc", "out_pose", "out_info", "out_chi2")]
+
+
+class correct_landmarks_args_c(C.Structure):
+    """plp_correct_landmarks_args"""
+    _fields_ = [("L", C.c_int32), ("F", C.c_int32)] + [(k, _VP) for k in ("pos_w", "lm_erased", "ref_kf", "kf_erased", "sim3_cw", "corrected_wc", "out_pos_w",
+                                                                         "out_status")]
+
+
 class local_map_args_c(C.Structure):
     """plp_local_map_args"""
     _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("LL", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32),
@@ -3444,6 +3664,46 @@ class matcher:
         a.camera = camera_model_c.from_buffer_copy(camera)
         st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
         _check(lib().plp_local_ba_device(self._h, C.byref(a), st))
+
+    def pose_graph_optimize(self, tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV, max_iter=50, outputs=None, out=None):
+        """optimize::graph_optimizer::optimize for G problems over one key-frame table (plp_pose_graph_optimize_host; DESIGN.md section 5, D22): tables a dict of
+        POSE_GRAPH_TABLES (pose (F, >= 12), kf_parent, D21's kf_conn / kf_conn_w / kf_n_conn / kf_covis / kf_covis_w / kf_n_covis, the loop edges kf_loop_offsets
+        (F + 1,) / kf_loop; kf_erased, kf_id (default: the row) optional), problems a list of dicts (pose_graph_problems) or its arrays.  Returns dict(status (G,)
+        u8: POSE_GRAPH_*, num_edges (G,), edges (G, edge_cap, 3), sim3_cw, corrected_wc (G, F, 8), pose (G, F, 15), info (G, 4), chi2 (G, 2)); `outputs` names
+        the optional ones wanted (default all); out[name]: the caller's array (slots the optimizer does not write keep their values)."""
+        call = lambda a: _check(lib().plp_pose_graph_optimize_host(self._h, C.byref(a)))
+        return _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out)
+
+    def pose_graph_optimize_device(self, G, F, tables, problems, out, conn_cap, covis_cap, edge_cap, env_cap, pose_stride=15, max_iter=50, stream=None):
+        """plp_pose_graph_optimize_device: tables / problems: dicts of device pointers (int) or torch tensors on the matcher's device named as POSE_GRAPH_TABLES and
+        as pose_graph_problems() names them; out: dict of the device outputs named as in POSE_GRAPH_OUTPUTS (all but status may be absent); asynchronous, three
+        kernels on the stream"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(pose_graph_args_c, dict(G=int(G), F=int(F), pose_stride=int(pose_stride), conn_cap=int(conn_cap), covis_cap=int(covis_cap), edge_cap=int(edge_cap),
+                                            env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: D(tables.get(k)) for k in POSE_GRAPH_TABLES},
+                                                                                            **{k: D(v) for k, v in problems.items()}})
+        for k in POSE_GRAPH_OUTPUTS:
+            setattr(a, "out_" + k, D(out.get(k)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_pose_graph_optimize_device(self._h, C.byref(a), st))
+
+    def correct_landmarks(self, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased=None, kf_erased=None, out=None):
+        """The landmark half of graph_optimizer::optimize (:331-350; plp_correct_landmarks_host): pos_w (L, 3), ref_kf (L,) the row each landmark is corrected
+        with, sim3_cw / corrected_wc (F, 8) one problem's outputs of pose_graph_optimize.  Returns dict(pos_w (L, 3), status (L,) u8: CORRECT_LM_*); out[name]:
+        the caller's array (a landmark that is not corrected keeps its slot)."""
+        call = lambda a: _check(lib().plp_correct_landmarks_host(self._h, C.byref(a)))
+        return _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
+
+    def correct_landmarks_device(self, L, F, pos_w, ref_kf, sim3_cw, corrected_wc, out_pos_w, out_status, lm_erased=None, kf_erased=None, stream=None):
+        """plp_correct_landmarks_device: device pointers (int) or torch tensors; out_pos_w may be pos_w; asynchronous"""
+        import torch
+        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
+        a = _struct(correct_landmarks_args_c, dict(L=int(L), F=int(F)), dict(pos_w=D(pos_w), lm_erased=D(lm_erased), ref_kf=D(ref_kf), kf_erased=D(kf_erased),
+                                                                            sim3_cw=D(sim3_cw), corrected_wc=D(corrected_wc), out_pos_w=D(out_pos_w),
+                                                                            out_status=D(out_status)))
+        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
+        _check(lib().plp_correct_landmarks_device(self._h, C.byref(a), st))
 
     def local_map(self, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap=0, kf_erased=None,
                   kf_counts=None, kf_lm_lines=None, kf_kl_counts=None, lm_erased=None, lm_erased_lines=None, LL=None, frm_counts=None, frm_lm_lines=None,

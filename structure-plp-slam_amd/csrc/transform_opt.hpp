@@ -71,19 +71,25 @@ __host__ __device__ __forceinline__ void tf_mul(const double* a, const double* b
     out[4] = a[7] * x + a[4]; out[5] = a[7] * y + a[5]; out[6] = a[7] * z + a[6];
     out[7] = a[7] * b[7];
 }
+// where tf_oplus takes exp, sin and cos from: D16's functions with their coefficients as literals (pose_graph.hpp reads the same coefficients from its shared state)
+struct TfMathLit {
+    __host__ __device__ __forceinline__ double exp(double x) const { return pose_exp(x); }
+    __host__ __device__ __forceinline__ void sincos(double x, double& s, double& c) const { pose_sincos(x, s, c); }
+};
 // Sim3(update) * est (transform_vertex::oplusImpl), update = (omega, upsilon, sigma); fix_scale: sigma is taken as 0.  out may not alias est.
-__host__ __device__ __forceinline__ void tf_oplus(const double* u, bool fix_scale, const double* est, double* out) {
+template <class M = TfMathLit>
+__host__ __device__ __forceinline__ void tf_oplus(const double* u, bool fix_scale, const double* est, double* out, const M& math = M()) {
     const double a = u[0], b = u[1], c = u[2];
     const double sigma = fix_scale ? 0.0 : u[6];
     const double theta = __builtin_sqrt((a * a + b * b) + c * c);
-    const double s = pose_exp(sigma);
+    const double s = math.exp(sigma);
     const double O2[9] = {-(b * b + c * c), a * b, a * c, a * b, -(a * a + c * c), b * c, a * c, b * c, -(a * a + b * b)};
     const double O[9] = {0.0, -c, b, c, 0.0, -a, -b, a, 0.0};
     const double eps = 0.00001;
     double A, B, C, k1 = 1.0, k2 = 1.0;      // R = I + k1 Omega + k2 Omega2; theta < eps: I + Omega + Omega2
     double si = 0.0, co = 1.0;
     if (!(theta < eps)) {
-        pose_sincos(theta, si, co);
+        math.sincos(theta, si, co);
         k1 = si / theta;
         k2 = (1.0 - co) / (theta * theta);
     }
