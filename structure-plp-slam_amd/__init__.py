@@ -5,6 +5,11 @@ in ``include/plp_front.h``).  This package is the thin Python host mirror used b
 the bench: class and method names follow the reference's C++ interface
 (``feature::orb_extractor`` — src/PLPSLAM/feature/orb_extractor.h:38-176).  There is no CPU
 fallback: if the shared library is missing or no GPU is visible the calls raise.
+
+Three modules carry what every mirror shares: ``_core`` (the library handle and its symbol table), ``_abi`` (the struct mirrors and
+constants of the header) and ``_marshal`` (arrays, tensors and streams to the ABI's arguments).  Their names are re-exported here.
+The mirrors below are still one file; each subsystem is to move to a module of its own over those three, a pure move per change that
+``tests/golden/package_surface.txt`` guards (everything stays an attribute of the package), with ``matcher`` importing the subsystems.
 """
 import ctypes as C
 import math
@@ -14,251 +19,12 @@ import subprocess
 
 import numpy as np
 
-_PKG = pathlib.Path(__file__).resolve().parent
-ROOT = _PKG.parent
-LIB_PATH = pathlib.Path(os.environ["PLP_FRONT_LIB"]).resolve() if os.environ.get("PLP_FRONT_LIB") else _PKG / "libplp_front.so"   # PLP_FRONT_LIB: an experiment's build (tools/build_variant.sh)
-
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
-                     ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
-assert KP_DTYPE.itemsize == 28
-
-PLP_OK, PLP_ERR_INVALID_ARG, PLP_ERR_NO_DEVICE, PLP_ERR_HIP, PLP_ERR_CAPACITY, PLP_ERR_OVERFLOW, PLP_ERR_UNSUPPORTED = range(7)
-
-
-class PlpError(RuntimeError):
-    def __init__(self, status, detail):
-        super().__init__(f"plp_front status {status}: {detail}")
-        self.status = status
-
-
-class orb_params_c(C.Structure):
-    _fields_ = [("max_num_keypts", C.c_uint32), ("scale_factor", C.c_float), ("num_levels", C.c_uint32),
-                ("ini_fast_thr", C.c_uint32), ("min_fast_thr", C.c_uint32), ("mask_rects", C.c_void_p),
-                ("n_mask_rects", C.c_int32)]
-
-
-def build(verbose=False):
-    """Compile libplp_front.so for gfx950 (hipcc cross-compiles without a GPU)."""
-    r = subprocess.run(["make", "-j", str(min(8, os.cpu_count() or 1)), "-C", str(_PKG / "csrc")], capture_output=not verbose, text=True)
-    if r.returncode != 0:
-        raise RuntimeError("building libplp_front.so failed:\n" + (r.stdout or "") + (r.stderr or ""))
-    return LIB_PATH
-
-
-_lib = None
-
-# every symbol include/plp_front.h declares: (name, restype, argtypes)
-_VP, _I32, _SZ = C.c_void_p, C.c_int32, C.c_size_t
-_API = [
-    ("plp_strerror", C.c_char_p, [C.c_int]),
-    ("plp_last_error", C.c_char_p, []),
-    ("plp_version", C.c_int, []),
-    ("plp_device_count", C.c_int, []),
-    ("plp_orb_default_params", None, [_VP]),
-    ("plp_orb_create", C.c_int, [_VP, C.c_int, _VP]),
-    ("plp_orb_destroy", None, [_VP]),
-    ("plp_orb_set_param", C.c_int, [_VP, C.c_int, C.c_double]),
-    ("plp_orb_get_param", C.c_int, [_VP, C.c_int, _VP]),
-    ("plp_orb_get_tables", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_orb_extract", C.c_int, [_VP, _VP, _I32, _I32, _SZ, _VP, _SZ, _VP, _VP, _I32, _VP]),
-    ("plp_orb_extract_batch_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, _SZ, _SZ, _VP, _SZ, _SZ, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_orb_last_batch_status", C.c_int, [_VP]),
-    ("plp_orb_set_profiling", C.c_int, [_VP, _I32]),
-    ("plp_orb_get_stage_times", C.c_int, [_VP, _VP, _VP]),
-    ("plp_orb_pyramid_level_size", C.c_int, [_VP, _I32, _VP, _VP]),
-    ("plp_orb_pyramid_host", C.c_int, [_VP, _I32, _I32, _VP, _SZ]),
-    ("plp_orb_debug_read", C.c_int, [_VP, C.c_int, _I32, _I32, _VP, _SZ, _VP]),
-    ("plp_model_quadtree_host", _I32, [_VP, _I32, _I32, _I32, C.c_uint32, _VP]),
-    ("plp_model_quadtree_rank_sort_host", _I32, [_VP, _I32, _I32, _VP]),
-    ("plp_model_sincos_host", _I32, [_VP, C.c_int64, _VP, _VP, _VP]),
-    ("plp_model_index_sort_host", _I32, [_VP, _I32, _I32, _VP]),
-    ("plp_model_null_vector4_host", _I32, [_VP, _I32, _VP, _VP]),
-    ("plp_line_create", C.c_int, [C.c_int, _VP]),
-    ("plp_line_destroy", None, [_VP]),
-    ("plp_line_extract", C.c_int, [_VP, _VP, _I32, _I32, _SZ, _VP, _VP, _VP, _I32, _VP]),
-    ("plp_line_extract_batch_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, _SZ, _SZ, _VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_line_last_batch_status", C.c_int, [_VP]),
-    ("plp_line_set_profiling", C.c_int, [_VP, _I32]),
-    ("plp_line_set_grow_waves", C.c_int, [_VP, _I32]),
-    ("plp_line_set_seed_order", C.c_int, [_VP, _I32]),
-    ("plp_line_get_seed_order", C.c_int, [_VP, _VP]),
-    ("plp_line_trim", C.c_int, [_VP]),
-    ("plp_model_seed_introsort_host", _I32, [_VP, C.c_int64, _I32, C.c_uint32]),
-    ("plp_seed_introsort_debug", C.c_int, [_I32, _VP, C.c_int64, _I32, C.c_uint32, _I32, _VP]),
-    ("plp_line_get_stage_times", C.c_int, [_VP, _VP, _VP]),
-    ("plp_line_debug_read", C.c_int, [_VP, C.c_int, _I32, _VP, _SZ, _VP]),
-    ("plp_line_scaled_size", C.c_int, [_VP, _VP, _VP]),
-    ("plp_line_debug_grow_profile", C.c_int, [_VP, _VP]),
-    ("plp_matcher_create", C.c_int, [C.c_int, _VP]),
-    ("plp_matcher_destroy", None, [_VP]),
-    ("plp_match_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_match_host", C.c_int, [_VP, _VP]),
-    ("plp_match_debug_counters", C.c_int, [_VP, _VP]),
-    ("plp_match_debug_plan", C.c_int, [_VP, _VP]),
-    ("plp_match_area_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _VP, _VP, _I32, C.c_float, _I32, _VP, _VP]),
-    ("plp_convert_to_grayscale_device", C.c_int, [_VP, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _I32, _I32, _I32, _VP, C.c_size_t, C.c_size_t, _VP]),
-    ("plp_convert_to_true_depth_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_size_t, C.c_size_t, C.c_double, _I32, _VP, C.c_size_t, C.c_size_t, _VP]),
-    ("plp_rectify_map_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, C.c_size_t, _VP]),
-    ("plp_rectify_map_fisheye_device", C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, C.c_size_t, _VP]),
-    ("plp_remap_linear_device", C.c_int, [_VP, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, C.c_size_t, _I32, _I32, _I32, _VP, C.c_size_t, C.c_size_t, _VP]),
-    ("plp_bow_vocab_create", C.c_int, [C.c_int, _VP, _VP]),
-    ("plp_bow_vocab_destroy", None, [_VP]),
-    ("plp_bow_transform_device", C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_bow_transform_host", C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_bow_query_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_bow_query_host", C.c_int, [_VP, _VP]),
-    ("plp_bow_score_pairs_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_bow_score_pairs_host", C.c_int, [_VP, _VP]),
-    ("plp_model_bow_score_host", C.c_double, [_VP, _VP, _I32, _VP, _VP, _I32]),
-    ("plp_color_vote_device", C.c_int, [_VP, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP]),
-    ("plp_landmark_descriptor_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_landmark_descriptor_host", C.c_int, [_VP, _VP, _VP, _I32, _VP]),
-    ("plp_post_extract_device", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
-    ("plp_post_extract_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_post_extract_model_device", C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _I32, _I32, C.c_size_t, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP]),
-    ("plp_post_extract_model_host", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _I32, C.c_size_t, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_observe_landmarks_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_observe_landmarks_host", C.c_int, [_VP, _VP]),
-    ("plp_observe_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_observe_landmark_lines_host", C.c_int, [_VP, _VP]),
-    ("plp_project_last_frame_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_project_last_frame_host", C.c_int, [_VP, _VP]),
-    ("plp_project_last_frame_lines_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_project_last_frame_lines_host", C.c_int, [_VP, _VP]),
-    ("plp_project_landmarks_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_project_landmarks_host", C.c_int, [_VP, _VP]),
-    ("plp_project_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_project_landmark_lines_host", C.c_int, [_VP, _VP]),
-    ("plp_stereo_keylines_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_stereo_keylines_host", C.c_int, [_VP, _VP]),
-    ("plp_keylines_3d_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_keylines_3d_host", C.c_int, [_VP, _VP]),
-    ("plp_median_depth_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_median_depth_host", C.c_int, [_VP, _VP]),
-    ("plp_triangulate_keyline_pairs_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_triangulate_keyline_pairs_host", C.c_int, [_VP, _VP]),
-    ("plp_keyframe_pair_geometry_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_keyframe_pair_geometry_host", C.c_int, [_VP, _VP]),
-    ("plp_triangulate_keypoint_pairs_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_triangulate_keypoint_pairs_host", C.c_int, [_VP, _VP]),
-    ("plp_landmark_geometry_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_landmark_geometry_host", C.c_int, [_VP, _VP]),
-    ("plp_landmark_line_geometry_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_landmark_line_geometry_host", C.c_int, [_VP, _VP]),
-    ("plp_model_landmark_geometry_host", _I32, [_VP, _I32]),
-    ("plp_sim3_ransac_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_sim3_ransac_host", C.c_int, [_VP, _VP]),
-    ("plp_model_sim3_ransac_host", _I32, [_VP]),
-    ("plp_model_horn_sim3_host", _I32, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_model_sym_eig4_max_host", _I32, [_VP, _I32, _VP, _VP]),
-    ("plp_model_sim3_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
-    ("plp_pnp_ransac_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_pnp_ransac_host", C.c_int, [_VP, _VP]),
-    ("plp_model_pnp_ransac_host", _I32, [_VP]),
-    ("plp_model_epnp_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_model_sym_jacobi_host", _I32, [_VP, _I32, _I32, _VP, _VP, _VP]),
-    ("plp_model_lstsq6_host", _I32, [_VP, _VP, _I32, _I32, _VP, _VP]),
-    ("plp_model_rot_from_abt_host", _I32, [_VP, _I32, _VP, _VP]),
-    ("plp_model_pnp_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
-    ("plp_model_pnp_thresholds_host", _I32, [_VP, _I32, _VP]),
-    ("plp_pose_optimize_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_pose_optimize_host", C.c_int, [_VP, _VP]),
-    ("plp_model_pose_optimize_host", _I32, [_VP]),
-    ("plp_model_pose_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_model_se3_exp_host", _I32, [_VP, _VP, _I32, _VP]),
-    ("plp_model_chol6_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_model_pose_sincos_host", _I32, [_VP, _I32, _VP, _VP]),
-    ("plp_transform_optimize_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_transform_optimize_host", C.c_int, [_VP, _VP]),
-    ("plp_model_transform_optimize_host", _I32, [_VP]),
-    ("plp_model_transform_linearize_host", _I32, [_VP, _VP, _VP, _VP]),
-    ("plp_model_sim3_exp_host", _I32, [_VP, _VP, _I32, _I32, _VP]),
-    ("plp_model_chol7_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_model_pose_exp_host", _I32, [_VP, _I32, _VP]),
-    ("plp_local_ba_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_local_ba_host", C.c_int, [_VP, _VP]),
-    ("plp_model_local_ba_host", _I32, [_VP]),
-    ("plp_local_map_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_local_map_host", C.c_int, [_VP, _VP]),
-    ("plp_model_local_map_host", _I32, [_VP]),
-    ("plp_model_local_ba_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_model_local_ba_solve_host", _I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, C.c_double, _VP, _VP]),
-    ("plp_model_inv3_host", _I32, [_VP, _I32, _VP, _VP]),
-    ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
-    ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
-    ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),
-    ("plp_stereo_compute_batch_device", C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, C.c_float, C.c_float, _VP, _VP, _VP]),
-    ("plp_hamming_matrix_device", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
-    ("plp_hamming_matrix_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP]),
-    ("plp_replay_point_queries_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
-    ("plp_pack_rows_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
-    ("plp_replay_line_queries_device", C.c_int, [_VP, _VP, _I32, _I32, _I32, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I32, _VP, _VP]),
-    ("plp_plane_ransac_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_plane_ransac_host", C.c_int, [_VP, _VP]),
-    ("plp_model_plane_ransac_host", _I32, [_VP]),
-    ("plp_model_plane_fit_host", _I32, [_VP, _I32, _VP, _VP, _I32, _VP, _VP, _VP]),
-    ("plp_model_plane_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _I32, _VP]),
-    ("plp_plane_refine_points_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_plane_refine_points_host", C.c_int, [_VP, _VP]),
-    ("plp_model_plane_refine_points_host", _I32, [_VP]),
-    ("plp_cull_keyframes_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_cull_keyframes_host", C.c_int, [_VP, _VP]),
-    ("plp_model_cull_keyframes_host", _I32, [_VP]),
-    ("plp_cull_landmarks_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_cull_landmarks_host", C.c_int, [_VP, _VP]),
-    ("plp_model_cull_landmarks_host", _I32, [_VP]),
-    ("plp_covisibility_update_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_covisibility_update_host", C.c_int, [_VP, _VP]),
-    ("plp_model_covisibility_update_host", _I32, [_VP]),
-    ("plp_covisibility_erase_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_covisibility_erase_host", C.c_int, [_VP, _VP]),
-    ("plp_model_covisibility_erase_host", _I32, [_VP]),
-    ("plp_pose_graph_optimize_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_pose_graph_optimize_host", C.c_int, [_VP, _VP]),
-    ("plp_model_pose_graph_optimize_host", _I32, [_VP]),
-    ("plp_model_pose_graph_edges_host", _I32, [_VP]),
-    ("plp_model_sim3_log_host", _I32, [_VP, _I32, _VP]),
-    ("plp_model_pose_log_host", _I32, [_VP, _I32, _VP]),
-    ("plp_model_pose_acos_host", _I32, [_VP, _I32, _VP]),
-    ("plp_model_block_chol7_host", _I32, [_I32, _VP, _VP, _VP, C.c_double, _VP]),
-    ("plp_correct_landmarks_device", C.c_int, [_VP, _VP, _VP]),
-    ("plp_correct_landmarks_host", C.c_int, [_VP, _VP]),
-    ("plp_model_correct_landmarks_host", _I32, [_VP]),
-]
-
-
-def api_symbols():
-    return [n for n, _, _ in _API]
-
-
-def lib():
-    """Load libplp_front.so; raises if it has not been built (no fallback path exists)."""
-    global _lib
-    if _lib is None:
-        if not LIB_PATH.exists():
-            raise FileNotFoundError(f"{LIB_PATH} is missing: run __graft_entry__.build() (hipcc --offload-arch=gfx950)")
-        try:
-            # PyTorch bundles its own HIP/HSA runtime; a process must hold exactly one.  Loading torch first
-            # makes libplp_front.so (NEEDED libamdhip64.so.7) bind to that copy instead of /opt/rocm's.
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(str(LIB_PATH))
-        for name, res, args in _API:
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
-
-def _check(status):
-    if status != PLP_OK:
-        raise PlpError(status, lib().plp_last_error().decode())
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
+# _lib below is the value at import time (None), kept as a name of the package only: the loaded handle is _core._lib, read through lib()
+from ._core import (LIB_PATH, PLP_ERR_CAPACITY, PLP_ERR_HIP, PLP_ERR_INVALID_ARG, PLP_ERR_NO_DEVICE, PLP_ERR_OVERFLOW, PLP_ERR_UNSUPPORTED, PLP_OK, PlpError,
+                    ROOT, _API, _I32, _PKG, _SZ, _VP, _check, _lib, _p, api_symbols, build, lib)
+from ._abi import *        # noqa: F401,F403  every struct mirror, record dtype, enum and limit of include/plp_front.h
+from ._abi import _struct
+from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, stream_handle, wanted
 
 
 def model_quadtree(xys, level_w, level_h, quota):
@@ -275,9 +41,6 @@ def model_quadtree_rank_sort(keys, shift=0):
     perm = np.zeros(max(len(k), 1), np.uint32)
     assert lib().plp_model_quadtree_rank_sort_host(_p(k), len(k), int(shift), _p(perm)) == len(k)
     return perm[:len(k)].copy()
-
-
-SEED_ORDER_STABLE, SEED_ORDER_LIBSTDCXX = 0, 1          # plp_seed_order (include/plp_front.h)
 
 
 def model_seed_introsort(entries, depth_limit=-1, skip_key=0):
@@ -334,20 +97,12 @@ def _landmark_geometry_host(call, lines, pose, feats, pos_w, ref_kf, obs_offsets
     cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
     sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
     sl = np.ascontiguousarray(scale_factors_lsd, np.float32).reshape(-1) if lines else None
-    shapes = dict(min_dist=((L,), np.float32), max_dist=((L,), np.float32), status=((L,), np.uint8))
-    if not lines:
-        shapes["normal"] = ((L, 3), np.float64)
-    o = {}
-    for k, (shape, dt) in shapes.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-        o[k] = v if v is not None else np.zeros(shape, dt)
-    P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    a = _struct(landmark_geometry_args_c, dict(F=F, cap=M, L=L, num_levels=len(sf), num_levels_lsd=len(sl) if lines else 0), dict(
-        pose=P(po), counts=P(cn), keypts=None if lines else P(ft), keylines=P(ft) if lines else None, scale_factors=P(sf), scale_factors_lsd=P(sl),
-        pos_w=P(pw), ref_kf=P(rk), skip=P(sk), obs_offsets=P(oo), obs_kf=P(ok), obs_idx=P(oi), out_mean_normal=P(o.get("normal")),
-        out_min_valid_dist=P(o["min_dist"]), out_max_valid_dist=P(o["max_dist"]), out_status=P(o["status"])))
+    o = out_arrays((("min_dist", (L,), np.float32), ("max_dist", (L,), np.float32), ("status", (L,), np.uint8))
+                   + (() if lines else (("normal", (L, 3), np.float64),)), out)
+    a = _struct(landmark_geometry_args_c, dict(F=F, cap=M, L=L, num_levels=len(sf), num_levels_lsd=len(sl) if lines else 0), host_ptrs(
+        pose=po, counts=cn, keypts=None if lines else ft, keylines=ft if lines else None, scale_factors=sf, scale_factors_lsd=sl, pos_w=pw, ref_kf=rk,
+        skip=sk, obs_offsets=oo, obs_kf=ok, obs_idx=oi, out_mean_normal=o.get("normal"), out_min_valid_dist=o["min_dist"], out_max_valid_dist=o["max_dist"],
+        out_status=o["status"]))
     call(a)
     return o
 
@@ -356,11 +111,8 @@ def model_landmark_geometry(pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs
                             lines=False, out=None):
     """Host build of landmark::update_normal_and_depth / Line::update_information (csrc/landmark_geometry.hpp, DESIGN.md section 5, D11; no GPU
     needed): the arguments and the result of matcher.landmark_geometry (lines: matcher.landmark_line_geometry)."""
-    def call(a):
-        if lib().plp_model_landmark_geometry_host(C.byref(a), int(bool(lines))) != a.L:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _landmark_geometry_host(call, bool(lines), pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip,
-                                   counts, out)
+    return _landmark_geometry_host(model_call("plp_model_landmark_geometry_host", "L", int(bool(lines))), bool(lines), pose, feats, pos_w, ref_kf, obs_offsets,
+                                   obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip, counts, out)
 
 
 def model_bow_score(wa, va, wb, vb):
@@ -370,8 +122,7 @@ def model_bow_score(wa, va, wb, vb):
     wb = np.ascontiguousarray(wb, np.uint32).reshape(-1); vb = np.ascontiguousarray(vb, np.float64).reshape(-1)
     if len(wa) != len(va) or len(wb) != len(vb):
         raise PlpError(PLP_ERR_INVALID_ARG, "words and values must have the same length")
-    P = lambda v: v.ctypes.data if v.size else None
-    return float(lib().plp_model_bow_score_host(P(wa), P(va), len(wa), P(wb), P(vb), len(wb)))
+    return float(lib().plp_model_bow_score_host(host_ptr(wa), host_ptr(va), len(wa), host_ptr(wb), host_ptr(vb), len(wb)))
 
 
 def model_null_vector4(A):
@@ -393,8 +144,7 @@ def model_sym_eig4_max(N):
     single = N.ndim == 2
     N = N.reshape(-1, 16)
     v = np.zeros((len(N), 4), np.float64); sw = np.zeros(len(N), np.int32)
-    P = lambda a: a.ctypes.data if a.size else None
-    assert lib().plp_model_sym_eig4_max_host(P(N), len(N), P(v), P(sw)) == len(N)
+    assert lib().plp_model_sym_eig4_max_host(host_ptr(N), len(N), host_ptr(v), host_ptr(sw)) == len(N)
     return (v[0], int(sw[0])) if single else (v, sw)
 
 
@@ -410,22 +160,17 @@ def model_horn_sim3(pts_1, pts_2, fix_scale=False):
     n = len(a)
     o = dict(rot_12=np.zeros((n, 3, 3)), trans_12=np.zeros((n, 3)), scale_12=np.zeros(n, np.float32), rot_21=np.zeros((n, 3, 3)), trans_21=np.zeros((n, 3)),
              scale_21=np.zeros(n, np.float32), sweeps=np.zeros(n, np.int32))
-    P = lambda v: v.ctypes.data if v.size else None
-    assert lib().plp_model_horn_sim3_host(P(a), P(b), n, int(bool(fix_scale)), P(o["rot_12"]), P(o["trans_12"]), P(o["scale_12"]), P(o["rot_21"]),
-                                          P(o["trans_21"]), P(o["scale_21"]), P(o["sweeps"])) == n
+    assert lib().plp_model_horn_sim3_host(host_ptr(a), host_ptr(b), n, int(bool(fix_scale)), host_ptr(o["rot_12"]), host_ptr(o["trans_12"]),
+                                          host_ptr(o["scale_12"]), host_ptr(o["rot_21"]), host_ptr(o["trans_21"]), host_ptr(o["scale_21"]), host_ptr(o["sweeps"])) == n
     return {k: v[0] for k, v in o.items()} if single else o
 
 
 def model_sim3_draw(seed, p, iters, num_common, iter0=0):
     """The samples plp_sim3_ransac_* draw for problem p when the caller passes none (D13's generator; no GPU needed): (iters, 3) i32"""
     out = np.zeros((int(iters), 3), np.int32)
-    if lib().plp_model_sim3_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_common), out.ctypes.data if out.size else None) != int(iters):
+    if lib().plp_model_sim3_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_common), host_ptr(out)) != int(iters):
         raise PlpError(PLP_ERR_INVALID_ARG, "num_common must be at least 3, iters non-negative")
     return out
-
-
-# plp_sim3_status: where sim3_solver::find_via_ransac leaves a problem
-SIM3_OK, SIM3_TOO_FEW_POINTS, SIM3_TOO_FEW_INLIERS = range(3)
 # the outputs of plp_sim3_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
 SIM3_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_common=(lambda M, I: (), np.int32, False), rot_12=(lambda M, I: (3, 3), np.float64, False),
                     trans_12=(lambda M, I: (3,), np.float64, False), scale_12=(lambda M, I: (), np.float32, False),
@@ -449,22 +194,11 @@ def _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2,
     I = int(iters)
     sm = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(P_, I, 3)
     cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
-    o = {}
-    for k, (shape, dt, optional) in SIM3_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (P_,) + shape(M, max(I, 0))
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    o = out_arrays(((k, (P_,) + shape(M, max(I, 0)), dt) for k, (shape, dt, optional) in SIM3_OUTPUTS.items() if wanted(k, optional, outputs)), out)
     a = _struct(sim3_ransac_args_c, dict(P=P_, n_cap=M, fix_scale=int(bool(fix_scale)), min_num_inliers=int(min_num_inliers), iters=I,
-                                         seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(s1)), dict(
-        level_sigma_sq_1=Pt(s1), level_sigma_sq_2=Pt(s2), counts=Pt(cn), valid=Pt(va), pos_w_1=Pt(w1), pos_w_2=Pt(w2), octave_1=Pt(o1), octave_2=Pt(o2),
-        pose_1=Pt(p1), pose_2=Pt(p2), samples=Pt(sm), out_status=Pt(o["status"]), out_num_common=Pt(o["num_common"]), out_rot_12=Pt(o["rot_12"]),
-        out_trans_12=Pt(o["trans_12"]), out_scale_12=Pt(o["scale_12"]), out_num_inliers=Pt(o["num_inliers"]), out_best_iter=Pt(o["best_iter"]),
-        out_inliers=Pt(o.get("inliers")), out_hyp_inliers=Pt(o.get("hyp_inliers"))))
+                                         seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(s1)), host_ptrs(
+        level_sigma_sq_1=s1, level_sigma_sq_2=s2, counts=cn, valid=va, pos_w_1=w1, pos_w_2=w2, octave_1=o1, octave_2=o2, pose_1=p1, pose_2=p2, samples=sm))
+    set_outputs(a, SIM3_OUTPUTS, o, host_ptr)
     a.camera = camera_model_c.from_buffer_copy(camera)
     call(a)
     return o
@@ -474,11 +208,8 @@ def model_sim3_ransac(camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_
                       min_num_inliers=20, samples=None, seed=0, counts=None, outputs=None, out=None):
     """Host build of solve::sim3_solver's constructor and find_via_ransac (csrc/sim3.hpp, DESIGN.md section 5, D13; no GPU needed): the arguments
     and the result of matcher.sim3_ransac."""
-    def call(a):
-        if lib().plp_model_sim3_ransac_host(C.byref(a)) != a.P:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters, fix_scale,
-                             min_num_inliers, samples, seed, counts, outputs, out)
+    return _sim3_ransac_host(model_call("plp_model_sim3_ransac_host", "P"), camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2,
+                             level_sigma_sq_1, level_sigma_sq_2, iters, fix_scale, min_num_inliers, samples, seed, counts, outputs, out)
 
 
 class sim3_solver:
@@ -517,11 +248,6 @@ class sim3_solver:
         return self._r["inliers"][0].astype(bool)
 
 
-# plp_plane_mode, plp_plane_status, the landmark byte and out_flags of plp_plane_ransac_* (include/plp_front.h)
-PLANE_CREATE, PLANE_UPDATE = range(2)
-PLANE_OK, PLANE_TOO_FEW_POINTS, PLANE_NO_ELIGIBLE, PLANE_NOT_FOUND, PLANE_ERROR_ABOVE_THRESHOLD, PLANE_TOO_FEW_LEFT = range(6)
-PLANE_LM_ERASED, PLANE_LM_OWNED = 1, 2
-PLANE_FLAG_INVALID, PLANE_FLAG_NEED_REFINEMENT, PLANE_FLAG_GATED = 1, 2, 4
 # the outputs of plp_plane_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
 PLANE_RANSAC_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), flags=(lambda M, I: (), np.uint8, False),
                             equation=(lambda M, I: (4,), np.float64, False), best_error=(lambda M, I: (), np.float64, False),
@@ -556,21 +282,12 @@ def _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, poin
     if sm is not None and (sm.ndim != 3 or sm.shape[:2] != (P_, I)):
         raise PlpError(PLP_ERR_INVALID_ARG, "samples must be (P, iters, m_cap)")
     cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
-    o = {}
-    for k, (shape, dt, optional) in PLANE_RANSAC_OUTPUTS.items():   # the caller's arrays are the outputs when given (what the library does not write keeps its value)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (P_,) + shape(M, max(I, 0))
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    o = out_arrays(((k, (P_,) + shape(M, max(I, 0)), dt) for k, (shape, dt, optional) in PLANE_RANSAC_OUTPUTS.items() if wanted(k, optional, outputs)), out)
     a = _struct(plane_ransac_args_c, dict(mode=int(mode), P=P_, n_cap=M, points_per_ransac=int(points_per_ransac),
                                           min_points_before_ransac=int(min_points_before_ransac), iters=I, inliers_ratio_thr=float(inliers_ratio_thr),
-                                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=0 if sm is None else sm.shape[2]), dict(
-        counts=Pt(cn), pos_w=Pt(pw), flags=Pt(fl), dist_thresh=Pt(dt_), error_thresh=Pt(et_), best_error_in=Pt(be), equation_in=Pt(eq), samples=Pt(sm),
-        **{"out_" + k: Pt(o.get(k)) for k in PLANE_RANSAC_OUTPUTS}))
+                                          seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=0 if sm is None else sm.shape[2]), host_ptrs(
+        counts=cn, pos_w=pw, flags=fl, dist_thresh=dt_, error_thresh=et_, best_error_in=be, equation_in=eq, samples=sm))
+    set_outputs(a, PLANE_RANSAC_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -579,11 +296,8 @@ def model_plane_ransac(mode, pos_w, flags, dist_thresh, error_thresh, points_per
                        best_error_in=None, equation_in=None, samples=None, seed=0, counts=None, outputs=None, out=None):
     """Host build of Planar_Mapping_module's RANSAC (csrc/plane_fit.hpp; no GPU needed): the arguments and the result
     of matcher.plane_ransac."""
-    def call(a):
-        if lib().plp_model_plane_ransac_host(C.byref(a)) != a.P:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac, min_points_before_ransac, iters, inliers_ratio_thr,
-                              best_error_in, equation_in, samples, seed, counts, outputs, out)
+    return _plane_ransac_host(model_call("plp_model_plane_ransac_host", "P"), mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac,
+                              min_points_before_ransac, iters, inliers_ratio_thr, best_error_in, equation_in, samples, seed, counts, outputs, out)
 
 
 def model_plane_fit(pos_w, lists):
@@ -596,8 +310,7 @@ def model_plane_fit(pos_w, lists):
     idx = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), np.int32)
     n = len(lists)
     eq = np.zeros((n, 4)); res = np.zeros(n); sw = np.zeros(n, np.int32)
-    Pt = lambda v: v.ctypes.data if v.size else None
-    if lib().plp_model_plane_fit_host(Pt(pw), len(pw), Pt(idx), Pt(off), n, Pt(eq), Pt(res), Pt(sw)) != n:
+    if lib().plp_model_plane_fit_host(host_ptr(pw), len(pw), host_ptr(idx), host_ptr(off), n, host_ptr(eq), host_ptr(res), host_ptr(sw)) != n:
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_plane_fit_host")
     return eq, res, sw
 
@@ -606,7 +319,7 @@ def model_plane_draw(seed, p, iters, m, n_eligible, iter0=0):
     """The ranks plp_plane_ransac_* draw for problem p when the caller passes none (D19 item 2; no GPU needed): (iters, m) i32"""
     out = np.zeros((int(iters), int(m)), np.int32)
     if lib().plp_model_plane_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(m), int(n_eligible),
-                                       out.ctypes.data if out.size else None) != int(iters):
+                                       host_ptr(out)) != int(iters):
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_plane_draw_host: n_eligible must be at least 1")
     return out
 
@@ -619,19 +332,14 @@ def _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thre
     eq = np.ascontiguousarray(equation, np.float64).reshape(-1, 4); ac = np.ascontiguousarray(active, np.uint8).reshape(len(eq))
     th = np.array([dist_thresh], np.float64)
     ch = np.zeros(M, np.uint8)
-    Pt = lambda v: v.ctypes.data if v.size else None
-    call(_struct(plane_refine_args_c, dict(M=M, NP=len(eq)), dict(pos_w=Pt(pw), lm_plane=Pt(lp), flags=Pt(fl), equation=Pt(eq), active=Pt(ac),
-                                                                  dist_thresh=Pt(th), out_changed=Pt(ch))))
+    call(_struct(plane_refine_args_c, dict(M=M, NP=len(eq)), host_ptrs(pos_w=pw, lm_plane=lp, flags=fl, equation=eq, active=ac, dist_thresh=th, out_changed=ch)))
     return pw, ch
 
 
 def model_plane_refine_points(pos_w, lm_plane, flags, equation, active, dist_thresh):
     """Host build of Planar_Mapping_module::refine_points (csrc/plane_fit.hpp, D19; no GPU needed): the arguments and result of
     matcher.plane_refine_points."""
-    def call(a):
-        if lib().plp_model_plane_refine_points_host(C.byref(a)) != a.M:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh)
+    return _plane_refine_host(model_call("plp_model_plane_refine_points_host", "M"), pos_w, lm_plane, flags, equation, active, dist_thresh)
 
 
 class planar_mapper:
@@ -692,8 +400,7 @@ def model_sym_jacobi(A):
     A = A.reshape(-1, d * d)
     n = len(A)
     vals = np.zeros((n, d)); ut = np.zeros((n, d, d)); sw = np.zeros(n, np.int32)
-    P = lambda a: a.ctypes.data if a.size else None
-    if lib().plp_model_sym_jacobi_host(P(A), d, n, P(vals), P(ut), P(sw)) != n:
+    if lib().plp_model_sym_jacobi_host(host_ptr(A), d, n, host_ptr(vals), host_ptr(ut), host_ptr(sw)) != n:
         raise PlpError(PLP_ERR_INVALID_ARG, "A must be (n, 3, 3) or (n, 12, 12)")
     return (vals[0], ut[0], int(sw[0])) if single else (vals, ut, sw)
 
@@ -707,8 +414,7 @@ def model_lstsq6(A, b):
     A = A.reshape(-1, 6 * k); b = b.reshape(-1, 6)
     n = len(A)
     x = np.zeros((n, k)); sw = np.zeros(n, np.int32)
-    P = lambda a: a.ctypes.data if a.size else None
-    if len(b) != n or lib().plp_model_lstsq6_host(P(A), P(b), k, n, P(x), P(sw)) != n:
+    if len(b) != n or lib().plp_model_lstsq6_host(host_ptr(A), host_ptr(b), k, n, host_ptr(x), host_ptr(sw)) != n:
         raise PlpError(PLP_ERR_INVALID_ARG, "A must be (n, 6, k) with k = 3, 4, 5 and b (n, 6)")
     return (x[0], int(sw[0])) if single else (x, sw)
 
@@ -721,8 +427,7 @@ def model_rot_from_abt(Abt):
     A = A.reshape(-1, 9)
     n = len(A)
     R = np.zeros((n, 3, 3)); sw = np.zeros(n, np.int32)
-    P = lambda a: a.ctypes.data if a.size else None
-    assert lib().plp_model_rot_from_abt_host(P(A), n, P(R), P(sw)) == n
+    assert lib().plp_model_rot_from_abt_host(host_ptr(A), n, host_ptr(R), host_ptr(sw)) == n
     return (R[0], int(sw[0])) if single else (R, sw)
 
 
@@ -740,8 +445,8 @@ def model_epnp(pos_w, bearing, offsets=None):
     if n < 0 or (n and int(off[-1]) > len(w)):
         raise PlpError(PLP_ERR_INVALID_ARG, "offsets must be ascending within the rows")
     o = dict(rot=np.zeros((n, 3, 3)), trans=np.zeros((n, 3)), err=np.zeros(n), N=np.zeros(n, np.int32), sweeps=np.zeros((n, 8), np.int32))
-    P = lambda a: a.ctypes.data if a.size else None
-    if lib().plp_model_epnp_host(P(w), P(b), P(off), n, P(o["rot"]), P(o["trans"]), P(o["err"]), P(o["N"]), P(o["sweeps"])) != n:
+    if lib().plp_model_epnp_host(host_ptr(w), host_ptr(b), host_ptr(off), n, host_ptr(o["rot"]), host_ptr(o["trans"]), host_ptr(o["err"]),
+                                 host_ptr(o["N"]), host_ptr(o["sweeps"])) != n:
         raise PlpError(PLP_ERR_INVALID_ARG, "offsets must be ascending within the rows")
     return {k: v[0] for k, v in o.items()} if single else o
 
@@ -749,7 +454,7 @@ def model_epnp(pos_w, bearing, offsets=None):
 def model_pnp_draw(seed, p, iters, num_matches, iter0=0):
     """The samples plp_pnp_ransac_* draw for problem p when the caller passes none (D14's generator; no GPU needed): (iters, 4) i32"""
     out = np.zeros((int(iters), 4), np.int32)
-    if lib().plp_model_pnp_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_matches), out.ctypes.data if out.size else None) != int(iters):
+    if lib().plp_model_pnp_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_matches), host_ptr(out)) != int(iters):
         raise PlpError(PLP_ERR_INVALID_ARG, "num_matches must be at least 4, iters non-negative")
     return out
 
@@ -758,12 +463,10 @@ def model_pnp_thresholds(scale_factors):
     """max_cos_errors_ per level (solve/pnp_solver.cc:47-51): util::cos((float)(scale_factors[l] * (1.0 * M_PI / 180.0))), f32 (no GPU needed)"""
     sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
     out = np.zeros(len(sf), np.float32)
-    assert lib().plp_model_pnp_thresholds_host(sf.ctypes.data if len(sf) else None, len(sf), out.ctypes.data if len(sf) else None) == len(sf)
+    assert lib().plp_model_pnp_thresholds_host(host_ptr(sf), len(sf), host_ptr(out)) == len(sf)
     return out
 
 
-# plp_pnp_status: where pnp_solver::find_via_ransac leaves a problem
-PNP_OK, PNP_TOO_FEW_MATCHES, PNP_TOO_FEW_INLIERS = range(3)
 # the outputs of plp_pnp_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
 PNP_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_matches=(lambda M, I: (), np.int32, False), rot_cw=(lambda M, I: (3, 3), np.float64, False),
                    trans_cw=(lambda M, I: (3,), np.float64, False), num_inliers=(lambda M, I: (), np.int32, False),
@@ -782,21 +485,11 @@ def _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, 
     I = int(iters)
     sm = None if samples is None else np.ascontiguousarray(samples, np.int32).reshape(P_, I, 4)
     cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(P_)
-    o = {}
-    for k, (shape, dt, optional) in PNP_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (P_,) + shape(M, max(I, 0))
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+    o = out_arrays(((k, (P_,) + shape(M, max(I, 0)), dt) for k, (shape, dt, optional) in PNP_OUTPUTS.items() if wanted(k, optional, outputs)), out)
     a = _struct(pnp_ransac_args_c, dict(P=P_, n_cap=M, min_num_inliers=int(min_num_inliers), iters=I, recompute=int(bool(recompute)),
-                                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(sf)), dict(
-        scale_factors=Pt(sf), counts=Pt(cn), valid=Pt(va), bearing=Pt(be), pos_w=Pt(pw), octave=Pt(oc), samples=Pt(sm), out_status=Pt(o["status"]),
-        out_num_matches=Pt(o["num_matches"]), out_rot_cw=Pt(o["rot_cw"]), out_trans_cw=Pt(o["trans_cw"]), out_num_inliers=Pt(o["num_inliers"]),
-        out_best_iter=Pt(o["best_iter"]), out_inliers=Pt(o.get("inliers")), out_hyp_inliers=Pt(o.get("hyp_inliers"))))
+                                        seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(sf)), host_ptrs(
+        scale_factors=sf, counts=cn, valid=va, bearing=be, pos_w=pw, octave=oc, samples=sm))
+    set_outputs(a, PNP_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -805,10 +498,8 @@ def model_pnp_ransac(valid, bearing, pos_w, octave, scale_factors, iters=30, min
                      outputs=None, out=None):
     """Host build of solve::pnp_solver's constructor and find_via_ransac (csrc/pnp.hpp, DESIGN.md section 5, D14; no GPU needed): the arguments
     and the result of matcher.pnp_ransac."""
-    def call(a):
-        if lib().plp_model_pnp_ransac_host(C.byref(a)) != a.P:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples, seed, counts, outputs, out)
+    return _pnp_ransac_host(model_call("plp_model_pnp_ransac_host", "P"), valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute,
+                            samples, seed, counts, outputs, out)
 
 
 class pnp_solver:
@@ -850,10 +541,6 @@ class pnp_solver:
         return self._r["inliers"][0, :self._n].astype(bool)
 
 
-# plp_pose_opt_status: where pose_optimizer::optimize leaves a frame
-POSE_OPT_OK, POSE_OPT_TOO_FEW_OBS = range(2)
-# why a trial's optimize() ended (trial_info[..., 3]); 0 = the trial was not run
-POSE_OPT_END_ITERATIONS, POSE_OPT_END_TRIES, POSE_OPT_END_RHO_ZERO = 1, 2, 3
 # the outputs of plp_pose_optimize_*: name -> (shape per frame given (n_cap, l_cap, num_trials), dtype, optional)
 POSE_OPT_OUTPUTS = dict(status=(lambda N, L, T: (), np.uint8, False), pose=(lambda N, L, T: (15,), np.float64, False),
                         num_init_obs=(lambda N, L, T: (), np.int32, False), num_valid=(lambda N, L, T: (), np.int32, False),
@@ -881,11 +568,10 @@ def _pose_optimize_inputs(camera, setup_type, pose_in, valid, undist, pos_w, inv
         kl = np.ascontiguousarray(lines["keylines"], KL_DTYPE).reshape(B, L); lw = np.ascontiguousarray(lines["pos_w"], np.float64).reshape(B, L, 6)
         lc = None if lines.get("counts") is None else np.ascontiguousarray(lines["counts"], np.int32).reshape(B)
         sl = np.ascontiguousarray(lines["inv_level_sigma_sq_lsd"], np.float32).reshape(-1)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(pose_optimize_args_c, dict(setup_type=int(setup_type), B=B, n_cap=N, l_cap=L, num_trials=int(num_trials), num_each_iter=int(num_each_iter),
-                                           pose_stride=po.shape[1], num_levels=len(sg), num_levels_lsd=0 if sl is None else len(sl)), dict(
-        inv_level_sigma_sq=Pt(sg), inv_level_sigma_sq_lsd=Pt(sl), pose_in=Pt(po), counts=Pt(cn), line_counts=Pt(lc), valid=Pt(va), undist=Pt(kp), x_right=Pt(xr),
-        pos_w=Pt(pw), line_valid=Pt(lv), keylines=Pt(kl), pos_w_lines=Pt(lw)))
+                                           pose_stride=po.shape[1], num_levels=len(sg), num_levels_lsd=0 if sl is None else len(sl)), host_ptrs(
+        inv_level_sigma_sq=sg, inv_level_sigma_sq_lsd=sl, pose_in=po, counts=cn, line_counts=lc, valid=va, undist=kp, x_right=xr, pos_w=pw, line_valid=lv,
+        keylines=kl, pos_w_lines=lw))
     a.camera = camera_model_c.from_buffer_copy(camera)
     return a, (va, po, kp, pw, xr, cn, sg, lv, kl, lw, lc, sl), B, N, L
 
@@ -895,18 +581,8 @@ def _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w,
     """the numpy side of plp_pose_optimize_host and plp_model_pose_optimize_host: call(args struct) runs the entry"""
     a, keep, B, N, L = _pose_optimize_inputs(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
                                              num_each_iter)
-    o = {}
-    for k, (shape, dt, optional) in POSE_OPT_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (B,) + shape(N, L, max(int(num_trials), 0))
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    for k in POSE_OPT_OUTPUTS:
-        setattr(a, "out_" + k, Pt(o.get(k)))
+    o = out_arrays(((k, (B,) + shape(N, L, max(int(num_trials), 0)), dt) for k, (shape, dt, optional) in POSE_OPT_OUTPUTS.items() if wanted(k, optional, outputs)), out)
+    set_outputs(a, POSE_OPT_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -915,12 +591,8 @@ def model_pose_optimize(camera, setup_type, pose_in, valid, undist, pos_w, inv_l
                         num_each_iter=10, outputs=None, out=None):
     """Host build of optimize::pose_optimizer[_extended_line]::optimize (csrc/pose_opt.hpp, DESIGN.md section 5, D15; no GPU needed): the arguments
     and the result of matcher.pose_optimize."""
-    def call(a):
-        r = lib().plp_model_pose_optimize_host(C.byref(a))
-        if r != a.B:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
-                               num_each_iter, outputs, out)
+    return _pose_optimize_host(model_call("plp_model_pose_optimize_host", "B", neg_status=True), camera, setup_type, pose_in, valid, undist, pos_w,
+                               inv_level_sigma_sq, x_right, counts, lines, num_trials, num_each_iter, outputs, out)
 
 
 def model_pose_linearize(camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, robust=True,
@@ -932,12 +604,11 @@ def model_pose_linearize(camera, setup_type, pose_in, valid, undist, pos_w, inv_
     ac = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(B, N)
     al = None if active_lines is None else np.ascontiguousarray(active_lines, np.uint8).reshape(B, L)
     sums = np.zeros((B, 28)); ec = np.full((B, N), np.nan); el = np.full((B, L), np.nan)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     # the checks of the entry want its required outputs
     dummy = _pose_optimize_host(lambda a_: None, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, 1, 1, None, None)
     for k in ("status", "pose", "num_init_obs", "num_valid", "outlier", "outlier_lines"):
-        setattr(a, "out_" + k, Pt(dummy[k]))
-    r = lib().plp_model_pose_linearize_host(C.byref(a), int(bool(robust)), Pt(ac), Pt(al), Pt(sums), Pt(ec), Pt(el))
+        setattr(a, "out_" + k, host_ptr(dummy[k]))
+    r = lib().plp_model_pose_linearize_host(C.byref(a), int(bool(robust)), host_ptr(ac), host_ptr(al), host_ptr(sums), host_ptr(ec), host_ptr(el))
     if r != B:
         raise PlpError(-r, lib().plp_last_error().decode())
     return dict(H=sums[:, :21].copy(), b=sums[:, 21:27].copy(), chi2=sums[:, 27].copy(), edge_chi2=ec, edge_chi2_lines=el)
@@ -999,8 +670,6 @@ class pose_optimizer:
         return int(o["num_valid"]), o
 
 
-# plp_transform_opt_status: where transform_optimizer::optimize leaves a problem
-TRANSFORM_OPT_OK, TRANSFORM_OPT_TOO_FEW_INLIERS = range(2)
 # the outputs of plp_transform_optimize_*: name -> (shape per problem given n_cap, dtype, optional); round_info[..., 3] is a POSE_OPT_END_*
 TRANSFORM_OPT_OUTPUTS = dict(status=(lambda N: (), np.uint8, False), num_valid=(lambda N: (), np.int32, False), num_inliers=(lambda N: (), np.int32, False),
                              rot_12=(lambda N: (9,), np.float64, False), trans_12=(lambda N: (3,), np.float64, False), scale_12=(lambda N: (), np.float64, False),
@@ -1024,10 +693,9 @@ def _transform_optimize_inputs(camera, fix_scale, valid, pos_w_1, pos_w_2, undis
     s1 = np.ascontiguousarray(inv_level_sigma_sq_1, np.float32).reshape(-1); s2 = np.ascontiguousarray(inv_level_sigma_sq_2, np.float32).reshape(-1)
     if len(s1) != len(s2):
         raise PlpError(PLP_ERR_INVALID_ARG, "the two sigma tables must have one length")
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    a = _struct(transform_optimize_args_c, dict(fix_scale=int(bool(fix_scale)), num_iter=int(num_iter), chi_sq=float(chi_sq), P=P, n_cap=N, num_levels=len(s1)), dict(
-        inv_level_sigma_sq_1=Pt(s1), inv_level_sigma_sq_2=Pt(s2), counts=Pt(cn), valid=Pt(va), pos_w_1=Pt(w1), pos_w_2=Pt(w2), undist_1=Pt(k1), undist_2=Pt(k2),
-        pose_1=Pt(p1), pose_2=Pt(p2), rot_12=Pt(r), trans_12=Pt(t), scale_12=Pt(sc)))
+    a = _struct(transform_optimize_args_c, dict(fix_scale=int(bool(fix_scale)), num_iter=int(num_iter), chi_sq=float(chi_sq), P=P, n_cap=N, num_levels=len(s1)), host_ptrs(
+        inv_level_sigma_sq_1=s1, inv_level_sigma_sq_2=s2, counts=cn, valid=va, pos_w_1=w1, pos_w_2=w2, undist_1=k1, undist_2=k2, pose_1=p1, pose_2=p2,
+        rot_12=r, trans_12=t, scale_12=sc))
     a.camera = camera_model_c.from_buffer_copy(camera)
     return a, (va, w1, w2, k1, k2, p1, p2, r, t, sc, cn, s1, s2), P, N
 
@@ -1035,18 +703,8 @@ def _transform_optimize_inputs(camera, fix_scale, valid, pos_w_1, pos_w_2, undis
 def _transform_optimize_host(call, inputs, outputs, out):
     """the numpy side of plp_transform_optimize_host and plp_model_transform_optimize_host: call(args struct) runs the entry"""
     a, keep, P, N = _transform_optimize_inputs(**inputs)
-    o = {}
-    for k, (shape, dt, optional) in TRANSFORM_OPT_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (P,) + shape(N)
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    for k in TRANSFORM_OPT_OUTPUTS:
-        setattr(a, "out_" + k, Pt(o.get(k)))
+    o = out_arrays(((k, (P,) + shape(N), dt) for k, (shape, dt, optional) in TRANSFORM_OPT_OUTPUTS.items() if wanted(k, optional, outputs)), out)
+    set_outputs(a, TRANSFORM_OPT_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -1055,10 +713,7 @@ def model_transform_optimize(camera, fix_scale, valid, pos_w_1, pos_w_2, undist_
                              inv_level_sigma_sq_2, counts=None, num_iter=10, chi_sq=10.0, outputs=None, out=None):
     """Host build of optimize::transform_optimizer::optimize (csrc/transform_opt.hpp, DESIGN.md section 5, D16; no GPU needed): the arguments and
     the result of matcher.transform_optimize."""
-    def call(a):
-        r = lib().plp_model_transform_optimize_host(C.byref(a))
-        if r != a.P:
-            raise PlpError(-r, lib().plp_last_error().decode())
+    call = model_call("plp_model_transform_optimize_host", "P", neg_status=True)
     inputs = dict(camera=camera, fix_scale=fix_scale, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1,
                   pose_2=pose_2, rot_12=rot_12, trans_12=trans_12, scale_12=scale_12, inv_level_sigma_sq_1=inv_level_sigma_sq_1,
                   inv_level_sigma_sq_2=inv_level_sigma_sq_2, counts=counts, num_iter=num_iter, chi_sq=chi_sq)
@@ -1076,8 +731,7 @@ def model_transform_linearize(camera, fix_scale, valid, pos_w_1, pos_w_2, undist
     a, keep, P, N = _transform_optimize_inputs(**inputs)
     ac = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(P, N)
     sums = np.zeros((P, 36)); ec = np.full((P, N, 2), np.nan)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    r = lib().plp_model_transform_linearize_host(C.byref(a), Pt(ac), Pt(sums), Pt(ec))
+    r = lib().plp_model_transform_linearize_host(C.byref(a), host_ptr(ac), host_ptr(sums), host_ptr(ec))
     if r != P:
         raise PlpError(-r, lib().plp_last_error().decode())
     return dict(H=sums[:, :28].copy(), b=sums[:, 28:35].copy(), chi2=sums[:, 35].copy(), edge_chi2=ec)
@@ -1136,10 +790,6 @@ class transform_optimizer:
         return int(o["num_inliers"]), o
 
 
-# plp_local_ba_status / plp_local_ba_kf_role
-LOCAL_BA_OK, LOCAL_BA_NO_EDGES, LOCAL_BA_TOO_MANY_FREE = range(3)
-LOCAL_BA_KF_NONE, LOCAL_BA_KF_FREE, LOCAL_BA_KF_ORIGIN, LOCAL_BA_KF_FIXED = range(4)
-LOCAL_BA_MAX_FREE = 64
 # the outputs of plp_local_ba_*: name -> (shape per problem given (F, L, T), dtype, optional); round_info[..., 3] is a POSE_OPT_END_* (0: round not run)
 LOCAL_BA_OUTPUTS = dict(status=(lambda F, L, T: (), np.uint8, False), kf_role=(lambda F, L, T: (F,), np.uint8, False), lm_role=(lambda F, L, T: (L,), np.uint8, False),
                         pose=(lambda F, L, T: (F, 15), np.float64, False), pos_w=(lambda F, L, T: (L, 3), np.float64, False),
@@ -1171,11 +821,10 @@ def _local_ba_inputs(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_k
     ke, ko, le = u8(kf_erased, F), u8(kf_is_origin, F), u8(lm_erased, L)
     cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
     sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(local_ba_args_c, dict(setup_type=int(setup_type), num_first_iter=int(num_first_iter), num_second_iter=int(num_second_iter), G=G, F=F, L=L, T=T,
-                                      kp_stride=int(K), pose_stride=po.shape[1], num_levels=len(sg)), dict(
-        inv_level_sigma_sq=Pt(sg), pose=Pt(po), kf_erased=Pt(ke), kf_is_origin=Pt(ko), undist=Pt(ku), x_right=Pt(xr), counts=Pt(cn), pos_w=Pt(pw), lm_erased=Pt(le),
-        obs_offsets=Pt(oo), obs_kf=Pt(ok), obs_idx=Pt(oi), kf_local=Pt(kl)))
+                                      kp_stride=int(K), pose_stride=po.shape[1], num_levels=len(sg)), host_ptrs(
+        inv_level_sigma_sq=sg, pose=po, kf_erased=ke, kf_is_origin=ko, undist=ku, x_right=xr, counts=cn, pos_w=pw, lm_erased=le, obs_offsets=oo, obs_kf=ok,
+        obs_idx=oi, kf_local=kl))
     a.camera = camera_model_c.from_buffer_copy(camera)
     return a, (po, ku, xr, pw, oo, ok, oi, kl, ke, ko, le, cn, sg), G, F, L, T
 
@@ -1183,18 +832,8 @@ def _local_ba_inputs(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_k
 def _local_ba_host(call, inputs, outputs, out):
     """the numpy side of plp_local_ba_host and plp_model_local_ba_host: call(args struct) runs the entry"""
     a, keep, G, F, L, T = _local_ba_inputs(**inputs)
-    o = {}
-    for k, (shape, dt, optional) in LOCAL_BA_OUTPUTS.items():     # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (G,) + shape(F, L, T)
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    for k in LOCAL_BA_OUTPUTS:
-        setattr(a, "out_" + k, Pt(o.get(k)))
+    o = out_arrays(((k, (G,) + shape(F, L, T), dt) for k, (shape, dt, optional) in LOCAL_BA_OUTPUTS.items() if wanted(k, optional, outputs)), out)
+    set_outputs(a, LOCAL_BA_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -1210,12 +849,9 @@ def model_local_ba(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf,
                    kf_erased=None, kf_is_origin=None, lm_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
     """Host build of optimize::local_bundle_adjuster::optimize (csrc/local_ba.hpp, DESIGN.md section 5, D17; no GPU needed): the arguments and the
     result of matcher.local_ba."""
-    def call(a):
-        r = lib().plp_model_local_ba_host(C.byref(a))
-        if r != a.G:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _local_ba_host(call, _local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts,
-                                             kf_erased, kf_is_origin, lm_erased, num_first_iter, num_second_iter), outputs, out)
+    return _local_ba_host(model_call("plp_model_local_ba_host", "G", neg_status=True), _local_ba_kw(
+        camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts, kf_erased, kf_is_origin, lm_erased,
+        num_first_iter, num_second_iter), outputs, out)
 
 
 def model_local_ba_linearize(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
@@ -1227,8 +863,7 @@ def model_local_ba_linearize(camera, setup_type, pose, undist, pos_w, obs_offset
                                                           x_right, counts, kf_erased, kf_is_origin, lm_erased, 1, 1))
     fk = np.full(LOCAL_BA_MAX_FREE, -1, np.int32); hpp = np.full((LOCAL_BA_MAX_FREE, 27), np.nan); hll = np.full((L, 9), np.nan); w = np.full((T, 18), np.nan)
     chi = np.zeros(1); ec = np.full(T, np.nan)
-    Pt = lambda v: None if v.size == 0 else v.ctypes.data
-    r = lib().plp_model_local_ba_linearize_host(C.byref(a), int(bool(robust)), Pt(fk), Pt(hpp), Pt(hll), Pt(w), Pt(chi), Pt(ec))
+    r = lib().plp_model_local_ba_linearize_host(C.byref(a), int(bool(robust)), host_ptr(fk), host_ptr(hpp), host_ptr(hll), host_ptr(w), host_ptr(chi), host_ptr(ec))
     if r < 0:
         raise PlpError(-r, lib().plp_last_error().decode())
     return dict(free_kf=fk[:r].copy(), Hpp=hpp[:r, :21].copy(), bp=hpp[:r, 21:].copy(), Hll=hll[:, :6].copy(), bl=hll[:, 6:].copy(), W=w.reshape(T, 6, 3),
@@ -1243,8 +878,7 @@ def model_local_ba_solve(Hpp, bp, Hll, bl, e_pose, e_lm, W, lam):
     ep = np.ascontiguousarray(e_pose, np.int32).reshape(-1); el = np.ascontiguousarray(e_lm, np.int32).reshape(-1)
     w = np.ascontiguousarray(W, np.float64).reshape(len(ep), 18)
     xp = np.zeros((len(hp), 6)); xl = np.zeros((len(hl), 3))
-    Pt = lambda v: None if v.size == 0 else v.ctypes.data
-    r = lib().plp_model_local_ba_solve_host(len(hp), len(hl), len(ep), Pt(hp), Pt(hl), Pt(ep), Pt(el), Pt(w), float(lam), Pt(xp), Pt(xl))
+    r = lib().plp_model_local_ba_solve_host(len(hp), len(hl), len(ep), *map(host_ptr, (hp, hl, ep, el, w)), float(lam), host_ptr(xp), host_ptr(xl))
     if r < 0:
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_local_ba_solve_host")
     return xp, xl, bool(r)
@@ -1277,11 +911,6 @@ class local_bundle_adjuster:
         return {k: v[0] for k, v in r.items()}
 
 
-# plp_pose_graph_status / plp_pose_graph_edge_type / plp_correct_landmark_status
-POSE_GRAPH_OK, POSE_GRAPH_NO_EDGES, POSE_GRAPH_ENVELOPE_TOO_LARGE, POSE_GRAPH_TOO_MANY_EDGES, POSE_GRAPH_BAD_LOOP_KF = range(5)
-POSE_GRAPH_EDGE_LOOP_CONNECTION, POSE_GRAPH_EDGE_PARENT, POSE_GRAPH_EDGE_LOOP, POSE_GRAPH_EDGE_COVIS = range(1, 5)
-CORRECT_LM_OK, CORRECT_LM_ERASED, CORRECT_LM_NO_VERTEX = range(3)
-POSE_GRAPH_MAX_KF, POSE_GRAPH_MAX_EDGES, POSE_GRAPH_MAX_ENV, POSE_GRAPH_MAX_PROBLEMS = 1024, 1 << 14, 1 << 16, 16
 # the outputs of plp_pose_graph_optimize_*: name -> (shape per problem given (F, edge_cap), dtype, optional)
 POSE_GRAPH_OUTPUTS = dict(status=(lambda F, E: (), np.uint8, False), num_edges=(lambda F, E: (), np.int32, True), edges=(lambda F, E: (E, 3), np.int32, True),
                           sim3_cw=(lambda F, E: (F, 8), np.float64, True), corrected_wc=(lambda F, E: (F, 8), np.float64, True),
@@ -1338,27 +967,16 @@ def _pose_graph_inputs(tables, problems, edge_cap, env_cap, max_iter):
         if pr[k].size == 0:
             pr[k] = np.zeros(8, pr[k].dtype)
     G = len(pr["loop_kf"])
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(pose_graph_args_c, dict(G=G, F=F, pose_stride=po.shape[1], conn_cap=t["kf_conn"].shape[1], covis_cap=t["kf_covis"].shape[1], edge_cap=int(edge_cap),
-                                        env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: Pt(v) for k, v in t.items()}, **{k: Pt(v) for k, v in pr.items()}})
+                                        env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: host_ptr(v) for k, v in t.items()}, **{k: host_ptr(v) for k, v in pr.items()}})
     return a, (t, pr), G, F
 
 
 def _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out):
     """the numpy side of plp_pose_graph_optimize_host and the host builds: call(args struct) runs the entry"""
     a, keep, G, F = _pose_graph_inputs(tables, problems, edge_cap, env_cap, max_iter)
-    o = {}
-    for k, (shape, dt, optional) in POSE_GRAPH_OUTPUTS.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-        if optional and outputs is not None and k not in outputs:
-            continue
-        full = (G,) + shape(F, int(edge_cap))
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    for k in POSE_GRAPH_OUTPUTS:
-        setattr(a, "out_" + k, Pt(o.get(k)))
+    o = out_arrays(((k, (G,) + shape(F, int(edge_cap)), dt) for k, (shape, dt, optional) in POSE_GRAPH_OUTPUTS.items() if wanted(k, optional, outputs)), out)
+    set_outputs(a, POSE_GRAPH_OUTPUTS, o, host_ptr)
     call(a)
     return o
 
@@ -1366,20 +984,13 @@ def _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, output
 def model_pose_graph_optimize(tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV, max_iter=50, outputs=None, out=None):
     """Host build of optimize::graph_optimizer::optimize (csrc/pose_graph.hpp, DESIGN.md section 5, D22; no GPU needed): the arguments and the result
     of matcher.pose_graph_optimize."""
-    def call(a):
-        r = lib().plp_model_pose_graph_optimize_host(C.byref(a))
-        if r != a.G:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out)
+    return _pose_graph_host(model_call("plp_model_pose_graph_optimize_host", "G", neg_status=True), tables, problems, edge_cap, env_cap, max_iter, outputs, out)
 
 
 def model_pose_graph_edges(tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, out=None):
     """Host build of D22's vertices and edge list alone (:85-298; no GPU needed): dict(status, num_edges, edges (G, edge_cap, 3), sim3_cw (G, F, 8))"""
-    def call(a):
-        r = lib().plp_model_pose_graph_edges_host(C.byref(a))
-        if r != a.G:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _pose_graph_host(call, tables, problems, edge_cap, 1, 0, ("num_edges", "edges", "sim3_cw"), out)
+    return _pose_graph_host(model_call("plp_model_pose_graph_edges_host", "G", neg_status=True), tables, problems, edge_cap, 1, 0,
+                            ("num_edges", "edges", "sim3_cw"), out)
 
 
 def model_sim3_log(sim3):
@@ -1388,7 +999,7 @@ def model_sim3_log(sim3):
     single = a.ndim == 1
     a = a.reshape(-1, 8)
     o = np.zeros((len(a), 7))
-    if lib().plp_model_sim3_log_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+    if lib().plp_model_sim3_log_host(host_ptr(a), len(a), host_ptr(o)) != len(a):
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_sim3_log_host")
     return o[0] if single else o
 
@@ -1397,7 +1008,7 @@ def model_pose_log(x):
     """Host build of D22's log (no GPU needed): NaN outside 1e-300 <= x <= 1e300"""
     a = np.ascontiguousarray(x, np.float64).reshape(-1)
     o = np.zeros_like(a)
-    if lib().plp_model_pose_log_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+    if lib().plp_model_pose_log_host(host_ptr(a), len(a), host_ptr(o)) != len(a):
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_log_host")
     return o
 
@@ -1406,7 +1017,7 @@ def model_pose_acos(x):
     """Host build of D22's acos (no GPU needed): NaN outside -1 <= x <= 1"""
     a = np.ascontiguousarray(x, np.float64).reshape(-1)
     o = np.zeros_like(a)
-    if lib().plp_model_pose_acos_host(a.ctypes.data if a.size else None, len(a), o.ctypes.data if o.size else None) != len(a):
+    if lib().plp_model_pose_acos_host(host_ptr(a), len(a), host_ptr(o)) != len(a):
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_pose_acos_host")
     return o
 
@@ -1423,8 +1034,7 @@ def model_block_chol7(H, first, b, lam):
     fi = np.ascontiguousarray(first, np.int32).reshape(-1)
     env = pose_graph_envelope(H, fi); bb = np.ascontiguousarray(b, np.float64).reshape(-1)
     x = np.zeros(7 * len(fi))
-    P = lambda v: v.ctypes.data if v.size else None
-    r = lib().plp_model_block_chol7_host(len(fi), P(fi), P(env), P(bb), float(lam), P(x))
+    r = lib().plp_model_block_chol7_host(len(fi), host_ptr(fi), host_ptr(env), host_ptr(bb), float(lam), host_ptr(x))
     if r < 0:
         raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_block_chol7_host")
     return x, bool(r)
@@ -1441,19 +1051,15 @@ def _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erase
     o["status"] = np.zeros(L, np.uint8) if o["status"] is None else o["status"]
     if o["pos_w"].shape != (L, 3) or o["pos_w"].dtype != np.float64 or o["status"].shape != (L,) or o["status"].dtype != np.uint8:
         raise PlpError(PLP_ERR_INVALID_ARG, "out['pos_w'] must be (L, 3) f64, out['status'] (L,) u8")
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-    a = _struct(correct_landmarks_args_c, dict(L=L, F=F), dict(pos_w=Pt(pw), lm_erased=Pt(le), ref_kf=Pt(rk), kf_erased=Pt(ke), sim3_cw=Pt(cw), corrected_wc=Pt(wc),
-                                                              out_pos_w=Pt(o["pos_w"]), out_status=Pt(o["status"])))
+    a = _struct(correct_landmarks_args_c, dict(L=L, F=F), host_ptrs(pos_w=pw, lm_erased=le, ref_kf=rk, kf_erased=ke, sim3_cw=cw, corrected_wc=wc,
+                                                                    out_pos_w=o["pos_w"], out_status=o["status"]))
     call(a)
     return o
 
 
 def model_correct_landmarks(pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased=None, kf_erased=None, out=None):
     """Host build of the landmark half of graph_optimizer::optimize (:331-350; no GPU needed): the arguments and the result of matcher.correct_landmarks"""
-    def call(a):
-        if lib().plp_model_correct_landmarks_host(C.byref(a)) != a.L:
-            raise PlpError(PLP_ERR_INVALID_ARG, lib().plp_last_error().decode())
-    return _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
+    return _correct_landmarks_host(model_call("plp_model_correct_landmarks_host", "L"), pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
 
 
 class graph_optimizer:
@@ -1470,15 +1076,10 @@ class graph_optimizer:
         r = fn(self.tables, [dict(loop_kf=loop_kf, curr_kf=curr_kf, fix_scale=self.fix_scale, non_corrected=non_corrected, pre_corrected=pre_corrected,
                                   loop_connections=loop_connections)], edge_cap=self.edge_cap, env_cap=self.env_cap)
         return {k: v[0] for k, v in r.items()}
-
-
-# plp_local_map_status
-LOCAL_MAP_OK, LOCAL_MAP_NO_KEYFRAMES, LOCAL_MAP_KF_OVERFLOW, LOCAL_MAP_LM_OVERFLOW, LOCAL_MAP_LINE_OVERFLOW = range(5)
-LOCAL_MAP_MAX_KF = 8192             # F: the weights of a frame are an LDS table of that many counters
-LOCAL_MAP_MAX_SLOTS = 8192          # cap, lcap, fcap, flcap
-LOCAL_MAP_MAX_FRAMES = 65535        # B
 LOCAL_MAP_INPUTS = ("kf_erased", "kf_covis", "kf_parent", "kf_children_offsets", "kf_children", "kf_lm", "kf_counts", "kf_lm_lines", "kf_kl_counts",
                     "obs_offsets", "obs_kf", "lm_erased", "lm_erased_lines", "frm_lm", "frm_counts", "frm_lm_lines", "frm_kl_counts")
+
+
 # the outputs of plp_local_map_*: name -> (which of k_cap / m_cap / ml_cap is its row length or None, dtype, optional, line side only)
 LOCAL_MAP_OUTPUTS = dict(status=(None, np.uint8, False, False), num_first=(None, np.int32, False, False), num_kf=(None, np.int32, False, False),
                          local_kf=("k_cap", np.int32, False, False), first_weight=("k_cap", np.int32, True, False),
@@ -1492,8 +1093,8 @@ def _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children,
                     fcap, flcap, outputs, out):
     """the numpy side of plp_local_map_host and plp_model_local_map_host: call(args struct) runs the entry.  The row widths of kf_lm, kf_lm_lines,
     frm_lm and frm_lm_lines are cap, lcap and the two frame strides; fcap / flcap (default: the stride) are the slots read of a frame's row."""
-    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
-    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    i32 = lambda v: array_or_none(v, np.int32)
+    u8 = lambda v: array_or_none(v, np.uint8, -1)
     kp = i32(kf_parent).reshape(-1)
     F = len(kp)
     rows = lambda v, n: None if v is None else (i32(v).reshape(n, -1) if n else np.zeros((0, 0), np.int32))
@@ -1519,27 +1120,18 @@ def _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children,
         if v is not None and v.size != n:
             raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
     caps = dict(k_cap=int(k_cap), m_cap=int(m_cap), ml_cap=int(ml_cap))
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     lines = kll is not None
     a = _struct(local_map_args_c, dict(B=B, F=F, C=len(ch), L=L, LL=LL, T=len(ok), cap=kl.shape[1], lcap=kll.shape[1] if lines else 0,
                                        fcap=fl.shape[1] if fcap is None else int(fcap), flcap=(fll.shape[1] if fll is not None else 0) if flcap is None else int(flcap),
                                        frm_stride=fl.shape[1], frm_stride_lines=fll.shape[1] if fll is not None else 0,
-                                       max_num_local_keyfrms=int(max_num_local_keyfrms), workspace_bytes=int(workspace_bytes), **caps), dict(
-        kf_erased=Pt(ke), kf_covis=Pt(kc), kf_parent=Pt(kp), kf_children_offsets=Pt(co), kf_children=Pt(ch), kf_lm=Pt(kl), kf_counts=Pt(kcn),
-        kf_kl_counts=Pt(kkc), obs_offsets=Pt(oo), obs_kf=Pt(ok), lm_erased=Pt(le), lm_erased_lines=Pt(lel), frm_lm=Pt(fl), frm_counts=Pt(fc),
-        frm_lm_lines=Pt(fll), frm_kl_counts=Pt(fkc)))
+                                       max_num_local_keyfrms=int(max_num_local_keyfrms), workspace_bytes=int(workspace_bytes), **caps), host_ptrs(
+        kf_erased=ke, kf_covis=kc, kf_parent=kp, kf_children_offsets=co, kf_children=ch, kf_lm=kl, kf_counts=kcn, kf_kl_counts=kkc, obs_offsets=oo, obs_kf=ok,
+        lm_erased=le, lm_erased_lines=lel, frm_lm=fl, frm_counts=fc, frm_lm_lines=fll, frm_kl_counts=fkc))
     if lines:      # a table without a slot is still "line tracking is on": the pointer only has to be non-NULL
         a.kf_lm_lines = kll.ctypes.data if kll.size else kp.ctypes.data if kp.size else co.ctypes.data
-    o = {}
-    for k, (cap_name, dt, optional, line_side) in LOCAL_MAP_OUTPUTS.items():   # the caller's arrays are the outputs when given (unwritten slots keep their values)
-        if (line_side and not lines) or (optional and outputs is not None and k not in outputs):
-            continue
-        full = (B,) if cap_name is None else (B, max(caps[cap_name], 0))      # a negative cap is the library's to refuse
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-        setattr(a, "out_" + k, Pt(o[k]))
+    o = out_arrays(((k, (B,) if cap_name is None else (B, max(caps[cap_name], 0)), dt)      # a negative cap is the library's to refuse
+                    for k, (cap_name, dt, optional, line_side) in LOCAL_MAP_OUTPUTS.items() if (lines or not line_side) and wanted(k, optional, outputs)), out)
+    set_outputs(a, o, o, host_ptr)
     call(a)
     return o
 
@@ -1549,13 +1141,9 @@ def model_local_map(kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm
                     frm_kl_counts=None, max_num_local_keyfrms=60, workspace_bytes=0, fcap=None, flcap=None, outputs=None, out=None):
     """Host build of module::local_map_updater for B frames (csrc/local_map.hpp, DESIGN.md section 5, D18; no GPU needed): the arguments and the
     result of matcher.local_map."""
-    def call(a):
-        r = lib().plp_model_local_map_host(C.byref(a))
-        if r != a.B:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased,
-                           kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines, frm_kl_counts,
-                           max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
+    return _local_map_host(model_call("plp_model_local_map_host", "B", neg_status=True), kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm,
+                           obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased, kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL,
+                           frm_counts, frm_lm_lines, frm_kl_counts, max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
 
 
 def kf_landmarks_from_observations(obs_offsets, obs_kf, obs_idx, F, cap):
@@ -1610,35 +1198,26 @@ class local_map_updater:
     def get_nearest_covisibility(self):
         """the key-frame row, or -1 where the reference's member is indeterminate (D18)"""
         return int(self._r["nearest_kf"])
-
-
-# plp_cull_keyframe_decision and plp_cull_landmark_state
-CULL_KF_SKIP_ORIGIN, CULL_KF_SKIP_WINDOW, CULL_KF_KEPT, CULL_KF_REMOVED, CULL_KF_REMOVED_HELD, CULL_KF_ABSENT = range(6)
-CULL_HOLD, CULL_DROP, CULL_ERASE = range(3)
-CULL_MAX_KF = 8192                  # F: the removed set of a problem is an LDS bitmap
-CULL_MAX_SLOTS = 8192               # cap
-CULL_MAX_PROBLEMS = 65535           # G
 CULL_KEYFRAMES_INPUTS = ("kf_lm", "kf_counts", "undist", "x_right", "depths", "depth_thr", "kf_id", "kf_erased", "kf_cannot_erase", "obs_offsets",
                          "obs_kf", "obs_idx", "lm_erased", "lm_num_obs", "cur_kf", "covis_offsets", "covis")
+
+
 # the outputs of plp_cull_keyframes_*: name -> (shape from (G, Cv, F, L), dtype, optional)
 CULL_KEYFRAMES_OUTPUTS = dict(num_removed=(lambda G, Cv, F, L: (G,), np.int32, False), decision=(lambda G, Cv, F, L: (Cv,), np.uint8, False),
                               num_valid=(lambda G, Cv, F, L: (Cv,), np.int32, False), num_redundant=(lambda G, Cv, F, L: (Cv,), np.int32, False),
                               kf_removed=(lambda G, Cv, F, L: (G, F), np.uint8, True), lm_erased=(lambda G, Cv, F, L: (G, L), np.uint8, True))
 CULL_LANDMARKS_INPUTS = ("fresh_offsets", "fresh", "lm_erased", "num_observed", "num_observable", "first_kf_id", "num_obs", "owning_plane",
                          "cur_kf_id", "num_obs_thr")
+
+
 # the outputs of plp_cull_landmarks_*: name -> (per entry (N) or per list (R), dtype)
 CULL_LANDMARKS_OUTPUTS = dict(state=("N", np.uint8), num_removed=("R", np.int32), num_fresh=("R", np.int32), fresh=("N", np.int32))
 
 
 def _cull_out(spec_items, out, a):
     """the output arrays of a culling entry: the caller's where given (unwritten slots keep their values), zeros otherwise"""
-    o = {}
-    for k, full, dt in spec_items:
-        v = None if out is None else out.get(k)
-        if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == full and v.flags.c_contiguous):
-            raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {full}")
-        o[k] = v if v is not None else np.zeros(full, dt)
-        setattr(a, "out_" + k, o[k].ctypes.data if o[k].size else None)
+    o = out_arrays(spec_items, out)
+    set_outputs(a, o, o, host_ptr)
     return o
 
 
@@ -1646,9 +1225,9 @@ def _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_id
                          x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out):
     """the numpy side of plp_cull_keyframes_host and plp_model_cull_keyframes_host: call(args struct) runs the entry.  The row widths of kf_lm and
     of undist (with x_right and depths) are cap and kp_stride."""
-    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
-    u32 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint32).reshape(-1)
-    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    i32 = lambda v: array_or_none(v, np.int32)
+    u32 = lambda v: array_or_none(v, np.uint32, -1)
+    u8 = lambda v: array_or_none(v, np.uint8, -1)
     kid = u32(kf_id)
     F = len(kid)
     kl = i32(kf_lm).reshape(F, -1) if F else np.zeros((0, 0), np.int32)
@@ -1668,14 +1247,11 @@ def _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_id
     for name, v, n in (("kf_counts", kcn, F), ("kf_erased", ke, F), ("kf_cannot_erase", kce, F), ("lm_erased", le, L), ("lm_num_obs", ln, L)):
         if v is not None and v.size != n:
             raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(cull_keyframes_args_c, dict(F=F, L=L, T=len(ok), cap=cap, kp_stride=stride, G=G, Cv=Cv, origin_id=int(origin_id),
                                             is_monocular=int(bool(is_monocular))),
-                dict(kf_lm=Pt(kl), kf_counts=Pt(kcn), undist=Pt(un), x_right=Pt(xr), depths=Pt(dp), depth_thr=Pt(dt_), kf_id=Pt(kid), kf_erased=Pt(ke),
-                     kf_cannot_erase=Pt(kce), obs_offsets=Pt(oo), obs_kf=Pt(ok), obs_idx=Pt(oi), lm_erased=Pt(le), lm_num_obs=Pt(ln), cur_kf=Pt(ck),
-                     covis_offsets=Pt(co), covis=Pt(cv)))
-    o = _cull_out([(k, shape(G, Cv, F, L), dt) for k, (shape, dt, optional) in CULL_KEYFRAMES_OUTPUTS.items()
-                   if not (optional and outputs is not None and k not in outputs)], out, a)
+                host_ptrs(kf_lm=kl, kf_counts=kcn, undist=un, x_right=xr, depths=dp, depth_thr=dt_, kf_id=kid, kf_erased=ke, kf_cannot_erase=kce,
+                          obs_offsets=oo, obs_kf=ok, obs_idx=oi, lm_erased=le, lm_num_obs=ln, cur_kf=ck, covis_offsets=co, covis=cv))
+    o = _cull_out(((k, shape(G, Cv, F, L), dt) for k, (shape, dt, optional) in CULL_KEYFRAMES_OUTPUTS.items() if wanted(k, optional, outputs)), out, a)
     call(a)
     return o
 
@@ -1685,12 +1261,9 @@ def model_cull_keyframes(kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur
                          lm_num_obs=None, outputs=None, out=None):
     """Host build of local_map_cleaner::remove_redundant_keyframes for G problems (csrc/map_cull.hpp, DESIGN.md section 5, D20; no GPU needed): the
     arguments and the result of matcher.cull_keyframes."""
-    def call(a):
-        r = lib().plp_model_cull_keyframes_host(C.byref(a))
-        if r != a.G:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id, is_monocular,
-                                kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out)
+    return _cull_keyframes_host(model_call("plp_model_cull_keyframes_host", "G", neg_status=True), kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf,
+                                covis_offsets, covis, origin_id, is_monocular, kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased,
+                                lm_num_obs, outputs, out)
 
 
 def _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased, owning_plane,
@@ -1698,17 +1271,16 @@ def _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observabl
     """the numpy side of plp_cull_landmarks_host and plp_model_cull_landmarks_host"""
     i32 = lambda v: np.ascontiguousarray(v, np.int32).reshape(-1)
     u32 = lambda v: np.ascontiguousarray(v, np.uint32).reshape(-1)
-    u8 = lambda v: None if v is None else np.ascontiguousarray(v, np.uint8).reshape(-1)
+    u8 = lambda v: array_or_none(v, np.uint8, -1)
     fo, fr = i32(fresh_offsets), i32(fresh)
     nd, nb, fk, no, ck, th = u32(num_observed), u32(num_observable), u32(first_kf_id), u32(num_obs), u32(cur_kf_id), u32(num_obs_thr)
     L, R, N = len(nd), len(ck), len(fr)
     le, pl = u8(lm_erased), u8(owning_plane)
     if len(fo) != R + 1 or len(th) != R or any(len(v) != L for v in (nb, fk, no)) or any(v is not None and len(v) != L for v in (le, pl)):
         raise PlpError(PLP_ERR_INVALID_ARG, "fresh_offsets must have R + 1 entries, num_obs_thr R, every landmark table L")
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(cull_landmarks_args_c, dict(R=R, N=N, L=L),
-                dict(fresh_offsets=Pt(fo), fresh=Pt(fr), lm_erased=Pt(le), num_observed=Pt(nd), num_observable=Pt(nb), first_kf_id=Pt(fk), num_obs=Pt(no),
-                     owning_plane=Pt(pl), cur_kf_id=Pt(ck), num_obs_thr=Pt(th)))
+                host_ptrs(fresh_offsets=fo, fresh=fr, lm_erased=le, num_observed=nd, num_observable=nb, first_kf_id=fk, num_obs=no, owning_plane=pl,
+                          cur_kf_id=ck, num_obs_thr=th))
     o = _cull_out([(k, (N,) if per == "N" else (R,), dt) for k, (per, dt) in CULL_LANDMARKS_OUTPUTS.items()], out, a)
     call(a)
     return o
@@ -1718,12 +1290,8 @@ def model_cull_landmarks(fresh_offsets, fresh, num_observed, num_observable, fir
                          owning_plane=None, out=None):
     """Host build of local_map_cleaner::remove_redundant_landmarks[_line] for R fresh lists (csrc/map_cull.hpp, D20; no GPU needed): the arguments
     and the result of matcher.cull_landmarks."""
-    def call(a):
-        r = lib().plp_model_cull_landmarks_host(C.byref(a))
-        if r != a.R:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased,
-                                owning_plane, out)
+    return _cull_landmarks_host(model_call("plp_model_cull_landmarks_host", "R", neg_status=True), fresh_offsets, fresh, num_observed, num_observable,
+                                first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased, owning_plane, out)
 
 
 class local_map_cleaner:
@@ -1775,13 +1343,6 @@ class local_map_cleaner:
                cv, origin_id=self.origin_keyfrm_id, is_monocular=self.is_monocular, **opt)
         self.last = r
         return int(r["num_removed"][0])
-
-
-# plp_covisibility_status
-COVIS_OK, COVIS_NO_SHARED, COVIS_ROW_ABSENT, COVIS_DUPLICATE, COVIS_OVERFLOW = range(5)
-COVIS_MAX_KF = 8192                 # F, G, conn_cap, covis_cap: the weights of an owner are an LDS table
-COVIS_MAX_SLOTS = 8192              # cap
-COVIS_WEIGHT_THR = 15               # weight_thr_
 COVISIBILITY_INPUTS = ("kf_lm", "kf_counts", "obs_offsets", "obs_kf", "lm_erased", "kf_id", "owners")
 # the state tables of plp_covisibility_*: name -> (row length from (conn_cap, covis_cap) or None, dtype, what an empty row holds)
 COVISIBILITY_STATE = dict(kf_conn=(lambda cc, vc: cc, np.int32, -1), kf_conn_w=(lambda cc, vc: cc, np.int32, 0), kf_n_conn=(None, np.int32, 0),
@@ -1810,12 +1371,12 @@ def _covisibility_state_ptrs(state, names, F):
     cc, vc = state["kf_conn"].shape[1], state["kf_covis"].shape[1]
     if state["kf_conn_w"].shape[1] != cc or state["kf_covis_w"].shape[1] != vc:
         raise PlpError(PLP_ERR_INVALID_ARG, "kf_conn_w and kf_covis_w must have the row lengths of kf_conn and kf_covis")
-    return cc, vc, {k: (state[k].ctypes.data if state[k].size else None) for k in names}
+    return cc, vc, {k: host_ptr(state[k]) for k in names}
 
 
 def _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out):
     """the numpy side of plp_covisibility_update_host and plp_model_covisibility_update_host: call(args struct) runs the entry"""
-    i32 = lambda v: None if v is None else np.ascontiguousarray(v, np.int32)
+    i32 = lambda v: array_or_none(v, np.int32)
     kid = np.ascontiguousarray(kf_id, np.uint32).reshape(-1)
     F = len(kid)
     kl = i32(kf_lm).reshape(F, -1) if F else np.zeros((0, 0), np.int32)
@@ -1829,11 +1390,9 @@ def _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, ow
         if v is not None and v.size != n:
             raise PlpError(PLP_ERR_INVALID_ARG, f"{name} must have {n} entries")
     cc, vc, sp = _covisibility_state_ptrs(state, COVISIBILITY_STATE, F)
-    Pt = lambda v: None if v is None or v.size == 0 else v.ctypes.data
     a = _struct(covisibility_update_args_c, dict(F=F, L=L, T=len(ok), cap=kl.shape[1], conn_cap=cc, covis_cap=vc, G=G),
-                dict(sp, kf_lm=Pt(kl), kf_counts=Pt(kcn), obs_offsets=Pt(oo), obs_kf=Pt(ok), lm_erased=Pt(le), kf_id=Pt(kid), owners=Pt(ow)))
-    o = _cull_out([(k, (G,) if per == "G" else (F,), dt) for k, (per, dt, optional) in COVISIBILITY_OUTPUTS.items()
-                   if not (optional and outputs is not None and k not in outputs)], out, a)
+                dict(sp, **host_ptrs(kf_lm=kl, kf_counts=kcn, obs_offsets=oo, obs_kf=ok, lm_erased=le, kf_id=kid, owners=ow)))
+    o = _cull_out(((k, (G,) if per == "G" else (F,), dt) for k, (per, dt, optional) in COVISIBILITY_OUTPUTS.items() if wanted(k, optional, outputs)), out, a)
     call(a)
     return o
 
@@ -1843,7 +1402,7 @@ def _covisibility_erase_host(call, state, erased, out):
     er = np.ascontiguousarray(erased, np.uint8).reshape(-1)
     F = len(er)
     cc, vc, sp = _covisibility_state_ptrs(state, COVISIBILITY_ERASE_STATE, F)
-    a = _struct(covisibility_erase_args_c, dict(F=F, conn_cap=cc, covis_cap=vc), dict(sp, erased=er.ctypes.data if F else None))
+    a = _struct(covisibility_erase_args_c, dict(F=F, conn_cap=cc, covis_cap=vc), dict(sp, erased=host_ptr(er)))
     o = _cull_out([("status", (F,), np.uint8), ("touched", (F,), np.uint8)], out, a)
     call(a)
     return o
@@ -1852,21 +1411,14 @@ def _covisibility_erase_host(call, state, erased, out):
 def model_covisibility_update(kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts=None, lm_erased=None, outputs=None, out=None):
     """Host build of graph_node::update_connections for a list of owners (csrc/covisibility.hpp, DESIGN.md section 5, D21; no GPU needed): the
     arguments and the result of matcher.covisibility_update."""
-    def call(a):
-        r = lib().plp_model_covisibility_update_host(C.byref(a))
-        if r != a.G:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out)
+    return _covisibility_update_host(model_call("plp_model_covisibility_update_host", "G", neg_status=True), kf_lm, obs_offsets, obs_kf, kf_id, state, owners,
+                                     kf_counts, lm_erased, outputs, out)
 
 
 def model_covisibility_erase(state, erased, out=None):
     """Host build of graph_node::erase_all_connections for a set of key frames (csrc/covisibility.hpp, D21; no GPU needed): the arguments and the
     result of matcher.covisibility_erase."""
-    def call(a):
-        r = lib().plp_model_covisibility_erase_host(C.byref(a))
-        if r != a.F:
-            raise PlpError(-r, lib().plp_last_error().decode())
-    return _covisibility_erase_host(call, state, erased, out)
+    return _covisibility_erase_host(model_call("plp_model_covisibility_erase_host", "F", neg_status=True), state, erased, out)
 
 
 class covisibility_graph:
@@ -1997,7 +1549,7 @@ class orb_extractor:
                  mask_rects=(), device=0):
         r = np.ascontiguousarray(np.asarray(mask_rects, np.float32).reshape(-1, 4))
         p = orb_params_c(max_num_keypts, scale_factor, num_levels, ini_fast_thr, min_fast_thr,
-                         r.ctypes.data if len(r) else None, len(r))
+                         host_ptr(r), len(r))
         h = C.c_void_p()
         st = lib().plp_orb_create(C.byref(p), device, C.byref(h))
         if st == PLP_ERR_INVALID_ARG:
@@ -2126,14 +1678,6 @@ class orb_extractor:
 # ------------------------------------------------------------------------------------------------
 # Line front-end (feature::LineFeatureTracker of the reference)
 # ------------------------------------------------------------------------------------------------
-KL_DTYPE = np.dtype([("angle", "<f4"), ("class_id", "<i4"), ("octave", "<i4"), ("pt_x", "<f4"), ("pt_y", "<f4"), ("response", "<f4"),
-                     ("size", "<f4"), ("startPointX", "<f4"), ("startPointY", "<f4"), ("endPointX", "<f4"), ("endPointY", "<f4"),
-                     ("sPointInOctaveX", "<f4"), ("sPointInOctaveY", "<f4"), ("ePointInOctaveX", "<f4"), ("ePointInOctaveY", "<f4"),
-                     ("lineLength", "<f4"), ("numOfPixels", "<i4")])
-assert KL_DTYPE.itemsize == 68
-LINE_CAP = 2048
-
-
 class LineFeatureTracker:
     """Mirror of feature::LineFeatureTracker (src/PLPSLAM/feature/line_extractor.h:61-104) over the C ABI."""
 
@@ -2231,21 +1775,6 @@ class LineFeatureTracker:
 # ------------------------------------------------------------------------------------------------
 # Hamming matchers, array form (match::projection / match::robust of the reference)
 # ------------------------------------------------------------------------------------------------
-class camera_c(C.Structure):
-    """plp_camera: camera::perspective intrinsics, distortion, focal_x_baseline"""
-    _fields_ = [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "focal_x_baseline")]
-
-
-CAMERA_PERSPECTIVE, CAMERA_FISHEYE, CAMERA_EQUIRECTANGULAR = 0, 1, 2     # plp_camera_model_type (camera::model_type_t)
-CAMERA_MODEL_NAMES = {"perspective": CAMERA_PERSPECTIVE, "fisheye": CAMERA_FISHEYE, "equirectangular": CAMERA_EQUIRECTANGULAR}   # camera/base.cc:81-98
-
-
-class camera_model_c(C.Structure):
-    """plp_camera_model: any of the reference's three camera models"""
-    _fields_ = [("model", C.c_int32), ("cols", C.c_int32), ("rows", C.c_int32)] + \
-               [(k, C.c_double) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "k4", "focal_x_baseline")]
-
-
 class camera_model(camera_model_c):
     """Mirror of the camera the reference's config builds from the yaml's Camera.* keys (config.cc:62-72 switches on Camera.model):
     camera::perspective (perspective.cc:59-75), camera::fisheye (fisheye.cc:59-75) or camera::equirectangular (equirectangular.cc:45-50).
@@ -2321,14 +1850,6 @@ class camera_model(camera_model_c):
         return match_grid_c(float(b[0]), float(b[2]), float(inv_w), float(inv_h), self.NUM_GRID_COLS, self.NUM_GRID_ROWS)
 
 
-class observe_args_c(C.Structure):
-    """plp_observe_args"""
-    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("ray_cos_thr", C.c_float), ("log_scale_factor", C.c_float),
-                ("num_levels", C.c_int32), ("B", C.c_int32), ("m_cap", C.c_int32),
-                ("pose", _VP), ("counts", _VP), ("pos_w", _VP), ("obs_mean_normal", _VP), ("min_valid_dist", _VP), ("max_valid_dist", _VP), ("skip", _VP),
-                ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_level", _VP), ("out_valid", _VP), ("out_num_valid", _VP)]
-
-
 def frame_pose(rot_cw, trans_cw):
     """One problem's pose row of plp_observe_args (15 doubles): rot_cw_ row-major, trans_cw_ and cam_center_ = -rot_cw_^T trans_cw_ formed as
     frame::update_pose_params does (frame.cc:745-751; each coefficient a left-to-right sum of the negated column times trans_cw_)."""
@@ -2338,69 +1859,27 @@ def frame_pose(rot_cw, trans_cw):
     return np.array(R[0] + R[1] + R[2] + t + cc, np.float64)
 
 
-def _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, ptrs):
-    a = observe_args_c()
+def _camera_args(cls, camera, img_bounds, B, m_cap, fields, ptrs):
+    """an args struct that begins with the camera and the image bounds (the camera's own unless given)"""
+    a = _struct(cls, dict(fields, B=int(B), m_cap=int(m_cap)), ptrs)
     a.camera = camera_model_c.from_buffer_copy(camera)
-    b = camera.img_bounds if img_bounds is None else img_bounds
-    a.img_bounds[:] = [float(np.float32(v)) for v in b]
-    a.ray_cos_thr, a.log_scale_factor, a.num_levels = float(ray_cos_thr), float(np.float32(log_scale_factor)), int(num_levels)
-    a.B, a.m_cap = int(B), int(m_cap)
-    for k, v in ptrs.items():
-        setattr(a, k, v)
+    a.img_bounds[:] = [float(np.float32(v)) for v in (camera.img_bounds if img_bounds is None else img_bounds)]
     return a
 
 
-SETUP_MONOCULAR, SETUP_STEREO, SETUP_RGBD = 0, 1, 2     # camera::setup_type_t (camera/base.h:41-46)
-
-
-class last_frame_args_c(C.Structure):
-    """plp_last_frame_args"""
-    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
-                ("B", C.c_int32), ("m_cap", C.c_int32),
-                ("counts", _VP), ("pose_curr", _VP), ("pose_last", _VP), ("pos_w", _VP), ("skip", _VP), ("keypts", _VP), ("keylines", _VP),
-                ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_x_right2", _VP), ("out_level", _VP), ("out_angle", _VP),
-                ("out_valid", _VP), ("out_direction", _VP), ("out_num_valid", _VP)]
+def _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, ptrs):
+    return _camera_args(observe_args_c, camera, img_bounds, B, m_cap, dict(
+        ray_cos_thr=float(ray_cos_thr), log_scale_factor=float(np.float32(log_scale_factor)), num_levels=int(num_levels)), ptrs)
 
 
 def _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, ptrs):
-    a = last_frame_args_c()
-    a.camera = camera_model_c.from_buffer_copy(camera)
-    b = camera.img_bounds if img_bounds is None else img_bounds
-    a.img_bounds[:] = [float(np.float32(v)) for v in b]
-    a.setup_type, a.true_baseline = int(setup_type), float(true_baseline)
-    a.B, a.m_cap = int(B), int(m_cap)
-    for k, v in ptrs.items():
-        setattr(a, k, v)
-    return a
-
-
-class project_args_c(C.Structure):
-    """plp_project_args"""
-    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("log_scale_factor", C.c_float), ("num_levels", C.c_int32),
-                ("B", C.c_int32), ("m_cap", C.c_int32), ("shared_landmarks", C.c_int32), ("dist_mode", C.c_int32), ("ray_test", C.c_int32),
-                ("line_dist_mode", C.c_int32),
-                ("pose", _VP), ("counts", _VP), ("pos_w", _VP), ("obs_mean_normal", _VP), ("min_valid_dist", _VP), ("max_valid_dist", _VP), ("skip", _VP),
-                ("out_reproj_d", _VP), ("out_reproj2_d", _VP), ("out_reproj", _VP), ("out_reproj2", _VP), ("out_x_right", _VP), ("out_x_right2", _VP),
-                ("out_level", _VP), ("out_valid", _VP), ("out_status", _VP), ("out_num_valid", _VP)]
-
-
-PROJECT_DIST_CENTER, PROJECT_DIST_CAMERA = 0, 1           # plp_project_dist_mode
-PROJECT_LINE_ENDPOINTS, PROJECT_LINE_MIDPOINT = 0, 1      # plp_project_line_dist_mode
-# plp_project_status: where the reference leaves an iteration of the fuse / Sim3 / relocalisation loops
-PROJECT_KEPT, PROJECT_SKIPPED, PROJECT_NOT_IN_IMAGE, PROJECT_MIDPOINT_OUT, PROJECT_DISTANCE, PROJECT_RAY = range(6)
+    return _camera_args(last_frame_args_c, camera, img_bounds, B, m_cap, dict(setup_type=int(setup_type), true_baseline=float(true_baseline)), ptrs)
 
 
 def _project_args(camera, img_bounds, log_scale_factor, num_levels, B, m_cap, shared_landmarks, dist_mode, ray_test, line_dist_mode, ptrs):
-    a = project_args_c()
-    a.camera = camera_model_c.from_buffer_copy(camera)
-    b = camera.img_bounds if img_bounds is None else img_bounds
-    a.img_bounds[:] = [float(np.float32(v)) for v in b]
-    a.log_scale_factor, a.num_levels = float(np.float32(log_scale_factor)), int(num_levels)
-    a.B, a.m_cap = int(B), int(m_cap)
-    a.shared_landmarks, a.dist_mode, a.ray_test, a.line_dist_mode = int(bool(shared_landmarks)), int(dist_mode), int(bool(ray_test)), int(line_dist_mode)
-    for k, v in ptrs.items():
-        setattr(a, k, v)
-    return a
+    return _camera_args(project_args_c, camera, img_bounds, B, m_cap, dict(
+        log_scale_factor=float(np.float32(log_scale_factor)), num_levels=int(num_levels), shared_landmarks=int(bool(shared_landmarks)),
+        dist_mode=int(dist_mode), ray_test=int(bool(ray_test)), line_dist_mode=int(line_dist_mode)), ptrs)
 
 
 def _mat3(m):
@@ -2452,263 +1931,6 @@ def mutual_poses(s_12, rot_12, trans_12, rot_1w, trans_1w, rot_2w, trans_2w):
     return np.array([flat(s_rot_21w) + trans_21w + [0.0] * 3, flat(s_rot_12w) + trans_12w + [0.0] * 3], np.float64)
 
 
-class stereo_keylines_args_c(C.Structure):
-    """plp_stereo_keylines_args"""
-    _fields_ = [("B", C.c_int32), ("cap_left", C.c_int32), ("cap_right", C.c_int32),
-                ("keylines_left", _VP), ("counts_left", _VP), ("keylines_right", _VP), ("counts_right", _VP), ("train_idx", _VP), ("dist", _VP),
-                ("out_good_match", _VP), ("out_kl_depths", _VP), ("out_kl_x_right", _VP)]
-
-
-class keylines_3d_args_c(C.Structure):
-    """plp_keylines_3d_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("B", C.c_int32), ("cap", C.c_int32), ("cap_right", C.c_int32),
-                ("counts", _VP), ("pose", _VP), ("keylines", _VP), ("kl_depths", _VP), ("good_match", _VP), ("keylines_right", _VP),
-                ("counts_right", _VP), ("out_pos_w", _VP), ("out_valid", _VP)]
-
-
-class median_depth_args_c(C.Structure):
-    """plp_median_depth_args"""
-    _fields_ = [("F", C.c_int32), ("m_cap", C.c_int32), ("abs_flag", C.c_int32),
-                ("pose", _VP), ("pos_w", _VP), ("valid", _VP), ("counts", _VP), ("out_median", _VP), ("out_count", _VP)]
-
-
-class keyline_pairs_args_c(C.Structure):
-    """plp_keyline_pairs_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
-                ("scale_factors", _VP), ("level_sigma_sq", _VP), ("num_levels", C.c_int32), ("scale_factor", C.c_float),
-                ("rays_parallax_deg_thr", C.c_float), ("dist_thr", C.c_float), ("endpoint_thr", C.c_float), ("angle_thr", C.c_float),
-                ("skip_occupied", C.c_int32), ("F", C.c_int32), ("cap", C.c_int32), ("kp_cap", C.c_int32),
-                ("keylines", _VP), ("counts", _VP), ("line_functions", _VP), ("kl_x_right", _VP), ("kp_depths", _VP), ("kp_counts", _VP),
-                ("pose", _VP), ("median_depth", _VP), ("lines_3d", _VP), ("occupied", _VP),
-                ("P", C.c_int32), ("G", C.c_int32), ("pairs", _VP), ("group_offsets", _VP), ("train_idx", _VP), ("dist", _VP),
-                ("out_match", _VP), ("out_pos_w", _VP), ("out_status", _VP), ("out_occupied_cur", _VP)]
-
-
-# plp_keyline_pair_status: where the reference leaves an iteration of triangulate_line_with_two_keyframes
-(KLP_CREATED, KLP_GATE_DISTANCE, KLP_GATE_ENDPOINTS, KLP_GATE_ANGLE, KLP_OCCUPIED_CUR, KLP_OCCUPIED_NGH, KLP_NO_PARALLAX, KLP_TOO_CLOSE,
- KLP_TOO_LONG, KLP_DEPTH, KLP_REPROJ_MID, KLP_REPROJ_END, KLP_SCALE, KLP_NON_FINITE, KLP_KP_DEPTH_RANGE) = range(15)
-KLP_MAPPING = dict(dist_thr=50.0, endpoint_thr=400.0, angle_thr=20.0, skip_occupied=1)       # mapping_module.cc:506, :529, :564
-KLP_INITIALIZER = dict(dist_thr=30.0, endpoint_thr=200.0, angle_thr=5.0, skip_occupied=0)    # module/initializer.cc:585-667
-
-
-class pair_geometry_args_c(C.Structure):
-    """plp_keyframe_pair_geometry_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double), ("F", C.c_int32), ("P", C.c_int32),
-                ("pose", _VP), ("median_depth", _VP), ("pairs", _VP), ("out_skip", _VP), ("out_epipolar", _VP), ("out_baseline", _VP)]
-
-
-class keypoint_pairs_args_c(C.Structure):
-    """plp_keypoint_pairs_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("true_baseline", C.c_double),
-                ("scale_factors", _VP), ("level_sigma_sq", _VP), ("num_levels", C.c_int32), ("scale_factor", C.c_float),
-                ("rays_parallax_deg_thr", C.c_float), ("F", C.c_int32), ("cap", C.c_int32), ("m_cap", C.c_int32), ("P", C.c_int32),
-                ("keypts", _VP), ("bearings", _VP), ("x_right", _VP), ("depths", _VP), ("counts", _VP), ("pose", _VP), ("pairs", _VP),
-                ("match_q", _VP), ("q_feature", _VP), ("pair_skip", _VP),
-                ("out_idx_1", _VP), ("out_pos_w", _VP), ("out_status", _VP), ("occupied_1_io", _VP), ("occupied_2_io", _VP)]
-
-
-# plp_keypoint_pair_status: where the reference leaves an iteration of triangulate_with_two_keyframes
-(KPP_CREATED, KPP_PAIR_SKIPPED, KPP_NO_MATCH, KPP_NO_PARALLAX, KPP_DEPTH, KPP_REPROJ_1, KPP_REPROJ_2, KPP_SCALE, KPP_NON_FINITE,
- KPP_INDEX_RANGE) = range(10)
-
-
-class landmark_geometry_args_c(C.Structure):
-    """plp_landmark_geometry_args"""
-    _fields_ = [("F", C.c_int32), ("cap", C.c_int32), ("pose", _VP), ("counts", _VP), ("keypts", _VP), ("keylines", _VP),
-                ("scale_factors", _VP), ("num_levels", C.c_int32), ("scale_factors_lsd", _VP), ("num_levels_lsd", C.c_int32), ("L", C.c_int32),
-                ("pos_w", _VP), ("ref_kf", _VP), ("skip", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("obs_idx", _VP),
-                ("out_mean_normal", _VP), ("out_min_valid_dist", _VP), ("out_max_valid_dist", _VP), ("out_status", _VP)]
-
-
-# plp_landmark_geometry_status: where landmark::update_normal_and_depth / Line::update_information leave a landmark
-LG_UPDATED, LG_SKIPPED, LG_NO_OBSERVATIONS, LG_REF_NOT_OBSERVED, LG_INDEX_RANGE, LG_OCTAVE_RANGE = range(6)
-
-
-class sim3_ransac_args_c(C.Structure):
-    """plp_sim3_ransac_args"""
-    _fields_ = [("camera", camera_model_c), ("P", C.c_int32), ("n_cap", C.c_int32), ("fix_scale", C.c_int32), ("min_num_inliers", C.c_int32),
-                ("iters", C.c_int32), ("seed", C.c_uint64), ("level_sigma_sq_1", _VP), ("level_sigma_sq_2", _VP), ("num_levels", C.c_int32),
-                ("counts", _VP), ("valid", _VP), ("pos_w_1", _VP), ("pos_w_2", _VP), ("octave_1", _VP), ("octave_2", _VP), ("pose_1", _VP), ("pose_2", _VP),
-                ("samples", _VP), ("out_status", _VP), ("out_num_common", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
-                ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
-
-
-class plane_ransac_args_c(C.Structure):
-    """plp_plane_ransac_args"""
-    _fields_ = [("mode", C.c_int32), ("P", C.c_int32), ("n_cap", C.c_int32), ("points_per_ransac", C.c_int32), ("min_points_before_ransac", C.c_int32),
-                ("iters", C.c_int32), ("inliers_ratio_thr", C.c_double), ("seed", C.c_uint64), ("m_cap", C.c_int32), ("counts", _VP), ("pos_w", _VP),
-                ("flags", _VP), ("dist_thresh", _VP), ("error_thresh", _VP), ("best_error_in", _VP), ("equation_in", _VP), ("samples", _VP),
-                ("out_status", _VP), ("out_flags", _VP), ("out_equation", _VP), ("out_best_error", _VP), ("out_best_iter", _VP), ("out_last_iter", _VP),
-                ("out_num_inliers", _VP), ("out_inliers", _VP), ("out_hyp_residual", _VP), ("out_hyp_inliers", _VP), ("out_hyp_error", _VP)]
-
-
-class plane_refine_args_c(C.Structure):
-    """plp_plane_refine_args"""
-    _fields_ = [("M", C.c_int32), ("NP", C.c_int32), ("pos_w", _VP), ("lm_plane", _VP), ("flags", _VP), ("equation", _VP), ("active", _VP),
-                ("dist_thresh", _VP), ("out_changed", _VP)]
-
-
-class pnp_ransac_args_c(C.Structure):
-    """plp_pnp_ransac_args"""
-    _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("min_num_inliers", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32),
-                ("seed", C.c_uint64), ("scale_factors", _VP), ("num_levels", C.c_int32), ("counts", _VP), ("valid", _VP), ("bearing", _VP), ("pos_w", _VP),
-                ("octave", _VP), ("samples", _VP), ("out_status", _VP), ("out_num_matches", _VP), ("out_rot_cw", _VP), ("out_trans_cw", _VP),
-                ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
-
-
-class pose_optimize_args_c(C.Structure):
-    """plp_pose_optimize_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("B", C.c_int32), ("n_cap", C.c_int32), ("l_cap", C.c_int32),
-                ("num_trials", C.c_int32), ("num_each_iter", C.c_int32), ("pose_stride", C.c_int32), ("inv_level_sigma_sq", _VP), ("num_levels", C.c_int32),
-                ("inv_level_sigma_sq_lsd", _VP), ("num_levels_lsd", C.c_int32), ("pose_in", _VP), ("counts", _VP), ("line_counts", _VP), ("valid", _VP),
-                ("undist", _VP), ("x_right", _VP), ("pos_w", _VP), ("line_valid", _VP), ("keylines", _VP), ("pos_w_lines", _VP), ("out_status", _VP),
-                ("out_pose", _VP), ("out_num_init_obs", _VP), ("out_num_valid", _VP), ("out_outlier", _VP), ("out_outlier_lines", _VP),
-                ("out_trial_info", _VP), ("out_trial_chi2", _VP)]
-
-
-class transform_optimize_args_c(C.Structure):
-    """plp_transform_optimize_args"""
-    _fields_ = [("camera", camera_model_c), ("fix_scale", C.c_int32), ("num_iter", C.c_int32), ("chi_sq", C.c_float), ("P", C.c_int32), ("n_cap", C.c_int32),
-                ("inv_level_sigma_sq_1", _VP), ("inv_level_sigma_sq_2", _VP), ("num_levels", C.c_int32), ("counts", _VP), ("valid", _VP), ("pos_w_1", _VP),
-                ("pos_w_2", _VP), ("undist_1", _VP), ("undist_2", _VP), ("pose_1", _VP), ("pose_2", _VP), ("rot_12", _VP), ("trans_12", _VP), ("scale_12", _VP),
-                ("out_status", _VP), ("out_num_valid", _VP), ("out_num_inliers", _VP), ("out_rot_12", _VP), ("out_trans_12", _VP), ("out_scale_12", _VP),
-                ("out_world_to_1", _VP), ("out_kept", _VP), ("out_round_info", _VP), ("out_round_chi2", _VP)]
-
-
-class local_ba_args_c(C.Structure):
-    """plp_local_ba_args"""
-    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("num_first_iter", C.c_int32), ("num_second_iter", C.c_int32), ("G", C.c_int32),
-                ("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("kp_stride", C.c_int32), ("pose_stride", C.c_int32), ("inv_level_sigma_sq", _VP),
-                ("num_levels", C.c_int32), ("pose", _VP), ("kf_erased", _VP), ("kf_is_origin", _VP), ("undist", _VP), ("x_right", _VP), ("counts", _VP),
-                ("pos_w", _VP), ("lm_erased", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("obs_idx", _VP), ("kf_local", _VP), ("out_status", _VP),
-                ("out_kf_role", _VP), ("out_lm_role", _VP), ("out_pose", _VP), ("out_pos_w", _VP), ("out_outlier", _VP), ("out_round_info", _VP),
-                ("out_round_chi2", _VP)]
-
-
-class pose_graph_args_c(C.Structure):
-    """plp_pose_graph_args"""
-    _fields_ = [(k, C.c_int32) for k in ("G", "F", "pose_stride", "conn_cap", "covis_cap", "edge_cap", "env_cap", "max_iter")] + [(k, _VP) for k in (
-        "pose", "kf_erased", "kf_id", "kf_parent", "kf_conn", "kf_conn_w", "kf_n_conn", "kf_covis", "kf_covis_w", "kf_n_covis", "kf_loop_offsets", "kf_loop",
-        "loop_kf", "curr_kf", "fix_scale", "pre_offsets", "pre_row", "pre_sim3", "non_offsets", "non_row", "non_sim3", "lc_offsets", "lc_owner", "lc_target",
-        "out_status", "out_num_edges", "out_edges", "out_sim3_cw", "out_corrected_wc", "out_pose", "out_info", "out_chi2")]
-
-
-class correct_landmarks_args_c(C.Structure):
-    """plp_correct_landmarks_args"""
-    _fields_ = [("L", C.c_int32), ("F", C.c_int32)] + [(k, _VP) for k in ("pos_w", "lm_erased", "ref_kf", "kf_erased", "sim3_cw", "corrected_wc", "out_pos_w",
-                                                                         "out_status")]
-
-
-class local_map_args_c(C.Structure):
-    """plp_local_map_args"""
-    _fields_ = [("B", C.c_int32), ("F", C.c_int32), ("C", C.c_int32), ("L", C.c_int32), ("LL", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32),
-                ("lcap", C.c_int32), ("fcap", C.c_int32), ("flcap", C.c_int32), ("frm_stride", C.c_int32), ("frm_stride_lines", C.c_int32),
-                ("max_num_local_keyfrms", C.c_int32), ("k_cap", C.c_int32), ("m_cap", C.c_int32), ("ml_cap", C.c_int32), ("workspace_bytes", C.c_int64),
-                ("kf_erased", _VP), ("kf_covis", _VP), ("kf_parent", _VP), ("kf_children_offsets", _VP), ("kf_children", _VP), ("kf_lm", _VP),
-                ("kf_counts", _VP), ("kf_lm_lines", _VP), ("kf_kl_counts", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("lm_erased", _VP),
-                ("lm_erased_lines", _VP), ("frm_lm", _VP), ("frm_counts", _VP), ("frm_lm_lines", _VP), ("frm_kl_counts", _VP), ("out_status", _VP),
-                ("out_num_first", _VP), ("out_num_kf", _VP), ("out_local_kf", _VP), ("out_first_weight", _VP), ("out_nearest_kf", _VP),
-                ("out_num_lm", _VP), ("out_local_lm", _VP), ("out_held", _VP), ("out_num_lines", _VP), ("out_local_lines", _VP), ("out_held_lines", _VP)]
-
-
-class cull_keyframes_args_c(C.Structure):
-    """plp_cull_keyframes_args"""
-    _fields_ = [("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32), ("kp_stride", C.c_int32), ("G", C.c_int32), ("Cv", C.c_int32),
-                ("origin_id", C.c_uint32), ("is_monocular", C.c_int32), ("kf_lm", _VP), ("kf_counts", _VP), ("undist", _VP), ("x_right", _VP),
-                ("depths", _VP), ("depth_thr", _VP), ("kf_id", _VP), ("kf_erased", _VP), ("kf_cannot_erase", _VP), ("obs_offsets", _VP), ("obs_kf", _VP),
-                ("obs_idx", _VP), ("lm_erased", _VP), ("lm_num_obs", _VP), ("cur_kf", _VP), ("covis_offsets", _VP), ("covis", _VP),
-                ("out_num_removed", _VP), ("out_decision", _VP), ("out_num_valid", _VP), ("out_num_redundant", _VP), ("out_kf_removed", _VP),
-                ("out_lm_erased", _VP)]
-
-
-class cull_landmarks_args_c(C.Structure):
-    """plp_cull_landmarks_args"""
-    _fields_ = [("R", C.c_int32), ("N", C.c_int32), ("L", C.c_int32), ("fresh_offsets", _VP), ("fresh", _VP), ("lm_erased", _VP), ("num_observed", _VP),
-                ("num_observable", _VP), ("first_kf_id", _VP), ("num_obs", _VP), ("owning_plane", _VP), ("cur_kf_id", _VP), ("num_obs_thr", _VP),
-                ("out_state", _VP), ("out_num_removed", _VP), ("out_num_fresh", _VP), ("out_fresh", _VP)]
-
-
-class covisibility_update_args_c(C.Structure):
-    """plp_covisibility_update_args"""
-    _fields_ = [("F", C.c_int32), ("L", C.c_int32), ("T", C.c_int32), ("cap", C.c_int32), ("conn_cap", C.c_int32), ("covis_cap", C.c_int32),
-                ("G", C.c_int32), ("kf_lm", _VP), ("kf_counts", _VP), ("obs_offsets", _VP), ("obs_kf", _VP), ("lm_erased", _VP), ("kf_id", _VP),
-                ("kf_conn", _VP), ("kf_conn_w", _VP), ("kf_n_conn", _VP), ("kf_covis", _VP), ("kf_covis_w", _VP), ("kf_n_covis", _VP),
-                ("kf_parent", _VP), ("kf_parent_unset", _VP), ("owners", _VP), ("out_status", _VP), ("out_nearest", _VP), ("out_max_weight", _VP),
-                ("out_touched", _VP)]
-
-
-class covisibility_erase_args_c(C.Structure):
-    """plp_covisibility_erase_args"""
-    _fields_ = [("F", C.c_int32), ("conn_cap", C.c_int32), ("covis_cap", C.c_int32), ("kf_conn", _VP), ("kf_conn_w", _VP), ("kf_n_conn", _VP),
-                ("kf_covis", _VP), ("kf_covis_w", _VP), ("kf_n_covis", _VP), ("erased", _VP), ("out_status", _VP), ("out_touched", _VP)]
-
-
-class bow_query_args_c(C.Structure):
-    """plp_bow_query_args"""
-    _fields_ = [("scoring", C.c_int32), ("n_words", C.c_uint32), ("N", C.c_int32), ("stride", C.c_int32), ("db_word", _VP), ("db_value", _VP),
-                ("db_n", _VP), ("db_alive", _VP), ("Q", C.c_int32), ("q_stride", C.c_int32), ("q_word", _VP), ("q_value", _VP), ("q_n", _VP),
-                ("reject", _VP), ("min_score", _VP), ("covis_cap", C.c_int32), ("covis", _VP), ("n_covis", _VP), ("out_common", _VP),
-                ("out_score", _VP), ("out_total", _VP), ("out_best_kf", _VP), ("out_final", _VP), ("out_n_final", _VP), ("out_max_common", _VP),
-                ("out_best_total", _VP), ("out_status", _VP)]
-
-
-class bow_score_pairs_args_c(C.Structure):
-    """plp_bow_score_pairs_args"""
-    _fields_ = [("scoring", C.c_int32), ("NA", C.c_int32), ("stride_a", C.c_int32), ("a_word", _VP), ("a_value", _VP), ("a_n", _VP),
-                ("NB", C.c_int32), ("stride_b", C.c_int32), ("b_word", _VP), ("b_value", _VP), ("b_n", _VP), ("P", C.c_int32), ("a_row", _VP),
-                ("b_row", _VP), ("out_score", _VP)]
-
-
-# plp_bow_query_status: where acquire_loop_candidates / acquire_relocalization_candidates leave a query
-BOW_CANDIDATES, BOW_NO_COMMON_WORDS, BOW_NO_SCORE, BOW_BELOW_MIN_SCORE = range(4)
-BOW_BITMAP_WORDS = 1310720          # up to this n_words the count kernel tests bits of an LDS bitmap, above it bisects the query's words
-# the outputs of plp_bow_query_*: name -> (per row?, dtype)
-BOW_QUERY_OUTPUTS = dict(common=(True, np.uint32), score=(True, np.float32), total=(True, np.float32), best_kf=(True, np.int32), final=(True, np.uint8),
-                         n_final=(False, np.int32), max_common=(False, np.uint32), best_total=(False, np.float32), status=(False, np.uint8))
-
-
-def _struct(cls, fields, ptrs):
-    a = cls()
-    for k, v in fields.items():
-        setattr(a, k, v)
-    for k, v in ptrs.items():
-        setattr(a, k, v)
-    return a
-
-
-class match_grid_c(C.Structure):
-    _fields_ = [("min_x", C.c_float), ("min_y", C.c_float), ("inv_cell_width", C.c_double), ("inv_cell_height", C.c_double),
-                ("cols", C.c_int32), ("rows", C.c_int32)]
-
-
-class match_args_c(C.Structure):
-    _fields_ = [("mode", C.c_int32), ("B", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
-                ("t_kps", _VP), ("t_desc", _VP), ("t_x_right", _VP), ("t_occupied", _VP), ("t_angle", _VP), ("t_counts", _VP),
-                ("q_valid", _VP), ("q_reproj", _VP), ("q_x_right", _VP), ("q_level", _VP), ("q_angle", _VP), ("q_desc", _VP),
-                ("q_has_obs", _VP), ("q_counts", _VP),
-                ("margin", C.c_float), ("lowe_ratio", C.c_float), ("direction", C.c_int32), ("check_orientation", C.c_int32),
-                ("num_levels", C.c_int32), ("scale_factors", _VP), ("grid", match_grid_c),
-                ("t_kl", _VP), ("t_kp_octave", _VP), ("t_x_right2", _VP), ("q_reproj2", _VP), ("q_x_right2", _VP),
-                ("is_rgbd", C.c_int32), ("num_levels_lsd", C.c_int32),
-                ("q_group", _VP), ("t_group", _VP), ("q_reproj_d", _VP), ("inv_level_sigma_sq", _VP), ("out_query_best", _VP),
-                ("hamm_dist_thr", C.c_int32), ("level_window", C.c_int32), ("flags", C.c_int32),
-                ("q_reproj2_d", _VP), ("q_bearing", _VP), ("t_bearing", _VP), ("epipolar", _VP),
-                ("out_match", _VP), ("out_num", _VP), ("q_desc_stride", C.c_int32), ("t_count_hint", C.c_int32), ("directions", _VP)]
-
-
-MODE_LANDMARKS, MODE_LAST_FRAME, MODE_BRUTE_FORCE, MODE_LANDMARKS_LINE, MODE_LAST_FRAME_LINE, MODE_BOW, MODE_FUSE, MODE_FUSE_LINE, MODE_TRIANGULATION = 0, 1, 2, 3, 4, 5, 6, 7, 8
-FLAG_NO_CHI2, FLAG_SIGNED_LEVEL, FLAG_UNSIGNED_LEVEL, FLAG_MARK_INVALIDATED = 1, 2, 4, 8
-
-
-def _rows_u8(a):
-    """a 2-D uint8 image as the C ABI takes it: unit stride inside a row, any row step >= the row length -- a view into a larger image (cv::Mat ROI, a cropped numpy
-    slice) is passed AS IT IS, with its step; anything else is copied to a contiguous array first"""
-    a = np.asarray(a)
-    if a.dtype == np.uint8 and a.ndim == 2 and a.size and a.strides[1] == 1 and a.strides[0] >= a.shape[1]:
-        return a
-    return np.ascontiguousarray(a, np.uint8)
-
-
 def make_grid(cols_px, rows_px, grid_cols=64, grid_rows=48, min_x=0.0, min_y=0.0):
     """camera::base grid for an undistorted image of cols_px x rows_px (camera/base.h:91, perspective.cc ctor)."""
     inv_w = np.float64(grid_cols) / np.float64(np.float32(cols_px) - np.float32(min_x))   # perspective.cc:55-56
@@ -2754,6 +1976,14 @@ class matcher:
         if h:
             lib().plp_matcher_destroy(h)
             self._h = None
+
+    def _host(self, symbol):
+        """call(args struct) for the host-pointer entry `symbol` of this context"""
+        return lambda a: _check(getattr(lib(), symbol)(self._h, C.byref(a)))
+
+    def _device(self, symbol, a, stream):
+        """the device-pointer entry `symbol` of this context on the stream (int handle, torch stream or None = torch's current one); asynchronous"""
+        _check(getattr(lib(), symbol)(self._h, C.byref(a), stream_handle(stream)))
 
     def _args(self, mode, B, n_cap, m_cap, fields, margin, direction, scale_factors, grid, out_match, out_num, ptr):
         a = match_args_c()
@@ -2876,12 +2106,12 @@ class matcher:
             out["reproj_ep"] = np.zeros((B, M, 2), np.float32)
         else:
             out["x_right"] = np.zeros((B, M), np.float32)
-        P = lambda v: None if v is None else v.ctypes.data
-        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, M, dict(
-            pose=P(pose), counts=P(cn), pos_w=P(pw), obs_mean_normal=P(nm), min_valid_dist=P(mn), max_valid_dist=P(mx), skip=P(sk),
-            out_reproj=P(out["reproj"]), out_reproj2=P(out.get("reproj_ep")), out_x_right=P(out.get("x_right")), out_level=P(out["level"]),
-            out_valid=P(out["valid"]), out_num_valid=P(out["num_valid"])))
-        _check((lib().plp_observe_landmark_lines_host if lines else lib().plp_observe_landmarks_host)(self._h, C.byref(a)))
+        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, M, host_ptrs(
+            empty_null=False,   # these entries check their pointers before m_cap / cap
+            pose=pose, counts=cn, pos_w=pw, obs_mean_normal=nm, min_valid_dist=mn, max_valid_dist=mx, skip=sk,
+            out_reproj=out["reproj"], out_reproj2=out.get("reproj_ep"), out_x_right=out.get("x_right"), out_level=out["level"],
+            out_valid=out["valid"], out_num_valid=out["num_valid"]))
+        self._host("plp_observe_landmark_lines_host" if lines else "plp_observe_landmarks_host")(a)
         if lines:
             out["reproj_sp"] = out.pop("reproj")
         return {k: v[0] for k, v in out.items()} if single else out
@@ -2907,14 +2137,10 @@ class matcher:
 
     def _observe_device(self, lines, camera, B, m_cap, pose, pos_w, out_reproj, out_valid, obs_mean_normal, min_valid_dist, max_valid_dist, skip,
                         counts, out_reproj2, out_x_right, out_level, out_num_valid, ray_cos_thr, log_scale_factor, num_levels, img_bounds, stream):
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, dict(
-            pose=D(pose), counts=D(counts), pos_w=D(pos_w), obs_mean_normal=D(obs_mean_normal), min_valid_dist=D(min_valid_dist),
-            max_valid_dist=D(max_valid_dist), skip=D(skip), out_reproj=D(out_reproj), out_reproj2=D(out_reproj2), out_x_right=D(out_x_right),
-            out_level=D(out_level), out_valid=D(out_valid), out_num_valid=D(out_num_valid)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check((lib().plp_observe_landmark_lines_device if lines else lib().plp_observe_landmarks_device)(self._h, C.byref(a), st))
+        a = _observe_args(camera, img_bounds, ray_cos_thr, log_scale_factor, num_levels, B, m_cap, dev_ptrs(
+            pose=pose, counts=counts, pos_w=pos_w, obs_mean_normal=obs_mean_normal, min_valid_dist=min_valid_dist, max_valid_dist=max_valid_dist, skip=skip,
+            out_reproj=out_reproj, out_reproj2=out_reproj2, out_x_right=out_x_right, out_level=out_level, out_valid=out_valid, out_num_valid=out_num_valid))
+        self._device("plp_observe_landmark_lines_device" if lines else "plp_observe_landmarks_device", a, stream)
 
     def observe_landmarks_device(self, camera, B, m_cap, pose, pos_w, out_reproj, out_valid, obs_mean_normal=None, min_valid_dist=None,
                                  max_valid_dist=None, skip=None, counts=None, out_x_right=None, out_level=None, out_num_valid=None, ray_cos_thr=0.5,
@@ -2945,24 +2171,16 @@ class matcher:
         ft = np.ascontiguousarray(feats, KL_DTYPE if lines else KP_DTYPE).reshape(B, M)
         sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(B, M)
         cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
-        shapes = dict(reproj=((B, M, 2), np.float32), x_right=((B, M), np.float32), level=((B, M), np.int32), valid=((B, M), np.uint8),
-                      direction=((B,), np.int32), num_valid=((B,), np.int32))
-        shapes.update(dict(reproj_ep=((B, M, 2), np.float32), x_right_ep=((B, M), np.float32)) if lines else dict(angle=((B, M), np.float32)))
-        o = {}
-        for k, (shape, dt) in shapes.items():   # the caller's arrays are the outputs when given (slots the library does not write keep their values)
-            v = None if out is None else out.get(k)
-            if v is not None:
-                if not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                    raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-                o[k] = v
-            else:
-                o[k] = np.zeros(shape, dt)
-        P = lambda v: None if v is None else v.ctypes.data
-        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, M, dict(
-            counts=P(cn), pose_curr=P(pc), pose_last=P(pl), pos_w=P(pw), skip=P(sk), keypts=None if lines else P(ft), keylines=P(ft) if lines else None,
-            out_reproj=P(o["reproj"]), out_reproj2=P(o.get("reproj_ep")), out_x_right=P(o["x_right"]), out_x_right2=P(o.get("x_right_ep")),
-            out_level=P(o["level"]), out_angle=P(o.get("angle")), out_valid=P(o["valid"]), out_direction=P(o["direction"]), out_num_valid=P(o["num_valid"])))
-        _check((lib().plp_project_last_frame_lines_host if lines else lib().plp_project_last_frame_host)(self._h, C.byref(a)))
+        specs = (("reproj", (B, M, 2), np.float32), ("x_right", (B, M), np.float32), ("level", (B, M), np.int32), ("valid", (B, M), np.uint8),
+                 ("direction", (B,), np.int32), ("num_valid", (B,), np.int32))
+        specs += (("reproj_ep", (B, M, 2), np.float32), ("x_right_ep", (B, M), np.float32)) if lines else (("angle", (B, M), np.float32),)
+        o = out_arrays(specs, out)
+        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, M, host_ptrs(
+            empty_null=False,   # these entries check their pointers before m_cap / cap
+            counts=cn, pose_curr=pc, pose_last=pl, pos_w=pw, skip=sk, keypts=None if lines else ft, keylines=ft if lines else None,
+            out_reproj=o["reproj"], out_reproj2=o.get("reproj_ep"), out_x_right=o["x_right"], out_x_right2=o.get("x_right_ep"),
+            out_level=o["level"], out_angle=o.get("angle"), out_valid=o["valid"], out_direction=o["direction"], out_num_valid=o["num_valid"]))
+        self._host("plp_project_last_frame_lines_host" if lines else "plp_project_last_frame_host")(a)
         if lines:
             o["reproj_sp"], o["x_right_sp"] = o.pop("reproj"), o.pop("x_right")
         return {k: v[0] for k, v in o.items()} if single else o
@@ -2983,11 +2201,8 @@ class matcher:
         return self._last_frame_host(True, camera, pose_curr, pose_last, pos_w, keylines, skip, counts, setup_type, true_baseline, img_bounds, out)
 
     def _last_frame_device(self, lines, camera, B, m_cap, ptrs, setup_type, true_baseline, img_bounds, stream):
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, {k: D(v) for k, v in ptrs.items()})
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check((lib().plp_project_last_frame_lines_device if lines else lib().plp_project_last_frame_device)(self._h, C.byref(a), st))
+        a = _last_frame_args(camera, img_bounds, setup_type, true_baseline, B, m_cap, dev_ptrs(**ptrs))
+        self._device("plp_project_last_frame_lines_device" if lines else "plp_project_last_frame_device", a, stream)
 
     def project_last_frame_device(self, camera, B, m_cap, pose_curr, pose_last, pos_w, keypts, out_reproj, out_level, out_valid, out_direction,
                                   skip=None, counts=None, out_x_right=None, out_angle=None, out_num_valid=None, setup_type=SETUP_MONOCULAR,
@@ -3027,13 +2242,13 @@ class matcher:
                    level=np.zeros((B, M), np.int32), valid=np.zeros((B, M), np.uint8), status=np.zeros((B, M), np.uint8), num_valid=np.zeros(B, np.int32))
         if lines:
             out.update(reproj_ep_d=np.zeros((B, M, 2), np.float64), reproj_ep=np.zeros((B, M, 2), np.float32), x_right_ep=np.zeros((B, M), np.float32))
-        P = lambda v: None if v is None else v.ctypes.data
-        a = _project_args(camera, img_bounds, log_scale_factor, num_levels, B, M, shared_landmarks, dist_mode, ray_test, line_dist_mode, dict(
-            pose=P(pose), counts=P(cn), pos_w=P(pw), obs_mean_normal=P(nm), min_valid_dist=P(mn), max_valid_dist=P(mx), skip=P(sk),
-            out_reproj_d=P(out["reproj_d"]), out_reproj2_d=P(out.get("reproj_ep_d")), out_reproj=P(out["reproj"]), out_reproj2=P(out.get("reproj_ep")),
-            out_x_right=P(out["x_right"]), out_x_right2=P(out.get("x_right_ep")), out_level=P(out["level"]), out_valid=P(out["valid"]),
-            out_status=P(out["status"]), out_num_valid=P(out["num_valid"])))
-        _check((lib().plp_project_landmark_lines_host if lines else lib().plp_project_landmarks_host)(self._h, C.byref(a)))
+        a = _project_args(camera, img_bounds, log_scale_factor, num_levels, B, M, shared_landmarks, dist_mode, ray_test, line_dist_mode, host_ptrs(
+            empty_null=False,   # these entries check their pointers before m_cap / cap
+            pose=pose, counts=cn, pos_w=pw, obs_mean_normal=nm, min_valid_dist=mn, max_valid_dist=mx, skip=sk,
+            out_reproj_d=out["reproj_d"], out_reproj2_d=out.get("reproj_ep_d"), out_reproj=out["reproj"], out_reproj2=out.get("reproj_ep"),
+            out_x_right=out["x_right"], out_x_right2=out.get("x_right_ep"), out_level=out["level"], out_valid=out["valid"],
+            out_status=out["status"], out_num_valid=out["num_valid"]))
+        self._host("plp_project_landmark_lines_host" if lines else "plp_project_landmarks_host")(a)
         if lines:
             out["reproj_sp_d"], out["reproj_sp"], out["x_right_sp"] = out.pop("reproj_d"), out.pop("reproj"), out.pop("x_right")
         return {k: v[0] for k, v in out.items()} if single else out
@@ -3062,12 +2277,9 @@ class matcher:
 
     def _project_device(self, lines, camera, B, m_cap, ptrs, shared_landmarks, dist_mode, ray_test, line_dist_mode, log_scale_factor, num_levels,
                         img_bounds, stream):
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _project_args(camera, img_bounds, log_scale_factor, num_levels, B, m_cap, shared_landmarks, dist_mode, ray_test, line_dist_mode,
-                          {k: D(v) for k, v in ptrs.items()})
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check((lib().plp_project_landmark_lines_device if lines else lib().plp_project_landmarks_device)(self._h, C.byref(a), st))
+                          dev_ptrs(**ptrs))
+        self._device("plp_project_landmark_lines_device" if lines else "plp_project_landmarks_device", a, stream)
 
     def project_landmarks_device(self, camera, B, m_cap, pose, pos_w, min_valid_dist, max_valid_dist, out_valid, out_reproj_d=None, out_reproj=None,
                                  obs_mean_normal=None, skip=None, counts=None, out_x_right=None, out_level=None, out_status=None, out_num_valid=None,
@@ -3109,15 +2321,9 @@ class matcher:
         di = np.ascontiguousarray(dist, np.int32).reshape(B, L)
         cl = None if counts_left is None else np.ascontiguousarray(counts_left, np.int32).reshape(B)
         cr = None if counts_right is None else np.ascontiguousarray(counts_right, np.int32).reshape(B)
-        o = {}
-        for k, shape, dt in (("good_match", (B, L), np.int32), ("kl_depths", (B, L, 2), np.float32), ("kl_x_right", (B, L, 2), np.float32)):
-            v = None if out is None else out.get(k)
-            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            o[k] = v if v is not None else np.zeros(shape, dt)
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        o = out_arrays((("good_match", (B, L), np.int32), ("kl_depths", (B, L, 2), np.float32), ("kl_x_right", (B, L, 2), np.float32)), out)
         a = _struct(stereo_keylines_args_c, dict(B=B, cap_left=L, cap_right=R), dict(
-            keylines_left=P(kl), counts_left=P(cl), keylines_right=P(kr), counts_right=P(cr), train_idx=P(ti), dist=P(di),
+            host_ptrs(keylines_left=kl, counts_left=cl, keylines_right=kr, counts_right=cr, train_idx=ti, dist=di),
             out_good_match=o["good_match"].ctypes.data, out_kl_depths=o["kl_depths"].ctypes.data, out_kl_x_right=o["kl_x_right"].ctypes.data))
         _check(lib().plp_stereo_keylines_host(self._h, C.byref(a)))
         return {k: v[0] for k, v in o.items()} if single else o
@@ -3125,13 +2331,10 @@ class matcher:
     def stereo_keylines_device(self, B, cap_left, cap_right, keylines_left, keylines_right, train_idx, dist, out_good_match, out_kl_depths,
                                out_kl_x_right, counts_left=None, counts_right=None, stream=None):
         """plp_stereo_keylines_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(stereo_keylines_args_c, dict(B=int(B), cap_left=int(cap_left), cap_right=int(cap_right)), dict(
-            keylines_left=D(keylines_left), counts_left=D(counts_left), keylines_right=D(keylines_right), counts_right=D(counts_right),
-            train_idx=D(train_idx), dist=D(dist), out_good_match=D(out_good_match), out_kl_depths=D(out_kl_depths), out_kl_x_right=D(out_kl_x_right)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_stereo_keylines_device(self._h, C.byref(a), st))
+        a = _struct(stereo_keylines_args_c, dict(B=int(B), cap_left=int(cap_left), cap_right=int(cap_right)), dev_ptrs(
+            keylines_left=keylines_left, counts_left=counts_left, keylines_right=keylines_right, counts_right=counts_right, train_idx=train_idx, dist=dist,
+            out_good_match=out_good_match, out_kl_depths=out_kl_depths, out_kl_x_right=out_kl_x_right))
+        self._device("plp_stereo_keylines_device", a, stream)
 
     def keylines_3d(self, camera, setup_type, pose, keylines, kl_depths=None, good_match=None, keylines_right=None, counts=None, counts_right=None,
                     out=None):
@@ -3149,16 +2352,11 @@ class matcher:
         kr = None if keylines_right is None else np.ascontiguousarray(keylines_right, KL_DTYPE).reshape(B, -1)
         cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(B)
         cr = None if counts_right is None else np.ascontiguousarray(counts_right, np.int32).reshape(B)
-        o = {}
-        for k, shape, dt in (("pos_w", (B, M, 6), np.float64), ("valid", (B, M), np.uint8)):
-            v = None if out is None else out.get(k)
-            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            o[k] = v if v is not None else np.zeros(shape, dt)
-        P = lambda v: None if v is None else v.ctypes.data
-        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=B, cap=M, cap_right=0 if kr is None else kr.shape[1]), dict(
-            counts=P(cn), pose=P(pose), keylines=P(kl), kl_depths=P(kd), good_match=P(gm), keylines_right=None if kr is None or kr.size == 0 else P(kr),
-            counts_right=P(cr), out_pos_w=o["pos_w"].ctypes.data, out_valid=o["valid"].ctypes.data))
+        o = out_arrays((("pos_w", (B, M, 6), np.float64), ("valid", (B, M), np.uint8)), out)
+        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=B, cap=M, cap_right=0 if kr is None else kr.shape[1]), host_ptrs(
+            empty_null=False,   # these entries check their pointers before m_cap / cap
+            counts=cn, pose=pose, keylines=kl, kl_depths=kd, good_match=gm, keylines_right=None if kr is None or kr.size == 0 else kr,
+            counts_right=cr, out_pos_w=o["pos_w"], out_valid=o["valid"]))
         a.camera = camera_model_c.from_buffer_copy(camera)
         _check(lib().plp_keylines_3d_host(self._h, C.byref(a)))
         return {k: v[0] for k, v in o.items()} if single else o
@@ -3166,14 +2364,11 @@ class matcher:
     def keylines_3d_device(self, camera, setup_type, B, cap, pose, keylines, out_pos_w, kl_depths=None, good_match=None, keylines_right=None,
                            cap_right=0, counts=None, counts_right=None, out_valid=None, stream=None):
         """plp_keylines_3d_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=int(B), cap=int(cap), cap_right=int(cap_right)), dict(
-            counts=D(counts), pose=D(pose), keylines=D(keylines), kl_depths=D(kl_depths), good_match=D(good_match), keylines_right=D(keylines_right),
-            counts_right=D(counts_right), out_pos_w=D(out_pos_w), out_valid=D(out_valid)))
+        a = _struct(keylines_3d_args_c, dict(setup_type=int(setup_type), B=int(B), cap=int(cap), cap_right=int(cap_right)), dev_ptrs(
+            counts=counts, pose=pose, keylines=keylines, kl_depths=kl_depths, good_match=good_match, keylines_right=keylines_right, counts_right=counts_right,
+            out_pos_w=out_pos_w, out_valid=out_valid))
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_keylines_3d_device(self._h, C.byref(a), st))
+        self._device("plp_keylines_3d_device", a, stream)
 
     # ---- key-frame pair line triangulation: keyframe::compute_median_depth (keyframe.cc:825-857), triangulate_line_with_two_keyframes
     # (mapping_module.cc:482-601) with two_view_triangulator_line::triangulate (two_view_triangulator_line.cc:52-296)
@@ -3189,35 +2384,23 @@ class matcher:
         va = None if valid is None else np.ascontiguousarray(valid, np.uint8).reshape(F, M)
         cn = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(F)
         med, cnt = np.zeros(F, np.float32), np.zeros(F, np.int32)
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
         a = _struct(median_depth_args_c, dict(F=F, m_cap=M, abs_flag=int(bool(abs_flag))), dict(
-            pose=P(pose), pos_w=P(pw), valid=P(va), counts=P(cn), out_median=med.ctypes.data, out_count=cnt.ctypes.data))
+            host_ptrs(pose=pose, pos_w=pw, valid=va, counts=cn), out_median=med.ctypes.data, out_count=cnt.ctypes.data))
         _check(lib().plp_median_depth_host(self._h, C.byref(a)))
         return (med[0], cnt[0]) if single else (med, cnt)
 
     def median_depth_device(self, F, m_cap, pose, pos_w, out_median, out_count, valid=None, counts=None, abs_flag=True, stream=None):
         """plp_median_depth_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(median_depth_args_c, dict(F=int(F), m_cap=int(m_cap), abs_flag=int(bool(abs_flag))), dict(
-            pose=D(pose), pos_w=D(pos_w), valid=D(valid), counts=D(counts), out_median=D(out_median), out_count=D(out_count)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_median_depth_device(self._h, C.byref(a), st))
+        a = _struct(median_depth_args_c, dict(F=int(F), m_cap=int(m_cap), abs_flag=int(bool(abs_flag))), dev_ptrs(
+            pose=pose, pos_w=pos_w, valid=valid, counts=counts, out_median=out_median, out_count=out_count))
+        self._device("plp_median_depth_device", a, stream)
 
     @staticmethod
     def _keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr, dist_thr,
                               endpoint_thr, angle_thr, skip_occupied):
-        sf = np.ascontiguousarray(scale_factors, np.float32)
-        ls = np.ascontiguousarray(level_sigma_sq, np.float32)
-        if sf.shape != ls.shape or sf.ndim != 1:
-            raise PlpError(PLP_ERR_INVALID_ARG, "scale_factors and level_sigma_sq must be vectors of the same length")
-        a.camera = camera_model_c.from_buffer_copy(camera)
-        a.setup_type, a.true_baseline = int(setup_type), float(true_baseline)
-        a.scale_factors, a.level_sigma_sq, a.num_levels = sf.ctypes.data, ls.ctypes.data, len(sf)
-        a.scale_factor = float(sf[1]) if scale_factor is None and len(sf) > 1 else float(1.0 if scale_factor is None else scale_factor)
-        a.rays_parallax_deg_thr = float(rays_parallax_deg_thr)
+        keep = matcher._keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr)
         a.dist_thr, a.endpoint_thr, a.angle_thr, a.skip_occupied = float(dist_thr), float(endpoint_thr), float(angle_thr), int(bool(skip_occupied))
-        return sf, ls                                          # kept alive by the caller until the call has returned
+        return keep
 
     def triangulate_keyline_pairs(self, camera, setup_type, groups, keylines, line_functions, kl_x_right, pose, median_depth, occupied,
                                   scale_factors, level_sigma_sq, counts=None, kp_depths=None, kp_counts=None, lines_3d=None, lbd=None,
@@ -3256,18 +2439,12 @@ class matcher:
         kd = None if kp_depths is None else np.ascontiguousarray(kp_depths, np.float32).reshape(F, -1)
         kc = None if kp_counts is None else np.ascontiguousarray(kp_counts, np.int32).reshape(F)
         l3 = None if lines_3d is None else np.ascontiguousarray(lines_3d, np.float64).reshape(F, M, 6)
-        o = {}
-        for k, shape, dt, fill in (("match", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 6), np.float64, 0), ("status", (Pn, M), np.uint8, 0),
-                                   ("occupied_cur", (G, M), np.uint8, 0)):
-            v = None if out is None else out.get(k)
-            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            o[k] = v if v is not None else np.full(shape, fill, dt)
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
+        o = out_arrays((("match", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 6), np.float64, 0), ("status", (Pn, M), np.uint8, 0),
+                                   ("occupied_cur", (G, M), np.uint8, 0)), out)
         a = _struct(keyline_pairs_args_c, dict(F=F, cap=M, kp_cap=0 if kd is None else kd.shape[1], P=Pn, G=G), dict(
-            keylines=P(kl), counts=P(cn), line_functions=P(fn), kl_x_right=P(xr), kp_depths=P(kd), kp_counts=P(kc), pose=P(po), median_depth=P(md),
-            lines_3d=P(l3), occupied=P(oc), pairs=P(pairs), group_offsets=offs.ctypes.data, train_idx=P(ti), dist=P(di),
-            out_match=P(o["match"]), out_pos_w=P(o["pos_w"]), out_status=P(o["status"]), out_occupied_cur=P(o["occupied_cur"])))
+            host_ptrs(keylines=kl, counts=cn, line_functions=fn, kl_x_right=xr, kp_depths=kd, kp_counts=kc, pose=po, median_depth=md, lines_3d=l3,
+                      occupied=oc, pairs=pairs, train_idx=ti, dist=di, out_match=o["match"], out_pos_w=o["pos_w"], out_status=o["status"],
+                      out_occupied_cur=o["occupied_cur"]), group_offsets=offs.ctypes.data))
         keep = self._keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr,
                                           dist_thr, endpoint_thr, angle_thr, skip_occupied)
         _check(lib().plp_triangulate_keyline_pairs_host(self._h, C.byref(a)))
@@ -3302,17 +2479,13 @@ class matcher:
                                          angle_thr=20.0, skip_occupied=True, stream=None):
         """plp_triangulate_keyline_pairs_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors and
         level_sigma_sq are host vectors); asynchronous, two kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(keyline_pairs_args_c, dict(F=int(F), cap=int(cap), kp_cap=int(kp_cap), P=int(P), G=int(G)), dict(
-            keylines=D(keylines), counts=D(counts), line_functions=D(line_functions), kl_x_right=D(kl_x_right), kp_depths=D(kp_depths),
-            kp_counts=D(kp_counts), pose=D(pose), median_depth=D(median_depth), lines_3d=D(lines_3d), occupied=D(occupied), pairs=D(pairs),
-            group_offsets=D(group_offsets), train_idx=D(train_idx), dist=D(dist), out_match=D(out_match), out_pos_w=D(out_pos_w),
-            out_status=D(out_status), out_occupied_cur=D(out_occupied_cur)))
+        a = _struct(keyline_pairs_args_c, dict(F=int(F), cap=int(cap), kp_cap=int(kp_cap), P=int(P), G=int(G)), dev_ptrs(
+            keylines=keylines, counts=counts, line_functions=line_functions, kl_x_right=kl_x_right, kp_depths=kp_depths, kp_counts=kp_counts, pose=pose,
+            median_depth=median_depth, lines_3d=lines_3d, occupied=occupied, pairs=pairs, group_offsets=group_offsets, train_idx=train_idx, dist=dist,
+            out_match=out_match, out_pos_w=out_pos_w, out_status=out_status, out_occupied_cur=out_occupied_cur))
         keep = self._keyline_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr,
                                           dist_thr, endpoint_thr, angle_thr, skip_occupied)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_triangulate_keyline_pairs_device(self._h, C.byref(a), st))
+        self._device("plp_triangulate_keyline_pairs_device", a, stream)
         del keep
 
     def keyframe_pair_geometry(self, camera, setup_type, pose, pairs, median_depth=None, true_baseline=0.0, out=None):
@@ -3323,15 +2496,9 @@ class matcher:
         pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
         F, Pn = len(po), len(pr)
         md = None if median_depth is None else np.ascontiguousarray(median_depth, np.float32).reshape(F)
-        o = {}
-        for k, shape, dt in (("skip", (Pn,), np.uint8), ("epipolar", (Pn, 12), np.float64), ("baseline", (Pn,), np.float64)):
-            v = None if out is None else out.get(k)
-            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            o[k] = v if v is not None else np.zeros(shape, dt)
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-        a = _struct(pair_geometry_args_c, dict(F=F, P=Pn, setup_type=int(setup_type), true_baseline=float(true_baseline)), dict(
-            pose=P(po), median_depth=P(md), pairs=P(pr), out_skip=P(o["skip"]), out_epipolar=P(o["epipolar"]), out_baseline=P(o["baseline"])))
+        o = out_arrays((("skip", (Pn,), np.uint8), ("epipolar", (Pn, 12), np.float64), ("baseline", (Pn,), np.float64)), out)
+        a = _struct(pair_geometry_args_c, dict(F=F, P=Pn, setup_type=int(setup_type), true_baseline=float(true_baseline)), host_ptrs(
+            pose=po, median_depth=md, pairs=pr, out_skip=o["skip"], out_epipolar=o["epipolar"], out_baseline=o["baseline"]))
         a.camera = camera_model_c.from_buffer_copy(camera)
         _check(lib().plp_keyframe_pair_geometry_host(self._h, C.byref(a)))
         return o
@@ -3339,14 +2506,10 @@ class matcher:
     def keyframe_pair_geometry_device(self, camera, setup_type, F, P, pose, pairs, out_skip, out_epipolar, out_baseline, median_depth=None,
                                       true_baseline=0.0, stream=None):
         """plp_keyframe_pair_geometry_device: every array a device pointer (int) or a torch tensor on the matcher's device; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(pair_geometry_args_c, dict(F=int(F), P=int(P), setup_type=int(setup_type), true_baseline=float(true_baseline)), dict(
-            pose=D(pose), median_depth=D(median_depth), pairs=D(pairs), out_skip=D(out_skip), out_epipolar=D(out_epipolar),
-            out_baseline=D(out_baseline)))
+        a = _struct(pair_geometry_args_c, dict(F=int(F), P=int(P), setup_type=int(setup_type), true_baseline=float(true_baseline)), dev_ptrs(
+            pose=pose, median_depth=median_depth, pairs=pairs, out_skip=out_skip, out_epipolar=out_epipolar, out_baseline=out_baseline))
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_keyframe_pair_geometry_device(self._h, C.byref(a), st))
+        self._device("plp_keyframe_pair_geometry_device", a, stream)
 
     @staticmethod
     def _keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr):
@@ -3387,17 +2550,10 @@ class matcher:
         sk = None if pair_skip is None else np.ascontiguousarray(pair_skip, np.uint8).reshape(Pn)
         o1 = None if occupied_1 is None else np.ascontiguousarray(occupied_1, np.uint8).reshape(Pn, M)
         o2 = None if occupied_2 is None else np.ascontiguousarray(occupied_2, np.uint8).reshape(Pn, M)
-        o = {}
-        for k, shape, dt, fill in (("idx_1", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 3), np.float64, 0), ("status", (Pn, M), np.uint8, 0)):
-            v = None if out is None else out.get(k)
-            if v is not None and not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == shape and v.flags.c_contiguous):
-                raise PlpError(PLP_ERR_INVALID_ARG, f"out[{k!r}] must be a C-contiguous {np.dtype(dt).name} array of shape {shape}")
-            o[k] = v if v is not None else np.full(shape, fill, dt)
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
-        a = _struct(keypoint_pairs_args_c, dict(F=F, cap=M, m_cap=Q, P=Pn), dict(
-            keypts=P(kp), bearings=P(be), x_right=P(xr), depths=P(de), counts=P(cn), pose=P(po), pairs=P(pr), match_q=P(mq), q_feature=P(qf),
-            pair_skip=P(sk), out_idx_1=P(o["idx_1"]), out_pos_w=P(o["pos_w"]), out_status=P(o["status"]), occupied_1_io=P(o1),
-            occupied_2_io=P(o2)))
+        o = out_arrays((("idx_1", (Pn, M), np.int32, -1), ("pos_w", (Pn, M, 3), np.float64, 0), ("status", (Pn, M), np.uint8, 0)), out)
+        a = _struct(keypoint_pairs_args_c, dict(F=F, cap=M, m_cap=Q, P=Pn), host_ptrs(
+            keypts=kp, bearings=be, x_right=xr, depths=de, counts=cn, pose=po, pairs=pr, match_q=mq, q_feature=qf, pair_skip=sk, out_idx_1=o["idx_1"],
+            out_pos_w=o["pos_w"], out_status=o["status"], occupied_1_io=o1, occupied_2_io=o2))
         keep = self._keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr)
         _check(lib().plp_triangulate_keypoint_pairs_host(self._h, C.byref(a)))
         del keep
@@ -3409,15 +2565,11 @@ class matcher:
                                           scale_factor=None, rays_parallax_deg_thr=1.0, stream=None):
         """plp_triangulate_keypoint_pairs_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors
         and level_sigma_sq are host vectors); asynchronous, one kernel on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(keypoint_pairs_args_c, dict(F=int(F), cap=int(cap), m_cap=int(m_cap), P=int(P)), dict(
-            keypts=D(keypts), bearings=D(bearings), x_right=D(x_right), depths=D(depths), counts=D(counts), pose=D(pose), pairs=D(pairs),
-            match_q=D(match_q), q_feature=D(q_feature), pair_skip=D(pair_skip), out_idx_1=D(out_idx_1), out_pos_w=D(out_pos_w),
-            out_status=D(out_status), occupied_1_io=D(occupied_1_io), occupied_2_io=D(occupied_2_io)))
+        a = _struct(keypoint_pairs_args_c, dict(F=int(F), cap=int(cap), m_cap=int(m_cap), P=int(P)), dev_ptrs(
+            keypts=keypts, bearings=bearings, x_right=x_right, depths=depths, counts=counts, pose=pose, pairs=pairs, match_q=match_q, q_feature=q_feature,
+            pair_skip=pair_skip, out_idx_1=out_idx_1, out_pos_w=out_pos_w, out_status=out_status, occupied_1_io=occupied_1_io, occupied_2_io=occupied_2_io))
         keep = self._keypoint_pairs_params(a, camera, setup_type, true_baseline, scale_factors, level_sigma_sq, scale_factor, rays_parallax_deg_thr)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_triangulate_keypoint_pairs_device(self._h, C.byref(a), st))
+        self._device("plp_triangulate_keypoint_pairs_device", a, stream)
         del keep
 
     def landmark_geometry(self, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, skip=None, counts=None, out=None):
@@ -3425,30 +2577,26 @@ class matcher:
         ref_kf (L,), skip (L,) u8 or None, the ragged observations obs_offsets (L + 1,) / obs_kf / obs_idx, scale_factors (num_levels,) f32.
         Returns dict(normal (L, 3) f64, min_dist / max_dist (L,) f32: the raw members, status (L,) u8: LG_*); the values are written where
         status is LG_UPDATED, elsewhere they keep 0 or out[name]."""
-        call = lambda a: _check(lib().plp_landmark_geometry_host(self._h, C.byref(a)))
-        return _landmark_geometry_host(call, False, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, None, skip, counts, out)
+        return _landmark_geometry_host(self._host("plp_landmark_geometry_host"), False, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx,
+                                       scale_factors, None, skip, counts, out)
 
     def landmark_line_geometry(self, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip=None,
                                counts=None, out=None):
         """Line::update_information for L line landmarks (plp_landmark_line_geometry_host): keylines (F, cap) KL_DTYPE, pos_w (L, 6),
         scale_factors the ORB table, scale_factors_lsd (num_levels_lsd,) the LSD table.  Returns dict(min_dist, max_dist, status)."""
-        call = lambda a: _check(lib().plp_landmark_line_geometry_host(self._h, C.byref(a)))
-        return _landmark_geometry_host(call, True, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, scale_factors, scale_factors_lsd, skip,
-                                       counts, out)
+        return _landmark_geometry_host(self._host("plp_landmark_line_geometry_host"), True, pose, keylines, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx,
+                                       scale_factors, scale_factors_lsd, skip, counts, out)
 
     def _landmark_geometry_device(self, lines, F, cap, L, pose, feats, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_mean_normal, out_min_valid_dist,
                                   out_max_valid_dist, out_status, scale_factors, scale_factors_lsd, skip, counts, stream):
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
         sl = np.ascontiguousarray(scale_factors_lsd, np.float32).reshape(-1) if lines else None    # both live until the call has returned
         a = _struct(landmark_geometry_args_c, dict(F=int(F), cap=int(cap), L=int(L), num_levels=len(sf), num_levels_lsd=len(sl) if lines else 0), dict(
-            pose=D(pose), counts=D(counts), keypts=None if lines else D(feats), keylines=D(feats) if lines else None, scale_factors=sf.ctypes.data,
-            scale_factors_lsd=sl.ctypes.data if lines else None, pos_w=D(pos_w), ref_kf=D(ref_kf), skip=D(skip), obs_offsets=D(obs_offsets),
-            obs_kf=D(obs_kf), obs_idx=D(obs_idx), out_mean_normal=D(out_mean_normal), out_min_valid_dist=D(out_min_valid_dist),
-            out_max_valid_dist=D(out_max_valid_dist), out_status=D(out_status)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check((lib().plp_landmark_line_geometry_device if lines else lib().plp_landmark_geometry_device)(self._h, C.byref(a), st))
+            dev_ptrs(pose=pose, counts=counts, keypts=None if lines else feats, keylines=feats if lines else None, pos_w=pos_w, ref_kf=ref_kf, skip=skip,
+                     obs_offsets=obs_offsets, obs_kf=obs_kf, obs_idx=obs_idx, out_mean_normal=out_mean_normal, out_min_valid_dist=out_min_valid_dist,
+                     out_max_valid_dist=out_max_valid_dist, out_status=out_status),
+            scale_factors=sf.ctypes.data, scale_factors_lsd=sl.ctypes.data if lines else None))
+        self._device("plp_landmark_line_geometry_device" if lines else "plp_landmark_geometry_device", a, stream)
 
     def landmark_geometry_device(self, F, cap, L, pose, keypts, pos_w, ref_kf, obs_offsets, obs_kf, obs_idx, out_mean_normal, out_min_valid_dist,
                                  out_max_valid_dist, out_status, scale_factors, skip=None, counts=None, stream=None):
@@ -3470,29 +2618,23 @@ class matcher:
         indices of common points or None = drawn from seed, counts (P,) or None.  Returns dict(status (P,) u8: SIM3_*, num_common, rot_12
         (P, 3, 3), trans_12 (P, 3), scale_12 (P,) f32, num_inliers, best_iter, inliers (P, n_cap) u8, hyp_inliers (P, iters)); `outputs` names
         the optional ones wanted (default both); out[name]: the caller's array."""
-        call = lambda a: _check(lib().plp_sim3_ransac_host(self._h, C.byref(a)))
-        return _sim3_ransac_host(call, camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, iters,
-                                 fix_scale, min_num_inliers, samples, seed, counts, outputs, out)
+        return _sim3_ransac_host(self._host("plp_sim3_ransac_host"), camera, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1,
+                                 level_sigma_sq_2, iters, fix_scale, min_num_inliers, samples, seed, counts, outputs, out)
 
     def sim3_ransac_device(self, camera, P, n_cap, valid, pos_w_1, pos_w_2, octave_1, octave_2, pose_1, pose_2, level_sigma_sq_1, level_sigma_sq_2, out,
                            iters=200, fix_scale=False, min_num_inliers=20, samples=None, seed=0, counts=None, stream=None):
         """plp_sim3_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device (the sigma tables are host
         vectors); out: dict of the device outputs named as in SIM3_OUTPUTS (inliers / hyp_inliers may be absent); asynchronous, three kernels
         on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         s1 = np.ascontiguousarray(level_sigma_sq_1, np.float32).reshape(-1)
         s2 = np.ascontiguousarray(level_sigma_sq_2, np.float32).reshape(-1)        # both live until the call has returned
         a = _struct(sim3_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), fix_scale=int(bool(fix_scale)), min_num_inliers=int(min_num_inliers),
                                              iters=int(iters), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=min(len(s1), len(s2))), dict(
-            level_sigma_sq_1=s1.ctypes.data if len(s1) else None, level_sigma_sq_2=s2.ctypes.data if len(s2) else None, counts=D(counts), valid=D(valid),
-            pos_w_1=D(pos_w_1), pos_w_2=D(pos_w_2), octave_1=D(octave_1), octave_2=D(octave_2), pose_1=D(pose_1), pose_2=D(pose_2), samples=D(samples),
-            out_status=D(out.get("status")), out_num_common=D(out.get("num_common")), out_rot_12=D(out.get("rot_12")), out_trans_12=D(out.get("trans_12")),
-            out_scale_12=D(out.get("scale_12")), out_num_inliers=D(out.get("num_inliers")), out_best_iter=D(out.get("best_iter")),
-            out_inliers=D(out.get("inliers")), out_hyp_inliers=D(out.get("hyp_inliers"))))
+            dev_ptrs(counts=counts, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, octave_1=octave_1, octave_2=octave_2, pose_1=pose_1, pose_2=pose_2,
+                     samples=samples), level_sigma_sq_1=host_ptr(s1), level_sigma_sq_2=host_ptr(s2)))
+        set_outputs(a, SIM3_OUTPUTS, out, dev_ptr)
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_sim3_ransac_device(self._h, C.byref(a), st))
+        self._device("plp_sim3_ransac_device", a, stream)
 
     def plane_ransac(self, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac=18, min_points_before_ransac=12, iters=50,
                      inliers_ratio_thr=0.7, best_error_in=None, equation_in=None, samples=None, seed=0, counts=None, outputs=None, out=None):
@@ -3502,9 +2644,8 @@ class matcher:
         the eligible slots or None = drawn from seed, counts (P,) or None.  Returns dict(status (P,) u8: PLANE_*, flags: PLANE_FLAG_*, equation
         (P, 4), best_error, best_iter, last_iter, num_inliers, inliers (P, n_cap) u8, hyp_residual / hyp_inliers / hyp_error (P, iters));
         `outputs` names the optional ones wanted (default all); out[name]: the caller's array."""
-        call = lambda a: _check(lib().plp_plane_ransac_host(self._h, C.byref(a)))
-        return _plane_ransac_host(call, mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac, min_points_before_ransac, iters,
-                                  inliers_ratio_thr, best_error_in, equation_in, samples, seed, counts, outputs, out)
+        return _plane_ransac_host(self._host("plp_plane_ransac_host"), mode, pos_w, flags, dist_thresh, error_thresh, points_per_ransac,
+                                  min_points_before_ransac, iters, inliers_ratio_thr, best_error_in, equation_in, samples, seed, counts, outputs, out)
 
     def plane_ransac_device(self, mode, P, n_cap, pos_w, flags, dist_thresh, error_thresh, out, points_per_ransac=18, min_points_before_ransac=12,
                             iters=50, inliers_ratio_thr=0.7, best_error_in=None, equation_in=None, samples=None, m_cap=0, seed=0, counts=None,
@@ -3512,32 +2653,26 @@ class matcher:
         """plp_plane_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device, the thresholds (P,) f64
         included; out: dict of the device outputs named as in PLANE_RANSAC_OUTPUTS (the hyp_* ones may be absent); asynchronous, two kernels
         on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(plane_ransac_args_c, dict(mode=int(mode), P=int(P), n_cap=int(n_cap), points_per_ransac=int(points_per_ransac),
                                               min_points_before_ransac=int(min_points_before_ransac), iters=int(iters),
-                                              inliers_ratio_thr=float(inliers_ratio_thr), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=int(m_cap)), dict(
-            counts=D(counts), pos_w=D(pos_w), flags=D(flags), dist_thresh=D(dist_thresh), error_thresh=D(error_thresh), best_error_in=D(best_error_in),
-            equation_in=D(equation_in), samples=D(samples), **{"out_" + k: D(out.get(k)) for k in PLANE_RANSAC_OUTPUTS}))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_plane_ransac_device(self._h, C.byref(a), st))
+                                              inliers_ratio_thr=float(inliers_ratio_thr), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, m_cap=int(m_cap)), dev_ptrs(
+            counts=counts, pos_w=pos_w, flags=flags, dist_thresh=dist_thresh, error_thresh=error_thresh, best_error_in=best_error_in, equation_in=equation_in,
+            samples=samples))
+        set_outputs(a, PLANE_RANSAC_OUTPUTS, out, dev_ptr)
+        self._device("plp_plane_ransac_device", a, stream)
 
     def plane_refine_points(self, pos_w, lm_plane, flags, equation, active, dist_thresh):
         """Planar_Mapping_module::refine_points over a landmark list (plp_plane_refine_points_host): pos_w (M, 3) f64, lm_plane (M,) plane
         rows or -1, flags (M,) u8 of PLANE_LM_*, equation (NP, 4), active (NP,) u8, dist_thresh a number.  Returns (the new pos_w, changed
         (M,) u8)."""
-        call = lambda a: _check(lib().plp_plane_refine_points_host(self._h, C.byref(a)))
-        return _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh)
+        return _plane_refine_host(self._host("plp_plane_refine_points_host"), pos_w, lm_plane, flags, equation, active, dist_thresh)
 
     def plane_refine_points_device(self, M, NP, pos_w, lm_plane, flags, equation, active, dist_thresh, out_changed, stream=None):
         """plp_plane_refine_points_device: device pointers (int) or torch tensors, dist_thresh one f64 on the device; pos_w is updated in
         place; asynchronous, one kernel on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(plane_refine_args_c, dict(M=int(M), NP=int(NP)), dict(pos_w=D(pos_w), lm_plane=D(lm_plane), flags=D(flags), equation=D(equation),
-                                                                          active=D(active), dist_thresh=D(dist_thresh), out_changed=D(out_changed)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_plane_refine_points_device(self._h, C.byref(a), st))
+        a = _struct(plane_refine_args_c, dict(M=int(M), NP=int(NP)), dev_ptrs(pos_w=pos_w, lm_plane=lm_plane, flags=flags, equation=equation, active=active,
+                                                                              dist_thresh=dist_thresh, out_changed=out_changed))
+        self._device("plp_plane_refine_points_device", a, stream)
 
     def pnp_ransac(self, valid, bearing, pos_w, octave, scale_factors, iters=30, min_num_inliers=10, recompute=True, samples=None, seed=0, counts=None,
                    outputs=None, out=None):
@@ -3545,24 +2680,19 @@ class matcher:
         (P, n_cap, 3) f64, octave (P, n_cap), scale_factors (num_levels,) f32, samples (P, iters, 4) indices of matches or None = drawn from
         seed, counts (P,) or None.  Returns dict(status (P,) u8: PNP_*, num_matches, rot_cw (P, 3, 3), trans_cw (P, 3), num_inliers, best_iter,
         inliers (P, n_cap) u8, hyp_inliers (P, iters)); `outputs` names the optional ones wanted (default both); out[name]: the caller's array."""
-        call = lambda a: _check(lib().plp_pnp_ransac_host(self._h, C.byref(a)))
-        return _pnp_ransac_host(call, valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples, seed, counts, outputs, out)
+        return _pnp_ransac_host(self._host("plp_pnp_ransac_host"), valid, bearing, pos_w, octave, scale_factors, iters, min_num_inliers, recompute, samples,
+                                seed, counts, outputs, out)
 
     def pnp_ransac_device(self, P, n_cap, valid, bearing, pos_w, octave, scale_factors, out, iters=30, min_num_inliers=10, recompute=True, samples=None,
                           seed=0, counts=None, stream=None):
         """plp_pnp_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device (scale_factors is a host vector);
         out: dict of the device outputs named as in PNP_OUTPUTS (inliers / hyp_inliers may be absent); asynchronous, five kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         sf = np.ascontiguousarray(scale_factors, np.float32).reshape(-1)           # lives until the call has returned
         a = _struct(pnp_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), min_num_inliers=int(min_num_inliers), iters=int(iters),
                                             recompute=int(bool(recompute)), seed=int(seed) & 0xFFFFFFFFFFFFFFFF, num_levels=len(sf)), dict(
-            scale_factors=sf.ctypes.data if len(sf) else None, counts=D(counts), valid=D(valid), bearing=D(bearing), pos_w=D(pos_w), octave=D(octave),
-            samples=D(samples), out_status=D(out.get("status")), out_num_matches=D(out.get("num_matches")), out_rot_cw=D(out.get("rot_cw")),
-            out_trans_cw=D(out.get("trans_cw")), out_num_inliers=D(out.get("num_inliers")), out_best_iter=D(out.get("best_iter")),
-            out_inliers=D(out.get("inliers")), out_hyp_inliers=D(out.get("hyp_inliers"))))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_pnp_ransac_device(self._h, C.byref(a), st))
+            dev_ptrs(counts=counts, valid=valid, bearing=bearing, pos_w=pos_w, octave=octave, samples=samples), scale_factors=host_ptr(sf)))
+        set_outputs(a, PNP_OUTPUTS, out, dev_ptr)
+        self._device("plp_pnp_ransac_device", a, stream)
 
     def pose_optimize(self, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, num_trials=4,
                       num_each_iter=10, outputs=None, out=None):
@@ -3573,9 +2703,8 @@ class matcher:
         dict(status (B,) u8: POSE_OPT_*, pose (B, 15), num_init_obs, num_valid, outlier (B, n_cap) u8, outlier_lines (B, l_cap), trial_info
         (B, num_trials, 4), trial_chi2 (B, num_trials, 2)); `outputs` names the optional ones wanted (default both); out[name]: the caller's array
         (slots the reference does not write keep their values)."""
-        call = lambda a: _check(lib().plp_pose_optimize_host(self._h, C.byref(a)))
-        return _pose_optimize_host(call, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts, lines, num_trials,
-                                   num_each_iter, outputs, out)
+        return _pose_optimize_host(self._host("plp_pose_optimize_host"), camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right, counts,
+                                   lines, num_trials, num_each_iter, outputs, out)
 
     def pose_optimize_device(self, camera, setup_type, B, n_cap, pose_in, valid, undist, pos_w, inv_level_sigma_sq, out, x_right=None, counts=None,
                              l_cap=0, line_valid=None, keylines=None, pos_w_lines=None, inv_level_sigma_sq_lsd=None, line_counts=None, num_trials=4,
@@ -3583,21 +2712,17 @@ class matcher:
         """plp_pose_optimize_device: every array a device pointer (int) or a torch tensor on the matcher's device (the two sigma tables are host
         vectors); out: dict of the device outputs named as in POSE_OPT_OUTPUTS (trial_info / trial_chi2 may be absent, outlier_lines when l_cap
         is 0); asynchronous, two kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)           # live until the call has returned
         sl = None if inv_level_sigma_sq_lsd is None else np.ascontiguousarray(inv_level_sigma_sq_lsd, np.float32).reshape(-1)
         a = _struct(pose_optimize_args_c, dict(setup_type=int(setup_type), B=int(B), n_cap=int(n_cap), l_cap=int(l_cap), num_trials=int(num_trials),
                                                num_each_iter=int(num_each_iter), pose_stride=int(pose_stride), num_levels=len(sg),
                                                num_levels_lsd=0 if sl is None else len(sl)), dict(
-            inv_level_sigma_sq=sg.ctypes.data if len(sg) else None, inv_level_sigma_sq_lsd=None if sl is None or not len(sl) else sl.ctypes.data,
-            pose_in=D(pose_in), counts=D(counts), line_counts=D(line_counts), valid=D(valid), undist=D(undist), x_right=D(x_right), pos_w=D(pos_w),
-            line_valid=D(line_valid), keylines=D(keylines), pos_w_lines=D(pos_w_lines)))
-        for k in POSE_OPT_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
+            dev_ptrs(pose_in=pose_in, counts=counts, line_counts=line_counts, valid=valid, undist=undist, x_right=x_right, pos_w=pos_w, line_valid=line_valid,
+                     keylines=keylines, pos_w_lines=pos_w_lines), inv_level_sigma_sq=host_ptr(sg),
+            inv_level_sigma_sq_lsd=host_ptr(sl)))
+        set_outputs(a, POSE_OPT_OUTPUTS, out, dev_ptr)
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_pose_optimize_device(self._h, C.byref(a), st))
+        self._device("plp_pose_optimize_device", a, stream)
 
     def transform_optimize(self, camera, fix_scale, valid, pos_w_1, pos_w_2, undist_1, undist_2, pose_1, pose_2, rot_12, trans_12, scale_12,
                            inv_level_sigma_sq_1, inv_level_sigma_sq_2, counts=None, num_iter=10, chi_sq=10.0, outputs=None, out=None):
@@ -3606,7 +2731,7 @@ class matcher:
         sigma tables (num_levels,) f32, counts (P,) or None.  Returns dict(status (P,) u8: TRANSFORM_OPT_*, num_valid, num_inliers, rot_12, trans_12,
         scale_12 (P,) f64, world_to_1 (P, 13), kept (P, n_cap) u8, round_info (P, 2, 4), round_chi2 (P, 2, 2)); `outputs` names the optional ones wanted
         (default all); out[name]: the caller's array (slots the reference does not write keep their values)."""
-        call = lambda a: _check(lib().plp_transform_optimize_host(self._h, C.byref(a)))
+        call = self._host("plp_transform_optimize_host")
         inputs = dict(camera=camera, fix_scale=fix_scale, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1,
                       pose_2=pose_2, rot_12=rot_12, trans_12=trans_12, scale_12=scale_12, inv_level_sigma_sq_1=inv_level_sigma_sq_1,
                       inv_level_sigma_sq_2=inv_level_sigma_sq_2, counts=counts, num_iter=num_iter, chi_sq=chi_sq)
@@ -3617,22 +2742,17 @@ class matcher:
         """plp_transform_optimize_device: every array a device pointer (int) or a torch tensor on the matcher's device (the two sigma tables are host
         vectors); out: dict of the device outputs named as in TRANSFORM_OPT_OUTPUTS (world_to_1 / round_info / round_chi2 may be absent); asynchronous,
         three kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         s1 = np.ascontiguousarray(inv_level_sigma_sq_1, np.float32).reshape(-1)         # live until the call has returned
         s2 = np.ascontiguousarray(inv_level_sigma_sq_2, np.float32).reshape(-1)
         if len(s1) != len(s2):
             raise PlpError(PLP_ERR_INVALID_ARG, "the two sigma tables must have one length")
         a = _struct(transform_optimize_args_c, dict(fix_scale=int(bool(fix_scale)), num_iter=int(num_iter), chi_sq=float(chi_sq), P=int(P), n_cap=int(n_cap),
                                                     num_levels=len(s1)), dict(
-            inv_level_sigma_sq_1=s1.ctypes.data if len(s1) else None, inv_level_sigma_sq_2=s2.ctypes.data if len(s2) else None, counts=D(counts), valid=D(valid),
-            pos_w_1=D(pos_w_1), pos_w_2=D(pos_w_2), undist_1=D(undist_1), undist_2=D(undist_2), pose_1=D(pose_1), pose_2=D(pose_2), rot_12=D(rot_12),
-            trans_12=D(trans_12), scale_12=D(scale_12)))
-        for k in TRANSFORM_OPT_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
+            dev_ptrs(counts=counts, valid=valid, pos_w_1=pos_w_1, pos_w_2=pos_w_2, undist_1=undist_1, undist_2=undist_2, pose_1=pose_1, pose_2=pose_2,
+                     rot_12=rot_12, trans_12=trans_12, scale_12=scale_12), inv_level_sigma_sq_1=host_ptr(s1), inv_level_sigma_sq_2=host_ptr(s2)))
+        set_outputs(a, TRANSFORM_OPT_OUTPUTS, out, dev_ptr)
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_transform_optimize_device(self._h, C.byref(a), st))
+        self._device("plp_transform_optimize_device", a, stream)
 
     def local_ba(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right=None, counts=None,
                  kf_erased=None, kf_is_origin=None, lm_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
@@ -3642,28 +2762,23 @@ class matcher:
         and lm_erased (L,) u8 or None.  Returns dict(status (G,) u8: LOCAL_BA_*, kf_role (G, F), lm_role (G, L), pose (G, F, 15), pos_w (G, L, 3),
         outlier (G, T), round_info (G, 2, 4), round_chi2 (G, 2, 2)); `outputs` names the optional ones wanted (default all); out[name]: the caller's
         array (slots the adjuster does not write keep their values)."""
-        call = lambda a: _check(lib().plp_local_ba_host(self._h, C.byref(a)))
-        return _local_ba_host(call, _local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right,
-                                                 counts, kf_erased, kf_is_origin, lm_erased, num_first_iter, num_second_iter), outputs, out)
+        return _local_ba_host(self._host("plp_local_ba_host"), _local_ba_kw(
+            camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts, kf_erased, kf_is_origin,
+            lm_erased, num_first_iter, num_second_iter), outputs, out)
 
     def local_ba_device(self, camera, setup_type, G, F, L, T, kp_stride, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, out,
                         x_right=None, counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None, pose_stride=15, num_first_iter=5, num_second_iter=10,
                         stream=None):
         """plp_local_ba_device: every array a device pointer (int) or a torch tensor on the matcher's device (the sigma table is a host vector); out: dict
         of the device outputs named as in LOCAL_BA_OUTPUTS (round_info / round_chi2 may be absent); asynchronous, three kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)             # live until the call has returned
         a = _struct(local_ba_args_c, dict(setup_type=int(setup_type), num_first_iter=int(num_first_iter), num_second_iter=int(num_second_iter), G=int(G), F=int(F),
                                           L=int(L), T=int(T), kp_stride=int(kp_stride), pose_stride=int(pose_stride), num_levels=len(sg)), dict(
-            inv_level_sigma_sq=sg.ctypes.data if len(sg) else None, pose=D(pose), kf_erased=D(kf_erased), kf_is_origin=D(kf_is_origin), undist=D(undist),
-            x_right=D(x_right), counts=D(counts), pos_w=D(pos_w), lm_erased=D(lm_erased), obs_offsets=D(obs_offsets), obs_kf=D(obs_kf), obs_idx=D(obs_idx),
-            kf_local=D(kf_local)))
-        for k in LOCAL_BA_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
+            dev_ptrs(pose=pose, kf_erased=kf_erased, kf_is_origin=kf_is_origin, undist=undist, x_right=x_right, counts=counts, pos_w=pos_w,
+                     lm_erased=lm_erased, obs_offsets=obs_offsets, obs_kf=obs_kf, obs_idx=obs_idx, kf_local=kf_local), inv_level_sigma_sq=host_ptr(sg)))
+        set_outputs(a, LOCAL_BA_OUTPUTS, out, dev_ptr)
         a.camera = camera_model_c.from_buffer_copy(camera)
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_local_ba_device(self._h, C.byref(a), st))
+        self._device("plp_local_ba_device", a, stream)
 
     def pose_graph_optimize(self, tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV, max_iter=50, outputs=None, out=None):
         """optimize::graph_optimizer::optimize for G problems over one key-frame table (plp_pose_graph_optimize_host; DESIGN.md section 5, D22): tables a dict of
@@ -3671,39 +2786,30 @@ class matcher:
         (F + 1,) / kf_loop; kf_erased, kf_id (default: the row) optional), problems a list of dicts (pose_graph_problems) or its arrays.  Returns dict(status (G,)
         u8: POSE_GRAPH_*, num_edges (G,), edges (G, edge_cap, 3), sim3_cw, corrected_wc (G, F, 8), pose (G, F, 15), info (G, 4), chi2 (G, 2)); `outputs` names
         the optional ones wanted (default all); out[name]: the caller's array (slots the optimizer does not write keep their values)."""
-        call = lambda a: _check(lib().plp_pose_graph_optimize_host(self._h, C.byref(a)))
-        return _pose_graph_host(call, tables, problems, edge_cap, env_cap, max_iter, outputs, out)
+        return _pose_graph_host(self._host("plp_pose_graph_optimize_host"), tables, problems, edge_cap, env_cap, max_iter, outputs, out)
 
     def pose_graph_optimize_device(self, G, F, tables, problems, out, conn_cap, covis_cap, edge_cap, env_cap, pose_stride=15, max_iter=50, stream=None):
         """plp_pose_graph_optimize_device: tables / problems: dicts of device pointers (int) or torch tensors on the matcher's device named as POSE_GRAPH_TABLES and
         as pose_graph_problems() names them; out: dict of the device outputs named as in POSE_GRAPH_OUTPUTS (all but status may be absent); asynchronous, three
         kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(pose_graph_args_c, dict(G=int(G), F=int(F), pose_stride=int(pose_stride), conn_cap=int(conn_cap), covis_cap=int(covis_cap), edge_cap=int(edge_cap),
-                                            env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: D(tables.get(k)) for k in POSE_GRAPH_TABLES},
-                                                                                            **{k: D(v) for k, v in problems.items()}})
-        for k in POSE_GRAPH_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_pose_graph_optimize_device(self._h, C.byref(a), st))
+                                            env_cap=int(env_cap), max_iter=int(max_iter)), {**{k: dev_ptr(tables.get(k)) for k in POSE_GRAPH_TABLES},
+                                                                                            **{k: dev_ptr(v) for k, v in problems.items()}})
+        set_outputs(a, POSE_GRAPH_OUTPUTS, out, dev_ptr)
+        self._device("plp_pose_graph_optimize_device", a, stream)
 
     def correct_landmarks(self, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased=None, kf_erased=None, out=None):
         """The landmark half of graph_optimizer::optimize (:331-350; plp_correct_landmarks_host): pos_w (L, 3), ref_kf (L,) the row each landmark is corrected
         with, sim3_cw / corrected_wc (F, 8) one problem's outputs of pose_graph_optimize.  Returns dict(pos_w (L, 3), status (L,) u8: CORRECT_LM_*); out[name]:
         the caller's array (a landmark that is not corrected keeps its slot)."""
-        call = lambda a: _check(lib().plp_correct_landmarks_host(self._h, C.byref(a)))
-        return _correct_landmarks_host(call, pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
+        return _correct_landmarks_host(self._host("plp_correct_landmarks_host"), pos_w, ref_kf, sim3_cw, corrected_wc, lm_erased, kf_erased, out)
 
     def correct_landmarks_device(self, L, F, pos_w, ref_kf, sim3_cw, corrected_wc, out_pos_w, out_status, lm_erased=None, kf_erased=None, stream=None):
         """plp_correct_landmarks_device: device pointers (int) or torch tensors; out_pos_w may be pos_w; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(correct_landmarks_args_c, dict(L=int(L), F=int(F)), dict(pos_w=D(pos_w), lm_erased=D(lm_erased), ref_kf=D(ref_kf), kf_erased=D(kf_erased),
-                                                                            sim3_cw=D(sim3_cw), corrected_wc=D(corrected_wc), out_pos_w=D(out_pos_w),
-                                                                            out_status=D(out_status)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_correct_landmarks_device(self._h, C.byref(a), st))
+        a = _struct(correct_landmarks_args_c, dict(L=int(L), F=int(F)), dev_ptrs(pos_w=pos_w, lm_erased=lm_erased, ref_kf=ref_kf, kf_erased=kf_erased,
+                                                                                 sim3_cw=sim3_cw, corrected_wc=corrected_wc, out_pos_w=out_pos_w,
+                                                                                 out_status=out_status))
+        self._device("plp_correct_landmarks_device", a, stream)
 
     def local_map(self, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap=0, kf_erased=None,
                   kf_counts=None, kf_lm_lines=None, kf_kl_counts=None, lm_erased=None, lm_erased_lines=None, LL=None, frm_counts=None, frm_lm_lines=None,
@@ -3714,23 +2820,18 @@ class matcher:
         None.  Returns dict(status (B,) u8: LOCAL_MAP_*, num_first, num_kf, nearest_kf, num_lm (B,), local_kf, first_weight (B, k_cap), local_lm, held
         (B, m_cap) and, with lines, num_lines, local_lines, held_lines); `outputs` names the optional ones wanted (default all); out[name]: the caller's
         array (slots the updater does not write keep their values)."""
-        call = lambda a: _check(lib().plp_local_map_host(self._h, C.byref(a)))
-        return _local_map_host(call, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap, kf_erased,
-                               kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines, frm_kl_counts,
-                               max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
+        return _local_map_host(self._host("plp_local_map_host"), kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm,
+                               k_cap, m_cap, ml_cap, kf_erased, kf_counts, kf_lm_lines, kf_kl_counts, lm_erased, lm_erased_lines, LL, frm_counts, frm_lm_lines,
+                               frm_kl_counts, max_num_local_keyfrms, workspace_bytes, fcap, flcap, outputs, out)
 
     def local_map_device(self, dims, tables, out, max_num_local_keyfrms=60, workspace_bytes=0, stream=None):
         """plp_local_map_device: dims a dict of the struct's sizes (B, F, C, L, LL, T, cap, lcap, fcap, flcap, k_cap, m_cap, ml_cap and optionally
         frm_stride, frm_stride_lines); tables a dict of LOCAL_MAP_INPUTS and out a dict of LOCAL_MAP_OUTPUTS, each a device pointer (int), a torch
         tensor on the matcher's device or absent / None; asynchronous on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(local_map_args_c, dict({k: int(v) for k, v in dims.items()}, max_num_local_keyfrms=int(max_num_local_keyfrms),
-                                           workspace_bytes=int(workspace_bytes)), {k: D(tables.get(k)) for k in LOCAL_MAP_INPUTS})
-        for k in LOCAL_MAP_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_local_map_device(self._h, C.byref(a), st))
+                                           workspace_bytes=int(workspace_bytes)), {k: dev_ptr(tables.get(k)) for k in LOCAL_MAP_INPUTS})
+        set_outputs(a, LOCAL_MAP_OUTPUTS, out, dev_ptr)
+        self._device("plp_local_map_device", a, stream)
 
     def cull_keyframes(self, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id=0, is_monocular=True,
                        kf_counts=None, x_right=None, depths=None, depth_thr=None, kf_erased=None, kf_cannot_erase=None, lm_erased=None, lm_num_obs=None,
@@ -3740,22 +2841,18 @@ class matcher:
         (G,) rows, covis_offsets (G + 1,) into covis (Cv,) rows; x_right / depths (F, kp_stride) f32, depth_thr (F,) f32, the byte tables and lm_num_obs
         (L,) u32 or None.  Returns dict(num_removed (G,), decision (Cv,) u8: CULL_KF_*, num_valid, num_redundant (Cv,), kf_removed (G, F), lm_erased
         (G, L)); `outputs` names the optional ones wanted (default all); out[name]: the caller's array (unwritten slots keep their values)."""
-        call = lambda a: _check(lib().plp_cull_keyframes_host(self._h, C.byref(a)))
-        return _cull_keyframes_host(call, kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis, origin_id, is_monocular,
-                                    kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs, out)
+        return _cull_keyframes_host(self._host("plp_cull_keyframes_host"), kf_lm, undist, kf_id, obs_offsets, obs_kf, obs_idx, cur_kf, covis_offsets, covis,
+                                    origin_id, is_monocular, kf_counts, x_right, depths, depth_thr, kf_erased, kf_cannot_erase, lm_erased, lm_num_obs, outputs,
+                                    out)
 
     def cull_keyframes_device(self, dims, tables, out, origin_id=0, is_monocular=True, stream=None):
         """plp_cull_keyframes_device: dims a dict of the struct's sizes (F, L, T, cap, G, Cv and optionally kp_stride); tables a dict of
         CULL_KEYFRAMES_INPUTS and out a dict of CULL_KEYFRAMES_OUTPUTS, each a device pointer (int), a torch tensor on the matcher's device or
         absent / None; asynchronous on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(cull_keyframes_args_c, dict({k: int(v) for k, v in dims.items()}, origin_id=int(origin_id), is_monocular=int(bool(is_monocular))),
-                    {k: D(tables.get(k)) for k in CULL_KEYFRAMES_INPUTS})
-        for k in CULL_KEYFRAMES_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_cull_keyframes_device(self._h, C.byref(a), st))
+                    {k: dev_ptr(tables.get(k)) for k in CULL_KEYFRAMES_INPUTS})
+        set_outputs(a, CULL_KEYFRAMES_OUTPUTS, out, dev_ptr)
+        self._device("plp_cull_keyframes_device", a, stream)
 
     def cull_landmarks(self, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased=None,
                        owning_plane=None, out=None):
@@ -3763,20 +2860,15 @@ class matcher:
         (N,) landmark rows; num_observed, num_observable, first_kf_id, num_obs (L,) u32; cur_kf_id, num_obs_thr (R,) u32; lm_erased, owning_plane (L,)
         u8 or None.  Returns dict(state (N,) u8: CULL_HOLD / CULL_DROP / CULL_ERASE, num_removed, num_fresh (R,), fresh (N,): the HOLD entries of
         list r in order from fresh_offsets[r] on)."""
-        call = lambda a: _check(lib().plp_cull_landmarks_host(self._h, C.byref(a)))
-        return _cull_landmarks_host(call, fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id, num_obs_thr, lm_erased,
-                                    owning_plane, out)
+        return _cull_landmarks_host(self._host("plp_cull_landmarks_host"), fresh_offsets, fresh, num_observed, num_observable, first_kf_id, num_obs, cur_kf_id,
+                                    num_obs_thr, lm_erased, owning_plane, out)
 
     def cull_landmarks_device(self, dims, tables, out, stream=None):
         """plp_cull_landmarks_device: dims dict(R, N, L); tables a dict of CULL_LANDMARKS_INPUTS and out a dict of CULL_LANDMARKS_OUTPUTS, device
         pointers (int) or torch tensors; asynchronous, one kernel on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        a = _struct(cull_landmarks_args_c, {k: int(v) for k, v in dims.items()}, {k: D(tables.get(k)) for k in CULL_LANDMARKS_INPUTS})
-        for k in CULL_LANDMARKS_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_cull_landmarks_device(self._h, C.byref(a), st))
+        a = _struct(cull_landmarks_args_c, {k: int(v) for k, v in dims.items()}, {k: dev_ptr(tables.get(k)) for k in CULL_LANDMARKS_INPUTS})
+        set_outputs(a, CULL_LANDMARKS_OUTPUTS, out, dev_ptr)
+        self._device("plp_cull_landmarks_device", a, stream)
 
     def covisibility_update(self, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts=None, lm_erased=None, outputs=None, out=None):
         """graph_node::update_connections of the key frames `owners` (G,), as if one after another in list order, over one map snapshot
@@ -3785,39 +2877,30 @@ class matcher:
         makes empty ones), updated in place.  Returns dict(status (G,) u8: COVIS_*, nearest, max_weight (G,), touched (F,) u8); `outputs` names
         the optional ones wanted (default all); out[name]: the caller's array (unwritten slots keep their values).  A list that names a key
         frame twice is refused."""
-        call = lambda a: _check(lib().plp_covisibility_update_host(self._h, C.byref(a)))
-        return _covisibility_update_host(call, kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased, outputs, out)
+        return _covisibility_update_host(self._host("plp_covisibility_update_host"), kf_lm, obs_offsets, obs_kf, kf_id, state, owners, kf_counts, lm_erased,
+                                         outputs, out)
 
     def covisibility_update_device(self, dims, tables, out, stream=None):
         """plp_covisibility_update_device: dims a dict of the struct's sizes (F, L, T, cap, conn_cap, covis_cap, G); tables a dict of
         COVISIBILITY_INPUTS and COVISIBILITY_STATE (updated in place) and out a dict of COVISIBILITY_OUTPUTS, each a device pointer (int), a torch
         tensor on the matcher's device or absent / None; asynchronous on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(covisibility_update_args_c, {k: int(v) for k, v in dims.items()},
-                    {k: D(tables.get(k)) for k in COVISIBILITY_INPUTS + tuple(COVISIBILITY_STATE)})
-        for k in COVISIBILITY_OUTPUTS:
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_covisibility_update_device(self._h, C.byref(a), st))
+                    {k: dev_ptr(tables.get(k)) for k in COVISIBILITY_INPUTS + tuple(COVISIBILITY_STATE)})
+        set_outputs(a, COVISIBILITY_OUTPUTS, out, dev_ptr)
+        self._device("plp_covisibility_update_device", a, stream)
 
     def covisibility_erase(self, state, erased, out=None):
         """graph_node::erase_all_connections of every key frame with erased[k] != 0 (plp_covisibility_erase_host; D21): state as for
         covisibility_update (the six connection tables), erased (F,) u8.  Returns dict(status (F,) u8, touched (F,) u8)."""
-        call = lambda a: _check(lib().plp_covisibility_erase_host(self._h, C.byref(a)))
-        return _covisibility_erase_host(call, state, erased, out)
+        return _covisibility_erase_host(self._host("plp_covisibility_erase_host"), state, erased, out)
 
     def covisibility_erase_device(self, dims, tables, out, stream=None):
         """plp_covisibility_erase_device: dims dict(F, conn_cap, covis_cap); tables the six connection tables and `erased`, out dict(status,
         touched), device pointers (int) or torch tensors; asynchronous, two launches on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(covisibility_erase_args_c, {k: int(v) for k, v in dims.items()},
-                    {k: D(tables.get(k)) for k in COVISIBILITY_ERASE_STATE + ("erased",)})
-        for k in ("status", "touched"):
-            setattr(a, "out_" + k, D(out.get(k)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_covisibility_erase_device(self._h, C.byref(a), st))
+                    {k: dev_ptr(tables.get(k)) for k in COVISIBILITY_ERASE_STATE + ("erased",)})
+        set_outputs(a, ("status", "touched"), out, dev_ptr)
+        self._device("plp_covisibility_erase_device", a, stream)
 
     def bow_query(self, n_words, db_word, db_value, db_n, q_word, q_value, q_n, db_alive=None, reject=None, min_score=None, covis=None, n_covis=None,
                   scoring=0, outputs=None):
@@ -3840,11 +2923,10 @@ class matcher:
             raise PlpError(PLP_ERR_INVALID_ARG, "covis must be (N, covis_cap)")
         nc = None if covis is None else np.ascontiguousarray(n_covis, np.int32).reshape(N)
         o = {k: np.zeros((Q, N) if rows else (Q,), dt) for k, (rows, dt) in BOW_QUERY_OUTPUTS.items() if outputs is None or k in outputs}
-        P = lambda v: None if v is None or v.size == 0 else v.ctypes.data
         a = _struct(bow_query_args_c, dict(scoring=int(scoring), n_words=int(n_words), N=N, stride=stride, Q=Q, q_stride=q_stride,
                                            covis_cap=0 if cv is None else cv.shape[1]),
-                    dict(db_word=P(dw), db_value=P(dv), db_n=P(dn), db_alive=P(al), q_word=P(qw), q_value=P(qv), q_n=P(qn), reject=P(rj), min_score=P(ms),
-                         covis=P(cv), n_covis=P(nc), **{"out_" + k: P(v) for k, v in o.items()}))
+                    host_ptrs(db_word=dw, db_value=dv, db_n=dn, db_alive=al, q_word=qw, q_value=qv, q_n=qn, reject=rj, min_score=ms, covis=cv, n_covis=nc))
+        set_outputs(a, o, o, host_ptr)
         _check(lib().plp_bow_query_host(self._h, C.byref(a)))
         return o
 
@@ -3852,14 +2934,12 @@ class matcher:
                          min_score=None, covis_cap=0, covis=None, n_covis=None, scoring=0, stream=None):
         """plp_bow_query_device: every array a device pointer (int) or a torch tensor on the matcher's device -- min_score too; `out` maps names of
         BOW_QUERY_OUTPUTS to tensors (the others are not written); asynchronous, four kernels on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(bow_query_args_c, dict(scoring=int(scoring), n_words=int(n_words), N=int(N), stride=int(stride), Q=int(Q), q_stride=int(q_stride),
                                            covis_cap=int(covis_cap)),
-                    dict(db_word=D(db_word), db_value=D(db_value), db_n=D(db_n), db_alive=D(db_alive), q_word=D(q_word), q_value=D(q_value), q_n=D(q_n),
-                         reject=D(reject), min_score=D(min_score), covis=D(covis), n_covis=D(n_covis), **{"out_" + k: D(v) for k, v in out.items()}))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_bow_query_device(self._h, C.byref(a), st))
+                    dev_ptrs(db_word=db_word, db_value=db_value, db_n=db_n, db_alive=db_alive, q_word=q_word, q_value=q_value, q_n=q_n, reject=reject,
+                             min_score=min_score, covis=covis, n_covis=n_covis))
+        set_outputs(a, out, out, dev_ptr)
+        self._device("plp_bow_query_device", a, stream)
 
     def bow_score_pairs(self, a_word, a_value, a_n, b_word, b_value, b_n, a_row, b_row, scoring=0):
         """plp_bow_score_pairs_host: (float)score(row a_row[p] of table A, row b_row[p] of table B), (P,) f32; tables as in bow_query"""
@@ -3870,29 +2950,21 @@ class matcher:
         an = np.ascontiguousarray(a_n, np.int32).reshape(aw.shape[0]); bn = np.ascontiguousarray(b_n, np.int32).reshape(bw.shape[0])
         ar = np.ascontiguousarray(a_row, np.int32).reshape(-1); br = np.ascontiguousarray(b_row, np.int32).reshape(len(ar))
         out = np.zeros(len(ar), np.float32)
-        P = lambda v: None if v.size == 0 else v.ctypes.data
         a = _struct(bow_score_pairs_args_c, dict(scoring=int(scoring), NA=aw.shape[0], stride_a=aw.shape[1], NB=bw.shape[0], stride_b=bw.shape[1], P=len(ar)),
-                    dict(a_word=P(aw), a_value=P(av), a_n=P(an), b_word=P(bw), b_value=P(bv), b_n=P(bn), a_row=P(ar), b_row=P(br), out_score=P(out)))
+                    host_ptrs(a_word=aw, a_value=av, a_n=an, b_word=bw, b_value=bv, b_n=bn, a_row=ar, b_row=br, out_score=out))
         _check(lib().plp_bow_score_pairs_host(self._h, C.byref(a)))
         return out
 
     def bow_score_pairs_device(self, NA, stride_a, a_word, a_value, a_n, NB, stride_b, b_word, b_value, b_n, P, a_row, b_row, out_score, scoring=0,
                                stream=None):
         """plp_bow_score_pairs_device: device pointers (int) or torch tensors; asynchronous, one kernel on the stream"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
         a = _struct(bow_score_pairs_args_c, dict(scoring=int(scoring), NA=int(NA), stride_a=int(stride_a), NB=int(NB), stride_b=int(stride_b), P=int(P)),
-                    dict(a_word=D(a_word), a_value=D(a_value), a_n=D(a_n), b_word=D(b_word), b_value=D(b_value), b_n=D(b_n), a_row=D(a_row),
-                         b_row=D(b_row), out_score=D(out_score)))
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_bow_score_pairs_device(self._h, C.byref(a), st))
+                    dev_ptrs(a_word=a_word, a_value=a_value, a_n=a_n, b_word=b_word, b_value=b_value, b_n=b_n, a_row=a_row, b_row=b_row, out_score=out_score))
+        self._device("plp_bow_score_pairs_device", a, stream)
 
     def landmark_descriptors_device(self, descs, offsets, L, out_best_idx, stream=None):
         """plp_landmark_descriptor_device: descs [total, 32] u8, offsets [L + 1] i32, out_best_idx [L] i32 on the matcher's device; asynchronous"""
-        import torch
-        D = lambda v: None if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
-        st = stream if isinstance(stream, int) else (stream or torch.cuda.current_stream()).cuda_stream
-        _check(lib().plp_landmark_descriptor_device(self._h, D(descs), D(offsets), int(L), D(out_best_idx), st))
+        _check(lib().plp_landmark_descriptor_device(self._h, dev_ptr(descs), dev_ptr(offsets), int(L), dev_ptr(out_best_idx), stream_handle(stream)))
 
     def lbd_match_1nn(self, query_lbd, train_lbd):
         """BinaryDescriptorMatcher::match: (trainIdx, distance) per query row"""
@@ -3978,16 +3050,6 @@ class stereo_rectifier:
 # ------------------------------------------------------------------------------------------------
 # data::bow_vocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) -- the transform of compute_bow
 # ------------------------------------------------------------------------------------------------
-class bow_tree_c(C.Structure):
-    _fields_ = [("n_nodes", C.c_int32), ("L", C.c_int32), ("child_offset", _VP), ("children", _VP), ("node_desc", _VP), ("node_weight", _VP),
-                ("node_word", _VP), ("accumulate", C.c_int32), ("norm", C.c_int32)]
-
-
-# DBoW2 enums (BowVector.h): WeightingType and ScoringType
-TF_IDF, TF, IDF, BINARY = 0, 1, 2, 3
-L1_NORM, L2_NORM, CHI_SQUARE, KL, BHATTACHARYYA, DOT_PRODUCT = 0, 1, 2, 3, 4, 5
-
-
 class bow_vocabulary:
     """Mirror of data::bow_vocabulary for the one call the front-end makes: transform(descriptors, bow_vec, bow_feat_vec,
     levelsup) (data/frame.cc:785-795).  Built from the node list in m_nodes order: parents[i] (node 0 = root, -1), is_leaf,

@@ -137,3 +137,63 @@ def test_facade_check_programs_are_built_and_load():
         assert exe.exists(), f"{exe} missing: run python -c 'import __graft_entry__ as g; g.build()'"
         r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60, env=env)
         assert r.returncode == 2, (exe, r.returncode, r.stderr)
+
+
+def test_package_surface_is_kept():
+    """tests/golden/package_surface.txt: every attribute of the package that was no module and no dunder when the binding was one file.  The list
+    is frozen; the modules the binding is split into must keep showing every name at the package."""
+    names = (plp.ROOT / "tests" / "golden" / "package_surface.txt").read_text().split()
+    assert len(names) > 300
+    missing = [n for n in names if not hasattr(plp, n)]
+    assert not missing, missing
+
+
+def _header_structs():
+    """{name: field names in order} of every `typedef struct plp_X { ... } plp_X;` of include/plp_front.h"""
+    header = (plp.ROOT / "include" / "plp_front.h").read_text()
+    structs = {}
+    for name, body in re.findall(r"typedef struct (plp_\w+)\s*\{(.*?)\}\s*\1;", header, flags=re.S):
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        fields = []
+        for stmt in body.split(";"):
+            if stmt.strip():
+                fields += [re.sub(r"\[\d+\]", "", d).strip(" *\n").split()[-1].lstrip("*") for d in stmt.split(",")]
+        structs[name] = fields
+    return structs
+
+
+def test_every_struct_mirror_follows_the_header(tmp_path):
+    """Every struct of include/plp_front.h against its Python mirror: the field names in order, and sizeof as the host compiler lays the struct
+    out.  plp_X is mirrored by X_c (plp_keyframe_pair_geometry_args by pair_geometry_args_c), plp_keypoint and plp_keyline by the two record
+    dtypes; no ctypes.Structure the package shows is left without a struct of the header."""
+    import os
+    import shutil
+    import subprocess
+    structs = _header_structs()
+    assert len(structs) >= 34 and "plp_project_args" in structs
+    dtypes = dict(plp_keypoint=plp.KP_DTYPE, plp_keyline=plp.KL_DTYPE)
+    assert (plp.KP_DTYPE.itemsize, plp.KL_DTYPE.itemsize) == (28, 68)
+    irregular = dict(plp_keyframe_pair_geometry_args="pair_geometry_args_c")
+    mirrors = {name: getattr(plp, irregular.get(name, name[len("plp_"):] + "_c")) for name in structs if name not in dtypes}
+    for name, fields in structs.items():
+        if name in dtypes:
+            assert fields == list(dtypes[name].names), name
+        else:
+            assert issubclass(mirrors[name], C.Structure) and fields == [f for f, _ in mirrors[name]._fields_], name
+    # no structure of the package without a struct of the header (camera_model is camera_model_c itself, with methods)
+    shown = {v for v in vars(plp).values() if isinstance(v, type) and issubclass(v, C.Structure)}
+    assert plp.camera_c in shown and len(mirrors) == len(set(mirrors.values())) >= 32
+    unmatched = [c.__name__ for c in shown if c not in mirrors.values() and not (c.__bases__[0] in mirrors.values() and "_fields_" not in vars(c))]
+    assert not unmatched, unmatched
+    # sizeof of every struct, from the host compiler the oracle is built with
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("cc")
+    assert cxx, "no host compiler"
+    src = tmp_path / ("sizes.c" if os.path.basename(cxx) == "cc" else "sizes.cpp")
+    src.write_text('#include <stdio.h>\n#include "plp_front.h"\nint main() {\n' +
+                   "".join(f'    printf("{n} %zu\\n", sizeof({n}));\n' for n in structs) + "    return 0;\n}\n")
+    subprocess.run([cxx, "-I", str(plp.ROOT / "include"), "-o", str(tmp_path / "sizes"), str(src)], check=True, capture_output=True, timeout=120)
+    out = subprocess.run([str(tmp_path / "sizes")], check=True, capture_output=True, text=True, timeout=60).stdout
+    sizes = {n: int(s) for n, s in (ln.split() for ln in out.splitlines())}
+    assert set(sizes) == set(structs)
+    for name, size in sizes.items():
+        assert size == (dtypes[name].itemsize if name in dtypes else C.sizeof(mirrors[name])), name
