@@ -1836,6 +1836,132 @@ int32_t plp_model_local_ba_solve_host(int32_t P, int32_t M, int32_t E, const dou
 int32_t plp_model_inv3_host(const double* a, int32_t n, double* out, int32_t* out_ok);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Global bundle adjustment: optimize::global_bundle_adjuster::optimize (src/PLPSLAM/optimize/global_bundle_adjuster.cc:64-311) over the whole
+ * point map -- what module::loop_bundle_adjuster::optimize runs after a loop closure (Huber off) and module::initializer on its first two key
+ * frames (Huber on) -- and the array half of the loop adjuster's map update (module/loop_bundle_adjuster.cc:109-181).  Numeric contract:
+ * DESIGN.md section 5, D23, on top of D17 and D15; g2o is not linked.  ONE problem per call; the problem uses the whole device.
+ *
+ * The key-frame and landmark tables are plp_local_ba_args', field for field.  Sets (:91-184): every key frame that is not erased is a vertex,
+ * kf_is_origin makes it constant; every landmark that is not erased and has an edge is a vertex; one edge per observation of such a landmark
+ * by a key frame that is not erased, with D17's rules for what is no edge.  There is no kf_local, no fixed key frame, no level and one
+ * optimize(num_iter); the Huber kernel is on or off for the whole run.
+ * Outputs; slots that are not written keep the caller's values:
+ *   out_status        [1] a plp_global_ba_status
+ *   out_kf_optimized  [F] 1 = the key frame is not erased (a vertex); out_lm_optimized [L] 1 = the landmark has an edge
+ *   out_pose          [F][15]: set_cam_pose's form, for EVERY key frame that is not erased (the origin and a key frame without an edge get the
+ *                     converted input)
+ *   out_pos_w         [L][3]: optimised landmarks only
+ *   out_info          optional [4]: iterations, rejected steps, factorisations, why optimize() ended (plp_local_ba_args.out_round_info's code)
+ *   out_chi2          optional [3]: the chi2 of the first linearisation, the chi2 of the kept estimate, lambda
+ * stop: optional HOST flag (force_stop_flag), read before every iteration and before every try; if it is set when the run ends the status is
+ * PLP_GLOBAL_BA_STOPPED and nothing else is written.  The host builds read it once, as a constant. */
+#define PLP_GLOBAL_BA_MAX_KF 4096
+#define PLP_GLOBAL_BA_PANEL 32          /* columns of a panel of the dense Cholesky of the reduced system (n = 6 P rows)               */
+#define PLP_GLOBAL_BA_ROWS 64           /* rows of a workgroup of the launch that computes a panel's rows below the diagonal block     */
+typedef enum plp_global_ba_status {
+    PLP_GLOBAL_BA_OK = 0,
+    PLP_GLOBAL_BA_NO_EDGES = 1,         /* nothing to optimise: out_pose is the input's (with its cam_center), no landmark is written  */
+    PLP_GLOBAL_BA_STOPPED = 2           /* `stop` was set: nothing but out_status is written                                           */
+} plp_global_ba_status;
+typedef struct plp_global_ba_args {
+    plp_camera_model camera;            /* model, fx, fy, cx, cy, focal_x_baseline are read */
+    int32_t setup_type;                 /* 0 monocular, 1 stereo, 2 RGB-D: the Huber delta */
+    int32_t num_iter;                   /* >= 1; 10 by the constructor's default */
+    int32_t use_huber_kernel;           /* 0 / 1 */
+    int32_t F, L, T;                    /* F <= 4096 key frames, L <= 2^20 landmarks, T <= 2^22 observations */
+    int32_t kp_stride, pose_stride;
+    const float* inv_level_sigma_sq;    /* HOST, num_levels */
+    int32_t num_levels;                 /* 1 .. 16 */
+    const double* pose;                 /* F rows */
+    const uint8_t* kf_erased;           /* F, or NULL = none */
+    const uint8_t* kf_is_origin;        /* F, or NULL = none */
+    const plp_keypoint* undist;         /* F x kp_stride */
+    const float* x_right;               /* F x kp_stride, or NULL */
+    const int32_t* counts;              /* F, or NULL */
+    const double* pos_w;                /* L x 3 */
+    const uint8_t* lm_erased;           /* L, or NULL = none */
+    const int32_t* obs_offsets;         /* L + 1 */
+    const int32_t* obs_kf;              /* T */
+    const int32_t* obs_idx;             /* T */
+    const volatile int32_t* stop;       /* HOST, or NULL */
+    uint8_t* out_status;                /* 1 */
+    uint8_t* out_kf_optimized;          /* F */
+    uint8_t* out_lm_optimized;          /* L */
+    double* out_pose;                   /* F x 15 */
+    double* out_pos_w;                  /* L x 3 */
+    int32_t* out_info;                  /* 4, or NULL */
+    double* out_chi2;                   /* 3, or NULL */
+} plp_global_ba_args;
+/* Checked before anything is written, as plp_local_ba_*: PLP_ERR_INVALID_ARG for NULL ctx / args, an unknown camera model or setup_type, fx or
+ * fy 0 or a non-finite fx, fy, cx, cy, a negative F, L, T or kp_stride, num_iter < 1, pose_stride < 12, num_levels outside 1 .. 16 or a NULL
+ * sigma table, a NULL obs_offsets, pose (F > 0), undist (F > 0 and kp_stride > 0), pos_w (L > 0), obs_kf or obs_idx (T > 0), a NULL required
+ * output of non-zero size; PLP_ERR_UNSUPPORTED for the equirectangular camera (D15's reason), F > 4096, L > 2^20, T > 2^22.  _host and the
+ * host builds also check that obs_offsets rises from 0 to T.
+ * _device: every array but the sigma table and `stop` a DEVICE pointer.  Separate launches on hip_stream, phase by phase (the sets and edges;
+ * per linearisation the edge pass and the sums; per try the 3 x 3 inverses, the Schur complement with one wave per free key frame, the dense
+ * Cholesky panel by panel -- one launch for a panel's diagonal block, one over all workgroups for the rows below it --, the substitutions,
+ * the update and the evaluation); no workgroup ever waits for another.  The entry reads the run's record back after the prepare launches
+ * (to size the reduced system, which it allocates in the context) and after every try: plp_global_ba_device is SYNCHRONOUS with respect to
+ * hip_stream, the only _device entry that is; it returns when the outputs are written.  The state lives in the context: one call at a time.
+ * _host: HOST pointers, staged, the same kernels. */
+plp_status plp_global_ba_device(plp_matcher* ctx, const plp_global_ba_args* args, void* hip_stream);
+plp_status plp_global_ba_host(plp_matcher* ctx, const plp_global_ba_args* args);
+
+/* The loop adjuster's map update after the global adjustment (module/loop_bundle_adjuster.cc:109-181), its array half: the correction is carried
+ * along the spanning tree (kf_parent, -1 = none) from the origin to the key frames the adjuster did not optimise (created in the meantime):
+ * after(c) = (pose(c) * pose_inv(p)) * after(p), p the parent, pose_inv as set_cam_pose stores it, after(p) the adjuster's pose_after [F][15] or
+ * the same rule one step up; then every landmark moves: an optimised one to pos_after, any other one that is not erased with its reference key
+ * frame, rot_wc_after (rot_before pos + t_before) + t_wc_after.  Every walk is bounded by F steps; no loop depends on kf_parent being a tree.
+ *   out_kf_status  [F] a plp_loop_ba_kf_status; out_pose [F][15] and out_pose_before [F][12] for OPTIMIZED and PROPAGATED rows only
+ *   out_lm_status  [L] a plp_loop_ba_lm_status; out_pos_w [L][3] for OPTIMIZED and MOVED rows only */
+typedef enum plp_loop_ba_kf_status {
+    PLP_LOOP_BA_KF_NOT_REACHED = 0,     /* the parent chain does not end at the origin within F steps (a broken link, an erased key frame, a cycle), or nothing on it was optimised */
+    PLP_LOOP_BA_KF_OPTIMIZED = 1,       /* reached, kf_optimized: pose_after                                                           */
+    PLP_LOOP_BA_KF_PROPAGATED = 2,      /* reached, not optimised: the correction of its nearest optimised ancestor                    */
+    PLP_LOOP_BA_KF_ERASED = 3
+} plp_loop_ba_kf_status;
+typedef enum plp_loop_ba_lm_status {
+    PLP_LOOP_BA_LM_NO_REF = 0,          /* not optimised and its reference key frame is outside the table or not reached (the reference's assert) */
+    PLP_LOOP_BA_LM_OPTIMIZED = 1,
+    PLP_LOOP_BA_LM_MOVED = 2,
+    PLP_LOOP_BA_LM_ERASED = 3
+} plp_loop_ba_lm_status;
+typedef struct plp_loop_ba_propagate_args {
+    int32_t F, L, pose_stride;          /* F <= 4096, L <= 2^20, pose_stride >= 12 */
+    const double* pose;                 /* F rows: the poses BEFORE the correction */
+    const uint8_t* kf_erased;           /* F, or NULL */
+    const uint8_t* kf_is_origin;        /* F, or NULL */
+    const int32_t* kf_parent;           /* F */
+    const uint8_t* kf_optimized;        /* F: plp_global_ba_args.out_kf_optimized */
+    const double* pose_after;           /* F x 15: plp_global_ba_args.out_pose */
+    const double* pos_w;                /* L x 3 */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const int32_t* ref_kf;              /* L */
+    const uint8_t* lm_optimized;        /* L */
+    const double* pos_after;            /* L x 3 */
+    double* out_pose;                   /* F x 15 */
+    double* out_pose_before;            /* F x 12 */
+    uint8_t* out_kf_status;             /* F */
+    double* out_pos_w;                  /* L x 3 */
+    uint8_t* out_lm_status;             /* L */
+} plp_loop_ba_propagate_args;
+/* PLP_ERR_INVALID_ARG: NULL ctx / args, negative F or L, pose_stride < 12, a NULL array of non-zero size other than kf_erased, kf_is_origin,
+ * lm_erased; PLP_ERR_UNSUPPORTED above the caps.  _device: DEVICE pointers, two kernels (one lane per key frame, one per landmark), no host
+ * synchronisation.  _host: HOST pointers, staged. */
+plp_status plp_loop_ba_propagate_device(plp_matcher* ctx, const plp_loop_ba_propagate_args* args, void* hip_stream);
+plp_status plp_loop_ba_propagate_host(plp_matcher* ctx, const plp_loop_ba_propagate_args* args);
+/* Host builds of the same source (csrc/global_ba.hpp), HOST pointers, no GPU and no context needed.  plp_model_global_ba_host and
+ * plp_model_loop_ba_propagate_host: the entries above; return 1, or the negated plp_status of a refused call.
+ * plp_model_chol_dense_host: (A + lambda I) x = b for one dense symmetric system of any n >= 0 (A n x n row-major, its upper triangle is read):
+ * the Cholesky in natural order and both substitutions of D23.  out_x n, out_ok 1 (0 = a pivot was not positive and finite; x is then zero).
+ * Returns n, or -1 for a bad argument. */
+int32_t plp_model_global_ba_host(const plp_global_ba_args* args);
+int32_t plp_model_loop_ba_propagate_host(const plp_loop_ba_propagate_args* args);
+int32_t plp_model_chol_dense_host(int32_t n, const double* A, const double* b, double lambda, double* out_x, int32_t* out_ok);
+/* the same system through the panel kernels of plp_global_ba_device (HOST pointers, staged, synchronous): what tests compare the two forms with */
+plp_status plp_chol_dense_host(plp_matcher* ctx, int32_t n, const double* A, const double* b, double lambda, double* out_x, int32_t* out_ok);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * The local map of B frames over one map snapshot: module::local_map_updater (src/PLPSLAM/module/local_map_updater.cc:60-273) as
  * tracking_module::update_local_map runs it (tracking_module.cc:837-906), and the landmarks search_local_landmarks[_line] skips because the
  * frame holds them (tracking_module.cc:911-946).  Integers only; contract: DESIGN.md section 5, D18 (the literal parts, and the orders

@@ -24,6 +24,8 @@ from ._core import (LIB_PATH, PLP_ERR_CAPACITY, PLP_ERR_HIP, PLP_ERR_INVALID_ARG
                     ROOT, _API, _I32, _PKG, _SZ, _VP, _check, _lib, _p, api_symbols, build, lib)
 from ._abi import *        # noqa: F401,F403  every struct mirror, record dtype, enum and limit of include/plp_front.h
 from ._abi import _struct
+from ._global_ba import (GLOBAL_BA_OUTPUTS, LOOP_BA_PROPAGATE_OUTPUTS, _chol_dense, _global_ba_host, _global_ba_kw, _loop_ba_propagate_host, global_bundle_adjuster,
+                         loop_bundle_adjuster, model_chol_dense, model_global_ba, model_loop_ba_propagate)
 from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, stream_handle, wanted
 
 
@@ -2810,6 +2812,51 @@ class matcher:
                                                                                  sim3_cw=sim3_cw, corrected_wc=corrected_wc, out_pos_w=out_pos_w,
                                                                                  out_status=out_status))
         self._device("plp_correct_landmarks_device", a, stream)
+
+    def global_ba(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, inv_level_sigma_sq, x_right=None, counts=None, kf_erased=None,
+                  kf_is_origin=None, lm_erased=None, num_iter=10, use_huber_kernel=True, stop=None, outputs=None, out=None):
+        """optimize::global_bundle_adjuster::optimize over the whole point map (plp_global_ba_host; DESIGN.md section 5, D23): the tables of local_ba without
+        kf_local; stop: None or an int32 array of one element (force_stop_flag).  Returns dict(status (1,) u8: GLOBAL_BA_*, kf_optimized (F,), lm_optimized (L,),
+        pose (F, 15), pos_w (L, 3), info (4,), chi2 (3,)); `outputs` names the optional ones wanted (default all); out[name]: the caller's array (slots the
+        adjuster does not write keep their values)."""
+        return _global_ba_host(self._host("plp_global_ba_host"), _global_ba_kw(
+            camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, inv_level_sigma_sq, x_right, counts, kf_erased, kf_is_origin, lm_erased, num_iter,
+            use_huber_kernel, stop), outputs, out)
+
+    def global_ba_device(self, camera, setup_type, F, L, T, kp_stride, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, inv_level_sigma_sq, out, x_right=None,
+                         counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None, pose_stride=15, num_iter=10, use_huber_kernel=True, stop=None, stream=None):
+        """plp_global_ba_device: every array a device pointer (int) or a torch tensor on the matcher's device (the sigma table is a host vector, stop None or a
+        host int32 array of one element); out: dict of the device outputs named as in GLOBAL_BA_OUTPUTS (info / chi2 may be absent).  SYNCHRONOUS with respect to
+        the stream: the entry reads the run's record back after every try; it returns when the outputs are written."""
+        sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)             # live until the call has returned
+        a = _struct(global_ba_args_c, dict(setup_type=int(setup_type), num_iter=int(num_iter), use_huber_kernel=int(bool(use_huber_kernel)), F=int(F), L=int(L), T=int(T),
+                                           kp_stride=int(kp_stride), pose_stride=int(pose_stride), num_levels=len(sg)), dict(
+            dev_ptrs(pose=pose, kf_erased=kf_erased, kf_is_origin=kf_is_origin, undist=undist, x_right=x_right, counts=counts, pos_w=pos_w, lm_erased=lm_erased,
+                     obs_offsets=obs_offsets, obs_kf=obs_kf, obs_idx=obs_idx), inv_level_sigma_sq=host_ptr(sg), stop=host_ptr(stop)))
+        set_outputs(a, GLOBAL_BA_OUTPUTS, out, dev_ptr)
+        a.camera = camera_model_c.from_buffer_copy(camera)
+        self._device("plp_global_ba_device", a, stream)
+
+    def loop_ba_propagate(self, pose, kf_parent, kf_optimized, pose_after, pos_w, ref_kf, lm_optimized, pos_after, kf_erased=None, kf_is_origin=None,
+                          lm_erased=None, out=None):
+        """The loop adjuster's map update (module/loop_bundle_adjuster.cc:109-181; plp_loop_ba_propagate_host): pose (F, >= 12) before the correction, kf_parent
+        (F,), the adjuster's kf_optimized / pose (F, 15) / lm_optimized / pos_w, the landmarks' pos_w and ref_kf.  Returns dict(pose (F, 15), pose_before (F, 12),
+        kf_status (F,) u8: LOOP_BA_KF_*, pos_w (L, 3), lm_status (L,) u8: LOOP_BA_LM_*); out[name]: the caller's array (rows that are not written keep their values)."""
+        return _loop_ba_propagate_host(self._host("plp_loop_ba_propagate_host"), pose, kf_parent, kf_optimized, pose_after, pos_w, ref_kf, lm_optimized, pos_after,
+                                       kf_erased, kf_is_origin, lm_erased, out)
+
+    def loop_ba_propagate_device(self, F, L, pose, kf_parent, kf_optimized, pose_after, pos_w, ref_kf, lm_optimized, pos_after, out, kf_erased=None, kf_is_origin=None,
+                                 lm_erased=None, pose_stride=15, stream=None):
+        """plp_loop_ba_propagate_device: device pointers (int) or torch tensors; out: dict of the device outputs named as in LOOP_BA_PROPAGATE_OUTPUTS; asynchronous"""
+        a = _struct(loop_ba_propagate_args_c, dict(F=int(F), L=int(L), pose_stride=int(pose_stride)), dev_ptrs(
+            pose=pose, kf_erased=kf_erased, kf_is_origin=kf_is_origin, kf_parent=kf_parent, kf_optimized=kf_optimized, pose_after=pose_after, pos_w=pos_w,
+            lm_erased=lm_erased, ref_kf=ref_kf, lm_optimized=lm_optimized, pos_after=pos_after))
+        set_outputs(a, LOOP_BA_PROPAGATE_OUTPUTS, out, dev_ptr)
+        self._device("plp_loop_ba_propagate_device", a, stream)
+
+    def chol_dense(self, A, b, lam=0.0):
+        """D23's dense solve (A + lam I) x = b through the panel kernels of plp_global_ba_device (plp_chol_dense_host).  Returns (x, ok)."""
+        return _chol_dense(lambda *args: _check(lib().plp_chol_dense_host(self._h, *args)), A, b, lam)
 
     def local_map(self, kf_covis, kf_parent, kf_children_offsets, kf_children, kf_lm, obs_offsets, obs_kf, frm_lm, k_cap, m_cap, ml_cap=0, kf_erased=None,
                   kf_counts=None, kf_lm_lines=None, kf_kl_counts=None, lm_erased=None, lm_erased_lines=None, LL=None, frm_counts=None, frm_lm_lines=None,

@@ -214,6 +214,21 @@ class local_ba_args_c(C.Structure):
                 ("out_round_chi2", _VP)]
 
 
+class global_ba_args_c(C.Structure):
+    """plp_global_ba_args"""
+    _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("num_iter", C.c_int32), ("use_huber_kernel", C.c_int32), ("F", C.c_int32), ("L", C.c_int32),
+                ("T", C.c_int32), ("kp_stride", C.c_int32), ("pose_stride", C.c_int32), ("inv_level_sigma_sq", _VP), ("num_levels", C.c_int32)] + [(k, _VP) for k in (
+        "pose", "kf_erased", "kf_is_origin", "undist", "x_right", "counts", "pos_w", "lm_erased", "obs_offsets", "obs_kf", "obs_idx", "stop", "out_status",
+        "out_kf_optimized", "out_lm_optimized", "out_pose", "out_pos_w", "out_info", "out_chi2")]
+
+
+class loop_ba_propagate_args_c(C.Structure):
+    """plp_loop_ba_propagate_args"""
+    _fields_ = [("F", C.c_int32), ("L", C.c_int32), ("pose_stride", C.c_int32)] + [(k, _VP) for k in (
+        "pose", "kf_erased", "kf_is_origin", "kf_parent", "kf_optimized", "pose_after", "pos_w", "lm_erased", "ref_kf", "lm_optimized", "pos_after", "out_pose",
+        "out_pose_before", "out_kf_status", "out_pos_w", "out_lm_status")]
+
+
 class pose_graph_args_c(C.Structure):
     """plp_pose_graph_args"""
     _fields_ = [(k, C.c_int32) for k in ("G", "F", "pose_stride", "conn_cap", "covis_cap", "edge_cap", "env_cap", "max_iter")] + [(k, _VP) for k in (
@@ -368,6 +383,12 @@ TRANSFORM_OPT_OK, TRANSFORM_OPT_TOO_FEW_INLIERS = range(2)
 LOCAL_BA_OK, LOCAL_BA_NO_EDGES, LOCAL_BA_TOO_MANY_FREE = range(3)
 LOCAL_BA_KF_NONE, LOCAL_BA_KF_FREE, LOCAL_BA_KF_ORIGIN, LOCAL_BA_KF_FIXED = range(4)
 LOCAL_BA_MAX_FREE = 64
+
+# plp_global_ba_status / plp_loop_ba_kf_status / plp_loop_ba_lm_status
+GLOBAL_BA_OK, GLOBAL_BA_NO_EDGES, GLOBAL_BA_STOPPED = range(3)
+LOOP_BA_KF_NOT_REACHED, LOOP_BA_KF_OPTIMIZED, LOOP_BA_KF_PROPAGATED, LOOP_BA_KF_ERASED = range(4)
+LOOP_BA_LM_NO_REF, LOOP_BA_LM_OPTIMIZED, LOOP_BA_LM_MOVED, LOOP_BA_LM_ERASED = range(4)
+GLOBAL_BA_MAX_KF, GLOBAL_BA_PANEL, GLOBAL_BA_ROWS = 4096, 32, 64
 
 
 # plp_pose_graph_status / plp_pose_graph_edge_type / plp_correct_landmark_status

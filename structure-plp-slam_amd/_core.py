@@ -208,6 +208,14 @@ _API = [
     ("plp_correct_landmarks_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_correct_landmarks_host", C.c_int, [_VP, _VP]),
     ("plp_model_correct_landmarks_host", _I32, [_VP]),
+    ("plp_global_ba_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_global_ba_host", C.c_int, [_VP, _VP]),
+    ("plp_model_global_ba_host", _I32, [_VP]),
+    ("plp_loop_ba_propagate_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_loop_ba_propagate_host", C.c_int, [_VP, _VP]),
+    ("plp_model_loop_ba_propagate_host", _I32, [_VP]),
+    ("plp_model_chol_dense_host", _I32, [_I32, _VP, _VP, C.c_double, _VP, _VP]),
+    ("plp_chol_dense_host", C.c_int, [_VP, _I32, _VP, _VP, C.c_double, _VP, _VP]),
 ]
 
 

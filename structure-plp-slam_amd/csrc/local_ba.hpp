@@ -286,8 +286,90 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_round_s
     par.barrier_g();
 }
 
-// ---- one pass over the level-0 edges at the estimates: chi2 and the robust chi2 of every edge, and when lin its blocks (linearizeOplus,
-// perspective_reproj_edge.cc:78-125, :166-214; BaseBinaryEdge::constructQuadraticForm)
+// ---- one edge at the estimates (est, p): chi2 and the robust chi2 into its record E, and when lin its blocks (linearizeOplus,
+// perspective_reproj_edge.cc:78-125, :166-214; BaseBinaryEdge::constructQuadraticForm); the pose block and W only for a free pose.  The local
+// and the global adjuster (global_ba.hpp) both call this.
+// is_free() is asked once, after the errors: whether the edge's pose is a free one.
+template <class Free> __host__ __device__ __forceinline__ void la_edge_terms(double* E, const double* est, const double* p, const PoseCam& C, const double& delta, bool lin,
+                                                                             bool robust, Free is_free) {
+    const double ox = E[kLaRowObs + 0], oy = E[kLaRowObs + 1], orr = E[kLaRowObs + 2], w = E[kLaRowObs + 3];
+    const bool mono = orr < 0.0;
+    double x, y, z, e0, e1, e2;
+    const double chi2 = pose_point_error(est, C, p, ox, oy, orr, mono, w, x, y, z, e0, e1, e2);
+    double rho0 = chi2, rho1 = 1.0;
+    if (robust) pose_huber(chi2, delta, rho0, rho1);
+    E[kLaRowChi] = chi2;
+    E[kLaRowRho] = rho0;
+    if (!lin) return;
+    const double z_sq = z * z;
+    double J[18];
+    J[0] = ((x * y) / z_sq) * C.fx;
+    J[1] = (-(1.0 + (x * x) / z_sq)) * C.fx;
+    J[2] = (y / z) * C.fx;
+    J[3] = (-1.0 / z) * C.fx;
+    J[4] = 0.0;
+    J[5] = (x / z_sq) * C.fx;
+    J[6] = (1.0 + (y * y) / z_sq) * C.fy;
+    J[7] = (((-x) * y) / z_sq) * C.fy;
+    J[8] = ((-x) / z) * C.fy;
+    J[9] = 0.0;
+    J[10] = (-1.0 / z) * C.fy;
+    J[11] = (y / z_sq) * C.fy;
+    J[12] = J[0] - (C.fxb * y) / z_sq;
+    J[13] = J[1] + (C.fxb * x) / z_sq;
+    J[14] = J[2];
+    J[15] = J[3];
+    J[16] = 0.0;
+    J[17] = J[5] - C.fxb / z_sq;
+    const bool free_pose = is_free();
+    if (free_pose) pose_terms(J, mono ? 2 : 3, e0, e1, e2, w, rho0, rho1, E, 1);
+    double R[9], Jl[9];
+    pose_rot_from_quat(est, R);
+    _Pragma("unroll") for (int c = 0; c < 3; ++c) {
+        Jl[c] = ((-C.fx) * R[c]) / z + ((C.fx * x) * R[6 + c]) / z_sq;
+        Jl[3 + c] = ((-C.fy) * R[3 + c]) / z + ((C.fy * y) * R[6 + c]) / z_sq;
+        Jl[6 + c] = Jl[c] - (C.fxb * R[6 + c]) / z_sq;
+    }
+    const double wr = rho1 * w;
+    const double o0 = (-(w * e0)) * rho1, o1 = (-(w * e1)) * rho1, o2 = (-(w * e2)) * rho1;
+    int k = 0;
+    _Pragma("unroll") for (int i = 0; i < 3; ++i)
+        _Pragma("unroll") for (int j = i; j < 3; ++j) {
+            double v = Jl[i] * (wr * Jl[j]) + Jl[3 + i] * (wr * Jl[3 + j]);
+            if (!mono) v = v + Jl[6 + i] * (wr * Jl[6 + j]);
+            E[kLaRowLm + (k++)] = v;
+        }
+    _Pragma("unroll") for (int i = 0; i < 3; ++i) {
+        double v = Jl[i] * o0 + Jl[3 + i] * o1;
+        if (!mono) v = v + Jl[6 + i] * o2;
+        E[kLaRowLm + 6 + i] = v;
+    }
+    if (free_pose)
+        _Pragma("unroll") for (int i = 0; i < 6; ++i)
+            _Pragma("unroll") for (int j = 0; j < 3; ++j) {
+                double v = J[i] * (wr * Jl[j]) + J[6 + i] * (wr * Jl[3 + j]);
+                if (!mono) v = v + J[12 + i] * (wr * Jl[6 + j]);
+                E[kLaRowW + 3 * i + j] = v;
+            }
+}
+
+// the sums of one landmark over the live edges [lo, hi) of its run in list order: the robust chi2, and when lin the nine terms of its block
+template <class Live> __host__ __device__ __forceinline__ void la_lm_sums(const double* et, int lo, int hi, bool lin, Live live, double& part, double* s) {
+    for (int t = lo; t < hi; ++t) {
+        if (!live(t)) continue;
+        part = part + et[(size_t)t * kLaEdgeRows + kLaRowRho];
+        if (lin)
+            _Pragma("unroll") for (int i = 0; i < 9; ++i) s[i] = s[i] + et[(size_t)t * kLaEdgeRows + kLaRowLm + i];
+    }
+}
+// one of the 27 sums of a pose over its edge list in edge order
+__host__ __device__ __forceinline__ double la_pose_sum(const double* et, const int32_t* list, int cnt, int term) {
+    double acc = 0.0;
+    for (int k = 0; k < cnt; ++k) acc = acc + et[(size_t)list[k] * kLaEdgeRows + term];
+    return acc;
+}
+
+// ---- one pass over the level-0 edges at the estimates: la_edge_terms for every edge
 template <class P, class AA> __host__ __device__ __forceinline__ void la_edge_pass(const AA& A, const LaView& V, LaShared& sh, P& par, bool lin, bool robust) {
     const int T = A.T, buf = lin ? sh.cur : 1 - sh.cur;     // a linearisation is at the kept estimates, an evaluation at the tried ones
     for (int t = par.tid(); t < T; t += P::NT) {
@@ -297,67 +379,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_edge_pa
         double est[7], p[3];
         _Pragma("unroll") for (int i = 0; i < 7; ++i) est[i] = la_k(V, kf, 7 * buf + i);
         _Pragma("unroll") for (int i = 0; i < 3; ++i) p[i] = la_l(V, l, 3 * buf + i);
-        double* E = V.et() + (size_t)t * kLaEdgeRows;
-        const double ox = E[kLaRowObs + 0], oy = E[kLaRowObs + 1], orr = E[kLaRowObs + 2], w = E[kLaRowObs + 3];
-        const bool mono = orr < 0.0;
-        double x, y, z, e0, e1, e2;
-        const double chi2 = pose_point_error(est, sh.cam, p, ox, oy, orr, mono, w, x, y, z, e0, e1, e2);
-        double rho0 = chi2, rho1 = 1.0;
-        if (robust) pose_huber(chi2, sh.delta, rho0, rho1);
-        E[kLaRowChi] = chi2;
-        E[kLaRowRho] = rho0;
-        if (!lin) continue;
-        const PoseCam& C = sh.cam;
-        const double z_sq = z * z;
-        double J[18];
-        J[0] = ((x * y) / z_sq) * C.fx;
-        J[1] = (-(1.0 + (x * x) / z_sq)) * C.fx;
-        J[2] = (y / z) * C.fx;
-        J[3] = (-1.0 / z) * C.fx;
-        J[4] = 0.0;
-        J[5] = (x / z_sq) * C.fx;
-        J[6] = (1.0 + (y * y) / z_sq) * C.fy;
-        J[7] = (((-x) * y) / z_sq) * C.fy;
-        J[8] = ((-x) / z) * C.fy;
-        J[9] = 0.0;
-        J[10] = (-1.0 / z) * C.fy;
-        J[11] = (y / z_sq) * C.fy;
-        J[12] = J[0] - (C.fxb * y) / z_sq;
-        J[13] = J[1] + (C.fxb * x) / z_sq;
-        J[14] = J[2];
-        J[15] = J[3];
-        J[16] = 0.0;
-        J[17] = J[5] - C.fxb / z_sq;
-        const bool free_pose = sh.kf2ai[kf] >= 0;
-        if (free_pose) pose_terms(J, mono ? 2 : 3, e0, e1, e2, w, rho0, rho1, E, 1);
-        double R[9], Jl[9];
-        pose_rot_from_quat(est, R);
-        _Pragma("unroll") for (int c = 0; c < 3; ++c) {
-            Jl[c] = ((-C.fx) * R[c]) / z + ((C.fx * x) * R[6 + c]) / z_sq;
-            Jl[3 + c] = ((-C.fy) * R[3 + c]) / z + ((C.fy * y) * R[6 + c]) / z_sq;
-            Jl[6 + c] = Jl[c] - (C.fxb * R[6 + c]) / z_sq;
-        }
-        const double wr = rho1 * w;
-        const double o0 = (-(w * e0)) * rho1, o1 = (-(w * e1)) * rho1, o2 = (-(w * e2)) * rho1;
-        int k = 0;
-        _Pragma("unroll") for (int i = 0; i < 3; ++i)
-            _Pragma("unroll") for (int j = i; j < 3; ++j) {
-                double v = Jl[i] * (wr * Jl[j]) + Jl[3 + i] * (wr * Jl[3 + j]);
-                if (!mono) v = v + Jl[6 + i] * (wr * Jl[6 + j]);
-                E[kLaRowLm + (k++)] = v;
-            }
-        _Pragma("unroll") for (int i = 0; i < 3; ++i) {
-            double v = Jl[i] * o0 + Jl[3 + i] * o1;
-            if (!mono) v = v + Jl[6 + i] * o2;
-            E[kLaRowLm + 6 + i] = v;
-        }
-        if (free_pose)
-            _Pragma("unroll") for (int i = 0; i < 6; ++i)
-                _Pragma("unroll") for (int j = 0; j < 3; ++j) {
-                    double v = J[i] * (wr * Jl[j]) + J[6 + i] * (wr * Jl[3 + j]);
-                    if (!mono) v = v + J[12 + i] * (wr * Jl[6 + j]);
-                    E[kLaRowW + 3 * i + j] = v;
-                }
+        la_edge_terms(V.et() + (size_t)t * kLaEdgeRows, est, p, sh.cam, sh.delta, lin, robust, [&sh, kf] { return sh.kf2ai[kf] >= 0; });
     }
     par.barrier_g();
 }
@@ -371,12 +393,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_sums(co
         int lo, hi;
         la_run(A, l, lo, hi);
         double part = 0.0, s[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        for (int t = lo; t < hi; ++t) {
-            if (V.e_kf()[t] < 0 || V.lvl()[t]) continue;
-            part = part + la_e(V, t, kLaRowRho);
-            if (lin)
-                _Pragma("unroll") for (int i = 0; i < 9; ++i) s[i] = s[i] + la_e(V, t, kLaRowLm + i);
-        }
+        la_lm_sums(V.et(), lo, hi, lin, [&V](int t) { return !(V.e_kf()[t] < 0 || V.lvl()[t]); }, part, s);
         la_l(V, l, kLaLmPart) = part;
         if (lin)
             _Pragma("unroll") for (int i = 0; i < 9; ++i) la_l(V, l, kLaLmH + i) = s[i];
@@ -384,10 +401,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_sums(co
     if (lin)
         for (int it = par.tid(); it < 27 * sh.nfa; it += P::NT) {
             const int a = it / 27, term = it % 27;
-            const int32_t* list = V.byp() + sh.aoff[a];
-            double acc = 0.0;
-            for (int k = 0; k < sh.acnt[a]; ++k) acc = acc + la_e(V, list[k], term);
-            la_p(V, a, term) = acc;
+            la_p(V, a, term) = la_pose_sum(V.et(), V.byp() + sh.aoff[a], sh.acnt[a], term);
         }
     par.barrier_g();
 }

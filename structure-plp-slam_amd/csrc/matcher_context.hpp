@@ -1,5 +1,5 @@
 // The matcher context (plp_matcher of include/plp_front.h) and what the files that implement its entry points share: match_context.hip and one
-// *_context.hip per solver (sim3, pnp, pose_opt, transform_opt, local_ba, local_map, plane, map_cull, covisibility, pose_graph).
+// *_context.hip per solver (sim3, pnp, pose_opt, transform_opt, local_ba, local_map, plane, map_cull, covisibility, pose_graph, global_ba).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,8 @@ struct plp_matcher {
     plp::DevBuf cull_cnt, cull_rem;                                                          // plp_cull_keyframes_device: the snapshot counts, the removed sets
     plp::DevBuf pg_d, pg_i;                                                                  // plp_pose_graph_optimize_device: what its launches hand to one another
     plp::DevBuf covis_ws;                                                                    // plp_covisibility_update_device: what its two launches hand to one another
+    plp::DevBuf gb_d, gb_i, gb_b, gb_S, gb_rec;                                              // plp_global_ba_device: the tables, the reduced system and the Levenberg record of the run
+    plp::HostPinned gb_pin;                                                                  // ... and where the entry reads the record back
     plp::HostPinned pin;                          // page-locked staging of host images (post-extract depth)
     std::mutex mu;
 };

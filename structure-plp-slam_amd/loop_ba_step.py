@@ -1,0 +1,96 @@
+"""Loop bundle adjustment: the global adjustment of the point map after a loop closure, its correction carried along the spanning tree, the poses and
+positions written back and the landmark geometry refreshed, on one stream.
+
+`loop_ba_step.run` does what module::loop_bundle_adjuster::optimize does for the point map (module/loop_bundle_adjuster.cc:68-181; DESIGN.md section 5,
+D23), over the tables local_ba_step and loop_correction_step share:
+
+  1  plp_global_ba_device            every key frame and landmark, num_iter Levenberg-Marquardt iterations without the Huber kernel      :81-86
+  2  plp_loop_ba_propagate_device    the correction along kf_parent from the origin; every landmark to its new position                  :109-181
+  3  torch, on the stream            pose and pos_w <- the rows step 2 wrote, in place (set_cam_pose, set_pos_in_world)
+  4  plp_landmark_geometry_device    landmark::update_normal_and_depth: normal, min_dist, max_dist
+
+Step 1 is synchronous with respect to the stream (the entry reads the run's record back after every try); steps 2 - 4 are enqueued.  Nothing branches
+on the host: the step's `optimized` bytes start every run as zero, so a run that `stop` ended (status GLOBAL_BA_STOPPED) reaches no key frame in step 2
+and every table keeps its values.  What stays on the host: the pause of the mapper, the mutexes, loop_BA_identifier_, every line landmark.
+
+Tables are torch tensors on the step's device:
+  key frames  pose [F, 15] f64 (updated in place), kps [F, cap, 28] u8, x_right [F, cap] f32 or absent, counts [F] or absent, kf_erased [F] u8 or absent,
+              kf_is_origin [F] u8, kf_parent [F] i32
+  landmarks   pos_w [L, 3] f64 (updated in place), ref_kf [L] i32, skip [L] u8 or absent (will_be_erased), obs_offsets [L + 1], obs_kf / obs_idx [T] i32, and
+              the tables normal [L, 3] f64, min_dist / max_dist [L] f32 (updated in place; a missing one is created zero-filled)
+"""
+import numpy as np
+
+
+class loop_ba_step:
+    def __init__(self, plp, camera, setup_type, inv_level_sigma_sq, num_iter=10, scale_factor=1.2, device_index=0, mt=None):
+        import torch
+        self.torch, self.plp = torch, plp
+        self.dev = torch.device("cuda", device_index)
+        self.camera, self.setup_type, self.num_iter = camera, int(setup_type), int(num_iter)
+        self.sigma = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)
+        sf = np.ones(len(self.sigma), np.float32)            # orb_params::calc_scale_factors: float products
+        for i in range(1, len(sf)):
+            sf[i] = np.float32(sf[i - 1] * np.float32(scale_factor))
+        self.sf = sf
+        self.mt = mt or plp.matcher(device=device_index)
+        self._bufs = {}
+
+    def _buf(self, name, shape, dtype):
+        t = self._bufs.get(name)
+        if t is None or tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            t = self.torch.empty(shape, dtype=dtype, device=self.dev)
+            self._bufs[name] = t
+        return t
+
+    def run(self, keyframes, landmarks, stop=None, stream=None):
+        """Returns dict(status [1] u8: GLOBAL_BA_*, info [4], chi2 [3], kf_optimized [F], lm_optimized [L], kf_status [F] u8: LOOP_BA_KF_*, lm_status [L] u8:
+        LOOP_BA_LM_*, pose_before [F, 12], geometry_status [L] u8 -- the step's own buffers, rewritten by the next run -- and pose, pos_w, normal, min_dist,
+        max_dist: the caller's tables, which local_map_step reads next).  stop: None or a host int32 array of one element."""
+        torch = self.torch
+        st = stream or torch.cuda.current_stream(self.dev)
+        f64, f32, i32, u8 = torch.float64, torch.float32, torch.int32, torch.uint8
+        pose, pos_w = keyframes["pose"], landmarks["pos_w"]
+        F, L, cap = pose.shape[0], pos_w.shape[0], keyframes["kps"].shape[1]
+        T = landmarks["obs_kf"].shape[0]
+        ba = dict(status=self._buf("status", (1,), u8), kf_optimized=self._buf("kf_optimized", (F,), u8), lm_optimized=self._buf("lm_optimized", (L,), u8),
+                  pose=self._buf("pose_after", (F, 15), f64), pos_w=self._buf("pos_after", (L, 3), f64), info=self._buf("info", (4,), i32),
+                  chi2=self._buf("chi2", (3,), f64))
+        with torch.cuda.stream(st):
+            for k in ("kf_optimized", "lm_optimized", "info", "chi2"):
+                ba[k].zero_()
+        # 1: the adjustment (Huber off, :81)
+        self.mt.global_ba_device(self.camera, self.setup_type, F, L, T, cap, pose, keyframes["kps"], pos_w, landmarks["obs_offsets"], landmarks["obs_kf"],
+                                 landmarks["obs_idx"], self.sigma, {k: v for k, v in ba.items() if v.numel()}, x_right=keyframes.get("x_right"),
+                                 counts=keyframes.get("counts"), kf_erased=keyframes.get("kf_erased"), kf_is_origin=keyframes["kf_is_origin"],
+                                 lm_erased=landmarks.get("skip"), pose_stride=pose.shape[1], num_iter=self.num_iter, use_huber_kernel=False, stop=stop, stream=st)
+        # 2: the map update into buffers that start as the tables (a lane reads its ancestors' poses from the table while others write)
+        pr = dict(pose=self._buf("pose_new", (F, 15), f64), pose_before=self._buf("pose_before", (F, 12), f64), kf_status=self._buf("kf_status", (F,), u8),
+                  pos_w=self._buf("pos_new", (L, 3), f64), lm_status=self._buf("lm_status", (L,), u8))
+        with torch.cuda.stream(st):
+            pr["pose"].copy_(pose[:, :15])
+            pr["pose_before"].copy_(pose[:, :12])
+            pr["pos_w"].copy_(pos_w)
+        self.mt.loop_ba_propagate_device(F, L, pose, keyframes["kf_parent"], ba["kf_optimized"], ba["pose"], pos_w, landmarks["ref_kf"], ba["lm_optimized"],
+                                         ba["pos_w"], pr, kf_erased=keyframes.get("kf_erased"), kf_is_origin=keyframes["kf_is_origin"],
+                                         lm_erased=landmarks.get("skip"), pose_stride=pose.shape[1], stream=st)
+        with torch.cuda.stream(st):
+            # 3: the write-back; rows step 2 did not write still hold what they held
+            pose[:, :15].copy_(pr["pose"])
+            pos_w.copy_(pr["pos_w"])
+
+        def table(name, shape, dtype):
+            t = landmarks.get(name)
+            if t is None:
+                with torch.cuda.stream(st):
+                    t = torch.zeros(shape, dtype=dtype, device=self.dev)
+            return t
+        normal, mn, mx = table("normal", (L, 3), f64), table("min_dist", (L,), f32), table("max_dist", (L,), f32)
+        geo = self._buf("geometry_status", (L,), u8)
+        # 4: update_normal_and_depth at the new poses and positions
+        if L:
+            self.mt.landmark_geometry_device(F, cap, L, pose, keyframes["kps"], pos_w, landmarks["ref_kf"], landmarks["obs_offsets"], landmarks["obs_kf"],
+                                             landmarks["obs_idx"], normal, mn, mx, geo, self.sf, skip=landmarks.get("skip"), counts=keyframes.get("counts"), stream=st)
+        return dict(status=ba["status"], info=ba["info"], chi2=ba["chi2"], kf_optimized=ba["kf_optimized"], lm_optimized=ba["lm_optimized"],
+                    kf_status=pr["kf_status"], lm_status=pr["lm_status"], pose_before=pr["pose_before"], geometry_status=geo, pose=pose, pos_w=pos_w, normal=normal,
+                    min_dist=mn, max_dist=mx)
