@@ -1545,6 +1545,167 @@ int32_t plp_model_pnp_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t
 int32_t plp_model_pnp_thresholds_host(const float* scale_factors, int32_t num_levels, float* out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Map initialisation and the tracker's robust match: solve::essential_solver (src/PLPSLAM/solve/essential_solver.cc:33-253), constructor,
+ * find_via_ransac, compute_E_21 and check_inliers, for P problems at once -- a problem is one pair of frames (1 = reference, 2 = current):
+ * `essential_solver(ref_bearings, cur_bearings, ref_cur_matches).find_via_ransac(num_ransac_iters)` of initialize::bearing_vector::initialize
+ * (initialize/bearing_vector.cc:55-75; 100 iterations, recompute true), the initialiser of the fisheye and equirectangular models
+ * (module/initializer.cc:169-178), and `find_via_ransac(50, false)` of match::robust::match_frame_and_keyframe (match/robust.cc:233).
+ * Numeric contract: DESIGN.md section 5, D24 (the two Eigen::JacobiSVD uses by D14's written-down one-sided Jacobi on A^T A and on the 3 x 3
+ * matrix, the sign rule, f64 in the reference's order with the reference's float residuals and float score, the sample generator, what the
+ * reference leaves undefined).
+ *
+ * The constructor's match list is given in slot form, [P][n_cap], slot = key-point index in frame 1:
+ *   bearing_1   bearings_1_.at(idx1), [P][n_cap][3]; bearing_2: bearings_2_.at(idx2), [P][m_cap][3] (the post-extract step's layout)
+ *   match       the index in frame 2 or a negative number: plp_match_*'s out_match, init_matches_ (bearing_vector.cc:58-65)
+ * Match k of matches_12_ is the k-th matched slot in slot order (both callers list their matches in ascending idx1): that is what a sample
+ * index means.  A match value at or above counts_2[p] (where bearings_2_.at() throws) is no match.
+ *
+ * find_via_ransac (:37-119) runs `iters` hypotheses.  Hypothesis i takes the matches samples[p][i][0..7] in that order (:73-78), compute_E_21
+ * (:121-154) and check_inliers (:196-253).  samples == NULL: the library draws them from `seed` (the reference draws from
+ * std::random_device, util/random_array.cc:37-44: there is no order to reproduce; the generator is D24's, the same on host and device).  A
+ * caller's sample with an index outside [0, num_matches) or a repeated index gives a hypothesis of score 0, which cannot win.  The best
+ * hypothesis is the reference's: a strictly greater score wins (:87), so among equal scores the LOWEST iteration wins; a NaN score never
+ * wins.  recompute (:103-118): compute_E_21 once more over the inliers of the best hypothesis in match order and check_inliers once more;
+ * its matrix, score and flags are the outputs, and its inliers may be fewer than eight with the status still PLP_ESSENTIAL_OK, as in the
+ * reference.
+ * Outputs per problem:
+ *   out_status       a plp_essential_status
+ *   out_num_matches  matches_12_.size()
+ *   out_E_21 (9, row-major)   get_best_E_21(); zero unless PLP_ESSENTIAL_OK
+ *   out_score        best_score_ (a float sum of float residuals in match order); 0 unless PLP_ESSENTIAL_OK
+ *   out_num_inliers  the inlier matches of the matrix returned; 0 unless PLP_ESSENTIAL_OK
+ *   out_best_iter    the iteration that won; -1 unless PLP_ESSENTIAL_OK
+ *   out_inliers      optional, [P][n_cap] in slot order: is_inlier_match_ of the matrix returned (0 for a slot that is no match; all 0 unless
+ *                    PLP_ESSENTIAL_OK); slots at or above counts_1[p] keep the caller's values
+ *   out_hyp_score    optional, [P][iters]: the score of every hypothesis (0 for PLP_ESSENTIAL_TOO_FEW_MATCHES, where the loop does not run) */
+typedef enum plp_essential_status {
+    PLP_ESSENTIAL_OK = 0,               /* solution_is_valid_                                                                   :96 */
+    PLP_ESSENTIAL_TOO_FEW_MATCHES = 1,  /* num_matches < 8                                                                      :45 */
+    PLP_ESSENTIAL_INVALID = 2           /* !(best_score_ > 0.0 && num_inliers >= 8)                                             :96 */
+} plp_essential_status;
+typedef struct plp_essential_ransac_args {
+    int32_t P, n_cap, m_cap;        /* P >= 0 problems of n_cap >= 0 slots (key points of frame 1) against m_cap >= 0 key points of frame 2; n_cap <= 8192 */
+    int32_t iters;                  /* max_num_iter (:69), >= 1; 100 in the initialiser, 50 at robust.cc:233 */
+    int32_t recompute;              /* :98-118; true in the initialiser, false at robust.cc:233 */
+    uint64_t seed;                  /* samples == NULL: the generator's seed */
+    const int32_t* counts_1;        /* P: slots in use, or NULL = n_cap everywhere */
+    const int32_t* counts_2;        /* P: key points of frame 2, or NULL = m_cap everywhere */
+    const double* bearing_1;        /* P x n_cap x 3 (:76) */
+    const double* bearing_2;        /* P x m_cap x 3 (:77) */
+    const int32_t* match;           /* P x n_cap */
+    const int32_t* samples;         /* P x iters x 8 indices of matches (:72), or NULL = drawn from seed */
+    uint8_t* out_status;            /* P */
+    int32_t* out_num_matches;       /* P */
+    double* out_E_21;               /* P x 9 (:90, :117) */
+    float* out_score;               /* P (:89, :118) */
+    int32_t* out_num_inliers;       /* P */
+    int32_t* out_best_iter;         /* P */
+    uint8_t* out_inliers;           /* P x n_cap, or NULL (:91, :118) */
+    float* out_hyp_score;           /* P x iters, or NULL */
+} plp_essential_ransac_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; P < 0, n_cap < 0, m_cap < 0, iters < 1; and -- when P > 0 and
+ * n_cap > 0 -- a NULL bearing_1, match, bearing_2 (with m_cap > 0), out_status, out_num_matches, out_E_21, out_score, out_num_inliers or
+ * out_best_iter.  n_cap > 8192, P > 65535 or iters > 65536: PLP_ERR_UNSUPPORTED.  P == 0 or n_cap == 0: PLP_OK, nothing written.
+ * _device: every array a DEVICE pointer; five kernels on hip_stream, no host synchronisation; bad samples are never an error.  The kernels
+ * hand the match list, the hypotheses, the refit's bearing pairs and the inlier codes to one another through buffers the context owns, so
+ * the calls of one context must be ordered on the device: one stream, or events between streams.  _host: HOST pointers, staged (the
+ * outputs too, so that every slot the kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_essential_ransac_device(plp_matcher* ctx, const plp_essential_ransac_args* args, void* hip_stream);
+plp_status plp_essential_ransac_host(plp_matcher* ctx, const plp_essential_ransac_args* args);
+/* Host builds of the same source (csrc/essential.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_essential_ransac_host: the entry above, one problem and one hypothesis after the other; the same checks.  Returns P, or -1 for
+ * a bad argument (plp_last_error() names it).
+ * plp_model_essential_fit_host: compute_E_21 (:121-154) for n lists of bearing pairs: list i holds rows offsets[i] .. offsets[i+1] of
+ * bearing_1 / bearing_2.  out_E_21 n x 9, out_sweeps n x 2 (may be NULL; the 9 x 9 and the 3 x 3 Jacobi, 60 = the limit).  Returns n.
+ * plp_model_essential_check_host: check_inliers (:196-253) of n matrices E_21 (n x 9) against one problem (bearing_1 n_cap x 3, bearing_2
+ * m_cap x 3, match n_cap; a match outside [0, m_cap) is none): out_score n, out_num_inliers n, out_inliers n x n_cap in slot order (may be
+ * NULL).  Returns n.  Both return -1 for a bad argument. */
+int32_t plp_model_essential_ransac_host(const plp_essential_ransac_args* args);
+int32_t plp_model_essential_fit_host(const double* bearing_1, const double* bearing_2, const int32_t* offsets, int32_t n, double* out_E_21, int32_t* out_sweeps);
+int32_t plp_model_essential_check_host(const double* bearing_1, const double* bearing_2, const int32_t* match, int32_t n_cap, int32_t m_cap, const double* E_21,
+                                       int32_t n, float* out_score, int32_t* out_num_inliers, uint8_t* out_inliers);
+/* The samples the entries draw for problem p, iterations iter0 .. iter0 + n_iters - 1, of num_matches >= 8 matches (D24's generator):
+ * out n_iters x 8.  Returns n_iters, or -1 for a bad argument. */
+int32_t plp_model_essential_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_matches, int32_t* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Map initialisation, from the matrix to the pose: bearing_vector::reconstruct_with_E (src/PLPSLAM/initialize/bearing_vector.cc:84-107) for P
+ * frame pairs -- essential_solver::decompose (solve/essential_solver.cc:156-186) and initialize::base::find_most_plausible_pose with its four
+ * check_pose calls (initialize/base.cc:62-243; solve::triangulator::triangulate, solve/triangulator.h:86-103).  Numeric contract: DESIGN.md
+ * section 5, D24 items c, f and g.  The inputs are the outputs of plp_essential_ransac_* (E_21 <- out_E_21, inliers <- out_inliers, in_status
+ * <- out_status, the same match and bearing tables) and the post-extract step's undistorted key points of both frames (only pt is read), so
+ * the two entries chain on one stream without the host.
+ *
+ * The four hypotheses are (rot_1, t), (rot_1, -t), (rot_2, t), (rot_2, -t) (:182-183), with D24 item c's rule for what the singular-value
+ * routine leaves open; every inlier match is triangulated under each and passes the tests of check_pose in the reference's order.
+ * Outputs per problem:
+ *   out_status             a plp_two_view_status
+ *   out_rot_ref_to_cur (9, row-major) / out_trans_ref_to_cur (3)   zero unless PLP_TWO_VIEW_OK (base.cc:83-84)
+ *   out_hypothesis         0 .. 3, -1 unless PLP_TWO_VIEW_OK
+ *   out_num_valid [P][4]   nums_valid_pts; out_parallax_deg [P][4] (float): init_parallax; both zero for PLP_TWO_VIEW_NO_SOLUTION
+ *   out_triangulated_pts [P][n_cap][3], out_is_triangulated [P][n_cap]   triangulated_pts_ / is_triangulated_ of the chosen hypothesis,
+ *                          indexed by slot (the reference key point); all zero unless PLP_TWO_VIEW_OK; a point that is not triangulated
+ *                          (uninitialised in the reference) is zero; slots at or above counts_1[p] keep the caller's values
+ *   out_hyp_is_triangulated   optional, [P][4][n_cap]: the flags of all four hypotheses (zero for PLP_TWO_VIEW_NO_SOLUTION) */
+typedef enum plp_two_view_status {
+    PLP_TWO_VIEW_OK = 0,
+    PLP_TWO_VIEW_NO_SOLUTION = 1,           /* in_status[p] != 0: the RANSAC gave no matrix (bearing_vector.cc:72-81)                    */
+    PLP_TWO_VIEW_TOO_FEW_TRIANGULATED = 2,  /* base.cc:92 */
+    PLP_TWO_VIEW_AMBIGUOUS = 3,             /* base.cc:103 */
+    PLP_TWO_VIEW_SMALL_PARALLAX = 4         /* base.cc:109 */
+} plp_two_view_status;
+typedef struct plp_two_view_pose_args {
+    plp_camera_model camera;        /* camera_ of both frames: model, cols, rows, fx, fy, cx, cy, focal_x_baseline are read; all three models */
+    float img_bounds[4];            /* camera::base img_bounds_: min_x, max_x, min_y, max_y (what reproject_to_image of perspective / fisheye returns) */
+    int32_t P, n_cap, m_cap;        /* as plp_essential_ransac_args */
+    int32_t min_num_triangulated;   /* min_num_triangulated_ (base.cc:92), >= 0; 50 */
+    float parallax_deg_thr;         /* parallax_deg_thr_ (base.cc:109); 1.0 */
+    float reproj_err_thr;           /* reproj_err_thr_ (base.cc:130); 4.0 */
+    int32_t depth_is_positive;      /* base.cc:173-184; false at bearing_vector.cc:99 */
+    const int32_t* counts_1;        /* P, or NULL = n_cap everywhere */
+    const int32_t* counts_2;        /* P, or NULL = m_cap everywhere */
+    const uint8_t* in_status;       /* P, or NULL: a problem whose byte is not 0 (PLP_ESSENTIAL_OK) is PLP_TWO_VIEW_NO_SOLUTION */
+    const double* E_21;             /* P x 9, row-major */
+    const uint8_t* inliers;         /* P x n_cap: is_inlier_match in slot order */
+    const int32_t* match;           /* P x n_cap */
+    const double* bearing_1;        /* P x n_cap x 3 */
+    const double* bearing_2;        /* P x m_cap x 3 */
+    const plp_keypoint* undist_1;   /* P x n_cap: ref_undist_keypts_ (pt is read) */
+    const plp_keypoint* undist_2;   /* P x m_cap: cur_undist_keypts_ */
+    uint8_t* out_status;            /* P */
+    double* out_rot_ref_to_cur;     /* P x 9 */
+    double* out_trans_ref_to_cur;   /* P x 3 */
+    int32_t* out_hypothesis;        /* P */
+    int32_t* out_num_valid;         /* P x 4 */
+    float* out_parallax_deg;        /* P x 4 */
+    double* out_triangulated_pts;   /* P x n_cap x 3 */
+    uint8_t* out_is_triangulated;   /* P x n_cap */
+    uint8_t* out_hyp_is_triangulated;   /* P x 4 x n_cap, or NULL */
+} plp_two_view_pose_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; the camera as for plp_post_extract_model_* (unknown model, fx
+ * or fy 0, cols or rows <= 0); P < 0, n_cap < 0, m_cap < 0, min_num_triangulated < 0; and -- when P > 0 and n_cap > 0 -- a NULL E_21, inliers,
+ * match, bearing_1, undist_1, bearing_2 or undist_2 (with m_cap > 0), out_status, out_rot_ref_to_cur, out_trans_ref_to_cur, out_hypothesis,
+ * out_num_valid, out_parallax_deg, out_triangulated_pts or out_is_triangulated.  n_cap > 8192 or P > 65535: PLP_ERR_UNSUPPORTED.  P == 0 or
+ * n_cap == 0: PLP_OK, nothing written.
+ * _device: every array a DEVICE pointer; one kernel on hip_stream, no host synchronisation.  The points and flags of the four hypotheses
+ * wait in buffers the context owns, so the calls of one context must be ordered on the device: one stream, or events between streams.
+ * _host: HOST pointers, staged (the outputs too, so that every slot the kernel does not write keeps the caller's value), the same kernel,
+ * synchronous. */
+plp_status plp_two_view_pose_device(plp_matcher* ctx, const plp_two_view_pose_args* args, void* hip_stream);
+plp_status plp_two_view_pose_host(plp_matcher* ctx, const plp_two_view_pose_args* args);
+/* Host builds of the same source (csrc/two_view.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_two_view_pose_host: the entry above, one problem after the other; the same checks.  Returns P, or -1 for a bad argument.
+ * plp_model_essential_decompose_host: decompose for n matrices (n x 9): out_rots n x 2 x 9 (rot_1, rot_2), out_trans n x 3.  Returns n.
+ * plp_model_check_pose_host: check_pose of ONE (rot 9, trans 3) against problem 0 of args (its E_21, in_status and outputs are not read):
+ * out_num_valid 1, out_parallax_deg 1, out_pts n_cap x 3, out_is_triangulated n_cap, out_code n_cap (may be NULL: per slot 0 = no inlier
+ * match, 1 .. 7 = the `continue` of base.cc:158, 175, 180, 194, 200, 210, 215 that the match takes, 8 = valid with a small parallax, 9 =
+ * valid and triangulated).  Returns 1, or -1. */
+int32_t plp_model_two_view_pose_host(const plp_two_view_pose_args* args);
+int32_t plp_model_essential_decompose_host(const double* E_21, int32_t n, double* out_rots, double* out_trans);
+int32_t plp_model_check_pose_host(const plp_two_view_pose_args* args, const double* rot, const double* trans, int32_t* out_num_valid, float* out_parallax_deg,
+                                  double* out_pts, uint8_t* out_is_triangulated, uint8_t* out_code);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Per-frame pose optimisation: optimize::pose_optimizer::optimize (src/PLPSLAM/optimize/pose_optimizer.cc:53-229) and
  * optimize::pose_optimizer_extended_line::optimize (optimize/pose_optimizer_extended_line.cc:62-305) for B frames at once, in slot form --
  * what the tracker runs after the last-frame match (module/frame_tracker.cc:83-96), after the local-map match (tracking_module.cc:750-759)

@@ -26,6 +26,10 @@ from ._abi import *        # noqa: F401,F403  every struct mirror, record dtype,
 from ._abi import _struct
 from ._global_ba import (GLOBAL_BA_OUTPUTS, LOOP_BA_PROPAGATE_OUTPUTS, _chol_dense, _global_ba_host, _global_ba_kw, _loop_ba_propagate_host, global_bundle_adjuster,
                          loop_bundle_adjuster, model_chol_dense, model_global_ba, model_loop_ba_propagate)
+from ._essential import (ESSENTIAL_OUTPUTS, _essential_ransac_host, essential_solver, model_essential_check, model_essential_draw, model_essential_fit,
+                         model_essential_ransac)
+from ._two_view import (TWO_VIEW_OUTPUTS, _two_view_pose_host, bearing_vector_initializer, model_check_pose, model_essential_decompose, model_two_view_pose,
+                        two_view_args)
 from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, stream_handle, wanted
 
 
@@ -2695,6 +2699,48 @@ class matcher:
             dev_ptrs(counts=counts, valid=valid, bearing=bearing, pos_w=pos_w, octave=octave, samples=samples), scale_factors=host_ptr(sf)))
         set_outputs(a, PNP_OUTPUTS, out, dev_ptr)
         self._device("plp_pnp_ransac_device", a, stream)
+
+    def essential_ransac(self, bearing_1, bearing_2, match, iters=100, recompute=True, samples=None, seed=0, counts_1=None, counts_2=None, outputs=None,
+                         out=None):
+        """solve::essential_solver's find_via_ransac for P pairs of frames (plp_essential_ransac_host; DESIGN.md section 5, D24): bearing_1
+        (P, n_cap, 3) / bearing_2 (P, m_cap, 3) f64, match (P, n_cap) i32: the index in frame 2 or a negative number, samples (P, iters, 8)
+        indices of matches or None = drawn from seed, counts_1 / counts_2 (P,) or None.  Returns dict(status (P,) u8: ESSENTIAL_*, num_matches,
+        E_21 (P, 3, 3), score (P,) f32, num_inliers, best_iter, inliers (P, n_cap) u8, hyp_score (P, iters) f32); `outputs` names the optional
+        ones wanted (default both); out[name]: the caller's array."""
+        return _essential_ransac_host(self._host("plp_essential_ransac_host"), bearing_1, bearing_2, match, iters, recompute, samples, seed, counts_1, counts_2,
+                                      outputs, out)
+
+    def essential_ransac_device(self, P, n_cap, m_cap, bearing_1, bearing_2, match, out, iters=100, recompute=True, samples=None, seed=0, counts_1=None,
+                                counts_2=None, stream=None):
+        """plp_essential_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device; out: dict of the device
+        outputs named as in ESSENTIAL_OUTPUTS (inliers / hyp_score may be absent); asynchronous, five kernels on the stream"""
+        a = _struct(essential_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), m_cap=int(m_cap), iters=int(iters), recompute=int(bool(recompute)),
+                                                  seed=int(seed) & 0xFFFFFFFFFFFFFFFF),
+                    dev_ptrs(counts_1=counts_1, counts_2=counts_2, bearing_1=bearing_1, bearing_2=bearing_2, match=match, samples=samples))
+        set_outputs(a, ESSENTIAL_OUTPUTS, out, dev_ptr)
+        self._device("plp_essential_ransac_device", a, stream)
+
+    def two_view_pose(self, camera, E_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2, min_num_triangulated=50, parallax_deg_thr=1.0,
+                      reproj_err_thr=4.0, depth_is_positive=False, in_status=None, counts_1=None, counts_2=None, img_bounds=None, outputs=None, out=None):
+        """bearing_vector::reconstruct_with_E for P frame pairs (plp_two_view_pose_host; DESIGN.md section 5, D24): camera a camera_model, E_21
+        (P, 3, 3), inliers (P, n_cap) u8 and match (P, n_cap) i32 as matcher.essential_ransac gives and takes them, bearing_1 (P, n_cap, 3) /
+        bearing_2 (P, m_cap, 3), undist_1 (P, n_cap) / undist_2 (P, m_cap) KP_DTYPE, in_status (P,) u8 or None: the RANSAC's status.  Returns
+        dict(status (P,) u8: TWO_VIEW_*, rot_ref_to_cur (P, 3, 3), trans_ref_to_cur (P, 3), hypothesis, num_valid (P, 4), parallax_deg (P, 4) f32,
+        triangulated_pts (P, n_cap, 3), is_triangulated (P, n_cap) u8, hyp_is_triangulated (P, 4, n_cap) u8)."""
+        return _two_view_pose_host(self._host("plp_two_view_pose_host"), camera, E_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2,
+                                   min_num_triangulated, parallax_deg_thr, reproj_err_thr, depth_is_positive, in_status, counts_1, counts_2, img_bounds, outputs, out)
+
+    def two_view_pose_device(self, camera, P, n_cap, m_cap, E_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2, out, min_num_triangulated=50,
+                             parallax_deg_thr=1.0, reproj_err_thr=4.0, depth_is_positive=False, in_status=None, counts_1=None, counts_2=None, img_bounds=None,
+                             stream=None):
+        """plp_two_view_pose_device: every array a device pointer (int) or a torch tensor on the matcher's device; out: dict of the device outputs
+        named as in TWO_VIEW_OUTPUTS (hyp_is_triangulated may be absent); asynchronous, one kernel on the stream"""
+        a = two_view_args(camera, dict(P=int(P), n_cap=int(n_cap), m_cap=int(m_cap), min_num_triangulated=int(min_num_triangulated),
+                                       parallax_deg_thr=float(parallax_deg_thr), reproj_err_thr=float(reproj_err_thr), depth_is_positive=int(bool(depth_is_positive))),
+                          dev_ptrs(counts_1=counts_1, counts_2=counts_2, in_status=in_status, E_21=E_21, inliers=inliers, match=match, bearing_1=bearing_1,
+                                   bearing_2=bearing_2, undist_1=undist_1, undist_2=undist_2), img_bounds)
+        set_outputs(a, TWO_VIEW_OUTPUTS, out, dev_ptr)
+        self._device("plp_two_view_pose_device", a, stream)
 
     def pose_optimize(self, camera, setup_type, pose_in, valid, undist, pos_w, inv_level_sigma_sq, x_right=None, counts=None, lines=None, num_trials=4,
                       num_each_iter=10, outputs=None, out=None):

@@ -185,6 +185,23 @@ class pnp_ransac_args_c(C.Structure):
                 ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP), ("out_hyp_inliers", _VP)]
 
 
+class essential_ransac_args_c(C.Structure):
+    """plp_essential_ransac_args"""
+    _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32), ("seed", C.c_uint64),
+                ("counts_1", _VP), ("counts_2", _VP), ("bearing_1", _VP), ("bearing_2", _VP), ("match", _VP), ("samples", _VP), ("out_status", _VP),
+                ("out_num_matches", _VP), ("out_E_21", _VP), ("out_score", _VP), ("out_num_inliers", _VP), ("out_best_iter", _VP), ("out_inliers", _VP),
+                ("out_hyp_score", _VP)]
+
+
+class two_view_pose_args_c(C.Structure):
+    """plp_two_view_pose_args"""
+    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("P", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
+                ("min_num_triangulated", C.c_int32), ("parallax_deg_thr", C.c_float), ("reproj_err_thr", C.c_float), ("depth_is_positive", C.c_int32),
+                ("counts_1", _VP), ("counts_2", _VP), ("in_status", _VP), ("E_21", _VP), ("inliers", _VP), ("match", _VP), ("bearing_1", _VP), ("bearing_2", _VP),
+                ("undist_1", _VP), ("undist_2", _VP), ("out_status", _VP), ("out_rot_ref_to_cur", _VP), ("out_trans_ref_to_cur", _VP), ("out_hypothesis", _VP),
+                ("out_num_valid", _VP), ("out_parallax_deg", _VP), ("out_triangulated_pts", _VP), ("out_is_triangulated", _VP), ("out_hyp_is_triangulated", _VP)]
+
+
 class pose_optimize_args_c(C.Structure):
     """plp_pose_optimize_args"""
     _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("B", C.c_int32), ("n_cap", C.c_int32), ("l_cap", C.c_int32),
@@ -367,6 +384,12 @@ PLANE_FLAG_INVALID, PLANE_FLAG_NEED_REFINEMENT, PLANE_FLAG_GATED = 1, 2, 4
 
 # plp_pnp_status: where pnp_solver::find_via_ransac leaves a problem
 PNP_OK, PNP_TOO_FEW_MATCHES, PNP_TOO_FEW_INLIERS = range(3)
+
+
+# plp_essential_status: where essential_solver::find_via_ransac leaves a problem
+ESSENTIAL_OK, ESSENTIAL_TOO_FEW_MATCHES, ESSENTIAL_INVALID = range(3)
+# plp_two_view_status: where bearing_vector::reconstruct_with_E leaves a problem
+TWO_VIEW_OK, TWO_VIEW_NO_SOLUTION, TWO_VIEW_TOO_FEW_TRIANGULATED, TWO_VIEW_AMBIGUOUS, TWO_VIEW_SMALL_PARALLAX = range(5)
 
 
 # plp_pose_opt_status: where pose_optimizer::optimize leaves a frame

@@ -145,6 +145,17 @@ _API = [
     ("plp_model_rot_from_abt_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_model_pnp_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
     ("plp_model_pnp_thresholds_host", _I32, [_VP, _I32, _VP]),
+    ("plp_essential_ransac_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_essential_ransac_host", C.c_int, [_VP, _VP]),
+    ("plp_model_essential_ransac_host", _I32, [_VP]),
+    ("plp_model_essential_fit_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_model_essential_check_host", _I32, [_VP, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
+    ("plp_model_essential_draw_host", _I32, [C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
+    ("plp_two_view_pose_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_two_view_pose_host", C.c_int, [_VP, _VP]),
+    ("plp_model_two_view_pose_host", _I32, [_VP]),
+    ("plp_model_essential_decompose_host", _I32, [_VP, _I32, _VP, _VP]),
+    ("plp_model_check_pose_host", _I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_pose_optimize_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_pose_optimize_host", C.c_int, [_VP, _VP]),
     ("plp_model_pose_optimize_host", _I32, [_VP]),
