@@ -2595,6 +2595,120 @@ plp_status plp_correct_landmarks_device(plp_matcher* ctx, const plp_correct_land
 plp_status plp_correct_landmarks_host(plp_matcher* ctx, const plp_correct_landmarks_args* args);
 int32_t plp_model_correct_landmarks_host(const plp_correct_landmarks_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * The line map update every optimiser of the reference ends with (csrc/line_update.hpp): the two Pluecker
+ * transforms of loop closing and the end-point trimming all four optimisers share.
+ *
+ * plp_trim_line_endpoints_*: endpoint_trimming (optimize/graph_optimizer.cc:424-532, module/loop_bundle_adjuster.cc:269-,
+ * optimize/global_bundle_adjuster.cc:362-, optimize/local_bundle_adjuster_extended_line.cc:676-787) for L lines over a table of F key
+ * frames, and the array half of what every call site does with its result: the Pluecker line pluecker[l] = (m, d) is reprojected into its
+ * reference key frame with that key frame's CURRENT pose row, l = _K (transformation_line_cw L)(0..2), the key line's start and end point
+ * are moved to their closest points on l, and the planes through them and the points on the x = 0 axis are intersected with the line's
+ * Pluecker matrix (line3d_trim, D7).  The key line is keylines[ref_kf][idx], idx = obs_idx of the first observation whose obs_kf is
+ * ref_kf (get_index_in_keyframe), -1 where there is none.
+ *   PLP_TRIM_DEPTH_POSITIVE  accepted when 0 < z_c(sp) && 0 < z_c(ep) in the reference key frame (the graph, loop and global adjusters)
+ *   PLP_TRIM_MAX_CHANGE      rejected when |sp - sp_old| / median_depth[ref_kf] > max_change || |ep - ep_old| / median_depth[ref_kf] >
+ *                            max_change, the local adjuster's test (:773-786; no depth test); median_depth is what plp_median_depth_*
+ *                            writes with abs_flag
+ * A comparison with a NaN is false, as in the reference: DEPTH_POSITIVE rejects such a line, MAX_CHANGE accepts it.
+ *   out_status  [L] a plp_trim_status, where the reference leaves the function, in its order of evaluation
+ *   out_pos_w   [L][6] (sp, ep), written only where the status is PLP_TRIM_OK (set_pos_in_world_without_update_pluecker); may be pos_w_old
+ *   out_erase   [L] 1 for NOT_OBSERVED and REJECTED (prepare_for_erasing), else 0 */
+typedef enum plp_trim_mode { PLP_TRIM_DEPTH_POSITIVE = 0, PLP_TRIM_MAX_CHANGE = 1 } plp_trim_mode;
+typedef enum plp_trim_status {
+    PLP_TRIM_OK = 0,
+    PLP_TRIM_SKIPPED = 1,               /* skip[l]: the caller never reaches the trim                                                   */
+    PLP_TRIM_NO_REF = 2,                /* ref_kf outside [0, F) or erased: the reference follows a pointer it does not hold           */
+    PLP_TRIM_NOT_OBSERVED = 3,          /* idx == -1: the trim returns false                                                            */
+    PLP_TRIM_INDEX_RANGE = 4,           /* idx outside [0, counts[ref_kf]), where _keylsd.at() throws                                   */
+    PLP_TRIM_REJECTED = 5               /* the mode's test                                                                              */
+} plp_trim_status;
+typedef struct plp_trim_line_endpoints_args {
+    plp_camera_model camera;            /* PLP_CAMERA_PERSPECTIVE (the trim static_casts to camera::perspective); fx, fy, cx, cy are read */
+    int32_t mode;                       /* a plp_trim_mode */
+    double max_change;                  /* PLP_TRIM_MAX_CHANGE: 0.1 at :777 */
+    int32_t L, F, cap, pose_stride;     /* L >= 0 lines, F >= 0 key frames of cap >= 0 key-line slots, pose_stride >= 12 */
+    const double* pluecker;             /* L x 6: (m, d), what set_PlueckerCoord_without_update_endpoints took */
+    const int32_t* ref_kf;              /* L: the reference key frame as a row of the table */
+    const uint8_t* skip;                /* L, or NULL = none */
+    const int32_t* obs_offsets;         /* L + 1, non-decreasing from 0: the layout of plp_landmark_geometry_args */
+    const int32_t* obs_kf;              /* obs_offsets[L] */
+    const int32_t* obs_idx;             /* obs_offsets[L] */
+    const double* pose;                 /* F x pose_stride: rot_cw (row-major), trans_cw */
+    const uint8_t* kf_erased;           /* F, or NULL */
+    const plp_keyline* keylines;        /* F x cap: _keylsd; only the start and the end point are read */
+    const int32_t* counts;              /* F: _keylsd.size(), or NULL = cap everywhere */
+    const double* pos_w_old;            /* PLP_TRIM_MAX_CHANGE: L x 6, get_pos_in_world() */
+    const float* median_depth;          /* PLP_TRIM_MAX_CHANGE: F, compute_median_depth(true) */
+    double* out_pos_w;                  /* L x 6 */
+    uint8_t* out_status;                /* L */
+    uint8_t* out_erase;                 /* L */
+} plp_trim_line_endpoints_args;
+/* Checked before anything is written: PLP_ERR_INVALID_ARG for NULL ctx / args, an unknown camera model or mode, fx or fy 0 or a non-finite
+ * fx, fy, cx, cy, a negative L, F or cap, pose_stride < 12, and -- when L > 0 -- a NULL pluecker, ref_kf, obs_offsets, out_pos_w, out_status
+ * or out_erase, a NULL pose (F > 0), a NULL keylines (F > 0 and cap > 0), a NULL pos_w_old or median_depth (F > 0) in PLP_TRIM_MAX_CHANGE;
+ * PLP_ERR_UNSUPPORTED for a camera that is not perspective.  L == 0: PLP_OK, nothing written.  _host and the host build also check that
+ * obs_offsets rises from 0 (PLP_ERR_INVALID_ARG); obs_kf / obs_idx may be NULL when it ends at 0.
+ * _device: DEVICE pointers, one lane per line (k_trim_line_endpoints), asynchronous.  _host: HOST pointers, staged (the outputs too), the
+ * same kernel, synchronous.  plp_model_*_host: the host build of csrc/line_update.hpp, no GPU; returns L, or the negated plp_status. */
+plp_status plp_trim_line_endpoints_device(plp_matcher* ctx, const plp_trim_line_endpoints_args* args, void* hip_stream);
+plp_status plp_trim_line_endpoints_host(plp_matcher* ctx, const plp_trim_line_endpoints_args* args);
+int32_t plp_model_trim_line_endpoints_host(const plp_trim_line_endpoints_args* args);
+
+/* The line cloud of graph_optimizer::optimize (:352-403): out_pluecker[l] = (corrected_Sim3_wc_pluecker * Sim3_cw_pluecker) * pluecker[l],
+ * each 6 x 6 matrix [s R, skew(t) R; 0, R] of the Sim3 of row corr_kf[l] (R = rotation().toRotationMatrix(), t the Sim3's translation); the
+ * product of the two matrices is formed first.  ref_kf[l] is the row the reference tests (:362-373), corr_kf[l] the row the caller resolves
+ * (:375-377).  out_pluecker may be pluecker; only an OK line's coordinates are written.  The trim of :407-417 is plp_trim_line_endpoints_*
+ * on the same stream, with the corrected poses. */
+typedef enum plp_correct_line_status {
+    PLP_CORRECT_LINE_OK = 0,
+    PLP_CORRECT_LINE_ERASED = 1,        /* lm_erased[l] (:357-360)                                                                       */
+    PLP_CORRECT_LINE_NO_REF = 2,        /* ref_kf outside [0, F) or erased: prepare_for_erasing (:362-373)                              */
+    PLP_CORRECT_LINE_NO_VERTEX = 3      /* corr_kf outside [0, F) or erased, where Sim3s_cw.at(id) throws                               */
+} plp_correct_line_status;
+typedef struct plp_correct_landmark_lines_args {
+    int32_t L, F;                       /* F <= 1024 */
+    const double* pluecker;             /* L x 6 */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const int32_t* ref_kf;              /* L */
+    const int32_t* corr_kf;             /* L, or NULL = ref_kf */
+    const uint8_t* kf_erased;           /* F, or NULL */
+    const double* sim3_cw;              /* F x 8 */
+    const double* corrected_wc;         /* F x 8 */
+    double* out_pluecker;               /* L x 6 */
+    uint8_t* out_status;                /* L */
+} plp_correct_landmark_lines_args;
+/* The checks of plp_correct_landmarks_*.  _device: DEVICE pointers, one lane per line (k_correct_landmark_lines), asynchronous.  _host: HOST
+ * pointers, staged, synchronous.  The host build returns L, or the negated plp_status. */
+plp_status plp_correct_landmark_lines_device(plp_matcher* ctx, const plp_correct_landmark_lines_args* args, void* hip_stream);
+plp_status plp_correct_landmark_lines_host(plp_matcher* ctx, const plp_correct_landmark_lines_args* args);
+int32_t plp_model_correct_landmark_lines_host(const plp_correct_landmark_lines_args* args);
+
+/* The line cloud of loop_bundle_adjuster::optimize (:184-244) over what plp_loop_ba_propagate_* wrote: an optimised line takes
+ * pluecker_after[l] (_pos_w_after_global_BA); any other line that is not erased goes L_c = T(pose_before[ref]) L, L_w = T(inverse of
+ * pose_after[ref]) L_c, T(R, t) = [R, skew(t) R; 0, R], the inverse as set_cam_pose stores it (rot_cw transposed, cam_center).
+ * out_status [L]: a plp_loop_ba_lm_status, NO_REF for a ref_kf outside the table or with a kf_status neither OPTIMIZED nor PROPAGATED;
+ * out_pluecker [L][6] for OPTIMIZED and MOVED rows only, may be pluecker. */
+typedef struct plp_loop_ba_propagate_lines_args {
+    int32_t L, F;                       /* F <= 4096 */
+    const double* pose_after;           /* F x 15: plp_loop_ba_propagate_args.out_pose */
+    const double* pose_before;          /* F x 12: plp_loop_ba_propagate_args.out_pose_before */
+    const uint8_t* kf_status;           /* F: plp_loop_ba_propagate_args.out_kf_status */
+    const double* pluecker;             /* L x 6 */
+    const uint8_t* lm_erased;           /* L, or NULL */
+    const int32_t* ref_kf;              /* L */
+    const uint8_t* line_optimized;      /* L, or NULL = none: _loop_BA_identifier == identifier */
+    const double* pluecker_after;       /* L x 6; may be NULL when line_optimized is */
+    double* out_pluecker;               /* L x 6 */
+    uint8_t* out_status;                /* L */
+} plp_loop_ba_propagate_lines_args;
+/* PLP_ERR_INVALID_ARG: NULL ctx / args, negative L or F, a NULL required array of non-zero size; PLP_ERR_UNSUPPORTED for F > 4096.
+ * _device: DEVICE pointers, one lane per line (k_loop_ba_propagate_lines), asynchronous.  _host: HOST pointers, staged, synchronous.  The
+ * host build returns L, or the negated plp_status. */
+plp_status plp_loop_ba_propagate_lines_device(plp_matcher* ctx, const plp_loop_ba_propagate_lines_args* args, void* hip_stream);
+plp_status plp_loop_ba_propagate_lines_host(plp_matcher* ctx, const plp_loop_ba_propagate_lines_args* args);
+int32_t plp_model_loop_ba_propagate_lines_host(const plp_loop_ba_propagate_lines_args* args);
+
 /* landmark::compute_descriptor (src/PLPSLAM/data/landmark.cc:181-245) and Line::compute_descriptor
  * (data/landmark_line.cc:256-320), the search part, for L landmarks at once: landmark l owns the
  * descriptors descs[offsets[l] .. offsets[l+1]) (32 B rows, observation order); best_idx[l] = the row (relative to

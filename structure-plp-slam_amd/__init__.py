@@ -30,6 +30,10 @@ from ._essential import (ESSENTIAL_OUTPUTS, _essential_ransac_host, essential_so
                          model_essential_ransac)
 from ._two_view import (TWO_VIEW_OUTPUTS, _two_view_pose_host, bearing_vector_initializer, model_check_pose, model_essential_decompose, model_two_view_pose,
                         two_view_args)
+from ._line_update import (CORRECT_LINE_ERASED, CORRECT_LINE_NO_REF, CORRECT_LINE_NO_VERTEX, CORRECT_LINE_OK, LINE_MOVE_OUTPUTS, TRIM_DEPTH_POSITIVE, TRIM_INDEX_RANGE,
+                           TRIM_MAX_CHANGE, TRIM_MAX_CHANGE_THR, TRIM_NO_REF, TRIM_NOT_OBSERVED, TRIM_OK, TRIM_OUTPUTS, TRIM_REJECTED, TRIM_SKIPPED,
+                           correct_landmark_lines_args_c, line_update_entries, loop_ba_propagate_lines_args_c, model_correct_landmark_lines,
+                           model_loop_ba_propagate_lines, model_trim_line_endpoints, trim_line_endpoints_args_c)
 from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, stream_handle, wanted
 
 
@@ -1964,7 +1968,7 @@ def match_plan(mode, B, n_cap, m_cap, grid=None, t_x_right=False, t_count_hint=0
     return MATCH_PLAN_TOPK[int(out[0])], MATCH_PLAN_FAMILY[int(out[1])], int(out[2]), MATCH_PLAN_RESOLVE[int(out[3])]
 
 
-class matcher:
+class matcher(line_update_entries):
     """Array-form mirror of match::projection / match::robust (value-constructed with (lowe_ratio, check_orientation)
     at every call site of the reference, match/base.h:94-110)."""
 

@@ -219,6 +219,15 @@ _API = [
     ("plp_correct_landmarks_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_correct_landmarks_host", C.c_int, [_VP, _VP]),
     ("plp_model_correct_landmarks_host", _I32, [_VP]),
+    ("plp_trim_line_endpoints_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_trim_line_endpoints_host", C.c_int, [_VP, _VP]),
+    ("plp_model_trim_line_endpoints_host", _I32, [_VP]),
+    ("plp_correct_landmark_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_correct_landmark_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_model_correct_landmark_lines_host", _I32, [_VP]),
+    ("plp_loop_ba_propagate_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_loop_ba_propagate_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_model_loop_ba_propagate_lines_host", _I32, [_VP]),
     ("plp_global_ba_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_global_ba_host", C.c_int, [_VP, _VP]),
     ("plp_model_global_ba_host", _I32, [_VP]),

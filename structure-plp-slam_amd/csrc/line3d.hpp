@@ -9,7 +9,7 @@
 namespace plp {
 
 // Eigen 3.3 MatrixBase::cross: (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0)
-__device__ __forceinline__ void line3d_cross(const double (&a)[3], const double (&b)[3], double (&r)[3]) {
+__host__ __device__ __forceinline__ void line3d_cross(const double (&a)[3], const double (&b)[3], double (&r)[3]) {
     r[0] = a[1] * b[2] - a[2] * b[1];
     r[1] = a[2] * b[0] - a[0] * b[2];
     r[2] = a[0] * b[1] - a[1] * b[0];
@@ -17,19 +17,19 @@ __device__ __forceinline__ void line3d_cross(const double (&a)[3], const double 
 
 // line^T * P (Vec4_t plane = line.transpose() * P) and P^T * line (Vec4_t plane = P.transpose() * line): the same sums,
 // plane(j) = (line(0) P(0,j) + line(1) P(1,j)) + line(2) P(2,j); P is 3 x 4 row-major
-__device__ __forceinline__ void line3d_plane(const double (&P)[12], const double (&l)[3], double (&pl)[4]) {
+__host__ __device__ __forceinline__ void line3d_plane(const double (&P)[12], const double (&l)[3], double (&pl)[4]) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) pl[j] = (l[0] * P[j] + l[1] * P[4 + j]) + l[2] * P[8 + j];
 }
 
-__device__ __forceinline__ bool line3d_finite(double v) { return isfinite(v); }
+__host__ __device__ __forceinline__ bool line3d_finite(double v) { return __builtin_isfinite(v); }
 
 // One end point p of view 1 trimmed to the 3-D line (Pluecker matrix M, 4 x 4 row-major; l = its reprojection into view 1, den = l1 l1 + l2 l2):
 //   x_closet = -(p.y - (l2 / l1) * p.x + (l3 / l2)) * ((l1 * l2) / (l1 * l1 + l2 * l2)),  y_closet = -(l1 / l2) * x_closet - (l3 / l2)
 //   x_0 = 0, y_0 = p.y - (l2 / l1) * p.x;  line_temp = (x_closet, y_closet, 1).cross((x_0, y_0, 1));  plane3d_temp = P1^T * line_temp
 //   intersect_endpoint = M * plane3d_temp (row sums left to right);  out = intersect_endpoint(0..2) / intersect_endpoint(3)
 // Returns false when the intersection or the end point is not finite.
-__device__ __forceinline__ bool line3d_trim(const double (&P1)[12], const double (&M)[16], double l1, double l2, double l3, double den, float px,
+__host__ __device__ __forceinline__ bool line3d_trim(const double (&P1)[12], const double (&M)[16], double l1, double l2, double l3, double den, float px,
                                             float py, double (&out)[3]) {
     const double x = (double)px, y = (double)py;
     const double xc = -((y - (l2 / l1) * x) + (l3 / l2)) * ((l1 * l2) / den);

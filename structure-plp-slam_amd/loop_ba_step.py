@@ -8,22 +8,29 @@ D23), over the tables local_ba_step and loop_correction_step share:
   2  plp_loop_ba_propagate_device    the correction along kf_parent from the origin; every landmark to its new position                  :109-181
   3  torch, on the stream            pose and pos_w <- the rows step 2 wrote, in place (set_cam_pose, set_pos_in_world)
   4  plp_landmark_geometry_device    landmark::update_normal_and_depth: normal, min_dist, max_dist
+  5  plp_loop_ba_propagate_lines_device  with `lines`: an optimised line takes pluecker_after, any other moves with its reference key frame       :184-244
+  6  line_map_update_step            the end points trimmed against the poses after the correction (depth mode), written back under the status,
+                                     the erased lines flagged in skip_lines, Line::update_information                                    :200-212, :244-256
 
 Step 1 is synchronous with respect to the stream (the entry reads the run's record back after every try); steps 2 - 4 are enqueued.  Nothing branches
 on the host: the step's `optimized` bytes start every run as zero, so a run that `stop` ended (status GLOBAL_BA_STOPPED) reaches no key frame in step 2
-and every table keeps its values.  What stays on the host: the pause of the mapper, the mutexes, loop_BA_identifier_, every line landmark.
+and every table keeps its values.  With `lines` the line cloud follows on the same stream (a stopped run moves and trims no
+line either); without it the step enqueues the four steps above and nothing else.  What stays on the host: the pause of the mapper, the mutexes,
+loop_BA_identifier_, and the line vertices of the adjustment itself: whoever ran them hands line_optimized and pluecker_after in.
 
 Tables are torch tensors on the step's device:
   key frames  pose [F, 15] f64 (updated in place), kps [F, cap, 28] u8, x_right [F, cap] f32 or absent, counts [F] or absent, kf_erased [F] u8 or absent,
               kf_is_origin [F] u8, kf_parent [F] i32
   landmarks   pos_w [L, 3] f64 (updated in place), ref_kf [L] i32, skip [L] u8 or absent (will_be_erased), obs_offsets [L + 1], obs_kf / obs_idx [T] i32, and
               the tables normal [L, 3] f64, min_dist / max_dist [L] f32 (updated in place; a missing one is created zero-filled)
+  lines       the tables of line_map_update_step, and line_optimized [LL] u8 with pluecker_after [LL, 6] f64 or both absent = no line was optimised; the key
+              lines kl [F, lcap, 68] u8 and kl_counts are read from `keyframes`
 """
 import numpy as np
 
 
 class loop_ba_step:
-    def __init__(self, plp, camera, setup_type, inv_level_sigma_sq, num_iter=10, scale_factor=1.2, device_index=0, mt=None):
+    def __init__(self, plp, camera, setup_type, inv_level_sigma_sq, num_iter=10, scale_factor=1.2, device_index=0, mt=None, scale_factor_lsd=2.0, num_levels_lsd=1):
         import torch
         self.torch, self.plp = torch, plp
         self.dev = torch.device("cuda", device_index)
@@ -35,6 +42,9 @@ class loop_ba_step:
         self.sf = sf
         self.mt = mt or plp.matcher(device=device_index)
         self._bufs = {}
+        self._line_args = dict(camera=camera, scale_factor=scale_factor, num_levels=len(self.sigma), scale_factor_lsd=scale_factor_lsd, num_levels_lsd=num_levels_lsd,
+                               device_index=device_index)
+        self._line_step = None
 
     def _buf(self, name, shape, dtype):
         t = self._bufs.get(name)
@@ -43,10 +53,33 @@ class loop_ba_step:
             self._bufs[name] = t
         return t
 
-    def run(self, keyframes, landmarks, stop=None, stream=None):
+    def _lines(self, keyframes, lines, ba, pr, st):
+        """steps 5 and 6: dict(line_status [LL] u8: LOOP_BA_LM_*, and what line_map_update_step.run returns)"""
+        import importlib
+        torch, plp = self.torch, self.plp
+        if self._line_step is None:
+            mod = importlib.import_module(__package__ + ".line_map_update_step")
+            self._line_step = mod.line_map_update_step(plp, mt=self.mt, **self._line_args)
+        pk = lines["pluecker_lines"]
+        LL, F = pk.shape[0], keyframes["pose"].shape[0]
+        pk_new, lst = self._buf("pluecker_new", (LL, 6), torch.float64), self._buf("line_status", (LL,), torch.uint8)
+        with torch.cuda.stream(st):
+            pk_new.copy_(pk)
+        if LL:
+            self.mt.loop_ba_propagate_lines_device(LL, F, pr["pose"], pr["pose_before"], pr["kf_status"], pk, lines["ref_kf_lines"], pk_new, lst,
+                                                   line_optimized=lines.get("line_optimized"), pluecker_after=lines.get("pluecker_after"),
+                                                   lm_erased=lines.get("skip_lines"), stream=st)
+        with torch.cuda.stream(st):
+            ran = ba["status"][0] != plp.GLOBAL_BA_STOPPED
+            moved = (((lst == plp.LOOP_BA_LM_OPTIMIZED) | (lst == plp.LOOP_BA_LM_MOVED)) & ran).to(torch.uint8)
+        r = self._line_step.run(keyframes, lines, mode=plp.TRIM_DEPTH_POSITIVE, pluecker=pk_new, moved=moved, stream=st)
+        return dict(r, line_status=lst)
+
+    def run(self, keyframes, landmarks, stop=None, stream=None, lines=None):
         """Returns dict(status [1] u8: GLOBAL_BA_*, info [4], chi2 [3], kf_optimized [F], lm_optimized [L], kf_status [F] u8: LOOP_BA_KF_*, lm_status [L] u8:
         LOOP_BA_LM_*, pose_before [F, 12], geometry_status [L] u8 -- the step's own buffers, rewritten by the next run -- and pose, pos_w, normal, min_dist,
-        max_dist: the caller's tables, which local_map_step reads next).  stop: None or a host int32 array of one element."""
+        max_dist: the caller's tables, which local_map_step reads next; with `lines` also line_status [LL] u8: LOOP_BA_LM_* and the results of
+        line_map_update_step.run).  stop: None or a host int32 array of one element."""
         torch = self.torch
         st = stream or torch.cuda.current_stream(self.dev)
         f64, f32, i32, u8 = torch.float64, torch.float32, torch.int32, torch.uint8
@@ -91,6 +124,9 @@ class loop_ba_step:
         if L:
             self.mt.landmark_geometry_device(F, cap, L, pose, keyframes["kps"], pos_w, landmarks["ref_kf"], landmarks["obs_offsets"], landmarks["obs_kf"],
                                              landmarks["obs_idx"], normal, mn, mx, geo, self.sf, skip=landmarks.get("skip"), counts=keyframes.get("counts"), stream=st)
-        return dict(status=ba["status"], info=ba["info"], chi2=ba["chi2"], kf_optimized=ba["kf_optimized"], lm_optimized=ba["lm_optimized"],
-                    kf_status=pr["kf_status"], lm_status=pr["lm_status"], pose_before=pr["pose_before"], geometry_status=geo, pose=pose, pos_w=pos_w, normal=normal,
-                    min_dist=mn, max_dist=mx)
+        res = dict(status=ba["status"], info=ba["info"], chi2=ba["chi2"], kf_optimized=ba["kf_optimized"], lm_optimized=ba["lm_optimized"],
+                   kf_status=pr["kf_status"], lm_status=pr["lm_status"], pose_before=pr["pose_before"], geometry_status=geo, pose=pose, pos_w=pos_w, normal=normal,
+                   min_dist=mn, max_dist=mx)
+        if lines is not None:
+            res.update(self._lines(keyframes, lines, ba, pr, st))
+        return res

@@ -8,11 +8,16 @@ frames, on one stream, without the host.
   2  torch, on the stream             pose <- the pose row where the problem was solved and the row is a vertex (set_cam_pose, :325)
   3  plp_correct_landmarks_device     pos_w <- corrected_Sim3_wc[ref].map(Sim3_cw[ref].map(pos_w)), in place                              :331-348
   4  plp_landmark_geometry_device     landmark::update_normal_and_depth: normal, min_dist, max_dist                                      :349
+  5  plp_correct_landmark_lines_device  with `lines`: pluecker <- (corrected_Sim3_wc_pluecker * Sim3_cw_pluecker) * pluecker                :352-403
+  6  line_map_update_step             the end points trimmed against the corrected poses (depth mode), written back under the status, the erased
+                                      lines flagged in skip_lines, Line::update_information                                              :405-417
 
 Step 2 is a torch selection of static shape (no .item(), no copy to the host, no boolean-mask indexing).  A problem the optimiser does not solve
 (a cap that is too small, a loop key frame that is no vertex: `status`) changes nothing: the step's Sim3 buffers start every run as the identity,
 which maps a landmark onto itself exactly, and the pose rows are kept.  The descriptors do not change with the geometry; landmark_refresh_step
-computes them.  What stays on the host: the line cloud of :352-419, add_loop_edge, the global bundle adjustment that follows.
+computes them.  With `lines` the line cloud of :352-419 follows on the same stream (a problem that is not solved moves and
+trims no line either); without it the step enqueues the four steps above and nothing else.  What stays on the host: add_loop_edge, the global bundle
+adjustment that follows.
 
 Tables are torch tensors on the step's device, named as landmark_refresh_step and covisibility_step name them:
   key frames  pose [F, 15] f64 (updated in place), kps [F, cap, 28] u8, counts [F] or absent, kf_erased [F] u8, kf_id [F] i32, kf_parent [F] i32,
@@ -21,13 +26,16 @@ Tables are torch tensors on the step's device, named as landmark_refresh_step an
   landmarks   pos_w [L, 3] f64 (updated in place), ref_kf [L] i32, corr_kf [L] i32 or absent = ref_kf (the row of ref_keyfrm_id_in_loop_fusion_ where the
               landmark was fused by this loop), skip [L] u8 or absent, obs_offsets [L + 1], obs_kf / obs_idx [T] i32, and the tables normal [L, 3] f64,
               min_dist / max_dist [L] f32 (updated in place; a missing one is created zero-filled)
+  lines       the tables of line_map_update_step, and corr_kf_lines [LL] i32 or absent = ref_kf_lines; the key lines kl [F, lcap, 68] u8 and kl_counts are
+              read from `keyframes`
   problem     the arrays of plp.pose_graph_problems for one problem, on the device
 """
 import numpy as np
 
 
 class loop_correction_step:
-    def __init__(self, plp, edge_cap=4096, env_cap=16384, scale_factor=1.2, num_levels=8, max_iter=50, device_index=0, mt=None):
+    def __init__(self, plp, edge_cap=4096, env_cap=16384, scale_factor=1.2, num_levels=8, max_iter=50, device_index=0, mt=None, camera=None, scale_factor_lsd=2.0,
+                 num_levels_lsd=1):
         import torch
         self.torch, self.plp = torch, plp
         self.dev = torch.device("cuda", device_index)
@@ -38,6 +46,9 @@ class loop_correction_step:
         self.sf = sf
         self.mt = mt or plp.matcher(device=device_index)
         self._bufs = {}
+        self._line_args = dict(camera=camera, scale_factor=scale_factor, num_levels=num_levels, scale_factor_lsd=scale_factor_lsd, num_levels_lsd=num_levels_lsd,
+                               device_index=device_index)
+        self._line_step = None
 
     def _buf(self, name, shape, dtype):
         t = self._bufs.get(name)
@@ -46,10 +57,35 @@ class loop_correction_step:
             self._bufs[name] = t
         return t
 
-    def run(self, keyframes, landmarks, problem, stream=None):
+    def _lines(self, keyframes, lines, o, st):
+        """steps 5 and 6: dict(line_status [LL] u8: CORRECT_LINE_*, and what line_map_update_step.run returns)"""
+        import importlib
+        torch, plp = self.torch, self.plp
+        if self._line_args["camera"] is None:
+            raise plp.PlpError(plp.PLP_ERR_INVALID_ARG, "loop_correction_step needs camera= to move line landmarks")
+        if self._line_step is None:
+            mod = importlib.import_module(__package__ + ".line_map_update_step")
+            self._line_step = mod.line_map_update_step(plp, mt=self.mt, **self._line_args)
+        pk = lines["pluecker_lines"]
+        LL, F = pk.shape[0], keyframes["pose"].shape[0]
+        pk_new, lst = self._buf("pluecker_new", (LL, 6), torch.float64), self._buf("line_status", (LL,), torch.uint8)
+        with torch.cuda.stream(st):
+            pk_new.copy_(pk)
+        if LL:
+            self.mt.correct_landmark_lines_device(LL, F, pk, lines["ref_kf_lines"], o["sim3_cw"], o["corrected_wc"], pk_new, lst, corr_kf=lines.get("corr_kf_lines"),
+                                                  lm_erased=lines.get("skip_lines"), kf_erased=keyframes.get("kf_erased"), stream=st)
+        with torch.cuda.stream(st):
+            solved = o["status"][0] == plp.POSE_GRAPH_OK
+            moved = ((lst == plp.CORRECT_LINE_OK) & solved).to(torch.uint8)
+            erase = ((lst == plp.CORRECT_LINE_NO_REF) & solved).to(torch.uint8)
+        r = self._line_step.run(keyframes, lines, mode=plp.TRIM_DEPTH_POSITIVE, pluecker=pk_new, moved=moved, erase=erase, stream=st)
+        return dict(r, line_status=lst)
+
+    def run(self, keyframes, landmarks, problem, stream=None, lines=None):
         """Enqueue the four steps on `stream` (default: the current stream).  Returns dict(status [1] u8: POSE_GRAPH_*, num_edges [1], info [1, 4], chi2 [1, 2],
         sim3_cw, corrected_wc [F, 8], lm_status [L] u8: CORRECT_LM_*, geometry_status [L] u8 -- the step's own buffers, rewritten by the next run -- and pose,
-        pos_w, normal, min_dist, max_dist: the caller's tables).  Nothing is synchronised."""
+        pos_w, normal, min_dist, max_dist: the caller's tables; with `lines` also line_status [LL] u8: CORRECT_LINE_* and the results of
+        line_map_update_step.run).  Nothing is synchronised."""
         torch, plp = self.torch, self.plp
         st = stream or torch.cuda.current_stream(self.dev)
         f64, f32, i32, u8 = torch.float64, torch.float32, torch.int32, torch.uint8
@@ -95,5 +131,8 @@ class loop_correction_step:
         if L:
             self.mt.landmark_geometry_device(F, cap, L, pose, keyframes["kps"], pos_w, landmarks["ref_kf"], landmarks["obs_offsets"], landmarks["obs_kf"],
                                              landmarks["obs_idx"], normal, mn, mx, geo, self.sf, skip=landmarks.get("skip"), counts=keyframes.get("counts"), stream=st)
-        return dict(status=o["status"], num_edges=o["num_edges"], info=o["info"], chi2=o["chi2"], sim3_cw=o["sim3_cw"][0], corrected_wc=o["corrected_wc"][0],
-                    lm_status=lm_status, geometry_status=geo, pose=pose, pos_w=pos_w, normal=normal, min_dist=mn, max_dist=mx)
+        res = dict(status=o["status"], num_edges=o["num_edges"], info=o["info"], chi2=o["chi2"], sim3_cw=o["sim3_cw"][0], corrected_wc=o["corrected_wc"][0],
+                   lm_status=lm_status, geometry_status=geo, pose=pose, pos_w=pos_w, normal=normal, min_dist=mn, max_dist=mx)
+        if lines is not None:
+            res.update(self._lines(keyframes, lines, o, st))
+        return res
