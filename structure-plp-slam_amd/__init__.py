@@ -34,7 +34,7 @@ from ._line_update import (CORRECT_LINE_ERASED, CORRECT_LINE_NO_REF, CORRECT_LIN
                            TRIM_MAX_CHANGE, TRIM_MAX_CHANGE_THR, TRIM_NO_REF, TRIM_NOT_OBSERVED, TRIM_OK, TRIM_OUTPUTS, TRIM_REJECTED, TRIM_SKIPPED,
                            correct_landmark_lines_args_c, line_update_entries, loop_ba_propagate_lines_args_c, model_correct_landmark_lines,
                            model_loop_ba_propagate_lines, model_trim_line_endpoints, trim_line_endpoints_args_c)
-from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, stream_handle, wanted
+from ._marshal import _rows_u8, array_or_none, dev_ptr, dev_ptrs, host_ptr, host_ptrs, model_call, model_draw, out_arrays, set_outputs, stream_handle, wanted
 
 
 def model_quadtree(xys, level_w, level_h, quota):
@@ -177,10 +177,7 @@ def model_horn_sim3(pts_1, pts_2, fix_scale=False):
 
 def model_sim3_draw(seed, p, iters, num_common, iter0=0):
     """The samples plp_sim3_ransac_* draw for problem p when the caller passes none (D13's generator; no GPU needed): (iters, 3) i32"""
-    out = np.zeros((int(iters), 3), np.int32)
-    if lib().plp_model_sim3_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_common), host_ptr(out)) != int(iters):
-        raise PlpError(PLP_ERR_INVALID_ARG, "num_common must be at least 3, iters non-negative")
-    return out
+    return model_draw("plp_model_sim3_draw_host", "num_common must be at least 3, iters non-negative", seed, p, iters, iter0, 3, num_common)
 # the outputs of plp_sim3_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
 SIM3_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_common=(lambda M, I: (), np.int32, False), rot_12=(lambda M, I: (3, 3), np.float64, False),
                     trans_12=(lambda M, I: (3,), np.float64, False), scale_12=(lambda M, I: (), np.float32, False),
@@ -327,11 +324,7 @@ def model_plane_fit(pos_w, lists):
 
 def model_plane_draw(seed, p, iters, m, n_eligible, iter0=0):
     """The ranks plp_plane_ransac_* draw for problem p when the caller passes none (D19 item 2; no GPU needed): (iters, m) i32"""
-    out = np.zeros((int(iters), int(m)), np.int32)
-    if lib().plp_model_plane_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(m), int(n_eligible),
-                                       host_ptr(out)) != int(iters):
-        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_plane_draw_host: n_eligible must be at least 1")
-    return out
+    return model_draw("plp_model_plane_draw_host", "plp_model_plane_draw_host: n_eligible must be at least 1", seed, p, iters, iter0, m, m, n_eligible)
 
 
 def _plane_refine_host(call, pos_w, lm_plane, flags, equation, active, dist_thresh):
@@ -463,10 +456,7 @@ def model_epnp(pos_w, bearing, offsets=None):
 
 def model_pnp_draw(seed, p, iters, num_matches, iter0=0):
     """The samples plp_pnp_ransac_* draw for problem p when the caller passes none (D14's generator; no GPU needed): (iters, 4) i32"""
-    out = np.zeros((int(iters), 4), np.int32)
-    if lib().plp_model_pnp_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_matches), host_ptr(out)) != int(iters):
-        raise PlpError(PLP_ERR_INVALID_ARG, "num_matches must be at least 4, iters non-negative")
-    return out
+    return model_draw("plp_model_pnp_draw_host", "num_matches must be at least 4, iters non-negative", seed, p, iters, iter0, 4, num_matches)
 
 
 def model_pnp_thresholds(scale_factors):

@@ -5,7 +5,7 @@ import numpy as np
 
 from ._abi import ESSENTIAL_OK, _struct, essential_ransac_args_c
 from ._core import PLP_ERR_INVALID_ARG, PlpError, lib
-from ._marshal import array_or_none, host_ptr, host_ptrs, model_call, out_arrays, set_outputs, wanted
+from ._marshal import array_or_none, host_ptr, host_ptrs, model_call, model_draw, out_arrays, set_outputs, wanted
 
 # the outputs of plp_essential_ransac_*: name -> (shape per problem given (n_cap, iters), dtype, optional)
 ESSENTIAL_OUTPUTS = dict(status=(lambda M, I: (), np.uint8, False), num_matches=(lambda M, I: (), np.int32, False), E_21=(lambda M, I: (3, 3), np.float64, False),
@@ -77,10 +77,7 @@ def model_essential_check(bearing_1, bearing_2, match, E_21):
 
 def model_essential_draw(seed, p, iters, num_matches, iter0=0):
     """The samples plp_essential_ransac_* draw for problem p when the caller passes none (D24's generator; no GPU needed): (iters, 8) i32"""
-    out = np.zeros((int(iters), 8), np.int32)
-    if lib().plp_model_essential_draw_host(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), int(num_matches), host_ptr(out)) != int(iters):
-        raise PlpError(PLP_ERR_INVALID_ARG, "num_matches must be at least 8, iters non-negative")
-    return out
+    return model_draw("plp_model_essential_draw_host", "num_matches must be at least 8, iters non-negative", seed, p, iters, iter0, 8, num_matches)
 
 
 class essential_solver:

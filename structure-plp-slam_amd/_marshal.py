@@ -77,6 +77,15 @@ def model_call(symbol, count, *extra, neg_status=False):
     return call
 
 
+def model_draw(symbol, message, seed, p, iters, iter0, width, *sizes):
+    """(iters, width) i32: the draws of the host build `symbol`(seed, p, iter0, iters, *sizes, out), which returns iters or, refused, less:
+    raises INVALID_ARG with `message`"""
+    out = np.zeros((int(iters), int(width)), np.int32)
+    if getattr(lib(), symbol)(int(seed) & 0xFFFFFFFFFFFFFFFF, int(p), int(iter0), int(iters), *map(int, sizes), host_ptr(out)) != int(iters):
+        raise PlpError(PLP_ERR_INVALID_ARG, message)
+    return out
+
+
 def _rows_u8(a):
     """a 2-D uint8 image as the C ABI takes it: unit stride inside a row, any row step >= the row length -- a view into a larger image (cv::Mat ROI, a cropped numpy
     slice) is passed AS IT IS, with its step; anything else is copied to a contiguous array first"""

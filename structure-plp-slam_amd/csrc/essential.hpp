@@ -1,8 +1,8 @@
 // solve::essential_solver (solve/essential_solver.cc:33-253), one definition of the arithmetic for host and device (plp_essential_ransac_* /
 // plp_model_essential_ransac_host, plp_model_essential_fit_host, plp_model_essential_check_host, plp_model_essential_draw_host,
-// include/plp_front.h): compute_E_21, the loop body of check_inliers and the sample generator.  f64 with IEEE
+// include/plp_front.h): compute_E_21 and the loop body of check_inliers; the samples are ransac.hpp's at K = 8 (D24 item d).  f64 with IEEE
 // + - * / sqrt only, every sum left to right, floats where the reference holds floats; translation units that include this file are compiled
-// with -ffp-contract=off.  The two Eigen::JacobiSVD uses of compute_E_21 are the one-sided Jacobi of pnp.hpp (D14), hestenes().
+// with -ffp-contract=off.  The two Eigen::JacobiSVD uses of compute_E_21 are the one-sided Jacobi of jacobi.hpp (D14), hestenes().
 //
 // Everything here works on memory the caller names: on the device that is LDS or a context buffer, reached with run-time indices, so that no
 // kernel keeps an indexed array in registers; on the host it is the stack.  The sums over bearing pairs are `chain` functions, one accumulator
@@ -12,7 +12,8 @@
 #include <stdint.h>
 
 #include "../../include/plp_front.h"
-#include "pnp.hpp"
+#include "jacobi.hpp"
+#include "ransac.hpp"
 
 namespace plp {
 
@@ -129,29 +130,6 @@ __host__ __device__ __forceinline__ float ess_score_add(float score, int code, f
     return score;
 }
 
-// The samples the library draws when the caller passes none (D24 item d): D13's generator with eight steps of the partial Fisher-Yates shuffle
-__host__ __device__ __forceinline__ void ess_draw(uint64_t seed, int p, int iter, int n, int out[8]) {
-    const uint64_t base = sim3_mix64(seed ^ sim3_mix64(((uint64_t)(uint32_t)p << 32) | (uint64_t)(uint32_t)iter));
-    int idx[16], val[16];                                           // the moved entries, latest last
-    int m = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const uint64_t r = sim3_mix64(base + (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
-        const int j = k + (int)((uint32_t)(r >> 32) % (uint32_t)(n - k));
-        int aj = j, ak = k;
-#pragma unroll
-        for (int i = 0; i < 16; ++i)
-            if (i < m) {
-                if (idx[i] == j) aj = val[i];
-                if (idx[i] == k) ak = val[i];
-            }
-        out[k] = aj;
-        idx[2 * k] = j; val[2 * k] = ak;
-        idx[2 * k + 1] = k; val[2 * k + 1] = aj;
-        m = 2 * k + 2;
-    }
-}
-
 struct EssArgs {
     int P, n_cap, m_cap, iters, recompute;
     unsigned long long seed;
@@ -168,34 +146,10 @@ struct EssArgs {
 };
 hipError_t launch_essential_ransac(hipStream_t st, const EssArgs& A);   // essential_kernels.hip: five launches, the first error
 
-__host__ __device__ __forceinline__ int ess_clamp_count(const int32_t* counts, int p, int cap) {
-    if (!counts) return cap;
-    const int n = counts[p];
-    return n < 0 ? 0 : (n > cap ? cap : n);
-}
 // whether slot `slot` < counts_1[p] of problem p holds a match: an index in frame 2 below counts_2[p] (D24 item e)
 __host__ __device__ __forceinline__ bool ess_matched(const EssArgs& A, int p, int slot, int count_2) {
     const int m = A.match[(size_t)p * A.n_cap + slot];
     return m >= 0 && m < count_2;
-}
-
-// the eight sample indices of hypothesis `iter` of problem p (the caller's, or drawn), and whether they name eight distinct matches
-__host__ __device__ __forceinline__ bool ess_sample(const EssArgs& A, int p, int iter, int n, int idx[8]) {
-    if (A.samples) {
-        const int32_t* s = A.samples + ((size_t)p * A.iters + iter) * 8;
-#pragma unroll
-        for (int a = 0; a < 8; ++a) idx[a] = s[a];
-    } else {
-        ess_draw(A.seed, p, iter, n, idx);
-    }
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 8; ++a) {
-        ok = ok && (unsigned)idx[a] < (unsigned)n;
-#pragma unroll
-        for (int b = a + 1; b < 8; ++b) ok = ok && idx[a] != idx[b];
-    }
-    return ok;
 }
 
 }  // namespace plp

@@ -58,7 +58,7 @@ float ess_model_check(const double* E, const double* pairs, int n, uint8_t* code
 
 // one problem of the host build: the kernels' steps, one hypothesis and one match after the other
 void ess_model_problem(const EssArgs& A, int p) {
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap), count_2 = ess_clamp_count(A.counts_2, p, A.m_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap), count_2 = clamp_count(A.counts_2, p, A.m_cap);
     const size_t row = (size_t)p * A.n_cap;
     std::vector<int> slot_of;
     for (int s = 0; s < count_1; ++s)
@@ -80,7 +80,7 @@ void ess_model_problem(const EssArgs& A, int p) {
     for (int it = 0; it < A.iters; ++it) {
         float score = 0;
         int idx[8];
-        if (enough && ess_sample(A, p, it, n, idx)) {
+        if (enough && ransac_sample<kEssMinSet>(A, p, it, n, idx)) {
             for (int k = 0; k < 8; ++k)                             // :73-78
                 for (int c = 0; c < kEssPairDoubles; ++c) fit[(size_t)k * kEssPairDoubles + c] = pairs[(size_t)idx[k] * kEssPairDoubles + c];
             ess_fit(fit.data(), kEssPairDoubles, kEssMinSet, S.M, S.G, S.V, S.null9, S.key, E, nullptr);   // :81
@@ -211,13 +211,7 @@ int32_t plp_model_essential_check_host(const double* bearing_1, const double* be
 }
 
 int32_t plp_model_essential_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_matches, int32_t* out) {
-    if (n_iters < 0 || num_matches < kEssMinSet || (n_iters > 0 && !out)) return -1;
-    for (int32_t i = 0; i < n_iters; ++i) {
-        int idx[8];
-        ess_draw(seed, p, iter0 + i, num_matches, idx);
-        for (int k = 0; k < 8; ++k) out[8 * (size_t)i + k] = idx[k];
-    }
-    return n_iters;
+    return ransac_draw_rows<kEssMinSet>(seed, p, iter0, n_iters, num_matches, out);
 }
 
 }  // extern "C"

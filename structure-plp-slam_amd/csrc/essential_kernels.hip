@@ -35,6 +35,7 @@
 
 #include "essential.hpp"
 #include "plp_barrier.hpp"
+#include "ransac_device.hpp"
 
 namespace plp {
 namespace {
@@ -51,41 +52,8 @@ struct EssWork {
     double E[9];
 };
 
-__device__ __forceinline__ unsigned long long ess_wg_max_u64(unsigned long long v, unsigned long long (&s_part)[4]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    wg_barrier();
-    unsigned long long m = s_part[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = s_part[w] > m ? s_part[w] : m;
-    wg_barrier();
-    return m;
-}
-
-// One step of an ordered compaction over the workgroup (as pnp_kernels.hip): the position of this lane's item among the flagged ones (n
-// before the step), and the new total.  Uniform over the workgroup; ends with a barrier.
-__device__ __forceinline__ int ess_compact_step(bool v, int& n, int (&s_wave_n)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long m = __ballot(v);
-    if (lane == 0) s_wave_n[w] = (int)__popcll(m);
-    wg_barrier();
-    int off = n, tot = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (u < w) off += s_wave_n[u];
-        tot += s_wave_n[u];
-    }
-    n += tot;
-    wg_barrier();   // s_wave_n is rewritten by the next step
-    return off + (int)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 // the winner of k_ess_count's key (score bits << 32 | ~iter; 0 = no hypothesis scored above 0)
-__device__ __forceinline__ int ess_best_iter(unsigned long long key) { return key != 0ull ? (int)(~(unsigned)key) : -1; }
+__device__ __forceinline__ int ess_best_iter(unsigned long long key) { return key != 0ull ? ransac_key_iter(key) : -1; }
 
 __device__ __forceinline__ double* ess_hyp_field(const EssArgs& A, int p, int field) { return A.ctx_hyp + ((size_t)p * kEssHypDoubles + field) * A.iters; }
 
@@ -93,12 +61,12 @@ __global__ __launch_bounds__(256) void k_ess_prepare(EssArgs A) {
     __shared__ int s_wave_n[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap), count_2 = ess_clamp_count(A.counts_2, p, A.m_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap), count_2 = clamp_count(A.counts_2, p, A.m_cap);
     int n = 0;
     for (int base = 0; base < count_1; base += 256) {
         const int slot = base + tid;
         const bool v = slot < count_1 && ess_matched(A, p, slot, count_2);
-        const int pos = ess_compact_step(v, n, s_wave_n);
+        const int pos = wg_compact_step(v, n, s_wave_n);
         if (v) A.ctx_slot[row + pos] = (uint16_t)slot;
     }
     if (tid == 0) {
@@ -152,7 +120,7 @@ __device__ __forceinline__ int jacobi9_group(double (&g)[9], double* null9, int 
         const bool any = ((bal >> (lane & 48)) & 0xFFFFull) != 0ull;
         if (!done) {
             if (!any) done = true;
-            else if (++sweeps >= kPnpSweepLimit) done = true;
+            else if (++sweeps >= kJacobiSweepLimit) done = true;
         }
     }
     double n2 = 0.0;
@@ -183,7 +151,7 @@ __global__ __launch_bounds__(256) void k_ess_hypotheses(EssArgs A) {
         bool have = false;
         if (j == 0) {
             int idx[8];
-            have = live && enough && ess_sample(A, p, it, n, idx);
+            have = live && enough && ransac_sample<kEssMinSet>(A, p, it, n, idx);
 #pragma unroll
             for (int k = 0; k < 8; ++k) {                           // :73-78, in the order given
                 if (have) {
@@ -267,12 +235,12 @@ __global__ __launch_bounds__(256) void k_ess_count(EssArgs A) {
         if (live) {
             if (A.out_hyp_score) A.out_hyp_score[(size_t)p * A.iters + it] = score;
             if (score > 0.0f) {                                     // :87 against best_score_ = 0.0 (:52); false for a NaN
-                const unsigned long long mine = ((unsigned long long)__float_as_uint(score) << 32) | (unsigned long long)(~(unsigned)it);
+                const unsigned long long mine = ransac_key(__float_as_uint(score), it);
                 key = mine > key ? mine : key;
             }
         }
     }
-    key = ess_wg_max_u64(key, s_part);
+    key = wg_max_u64(key, s_part);
     if (tid == 0 && key != 0ull) atomicMax(A.ctx_key + p, key);       // a maximum: the order of the workgroups does not matter
 }
 
@@ -310,7 +278,7 @@ __global__ __launch_bounds__(256) void k_ess_refit(EssArgs A) {
             A.ctx_code[row + k] = (uint8_t)code;
             in = code == 3;
         }
-        const int pos = ess_compact_step(in, nc, s_wave_n);
+        const int pos = wg_compact_step(in, nc, s_wave_n);
         if (in) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) { pairs[(size_t)pos * kEssPairDoubles + c] = b1[c]; pairs[(size_t)pos * kEssPairDoubles + 3 + c] = b2[c]; }
@@ -381,7 +349,7 @@ __global__ __launch_bounds__(256) void k_ess_refit(EssArgs A) {
 __global__ __launch_bounds__(256) void k_ess_finish(EssArgs A) {
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap), count_2 = ess_clamp_count(A.counts_2, p, A.m_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap), count_2 = clamp_count(A.counts_2, p, A.m_cap);
     const int32_t* ctx = A.ctx + (size_t)kEssCtxInts * p;
     const unsigned long long key = A.ctx_key[p];
     const int n = ctx[0], best_iter = ess_best_iter(key), num = ctx[3], refit = ctx[4];

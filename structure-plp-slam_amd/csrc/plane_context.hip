@@ -51,7 +51,7 @@ extern "C++" template <class R> void plane_rooms(R& r, plp_matcher* c, PlaneArgs
 
 // one problem of the host build: the kernels' steps, one hypothesis and one point after the other
 void plane_model_problem(const PlaneArgs& A, int p) {
-    const int n = plane_count(A.counts, A.n_cap, p), I = A.iters;
+    const int n = clamp_count(A.counts, p, A.n_cap), I = A.iters;
     const size_t row = (size_t)p * A.n_cap;
     const double* pos = A.pos_w + 3 * row;
     std::vector<int> elig, live;
@@ -87,7 +87,7 @@ void plane_model_problem(const PlaneArgs& A, int p) {
     for (int it = 0; it < I; ++it) {
         int sweeps;
         plane_fit(T, [&](int k, double x[3]) {
-            const int rank = A.samples ? A.samples[((size_t)p * I + it) * A.m_cap + k] : plane_draw(A.seed, p, it, k, n_elig);
+            const int rank = A.samples ? A.samples[((size_t)p * I + it) * A.m_cap + k] : ransac_draw_one(A.seed, p, it, k, n_elig);
             if ((unsigned)rank >= (unsigned)n_elig) return false;
             const double* w = pos + 3 * (size_t)elig[rank];
             x[0] = w[0]; x[1] = w[1]; x[2] = w[2];
@@ -246,7 +246,7 @@ int32_t plp_model_plane_fit_host(const double* pos_w, int32_t n_points, const in
 int32_t plp_model_plane_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t m, int32_t n_eligible, int32_t* out) {
     if (n_iters < 0 || m < 0 || n_eligible < 1 || ((size_t)n_iters * (size_t)m > 0 && !out)) return -1;
     for (int32_t i = 0; i < n_iters; ++i)
-        for (int32_t k = 0; k < m; ++k) out[(size_t)i * m + k] = plane_draw(seed, p, iter0 + i, k, n_eligible);
+        for (int32_t k = 0; k < m; ++k) out[(size_t)i * m + k] = ransac_draw_one(seed, p, iter0 + i, k, n_eligible);
     return n_iters;
 }
 

@@ -13,7 +13,8 @@
 #include <stdint.h>
 
 #include "../../include/plp_front.h"
-#include "pnp.hpp"
+#include "jacobi.hpp"
+#include "ransac.hpp"
 
 namespace plp {
 
@@ -22,12 +23,6 @@ constexpr int kPlaneMaxIters = 1024;
 constexpr int kPlaneHypDoubles = 12;                  // per hypothesis: sample equation (4), residual, refit equation (4), error, inliers, ok
 constexpr int kPlaneWorkDoubles = 42;                 // plane_normal's work: A, G, V (9 each), key, vals (3 each), Ut (9)
 constexpr double kPlaneMax = 1.7976931348623157e308;  // std::numeric_limits<double>::max() (:439)
-
-__host__ __device__ __forceinline__ int plane_count(const int32_t* counts, int n_cap, int p) {
-    if (!counts) return n_cap;
-    const int n = counts[p];
-    return n < 0 ? 0 : (n > n_cap ? n_cap : n);
-}
 
 // who may be sampled (:452, :623-628) and who is scanned for inliers (:480, :656)
 __host__ __device__ __forceinline__ bool plane_live(uint8_t f) { return (f & PLP_PLANE_LM_ERASED) == 0; }
@@ -44,13 +39,6 @@ __host__ __device__ __forceinline__ int plane_sample_size(int mode, int n, int p
     return m;
 }
 
-// sample k of hypothesis `iter` of problem p: a rank among the n_eligible eligible slots, with replacement (D19 item 2)
-__host__ __device__ __forceinline__ int plane_draw(uint64_t seed, int p, int iter, int k, int n_eligible) {
-    const uint64_t base = sim3_mix64(seed ^ sim3_mix64(((uint64_t)(uint32_t)p << 32) | (uint64_t)(uint32_t)iter));
-    const uint64_t r = sim3_mix64(base + (uint64_t)((uint32_t)k + 1u) * 0x9E3779B97F4A7C15ull);
-    return (int)((uint32_t)(r >> 32) % (uint32_t)n_eligible);
-}
-
 // Plane::set_equation's _abs_n (landmark_plane.cc:106) and Plane::calculate_distance (:118-123)
 __host__ __device__ __forceinline__ double plane_abs_n(const double eq[4]) { return __builtin_sqrt((eq[0] * eq[0] + eq[1] * eq[1]) + eq[2] * eq[2]); }
 __host__ __device__ __forceinline__ double plane_dot(const double eq[4], const double x[3]) { return (eq[0] * x[0] + eq[1] * x[1]) + eq[2] * x[2]; }
@@ -58,7 +46,7 @@ __host__ __device__ __forceinline__ double plane_distance(const double eq[4], do
     return __builtin_fabs((plane_dot(eq, x) + eq[3]) / abs_n);
 }
 
-// The unit normal of the scatter matrix C = (c00, c01, c02, c11, c12, c22): the eigenvector of the smallest eigenvalue by sym_jacobi (pnp.hpp)
+// The unit normal of the scatter matrix C = (c00, c01, c02, c11, c12, c22): the eigenvector of the smallest eigenvalue by sym_jacobi (jacobi.hpp)
 // at n = 3, Ut row 2, divided by its norm when that is > 0 (normalized()), the component of largest magnitude made positive (ties: the lowest
 // index).  W: kPlaneWorkDoubles of memory reached with run-time indices (LDS on the device).  Returns the sweeps that rotated.
 __host__ __device__ __forceinline__ int plane_normal(const double C[6], double* W, double nrm[3]) {

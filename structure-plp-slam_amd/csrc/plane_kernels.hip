@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void k_plane_hypotheses(PlaneArgs A) {
     __shared__ int s_wave_n[2][kPlaneWaves];
 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int n = plane_count(A.counts, A.n_cap, p);
+    const int n = clamp_count(A.counts, p, A.n_cap);
     const size_t row = (size_t)p * A.n_cap;
     const double* pos = A.pos_w + 3 * row;
     const unsigned long long below = (1ull << lane) - 1ull;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256) void k_plane_hypotheses(PlaneArgs A) {
         int sweeps;
         const int32_t* smp = A.samples ? A.samples + ((size_t)p * A.iters + it) * A.m_cap : nullptr;
         plane_fit(T, [&](int k, double x[3]) {
-            const int rank = smp ? smp[k] : plane_draw(A.seed, p, it, k, n_elig);
+            const int rank = smp ? smp[k] : ransac_draw_one(A.seed, p, it, k, n_elig);
             if ((unsigned)rank >= (unsigned)n_elig) return false;
             const double* q = pos + 3 * (size_t)s_elig[rank];
             x[0] = q[0]; x[1] = q[1]; x[2] = q[2];
@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void k_plane_finish(PlaneArgs A) {
     __shared__ int s_n[2];                                // eligible slots; members of step [4]
 
     const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, I = A.iters;
-    const int n = plane_count(A.counts, A.n_cap, p);
+    const int n = clamp_count(A.counts, p, A.n_cap);
     const size_t row = (size_t)p * A.n_cap;
     const double* pos = A.pos_w + 3 * row;
     if (tid < 2) s_n[tid] = 0;

@@ -1,8 +1,8 @@
 // solve::pnp_solver (solve/pnp_solver.cc:36-866), one definition of the arithmetic for host and device (plp_pnp_ransac_* / plp_model_pnp_ransac_host,
 // plp_model_epnp_host, plp_model_sym_jacobi_host, plp_model_lstsq6_host, plp_model_rot_from_abt_host, include/plp_front.h; DESIGN.md section 5,
-// D14): EPnP's compute_pose, the inlier test of check_inliers, the threshold table of the constructor and the sample generator.  f64 with
+// D14): EPnP's compute_pose, the inlier test of check_inliers and the threshold table of the constructor; the samples are ransac.hpp's at K = 4.  f64 with
 // IEEE + - * / sqrt only, every sum left to right from 0.0, floats where the reference holds floats; translation units that include this file are
-// compiled with -ffp-contract=off.  The four Eigen::JacobiSVD uses are one written-down one-sided (Hestenes) Jacobi, hestenes() below.
+// compiled with -ffp-contract=off.  The four Eigen::JacobiSVD uses are one written-down one-sided (Hestenes) Jacobi, jacobi.hpp's hestenes().
 //
 // Everything here works on memory the caller names (PnpWork and the correspondence arrays): on the device that is LDS or a context buffer, reached
 // with run-time indices, so that no kernel keeps an indexed array in registers; on the host it is the stack.  The sums over correspondences are
@@ -12,7 +12,8 @@
 #include <stdint.h>
 
 #include "../../include/plp_front.h"
-#include "sim3.hpp"
+#include "jacobi.hpp"
+#include "ransac.hpp"
 
 namespace plp {
 
@@ -20,8 +21,6 @@ constexpr int kPnpMaxSlots = 8192;                    // n_cap limit of the entr
 constexpr int kPnpCtxInts = 4;                        // per problem: num_matches, best count, best iteration, correspondences of the refit
 constexpr int kPnpHypDoubles = 13;                    // per hypothesis: rot_cw (9), trans_cw (3), whether it exists
 constexpr int kPnpCorrDoubles = 12;                   // per correspondence of the refit: pws (3), us (2), alphas (4), pcs (3)
-constexpr int kPnpSweepLimit = 60;                    // sweeps that rotate; scene matrices need far fewer (tests/test_pnp_solver_cpu.py)
-constexpr double kPnpSkipTol = 0x1p-100;              // a column pair is left alone unless (g_p . g_q)^2 > 2^-100 |g_p|^2 |g_q|^2: |cos| <= 4 eps
 
 // util::cos (util/trigonometric.h:42-73), float throughout; cvFloor is (int)v - ((int)v > v)
 __host__ __device__ __forceinline__ float pnp_poly_cos(float v) {
@@ -46,96 +45,7 @@ __host__ __device__ __forceinline__ float pnp_level_threshold(float scale_factor
     return pnp_ref_cos((float)((double)scale_factor * max_rad_error));
 }
 
-// ---- the one-sided Jacobi (D14 item 1)
-// The round-robin ("circle") schedule over N columns, N even: in round r = 0 .. N-2 column N-1 meets column r and every other column j meets
-// (2r - j) mod (N-1).  The pairs of a round are disjoint, so their rotations commute exactly.
-__host__ __device__ __forceinline__ int jacobi_partner(int j, int r, int N) {
-    if (j == N - 1) return r;
-    if (j == r) return N - 1;
-    int q = (2 * r - j) % (N - 1);
-    if (q < 0) q += N - 1;
-    return q;
-}
-
-// c, s of the rotation that makes columns p < q orthogonal, from alpha = |g_p|^2, beta = |g_q|^2, gamma = g_p . g_q; false = the pair is left alone
-// (the fixed skip test; a NaN skips too)
-__host__ __device__ __forceinline__ bool hestenes_cs(double alpha, double beta, double gamma, double& c, double& s) {
-    if (!(gamma * gamma > kPnpSkipTol * (alpha * beta))) return false;
-    const double zeta = (beta - alpha) / (2.0 * gamma);
-    const double root = __builtin_sqrt(1.0 + zeta * zeta);
-    const double t = zeta >= 0.0 ? 1.0 / (zeta + root) : -1.0 / (root - zeta);
-    c = 1.0 / __builtin_sqrt(1.0 + t * t);
-    s = c * t;
-    return true;
-}
-
-// G: m x n, V: n x n, both column-major (column j at G + j * m, V + j * n); V must hold the identity.  Sweeps of the schedule above (an odd n
-// gets a dummy last column whose pairs are skipped) until one rotates nothing.  Returns the number of sweeps that rotated; kPnpSweepLimit =
-// the limit was reached.  Afterwards A V = G with orthogonal columns: sigma_j = |g_j|, right vectors = columns of V, left = g_j / sigma_j.
-__host__ __device__ __forceinline__ int hestenes(double* G, double* V, int m, int n) {
-    const int N = n + (n & 1);
-    int sweeps = 0;
-    while (sweeps < kPnpSweepLimit) {
-        bool any = false;
-        for (int r = 0; r < N - 1; ++r)
-            for (int p = 0; p < n; ++p) {
-                const int q = jacobi_partner(p, r, N);
-                if (q >= n || q < p) continue;           // the dummy, or the pair is taken from its lower column
-                double* gp = G + p * m; double* gq = G + q * m;
-                double alpha = 0.0, beta = 0.0, gamma = 0.0;
-                for (int i = 0; i < m; ++i) { alpha = alpha + gp[i] * gp[i]; beta = beta + gq[i] * gq[i]; gamma = gamma + gp[i] * gq[i]; }
-                double c, s;
-                if (!hestenes_cs(alpha, beta, gamma, c, s)) continue;
-                any = true;
-                for (int i = 0; i < m; ++i) {
-                    const double a = gp[i], b = gq[i];
-                    gp[i] = c * a - s * b;
-                    gq[i] = s * a + c * b;
-                }
-                double* vp = V + p * n; double* vq = V + q * n;
-                for (int i = 0; i < n; ++i) {
-                    const double a = vp[i], b = vq[i];
-                    vp[i] = c * a - s * b;
-                    vq[i] = s * a + c * b;
-                }
-            }
-        if (!any) break;
-        ++sweeps;
-    }
-    return sweeps;
-}
-
-// the ordering key of a column: |g_j|^2, a NaN counts as +inf; rank j = the number of columns that come before j when the keys are sorted
-// descending, equal keys by ascending column
-__host__ __device__ __forceinline__ double jacobi_key(double n2) { return n2 == n2 ? n2 : __builtin_inf(); }
-__host__ __device__ __forceinline__ bool jacobi_before(double key_k, int k, double key_j, int j) { return key_k > key_j || (key_k == key_j && k < j); }
-
-__host__ __device__ __forceinline__ void set_identity(double* V, int n) {
-    for (int i = 0; i < n * n; ++i) V[i] = 0.0;
-    for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
-}
-
-// Uses 1 and 2 of D14: A n x n row-major, symmetric positive semi-definite.  vals[r] = the r-th largest singular value |g_j|, Ut row r
-// (row-major n x n) = the column of V that belongs to it.  G, V: n * n doubles of scratch each, key: n.
-__host__ __device__ __forceinline__ int sym_jacobi(const double* A, int n, double* G, double* V, double* key, double* vals, double* Ut) {
-    for (int j = 0; j < n; ++j)
-        for (int i = 0; i < n; ++i) G[j * n + i] = A[i * n + j];
-    set_identity(V, n);
-    const int sweeps = hestenes(G, V, n, n);
-    for (int j = 0; j < n; ++j) {
-        double n2 = 0.0;
-        for (int i = 0; i < n; ++i) n2 = n2 + G[j * n + i] * G[j * n + i];
-        key[j] = jacobi_key(n2);
-    }
-    for (int j = 0; j < n; ++j) {
-        int rank = 0;
-        for (int k = 0; k < n; ++k) rank += jacobi_before(key[k], k, key[j], j) ? 1 : 0;
-        vals[rank] = __builtin_sqrt(key[j]);
-        for (int i = 0; i < n; ++i) Ut[rank * n + i] = V[j * n + i];
-    }
-    return sweeps;
-}
-
+// ---- the small uses of the one-sided Jacobi (jacobi.hpp) that are EPnP's own
 // Use 3 of D14: the minimum-norm least-squares solution of the 6 x k system whose columns are G's (column-major, destroyed), k = 3, 4, 5:
 // x = sum over the columns j in ascending order with sigma_j > (k * 2^-52) * sigma_max of v_j * ((g_j . b) / |g_j|^2).  V: k * k, key: k.
 __host__ __device__ __forceinline__ int lstsq6(double* G, const double* b, int k, double* V, double* key, double* x) {
@@ -647,29 +557,6 @@ __host__ __device__ __forceinline__ bool pnp_inlier(const double* R, const doubl
     return !never && (double)thr < cos;
 }
 
-// The samples the library draws when the caller passes none (D14): D13's generator with four steps of the partial Fisher-Yates shuffle
-__host__ __device__ __forceinline__ void pnp_draw(uint64_t seed, int p, int iter, int n, int out[4]) {
-    const uint64_t base = sim3_mix64(seed ^ sim3_mix64(((uint64_t)(uint32_t)p << 32) | (uint64_t)(uint32_t)iter));
-    int idx[8], val[8];                                             // the moved entries, latest last
-    int m = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint64_t r = sim3_mix64(base + (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
-        const int j = k + (int)((uint32_t)(r >> 32) % (uint32_t)(n - k));
-        int aj = j, ak = k;
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-            if (i < m) {
-                if (idx[i] == j) aj = val[i];
-                if (idx[i] == k) ak = val[i];
-            }
-        out[k] = aj;
-        idx[2 * k] = j; val[2 * k] = ak;
-        idx[2 * k + 1] = k; val[2 * k + 1] = aj;
-        m = 2 * k + 2;
-    }
-}
-
 struct PnpArgs {
     int P, n_cap, iters, min_num_inliers, recompute, num_levels;
     unsigned long long seed;
@@ -685,29 +572,5 @@ struct PnpArgs {
     int32_t* ctx_sign;       // DEVICE, P: signs_[0] of the refit
 };
 hipError_t launch_pnp_ransac(hipStream_t st, const PnpArgs& A);     // pnp_kernels.hip: five launches, the first error
-
-__host__ __device__ __forceinline__ int pnp_count(const PnpArgs& A, int p) {
-    if (!A.counts) return A.n_cap;
-    const int n = A.counts[p];
-    return n < 0 ? 0 : (n > A.n_cap ? A.n_cap : n);
-}
-
-// the four sample indices of hypothesis `iter` of problem p (the caller's, or drawn), and whether they name four distinct matches
-__host__ __device__ __forceinline__ bool pnp_sample(const PnpArgs& A, int p, int iter, int n, int idx[4]) {
-    if (A.samples) {
-        const int32_t* s = A.samples + ((size_t)p * A.iters + iter) * 4;
-        idx[0] = s[0]; idx[1] = s[1]; idx[2] = s[2]; idx[3] = s[3];
-    } else {
-        pnp_draw(A.seed, p, iter, n, idx);
-    }
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        ok = ok && (unsigned)idx[a] < (unsigned)n;
-#pragma unroll
-        for (int b = a + 1; b < 4; ++b) ok = ok && idx[a] != idx[b];
-    }
-    return ok;
-}
 
 }  // namespace plp

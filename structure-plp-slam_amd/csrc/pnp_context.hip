@@ -53,7 +53,7 @@ int pnp_model_pose(PnpWork& W, double* corr, int nc, int sign0) {
 
 // one problem of the host build: the kernels' steps, one hypothesis and one match after the other
 void pnp_model_problem(const PnpArgs& A, int p) {
-    const int count = pnp_count(A, p);
+    const int count = clamp_count(A.counts, p, A.n_cap);
     const size_t row = (size_t)p * A.n_cap;
     std::vector<int> slot_of;
     for (int s = 0; s < count; ++s)
@@ -74,7 +74,7 @@ void pnp_model_problem(const PnpArgs& A, int p) {
     for (int it = 0; it < A.iters; ++it) {
         int num = 0;
         int idx[4];
-        if (enough && pnp_sample(A, p, it, n, idx)) {
+        if (enough && ransac_sample<4>(A, p, it, n, idx)) {
             int nc = 0, sign0 = 0;
             for (int k = 0; k < 4; ++k) {
                 const size_t s = row + slot_of[idx[k]];
@@ -234,13 +234,7 @@ int32_t plp_model_rot_from_abt_host(const double* Abt, int32_t n, double* out_ro
 }
 
 int32_t plp_model_pnp_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_matches, int32_t* out) {
-    if (n_iters < 0 || num_matches < 4 || (n_iters > 0 && !out)) return -1;
-    for (int32_t i = 0; i < n_iters; ++i) {
-        int idx[4];
-        pnp_draw(seed, p, iter0 + i, num_matches, idx);
-        for (int k = 0; k < 4; ++k) out[4 * (size_t)i + k] = idx[k];
-    }
-    return n_iters;
+    return ransac_draw_rows<4>(seed, p, iter0, n_iters, num_matches, out);
 }
 
 int32_t plp_model_pnp_thresholds_host(const float* scale_factors, int32_t num_levels, float* out) {

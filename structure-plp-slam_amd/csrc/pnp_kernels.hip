@@ -28,6 +28,7 @@
 
 #include "plp_barrier.hpp"
 #include "pnp.hpp"
+#include "ransac_device.hpp"
 
 namespace plp {
 namespace {
@@ -35,51 +36,18 @@ namespace {
 constexpr int kPnpTile = 256;    // matches per LDS tile: one per lane
 constexpr int kPnpPass = 16;     // hypotheses per workgroup pass: one per group of 16 lanes
 
-__device__ __forceinline__ unsigned long long pnp_wg_max_u64(unsigned long long v, unsigned long long (&s_part)[4]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    wg_barrier();
-    unsigned long long m = s_part[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = s_part[w] > m ? s_part[w] : m;
-    wg_barrier();
-    return m;
-}
-
-// One step of an ordered compaction over the workgroup: the position of this lane's item among the flagged ones (n before the step), and
-// the new total.  Uniform over the workgroup; ends with a barrier.
-__device__ __forceinline__ int compact_step(bool v, int& n, int (&s_wave_n)[4]) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const unsigned long long m = __ballot(v);
-    if (lane == 0) s_wave_n[w] = (int)__popcll(m);
-    wg_barrier();
-    int off = n, tot = 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (u < w) off += s_wave_n[u];
-        tot += s_wave_n[u];
-    }
-    n += tot;
-    wg_barrier();   // s_wave_n is rewritten by the next step
-    return off + (int)__popcll(m & ((1ull << lane) - 1ull));
-}
-
 __device__ __forceinline__ double* pnp_hyp_field(const PnpArgs& A, int p, int field) { return A.ctx_hyp + ((size_t)p * kPnpHypDoubles + field) * A.iters; }
 
 __global__ __launch_bounds__(256) void k_pnp_prepare(PnpArgs A) {
     __shared__ int s_wave_n[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count = pnp_count(A, p);
+    const int count = clamp_count(A.counts, p, A.n_cap);
     int n = 0;
     for (int base = 0; base < count; base += 256) {
         const int slot = base + tid;
         const bool v = slot < count && A.valid[row + slot] != 0;
-        const int pos = compact_step(v, n, s_wave_n);
+        const int pos = wg_compact_step(v, n, s_wave_n);
         if (v) A.ctx_slot[row + pos] = (uint16_t)slot;
     }
     if (tid == 0) A.ctx[(size_t)kPnpCtxInts * p] = n;
@@ -132,7 +100,7 @@ __device__ __forceinline__ int jacobi12_group(PnpWork& W, int j, bool write) {
         const bool any = ((bal >> (lane & 48)) & 0xFFFFull) != 0ull;
         if (!done) {
             if (!any) done = true;
-            else if (++sweeps >= kPnpSweepLimit) done = true;
+            else if (++sweeps >= kJacobiSweepLimit) done = true;
         }
     }
     double n2 = 0.0;
@@ -164,7 +132,7 @@ __global__ __launch_bounds__(256) void k_pnp_hypotheses(PnpArgs A) {
         int nc = 0, sign0 = 0;
         if (j == 0) {
             int idx[4];
-            if (live && enough && pnp_sample(A, p, it, n, idx)) {
+            if (live && enough && ransac_sample<4>(A, p, it, n, idx)) {
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {                       // :103-108, in the order given
                     const size_t s = row + A.ctx_slot[row + idx[k]];
@@ -246,16 +214,16 @@ __global__ __launch_bounds__(256) void k_pnp_count(PnpArgs A) {
         }
         if (live) {
             if (A.out_hyp_inliers) A.out_hyp_inliers[(size_t)p * A.iters + it] = num;
-            const unsigned long long mine = ((unsigned long long)(unsigned)num << 32) | (unsigned long long)(~(unsigned)it);
+            const unsigned long long mine = ransac_key((unsigned)num, it);
             key = mine > key ? mine : key;
         }
     }
-    key = pnp_wg_max_u64(key, s_part);
+    key = wg_max_u64(key, s_part);
     if (tid == 0) {
         const int best_count = (int)(key >> 32);
         int32_t* c = A.ctx + (size_t)kPnpCtxInts * p;
         c[1] = best_count;
-        c[2] = best_count > 0 ? (int)(~(unsigned)key) : -1;
+        c[2] = best_count > 0 ? ransac_key_iter(key) : -1;
         c[3] = 0;
     }
 }
@@ -293,7 +261,7 @@ __global__ __launch_bounds__(256) void k_pnp_refit(PnpArgs A) {
             const bool lv = (unsigned)o < (unsigned)A.num_levels;
             in = pnp_inlier(s_pose, s_pose + 9, A.pos_w + 3 * s, A.bearing + 3 * s, lv ? s_tab[o] : 0.0f, !lv) && A.bearing[3 * s + 2] != 0;
         }
-        const int pos = compact_step(in, nc, s_wave_n);
+        const int pos = wg_compact_step(in, nc, s_wave_n);
         if (in) {
             int sg;
             pnp_add_correspondence(A.pos_w + 3 * s, A.bearing + 3 * s, pws + (size_t)pos * S, us + (size_t)pos * S, sg);
@@ -375,7 +343,7 @@ __global__ __launch_bounds__(256) void k_pnp_finish(PnpArgs A) {
     __shared__ float s_tab[16];
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count = pnp_count(A, p);
+    const int count = clamp_count(A.counts, p, A.n_cap);
     const int32_t* ctx = A.ctx + (size_t)kPnpCtxInts * p;
     const int n = ctx[0], best_count = ctx[1], best_iter = ctx[2], refit = ctx[3];
     const bool enough = !(n < 4 || n < A.min_num_inliers);          // :76

@@ -1,13 +1,14 @@
 // solve::sim3_solver (solve/sim3_solver.cc), one definition of the arithmetic for host and device (plp_sim3_ransac_* / plp_model_sim3_ransac_host,
 // plp_model_horn_sim3_host, plp_model_sym_eig4_max_host, include/plp_front.h): the eigenvector of Horn's 4 x 4 matrix by a
-// written-down cyclic Jacobi, compute_Sim3 (:193-288), the sample generator, the per-point constants of the constructor (:96-118) and the inlier
-// test of count_inliers (:290-325).  f64 with IEEE + - * / sqrt only (the equirectangular reprojection's asin / atan2 aside, D5 item 2), every sum
+// written-down cyclic Jacobi, compute_Sim3 (:193-288), the per-point constants of the constructor (:96-118) and the inlier
+// test of count_inliers (:290-325); the samples are ransac.hpp's at K = 3.  f64 with IEEE + - * / sqrt only (the equirectangular reprojection's asin / atan2 aside, D5 item 2), every sum
 // left to right, floats where the reference holds floats; translation units that include this file are compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/plp_front.h"
+#include "ransac.hpp"
 #include "reproject.hpp"
 
 namespace plp {
@@ -173,38 +174,6 @@ __host__ __device__ __forceinline__ void sim3_pose_row(const double rot[9], cons
     m[9] = trans[0]; m[10] = trans[1]; m[11] = trans[2];
 }
 
-// The samples the library draws when the caller passes none (D13): a counter-based generator, splitmix64's finaliser over (seed, p, iter, k),
-// and three distinct indices of [0, n), n >= 3, by a partial Fisher-Yates shuffle of 0 .. n-1 (step k swaps position k with position
-// k + r_k mod (n - k)), the array kept as the few entries that moved.
-__host__ __device__ __forceinline__ uint64_t sim3_mix64(uint64_t x) {
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    x ^= x >> 31;
-    return x;
-}
-
-__host__ __device__ __forceinline__ void sim3_draw(uint64_t seed, int p, int iter, int n, int out[3]) {
-    const uint64_t base = sim3_mix64(seed ^ sim3_mix64(((uint64_t)(uint32_t)p << 32) | (uint64_t)(uint32_t)iter));
-    int idx[6], val[6];                                             // the moved entries, latest last
-    int m = 0;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const uint64_t r = sim3_mix64(base + (uint64_t)(k + 1) * 0x9E3779B97F4A7C15ull);
-        const int j = k + (int)((uint32_t)(r >> 32) % (uint32_t)(n - k));
-        int aj = j, ak = k;                                         // a[j], a[k] as they stand
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-            if (i < m) {
-                if (idx[i] == j) aj = val[i];
-                if (idx[i] == k) ak = val[i];
-            }
-        out[k] = aj;
-        idx[2 * k] = j; val[2 * k] = ak;                            // a[j] <- a[k]; a[k] <- a[j]
-        idx[2 * k + 1] = k; val[2 * k + 1] = aj;
-        m = 2 * k + 2;
-    }
-}
-
 // the camera fields reproject<MODEL> reads (set_camera, matcher_context.hpp) and what every problem of a call shares
 struct Sim3Args {
     int model;
@@ -221,12 +190,6 @@ struct Sim3Args {
     double* ctx_hyp;                                                // DEVICE, P x kSim3HypDoubles x iters: the hypotheses
 };
 hipError_t launch_sim3_ransac(hipStream_t st, const Sim3Args& A);   // sim3_kernels.hip: three launches, the first error
-
-__host__ __device__ __forceinline__ int sim3_count(const Sim3Args& A, int p) {
-    if (!A.counts) return A.n_cap;
-    const int n = A.counts[p];
-    return n < 0 ? 0 : (n > A.n_cap ? A.n_cap : n);
-}
 
 // What the constructor keeps of one common point (:96-118): the two camera-frame points, their reprojections into their own images and the
 // two float thresholds.  never: a point behind its own camera (perspective, fisheye), whose reprojected_1_ / reprojected_2_ entry the
@@ -272,18 +235,6 @@ __host__ __device__ __forceinline__ bool sim3_inlier(const Sim3Args& A, const do
     const double d2u = a.u - u2, d2v = a.v - v2, d1u = b.u - u1, d1v = b.v - v1;
     const double error_in_2 = d2u * d2u + d2v * d2v, error_in_1 = d1u * d1u + d1v * d1v;
     return !never && a.wrote && b.wrote && error_in_2 < (double)thr_2 && error_in_1 < (double)thr_1;
-}
-
-// the three sample indices of hypothesis `iter` of problem p (the caller's, or drawn), and whether they name three distinct common points
-__host__ __device__ __forceinline__ bool sim3_sample(const Sim3Args& A, int p, int iter, int n, int idx[3]) {
-    if (A.samples) {
-        const int32_t* s = A.samples + ((size_t)p * A.iters + iter) * 3;
-        idx[0] = s[0]; idx[1] = s[1]; idx[2] = s[2];
-    } else {
-        sim3_draw(A.seed, p, iter, n, idx);
-    }
-    return (unsigned)idx[0] < (unsigned)n && (unsigned)idx[1] < (unsigned)n && (unsigned)idx[2] < (unsigned)n && idx[0] != idx[1] && idx[0] != idx[2] &&
-           idx[1] != idx[2];
 }
 
 // the hypothesis of three common points given by their slots: their camera-frame points are formed as the constructor forms them

@@ -51,7 +51,7 @@ extern "C++" template <class R> void sim3_rooms(R& r, plp_matcher* c, Sim3Args& 
 
 // one problem of the host build: the kernel's steps, one hypothesis and one point after the other
 extern "C++" template <int MODEL> void sim3_model_problem(const Sim3Args& A, int p) {
-    const int count = sim3_count(A, p);
+    const int count = clamp_count(A.counts, p, A.n_cap);
     const size_t row = (size_t)p * A.n_cap;
     const double* P1 = A.pose_1 + (size_t)15 * p;
     const double* P2 = A.pose_2 + (size_t)15 * p;
@@ -69,7 +69,7 @@ extern "C++" template <int MODEL> void sim3_model_problem(const Sim3Args& A, int
         int num = 0;
         if (enough) {
             int idx[3];
-            if (sim3_sample(A, p, it, n, idx)) {
+            if (ransac_sample<3>(A, p, it, n, idx)) {
                 const int slot[3] = {slot_of[idx[0]], slot_of[idx[1]], slot_of[idx[2]]};
                 Sim3Hyp H;
                 sim3_hypothesis(A, P1, P2, p, slot, H);
@@ -165,13 +165,7 @@ int32_t plp_model_horn_sim3_host(const double* pts_1, const double* pts_2, int32
 }
 
 int32_t plp_model_sim3_draw_host(uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_common, int32_t* out) {
-    if (n_iters < 0 || num_common < 3 || (n_iters > 0 && !out)) return -1;
-    for (int32_t i = 0; i < n_iters; ++i) {
-        int idx[3];
-        sim3_draw(seed, p, iter0 + i, num_common, idx);
-        out[3 * (size_t)i] = idx[0]; out[3 * (size_t)i + 1] = idx[1]; out[3 * (size_t)i + 2] = idx[2];
-    }
-    return n_iters;
+    return ransac_draw_rows<3>(seed, p, iter0, n_iters, num_common, out);
 }
 
 int32_t plp_model_sym_eig4_max_host(const double* N, int32_t n, double* out_v, int32_t* out_sweeps) {

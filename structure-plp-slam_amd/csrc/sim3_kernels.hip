@@ -24,28 +24,13 @@
 #include <hip/hip_runtime.h>
 
 #include "plp_barrier.hpp"
+#include "ransac_device.hpp"
 #include "sim3.hpp"
 
 namespace plp {
 namespace {
 
 constexpr int kSim3Tile = 256;   // common points per LDS tile: one per lane
-
-// the maximum of v over the workgroup; ends with the barrier behind which s_part may be rewritten
-__device__ __forceinline__ unsigned long long wg_max_u64(unsigned long long v, unsigned long long (&s_part)[4]) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const unsigned long long o = __shfl_xor(v, d);
-        v = o > v ? o : v;
-    }
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = v;
-    wg_barrier();
-    unsigned long long m = s_part[0];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) m = s_part[w] > m ? s_part[w] : m;
-    wg_barrier();
-    return m;
-}
 
 // step 1 of both kernels below: the valid slots of problem p in slot order, s_slot[rank] = slot; returns their number.  Uniform over the
 // workgroup; ends with a barrier.
@@ -82,12 +67,12 @@ __global__ __launch_bounds__(256) void k_sim3_hypotheses(Sim3Args A) {
     __shared__ int s_wave_n[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     if (tid < 12) { s_pose[0][tid] = A.pose_1[(size_t)15 * p + tid]; s_pose[1][tid] = A.pose_2[(size_t)15 * p + tid]; }
-    const int n = compact_slots(A, p, sim3_count(A, p), s_slot, s_wave_n);   // its barriers publish s_pose too (count == 0: nothing reads it)
+    const int n = compact_slots(A, p, clamp_count(A.counts, p, A.n_cap), s_slot, s_wave_n);   // its barriers publish s_pose too (count == 0: nothing reads it)
     const bool enough = !(n < 3 || n < A.min_num_inliers);   // :130
     if (tid == 0) A.ctx[(size_t)kSim3CtxInts * p] = n;
     for (int it = tid; it < A.iters; it += 256) {
         int idx[3];
-        const bool hyp = enough && sim3_sample(A, p, it, n, idx);
+        const bool hyp = enough && ransac_sample<3>(A, p, it, n, idx);
         hyp_field(A, p, 37)[it] = hyp ? 1.0 : 0.0;
         if (!hyp) continue;
         const int slot[3] = {s_slot[idx[0]], s_slot[idx[1]], s_slot[idx[2]]};
@@ -120,7 +105,7 @@ __global__ __launch_bounds__(256) void k_sim3_count(Sim3Args A) {
     const int p = blockIdx.x, tid = threadIdx.x;
     if (tid < 16) { s_sigma[0][tid] = A.level_sigma_sq_1[tid]; s_sigma[1][tid] = A.level_sigma_sq_2[tid]; }
     if (tid < 12) { s_pose[0][tid] = A.pose_1[(size_t)15 * p + tid]; s_pose[1][tid] = A.pose_2[(size_t)15 * p + tid]; }
-    const int n = compact_slots(A, p, sim3_count(A, p), s_slot, s_wave_n);   // its barriers publish s_sigma and s_pose too
+    const int n = compact_slots(A, p, clamp_count(A.counts, p, A.n_cap), s_slot, s_wave_n);   // its barriers publish s_sigma and s_pose too
     const bool enough = !(n < 3 || n < A.min_num_inliers);   // :130
 
     unsigned long long key = 0;
@@ -160,7 +145,7 @@ __global__ __launch_bounds__(256) void k_sim3_count(Sim3Args A) {
         }
         if (live) {
             if (A.out_hyp_inliers) A.out_hyp_inliers[(size_t)p * A.iters + it] = num;
-            const unsigned long long mine = ((unsigned long long)(unsigned)num << 32) | (unsigned long long)(~(unsigned)it);
+            const unsigned long long mine = ransac_key((unsigned)num, it);
             key = mine > key ? mine : key;
         }
     }
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(256) void k_sim3_count(Sim3Args A) {
         const int best_count = (int)(key >> 32);
         int32_t* c = A.ctx + (size_t)kSim3CtxInts * p;
         c[1] = best_count;
-        c[2] = best_count > 0 ? (int)(~(unsigned)key) : -1;
+        c[2] = best_count > 0 ? ransac_key_iter(key) : -1;
     }
 }
 
@@ -181,7 +166,7 @@ __global__ __launch_bounds__(256) void k_sim3_finish(Sim3Args A) {
     __shared__ double s_pose[2][12];
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count = sim3_count(A, p);
+    const int count = clamp_count(A.counts, p, A.n_cap);
     if (tid < 16) { s_sigma[0][tid] = A.level_sigma_sq_1[tid]; s_sigma[1][tid] = A.level_sigma_sq_2[tid]; }
     if (tid < 12) { s_pose[0][tid] = A.pose_1[(size_t)15 * p + tid]; s_pose[1][tid] = A.pose_2[(size_t)15 * p + tid]; }
     wg_barrier();

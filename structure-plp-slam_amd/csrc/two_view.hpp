@@ -10,7 +10,9 @@
 
 #include "../../include/plp_front.h"
 #include "essential.hpp"
+#include "jacobi.hpp"
 #include "pose_graph.hpp"
+#include "ransac.hpp"
 #include "reproject.hpp"
 
 namespace plp {

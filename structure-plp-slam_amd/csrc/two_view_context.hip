@@ -52,7 +52,7 @@ extern "C++" template <class R> void tv_rooms(R& r, plp_matcher* c, TvArgs& A) {
 // point, the flag and the code (pts / flag / code: count_1 entries written, may be NULL)
 extern "C++" template <int MODEL> int tv_model_check_pose(const TvArgs& A, int p, const double* pose12, const double* coef, float& parallax_deg, double* pts, uint8_t* flag,
                                                           uint8_t* codes) {
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap), count_2 = ess_clamp_count(A.counts_2, p, A.m_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap), count_2 = clamp_count(A.counts_2, p, A.m_cap);
     const size_t row = (size_t)p * A.n_cap;
     double c[3];
     tv_center(pose12, c);
@@ -90,7 +90,7 @@ int tv_model_check_pose_any(const TvArgs& A, int p, const double* pose12, const 
 
 // one problem of the host build
 void tv_model_problem(const TvArgs& A, int p, const double* coef) {
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap);
     const size_t row = (size_t)p * A.n_cap, M = (size_t)A.n_cap;
     const bool solved = !(A.in_status && A.in_status[p] != 0);
     double ws[kTvDecomposeDoubles], rots[18], trans[3], pose12[12];

@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void k_two_view_pose(TvArgs A) {
     __shared__ float s_parallax[4];
     const int p = blockIdx.x, tid = threadIdx.x;
     const size_t row = (size_t)p * A.n_cap;
-    const int count_1 = ess_clamp_count(A.counts_1, p, A.n_cap), count_2 = ess_clamp_count(A.counts_2, p, A.m_cap);
+    const int count_1 = clamp_count(A.counts_1, p, A.n_cap), count_2 = clamp_count(A.counts_2, p, A.m_cap);
     const bool solved = !(A.in_status && A.in_status[p] != 0);      // uniform over the workgroup
     if (tid == 0) {
         if (solved) tv_decompose(A.E_21 + (size_t)9 * p, s_ws, s_rots, s_trans);

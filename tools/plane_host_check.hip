@@ -60,7 +60,7 @@ int run_problem(int mode, int n, int iters, double best_error_in, double* out_eq
     for (int it = 0; it < iters; ++it) {
         int sweeps = 0;
         plane_fit(*T, [&](int k, double x[3]) {
-            const int rank = it == 1 ? (int)elig.size() : plane_draw(A.seed, 0, it, k, (int)elig.size());   // iteration 1: a void sample
+            const int rank = it == 1 ? (int)elig.size() : ransac_draw_one(A.seed, 0, it, k, (int)elig.size());   // iteration 1: a void sample
             if ((unsigned)rank >= (unsigned)elig.size()) return false;
             for (int r = 0; r < 3; ++r) x[r] = pos[3 * (size_t)elig[rank] + r];
             return true;
@@ -140,8 +140,8 @@ int main() {
     good = good && fit_equal_points(1) && fit_equal_points(64) && fit_equal_points(65);
     {   // the draws stay in range at both ends; the sample size of UPDATE
         int lo = 1 << 30, hi = -1;
-        for (int k = 0; k < 20000; ++k) { const int r = plane_draw(7, 65534, 1023, k, 8192); lo = r < lo ? r : lo; hi = r > hi ? r : hi; }
-        good = good && lo >= 0 && hi < 8192 && plane_draw(1, 0, 0, 0, 1) == 0;
+        for (int k = 0; k < 20000; ++k) { const int r = ransac_draw_one(7, 65534, 1023, k, 8192); lo = r < lo ? r : lo; hi = r > hi ? r : hi; }
+        good = good && lo >= 0 && hi < 8192 && ransac_draw_one(1, 0, 0, 0, 1) == 0;
         good = good && plane_sample_size(PLP_PLANE_UPDATE, 8192, 18) == 6554 && plane_sample_size(PLP_PLANE_UPDATE, 5, 18) == 4 && plane_sample_size(PLP_PLANE_UPDATE, 0, 18) == 0;
         std::printf("draws in [%d, %d]\n", lo, hi);
     }
@@ -151,7 +151,7 @@ int main() {
         double res;
         int sweeps;
         plane_fit(*T, [&](int k, double x[3]) { for (int r = 0; r < 3; ++r) x[r] = pos[3 * k + r]; return true; }, 4, eq, res, sweeps);
-        good = good && res != res && sweeps < kPnpSweepLimit;
+        good = good && res != res && sweeps < kJacobiSweepLimit;
         std::printf("NaN position: residual %g after %d sweeps\n", res, sweeps);
     }
     good = good && refine_scene();
