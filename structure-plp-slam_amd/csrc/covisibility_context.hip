@@ -65,9 +65,28 @@ CvArgs cu_args(const plp_covisibility_update_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffer (device entry) or a room of the slab (host-pointer entry), one block of i32
-extern "C++" template <class R> void cu_rooms(R& r, plp_matcher* c, CvArgs& A) {
+// the state tables of either call
+extern "C++" template <class R> void cv_state_plan(R& r, CvArgs& A) {
+    const size_t F = (size_t)A.F;
+    r.out(A.kf_conn, F * A.conn_cap); r.out(A.kf_conn_w, F * A.conn_cap); r.out(A.kf_n_conn, F);
+    r.out(A.kf_covis, F * A.covis_cap); r.out(A.kf_covis_w, F * A.covis_cap); r.out(A.kf_n_covis, F);
+}
+
+// the arrays of the update; the room is what the launches hand to one another, one block of i32
+extern "C++" template <class R> void cu_plan(R& r, plp_matcher* c, CvArgs& A) {
+    const size_t F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, G = (size_t)A.G;
+    r.in(A.kf_lm, F * A.cap); r.in(A.kf_counts, F); r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.lm_erased, L); r.in(A.kf_id, F);
+    cv_state_plan(r, A);
+    r.out(A.kf_parent, F); r.out(A.kf_parent_unset, F);
+    r.in(A.owners, G);
+    r.out(A.out_status, G); r.out(A.out_nearest, G); r.out(A.out_max_weight, G); r.out(A.out_touched, F);
     r.room(c->covis_ws, A.pos_of, cv_scratch_words(A.F, A.G, A.conn_cap, A.covis_cap));
+}
+
+// the room's parts, once its device address is known, then the launches
+static hipError_t cu_run(hipStream_t st, CvArgs& A) {
+    cv_scratch_split(A);
+    return launch_covisibility_update(st, A);
 }
 
 plp_status ce_check(const plp_covisibility_erase_args* a) {
@@ -89,11 +108,11 @@ CvArgs ce_args(const plp_covisibility_erase_args* a) {
     return A;
 }
 
-// the state tables of either call, staged both ways
-void stage_state(Stage& s, CvArgs& A) {
+extern "C++" template <class R> void ce_plan(R& r, plp_matcher*, CvArgs& A) {
     const size_t F = (size_t)A.F;
-    s.out(A.kf_conn, F * A.conn_cap); s.out(A.kf_conn_w, F * A.conn_cap); s.out(A.kf_n_conn, F);
-    s.out(A.kf_covis, F * A.covis_cap); s.out(A.kf_covis_w, F * A.covis_cap); s.out(A.kf_n_covis, F);
+    cv_state_plan(r, A);
+    r.in(A.erased, F);
+    r.out(A.out_status, F); r.out(A.out_touched, F);
 }
 }  // namespace
 
@@ -101,36 +120,14 @@ plp_status plp_covisibility_update_device(plp_matcher* c, const plp_covisibility
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = cu_check(a, false)) return s;
     if (a->G == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    CvArgs A = cu_args(a);
-    DeviceRooms r;
-    cu_rooms(r, c, A);
-    PLP_HIP(r.err);
-    cv_scratch_split(A);
-    PLP_HIP(launch_covisibility_update((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, cu_args(a), cu_plan<DeviceRooms>, cu_run);
 }
 
 plp_status plp_covisibility_update_host(plp_matcher* c, const plp_covisibility_update_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = cu_check(a, true)) return s;
     if (a->G == 0) return PLP_OK;
-    CvArgs A = cu_args(a);
-    const size_t F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, G = (size_t)A.G;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kf_lm, F * A.cap); s.in(A.kf_counts, F); s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.lm_erased, L); s.in(A.kf_id, F);
-    stage_state(s, A);
-    s.out(A.kf_parent, F); s.out(A.kf_parent_unset, F);
-    s.in(A.owners, G);
-    s.out(A.out_status, G); s.out(A.out_nearest, G); s.out(A.out_max_weight, G); s.out(A.out_touched, F);
-    cu_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    cv_scratch_split(A);
-    PLP_HIP(launch_covisibility_update(c->stream, A));
-    return s.finish();
+    return host_call(c, cu_args(a), cu_plan<Stage>, cu_run);
 }
 
 // the host build of covisibility.hpp (no HIP call): every owner, then every key frame
@@ -152,27 +149,14 @@ plp_status plp_covisibility_erase_device(plp_matcher* c, const plp_covisibility_
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ce_check(a)) return s;
     if (a->F == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_covisibility_erase((hipStream_t)hip_stream, ce_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, ce_args(a), ce_plan<DeviceRooms>, launch_covisibility_erase);
 }
 
 plp_status plp_covisibility_erase_host(plp_matcher* c, const plp_covisibility_erase_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ce_check(a)) return s;
     if (a->F == 0) return PLP_OK;
-    CvArgs A = ce_args(a);
-    const size_t F = (size_t)A.F;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    stage_state(s, A);
-    s.in(A.erased, F);
-    s.out(A.out_status, F); s.out(A.out_touched, F);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_covisibility_erase(c->stream, A));
-    return s.finish();
+    return host_call(c, ce_args(a), ce_plan<Stage>, launch_covisibility_erase);
 }
 
 int32_t plp_model_covisibility_erase_host(const plp_covisibility_erase_args* a) {

@@ -35,9 +35,12 @@ EssArgs ess_args(const plp_essential_ransac_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void ess_rooms(R& r, plp_matcher* c, EssArgs& A) {
-    const size_t P = (size_t)A.P, M = (size_t)A.n_cap, I = (size_t)A.iters;
+// the arrays of the call; the rooms are what the launches hand to one another
+extern "C++" template <class R> void ess_plan(R& r, plp_matcher* c, EssArgs& A) {
+    const size_t P = (size_t)A.P, M = (size_t)A.n_cap, M2 = (size_t)A.m_cap, I = (size_t)A.iters;
+    r.in(A.bearing_1, P * M * 3); r.in(A.bearing_2, P * M2 * 3); r.in(A.match, P * M); r.in(A.counts_1, P); r.in(A.counts_2, P); r.in(A.samples, P * I * 8);
+    r.out(A.out_status, P, false); r.out(A.out_num_matches, P, false); r.out(A.out_E_21, P * 9, false); r.out(A.out_score, P, false);
+    r.out(A.out_num_inliers, P, false); r.out(A.out_best_iter, P, false); r.out(A.out_inliers, P * M); r.out(A.out_hyp_score, P * I, false);
     r.room(c->ess_ctx, A.ctx, P * kEssCtxInts); r.room(c->ess_slot, A.ctx_slot, P * M); r.room(c->ess_hyp, A.ctx_hyp, P * kEssHypDoubles * I);
     r.room(c->ess_pairs, A.ctx_pairs, P * M * kEssPairDoubles); r.room(c->ess_E, A.ctx_E, P * 9); r.room(c->ess_code, A.ctx_code, P * M); r.room(c->ess_key, A.ctx_key, P);
 }
@@ -125,32 +128,14 @@ plp_status plp_essential_ransac_device(plp_matcher* c, const plp_essential_ransa
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ess_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    EssArgs A = ess_args(a);
-    DeviceRooms r;
-    ess_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_essential_ransac((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, ess_args(a), ess_plan<DeviceRooms>, launch_essential_ransac);
 }
 
 plp_status plp_essential_ransac_host(plp_matcher* c, const plp_essential_ransac_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ess_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, M = (size_t)a->n_cap, M2 = (size_t)a->m_cap, I = (size_t)a->iters;
-    EssArgs A = ess_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.bearing_1, P * M * 3); s.in(A.bearing_2, P * M2 * 3); s.in(A.match, P * M); s.in(A.counts_1, P); s.in(A.counts_2, P); s.in(A.samples, P * I * 8);
-    s.out(A.out_status, P, false); s.out(A.out_num_matches, P, false); s.out(A.out_E_21, P * 9, false); s.out(A.out_score, P, false);
-    s.out(A.out_num_inliers, P, false); s.out(A.out_best_iter, P, false); s.out(A.out_inliers, P * M); s.out(A.out_hyp_score, P * I, false);
-    ess_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_essential_ransac(c->stream, A));
-    return s.finish();
+    return host_call(c, ess_args(a), ess_plan<Stage>, launch_essential_ransac);
 }
 
 // the host builds of essential.hpp (no HIP call)

@@ -55,6 +55,14 @@ GbArgs gb_args(const plp_global_ba_args* a) {
     return A;
 }
 
+extern "C++" template <class R> void gb_plan(R& r, plp_matcher*, GbArgs& A) {
+    const size_t F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, K = (size_t)A.kp_stride;
+    r.in(A.pose, F * A.pose_stride); r.in(A.kf_erased, F); r.in(A.kf_is_origin, F); r.in(A.undist, F * K); r.in(A.x_right, F * K); r.in(A.counts, F);
+    r.in(A.pos_w, L * 3); r.in(A.lm_erased, L); r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.obs_idx, T);
+    r.out(A.out_status, 1); r.out(A.out_kf_optimized, F); r.out(A.out_lm_optimized, L); r.out(A.out_pose, F * 15); r.out(A.out_pos_w, L * 3);
+    r.out(A.out_info, 4); r.out(A.out_chi2, 3);
+}
+
 // the run on the device, between the launches: the record comes back through pinned memory, one copy and one synchronisation of the stream
 struct GbDeviceDriver {
     plp_matcher* c; hipStream_t st; GbArgs& A; int P = 0; hipError_t err = hipSuccess;
@@ -72,13 +80,14 @@ struct GbDeviceDriver {
     }
 };
 
-plp_status gb_run_device(plp_matcher* c, GbArgs& A, hipStream_t st, int iters, const volatile int32_t* stop, DevBuf& d, DevBuf& i, DevBuf& b) {
-    PLP_HIP(d.reserve(gb_doubles(A.F, A.L, A.T) * sizeof(double)));
-    PLP_HIP(i.reserve(gb_ints(A.F, A.T) * sizeof(int32_t)));
-    PLP_HIP(b.reserve(gb_bytes(A.F, A.L)));
+// the whole run of either form, which holds its state in the context's buffers and waits for the stream: the host reads the record between the launches
+plp_status gb_run_device(plp_matcher* c, GbArgs& A, hipStream_t st, int iters, const volatile int32_t* stop) {
+    PLP_HIP(c->gb_d.reserve(gb_doubles(A.F, A.L, A.T) * sizeof(double)));
+    PLP_HIP(c->gb_i.reserve(gb_ints(A.F, A.T) * sizeof(int32_t)));
+    PLP_HIP(c->gb_b.reserve(gb_bytes(A.F, A.L)));
     PLP_HIP(c->gb_rec.reserve(sizeof(GbRec)));
     PLP_HIP(c->gb_pin.reserve(sizeof(GbRec)));
-    gb_bind(A, static_cast<double*>(d.p), static_cast<int32_t*>(i.p), static_cast<uint8_t*>(b.p));
+    gb_bind(A, static_cast<double*>(c->gb_d.p), static_cast<int32_t*>(c->gb_i.p), static_cast<uint8_t*>(c->gb_b.p));
     A.rec = static_cast<GbRec*>(c->gb_rec.p);
     GbDeviceDriver drv{c, st, A};
     PLP_HIP(gb_launch_prepare(st, A));
@@ -117,32 +126,26 @@ LpArgs lp_args(const plp_loop_ba_propagate_args* a) {
     A.out_pose = a->out_pose; A.out_pose_before = a->out_pose_before; A.out_kf_status = a->out_kf_status; A.out_pos_w = a->out_pos_w; A.out_lm_status = a->out_lm_status;
     return A;
 }
+
+extern "C++" template <class R> void lp_plan(R& r, plp_matcher*, LpArgs& A) {
+    const size_t F = (size_t)A.F, L = (size_t)A.L;
+    r.in(A.pose, F * A.pose_stride); r.in(A.kf_erased, F); r.in(A.kf_is_origin, F); r.in(A.kf_parent, F); r.in(A.kf_optimized, F); r.in(A.pose_after, F * 15);
+    r.in(A.pos_w, L * 3); r.in(A.lm_erased, L); r.in(A.ref_kf, L); r.in(A.lm_optimized, L); r.in(A.pos_after, L * 3);
+    r.out(A.out_pose, F * 15); r.out(A.out_pose_before, F * 12); r.out(A.out_kf_status, F); r.out(A.out_pos_w, L * 3); r.out(A.out_lm_status, L);
+}
 }  // namespace
 
 plp_status plp_global_ba_device(plp_matcher* c, const plp_global_ba_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = gb_check(a, false)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    GbArgs A = gb_args(a);
-    return gb_run_device(c, A, (hipStream_t)hip_stream, a->num_iter, a->stop, c->gb_d, c->gb_i, c->gb_b);
+    return device_call(c, hip_stream, gb_args(a), gb_plan<DeviceRooms>,
+                       [=](hipStream_t st, GbArgs& A) { return gb_run_device(c, A, st, a->num_iter, a->stop); });
 }
 
 plp_status plp_global_ba_host(plp_matcher* c, const plp_global_ba_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = gb_check(a, true)) return s;
-    GbArgs A = gb_args(a);
-    const size_t F = (size_t)a->F, L = (size_t)a->L, T = (size_t)a->T, K = (size_t)a->kp_stride;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * a->pose_stride); s.in(A.kf_erased, F); s.in(A.kf_is_origin, F); s.in(A.undist, F * K); s.in(A.x_right, F * K); s.in(A.counts, F);
-    s.in(A.pos_w, L * 3); s.in(A.lm_erased, L); s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T);
-    s.out(A.out_status, 1); s.out(A.out_kf_optimized, F); s.out(A.out_lm_optimized, L); s.out(A.out_pose, F * 15); s.out(A.out_pos_w, L * 3);
-    s.out(A.out_info, 4); s.out(A.out_chi2, 3);
-    PLP_TRY(s.upload());
-    PLP_TRY(gb_run_device(c, A, c->stream, a->num_iter, a->stop, c->gb_d, c->gb_i, c->gb_b));
-    return s.finish();
+    return host_call(c, gb_args(a), gb_plan<Stage>, [=](hipStream_t st, GbArgs& A) { return gb_run_device(c, A, st, a->num_iter, a->stop); });
 }
 
 int32_t plp_model_global_ba_host(const plp_global_ba_args* a) {
@@ -155,26 +158,13 @@ int32_t plp_model_global_ba_host(const plp_global_ba_args* a) {
 plp_status plp_loop_ba_propagate_device(plp_matcher* c, const plp_loop_ba_propagate_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lp_check(a)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(lp_launch((hipStream_t)hip_stream, lp_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, lp_args(a), lp_plan<DeviceRooms>, lp_launch);
 }
 
 plp_status plp_loop_ba_propagate_host(plp_matcher* c, const plp_loop_ba_propagate_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lp_check(a)) return s;
-    LpArgs A = lp_args(a);
-    const size_t F = (size_t)a->F, L = (size_t)a->L;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * a->pose_stride); s.in(A.kf_erased, F); s.in(A.kf_is_origin, F); s.in(A.kf_parent, F); s.in(A.kf_optimized, F); s.in(A.pose_after, F * 15);
-    s.in(A.pos_w, L * 3); s.in(A.lm_erased, L); s.in(A.ref_kf, L); s.in(A.lm_optimized, L); s.in(A.pos_after, L * 3);
-    s.out(A.out_pose, F * 15); s.out(A.out_pose_before, F * 12); s.out(A.out_kf_status, F); s.out(A.out_pos_w, L * 3); s.out(A.out_lm_status, L);
-    PLP_TRY(s.upload());
-    PLP_HIP(lp_launch(c->stream, A));
-    return s.finish();
+    return host_call(c, lp_args(a), lp_plan<Stage>, lp_launch);
 }
 
 int32_t plp_model_loop_ba_propagate_host(const plp_loop_ba_propagate_args* a) {

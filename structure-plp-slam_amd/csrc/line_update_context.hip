@@ -80,37 +80,60 @@ LinePropagateArgs lq_args(const plp_loop_ba_propagate_lines_args* a) {
     A.out_pluecker = a->out_pluecker; A.out_status = a->out_status;
     return A;
 }
+
+// An output of these calls may be one of its inputs (out_pos_w and pos_w_old, out_pluecker and pluecker): one block then serves both, as one
+// array serves both in the device form.  The plan leaves such an input out, as NULL, and the run points it at the output's block.
+extern "C++" template <class R> void lt_plan(R& r, plp_matcher*, LineTrimArgs& A) {
+    const size_t L = (size_t)A.L, F = (size_t)A.F, T = list_end(r, A.obs_offsets, A.L);
+    r.in(A.pluecker, L * 6); r.in(A.ref_kf, L); r.in(A.skip, L); r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.obs_idx, T);
+    r.in(A.pose, F * A.pose_stride); r.in(A.kf_erased, F); r.in(A.kl, F * A.cap); r.in(A.counts, F); r.in(A.median, F);
+    if ((const void*)A.pos_w_old == (const void*)A.out_pos_w) A.pos_w_old = nullptr;
+    r.in(A.pos_w_old, L * 6);
+    r.out(A.out_pos_w, L * 6); r.out(A.out_status, L); r.out(A.out_erase, L);
+}
+static hipError_t lt_run(hipStream_t st, LineTrimArgs& A) {
+    if (A.mode == PLP_TRIM_MAX_CHANGE && !A.pos_w_old) A.pos_w_old = A.out_pos_w;
+    return launch_trim_line_endpoints(st, A);
+}
+
+extern "C++" template <class R> void lc_plan(R& r, plp_matcher*, LineCorrectArgs& A) {
+    const size_t L = (size_t)A.L, F = (size_t)A.F;
+    if ((const void*)A.pluecker == (const void*)A.out_pluecker) A.pluecker = nullptr;
+    r.in(A.pluecker, L * 6);
+    r.in(A.lm_erased, L); r.in(A.ref_kf, L); r.in(A.corr_kf, L); r.in(A.kf_erased, F); r.in(A.sim3_cw, F * 8); r.in(A.corrected_wc, F * 8);
+    r.out(A.out_pluecker, L * 6); r.out(A.out_status, L);
+}
+static hipError_t lc_run(hipStream_t st, LineCorrectArgs& A) {
+    if (!A.pluecker) A.pluecker = A.out_pluecker;
+    return launch_correct_landmark_lines(st, A);
+}
+
+extern "C++" template <class R> void lq_plan(R& r, plp_matcher*, LinePropagateArgs& A) {
+    const size_t L = (size_t)A.L, F = (size_t)A.F;
+    r.in(A.pose_after, F * 15); r.in(A.pose_before, F * 12); r.in(A.kf_status, F);
+    if ((const void*)A.pluecker == (const void*)A.out_pluecker) A.pluecker = nullptr;
+    r.in(A.pluecker, L * 6);
+    r.in(A.lm_erased, L); r.in(A.ref_kf, L); r.in(A.line_optimized, L); r.in(A.pluecker_after, L * 6);
+    r.out(A.out_pluecker, L * 6); r.out(A.out_status, L);
+}
+static hipError_t lq_run(hipStream_t st, LinePropagateArgs& A) {
+    if (!A.pluecker) A.pluecker = A.out_pluecker;
+    return launch_loop_ba_propagate_lines(st, A);
+}
 }  // namespace
 
 plp_status plp_trim_line_endpoints_device(plp_matcher* c, const plp_trim_line_endpoints_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lt_check(a, false)) return s;
     if (a->L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_trim_line_endpoints((hipStream_t)hip_stream, lt_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, lt_args(a), lt_plan<DeviceRooms>, lt_run);
 }
 
 plp_status plp_trim_line_endpoints_host(plp_matcher* c, const plp_trim_line_endpoints_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lt_check(a, true)) return s;
     if (a->L == 0) return PLP_OK;
-    LineTrimArgs A = lt_args(a);
-    const size_t L = (size_t)a->L, F = (size_t)a->F, T = (size_t)a->obs_offsets[a->L];
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pluecker, L * 6); s.in(A.ref_kf, L); s.in(A.skip, L); s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T);
-    s.in(A.pose, F * a->pose_stride); s.in(A.kf_erased, F); s.in(A.kl, F * a->cap); s.in(A.counts, F); s.in(A.median, F);
-    // out_pos_w may be pos_w_old: one staged block then serves both, as one array serves both on the device entry
-    const bool alias = A.pos_w_old && (const void*)A.pos_w_old == (const void*)A.out_pos_w;
-    if (!alias) s.in(A.pos_w_old, L * 6);
-    s.out(A.out_pos_w, L * 6); s.out(A.out_status, L); s.out(A.out_erase, L);
-    PLP_TRY(s.upload());
-    if (alias) A.pos_w_old = A.out_pos_w;
-    PLP_HIP(launch_trim_line_endpoints(c->stream, A));
-    return s.finish();
+    return host_call(c, lt_args(a), lt_plan<Stage>, lt_run);
 }
 
 int32_t plp_model_trim_line_endpoints_host(const plp_trim_line_endpoints_args* a) {
@@ -124,29 +147,14 @@ plp_status plp_correct_landmark_lines_device(plp_matcher* c, const plp_correct_l
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lc_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_correct_landmark_lines((hipStream_t)hip_stream, lc_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, lc_args(a), lc_plan<DeviceRooms>, lc_run);
 }
 
 plp_status plp_correct_landmark_lines_host(plp_matcher* c, const plp_correct_landmark_lines_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lc_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    LineCorrectArgs A = lc_args(a);
-    const size_t L = (size_t)a->L, F = (size_t)a->F;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    const bool alias = (const void*)A.pluecker == (const void*)A.out_pluecker;
-    if (!alias) s.in(A.pluecker, L * 6);
-    s.in(A.lm_erased, L); s.in(A.ref_kf, L); s.in(A.corr_kf, L); s.in(A.kf_erased, F); s.in(A.sim3_cw, F * 8); s.in(A.corrected_wc, F * 8);
-    s.out(A.out_pluecker, L * 6); s.out(A.out_status, L);
-    PLP_TRY(s.upload());
-    if (alias) A.pluecker = A.out_pluecker;
-    PLP_HIP(launch_correct_landmark_lines(c->stream, A));
-    return s.finish();
+    return host_call(c, lc_args(a), lc_plan<Stage>, lc_run);
 }
 
 int32_t plp_model_correct_landmark_lines_host(const plp_correct_landmark_lines_args* a) {
@@ -160,30 +168,14 @@ plp_status plp_loop_ba_propagate_lines_device(plp_matcher* c, const plp_loop_ba_
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lq_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_loop_ba_propagate_lines((hipStream_t)hip_stream, lq_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, lq_args(a), lq_plan<DeviceRooms>, lq_run);
 }
 
 plp_status plp_loop_ba_propagate_lines_host(plp_matcher* c, const plp_loop_ba_propagate_lines_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lq_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    LinePropagateArgs A = lq_args(a);
-    const size_t L = (size_t)a->L, F = (size_t)a->F;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    const bool alias = (const void*)A.pluecker == (const void*)A.out_pluecker;
-    s.in(A.pose_after, F * 15); s.in(A.pose_before, F * 12); s.in(A.kf_status, F);
-    if (!alias) s.in(A.pluecker, L * 6);
-    s.in(A.lm_erased, L); s.in(A.ref_kf, L); s.in(A.line_optimized, L); s.in(A.pluecker_after, L * 6);
-    s.out(A.out_pluecker, L * 6); s.out(A.out_status, L);
-    PLP_TRY(s.upload());
-    if (alias) A.pluecker = A.out_pluecker;
-    PLP_HIP(launch_loop_ba_propagate_lines(c->stream, A));
-    return s.finish();
+    return host_call(c, lq_args(a), lq_plan<Stage>, lq_run);
 }
 
 int32_t plp_model_loop_ba_propagate_lines_host(const plp_loop_ba_propagate_lines_args* a) {

@@ -66,9 +66,13 @@ LaArgs la_args(const plp_local_ba_args* a) {
     return A;
 }
 
-// what the steps hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void la_rooms(R& r, plp_matcher* c, LaArgs& A) {
-    const size_t G = (size_t)A.G;
+// the arrays of the call; the rooms are what the steps hand to one another
+extern "C++" template <class R> void la_plan(R& r, plp_matcher* c, LaArgs& A) {
+    const size_t G = (size_t)A.G, F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, K = (size_t)A.kp_stride;
+    r.in(A.pose, F * A.pose_stride); r.in(A.kf_erased, F); r.in(A.kf_is_origin, F); r.in(A.undist, F * K); r.in(A.x_right, F * K); r.in(A.counts, F);
+    r.in(A.pos_w, L * 3); r.in(A.lm_erased, L); r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.obs_idx, T); r.in(A.kf_local, G * F);
+    r.out(A.out_status, G); r.out(A.out_kf_role, G * F); r.out(A.out_lm_role, G * L); r.out(A.out_pose, G * F * 15); r.out(A.out_pos_w, G * L * 3);
+    r.out(A.out_outlier, G * T); r.out(A.out_round_info, G * 8); r.out(A.out_round_chi2, G * 4);
     r.room(c->la_d, A.ctx_d, G * la_doubles(A.F, A.L, A.T)); r.room(c->la_i, A.ctx_i, G * la_ints(A.T)); r.room(c->la_b, A.ctx_b, G * la_bytes(A.F, A.L, A.T) + 16);
 }
 
@@ -101,33 +105,14 @@ plp_status plp_local_ba_device(plp_matcher* c, const plp_local_ba_args* a, void*
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = la_check(a, true, false)) return s;
     if (a->G == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    LaArgs A = la_args(a);
-    DeviceRooms r;
-    la_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_local_ba((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, la_args(a), la_plan<DeviceRooms>, launch_local_ba);
 }
 
 plp_status plp_local_ba_host(plp_matcher* c, const plp_local_ba_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = la_check(a, true, true)) return s;
     if (a->G == 0) return PLP_OK;
-    LaArgs A = la_args(a);
-    const size_t G = (size_t)a->G, F = (size_t)a->F, L = (size_t)a->L, T = (size_t)a->T, K = (size_t)a->kp_stride;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * a->pose_stride); s.in(A.kf_erased, F); s.in(A.kf_is_origin, F); s.in(A.undist, F * K); s.in(A.x_right, F * K); s.in(A.counts, F);
-    s.in(A.pos_w, L * 3); s.in(A.lm_erased, L); s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T); s.in(A.kf_local, G * F);
-    s.out(A.out_status, G); s.out(A.out_kf_role, G * F); s.out(A.out_lm_role, G * L); s.out(A.out_pose, G * F * 15); s.out(A.out_pos_w, G * L * 3);
-    s.out(A.out_outlier, G * T); s.out(A.out_round_info, G * 8); s.out(A.out_round_chi2, G * 4);
-    la_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_local_ba(c->stream, A));
-    return s.finish();
+    return host_call(c, la_args(a), la_plan<Stage>, launch_local_ba);
 }
 
 // the host builds of local_ba.hpp (no HIP call)

@@ -75,21 +75,30 @@ int lm_chunk(const plp_local_map_args* a, const LmArgs& A) {
     return (int)std::min<size_t>(n, (size_t)A.B);
 }
 
-// the mark table of a chunk of nc frames (lm_ws_frame_bytes is a multiple of 4): the context's buffer (device entry) or a room of the slab
-// (host-pointer entry), 32-bit words
-extern "C++" template <class R> void lm_rooms(R& r, plp_matcher* c, LmArgs& A, int nc) {
-    r.room(c->lm_ws, A.ws, (size_t)nc * lm_ws_frame_bytes(A.L, A.LL) / 4);
+// the arrays of a call that works in chunks of nc frames; the room is the mark table of a chunk (lm_ws_frame_bytes is a multiple of 4), 32-bit words
+extern "C++" auto lm_plan(int nc) {
+    return [nc](auto& r, plp_matcher* c, LmArgs& A) {
+        const size_t B = (size_t)A.B, F = (size_t)A.F;
+        r.in(A.kf_erased, F); r.in(A.kf_covis, F * kLmCovis); r.in(A.kf_parent, F); r.in(A.kf_children_offsets, F + 1); r.in(A.kf_children, (size_t)A.C);
+        r.in(A.kf_lm, F * A.cap); r.in(A.kf_counts, F); r.in(A.kf_lm_lines, F * A.lcap); r.in(A.kf_kl_counts, F);
+        r.in(A.obs_offsets, (size_t)A.L + 1); r.in(A.obs_kf, (size_t)A.T); r.in(A.lm_erased, (size_t)A.L); r.in(A.lm_erased_lines, (size_t)A.LL);
+        r.in(A.frm_lm, B * A.frm_stride); r.in(A.frm_counts, B); r.in(A.frm_lm_lines, B * A.frm_stride_lines); r.in(A.frm_kl_counts, B);
+        r.out(A.out_status, B); r.out(A.out_num_first, B); r.out(A.out_num_kf, B); r.out(A.out_local_kf, B * A.k_cap); r.out(A.out_first_weight, B * A.k_cap);
+        r.out(A.out_nearest_kf, B); r.out(A.out_num_lm, B); r.out(A.out_local_lm, B * A.m_cap); r.out(A.out_held, B * A.m_cap);
+        if (A.lines) { r.out(A.out_num_lines, B); r.out(A.out_local_lines, B * A.ml_cap); r.out(A.out_held_lines, B * A.ml_cap); }
+        r.room(c->lm_ws, A.ws, (size_t)nc * lm_ws_frame_bytes(A.L, A.LL) / 4);
+    };
 }
 
 // every launch of a call; A.ws holds nc frames
-plp_status lm_run_device(hipStream_t st, LmArgs A, int nc) {
-    PLP_HIP(launch_local_map_keyframes(st, A));
-    for (int b0 = 0; b0 < A.B; b0 += nc) {
+hipError_t lm_run_device(hipStream_t st, LmArgs A, int nc) {
+    hipError_t e = launch_local_map_keyframes(st, A);
+    for (int b0 = 0; b0 < A.B && e == hipSuccess; b0 += nc) {
         A.b0 = b0; A.nb = std::min(nc, A.B - b0);
-        PLP_HIP(launch_local_map_lists(st, A, false));
-        if (A.lines) PLP_HIP(launch_local_map_lists(st, A, true));
+        e = launch_local_map_lists(st, A, false);
+        if (A.lines && e == hipSuccess) e = launch_local_map_lists(st, A, true);
     }
-    return PLP_OK;
+    return e;
 }
 }  // namespace
 
@@ -97,37 +106,18 @@ plp_status plp_local_map_device(plp_matcher* c, const plp_local_map_args* a, voi
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lm_check(a, false)) return s;
     if (a->B == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    LmArgs A = lm_args(a);
+    const LmArgs A = lm_args(a);
     const int nc = lm_chunk(a, A);
-    DeviceRooms r;
-    lm_rooms(r, c, A, nc);
-    PLP_HIP(r.err);
-    return lm_run_device((hipStream_t)hip_stream, A, nc);
+    return device_call(c, hip_stream, A, lm_plan(nc), [nc](hipStream_t st, LmArgs& A) { return lm_run_device(st, A, nc); });
 }
 
 plp_status plp_local_map_host(plp_matcher* c, const plp_local_map_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = lm_check(a, true)) return s;
     if (a->B == 0) return PLP_OK;
-    LmArgs A = lm_args(a);
+    const LmArgs A = lm_args(a);
     const int nc = lm_chunk(a, A);
-    const size_t B = (size_t)A.B, F = (size_t)A.F;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kf_erased, F); s.in(A.kf_covis, F * kLmCovis); s.in(A.kf_parent, F); s.in(A.kf_children_offsets, F + 1); s.in(A.kf_children, (size_t)A.C);
-    s.in(A.kf_lm, F * A.cap); s.in(A.kf_counts, F); s.in(A.kf_lm_lines, F * A.lcap); s.in(A.kf_kl_counts, F);
-    s.in(A.obs_offsets, (size_t)A.L + 1); s.in(A.obs_kf, (size_t)A.T); s.in(A.lm_erased, (size_t)A.L); s.in(A.lm_erased_lines, (size_t)A.LL);
-    s.in(A.frm_lm, B * A.frm_stride); s.in(A.frm_counts, B); s.in(A.frm_lm_lines, B * A.frm_stride_lines); s.in(A.frm_kl_counts, B);
-    s.out(A.out_status, B); s.out(A.out_num_first, B); s.out(A.out_num_kf, B); s.out(A.out_local_kf, B * A.k_cap); s.out(A.out_first_weight, B * A.k_cap);
-    s.out(A.out_nearest_kf, B); s.out(A.out_num_lm, B); s.out(A.out_local_lm, B * A.m_cap); s.out(A.out_held, B * A.m_cap);
-    if (A.lines) { s.out(A.out_num_lines, B); s.out(A.out_local_lines, B * A.ml_cap); s.out(A.out_held_lines, B * A.ml_cap); }
-    lm_rooms(s, c, A, nc);
-    PLP_TRY(s.upload());
-    PLP_TRY(lm_run_device(c->stream, A, nc));
-    return s.finish();
+    return host_call(c, A, lm_plan(nc), [nc](hipStream_t st, LmArgs& A) { return lm_run_device(st, A, nc); });
 }
 
 // the host build of local_map.hpp (no HIP call): one frame's mark table at a time

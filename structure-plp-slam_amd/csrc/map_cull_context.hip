@@ -59,12 +59,19 @@ CullArgs ck_args(const plp_cull_keyframes_args* a) {
     return A;
 }
 
-// the snapshot counts of every entry and, when the dead landmarks are asked for, every problem's final removed set: the context's buffers
-// (device entry) or rooms of the slab (host-pointer entry).  A room is asked for only where it is used: a context buffer of no element is still a
-// pointer, and A.rem must stay NULL for the replay not to store the sets.
-extern "C++" template <class R> void ck_rooms(R& r, plp_matcher* c, CullArgs& A) {
-    if (A.Cv > 0) r.room(c->cull_cnt, A.cnt, (size_t)A.Cv * 2);
-    if (cull_mask_rows(A) > 0) r.room(c->cull_rem, A.rem, (size_t)A.G * A.words);
+// The arrays of the call.  The rooms are the snapshot counts of every entry and, when the dead landmarks are asked for, every problem's final
+// removed set.  A room is asked for only where it is used: a context buffer of no element is still a pointer, and A.rem must stay NULL for the
+// replay not to store the sets.
+extern "C++" template <class R> void ck_plan(R& r, plp_matcher* c, CullArgs& A) {
+    const size_t F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, G = (size_t)A.G, Cv = (size_t)A.Cv, K = F * A.kp_stride;
+    r.in(A.kf_lm, F * A.cap); r.in(A.kf_counts, F); r.in(A.undist, K); r.in(A.x_right, K); r.in(A.depths, K); r.in(A.depth_thr, F);
+    r.in(A.kf_id, F); r.in(A.kf_cannot_erase, F);
+    r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.obs_idx, T); r.in(A.lm_erased, L); r.in(A.lm_num_obs, L);
+    r.in(A.cur_kf, G); r.in(A.covis_offsets, G + 1); r.in(A.covis, Cv);
+    r.out(A.out_num_removed, G); r.out(A.out_decision, Cv); r.out(A.out_num_valid, Cv); r.out(A.out_num_redundant, Cv);
+    r.out(A.out_kf_removed, G * F); r.out(A.out_lm_erased, G * L);
+    if (A.Cv > 0) r.room(c->cull_cnt, A.cnt, Cv * 2);
+    if (cull_mask_rows(A) > 0) r.room(c->cull_rem, A.rem, G * A.words);
 }
 
 plp_status cl_check(const plp_cull_landmarks_args* a, bool host) {
@@ -89,41 +96,27 @@ CullLmArgs cl_args(const plp_cull_landmarks_args* a) {
     A.out_state = a->out_state; A.out_num_removed = a->out_num_removed; A.out_num_fresh = a->out_num_fresh; A.out_fresh = a->out_fresh;
     return A;
 }
+
+extern "C++" template <class R> void cl_plan(R& r, plp_matcher*, CullLmArgs& A) {
+    const size_t R_ = (size_t)A.R, N = (size_t)A.N, L = (size_t)A.L;
+    r.in(A.fresh_offsets, R_ + 1); r.in(A.fresh, N); r.in(A.lm_erased, L); r.in(A.num_observed, L); r.in(A.num_observable, L);
+    r.in(A.first_kf_id, L); r.in(A.num_obs, L); r.in(A.owning_plane, L); r.in(A.cur_kf_id, R_); r.in(A.num_obs_thr, R_);
+    r.out(A.out_state, N); r.out(A.out_num_removed, R_); r.out(A.out_num_fresh, R_); r.out(A.out_fresh, N);
+}
 }  // namespace
 
 plp_status plp_cull_keyframes_device(plp_matcher* c, const plp_cull_keyframes_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ck_check(a, false)) return s;
     if (a->G == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    CullArgs A = ck_args(a);
-    DeviceRooms r;
-    ck_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_cull_keyframes((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, ck_args(a), ck_plan<DeviceRooms>, launch_cull_keyframes);
 }
 
 plp_status plp_cull_keyframes_host(plp_matcher* c, const plp_cull_keyframes_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = ck_check(a, true)) return s;
     if (a->G == 0) return PLP_OK;
-    CullArgs A = ck_args(a);
-    const size_t F = (size_t)A.F, L = (size_t)A.L, T = (size_t)A.T, G = (size_t)A.G, Cv = (size_t)A.Cv, K = F * A.kp_stride;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kf_lm, F * A.cap); s.in(A.kf_counts, F); s.in(A.undist, K); s.in(A.x_right, K); s.in(A.depths, K); s.in(A.depth_thr, F);
-    s.in(A.kf_id, F); s.in(A.kf_cannot_erase, F);
-    s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T); s.in(A.lm_erased, L); s.in(A.lm_num_obs, L);
-    s.in(A.cur_kf, G); s.in(A.covis_offsets, G + 1); s.in(A.covis, Cv);
-    s.out(A.out_num_removed, G); s.out(A.out_decision, Cv); s.out(A.out_num_valid, Cv); s.out(A.out_num_redundant, Cv);
-    s.out(A.out_kf_removed, G * F); s.out(A.out_lm_erased, G * L);
-    ck_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_cull_keyframes(c->stream, A));
-    return s.finish();
+    return host_call(c, ck_args(a), ck_plan<Stage>, launch_cull_keyframes);
 }
 
 // the host build of map_cull.hpp (no HIP call): the replay alone, which counts every entry itself
@@ -144,27 +137,14 @@ plp_status plp_cull_landmarks_device(plp_matcher* c, const plp_cull_landmarks_ar
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = cl_check(a, false)) return s;
     if (a->R == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_cull_landmarks((hipStream_t)hip_stream, cl_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, cl_args(a), cl_plan<DeviceRooms>, launch_cull_landmarks);
 }
 
 plp_status plp_cull_landmarks_host(plp_matcher* c, const plp_cull_landmarks_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = cl_check(a, true)) return s;
     if (a->R == 0) return PLP_OK;
-    CullLmArgs A = cl_args(a);
-    const size_t R = (size_t)A.R, N = (size_t)A.N, L = (size_t)A.L;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.fresh_offsets, R + 1); s.in(A.fresh, N); s.in(A.lm_erased, L); s.in(A.num_observed, L); s.in(A.num_observable, L);
-    s.in(A.first_kf_id, L); s.in(A.num_obs, L); s.in(A.owning_plane, L); s.in(A.cur_kf_id, R); s.in(A.num_obs_thr, R);
-    s.out(A.out_state, N); s.out(A.out_num_removed, R); s.out(A.out_num_fresh, R); s.out(A.out_fresh, N);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_cull_landmarks(c->stream, A));
-    return s.finish();
+    return host_call(c, cl_args(a), cl_plan<Stage>, launch_cull_landmarks);
 }
 
 int32_t plp_model_cull_landmarks_host(const plp_cull_landmarks_args* a) {

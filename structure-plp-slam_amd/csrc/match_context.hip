@@ -1,5 +1,6 @@
 // Host driver + C ABI of the array-form Hamming matchers (include/plp_front.h): the matchers, the query builders, the pair triangulation, BoW and
-// the side kernels.  The solvers' entries of the same context are in sim3_, pnp_, pose_opt_, transform_opt_, local_ba_ and local_map_context.hip.
+// the side kernels.  The solvers' entries of the same context are in sim3_, pnp_, essential_, two_view_, pose_opt_, transform_opt_, local_ba_, local_map_,
+// plane_, map_cull_, covisibility_, pose_graph_, global_ba_ and line_update_context.hip; matcher_context.hpp holds what all of them run through.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -235,17 +236,14 @@ plp_status plp_lbd_match_1nn_host(plp_matcher* c, const uint8_t* q, int32_t nq, 
     if (!c || !q || !t || !train_idx || !dist) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (nq <= 0 || nt <= 0) return PLP_OK;   // the reference prints an error and returns with `matches` untouched (:201-205)
     if (nt > 65535) return set_error(PLP_ERR_UNSUPPORTED, "more than 65535 train descriptors (16-bit index in the tie-break key)");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    const uint8_t *d_q = q, *d_t = t;   // device addresses after upload()
-    int32_t *d_train_idx = train_idx, *d_dist = dist;
-    Stage s(c->stage, c->stream);
-    s.in(d_q, (size_t)nq * 32); s.in(d_t, (size_t)nt * 32); s.out(d_train_idx, nq, false); s.out(d_dist, nq, false);
-    PLP_TRY(s.upload());
-    static const MihRanks R = mih_ranks();
-    launch_lbd_match_1nn(c->stream, d_q, nullptr, nq, d_t, nullptr, nt, R, d_train_idx, d_dist, 1);
-    PLP_HIP(hipGetLastError());
-    return s.finish();
+    struct { const uint8_t *q, *t; int32_t *train_idx, *dist; } A{q, t, train_idx, dist};
+    return host_call(
+        c, A, [=](Stage& s, plp_matcher*, auto& A) { s.in(A.q, (size_t)nq * 32); s.in(A.t, (size_t)nt * 32); s.out(A.train_idx, nq, false); s.out(A.dist, nq, false); },
+        [=](hipStream_t st, auto& A) {
+            static const MihRanks R = mih_ranks();
+            launch_lbd_match_1nn(st, A.q, nullptr, nq, A.t, nullptr, nt, R, A.train_idx, A.dist, 1);
+            return hipGetLastError();
+        });
 }
 
 plp_status plp_match_area_host(plp_matcher* c, const plp_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const plp_keypoint* kps_2,
@@ -255,21 +253,19 @@ plp_status plp_match_area_host(plp_matcher* c, const plp_keypoint* kps_1, const 
     *num_matches = 0;
     if (n1 <= 0) return PLP_OK;
     if (!kps_1 || !desc_1 || !prev_matched_pts || n2 < 0 || (n2 > 0 && (!kps_2 || !desc_2)) || n2 > 65535) return set_error(PLP_ERR_INVALID_ARG, "bad argument");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
     AreaArgs A{};
     A.kps1 = kps_1; A.desc1 = desc_1; A.kps2 = kps_2; A.desc2 = desc_2; A.n1 = n1; A.n2 = n2;
     A.grid_min_x = grid->min_x; A.grid_min_y = grid->min_y; A.inv_cell_w = grid->inv_cell_width; A.inv_cell_h = grid->inv_cell_height;
     A.grid_cols = grid->cols; A.grid_rows = grid->rows;
     A.prev_pts = prev_matched_pts; A.margin = (float)margin; A.lowe_ratio = lowe_ratio; A.check_orientation = check_orientation;
     A.matched_2_in_1 = matched_2_in_1; A.num_matches = num_matches;
-    Stage s(c->stage, c->stream);   // n2 == 0: the kernel reads no key point of frame 2 and no scratch
-    s.in(A.kps1, n1); s.in(A.desc1, (size_t)n1 * 32); s.in(A.kps2, n2); s.in(A.desc2, (size_t)n2 * 32);
-    s.out(A.matched_2_in_1, n1, false); s.out(A.prev_pts, (size_t)n1 * 2); s.out(A.num_matches, 1, false); s.room(A.scratch, (size_t)n2 * 2);
-    PLP_TRY(s.upload());
-    launch_match_area(c->stream, A);
-    PLP_HIP(hipGetLastError());
-    return s.finish();
+    return host_call(
+        c, A,
+        [=](Stage& s, plp_matcher*, AreaArgs& A) {   // n2 == 0: the kernel reads no key point of frame 2 and no scratch
+            s.in(A.kps1, n1); s.in(A.desc1, (size_t)n1 * 32); s.in(A.kps2, n2); s.in(A.desc2, (size_t)n2 * 32);
+            s.out(A.matched_2_in_1, n1, false); s.out(A.prev_pts, (size_t)n1 * 2); s.out(A.num_matches, 1, false); s.room(A.scratch, (size_t)n2 * 2);
+        },
+        [](hipStream_t st, AreaArgs& A) { launch_match_area(st, A); return hipGetLastError(); });
 }
 
 namespace {
@@ -384,16 +380,12 @@ plp_status post_extract_device(plp_matcher* c, const PostArgs& cam_args, const p
     if (d_kps && !d_undist) return set_error(PLP_ERR_INVALID_ARG, "d_undist is required with d_kps");
     if (d_depth && (rows <= 0 || cols <= 0 || depth_step < (size_t)cols * 4)) return set_error(PLP_ERR_INVALID_ARG, "bad depth geometry");
     if (d_kl && (!d_depth || !d_kl_depths || !d_kl_x_right)) return set_error(PLP_ERR_INVALID_ARG, "key lines need depth, d_kl_depths, d_kl_x_right");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
     PostArgs A = cam_args;
     A.kps = d_kps; A.counts = d_counts; A.cap = d_kps ? cap : 0;
     A.depth = d_depth; A.depth_step = depth_step; A.depth_frame_stride = depth_frame_stride;
     A.undist = d_undist; A.bearings = d_bearings; A.x_right = d_x_right; A.depths = d_depths;
     A.kl = d_kl; A.kl_counts = d_kl_counts; A.kl_cap = d_kl ? kl_cap : 0; A.kl_depths = d_kl_depths; A.kl_x_right = d_kl_x_right;
-    launch_post_extract((hipStream_t)hip_stream, A, B);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, A, NoArrays{}, [B](hipStream_t st, PostArgs& A) { launch_post_extract(st, A, B); return hipGetLastError(); });
 }
 
 plp_status post_extract_host(plp_matcher* c, const PostArgs& cam_args, const plp_keypoint* kps, int32_t n, const float* depth, int32_t rows,
@@ -458,38 +450,40 @@ ObserveArgs observe_args(const plp_observe_args* a, bool lines) {
     return A;
 }
 
-plp_status observe_device(plp_matcher* c, const plp_observe_args* a, bool lines, void* hip_stream) {
-    if (plp_status s = observe_check(c, a, lines)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (a->m_cap == 0) {   // no landmark slot: the reference's loop does not run
-        if (a->out_num_valid) PLP_HIP(hipMemsetAsync(a->out_num_valid, 0, (size_t)a->B * 4, st));
-        return PLP_OK;
-    }
-    const ObserveArgs A = observe_args(a, lines);
-    PLP_HIP(lines ? launch_observe_lines(st, A, a->B) : launch_observe_points(st, A, a->B));
-    return PLP_OK;
+// a launch_* function that takes the number of problems (frames) after the arguments, as a run
+extern "C++" template <class Args> auto run_of(hipError_t (*launch)(hipStream_t, const Args&, int), int B) {
+    return [=](hipStream_t st, const Args& A) { return launch(st, A, B); };
 }
 
-// host pointers: every array staged through the context's slab (plp_common.hpp Stage), the device path's kernel, the outputs copied back
+// the device form of a call without a landmark slot (m_cap == 0), where the reference's loop does not run: only the counts are cleared
+static plp_status clear_num_valid_device(plp_matcher* c, int32_t* d_num_valid, int B, void* hip_stream) {
+    return device_call(c, hip_stream, NoArgs{}, NoArrays{},
+                       [=](hipStream_t st, NoArgs&) { return d_num_valid ? hipMemsetAsync(d_num_valid, 0, (size_t)B * 4, st) : hipSuccess; });
+}
+
+// the arrays of a call of B problems, points or lines
+extern "C++" auto observe_plan(int B_, bool lines) {
+    return [=](auto& r, plp_matcher*, ObserveArgs& A) {
+        const size_t B = (size_t)B_, BM = B * A.m_cap;
+        r.in(A.pose, B * 15); r.in(A.counts, B); r.in(A.pos_w, BM * (lines ? 6 : 3)); r.in(A.normal, BM * 3);
+        r.in(A.min_dist, BM); r.in(A.max_dist, BM); r.in(A.skip, BM);
+        r.out(A.reproj, BM * 2); r.out(A.reproj2, BM * 2); r.out(A.x_right, BM); r.out(A.level, BM); r.out(A.valid, BM); r.out(A.num_valid, B);
+    };
+}
+
+plp_status observe_device(plp_matcher* c, const plp_observe_args* a, bool lines, void* hip_stream) {
+    if (plp_status s = observe_check(c, a, lines)) return s;
+    if (a->m_cap == 0) return clear_num_valid_device(c, a->out_num_valid, a->B, hip_stream);
+    return device_call(c, hip_stream, observe_args(a, lines), observe_plan(a->B, lines), run_of(lines ? launch_observe_lines : launch_observe_points, a->B));
+}
+
 plp_status observe_host(plp_matcher* c, const plp_observe_args* a, bool lines) {
     if (plp_status s = observe_check(c, a, lines)) return s;
-    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
-    if (M == 0) {
-        if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
+    if (a->m_cap == 0) {
+        if (a->out_num_valid) std::memset(a->out_num_valid, 0, (size_t)a->B * 4);
         return PLP_OK;
     }
-    ObserveArgs A = observe_args(a, lines);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, B * 15); s.in(A.counts, B); s.in(A.pos_w, BM * (lines ? 6 : 3)); s.in(A.normal, BM * 3);
-    s.in(A.min_dist, BM); s.in(A.max_dist, BM); s.in(A.skip, BM);
-    s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.level, BM); s.out(A.valid, BM); s.out(A.num_valid, B);
-    PLP_TRY(s.upload());
-    PLP_HIP(lines ? launch_observe_lines(c->stream, A, a->B) : launch_observe_points(c->stream, A, a->B));
-    return s.finish();
+    return host_call(c, observe_args(a, lines), observe_plan(a->B, lines), run_of(lines ? launch_observe_lines : launch_observe_points, a->B));
 }
 }  // namespace
 
@@ -524,30 +518,25 @@ ObserveArgs last_frame_args(const plp_last_frame_args* a, bool lines) {
     return A;
 }
 
-plp_status last_frame_device(plp_matcher* c, const plp_last_frame_args* a, bool lines, void* hip_stream) {
-    if (plp_status s = last_frame_check(c, a, lines)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    const ObserveArgs A = last_frame_args(a, lines);
-    PLP_HIP(lines ? launch_last_frame_lines((hipStream_t)hip_stream, A, a->B) : launch_last_frame_points((hipStream_t)hip_stream, A, a->B));
-    return PLP_OK;
+// the arrays of a call of B problems, points or lines.  m_cap == 0: nothing per slot is staged, the kernels still write every problem's direction and num_valid
+extern "C++" auto last_frame_plan(int B_, bool lines) {
+    return [=](auto& r, plp_matcher*, ObserveArgs& A) {
+        const size_t B = (size_t)B_, BM = B * A.m_cap;
+        r.in(A.pose, B * 15); r.in(A.pose_last, B * 15); r.in(A.counts, B); r.in(A.pos_w, BM * (lines ? 6 : 3)); r.in(A.skip, BM);
+        r.in(A.kps, BM); r.in(A.kl, BM);
+        r.out(A.reproj, BM * 2); r.out(A.reproj2, BM * 2); r.out(A.x_right, BM); r.out(A.x_right2, BM); r.out(A.level, BM); r.out(A.angle, BM);
+        r.out(A.valid, BM); r.out(A.direction, B); r.out(A.num_valid, B);
+    };
 }
 
-// m_cap == 0: nothing per slot is staged, the kernels still write every problem's direction and num_valid
+plp_status last_frame_device(plp_matcher* c, const plp_last_frame_args* a, bool lines, void* hip_stream) {
+    if (plp_status s = last_frame_check(c, a, lines)) return s;
+    return device_call(c, hip_stream, last_frame_args(a, lines), last_frame_plan(a->B, lines), run_of(lines ? launch_last_frame_lines : launch_last_frame_points, a->B));
+}
+
 plp_status last_frame_host(plp_matcher* c, const plp_last_frame_args* a, bool lines) {
     if (plp_status s = last_frame_check(c, a, lines)) return s;
-    const size_t B = (size_t)a->B, BM = B * a->m_cap;
-    ObserveArgs A = last_frame_args(a, lines);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, B * 15); s.in(A.pose_last, B * 15); s.in(A.counts, B); s.in(A.pos_w, BM * (lines ? 6 : 3)); s.in(A.skip, BM);
-    s.in(A.kps, BM); s.in(A.kl, BM);
-    s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.x_right2, BM); s.out(A.level, BM); s.out(A.angle, BM);
-    s.out(A.valid, BM); s.out(A.direction, B); s.out(A.num_valid, B);
-    PLP_TRY(s.upload());
-    PLP_HIP(lines ? launch_last_frame_lines(c->stream, A, a->B) : launch_last_frame_points(c->stream, A, a->B));
-    return s.finish();
+    return host_call(c, last_frame_args(a, lines), last_frame_plan(a->B, lines), run_of(lines ? launch_last_frame_lines : launch_last_frame_points, a->B));
 }
 }  // namespace
 
@@ -594,39 +583,31 @@ ProjectArgs project_args(const plp_project_args* a, bool lines) {
     return A;
 }
 
+// the arrays of a call of B problems, points or lines
+extern "C++" auto project_plan(int B_, bool lines) {
+    return [=](auto& r, plp_matcher*, ProjectArgs& A) {
+        const size_t B = (size_t)B_, M = (size_t)A.m_cap, BM = B * M;
+        const size_t LM = A.shared ? M : BM;   // rows of the landmark tables
+        r.in(A.pose, B * 15); r.in(A.counts, B); r.in(A.pos_w, LM * (lines ? 6 : 3)); r.in(A.normal, LM * 3);
+        r.in(A.min_dist, LM); r.in(A.max_dist, LM); r.in(A.skip, BM);
+        r.out(A.reproj_d, BM * 2); r.out(A.reproj2_d, BM * 2); r.out(A.reproj, BM * 2); r.out(A.reproj2, BM * 2); r.out(A.x_right, BM); r.out(A.x_right2, BM);
+        r.out(A.level, BM); r.out(A.valid, BM); r.out(A.status, BM); r.out(A.num_valid, B);
+    };
+}
+
 plp_status project_device(plp_matcher* c, const plp_project_args* a, bool lines, void* hip_stream) {
     if (plp_status s = project_check(c, a, lines)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (a->m_cap == 0) {   // no landmark slot: the reference's loop does not run
-        if (a->out_num_valid) PLP_HIP(hipMemsetAsync(a->out_num_valid, 0, (size_t)a->B * 4, st));
-        return PLP_OK;
-    }
-    const ProjectArgs A = project_args(a, lines);
-    PLP_HIP(lines ? launch_project_lines(st, A, a->B) : launch_project_points(st, A, a->B));
-    return PLP_OK;
+    if (a->m_cap == 0) return clear_num_valid_device(c, a->out_num_valid, a->B, hip_stream);
+    return device_call(c, hip_stream, project_args(a, lines), project_plan(a->B, lines), run_of(lines ? launch_project_lines : launch_project_points, a->B));
 }
 
 plp_status project_host(plp_matcher* c, const plp_project_args* a, bool lines) {
     if (plp_status s = project_check(c, a, lines)) return s;
-    const size_t B = (size_t)a->B, M = (size_t)a->m_cap, BM = B * M;
-    if (M == 0) {
-        if (a->out_num_valid) std::memset(a->out_num_valid, 0, B * 4);
+    if (a->m_cap == 0) {
+        if (a->out_num_valid) std::memset(a->out_num_valid, 0, (size_t)a->B * 4);
         return PLP_OK;
     }
-    ProjectArgs A = project_args(a, lines);
-    const size_t LM = A.shared ? M : BM;   // rows of the landmark tables
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, B * 15); s.in(A.counts, B); s.in(A.pos_w, LM * (lines ? 6 : 3)); s.in(A.normal, LM * 3);
-    s.in(A.min_dist, LM); s.in(A.max_dist, LM); s.in(A.skip, BM);
-    s.out(A.reproj_d, BM * 2); s.out(A.reproj2_d, BM * 2); s.out(A.reproj, BM * 2); s.out(A.reproj2, BM * 2); s.out(A.x_right, BM); s.out(A.x_right2, BM);
-    s.out(A.level, BM); s.out(A.valid, BM); s.out(A.status, BM); s.out(A.num_valid, B);
-    PLP_TRY(s.upload());
-    PLP_HIP(lines ? launch_project_lines(c->stream, A, a->B) : launch_project_points(c->stream, A, a->B));
-    return s.finish();
+    return host_call(c, project_args(a, lines), project_plan(a->B, lines), run_of(lines ? launch_project_lines : launch_project_points, a->B));
 }
 }  // namespace
 
@@ -686,54 +667,45 @@ Keylines3dArgs keylines_3d_args(const plp_keylines_3d_args* a) {
     A.pos_w = a->out_pos_w; A.valid = a->out_valid;
     return A;
 }
+
+extern "C++" auto stereo_keylines_plan(int B_) {
+    return [=](auto& r, plp_matcher*, StereoKeylineArgs& A) {
+        const size_t B = (size_t)B_, L = (size_t)A.cap_l, R = (size_t)A.cap_r;
+        r.in(A.kl_l, B * L); r.in(A.counts_l, B); r.in(A.kl_r, B * R); r.in(A.counts_r, B); r.in(A.train_idx, B * L); r.in(A.dist, B * L);
+        r.out(A.good, B * L); r.out(A.depths, B * L * 2); r.out(A.x_right, B * L * 2);
+    };
+}
+extern "C++" auto keylines_3d_plan(int B_) {
+    return [=](auto& r, plp_matcher*, Keylines3dArgs& A) {
+        const size_t B = (size_t)B_, M = (size_t)A.cap, R = (size_t)A.cap_r;
+        r.in(A.counts, B); r.in(A.pose, B * 15); r.in(A.kl, B * M); r.in(A.kl_depths, B * M * 2); r.in(A.good_match, B * M); r.in(A.kl_r, B * R);
+        r.in(A.counts_r, B); r.out(A.pos_w, B * M * 6); r.out(A.valid, B * M);
+    };
+}
 }  // namespace
 
 plp_status plp_stereo_keylines_device(plp_matcher* c, const plp_stereo_keylines_args* a, void* hip_stream) {
     if (plp_status s = stereo_keylines_check(c, a)) return s;
     if (a->cap_left == 0) return PLP_OK;   // no left key line: nothing to write
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_stereo_keylines((hipStream_t)hip_stream, stereo_keylines_args(a), a->B));
-    return PLP_OK;
+    return device_call(c, hip_stream, stereo_keylines_args(a), stereo_keylines_plan(a->B), run_of(launch_stereo_keylines, a->B));
 }
 
 plp_status plp_stereo_keylines_host(plp_matcher* c, const plp_stereo_keylines_args* a) {
     if (plp_status s = stereo_keylines_check(c, a)) return s;
     if (a->cap_left == 0) return PLP_OK;
-    const size_t B = (size_t)a->B, L = (size_t)a->cap_left, R = (size_t)a->cap_right;
-    StereoKeylineArgs A = stereo_keylines_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kl_l, B * L); s.in(A.counts_l, B); s.in(A.kl_r, B * R); s.in(A.counts_r, B); s.in(A.train_idx, B * L); s.in(A.dist, B * L);
-    s.out(A.good, B * L); s.out(A.depths, B * L * 2); s.out(A.x_right, B * L * 2);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_stereo_keylines(c->stream, A, a->B));
-    return s.finish();
+    return host_call(c, stereo_keylines_args(a), stereo_keylines_plan(a->B), run_of(launch_stereo_keylines, a->B));
 }
 
 plp_status plp_keylines_3d_device(plp_matcher* c, const plp_keylines_3d_args* a, void* hip_stream) {
     if (plp_status s = keylines_3d_check(c, a)) return s;
     if (a->cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_keylines_3d((hipStream_t)hip_stream, keylines_3d_args(a), a->B));
-    return PLP_OK;
+    return device_call(c, hip_stream, keylines_3d_args(a), keylines_3d_plan(a->B), run_of(launch_keylines_3d, a->B));
 }
 
 plp_status plp_keylines_3d_host(plp_matcher* c, const plp_keylines_3d_args* a) {
     if (plp_status s = keylines_3d_check(c, a)) return s;
     if (a->cap == 0) return PLP_OK;
-    const size_t B = (size_t)a->B, M = (size_t)a->cap, R = (size_t)a->cap_right;
-    Keylines3dArgs A = keylines_3d_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.counts, B); s.in(A.pose, B * 15); s.in(A.kl, B * M); s.in(A.kl_depths, B * M * 2); s.in(A.good_match, B * M); s.in(A.kl_r, B * R);
-    s.in(A.counts_r, B); s.out(A.pos_w, B * M * 6); s.out(A.valid, B * M);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_keylines_3d(c->stream, A, a->B));
-    return s.finish();
+    return host_call(c, keylines_3d_args(a), keylines_3d_plan(a->B), run_of(launch_keylines_3d, a->B));
 }
 
 // ---- key-frame pair line triangulation (include/plp_front.h: plp_median_depth_*, plp_triangulate_keyline_pairs_*; keyline_pair_kernels.hip)
@@ -831,54 +803,43 @@ KeylinePairArgs keyline_pairs_args(const plp_keyline_pairs_args* a) {
     A.out_match = a->out_match; A.out_pos_w = a->out_pos_w; A.out_status = a->out_status; A.out_occ_cur = a->out_occupied_cur;
     return A;
 }
+
+extern "C++" auto median_depth_plan(int F_) {
+    return [=](auto& r, plp_matcher*, MedianDepthArgs& A) {
+        const size_t F = (size_t)F_, M = (size_t)A.m_cap;
+        r.in(A.pose, F * 15); r.in(A.pos_w, F * M * 3); r.in(A.valid, F * M); r.in(A.counts, F); r.out(A.median, F); r.out(A.count, F);
+    };
+}
+extern "C++" template <class R> void keyline_pairs_plan(R& r, plp_matcher*, KeylinePairArgs& A) {
+    const size_t F = (size_t)A.F, M = (size_t)A.cap, K = (size_t)A.kp_cap, P = (size_t)A.P, G = (size_t)A.G;
+    r.in(A.kl, F * M); r.in(A.counts, F); r.in(A.line_fn, F * M * 3); r.in(A.x_right, F * M * 2); r.in(A.kp_depths, F * K); r.in(A.kp_counts, F);
+    r.in(A.pose, F * 15); r.in(A.median, F); r.in(A.lines_3d, F * M * 6); r.in(A.occupied, F * M); r.in(A.pairs, P * 2); r.in(A.group_offsets, G + 1);
+    r.in(A.train_idx, P * M); r.in(A.dist, P * M);
+    r.out(A.out_match, P * M); r.out(A.out_pos_w, P * M * 6); r.out(A.out_status, P * M); r.out(A.out_occ_cur, G * M);
+}
 }  // namespace
 
 plp_status plp_median_depth_device(plp_matcher* c, const plp_median_depth_args* a, void* hip_stream) {
     if (plp_status s = median_depth_check(c, a)) return s;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_median_depth((hipStream_t)hip_stream, median_depth_args(a), a->F));
-    return PLP_OK;
+    return device_call(c, hip_stream, median_depth_args(a), median_depth_plan(a->F), run_of(launch_median_depth, a->F));
 }
 
 plp_status plp_median_depth_host(plp_matcher* c, const plp_median_depth_args* a) {
     if (plp_status s = median_depth_check(c, a)) return s;
-    const size_t F = (size_t)a->F, M = (size_t)a->m_cap;
-    MedianDepthArgs A = median_depth_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * 15); s.in(A.pos_w, F * M * 3); s.in(A.valid, F * M); s.in(A.counts, F); s.out(A.median, F); s.out(A.count, F);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_median_depth(c->stream, A, a->F));
-    return s.finish();
+    return host_call(c, median_depth_args(a), median_depth_plan(a->F), run_of(launch_median_depth, a->F));
 }
 
 plp_status plp_triangulate_keyline_pairs_device(plp_matcher* c, const plp_keyline_pairs_args* a, void* hip_stream) {
     if (plp_status s = keyline_pairs_check(c, a)) return s;
     if (keyline_pairs_empty(a)) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_keyline_pairs((hipStream_t)hip_stream, keyline_pairs_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, keyline_pairs_args(a), keyline_pairs_plan<DeviceRooms>, launch_keyline_pairs);
 }
 
 plp_status plp_triangulate_keyline_pairs_host(plp_matcher* c, const plp_keyline_pairs_args* a) {
     if (plp_status s = keyline_pairs_check(c, a)) return s;
     if (keyline_pairs_empty(a)) return PLP_OK;
     if (plp_status s = keyline_pairs_check_groups(a)) return s;
-    const size_t F = (size_t)a->F, M = (size_t)a->cap, K = (size_t)a->kp_cap, P = (size_t)a->P, G = (size_t)a->G;
-    KeylinePairArgs A = keyline_pairs_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kl, F * M); s.in(A.counts, F); s.in(A.line_fn, F * M * 3); s.in(A.x_right, F * M * 2); s.in(A.kp_depths, F * K); s.in(A.kp_counts, F);
-    s.in(A.pose, F * 15); s.in(A.median, F); s.in(A.lines_3d, F * M * 6); s.in(A.occupied, F * M); s.in(A.pairs, P * 2); s.in(A.group_offsets, G + 1);
-    s.in(A.train_idx, P * M); s.in(A.dist, P * M);
-    s.out(A.out_match, P * M); s.out(A.out_pos_w, P * M * 6); s.out(A.out_status, P * M); s.out(A.out_occ_cur, G * M);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_keyline_pairs(c->stream, A));
-    return s.finish();
+    return host_call(c, keyline_pairs_args(a), keyline_pairs_plan<Stage>, launch_keyline_pairs);
 }
 
 // ---- key-frame pair point triangulation (include/plp_front.h: plp_keyframe_pair_geometry_*, plp_triangulate_keypoint_pairs_*; keypoint_pair_kernels.hip)
@@ -942,56 +903,43 @@ KeypointPairArgs keypoint_pairs_args(const plp_keypoint_pairs_args* a) {
     A.out_idx_1 = a->out_idx_1; A.out_pos_w = a->out_pos_w; A.out_status = a->out_status; A.occ1 = a->occupied_1_io; A.occ2 = a->occupied_2_io;
     return A;
 }
+
+extern "C++" template <class R> void pair_geometry_plan(R& r, plp_matcher*, PairGeometryArgs& A) {
+    const size_t F = (size_t)A.F, P = (size_t)A.P;
+    r.in(A.pose, F * 15); r.in(A.median, F); r.in(A.pairs, P * 2); r.out(A.out_skip, P); r.out(A.out_epipolar, P * 12); r.out(A.out_baseline, P);
+}
+extern "C++" template <class R> void keypoint_pairs_plan(R& r, plp_matcher*, KeypointPairArgs& A) {
+    const size_t F = (size_t)A.F, M = (size_t)A.cap, Q = (size_t)A.m_cap, P = (size_t)A.P;
+    r.in(A.kps, F * M); r.in(A.bearings, F * M * 3); r.in(A.x_right, F * M); r.in(A.depths, F * M); r.in(A.counts, F); r.in(A.pose, F * 15);
+    r.in(A.pairs, P * 2); r.in(A.match_q, P * M); r.in(A.q_feature, P * Q); r.in(A.pair_skip, P);
+    r.out(A.out_idx_1, P * M); r.out(A.out_pos_w, P * M * 3); r.out(A.out_status, P * M); r.out(A.occ1, P * M); r.out(A.occ2, P * M);
+}
 }  // namespace
 
 plp_status plp_keyframe_pair_geometry_device(plp_matcher* c, const plp_keyframe_pair_geometry_args* a, void* hip_stream) {
     if (plp_status s = pair_geometry_check(c, a)) return s;
     if (a->P == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_pair_geometry((hipStream_t)hip_stream, pair_geometry_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, pair_geometry_args(a), pair_geometry_plan<DeviceRooms>, launch_pair_geometry);
 }
 
 plp_status plp_keyframe_pair_geometry_host(plp_matcher* c, const plp_keyframe_pair_geometry_args* a) {
     if (plp_status s = pair_geometry_check(c, a)) return s;
     if (a->P == 0) return PLP_OK;
     if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
-    const size_t F = (size_t)a->F, P = (size_t)a->P;
-    PairGeometryArgs A = pair_geometry_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * 15); s.in(A.median, F); s.in(A.pairs, P * 2); s.out(A.out_skip, P); s.out(A.out_epipolar, P * 12); s.out(A.out_baseline, P);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_pair_geometry(c->stream, A));
-    return s.finish();
+    return host_call(c, pair_geometry_args(a), pair_geometry_plan<Stage>, launch_pair_geometry);
 }
 
 plp_status plp_triangulate_keypoint_pairs_device(plp_matcher* c, const plp_keypoint_pairs_args* a, void* hip_stream) {
     if (plp_status s = keypoint_pairs_check(c, a)) return s;
     if (keypoint_pairs_empty(a)) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_keypoint_pairs((hipStream_t)hip_stream, keypoint_pairs_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, keypoint_pairs_args(a), keypoint_pairs_plan<DeviceRooms>, launch_keypoint_pairs);
 }
 
 plp_status plp_triangulate_keypoint_pairs_host(plp_matcher* c, const plp_keypoint_pairs_args* a) {
     if (plp_status s = keypoint_pairs_check(c, a)) return s;
     if (keypoint_pairs_empty(a)) return PLP_OK;
     if (plp_status s = check_pairs_in_table(a->pairs, a->P, a->F)) return s;
-    const size_t F = (size_t)a->F, M = (size_t)a->cap, Q = (size_t)a->m_cap, P = (size_t)a->P;
-    KeypointPairArgs A = keypoint_pairs_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.kps, F * M); s.in(A.bearings, F * M * 3); s.in(A.x_right, F * M); s.in(A.depths, F * M); s.in(A.counts, F); s.in(A.pose, F * 15);
-    s.in(A.pairs, P * 2); s.in(A.match_q, P * M); s.in(A.q_feature, P * Q); s.in(A.pair_skip, P);
-    s.out(A.out_idx_1, P * M); s.out(A.out_pos_w, P * M * 3); s.out(A.out_status, P * M); s.out(A.occ1, P * M); s.out(A.occ2, P * M);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_keypoint_pairs(c->stream, A));
-    return s.finish();
+    return host_call(c, keypoint_pairs_args(a), keypoint_pairs_plan<Stage>, launch_keypoint_pairs);
 }
 
 // ---- landmark normals and valid distance ranges (include/plp_front.h: plp_landmark[_line]_geometry_*; landmark_geometry_kernels.hip)
@@ -1031,15 +979,21 @@ LandmarkGeometryArgs landmark_geometry_args(const plp_landmark_geometry_args* a,
     return A;
 }
 
+extern "C++" auto landmark_geometry_plan(bool lines) {
+    return [=](auto& r, plp_matcher*, LandmarkGeometryArgs& A) {
+        const size_t F = (size_t)A.F, M = (size_t)A.cap, L = (size_t)A.L, T = list_end(r, A.obs_offsets, A.L);
+        r.in(A.pose, F * 15); r.in(A.counts, F); r.in(A.kps, F * M); r.in(A.kl, F * M); r.in(A.pos_w, L * (lines ? 6 : 3)); r.in(A.ref_kf, L); r.in(A.skip, L);
+        r.in(A.obs_offsets, L + 1); r.in(A.obs_kf, T); r.in(A.obs_idx, T);
+        r.out(A.normal, L * 3); r.out(A.min_dist, L); r.out(A.max_dist, L); r.out(A.status, L);
+    };
+}
+
 plp_status landmark_geometry_device(plp_matcher* c, const plp_landmark_geometry_args* a, void* hip_stream, bool lines) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = landmark_geometry_check(a, lines)) return s;
     if (a->L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    const LandmarkGeometryArgs A = landmark_geometry_args(a, lines);
-    PLP_HIP(lines ? launch_landmark_geometry_lines((hipStream_t)hip_stream, A) : launch_landmark_geometry_points((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, landmark_geometry_args(a, lines), landmark_geometry_plan(lines),
+                       lines ? launch_landmark_geometry_lines : launch_landmark_geometry_points);
 }
 
 plp_status landmark_geometry_host(plp_matcher* c, const plp_landmark_geometry_args* a, bool lines) {
@@ -1047,17 +1001,8 @@ plp_status landmark_geometry_host(plp_matcher* c, const plp_landmark_geometry_ar
     if (plp_status s = landmark_geometry_check(a, lines)) return s;
     if (a->L == 0) return PLP_OK;
     if (plp_status s = landmark_geometry_check_offsets(a)) return s;
-    const size_t F = (size_t)a->F, M = (size_t)a->cap, L = (size_t)a->L, T = (size_t)a->obs_offsets[a->L];
-    LandmarkGeometryArgs A = landmark_geometry_args(a, lines);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * 15); s.in(A.counts, F); s.in(A.kps, F * M); s.in(A.kl, F * M); s.in(A.pos_w, L * (lines ? 6 : 3)); s.in(A.ref_kf, L); s.in(A.skip, L);
-    s.in(A.obs_offsets, L + 1); s.in(A.obs_kf, T); s.in(A.obs_idx, T);
-    s.out(A.normal, L * 3); s.out(A.min_dist, L); s.out(A.max_dist, L); s.out(A.status, L);
-    PLP_TRY(s.upload());
-    PLP_HIP(lines ? launch_landmark_geometry_lines(c->stream, A) : launch_landmark_geometry_points(c->stream, A));
-    return s.finish();
+    return host_call(c, landmark_geometry_args(a, lines), landmark_geometry_plan(lines),
+                     lines ? launch_landmark_geometry_lines : launch_landmark_geometry_points);
 }
 }  // namespace
 
@@ -1147,6 +1092,14 @@ BowPairsArgs bow_pairs_args(const plp_bow_score_pairs_args* a) {
     A.a_row = a->a_row; A.b_row = a->b_row; A.out_score = a->out_score;
     return A;
 }
+
+extern "C++" template <class R> void bow_pairs_plan(R& r, plp_matcher*, BowPairsArgs& A) {
+    const size_t NA = (size_t)A.NA, NB = (size_t)A.NB, P = (size_t)A.P;
+    r.in(A.a_word, NA * A.stride_a); r.in(A.a_value, NA * A.stride_a); r.in(A.a_n, NA);
+    r.in(A.b_word, NB * A.stride_b); r.in(A.b_value, NB * A.stride_b); r.in(A.b_n, NB);
+    r.in(A.a_row, P); r.in(A.b_row, P);
+    r.out(A.out_score, P, false);
+}
 }  // namespace
 
 plp_status plp_bow_query_device(plp_matcher* c, const plp_bow_query_args* a, void* hip_stream) {
@@ -1209,27 +1162,14 @@ plp_status plp_bow_score_pairs_device(plp_matcher* c, const plp_bow_score_pairs_
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = bow_pairs_check(a)) return s;
     if (a->P == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_bow_score_pairs((hipStream_t)hip_stream, bow_pairs_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, bow_pairs_args(a), bow_pairs_plan<DeviceRooms>, launch_bow_score_pairs);
 }
 
 plp_status plp_bow_score_pairs_host(plp_matcher* c, const plp_bow_score_pairs_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = bow_pairs_check(a)) return s;
     if (a->P == 0) return PLP_OK;
-    BowPairsArgs A = bow_pairs_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.a_word, (size_t)a->NA * a->stride_a); s.in(A.a_value, (size_t)a->NA * a->stride_a); s.in(A.a_n, (size_t)a->NA);
-    s.in(A.b_word, (size_t)a->NB * a->stride_b); s.in(A.b_value, (size_t)a->NB * a->stride_b); s.in(A.b_n, (size_t)a->NB);
-    s.in(A.a_row, (size_t)a->P); s.in(A.b_row, (size_t)a->P);
-    s.out(A.out_score, (size_t)a->P, false);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_bow_score_pairs(c->stream, A));
-    return s.finish();
+    return host_call(c, bow_pairs_args(a), bow_pairs_plan<Stage>, launch_bow_score_pairs);
 }
 
 // the host build of bow_score.hpp (no HIP call)
@@ -1244,12 +1184,10 @@ plp_status plp_convert_to_grayscale_device(plp_matcher* c, const uint8_t* d_src,
     if (!c || !d_src || !d_gray) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (rows <= 0 || cols <= 0 || B <= 0 || (channels != 3 && channels != 4) || (color_order != 0 && color_order != 1) ||
         src_step < (size_t)cols * channels || gray_step < (size_t)cols) return set_error(PLP_ERR_INVALID_ARG, "bad geometry");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_to_gray((hipStream_t)hip_stream, d_src, rows, cols, src_step, src_frame_stride, channels, color_order, B, d_gray,
-                   gray_step, gray_frame_stride);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, NoArgs{}, NoArrays{}, [=](hipStream_t st, NoArgs&) {
+        launch_to_gray(st, d_src, rows, cols, src_step, src_frame_stride, channels, color_order, B, d_gray, gray_step, gray_frame_stride);
+        return hipGetLastError();
+    });
 }
 
 plp_status plp_convert_to_true_depth_device(plp_matcher* c, const void* d_src, int32_t src_is_u16, int32_t rows, int32_t cols, size_t src_step,
@@ -1258,12 +1196,10 @@ plp_status plp_convert_to_true_depth_device(plp_matcher* c, const void* d_src, i
     if (!c || !d_src || !d_dst) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (rows <= 0 || cols <= 0 || B <= 0 || src_step < (size_t)cols * (src_is_u16 ? 2 : 4) || dst_step < (size_t)cols * 4)
         return set_error(PLP_ERR_INVALID_ARG, "bad geometry");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_to_depth((hipStream_t)hip_stream, d_src, src_is_u16 != 0, rows, cols, src_step, src_frame_stride,
-                    (float)(1.0 / depthmap_factor), B, d_dst, dst_step, dst_frame_stride);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, NoArgs{}, NoArrays{}, [=](hipStream_t st, NoArgs&) {
+        launch_to_depth(st, d_src, src_is_u16 != 0, rows, cols, src_step, src_frame_stride, (float)(1.0 / depthmap_factor), B, d_dst, dst_step, dst_frame_stride);
+        return hipGetLastError();
+    });
 }
 
 static plp_status rectify_map_impl(plp_matcher* c, const double* K, const double* D, int32_t n_dist, const double* R, const plp_camera* rect_cam,
@@ -1291,11 +1227,7 @@ static plp_status rectify_map_impl(plp_matcher* c, const double* K, const double
     for (int i = 0; i < n_dist; ++i) A.d[i] = D[i];
     A.fx = K[0]; A.fy = K[4]; A.u0 = K[2]; A.v0 = K[5];
     A.rows = rows; A.cols = cols; A.map_x = d_map_x; A.map_y = d_map_y; A.map_step = map_step;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_rectify_map((hipStream_t)hip_stream, A, fisheye);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, A, NoArrays{}, [=](hipStream_t st, RectifyArgs& A) { launch_rectify_map(st, A, fisheye); return hipGetLastError(); });
 }
 
 plp_status plp_rectify_map_device(plp_matcher* c, const double* K, const double* D, int32_t n_dist, const double* R, const plp_camera* rect_cam,
@@ -1315,12 +1247,10 @@ plp_status plp_remap_linear_device(plp_matcher* c, const uint8_t* d_src, int32_t
     if (rows <= 0 || cols <= 0 || dst_rows <= 0 || dst_cols <= 0 || B <= 0 || rows > 32767 || cols > 32767 || src_step < (size_t)cols ||
         dst_step < (size_t)dst_cols || map_step < (size_t)dst_cols * 4 || (map_step & 3))
         return set_error(PLP_ERR_INVALID_ARG, "bad geometry");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_remap_linear((hipStream_t)hip_stream, d_src, rows, cols, src_step, src_frame_stride, d_map_x, d_map_y, map_step, dst_rows, dst_cols, B, d_dst,
-                        dst_step, dst_frame_stride);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, NoArgs{}, NoArrays{}, [=](hipStream_t st, NoArgs&) {
+        launch_remap_linear(st, d_src, rows, cols, src_step, src_frame_stride, d_map_x, d_map_y, map_step, dst_rows, dst_cols, B, d_dst, dst_step, dst_frame_stride);
+        return hipGetLastError();
+    });
 }
 
 plp_status plp_color_vote_device(plp_matcher* c, const uint8_t* d_mask, int32_t rows, int32_t cols, size_t mask_step,
@@ -1328,23 +1258,28 @@ plp_status plp_color_vote_device(plp_matcher* c, const uint8_t* d_mask, int32_t 
                                  int32_t cap, int32_t B, int32_t check_3x3_window, int32_t* d_labels, void* hip_stream) {
     if (!c || !d_mask || !d_undist || !d_labels) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (rows <= 0 || cols <= 0 || cap <= 0 || B <= 0 || mask_step < (size_t)cols * 3) return set_error(PLP_ERR_INVALID_ARG, "bad geometry");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_color_vote((hipStream_t)hip_stream, d_mask, rows, cols, mask_step, mask_frame_stride, d_undist, d_valid, d_counts, cap, B,
-                      check_3x3_window != 0, d_labels);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, NoArgs{}, NoArrays{}, [=](hipStream_t st, NoArgs&) {
+        launch_color_vote(st, d_mask, rows, cols, mask_step, mask_frame_stride, d_undist, d_valid, d_counts, cap, B, check_3x3_window != 0, d_labels);
+        return hipGetLastError();
+    });
 }
+
+namespace {
+struct LandmarkDescriptorArgs { const uint8_t* descs; const int32_t* offsets; int32_t L; int32_t* best_idx; };
+extern "C++" template <class R> void landmark_descriptor_plan(R& r, plp_matcher*, LandmarkDescriptorArgs& A) {   // no row at all: the kernel reads no descriptor
+    r.in(A.descs, list_end(r, A.offsets, A.L) * 32); r.in(A.offsets, (size_t)A.L + 1); r.out(A.best_idx, A.L, false);
+}
+static hipError_t landmark_descriptor_run(hipStream_t st, const LandmarkDescriptorArgs& A) {
+    launch_landmark_descriptor(st, A.descs, A.offsets, A.L, A.best_idx);
+    return hipGetLastError();
+}
+}  // namespace
 
 plp_status plp_landmark_descriptor_device(plp_matcher* c, const uint8_t* d_descs, const int32_t* d_offsets, int32_t L, int32_t* d_best_idx,
                                           void* hip_stream) {
     if (!c || !d_offsets || !d_best_idx || L < 0) return set_error(PLP_ERR_INVALID_ARG, "bad argument");
     if (L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    launch_landmark_descriptor((hipStream_t)hip_stream, d_descs, d_offsets, L, d_best_idx);
-    PLP_HIP(hipGetLastError());
-    return PLP_OK;
+    return device_call(c, hip_stream, LandmarkDescriptorArgs{d_descs, d_offsets, L, d_best_idx}, landmark_descriptor_plan<DeviceRooms>, landmark_descriptor_run);
 }
 
 plp_status plp_landmark_descriptor_host(plp_matcher* c, const uint8_t* descs, const int32_t* offsets, int32_t L, int32_t* best_idx) {
@@ -1354,17 +1289,7 @@ plp_status plp_landmark_descriptor_host(plp_matcher* c, const uint8_t* descs, co
     if (total < 0 || (total > 0 && !descs)) return set_error(PLP_ERR_INVALID_ARG, "bad offsets / descs");
     for (int l = 0; l < L; ++l)
         if (offsets[l + 1] < offsets[l] || offsets[l + 1] - offsets[l] > 1024) return set_error(PLP_ERR_UNSUPPORTED, "offsets must ascend, at most 1024 rows per landmark");
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    const uint8_t* d_descs = descs;   // device addresses after upload()
-    const int32_t* d_offsets = offsets;
-    int32_t* d_best_idx = best_idx;
-    Stage s(c->stage, c->stream);   // no row at all: the kernel reads no descriptor
-    s.in(d_descs, (size_t)total * 32); s.in(d_offsets, (size_t)L + 1); s.out(d_best_idx, L, false);
-    PLP_TRY(s.upload());
-    launch_landmark_descriptor(c->stream, d_descs, d_offsets, L, d_best_idx);
-    PLP_HIP(hipGetLastError());
-    return s.finish();
+    return host_call(c, LandmarkDescriptorArgs{descs, offsets, L, best_idx}, landmark_descriptor_plan<Stage>, landmark_descriptor_run);
 }
 
 plp_status plp_match_debug_plan(const plp_match_args* a, int32_t* out4) {
@@ -1406,16 +1331,10 @@ plp_status plp_hamming_matrix_device(plp_matcher* c, const uint8_t* d_q, int32_t
 plp_status plp_hamming_matrix_host(plp_matcher* c, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, uint16_t* dist) {
     if (!c || !q || !t || !dist) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
     if (nq <= 0 || nt <= 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    const uint8_t *d_q = q, *d_t = t;   // device addresses after upload()
-    uint16_t* d_dist = dist;
-    Stage s(c->stage, c->stream);
-    s.in(d_q, (size_t)nq * 32); s.in(d_t, (size_t)nt * 32); s.out(d_dist, (size_t)nq * nt, false);
-    PLP_TRY(s.upload());
-    launch_hamming_matrix(c->stream, d_q, nq, d_t, nt, d_dist);
-    PLP_HIP(hipGetLastError());
-    return s.finish();
+    struct { const uint8_t *q, *t; uint16_t* dist; } A{q, t, dist};
+    return host_call(
+        c, A, [=](Stage& s, plp_matcher*, auto& A) { s.in(A.q, (size_t)nq * 32); s.in(A.t, (size_t)nt * 32); s.out(A.dist, (size_t)nq * nt, false); },
+        [=](hipStream_t st, auto& A) { launch_hamming_matrix(st, A.q, nq, A.t, nt, A.dist); return hipGetLastError(); });
 }
 
 // Host model of the bin ranking inside the matchers' orientation check (csrc/libstdcxx_sort.hpp), callable without a GPU: the

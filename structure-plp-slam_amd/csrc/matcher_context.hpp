@@ -1,5 +1,6 @@
 // The matcher context (plp_matcher of include/plp_front.h) and what the files that implement its entry points share: match_context.hip and one
-// *_context.hip per solver (sim3, pnp, essential, two_view, pose_opt, transform_opt, local_ba, local_map, plane, map_cull, covisibility, pose_graph, global_ba).
+// *_context.hip per solver (sim3, pnp, essential, two_view, pose_opt, transform_opt, local_ba, local_map, plane, map_cull, covisibility, pose_graph,
+// global_ba, line_update).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,16 +49,60 @@ template <class Args> void set_camera(Args& A, const plp_camera_model& cm) {
     A.cols_d = (double)(unsigned)cm.cols; A.rows_d = (double)(unsigned)cm.rows;
 }
 
-// The device entries' side of a solver's *_rooms() function, which names every context buffer of the solver once, with its element count, for
-// both entries (the host-pointer entries pass a Stage, whose room() ignores the buffer): the buffer is reserved at count * sizeof(T), the
-// pointer set, the first error kept and nothing reserved after it.
+// Every entry of the context names the arrays of its call once, in a plan: a callable (R& r, plp_matcher* c, Args& A), usually a function template
+// xx_plan<R>, that declares every pointer field of A in the order the call lists it: r.in (read), r.out (written; keep, Stage's comment in
+// plp_common.hpp), r.room (a context buffer the launches hand work through).  The two forms of the entry run the same plan with two receivers:
+// DeviceRooms for the device form, whose arrays are the caller's device memory, and plp::Stage for the host-pointer form, which stages every
+// declared array through the context's slab.
+
+// The device form's receiver: in and out do nothing; room reserves the context's buffer at count * sizeof(T) and sets the pointer, the first
+// error is kept and nothing reserved after it.
 struct DeviceRooms {
     hipError_t err = hipSuccess;
+    template <class T> void in(const T*&, size_t) {}
+    template <class T> void out(T*&, size_t, bool = true) {}
     template <class T> void room(plp::DevBuf& buf, T*& p, size_t count) {
         if (err != hipSuccess) return;
         err = buf.reserve(count * sizeof(T));
         p = static_cast<T*>(buf.p);
     }
 };
+
+// the last entry of an offset list (NULL: 0), a count only the host-pointer form can read and only that form needs: for the plan of a call
+// whose array sizes stand in such a list.  Called before upload(), while the list is still the caller's host memory.
+inline size_t list_end(const plp::Stage&, const int32_t* offsets, int n) { return offsets ? (size_t)offsets[n] : 0; }
+inline size_t list_end(const DeviceRooms&, const int32_t*, int) { return 0; }
+
+// a call without an argument struct or without an array to declare (the image entries, which have a device form only)
+struct NoArgs {};
+struct NoArrays { template <class R, class Args> void operator()(R&, plp_matcher*, Args&) const {} };
+
+// what a run answers, as the entry's status: a launch_* function gives the first hipError_t of its launches, a run of several steps a plp_status
+inline plp_status run_status(plp_status s) { return s; }
+inline plp_status run_status(hipError_t launch_error) { PLP_HIP(launch_error); return PLP_OK; }
+
+// The two scaffolds, one per form of an entry, called once the entry has checked its arguments and answered an empty call (neither takes the
+// lock nor calls HIP).  They are the only places that know which lock is held, which device is set and which stream runs the call.  run is a
+// callable (hipStream_t, Args&), mostly the launch_* function itself; work that needs the rooms' device addresses belongs in it.
+// Device form: the caller's arrays are device memory and the call is queued on the caller's stream; the scaffold waits for nothing.
+template <class Args, class Plan, class Run> plp_status device_call(plp_matcher* c, void* hip_stream, Args A, Plan plan, Run run) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    DeviceRooms r;
+    plan(r, c, A);
+    PLP_HIP(r.err);
+    return run_status(run((hipStream_t)hip_stream, A));
+}
+
+// Host-pointer form: the plan's arrays go through the context's slab and the call runs on the context's stream; finish() is the one wait.
+template <class Args, class Plan, class Run> plp_status host_call(plp_matcher* c, Args A, Plan plan, Run run) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    PLP_HIP(hipSetDevice(c->device));
+    plp::Stage s(c->stage, c->stream);
+    plan(s, c, A);
+    PLP_TRY(s.upload());
+    PLP_TRY(run_status(run(c->stream, A)));
+    return s.finish();
+}
 
 }  // namespace

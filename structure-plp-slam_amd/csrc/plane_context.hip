@@ -44,9 +44,15 @@ PlaneArgs plane_args(const plp_plane_ransac_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffer (device entry) or a room of the slab (host-pointer entry), elements
-extern "C++" template <class R> void plane_rooms(R& r, plp_matcher* c, PlaneArgs& A) {
-    r.room(c->plane_hyp, A.ctx_hyp, (size_t)A.P * A.iters * kPlaneHypDoubles);
+// the arrays of the call; the room is what the launches hand to one another
+extern "C++" template <class R> void plane_plan(R& r, plp_matcher* c, PlaneArgs& A) {
+    const size_t P = (size_t)A.P, M = (size_t)A.n_cap, I = (size_t)A.iters;
+    r.in(A.counts, P); r.in(A.pos_w, P * M * 3); r.in(A.flags, P * M); r.in(A.dist_thresh, P); r.in(A.error_thresh, P); r.in(A.best_error_in, P);
+    r.in(A.equation_in, P * 4); r.in(A.samples, P * I * (size_t)(A.m_cap > 0 ? A.m_cap : 0));
+    r.out(A.out_status, P, false); r.out(A.out_flags, P, false); r.out(A.out_equation, P * 4); r.out(A.out_best_error, P);
+    r.out(A.out_best_iter, P, false); r.out(A.out_last_iter, P, false); r.out(A.out_num_inliers, P, false); r.out(A.out_inliers, P * M);
+    r.out(A.out_hyp_residual, P * I, false); r.out(A.out_hyp_inliers, P * I, false); r.out(A.out_hyp_error, P * I, false);
+    r.room(c->plane_hyp, A.ctx_hyp, P * I * kPlaneHypDoubles);
 }
 
 // one problem of the host build: the kernels' steps, one hypothesis and one point after the other
@@ -147,66 +153,40 @@ PlaneRefineArgs refine_args(const plp_plane_refine_args* a) {
     A.dist_thresh = a->dist_thresh; A.out_changed = a->out_changed;
     return A;
 }
+
+extern "C++" template <class R> void refine_plan(R& r, plp_matcher*, PlaneRefineArgs& A) {
+    const size_t M = (size_t)A.M, NP = (size_t)A.NP;
+    r.out(A.pos_w, M * 3); r.in(A.lm_plane, M); r.in(A.flags, M); r.in(A.equation, NP * 4); r.in(A.active, NP); r.in(A.dist_thresh, 1);
+    r.out(A.out_changed, M, false);
+}
 }  // namespace
 
 plp_status plp_plane_ransac_device(plp_matcher* c, const plp_plane_ransac_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = plane_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PlaneArgs A = plane_args(a);
-    DeviceRooms r;
-    plane_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_plane_ransac((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, plane_args(a), plane_plan<DeviceRooms>, launch_plane_ransac);
 }
 
 plp_status plp_plane_ransac_host(plp_matcher* c, const plp_plane_ransac_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = plane_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, M = (size_t)a->n_cap, I = (size_t)a->iters;
-    PlaneArgs A = plane_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.counts, P); s.in(A.pos_w, P * M * 3); s.in(A.flags, P * M); s.in(A.dist_thresh, P); s.in(A.error_thresh, P); s.in(A.best_error_in, P);
-    s.in(A.equation_in, P * 4); s.in(A.samples, P * I * (size_t)(a->m_cap > 0 ? a->m_cap : 0));
-    s.out(A.out_status, P, false); s.out(A.out_flags, P, false); s.out(A.out_equation, P * 4); s.out(A.out_best_error, P);
-    s.out(A.out_best_iter, P, false); s.out(A.out_last_iter, P, false); s.out(A.out_num_inliers, P, false); s.out(A.out_inliers, P * M);
-    s.out(A.out_hyp_residual, P * I, false); s.out(A.out_hyp_inliers, P * I, false); s.out(A.out_hyp_error, P * I, false);
-    plane_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_plane_ransac(c->stream, A));
-    return s.finish();
+    return host_call(c, plane_args(a), plane_plan<Stage>, launch_plane_ransac);
 }
 
 plp_status plp_plane_refine_points_device(plp_matcher* c, const plp_plane_refine_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = refine_check(a)) return s;
     if (a->M == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_plane_refine_points((hipStream_t)hip_stream, refine_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, refine_args(a), refine_plan<DeviceRooms>, launch_plane_refine_points);
 }
 
 plp_status plp_plane_refine_points_host(plp_matcher* c, const plp_plane_refine_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = refine_check(a)) return s;
     if (a->M == 0) return PLP_OK;
-    const size_t M = (size_t)a->M, NP = (size_t)a->NP;
-    PlaneRefineArgs A = refine_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.out(A.pos_w, M * 3); s.in(A.lm_plane, M); s.in(A.flags, M); s.in(A.equation, NP * 4); s.in(A.active, NP); s.in(A.dist_thresh, 1);
-    s.out(A.out_changed, M, false);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_plane_refine_points(c->stream, A));
-    return s.finish();
+    return host_call(c, refine_args(a), refine_plan<Stage>, launch_plane_refine_points);
 }
 
 // the host builds of plane_fit.hpp (no HIP call)

@@ -78,8 +78,10 @@ struct HostPinned {
     }
 };
 
-// The arrays of one host-pointer entry, staged through a context's slab.  Every array is declared once, by reference to the pointer field
-// of the kernel-argument struct that holds its HOST address, with its element count (bytes = count * sizeof(T)):
+// The arrays of one host-pointer entry, staged through a context's slab.  For the matcher context the declarations are a call's plan
+// (matcher_context.hpp), which host_call() runs with a Stage and device_call() with a DeviceRooms, so that both forms of an entry read one
+// list.  Every array is declared once, by reference to the pointer field of the kernel-argument struct that holds its HOST address, with its
+// element count (bytes = count * sizeof(T)):
 //   in    uploaded;
 //   out   downloaded by finish().  keep: uploaded first, as the caller holds it.  The kernels write only the slots they compute (below a
 //         problem's count, not skipped), and finish() copies the whole block back, so the unwritten slots must hold the caller's values, as
@@ -89,15 +91,15 @@ struct HostPinned {
 // upload() lays the arrays out in the order declared, 256-byte aligned, reserves the slab, rewrites every declared pointer to its device
 // address and issues the host-to-device copies.  A NULL pointer or a count of 0 is not staged: the kernel sees NULL for it.
 // finish() issues the device-to-host copies and waits for the stream.  The slab must not be reserved again in between.
-// Nothing checks that every pointer field of an argument struct was declared: a field left out reaches the kernel as the caller's HOST
-// address.  After upload() a declared pointer is a device address, whatever its name: host code must not dereference it.
+// Nothing checks that every pointer field of an argument struct was declared: a field left out of the plan reaches the kernel as the caller's
+// HOST address.  After upload() a declared pointer is a device address, whatever its name: host code must not dereference it.
 class Stage {
 public:
     Stage(DevBuf& slab, hipStream_t st) : slab_(slab), st_(st) { parts_.reserve(32); }
     template <class T> void in(const T*& p, size_t count) { parts_.push_back({&p, p, nullptr, p ? count * sizeof(T) : 0, 0}); }
     template <class T> void out(T*& p, size_t count, bool keep = true) { parts_.push_back({&p, keep ? p : nullptr, p, p ? count * sizeof(T) : 0, 0}); }
     template <class T> void room(T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }
-    template <class T> void room(DevBuf&, T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }   // a solver's *_rooms() (matcher_context.hpp): the slab serves, not the context's buffer
+    template <class T> void room(DevBuf&, T*& p, size_t count) { parts_.push_back({&p, nullptr, nullptr, count * sizeof(T), 0}); }   // a plan's room (matcher_context.hpp): the slab serves, not the context's buffer
     plp_status upload() {
         size_t tot = 0;
         for (Part& p : parts_) { p.off = tot; tot += (p.bytes + 255) / 256 * 256; }

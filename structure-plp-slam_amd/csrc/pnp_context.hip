@@ -36,9 +36,12 @@ PnpArgs pnp_args(const plp_pnp_ransac_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void pnp_rooms(R& r, plp_matcher* c, PnpArgs& A) {
+// the arrays of the call; the rooms are what the launches hand to one another
+extern "C++" template <class R> void pnp_plan(R& r, plp_matcher* c, PnpArgs& A) {
     const size_t P = (size_t)A.P, M = (size_t)A.n_cap, I = (size_t)A.iters;
+    r.in(A.valid, P * M); r.in(A.bearing, P * M * 3); r.in(A.pos_w, P * M * 3); r.in(A.octave, P * M); r.in(A.counts, P); r.in(A.samples, P * I * 4);
+    r.out(A.out_status, P, false); r.out(A.out_num_matches, P, false); r.out(A.out_rot_cw, P * 9, false); r.out(A.out_trans_cw, P * 3, false);
+    r.out(A.out_num_inliers, P, false); r.out(A.out_best_iter, P, false); r.out(A.out_inliers, P * M); r.out(A.out_hyp_inliers, P * I, false);
     r.room(c->pnp_ctx, A.ctx, P * kPnpCtxInts); r.room(c->pnp_slot, A.ctx_slot, P * M); r.room(c->pnp_hyp, A.ctx_hyp, P * kPnpHypDoubles * I);
     r.room(c->pnp_corr, A.ctx_corr, P * M * kPnpCorrDoubles); r.room(c->pnp_pose, A.ctx_pose, P * 12); r.room(c->pnp_sign, A.ctx_sign, P);
 }
@@ -133,32 +136,14 @@ plp_status plp_pnp_ransac_device(plp_matcher* c, const plp_pnp_ransac_args* a, v
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pnp_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PnpArgs A = pnp_args(a);
-    DeviceRooms r;
-    pnp_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_pnp_ransac((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, pnp_args(a), pnp_plan<DeviceRooms>, launch_pnp_ransac);
 }
 
 plp_status plp_pnp_ransac_host(plp_matcher* c, const plp_pnp_ransac_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pnp_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, M = (size_t)a->n_cap, I = (size_t)a->iters;
-    PnpArgs A = pnp_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.valid, P * M); s.in(A.bearing, P * M * 3); s.in(A.pos_w, P * M * 3); s.in(A.octave, P * M); s.in(A.counts, P); s.in(A.samples, P * I * 4);
-    s.out(A.out_status, P, false); s.out(A.out_num_matches, P, false); s.out(A.out_rot_cw, P * 9, false); s.out(A.out_trans_cw, P * 3, false);
-    s.out(A.out_num_inliers, P, false); s.out(A.out_best_iter, P, false); s.out(A.out_inliers, P * M); s.out(A.out_hyp_inliers, P * I, false);
-    pnp_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_pnp_ransac(c->stream, A));
-    return s.finish();
+    return host_call(c, pnp_args(a), pnp_plan<Stage>, launch_pnp_ransac);
 }
 
 // the host builds of pnp.hpp (no HIP call)

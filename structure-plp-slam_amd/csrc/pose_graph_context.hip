@@ -56,9 +56,18 @@ PgArgs pg_args(const plp_pose_graph_args* a) {
     return A;
 }
 
-// what the steps hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void pg_rooms(R& r, plp_matcher* c, PgArgs& A) {
-    const size_t G = (size_t)A.G;
+// the arrays of the call; the rooms are what the steps hand to one another
+extern "C++" template <class R> void pg_plan(R& r, plp_matcher* c, PgArgs& A) {
+    const size_t G = (size_t)A.G, F = (size_t)A.F;
+    const size_t n_loop = list_end(r, A.kf_loop_offsets, A.F), n_pre = list_end(r, A.pre_offsets, A.G);
+    const size_t n_non = list_end(r, A.non_offsets, A.G), n_lc = list_end(r, A.lc_offsets, A.G);
+    r.in(A.pose, F * A.pose_stride); r.in(A.kf_erased, F); r.in(A.kf_id, F); r.in(A.kf_parent, F); r.in(A.kf_conn, F * A.conn_cap); r.in(A.kf_conn_w, F * A.conn_cap);
+    r.in(A.kf_n_conn, F); r.in(A.kf_covis, F * A.covis_cap); r.in(A.kf_covis_w, F * A.covis_cap); r.in(A.kf_n_covis, F); r.in(A.kf_loop_offsets, F + 1);
+    r.in(A.kf_loop, n_loop); r.in(A.loop_kf, G); r.in(A.curr_kf, G); r.in(A.fix_scale, G); r.in(A.pre_offsets, G + 1); r.in(A.pre_row, n_pre);
+    r.in(A.pre_sim3, n_pre * 8); r.in(A.non_offsets, G + 1); r.in(A.non_row, n_non); r.in(A.non_sim3, n_non * 8); r.in(A.lc_offsets, G + 1); r.in(A.lc_owner, n_lc);
+    r.in(A.lc_target, n_lc);
+    r.out(A.out_status, G); r.out(A.out_num_edges, G); r.out(A.out_edges, G * A.edge_cap * 3); r.out(A.out_sim3_cw, G * F * 8); r.out(A.out_corrected_wc, G * F * 8);
+    r.out(A.out_pose, G * F * 15); r.out(A.out_info, G * 4); r.out(A.out_chi2, G * 2);
     r.room(c->pg_d, A.ctx_d, G * pg_doubles(A.F, A.edge_cap, A.env_cap)); r.room(c->pg_i, A.ctx_i, G * pg_ints(A.F, A.edge_cap, A.env_cap));
 }
 
@@ -90,44 +99,26 @@ PgLmArgs pgl_args(const plp_correct_landmarks_args* a) {
     A.corrected_wc = a->corrected_wc; A.out_pos_w = a->out_pos_w; A.out_status = a->out_status;
     return A;
 }
+
+extern "C++" template <class R> void pgl_plan(R& r, plp_matcher*, PgLmArgs& A) {
+    const size_t L = (size_t)A.L, F = (size_t)A.F;
+    r.in(A.pos_w, L * 3); r.in(A.lm_erased, L); r.in(A.ref_kf, L); r.in(A.kf_erased, F); r.in(A.sim3_cw, F * 8); r.in(A.corrected_wc, F * 8);
+    r.out(A.out_pos_w, L * 3); r.out(A.out_status, L);
+}
 }  // namespace
 
 plp_status plp_pose_graph_optimize_device(plp_matcher* c, const plp_pose_graph_args* a, void* hip_stream) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pg_check(a, false)) return s;
     if (a->G == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PgArgs A = pg_args(a);
-    DeviceRooms r;
-    pg_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_pose_graph((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, pg_args(a), pg_plan<DeviceRooms>, launch_pose_graph);
 }
 
 plp_status plp_pose_graph_optimize_host(plp_matcher* c, const plp_pose_graph_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pg_check(a, true)) return s;
     if (a->G == 0) return PLP_OK;
-    PgArgs A = pg_args(a);
-    const size_t G = (size_t)a->G, F = (size_t)a->F;
-    const size_t n_loop = a->kf_loop_offsets ? a->kf_loop_offsets[a->F] : 0, n_pre = a->pre_offsets ? a->pre_offsets[a->G] : 0;
-    const size_t n_non = a->non_offsets ? a->non_offsets[a->G] : 0, n_lc = a->lc_offsets ? a->lc_offsets[a->G] : 0;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose, F * a->pose_stride); s.in(A.kf_erased, F); s.in(A.kf_id, F); s.in(A.kf_parent, F); s.in(A.kf_conn, F * a->conn_cap); s.in(A.kf_conn_w, F * a->conn_cap);
-    s.in(A.kf_n_conn, F); s.in(A.kf_covis, F * a->covis_cap); s.in(A.kf_covis_w, F * a->covis_cap); s.in(A.kf_n_covis, F); s.in(A.kf_loop_offsets, F + 1);
-    s.in(A.kf_loop, n_loop); s.in(A.loop_kf, G); s.in(A.curr_kf, G); s.in(A.fix_scale, G); s.in(A.pre_offsets, G + 1); s.in(A.pre_row, n_pre);
-    s.in(A.pre_sim3, n_pre * 8); s.in(A.non_offsets, G + 1); s.in(A.non_row, n_non); s.in(A.non_sim3, n_non * 8); s.in(A.lc_offsets, G + 1); s.in(A.lc_owner, n_lc);
-    s.in(A.lc_target, n_lc);
-    s.out(A.out_status, G); s.out(A.out_num_edges, G); s.out(A.out_edges, G * a->edge_cap * 3); s.out(A.out_sim3_cw, G * F * 8); s.out(A.out_corrected_wc, G * F * 8);
-    s.out(A.out_pose, G * F * 15); s.out(A.out_info, G * 4); s.out(A.out_chi2, G * 2);
-    pg_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_pose_graph(c->stream, A));
-    return s.finish();
+    return host_call(c, pg_args(a), pg_plan<Stage>, launch_pose_graph);
 }
 
 // the host builds of pose_graph.hpp (no HIP call)
@@ -200,26 +191,14 @@ plp_status plp_correct_landmarks_device(plp_matcher* c, const plp_correct_landma
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pgl_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PLP_HIP(launch_correct_landmarks((hipStream_t)hip_stream, pgl_args(a)));
-    return PLP_OK;
+    return device_call(c, hip_stream, pgl_args(a), pgl_plan<DeviceRooms>, launch_correct_landmarks);
 }
 
 plp_status plp_correct_landmarks_host(plp_matcher* c, const plp_correct_landmarks_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pgl_check(a)) return s;
     if (a->L == 0) return PLP_OK;
-    PgLmArgs A = pgl_args(a);
-    const size_t L = (size_t)a->L, F = (size_t)a->F;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pos_w, L * 3); s.in(A.lm_erased, L); s.in(A.ref_kf, L); s.in(A.kf_erased, F); s.in(A.sim3_cw, F * 8); s.in(A.corrected_wc, F * 8);
-    s.out(A.out_pos_w, L * 3); s.out(A.out_status, L);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_correct_landmarks(c->stream, A));
-    return s.finish();
+    return host_call(c, pgl_args(a), pgl_plan<Stage>, launch_correct_landmarks);
 }
 
 int32_t plp_model_correct_landmarks_host(const plp_correct_landmarks_args* a) {

@@ -53,9 +53,14 @@ PoseArgs pose_args(const plp_pose_optimize_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void pose_rooms(R& r, plp_matcher* c, PoseArgs& A) {
-    const size_t B = (size_t)A.B, N = (size_t)A.n_cap, L = (size_t)A.l_cap;
+// the arrays of the call; the rooms are what the launches hand to one another
+extern "C++" template <class R> void pose_plan(R& r, plp_matcher* c, PoseArgs& A) {
+    const size_t B = (size_t)A.B, N = (size_t)A.n_cap, L = (size_t)A.l_cap, T = (size_t)A.num_trials;
+    r.in(A.pose_in, (B - 1) * A.pose_stride + 12); r.in(A.counts, B); r.in(A.line_counts, B);
+    r.in(A.valid, B * N); r.in(A.undist, B * N); r.in(A.x_right, B * N); r.in(A.pos_w, B * N * 3);
+    r.in(A.line_valid, B * L); r.in(A.keylines, B * L); r.in(A.pos_w_lines, B * L * 6);
+    r.out(A.out_status, B, false); r.out(A.out_pose, B * 15, false); r.out(A.out_num_init_obs, B, false); r.out(A.out_num_valid, B, false);
+    r.out(A.out_outlier, B * N); r.out(A.out_outlier_lines, B * L); r.out(A.out_trial_info, B * T * 4, false); r.out(A.out_trial_chi2, B * T * 2, false);
     r.room(c->pose_slot, A.ctx_slot, B * N + 1); r.room(c->pose_slot_lines, A.ctx_slot_lines, B * L + 1);
     r.room(c->pose_chi2, A.ctx_chi2, B * (N + L) + 1); r.room(c->pose_n, A.ctx_n, B * 2);
 }
@@ -215,34 +220,14 @@ plp_status plp_pose_optimize_device(plp_matcher* c, const plp_pose_optimize_args
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pose_check(a)) return s;
     if (a->B == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    PoseArgs A = pose_args(a);
-    DeviceRooms r;
-    pose_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_pose_optimize((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, pose_args(a), pose_plan<DeviceRooms>, launch_pose_optimize);
 }
 
 plp_status plp_pose_optimize_host(plp_matcher* c, const plp_pose_optimize_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = pose_check(a)) return s;
     if (a->B == 0) return PLP_OK;
-    const size_t B = (size_t)a->B, N = (size_t)a->n_cap, L = (size_t)a->l_cap, T = (size_t)a->num_trials;
-    PoseArgs A = pose_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.pose_in, (B - 1) * a->pose_stride + 12); s.in(A.counts, B); s.in(A.line_counts, B);
-    s.in(A.valid, B * N); s.in(A.undist, B * N); s.in(A.x_right, B * N); s.in(A.pos_w, B * N * 3);
-    s.in(A.line_valid, B * L); s.in(A.keylines, B * L); s.in(A.pos_w_lines, B * L * 6);
-    s.out(A.out_status, B, false); s.out(A.out_pose, B * 15, false); s.out(A.out_num_init_obs, B, false); s.out(A.out_num_valid, B, false);
-    s.out(A.out_outlier, B * N); s.out(A.out_outlier_lines, B * L); s.out(A.out_trial_info, B * T * 4, false); s.out(A.out_trial_chi2, B * T * 2, false);
-    pose_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_pose_optimize(c->stream, A));
-    return s.finish();
+    return host_call(c, pose_args(a), pose_plan<Stage>, launch_pose_optimize);
 }
 
 // the host builds of pose_opt.hpp (no HIP call)

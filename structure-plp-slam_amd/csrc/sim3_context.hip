@@ -43,9 +43,14 @@ Sim3Args sim3_args(const plp_sim3_ransac_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void sim3_rooms(R& r, plp_matcher* c, Sim3Args& A) {
-    const size_t P = (size_t)A.P, I = (size_t)A.iters;
+// the arrays of the call; the rooms are what the launches hand to one another
+extern "C++" template <class R> void sim3_plan(R& r, plp_matcher* c, Sim3Args& A) {
+    const size_t P = (size_t)A.P, M = (size_t)A.n_cap, I = (size_t)A.iters;
+    r.in(A.valid, P * M); r.in(A.pos_w_1, P * M * 3); r.in(A.pos_w_2, P * M * 3); r.in(A.octave_1, P * M); r.in(A.octave_2, P * M); r.in(A.counts, P);
+    r.in(A.pose_1, P * 15); r.in(A.pose_2, P * 15); r.in(A.samples, P * I * 3);
+    r.out(A.out_status, P, false); r.out(A.out_num_common, P, false); r.out(A.out_rot_12, P * 9, false); r.out(A.out_trans_12, P * 3, false);
+    r.out(A.out_scale_12, P, false); r.out(A.out_num_inliers, P, false); r.out(A.out_best_iter, P, false); r.out(A.out_inliers, P * M);
+    r.out(A.out_hyp_inliers, P * I, false);
     r.room(c->sim3_ctx, A.ctx, P * kSim3CtxInts); r.room(c->sim3_hyp, A.ctx_hyp, P * kSim3HypDoubles * I);
 }
 
@@ -107,34 +112,14 @@ plp_status plp_sim3_ransac_device(plp_matcher* c, const plp_sim3_ransac_args* a,
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = sim3_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Sim3Args A = sim3_args(a);
-    DeviceRooms r;
-    sim3_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_sim3_ransac((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, sim3_args(a), sim3_plan<DeviceRooms>, launch_sim3_ransac);
 }
 
 plp_status plp_sim3_ransac_host(plp_matcher* c, const plp_sim3_ransac_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = sim3_check(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, M = (size_t)a->n_cap, I = (size_t)a->iters;
-    Sim3Args A = sim3_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.valid, P * M); s.in(A.pos_w_1, P * M * 3); s.in(A.pos_w_2, P * M * 3); s.in(A.octave_1, P * M); s.in(A.octave_2, P * M); s.in(A.counts, P);
-    s.in(A.pose_1, P * 15); s.in(A.pose_2, P * 15); s.in(A.samples, P * I * 3);
-    s.out(A.out_status, P, false); s.out(A.out_num_common, P, false); s.out(A.out_rot_12, P * 9, false); s.out(A.out_trans_12, P * 3, false);
-    s.out(A.out_scale_12, P, false); s.out(A.out_num_inliers, P, false); s.out(A.out_best_iter, P, false); s.out(A.out_inliers, P * M);
-    s.out(A.out_hyp_inliers, P * I, false);
-    sim3_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_sim3_ransac(c->stream, A));
-    return s.finish();
+    return host_call(c, sim3_args(a), sim3_plan<Stage>, launch_sim3_ransac);
 }
 
 // the host builds of sim3.hpp (no HIP call)

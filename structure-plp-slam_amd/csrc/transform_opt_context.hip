@@ -55,9 +55,14 @@ TfArgs tf_args(const plp_transform_optimize_args* a) {
     return A;
 }
 
-// what the launches hand to one another: the context's buffers (device entry) or rooms of the slab (host-pointer entry), elements
-extern "C++" template <class R> void tf_rooms(R& r, plp_matcher* c, TfArgs& A) {
+// the arrays of the call; the rooms are what the launches hand to one another
+extern "C++" template <class R> void tf_plan(R& r, plp_matcher* c, TfArgs& A) {
     const size_t P = (size_t)A.P, N = (size_t)A.n_cap;
+    r.in(A.counts, P); r.in(A.valid, P * N); r.in(A.pos_w_1, P * N * 3); r.in(A.pos_w_2, P * N * 3); r.in(A.undist_1, P * N); r.in(A.undist_2, P * N);
+    r.in(A.pose_1, P * 15); r.in(A.pose_2, P * 15); r.in(A.rot_12, P * 9); r.in(A.trans_12, P * 3); r.in(A.scale_12, P);
+    r.out(A.out_status, P, false); r.out(A.out_num_valid, P, false); r.out(A.out_num_inliers, P, false); r.out(A.out_rot_12, P * 9, false);
+    r.out(A.out_trans_12, P * 3, false); r.out(A.out_scale_12, P, false); r.out(A.out_world_to_1, P * 13, false); r.out(A.out_kept, P * N);
+    r.out(A.out_round_info, P * 8, false); r.out(A.out_round_chi2, P * 4, false);
     r.room(c->tf_slot, A.ctx_slot, P * N + 1); r.room(c->tf_chi2, A.ctx_chi2, 2 * P * N + kTfCtxDoubles * P); r.room(c->tf_n, A.ctx_n, kTfCtxInts * P);
     r.room(c->tf_level, A.ctx_level, P * N + 1); r.room(c->tf_edge, A.ctx_edge, 12 * P * N + 1);
 }
@@ -171,34 +176,14 @@ plp_status plp_transform_optimize_device(plp_matcher* c, const plp_transform_opt
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = tf_check(a)) return s;
     if (a->P == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    TfArgs A = tf_args(a);
-    DeviceRooms r;
-    tf_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_transform_optimize((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, tf_args(a), tf_plan<DeviceRooms>, launch_transform_optimize);
 }
 
 plp_status plp_transform_optimize_host(plp_matcher* c, const plp_transform_optimize_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = tf_check(a)) return s;
     if (a->P == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, N = (size_t)a->n_cap;
-    TfArgs A = tf_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.counts, P); s.in(A.valid, P * N); s.in(A.pos_w_1, P * N * 3); s.in(A.pos_w_2, P * N * 3); s.in(A.undist_1, P * N); s.in(A.undist_2, P * N);
-    s.in(A.pose_1, P * 15); s.in(A.pose_2, P * 15); s.in(A.rot_12, P * 9); s.in(A.trans_12, P * 3); s.in(A.scale_12, P);
-    s.out(A.out_status, P, false); s.out(A.out_num_valid, P, false); s.out(A.out_num_inliers, P, false); s.out(A.out_rot_12, P * 9, false);
-    s.out(A.out_trans_12, P * 3, false); s.out(A.out_scale_12, P, false); s.out(A.out_world_to_1, P * 13, false); s.out(A.out_kept, P * N);
-    s.out(A.out_round_info, P * 8, false); s.out(A.out_round_chi2, P * 4, false);
-    tf_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_transform_optimize(c->stream, A));
-    return s.finish();
+    return host_call(c, tf_args(a), tf_plan<Stage>, launch_transform_optimize);
 }
 
 // the host builds of transform_opt.hpp (no HIP call)

@@ -43,8 +43,14 @@ TvArgs tv_args(const plp_two_view_pose_args* a) {
     return A;
 }
 
-extern "C++" template <class R> void tv_rooms(R& r, plp_matcher* c, TvArgs& A) {
-    const size_t P = (size_t)A.P, M = (size_t)A.n_cap;
+// the arrays of the call; the rooms are the points and flags of the four hypotheses
+extern "C++" template <class R> void tv_plan(R& r, plp_matcher* c, TvArgs& A) {
+    const size_t P = (size_t)A.P, M = (size_t)A.n_cap, M2 = (size_t)A.m_cap;
+    r.in(A.E_21, P * 9); r.in(A.inliers, P * M); r.in(A.match, P * M); r.in(A.counts_1, P); r.in(A.counts_2, P); r.in(A.bearing_1, P * M * 3);
+    r.in(A.bearing_2, P * M2 * 3); r.in(A.undist_1, P * M); r.in(A.undist_2, P * M2); r.in(A.in_status, P);
+    r.out(A.out_status, P, false); r.out(A.out_rot, P * 9, false); r.out(A.out_trans, P * 3, false); r.out(A.out_hypothesis, P, false);
+    r.out(A.out_num_valid, P * 4, false); r.out(A.out_parallax_deg, P * 4, false); r.out(A.out_pts, P * M * 3); r.out(A.out_is_triangulated, P * M);
+    r.out(A.out_hyp_is_triangulated, P * 4 * M);
     r.room(c->tv_pts, A.ctx_pts, P * 4 * M * 3); r.room(c->tv_flag, A.ctx_flag, P * 4 * M);
 }
 
@@ -126,34 +132,14 @@ plp_status plp_two_view_pose_device(plp_matcher* c, const plp_two_view_pose_args
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = tv_check_args(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    TvArgs A = tv_args(a);
-    DeviceRooms r;
-    tv_rooms(r, c, A);
-    PLP_HIP(r.err);
-    PLP_HIP(launch_two_view_pose((hipStream_t)hip_stream, A));
-    return PLP_OK;
+    return device_call(c, hip_stream, tv_args(a), tv_plan<DeviceRooms>, launch_two_view_pose);
 }
 
 plp_status plp_two_view_pose_host(plp_matcher* c, const plp_two_view_pose_args* a) {
     if (!c) return set_error(PLP_ERR_INVALID_ARG, "ctx is NULL");
     if (plp_status s = tv_check_args(a)) return s;
     if (a->P == 0 || a->n_cap == 0) return PLP_OK;
-    const size_t P = (size_t)a->P, M = (size_t)a->n_cap, M2 = (size_t)a->m_cap;
-    TvArgs A = tv_args(a);
-    std::lock_guard<std::mutex> lk(c->mu);
-    PLP_HIP(hipSetDevice(c->device));
-    Stage s(c->stage, c->stream);
-    s.in(A.E_21, P * 9); s.in(A.inliers, P * M); s.in(A.match, P * M); s.in(A.counts_1, P); s.in(A.counts_2, P); s.in(A.bearing_1, P * M * 3);
-    s.in(A.bearing_2, P * M2 * 3); s.in(A.undist_1, P * M); s.in(A.undist_2, P * M2); s.in(A.in_status, P);
-    s.out(A.out_status, P, false); s.out(A.out_rot, P * 9, false); s.out(A.out_trans, P * 3, false); s.out(A.out_hypothesis, P, false);
-    s.out(A.out_num_valid, P * 4, false); s.out(A.out_parallax_deg, P * 4, false); s.out(A.out_pts, P * M * 3); s.out(A.out_is_triangulated, P * M);
-    s.out(A.out_hyp_is_triangulated, P * 4 * M);
-    tv_rooms(s, c, A);
-    PLP_TRY(s.upload());
-    PLP_HIP(launch_two_view_pose(c->stream, A));
-    return s.finish();
+    return host_call(c, tv_args(a), tv_plan<Stage>, launch_two_view_pose);
 }
 
 // the host builds of two_view.hpp (no HIP call)
