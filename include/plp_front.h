@@ -444,7 +444,8 @@ plp_status plp_pack_rows_device(const void* src, const int32_t* counts, int32_t 
 /* area::match_in_consistent_area(frm_1, frm_2, prev_matched_pts, matched_indices_2_in_frm_1, margin)
  * (src/PLPSLAM/match/area.cc:33-153; monocular initialisation, module/initializer.cc:191-192).  Host pointers, one
  * problem, synchronous.  kps_1/kps_2 = undist_keypts_ of the two frames, prev_matched_pts = n1 x 2 floats (updated in
- * place for matched key points), matched_2_in_1 = n1 int32 (idx_2 or -1); *num_matches = return value. */
+ * place for matched key points), matched_2_in_1 = n1 int32 (idx_2 or -1); *num_matches = return value.
+ * PLP_ERR_INVALID_ARG, with no output written, for n2 > 65535, a grid of more than 65536 cells or a non-positive grid extent. */
 plp_status plp_match_area_host(plp_matcher* ctx, const plp_keypoint* kps_1, const uint8_t* desc_1, int32_t n1, const plp_keypoint* kps_2,
                                const uint8_t* desc_2, int32_t n2, const plp_match_grid* grid, float* prev_matched_pts, int32_t margin,
                                float lowe_ratio, int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches);

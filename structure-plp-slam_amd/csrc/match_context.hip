@@ -250,9 +250,10 @@ plp_status plp_match_area_host(plp_matcher* c, const plp_keypoint* kps_1, const 
                                const uint8_t* desc_2, int32_t n2, const plp_match_grid* grid, float* prev_matched_pts, int32_t margin,
                                float lowe_ratio, int32_t check_orientation, int32_t* matched_2_in_1, int32_t* num_matches) {
     if (!c || !grid || !matched_2_in_1 || !num_matches) return set_error(PLP_ERR_INVALID_ARG, "NULL argument");
-    *num_matches = 0;
-    if (n1 <= 0) return PLP_OK;
+    if (n1 <= 0) { *num_matches = 0; return PLP_OK; }
+    // refusals come before anything is written: the tie-break key holds the cell index (at most 65535) and idx_2 in 16 bits each
     if (!kps_1 || !desc_1 || !prev_matched_pts || n2 < 0 || (n2 > 0 && (!kps_2 || !desc_2)) || n2 > 65535) return set_error(PLP_ERR_INVALID_ARG, "bad argument");
+    if (grid->cols <= 0 || grid->rows <= 0 || (int64_t)grid->cols * grid->rows > 65536) return set_error(PLP_ERR_INVALID_ARG, "grid must have a positive extent and at most 65536 cells");
     AreaArgs A{};
     A.kps1 = kps_1; A.desc1 = desc_1; A.kps2 = kps_2; A.desc2 = desc_2; A.n1 = n1; A.n2 = n2;
     A.grid_min_x = grid->min_x; A.grid_min_y = grid->min_y; A.inv_cell_w = grid->inv_cell_width; A.inv_cell_h = grid->inv_cell_height;

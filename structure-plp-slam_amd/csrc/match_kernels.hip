@@ -1164,7 +1164,7 @@ __global__ __launch_bounds__(64) void k_match_area(AreaArgs A) {
             const int cx = floor_d((double)__fsub_rn(k.x, A.grid_min_x) * A.inv_cell_w), cy = floor_d((double)__fsub_rn(k.y, A.grid_min_y) * A.inv_cell_h);
             if (cx < 0 || cx >= A.grid_cols || cy < 0 || cy >= A.grid_rows) continue;
             if (cx < min_cx || cx > max_cx || cy < min_cy || cy > max_cy) continue;
-            if (k.octave < 0 || 0 < k.octave) continue;                      // min_level = max_level = 0
+            if (0 <= k1.octave && k.octave != 0) continue;                   // min_level = max_level = octave of idx_1: 0 -> level 0 only, below 0 -> no level check (common.cc:268)
             if (!(fabsf(__fsub_rn(k.x, rx)) < mg && fabsf(__fsub_rn(k.y, ry)) < mg)) continue;
             const uint4* d = reinterpret_cast<const uint4*>(A.desc2 + 32 * (size_t)t);
             const unsigned dist = hamming256(q0, q1, d[0], d[1]);
