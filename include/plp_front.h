@@ -1228,6 +1228,110 @@ plp_status plp_plane_refine_points_device(plp_matcher* ctx, const plp_plane_refi
 plp_status plp_plane_refine_points_host(plp_matcher* ctx, const plp_plane_refine_args* args);
 int32_t plp_model_plane_refine_points_host(const plp_plane_refine_args* args);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Plane refinement: Planar_Mapping_module::refinement() (planar_mapping_module.cc:773-793) -- merge_planes (:795-898), refine_planes
+ * (:900-952), refine_points (:954-1004) -- for G independent map snapshots over plane and landmark tables that are updated IN PLACE.
+ * Numeric contract: DESIGN.md section 5, D26; reformulation: DESIGN.md section 4.  The reference's text is followed literally, quirks
+ * included; defined here is only what it leaves to the order of an unordered_map or to std::random_device.
+ *
+ * Problem g is one map; every array is problem-major.
+ * Planes, NP_cap rows per problem; a row is a data::Plane that is or was in _landmarks_plane:
+ *   pl_state      PLP_PLANE_ROW_IN_DB | PLP_PLANE_ROW_VALID (is_valid()) | PLP_PLANE_ROW_NEED_REFINEMENT (need_refinement()).
+ *                 get_all_landmark_planes() is BY DEFINITION the rows with IN_DB in ascending row; the loops of merge_planes index that
+ *                 compacted vector
+ *   pl_equation / pl_best_error   get_equation() / get_best_error(); _abs_n is sqrt((a a + b b) + c c) as set_equation stores it
+ *   pl_count / pl_lm              Plane::_landmarks as landmark rows: get_landmarks() is slots 0 .. pl_count - 1 in slot order (D19 item 1);
+ *                 a count is clamped to [0, n_cap]; a slot at or above the count is no entry: it holds the caller's value, or -- below the
+ *                 largest count the row had during the call -- an entry the list held then.  A list names a landmark at most
+ *                 once (it is a map keyed by id_); an entry outside [0, L) counts as will_be_erased() without an owner and is never written to
+ * Landmarks, L rows per problem: pos_w (written by refine_points only), lm_erased (will_be_erased()), lm_owner (the row of
+ * get_Owning_Plane(), -1 = none).  Membership (pl_lm) and ownership (lm_owner) are two relations, as in the reference: Plane::merge
+ * (data/landmark_plane.cc:221-248) leaves other->_landmarks as it was, remove_landmarks_ownership() (:197-207) clears the owner of every
+ * MEMBER whoever owns it, so a landmark can stand in two lists and an erased plane can still be named as owner.
+ *
+ * stages: PLP_PLANE_STAGE_MERGE | PLP_PLANE_STAGE_REFINE_PLANES | PLP_PLANE_STAGE_REFINE_POINTS; 7 is refinement() with its gate (:777:
+ * fewer than two IN_DB rows: PLP_PLANE_REFINEMENT_TOO_FEW_PLANES, no table touched); a single bit is that function alone with its own
+ * early returns (:799-808).
+ * merge_planes: the double loop as written -- the candidate skip steps over ONE invalid j and tests the next j whatever its validity,
+ * breaking when it runs off the end (:828-835); the parent's validity is tested once per i (:820), so a parent the else arm invalidates
+ * (:873-881) goes on; the two-sided test, mixed outcomes neither continue nor merge (:853-860); `>` between the sizes (:864); Plane::merge
+ * appends other's non-erased entries that the parent does not hold in other's slot order and owns every non-erased entry of other;
+ * update_plane_via_RANSAC on the grown plane at once, set_need_refinement() whatever it returned (:870-871, :879-880); the rows on
+ * planes_will_be_removed lose IN_DB after the loop (:889-895) and nothing else.  offset_delta = d_i * (1 / abs_i) - d_j * (1 / abs_j),
+ * dot = ((n_i0 n_j0 + n_i1 n_j1) + n_i2 n_j2) * ((1 / abs_i) * (1 / abs_j)), OFFSET_DELTA_THRESHOLD = (double)offset_delta_factor *
+ * dist_thresh[g] (:813), IEEE operations in that order.
+ * update_plane_via_RANSAC (:593-733) is PLP_PLANE_UPDATE above, unchanged, on the row's current list: the flag byte of a slot is ERASED
+ * from lm_erased and OWNED from lm_owner >= 0 at the time of the call; equation and best error as out_equation / out_best_error there;
+ * PLP_PLANE_FLAG_INVALID clears VALID, PLP_PLANE_FLAG_NEED_REFINEMENT sets NEED_REFINEMENT; on PLP_PLANE_OK (:728-730) every old member's
+ * owner becomes -1, the list becomes step [4]'s members in slot order and their owner the row.  The c-th update call of problem g (counted
+ * from 0 in the reference's order, through the merge and then refine_planes) draws ransac_draw_one(seed + g, c, iter, k, n_eligible): it is
+ * plp_model_plane_ransac_host with seed + g and samples drawn for problem c (plp_model_plane_draw_host(seed + g, c, ...)).
+ * refine_planes over the IN_DB rows after the merge's removals, ascending: an invalid row goes to the erase list (:907-911); a row that
+ * needs refinement is updated and on true loses NEED_REFINEMENT (:913-922); else a row of fewer than 2 * points_per_ransac members goes
+ * to the erase list (:926-929); after the loop every member of a listed row loses its owner and the row IN_DB (:934-941).
+ * refine_points over the IN_DB rows, ascending: rows that are invalid, need refinement or hold fewer than points_per_ransac members are
+ * skipped (:960-965); every member that is not erased and has an owner -- any owner -- (:970) is moved as plp_plane_refine_points_* moves
+ * it, with THIS row's equation.  A landmark in two active lists is moved twice, the second time from the first result.
+ * Outputs per problem:
+ *   out_status        a plp_plane_refinement_status.  OVERFLOW: a merge would take a list above n_cap; the problem stops there, its tables
+ *                     are undefined, the caller restores its copy and grows n_cap (the convention of plp_covisibility_update_*)
+ *   out_was_merged / out_planes_changed / out_points_changed   the return values of the three functions
+ *   out_removed       [G][NP_cap]: bit 0 erased at :893, bit 1 erased at :939
+ *   out_num_merges / out_merges [G][merge_cap][2]   (parent row, other row) in order; merges beyond merge_cap are counted, not listed, and
+ *                     pairs at or above the number of merges keep the caller's values
+ *   out_num_updates / out_update_status [G][NP_cap]   the calls of update_plane_via_RANSAC; the plp_plane_status of the row's last one in
+ *                     this call, 255 = none
+ *   out_lm_changed    [G][L]: 1 where refine_points wrote pos_w */
+typedef enum plp_plane_refinement_status {
+    PLP_PLANE_REFINEMENT_OK = 0,
+    PLP_PLANE_REFINEMENT_TOO_FEW_PLANES = 1,   /* :777 */
+    PLP_PLANE_REFINEMENT_OVERFLOW = 2          /* Plane::merge (landmark_plane.cc:235-242) past n_cap */
+} plp_plane_refinement_status;
+enum { PLP_PLANE_ROW_IN_DB = 1, PLP_PLANE_ROW_VALID = 2, PLP_PLANE_ROW_NEED_REFINEMENT = 4 };
+enum { PLP_PLANE_STAGE_MERGE = 1, PLP_PLANE_STAGE_REFINE_PLANES = 2, PLP_PLANE_STAGE_REFINE_POINTS = 4 };
+typedef struct plp_plane_refinement_args {
+    int32_t G, NP_cap, n_cap, L;       /* G <= 65535 maps of NP_cap <= 4096 plane rows of n_cap <= 8192 slots and L landmarks */
+    int32_t merge_cap;                 /* pairs per problem in out_merges, >= 0 */
+    int32_t stages;                    /* PLP_PLANE_STAGE_*; 7: refinement() (:773-793) */
+    int32_t points_per_ransac;         /* POINTS_PER_RANSAC, >= 1 (:602, :926, :962) */
+    int32_t iters;                     /* _iterationsCount, 1 .. 1024 (:616) */
+    int32_t offset_delta_factor;       /* _offset_delta_factor, an int in load_configuration (:813) */
+    double dot_product_threshold;      /* DOT_PRODUCT_THRESHOLD (:854, :860) */
+    uint64_t seed;                     /* problem g draws from seed + g */
+    uint8_t* pl_state;                 /* G x NP_cap: PLP_PLANE_ROW_*, in/out (:820, :828, :889-895, :907-941) */
+    double* pl_equation;               /* G x NP_cap x 4, in/out (:838-847, :649, :682) */
+    double* pl_best_error;             /* G x NP_cap, in/out (:609, :650, :683) */
+    int32_t* pl_count;                 /* G x NP_cap, in/out: get_num_landmarks() (:864, :926, :962) */
+    int32_t* pl_lm;                    /* G x NP_cap x n_cap, in/out: get_landmarks() (:595, :967) */
+    double* pos_w;                     /* G x L x 3, in/out (:975, :988) */
+    const uint8_t* lm_erased;          /* G x L: will_be_erased() (:628, :656, :970) */
+    int32_t* lm_owner;                 /* G x L, in/out: get_Owning_Plane() as a row, -1 = nullptr (:623, :970) */
+    const double* dist_thresh;         /* G: _planar_distance_thresh (:663, :813, :985) */
+    const double* error_thresh;        /* G: _final_error_thresh (:698) */
+    uint8_t* out_status;               /* G */
+    uint8_t* out_was_merged;           /* G (:897) */
+    uint8_t* out_planes_changed;       /* G (:951) */
+    uint8_t* out_points_changed;       /* G (:1003) */
+    uint8_t* out_removed;              /* G x NP_cap (:893, :939) */
+    int32_t* out_num_merges;           /* G */
+    int32_t* out_merges;               /* G x merge_cap x 2 (:866-867, :875-876), or NULL when merge_cap == 0 */
+    int32_t* out_num_updates;          /* G */
+    uint8_t* out_update_status;        /* G x NP_cap (:870, :879, :917) */
+    uint8_t* out_lm_changed;           /* G x L (:988) */
+} plp_plane_refinement_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; G, NP_cap, n_cap, L or merge_cap < 0; points_per_ransac < 1;
+ * iters < 1; stages outside 1 .. 7; and -- when G > 0 -- a NULL dist_thresh, error_thresh or G-sized output, (NP_cap > 0) a NULL plane table,
+ * out_removed or out_update_status, (NP_cap > 0 and n_cap > 0) a NULL pl_lm, (L > 0) a NULL landmark table or out_lm_changed, (merge_cap > 0)
+ * a NULL out_merges.  n_cap > 8192, iters > 1024, NP_cap > 4096 or G > 65535: PLP_ERR_UNSUPPORTED.  G == 0: PLP_OK, nothing written.
+ * _device: every array a DEVICE pointer; one kernel on hip_stream, one workgroup per problem, no host synchronisation.  The kernel keeps the
+ * hypotheses of an update and the marks of a merge in buffers the context owns, so the calls of one context must be ordered on the device:
+ * one stream, or events between streams.  _host: HOST pointers, staged (tables and outputs, so that every slot the kernel does not write
+ * keeps the caller's value), the same kernel, synchronous.  plp_model_plane_refinement_host: the host build of csrc/plane_refinement.hpp,
+ * HOST pointers, no GPU and no context; returns G, or -1 for a refused argument (plp_last_error() names it). */
+plp_status plp_plane_refinement_device(plp_matcher* ctx, const plp_plane_refinement_args* args, void* hip_stream);
+plp_status plp_plane_refinement_host(plp_matcher* ctx, const plp_plane_refinement_args* args);
+int32_t plp_model_plane_refinement_host(const plp_plane_refinement_args* args);
+
 /* Bag-of-words transform: data::frame::compute_bow / data::keyframe::compute_bow
  * (src/PLPSLAM/data/frame.cc:785-795) = bow_vocab_->transform(to_desc_vec(descriptors_), bow_vec_, bow_feat_vec_, 4) of
  * DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB> (data/bow_vocabulary.h:22; the USE_DBOW2 build).  DBoW2 and the

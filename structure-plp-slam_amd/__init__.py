@@ -345,12 +345,65 @@ def model_plane_refine_points(pos_w, lm_plane, flags, equation, active, dist_thr
     return _plane_refine_host(model_call("plp_model_plane_refine_points_host", "M"), pos_w, lm_plane, flags, equation, active, dist_thresh)
 
 
+# the tables of plp_plane_refinement_*: name -> (shape per problem given (NP_cap, n_cap, L), dtype); all but lm_erased are updated in place
+PLANE_REFINEMENT_TABLES = dict(pl_state=(lambda NP, M, L: (NP,), np.uint8), pl_equation=(lambda NP, M, L: (NP, 4), np.float64),
+                               pl_best_error=(lambda NP, M, L: (NP,), np.float64), pl_count=(lambda NP, M, L: (NP,), np.int32),
+                               pl_lm=(lambda NP, M, L: (NP, M), np.int32), pos_w=(lambda NP, M, L: (L, 3), np.float64),
+                               lm_erased=(lambda NP, M, L: (L,), np.uint8), lm_owner=(lambda NP, M, L: (L,), np.int32))
+# the outputs of plp_plane_refinement_*: name -> (shape per problem given (NP_cap, L, merge_cap), dtype)
+PLANE_REFINEMENT_OUTPUTS = dict(status=(lambda NP, L, MC: (), np.uint8), was_merged=(lambda NP, L, MC: (), np.uint8),
+                                planes_changed=(lambda NP, L, MC: (), np.uint8), points_changed=(lambda NP, L, MC: (), np.uint8),
+                                removed=(lambda NP, L, MC: (NP,), np.uint8), num_merges=(lambda NP, L, MC: (), np.int32),
+                                merges=(lambda NP, L, MC: (MC, 2), np.int32), num_updates=(lambda NP, L, MC: (), np.int32),
+                                update_status=(lambda NP, L, MC: (NP,), np.uint8), lm_changed=(lambda NP, L, MC: (L,), np.uint8))
+
+
+def _plane_refinement_host(call, tables, dist_thresh, error_thresh, points_per_ransac, iters, dot_product_threshold, offset_delta_factor, seed, stages,
+                           merge_cap, out):
+    """the numpy side of plp_plane_refinement_host and plp_model_plane_refinement_host: call(args struct) runs the entry.  tables: a dict of the
+    arrays of PLANE_REFINEMENT_TABLES with a leading problem axis; an array of the right type is updated in place, anything else is replaced in
+    the dict by the array that was."""
+    st = np.asarray(tables["pl_state"])
+    lm = np.asarray(tables["pl_lm"])
+    if st.ndim != 2 or lm.ndim != 3 or lm.shape[:2] != st.shape:
+        raise PlpError(PLP_ERR_INVALID_ARG, "pl_state must be (G, NP_cap) and pl_lm (G, NP_cap, n_cap)")
+    G, NP = st.shape
+    M = lm.shape[2]
+    L = int(np.asarray(tables["lm_owner"]).reshape(G, -1).shape[1]) if G else 0
+    t = {}
+    for k, (shape, dt) in PLANE_REFINEMENT_TABLES.items():
+        v = tables[k]
+        if not (isinstance(v, np.ndarray) and v.dtype == dt and v.shape == (G,) + shape(NP, M, L) and v.flags.c_contiguous and v.flags.writeable):
+            v = np.array(v, dt, order="C").reshape((G,) + shape(NP, M, L))
+        t[k] = v
+    vec = lambda v: np.ascontiguousarray(np.broadcast_to(np.asarray(v, np.float64), (G,)))
+    dt_, et_ = vec(dist_thresh), vec(error_thresh)
+    MC = int(merge_cap)
+    o = out_arrays(((k, (G,) + shape(NP, L, MC), dt) for k, (shape, dt) in PLANE_REFINEMENT_OUTPUTS.items()), out)
+    a = _struct(plane_refinement_args_c, dict(G=G, NP_cap=NP, n_cap=M, L=L, merge_cap=MC, stages=int(stages), points_per_ransac=int(points_per_ransac),
+                                              iters=int(iters), offset_delta_factor=int(offset_delta_factor), dot_product_threshold=float(dot_product_threshold),
+                                              seed=int(seed) & 0xFFFFFFFFFFFFFFFF), host_ptrs(dist_thresh=dt_, error_thresh=et_, **t))
+    set_outputs(a, PLANE_REFINEMENT_OUTPUTS, o, host_ptr)
+    call(a)
+    tables.update(t)
+    return o
+
+
+def model_plane_refinement(tables, dist_thresh, error_thresh, points_per_ransac=18, iters=50, dot_product_threshold=0.8, offset_delta_factor=6, seed=0,
+                           stages=PLANE_STAGE_ALL, merge_cap=16, out=None):
+    """Host build of Planar_Mapping_module::refinement() (csrc/plane_refinement.hpp, DESIGN.md section 5, D26; no GPU needed): the arguments and the
+    result of matcher.plane_refinement."""
+    return _plane_refinement_host(model_call("plp_model_plane_refinement_host", "G"), tables, dist_thresh, error_thresh, points_per_ransac, iters,
+                                  dot_product_threshold, offset_delta_factor, seed, stages, merge_cap, out)
+
+
 class planar_mapper:
     """Mirror of Planar_Mapping_module's plane fitting (planar_mapping_module.h) under the yaml's names: cfg maps "Threshold.iterationsCount",
     "Threshold.inliers_ratio_thr", "Threshold.min_number_points_before_ransac", "Threshold.point_per_ransac", "Threshold.plane_distance_correction"
     and "Threshold.final_error_correction" (load_configuration, :1162-1184; "Threshold.use_graph_cut" must be absent or false: that estimator
     needs a third-party library and is not offered).  mt: a matcher (the GPU entry), or None = the host build.  A plane is its landmark list:
-    pos_w (n, 3), flags (n,) PLANE_LM_* bytes."""
+    pos_w (n, 3), flags (n,) PLANE_LM_* bytes.  merge_planes, refine_planes, refinement and the table form of refine_points
+    take the map's tables as a dict and need "Threshold.dot_product_threshold" and "Threshold.offset_delta_factor" (:1172-1173) as well."""
 
     def __init__(self, cfg, mt=None, seed=0):
         if cfg.get("Threshold.use_graph_cut", False):
@@ -361,7 +414,7 @@ class planar_mapper:
         self._ppr = int(cfg["Threshold.point_per_ransac"])
         self._dist_corr = float(cfg["Threshold.plane_distance_correction"])
         self._err_corr = float(cfg["Threshold.final_error_correction"])
-        self._mt, self._seed = mt, seed
+        self._mt, self._seed, self._cfg = mt, seed, cfg
         self.set_map_scale(1.0)
 
     def set_map_scale(self, map_scale):
@@ -387,10 +440,46 @@ class planar_mapper:
         """update_plane_via_RANSAC (:593-733) of a plane with this equation and best error"""
         return self._run(PLANE_UPDATE, pos_w, flags, samples, equation_in=np.asarray(equation, np.float64).reshape(1, 4), best_error_in=[best_error])
 
-    def refine_points(self, pos_w, lm_plane, flags, equation, active):
-        """refine_points (:954-1004): (the new pos_w, changed)"""
+    def refine_points(self, pos_w, lm_plane=None, flags=None, equation=None, active=None):
+        """refine_points (:954-1004): (the new pos_w, changed).  With a dict of the map's tables (PLANE_REFINEMENT_TABLES) as the only argument:
+        the function over the plane table, as merge_planes below"""
+        if isinstance(pos_w, dict):
+            return self._refinement(pos_w, PLANE_STAGE_REFINE_POINTS)
         fn = model_plane_refine_points if self._mt is None else self._mt.plane_refine_points
         return fn(pos_w, lm_plane, flags, equation, active, self.planar_distance_thresh)
+
+    def _refinement(self, tables, stages, merge_cap=16, out=None):
+        """plp_plane_refinement_* on the map's tables (one map: no problem axis; updated in place or replaced in the dict); grows n_cap and runs
+        again from the tables as they were when a merge passes it (PLANE_REFINEMENT_OVERFLOW)"""
+        if "Threshold.dot_product_threshold" not in self._cfg or "Threshold.offset_delta_factor" not in self._cfg:
+            raise PlpError(PLP_ERR_INVALID_ARG, "Threshold.dot_product_threshold and Threshold.offset_delta_factor are required (load_configuration, :1172-1173)")
+        fn = model_plane_refinement if self._mt is None else self._mt.plane_refinement
+        while True:
+            t = {k: np.array(tables[k], dt)[None] for k, (_, dt) in PLANE_REFINEMENT_TABLES.items()}
+            r = fn(t, self.planar_distance_thresh, self.final_error_thresh, points_per_ransac=self._ppr, iters=self._iters,
+                   dot_product_threshold=float(self._cfg["Threshold.dot_product_threshold"]), offset_delta_factor=int(self._cfg["Threshold.offset_delta_factor"]),
+                   seed=self._seed, stages=stages, merge_cap=merge_cap, out=out)
+            if int(r["status"][0]) != PLANE_REFINEMENT_OVERFLOW:
+                break
+            lm = np.asarray(tables["pl_lm"], np.int32)                        # the caller's tables are as they were: twice the slots
+            tables["pl_lm"] = np.concatenate([lm, np.full((lm.shape[0], max(lm.shape[1], 1)), -1, np.int32)], axis=1)
+        for k in PLANE_REFINEMENT_TABLES:
+            tables[k] = t[k][0]
+        return {k: v[0] for k, v in r.items()}
+
+    def merge_planes(self, tables, merge_cap=16):
+        """merge_planes (:795-898) over a dict of the map's tables: pl_state (NP,), pl_equation (NP, 4), pl_best_error, pl_count (NP,), pl_lm
+        (NP, n_cap), pos_w (L, 3), lm_erased, lm_owner (L,).  Returns the outputs of one problem (PLANE_REFINEMENT_OUTPUTS); it returned true
+        where was_merged"""
+        return self._refinement(tables, PLANE_STAGE_MERGE, merge_cap)
+
+    def refine_planes(self, tables):
+        """refine_planes (:900-952) over the tables; it returned true where planes_changed"""
+        return self._refinement(tables, PLANE_STAGE_REFINE_PLANES)
+
+    def refinement(self, tables, merge_cap=16):
+        """refinement() (:773-793) over the tables: the gate, merge_planes, refine_planes, refine_points"""
+        return self._refinement(tables, PLANE_STAGE_ALL, merge_cap)
 
 
 def model_sym_jacobi(A):
@@ -2673,6 +2762,28 @@ class matcher(line_update_entries):
         a = _struct(plane_refine_args_c, dict(M=int(M), NP=int(NP)), dev_ptrs(pos_w=pos_w, lm_plane=lm_plane, flags=flags, equation=equation, active=active,
                                                                               dist_thresh=dist_thresh, out_changed=out_changed))
         self._device("plp_plane_refine_points_device", a, stream)
+
+    def plane_refinement(self, tables, dist_thresh, error_thresh, points_per_ransac=18, iters=50, dot_product_threshold=0.8, offset_delta_factor=6, seed=0,
+                         stages=PLANE_STAGE_ALL, merge_cap=16, out=None):
+        """Planar_Mapping_module::refinement() for G map snapshots (plp_plane_refinement_host): tables a dict of the arrays of
+        PLANE_REFINEMENT_TABLES with a leading problem axis -- pl_state (G, NP_cap) u8 of PLANE_ROW_*, pl_equation (G, NP_cap, 4), pl_best_error
+        (G, NP_cap) f64, pl_count (G, NP_cap), pl_lm (G, NP_cap, n_cap) i32, pos_w (G, L, 3) f64, lm_erased (G, L) u8, lm_owner (G, L) i32 --
+        updated in place (an array of another type or layout is replaced in the dict); dist_thresh / error_thresh scalars or (G,); stages a mask
+        of PLANE_STAGE_*.  Returns the outputs (PLANE_REFINEMENT_OUTPUTS); out: arrays to write into, whose unwritten slots keep their values."""
+        return _plane_refinement_host(self._host("plp_plane_refinement_host"), tables, dist_thresh, error_thresh, points_per_ransac, iters,
+                                      dot_product_threshold, offset_delta_factor, seed, stages, merge_cap, out)
+
+    def plane_refinement_device(self, G, NP_cap, n_cap, L, tables, dist_thresh, error_thresh, out, points_per_ransac=18, iters=50, dot_product_threshold=0.8,
+                                offset_delta_factor=6, seed=0, stages=PLANE_STAGE_ALL, merge_cap=16, stream=None):
+        """plp_plane_refinement_device: every array a device pointer (int) or a torch tensor on the matcher's device, the thresholds (G,) f64
+        tensors, `tables` and `out` dicts named as PLANE_REFINEMENT_TABLES / PLANE_REFINEMENT_OUTPUTS (all required; merges may be absent when
+        merge_cap is 0); asynchronous on `stream`"""
+        a = _struct(plane_refinement_args_c, dict(G=int(G), NP_cap=int(NP_cap), n_cap=int(n_cap), L=int(L), merge_cap=int(merge_cap), stages=int(stages),
+                                                  points_per_ransac=int(points_per_ransac), iters=int(iters), offset_delta_factor=int(offset_delta_factor),
+                                                  dot_product_threshold=float(dot_product_threshold), seed=int(seed) & 0xFFFFFFFFFFFFFFFF),
+                    dev_ptrs(dist_thresh=dist_thresh, error_thresh=error_thresh, **{k: tables[k] for k in PLANE_REFINEMENT_TABLES}))
+        set_outputs(a, PLANE_REFINEMENT_OUTPUTS, out, dev_ptr)
+        self._device("plp_plane_refinement_device", a, stream)
 
     def pnp_ransac(self, valid, bearing, pos_w, octave, scale_factors, iters=30, min_num_inliers=10, recompute=True, samples=None, seed=0, counts=None,
                    outputs=None, out=None):

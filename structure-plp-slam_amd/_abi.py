@@ -177,6 +177,16 @@ class plane_refine_args_c(C.Structure):
                 ("dist_thresh", _VP), ("out_changed", _VP)]
 
 
+class plane_refinement_args_c(C.Structure):
+    """plp_plane_refinement_args"""
+    _fields_ = [("G", C.c_int32), ("NP_cap", C.c_int32), ("n_cap", C.c_int32), ("L", C.c_int32), ("merge_cap", C.c_int32), ("stages", C.c_int32),
+                ("points_per_ransac", C.c_int32), ("iters", C.c_int32), ("offset_delta_factor", C.c_int32), ("dot_product_threshold", C.c_double),
+                ("seed", C.c_uint64), ("pl_state", _VP), ("pl_equation", _VP), ("pl_best_error", _VP), ("pl_count", _VP), ("pl_lm", _VP), ("pos_w", _VP),
+                ("lm_erased", _VP), ("lm_owner", _VP), ("dist_thresh", _VP), ("error_thresh", _VP), ("out_status", _VP), ("out_was_merged", _VP),
+                ("out_planes_changed", _VP), ("out_points_changed", _VP), ("out_removed", _VP), ("out_num_merges", _VP), ("out_merges", _VP),
+                ("out_num_updates", _VP), ("out_update_status", _VP), ("out_lm_changed", _VP)]
+
+
 class pnp_ransac_args_c(C.Structure):
     """plp_pnp_ransac_args"""
     _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("min_num_inliers", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32),
@@ -380,6 +390,12 @@ PLANE_CREATE, PLANE_UPDATE = range(2)
 PLANE_OK, PLANE_TOO_FEW_POINTS, PLANE_NO_ELIGIBLE, PLANE_NOT_FOUND, PLANE_ERROR_ABOVE_THRESHOLD, PLANE_TOO_FEW_LEFT = range(6)
 PLANE_LM_ERASED, PLANE_LM_OWNED = 1, 2
 PLANE_FLAG_INVALID, PLANE_FLAG_NEED_REFINEMENT, PLANE_FLAG_GATED = 1, 2, 4
+# plp_plane_refinement_status, the state byte of a plane row and the stage mask of plp_plane_refinement_*
+PLANE_REFINEMENT_OK, PLANE_REFINEMENT_TOO_FEW_PLANES, PLANE_REFINEMENT_OVERFLOW = range(3)
+PLANE_ROW_IN_DB, PLANE_ROW_VALID, PLANE_ROW_NEED_REFINEMENT = 1, 2, 4
+PLANE_STAGE_MERGE, PLANE_STAGE_REFINE_PLANES, PLANE_STAGE_REFINE_POINTS, PLANE_STAGE_ALL = 1, 2, 4, 7
+PLANE_REFINEMENT_MAX_ROWS = 4096    # NP_cap: the state bytes and the compacted vector of a problem are LDS tables
+PLANE_REFINEMENT_NO_UPDATE = 255    # out_update_status of a row no update touched
 
 
 # plp_pnp_status: where pnp_solver::find_via_ransac leaves a problem

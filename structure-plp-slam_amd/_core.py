@@ -196,6 +196,9 @@ _API = [
     ("plp_plane_refine_points_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_plane_refine_points_host", C.c_int, [_VP, _VP]),
     ("plp_model_plane_refine_points_host", _I32, [_VP]),
+    ("plp_plane_refinement_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_plane_refinement_host", C.c_int, [_VP, _VP]),
+    ("plp_model_plane_refinement_host", _I32, [_VP]),
     ("plp_cull_keyframes_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_cull_keyframes_host", C.c_int, [_VP, _VP]),
     ("plp_model_cull_keyframes_host", _I32, [_VP]),

@@ -1,6 +1,6 @@
 // The matcher context (plp_matcher of include/plp_front.h) and what the files that implement its entry points share: match_context.hip and one
-// *_context.hip per solver (sim3, pnp, essential, two_view, pose_opt, transform_opt, local_ba, local_map, plane, map_cull, covisibility, pose_graph,
-// global_ba, line_update).
+// *_context.hip per solver (sim3, pnp, essential, two_view, pose_opt, transform_opt, local_ba, local_map, plane, plane_refinement, map_cull,
+// covisibility, pose_graph, global_ba, line_update).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,7 +23,8 @@ struct plp_matcher {
     plp::DevBuf la_d, la_i, la_b;                                                            // plp_local_ba_device: likewise
     plp::DevBuf lm_ws;                                                                       // plp_local_map_device: the mark table of a chunk of frames
     plp::DevBuf plane_hyp;                                                                   // plp_plane_ransac_device: the hypotheses' records
-    plp::DevBuf cull_cnt, cull_rem;                                                          // plp_cull_keyframes_device: the snapshot counts, the removed sets
+    plp::DevBuf plane_ref_hyp, plane_ref_mark;                                               // plp_plane_refinement_device: the records of the update that runs, the marks of a merge
+    plp::DevBuf cull_cnt, cull_rem;                                                         // plp_cull_keyframes_device: the snapshot counts, the removed sets
     plp::DevBuf pg_d, pg_i;                                                                  // plp_pose_graph_optimize_device: what its launches hand to one another
     plp::DevBuf covis_ws;                                                                    // plp_covisibility_update_device: what its two launches hand to one another
     plp::DevBuf gb_d, gb_i, gb_b, gb_S, gb_rec;                                              // plp_global_ba_device: the tables, the reduced system and the Levenberg record of the run

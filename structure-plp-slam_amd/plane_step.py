@@ -18,8 +18,9 @@ key frame, up to the objects:
                   frame it visits first and marked it owned); equation [G * c_cap, 4] and active [G * c_cap] u8 (PLANE_OK and at least
                   points_per_ransac members), which plp_plane_refine_points_device reads
 
-What stays on the host (INTEGRATION.md section 3): new data::Plane, set_landmarks / the ownership writes, add_landmark_plane /
-erase_landmark_plane, and merge_planes, whose pair loop mutates the map as it goes.
+What stays on the host (INTEGRATION.md section 3): new data::Plane, set_landmarks / the ownership writes of a new plane, add_landmark_plane /
+erase_landmark_plane.  merge_planes, refine_planes and refine_points over the map's plane table are plane_refinement_step.py, which appends this
+step's rows to that table.
 
 Tables are torch tensors on the step's device:
   key frames  mask [G, rows, cols, 3] u8, undist [G, cap, 28] u8 (undist_keypts_ as plp_keypoint), counts [G] i32, lm_index [G, cap] i32 (the
