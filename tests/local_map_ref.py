@@ -129,17 +129,32 @@ def update_local_map(t, frm_lm, frm_lm_lines, max_num_local_keyfrms=60, ev=None)
         else:
             ev.add("covis_all_rejected")
         lo, hi = _run(t["kf_children_offsets"], kf, C)
+        long_rejected = False
         for o in range(lo, hi):
             if add(t["kf_children"][o], "child"):
                 ev.add("child_added")
+                if o - lo >= 64:                       # the wide census of tests/test_local_map_wide_cpu.py: runs past one wave of 64
+                    ev.add("child_added_at_64_or_later")
+                if o - lo >= 128:
+                    ev.add("child_added_at_128_or_later")
                 break
         else:
             if hi > lo:
                 ev.add("children_all_rejected")
+            if hi - lo > 64:
+                ev.add("children_all_rejected_over_64")
+                long_rejected = True
+            if hi - lo >= 200:
+                ev.add("children_all_rejected_over_200")
         p = t["kf_parent"][kf]
-        ev.add("parent_added" if add(p, "parent") else "parent_minus_one" if p == -1 else "parent_rejected")
+        took = add(p, "parent")
+        ev.add("parent_added" if took else "parent_minus_one" if p == -1 else "parent_rejected")
+        if took and long_rejected:
+            ev.add("parent_added_after_over_64_rejected")
     if first:
         ev.add("cut_never" if cut is None else "cut_at_first_iteration" if cut == 0 else "cut_mid_list")
+        if cut is not None and len(first) > 512:
+            ev.add("cut_with_over_512_first")
 
     # find_local_landmarks[_line], :206-273, and the held byte, tracking_module.cc:911-946
     def landmarks(kf_lm, counts, cap, rows, erased, frame_slots, tag):

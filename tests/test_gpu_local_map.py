@@ -1,9 +1,9 @@
 """module::local_map_updater on the device (plp_local_map_device / _host, csrc/local_map_kernels.hip) against the restatement of DESIGN.md
 section 5, D18 (tests/local_map_ref.py), on the scenes tests/test_local_map_cpu.py holds the host build to: exact equality of every output over
 sentinel-filled arrays.  The widths the kernels use: the workgroup of 512 lanes of k_local_map_keyframes and k_local_map_compact (the stride of
-the loops over key frames, frame slots and candidates: F = 130 and 600 landmarks cross neither, so the caps of 63 .. 70 slots sit around the wave
-of 64 instead, which is what the ballots and the children tiles work in), the 256 lanes of k_local_map_mark, and the chunk of frames that shares
-one mark table."""
+the loops over key frames, frame slots and candidates: F = 130 and rows of at most 70 slots stay inside one pass of it, so the caps of 63 .. 70
+slots sit around the wave of 64 instead, which is what the ballots and the children tiles work in), the 256 lanes of k_local_map_mark, and the
+chunk of frames that shares one mark table.  The scenes in which a workgroup takes a second pass are those of tests/test_gpu_local_map_wide.py."""
 import numpy as np
 import pytest
 

@@ -145,17 +145,10 @@ def test_the_step_equals_the_restatement_and_feeds_run_local():
         assert np.array_equal(a["q2v"][b, :c], b_["q2v"][b, :c]) and np.array_equal(a["q4v"][b, :cl], b_["q4v"][b, :cl]), b
 
 
-def test_ref_kf_keeps_the_previous_value_and_overflow_empties_the_dict():
-    """ref_kf is `nearest`, or the caller's previous value where no key frame voted or every one that did is erased (tracking_module.cc:877-892);
-    a frame whose key-frame list overflows has counts of 0"""
-    import torch
-    import local_map_scene as S
-    sc = S.scene("f130")
-    res = R.run_scene(sc, sc["max_kf"])
-    assert not res[3]["found"] and res[4]["found"] and res[4]["nearest"] == -1
+def scene_tables(sc, T):
+    """the key-frame and landmark tables of the step for a scene of tests/local_map_scene.py; the landmarks' geometry is random"""
     rng = np.random.default_rng(1802)
-    F, L, LL, B = len(sc["kf_parent"]), len(sc["obs_offsets"]) - 1, sc["LL"], sc["frm_lm"].shape[0]
-    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    L, LL = len(sc["obs_offsets"]) - 1, sc["LL"]
     keyframes = {k: T(sc[k]) for k in ("kf_erased", "kf_covis", "kf_parent", "kf_children_offsets", "kf_children", "kf_lm", "kf_lm_lines")}
     keyframes.update(counts=T(sc["kf_counts"]), kl_counts=T(sc["kf_kl_counts"]))
     landmarks = dict(pos_w=T(rng.random((L, 3))), normal=T(rng.random((L, 3))), min_dist=T(rng.random(L).astype(np.float32)),
@@ -164,6 +157,20 @@ def test_ref_kf_keeps_the_previous_value_and_overflow_empties_the_dict():
                      min_dist_lines=T(rng.random(LL).astype(np.float32)), max_dist_lines=T(rng.random(LL).astype(np.float32)),
                      desc_lines=T(rng.integers(0, 256, (LL, 32), dtype=u8)), skip_lines=T(sc["lm_erased_lines"]),
                      obs_offsets_lines=T(np.arange(LL + 1, dtype=i32)))
+    return keyframes, landmarks
+
+
+def test_ref_kf_keeps_the_previous_value_and_overflow_empties_the_dict():
+    """ref_kf is `nearest`, or the caller's previous value where no key frame voted or every one that did is erased (tracking_module.cc:877-892);
+    a frame whose key-frame list overflows has counts of 0"""
+    import torch
+    import local_map_scene as S
+    sc = S.scene("f130")
+    res = R.run_scene(sc, sc["max_kf"])
+    assert not res[3]["found"] and res[4]["found"] and res[4]["nearest"] == -1
+    F, L, LL, B = len(sc["kf_parent"]), len(sc["obs_offsets"]) - 1, sc["LL"], sc["frm_lm"].shape[0]
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    keyframes, landmarks = scene_tables(sc, T)
     prev = np.arange(100, 100 + B, dtype=i32)
     frames = dict(frm_lm=T(sc["frm_lm"][:, :sc["fcap"]]), frm_counts=T(sc["frm_counts"]), frm_lm_lines=T(sc["frm_lm_lines"][:, :sc["flcap"]]),
                   frm_kl_counts=T(sc["frm_kl_counts"]), ref_kf=T(prev))
@@ -180,3 +187,37 @@ def test_ref_kf_keeps_the_previous_value_and_overflow_empties_the_dict():
     counts = [0 if s in (R.NO_KEYFRAMES, R.KF_OVERFLOW) else len(r["local_lm"]) for r, s in zip(res, want["status"])]
     assert np.array_equal(N(out["local"]["counts"]), counts) and counts[0] == 0 and counts[1] > 0
     assert (N(out["local"]["skip"])[0] == 1).all() and (N(out["local"]["skip"])[3] == 1).all()
+
+
+def test_the_step_on_a_map_wider_than_a_workgroup():
+    """the step on `wide_f` (1100 key frames, 600 slots per frame: three passes of k_local_map_keyframes' 512 lanes): every output of the entry, ref_kf
+    and the gathered rows against the restatement"""
+    import torch
+    import local_map_scene as S
+    sc = S.scene("wide_f")
+    res = R.run_scene(sc, sc["max_kf"])
+    F, L, LL, B = len(sc["kf_parent"]), len(sc["obs_offsets"]) - 1, sc["LL"], sc["frm_lm"].shape[0]
+    assert len(res[0]["first"]) > 512 and res[1]["nearest"] >= 512 and res[2]["nearest"] >= 1024
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    N = lambda t: t.cpu().numpy()
+    keyframes, landmarks = scene_tables(sc, T)
+    prev = np.arange(5000, 5000 + B, dtype=i32)
+    frames = dict(frm_lm=T(sc["frm_lm"][:, :sc["fcap"]]), frm_counts=T(sc["frm_counts"]), frm_lm_lines=T(sc["frm_lm_lines"][:, :sc["flcap"]]),
+                  frm_kl_counts=T(sc["frm_kl_counts"]), ref_kf=T(prev))
+    step = importlib.import_module("structure-plp-slam_amd.local_map_step").local_map_step(plp, k_cap=F, m_cap=L, ml_cap=LL, max_num_local_keyfrms=sc["max_kf"])
+    out = step.run(keyframes, landmarks, frames)
+    torch.cuda.synchronize()
+    want = R.expected(res, F, L, LL, True)
+    assert (want["status"][:3] == R.OK).all()
+    for k in want:
+        sel = want[k] != R.SENTINEL[k]
+        assert np.array_equal(N(out[k])[sel], want[k][sel]), k
+    assert np.array_equal(N(out["ref_kf"]), [r["nearest"] if r["found"] and r["nearest"] >= 0 else prev[b] for b, r in enumerate(res)])
+    local = out["local"]
+    assert np.array_equal(N(local["counts"]), [len(r["local_lm"]) if r["found"] else 0 for r in res])
+    pos, desc, skip = N(landmarks["pos_w"]), N(landmarks["desc"]), N(local["skip"])
+    for b, r in enumerate(res):
+        if r["found"]:
+            rows, n = np.array(r["local_lm"], np.int64), len(r["local_lm"])
+            assert N(local["pos_w"])[b, :n].tobytes() == pos[rows].tobytes() and N(local["desc"])[b, :n].tobytes() == desc[rows].tobytes(), b
+            assert np.array_equal(skip[b, :n], np.array(r["held"], u8) | sc["lm_erased"][rows]) and (skip[b, n:] == 1).all(), b
