@@ -243,6 +243,11 @@ int32_t plp_model_seed_introsort_host(uint32_t* entries, int64_t n, int32_t dept
  * whose pivot key lies below it once that part is the end of the live array (only keys below the skip key live there, nothing reads them again): entries
  * [0, n_live) equal the host model's, entries behind are unspecified (stale copies).  Without a skip key n_live = n. */
 plp_status plp_seed_introsort_debug(int32_t device, uint32_t* entries, int64_t n, int32_t depth_limit, uint32_t skip_key, int32_t variant, int32_t* n_live);
+/* How the exact seed sort's kernel partitions a segment of n_segment entries (longer than the variant's LDS window) of a frame whose seed array has n_frame
+ * entries: the stoppers' entries change sides through an LDS tile of the returned number of ranks per side, tile after tile (at least 64 for every frame size).
+ * masks_in_lds (may be NULL): 1 when the segment's chunk masks are held in LDS too.
+ * No GPU needed.  Returns -1 for a bad argument. */
+int32_t plp_seed_sort_tile_ranks(int64_t n_frame, int64_t n_segment, int32_t variant, int32_t* masks_in_lds);
 /* Host model of the LSD gradient kernel's (float)cos((double)a), (float)sin((double)a) fast path (csrc/sincos_ziv.hpp): proven[i] = 0 marks the
  * arguments for which the kernel falls back to the general f64 routine.  Returns the number of proven arguments.  No GPU needed. */
 int32_t plp_model_sincos_host(const float* a, int64_t n, float* c, float* s, uint8_t* proven);

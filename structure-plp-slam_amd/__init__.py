@@ -70,6 +70,16 @@ def seed_introsort_debug(entries, depth_limit=-1, skip_key=0, variant=0, device=
     return (e, nl.value) if return_live else e
 
 
+def seed_sort_tile_ranks(n_frame, n_segment=None, variant=0, return_masks=False):
+    """How the exact seed sort's kernel (variant 0 / 1 as in seed_introsort_debug) partitions a segment of n_segment entries of a frame of n_frame: the ranks per
+    side of the LDS tile its stoppers' entries change sides through.  return_masks: also whether the chunk masks are in LDS.  No GPU"""
+    lm = C.c_int32(0)
+    r = lib().plp_seed_sort_tile_ranks(int(n_frame), int(n_frame if n_segment is None else n_segment), int(variant), C.byref(lm))
+    if r < 0:
+        raise ValueError("bad arguments")
+    return (r, bool(lm.value)) if return_masks else r
+
+
 def model_index_sort(sizes, depth_limit=-1):
     """Host model of the matchers' bin ranking (libstdc++ std::sort order of the indices by size, descending); no GPU needed"""
     sz = np.ascontiguousarray(sizes, np.int32)

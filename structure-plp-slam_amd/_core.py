@@ -69,6 +69,7 @@ _API = [
     ("plp_line_trim", C.c_int, [_VP]),
     ("plp_model_seed_introsort_host", _I32, [_VP, C.c_int64, _I32, C.c_uint32]),
     ("plp_seed_introsort_debug", C.c_int, [_I32, _VP, C.c_int64, _I32, C.c_uint32, _I32, _VP]),
+    ("plp_seed_sort_tile_ranks", _I32, [C.c_int64, C.c_int64, _I32, _VP]),
     ("plp_line_get_stage_times", C.c_int, [_VP, _VP, _VP]),
     ("plp_line_debug_read", C.c_int, [_VP, C.c_int, _I32, _VP, _SZ, _VP]),
     ("plp_line_scaled_size", C.c_int, [_VP, _VP, _VP]),

@@ -487,6 +487,14 @@ int32_t plp_model_seed_introsort_host(uint32_t* entries, int64_t n, int32_t dept
     return 0;
 }
 
+int32_t plp_seed_sort_tile_ranks(int64_t n_frame, int64_t n_segment, int32_t variant, int32_t* masks_in_lds) {
+    if (n_frame < 0 || n_frame > (int64_t)kLsdMaxScaledPixels || n_segment < 2 || n_segment > n_frame || variant < 0 || variant > 1) return -1;
+    int lm = 0;
+    const int r = seed_sort_tile_ranks((size_t)n_frame, (size_t)n_segment, variant, &lm);
+    if (masks_in_lds) *masks_in_lds = lm;
+    return r;
+}
+
 // The kernel's introsort loop on caller-made entries (host pointers; one workgroup), with a chosen recursion budget: the tests' way to
 // reach every branch (global partitions, LDS window, wave tasks, lanes, heap sort) on arbitrary key distributions.
 plp_status plp_seed_introsort_debug(int32_t device, uint32_t* entries, int64_t n, int32_t depth_limit, uint32_t skip_key, int32_t variant, int32_t* n_live) {

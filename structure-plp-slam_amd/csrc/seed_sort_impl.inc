@@ -37,7 +37,7 @@ struct SsCtl {                       // LDS control block
     int w_n; int w_first[kSsWStack], w_last[kSsWStack], w_depth[kSsWStack];
     int q_head, q_tail, q_pending, q_open, n_small, small_head, overflow;
     int n_live;                      // entries [n_live, n) are DEAD: right parts of global partitions whose pivot bin lies below the skip key (see wg_partition)
-    long long t[24];                      // diagnostics (debug entry only): cycles in {G partitions, window load, workgroup levels, wave tasks, lanes, store}, windows, G partitions
+    long long t[24];                      // diagnostics (debug entry only): cycles in {G partitions, window load, workgroup levels, wave tasks, lanes, store}, windows, G partitions; [16..19] of the G partitions: classify, scan, crossing, exchange
 };
 
 // dynamic LDS layout (bytes): control block and queues first, the window LAST -- the prefix arrays of a partition in global memory (12 bytes per
@@ -56,10 +56,26 @@ constexpr size_t kOffWin = kOffRpos + ((size_t)(kSsT / 2 + 64) * sizeof(lrpos_t)
 constexpr size_t kSsLdsBytes = kOffWin + (size_t)kSsT * 4 + 16;   // + a pad: lane_introsort reads two entries per LDS access, the second may lie one word behind the window
 static_assert(kOffRpos + (size_t)kSsMaxChunksG * 12 <= 160 * 1024 && kSsLdsBytes <= 160 * 1024, "LDS of the seed sort");
 
+// A partition in global memory lays out the area from kOffRpos on as: pA, pBx (4 bytes per chunk slot each), the chunk masks when they are held in LDS (16 bytes per
+// chunk), pBi.  After the crossing pBi is dead, and what lies from its offset on is the EXCHANGE TILE: two arrays of `ranks` entries, through which the stoppers of
+// `ranks` consecutive ranks change sides (wg_partition, "B / C").  Host and device compute the tile from the same two functions.
+constexpr int kSsTileMin = 512;      // masks in LDS only where they leave a tile of this many ranks (two barriers and one memory latency per tile; every partition of a 640 x 480 frame but the first)
+__host__ __device__ constexpr size_t ss_tile_off(int nch, bool lm) { return (size_t)((nch + 2) & ~1) * 8 + (lm ? (size_t)nch * 16 : 0); }
+// a segment of n_seg entries when the area has `area` bytes: *lm = masks in LDS; returns the ranks per tile
+__host__ __device__ inline int ss_tile_plan(int n_seg, size_t area, bool* lm) {
+    const int nch = (n_seg - 1 + 63) >> 6;
+    const size_t offL = ss_tile_off(nch, true), offN = ss_tile_off(nch, false);
+    const size_t rL = area > offL ? (area - offL) / 8 : 0, rN = area > offN ? (area - offN) / 8 : 0;
+    *lm = rL >= (size_t)kSsTileMin && offL + (size_t)((nch + 2) & ~1) * 4 <= area;   // (... and pBi fits where the tile will be: it has a slot per chunk, a long segment of a large frame more than a short tile)
+    return (int)(*lm ? rL : rN);
+}
+// Without the masks a tile is never short: the area is the larger of what the window phase needs (A) and 12 bytes per chunk slot of the FRAME (lds_bytes), a segment
+// has at most the frame's chunks + 1 slots at 8 bytes, so the tile has at least min(A / 24, A / 12 / 2) - 2 ranks
+static_assert((kSsLdsBytes - kOffRpos - 16) / 24 >= 64 + 2, "every global partition has an exchange tile");
+
 struct SsMem {
     uint32_t* a;                      // the entries the partition works on (global: the frame's array; LDS: the window)
-    void* rpos;                       // LDS partitions: partner positions by rank, uint16_t[].  Global partitions: the LEFT stoppers' entries by rank (uint32_t[]) ...
-    uint32_t* xr;                     // ... and the RIGHT stoppers' entries by rank (global partitions only)
+    void* rpos;                       // LDS partitions: partner positions by rank, uint16_t[] (global partitions exchange entries through an LDS tile: no list)
     unsigned long long *mL, *mR;      // chunk masks of left / right stoppers
     uint32_t *pA, *pBx, *pBi;         // per chunk: left stoppers before it / right stoppers after it / in it and after it (LDS in both cases)
     size_t lds_bytes_g;               // global partitions: bytes of LDS from pA on (prefix arrays, then the masks if they fit)
@@ -98,7 +114,7 @@ __device__ __forceinline__ int above_cnt(unsigned long long m, int lane) { retur
 // Barriers.  wg_barrier() (plp_barrier.hpp) = a HARD `s_waitcnt lgkmcnt(0)` + `__syncthreads()`: the soft wait of __syncthreads()'s own fence was deleted by the compiler
 // at the barrier that heads the loop over a frame's global partitions in some builds of this file -- the cause of the fault of rounds 4 - 6 (an experiment build with two
 // waves per workgroup in round 4, every build with vector-address accesses to the masks' HBM copy in round 6, the debug entry's kernel always; profiles/r06_seed_sort.md
-// section 4).  Between the passes of a partition in GLOBAL memory chunk masks, rank-indexed lists and the entries themselves go from wave to wave through HBM / L2: that
+// section 4).  Between the passes of a partition in GLOBAL memory chunk masks and the entries themselves go from wave to wave through HBM / L2: that
 // barrier drains the wave's own stores as well (the memory model lets a workgroup-scope release skip vmcnt because the waves of a workgroup share a CU and its vector L1).
 // What stays from the hunt is the CHECK of every partition's swap count and cut (ADVICE r05): damaged masks are never used as addresses, the frame reports status bit 32.
 #define SS_PLAIN_BARRIER() wg_barrier()
@@ -123,24 +139,28 @@ template <class Pred> __device__ __forceinline__ int wave_count_prefix(int nch, 
 // Whole-workgroup partition of [first, last) (more than 64 entries) around the median of three; returns the cut.  Ends with a barrier.
 // Every pass takes U chunks per wave and trip, so that U independent loads (and, in the swap pass, U chains of three dependent ones) are
 // in flight per wave: with one chunk per trip the global-memory form ran at one memory latency per 64 entries and wave.
-template <bool G, bool LM = false> __device__ __forceinline__ int wg_partition(const SsMem& M, SsCtl* ctl, int first, int last, uint32_t skip_key, bool prof = false) {
+// Global partitions: the entries of the stoppers change sides through an LDS tile of `tile_ranks` ranks per side (ss_tile_plan).
+template <bool G, bool LM = false> __device__ __forceinline__ int wg_partition(const SsMem& M, SsCtl* ctl, int first, int last, uint32_t skip_key, bool prof = false, int tile_ranks = 0) {
     long long tp0 = prof ? clock64() : 0;
     auto plap = [&](int k) { if (prof && threadIdx.x == 0) { const long long t1 = clock64(); ctl->t[(G ? 16 : 10) + k] += t1 - tp0; tp0 = t1; } };
-    using rpos_t = typename std::conditional<G, uint32_t, lrpos_t>::type;
-    constexpr int U = G ? 8 : 4, UA = G ? 16 : 4;   // chunks per wave and trip: swap passes / the classifying pass (one load per chunk)
-    [[maybe_unused]] rpos_t* rpos = (rpos_t*)M.rpos + (G ? 0 : (first >> 1));
+    using rpos_t = lrpos_t;
+    [[maybe_unused]] constexpr int U = 4;  // chunks per wave and trip: the swap passes ...
+    constexpr int UA = G ? 16 : 4;         // ... and the classifying pass (one load per chunk)
+    [[maybe_unused]] rpos_t* rpos = G ? nullptr : (rpos_t*)M.rpos + (first >> 1);
     uint32_t* a = M.a;
     const int tid = threadIdx.x, lane = tid & 63, wv = uni(tid >> 6);
     first = uni(first); last = uni(last);
     const int p0 = first + 1, np = last - p0, nch = (np + 63) >> 6, mid = first + (last - first) / 2;
     // Where the chunk masks and prefix arrays of THIS partition live.  In LDS both; a global partition (round 6) packs its prefix arrays at the start of the area
-    // the idle window leaves and puts the masks behind them when they fit as well -- every partition but the first of a 640 x 480 frame (12 + 16 bytes per chunk of
-    // the segment: 41 k entries need 18 KB) -- so that the passes below read them from LDS instead of making a round trip through HBM before their entry loads.
+    // the idle window leaves and puts the masks behind them where they leave room for an exchange tile (ss_tile_plan) -- every partition but the first of a 640 x 480 frame:
+    // 12 + 16 bytes per chunk of the segment, 41 k entries need 18 KB -- so that the passes below read them from LDS instead of making a round trip through HBM before their entry loads.
     SsMem Q = M;
     if constexpr (G) {
+        // pBi comes LAST: only the crossing reads it, so the exchange tile starts where it lies (ss_tile_off)
         const int nchp = (nch + 2) & ~1;
-        Q.pA = M.pA; Q.pBx = M.pA + nchp; Q.pBi = M.pA + 2 * nchp;
-        if constexpr (LM) { Q.mL = (unsigned long long*)(M.pA + 3 * nchp); Q.mR = Q.mL + nch; }   // (the caller checked that they fit)
+        Q.pA = M.pA; Q.pBx = M.pA + nchp;
+        if constexpr (LM) { Q.mL = (unsigned long long*)(M.pA + 2 * nchp); Q.mR = Q.mL + nch; }   // (the caller's choice: ss_tile_plan)
+        Q.pBi = (uint32_t*)((unsigned char*)M.pA + ss_tile_off(nch, LM));
     }
     const uint32_t e0 = a[first], ea = a[p0], eb = a[mid], ec = a[last - 1];
     const int m3 = median3_pos(ea >> kSsShift, eb >> kSsShift, ec >> kSsShift, p0, mid, last - 1);
@@ -239,71 +259,67 @@ template <bool G, bool LM = false> __device__ __forceinline__ int wg_partition(c
     plap(2);
     const int m = uni(ctl->bc[0]), cut = uni(ctl->bc[1]);
     if constexpr (G) {
-        // Global memory (round 6).  Until round 5 the swap pass was a chain of dependent scattered accesses per stopper -- partner position from the rank-indexed
-        // list, then the partner's entry, then two scattered stores -- and with the chip full it was the sort's largest phase (1.28 M of a workgroup's 3.47 M cycles,
-        // three times its time alone).  Now both sides EXPORT their entries by rank (entry loads and rank-indexed stores are coalesced: consecutive stoppers have
-        // consecutive ranks), and after one barrier IMPORT the other side's entry of the same rank into their own position: no address ever comes from memory, no
-        // load depends on another, every access of a wave falls into a few consecutive lines.
-        uint32_t* xl = (uint32_t*)Q.rpos; uint32_t* xr = Q.xr;
+        // Global memory, exchange through LDS.  Until round 6 the swap pass was a chain of dependent scattered accesses per stopper (partner position from a rank-indexed
+        // list, the partner's entry, two scattered stores); round 6 handed the entries over BY RANK through two lists in HBM -- coalesced, no address from memory, but a
+        // load and a store to export an entry and a load and a store to import it, in two latency-bound passes.  The lists only took a value from one wave of the
+        // workgroup to another: LDS does that.  The ranks [0, m) are cut into tiles of R; the stoppers of a tile load their own
+        // entries and put them into tileL / tileR by rank, and after a barrier take the other side's entry of their rank from there and store it to their own position:
+        // one load and one store per moved entry.  Ranks rise with the position on the left side and towards the left on the right side, so the stoppers of a tile lie in
+        // one run of chunks per side; [cL, cLe) and (cRe, cR] are found from the prefix arrays by a cursor that only moves forward (a chunk that straddles a tile's border
+        // is the last chunk of one tile and the first of the next; a lane acts in the tile its rank falls in).  The loads take the whole chunk, so that they do not wait
+        // for the chunk's mask (in HBM in a frame's first partition): a chunk of a tile is half stoppers, the lines are the same.
+        constexpr int UT = 4;
+        const int R = uni(tile_ranks);
+        uint32_t* tileL = Q.pBi; uint32_t* tileR = tileL + R;
         const bool dead = uni(ctl->bc[5]) != 0;
-        auto left_chunks = [&](auto&& body) {
-            for (int c0 = wv * U; c0 < nch; c0 += kSsWaves * U) {
-                if (uni((int)Q.pA[c0]) >= m) break;
-                unsigned long long mk[U]; int r0[U];
+        const int wr = kSsWaves - 1 - wv;                            // the right side's chunks go to the waves in reverse order: a tile of a few chunks per side keeps all waves busy
+        int cL = 0, cR = nch - 1;                                    // pA[cL] <= r0 and pBx[cR] <= r0: the chunks that hold rank r0
+        for (int r0 = 0; r0 < m; r0 += R) {
+            const int r1 = min(r0 + R, m);
+            int cLe = cL, cRe = cR;
+            while (true) { const int c = cLe + lane, k = __popcll(__ballot(c < nch && (int)Q.pA[c] < r1)); cLe += k; if (k < 64) break; }
+            while (true) { const int c = cRe - lane, k = __popcll(__ballot(c >= 0 && (int)Q.pBx[c] < r1)); cRe -= k; if (k < 64) break; }
+            cLe = uni(cLe); cRe = uni(cRe);
+            // one side's chunks of the tile, counted from the cursor (chunk cb + j on the left, cb - j on the right); PUT: entry -> tile, else: the other side's entry -> position
+            auto pass = [&](auto is_left, auto is_put) {
+                constexpr bool LEFT = decltype(is_left)::value, PUT = decltype(is_put)::value;
+                uint32_t* mine = LEFT ? tileL : tileR; const uint32_t* theirs = LEFT ? tileR : tileL;
+                const unsigned long long* msk = LEFT ? Q.mL : Q.mR; const uint32_t* pre = LEFT ? Q.pA : Q.pBx;
+                const int cb = LEFT ? cL : cR, nj = LEFT ? cLe - cL : cR - cRe;
+                for (int j0 = (LEFT ? wv : wr) * UT; j0 < nj; j0 += kSsWaves * UT) {
+                    [[maybe_unused]] uint32_t e[UT];
+                    if constexpr (PUT) {
 #pragma unroll
-                for (int u = 0; u < U; ++u) { const int c = c0 + u; mk[u] = c < nch ? Q.mL[c] : 0ull; r0[u] = c < nch ? (int)Q.pA[c] : m; }
-                int rank[U];
+                        for (int u = 0; u < UT; ++u) {
+                            const int pos = p0 + ((LEFT ? cb + j0 + u : cb - j0 - u) << 6) + lane;
+                            e[u] = (j0 + u < nj && pos < last) ? a[pos] : 0u;
+                        }
+                    }
 #pragma unroll
-                for (int u = 0; u < U; ++u) { const int r = r0[u] + below_cnt(mk[u]); rank[u] = (((mk[u] >> lane) & 1ull) && r < m) ? r : -1; }
-                body(c0, rank);
-            }
-        };
-        auto right_chunks = [&](auto&& body) {
-            for (int c0 = nch - 1 - wv * U; c0 >= 0; c0 -= kSsWaves * U) {
-                if (uni((int)Q.pBx[c0]) >= m) break;
-                unsigned long long mk[U]; int r0[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) { const int c = c0 - u; mk[u] = c >= 0 ? Q.mR[c] : 0ull; r0[u] = c >= 0 ? (int)Q.pBx[c] : m; }
-                int rank[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) { const int r = r0[u] + above_cnt(mk[u], lane); rank[u] = (((mk[u] >> lane) & 1ull) && r < m) ? r : -1; }
-                body(c0, rank);
-            }
-        };
-        // B: export
-        if (!dead) left_chunks([&](int c0, const int (&rank)[U]) {
-            uint32_t v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) v[u] = a[p0 + ((c0 + u) << 6) + lane];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) xl[rank[u]] = v[u];
-        });
-        right_chunks([&](int c0, const int (&rank)[U]) {
-            uint32_t v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) v[u] = a[p0 + ((c0 - u) << 6) + lane];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) xr[rank[u]] = v[u];
-        });
+                    for (int u = 0; u < UT; ++u) {
+                        if (j0 + u >= nj) break;
+                        const int c = LEFT ? cb + j0 + u : cb - j0 - u;
+                        const unsigned long long mk = msk[c];
+                        const int r = (int)pre[c] + (LEFT ? below_cnt(mk) : above_cnt(mk, lane));
+                        if (((mk >> lane) & 1ull) && r >= r0 && r < r1) {
+                            if constexpr (PUT) mine[r - r0] = e[u];
+                            else a[p0 + (c << 6) + lane] = theirs[r - r0];
+                        }
+                    }
+                }
+            };
+            // B: every stopper of the tile puts its entry into the tile (the left stoppers of a partition whose right part is dead need not: their entries are dropped)
+            if (!dead) pass(std::true_type{}, std::true_type{});
+            pass(std::false_type{}, std::true_type{});
+            wg_barrier();
+            // C: ... and takes the other side's entry of its rank into its own position (nothing is stored into a dead right part)
+            pass(std::true_type{}, std::false_type{});
+            if (!dead) pass(std::false_type{}, std::false_type{});
+            wg_barrier();                                            // (the tile is written again)
+            cL = cLe - 1; cR = cRe + 1;
+        }
         ss_barrier<G>();
         plap(3);
-        // C: import
-        left_chunks([&](int c0, const int (&rank)[U]) {
-            uint32_t v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) v[u] = xr[rank[u]];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) a[p0 + ((c0 + u) << 6) + lane] = v[u];
-        });
-        if (!dead) right_chunks([&](int c0, const int (&rank)[U]) {
-            uint32_t v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) v[u] = xl[rank[u]];
-#pragma unroll
-            for (int u = 0; u < U; ++u) if (rank[u] >= 0) a[p0 + ((c0 - u) << 6) + lane] = v[u];
-        });
-        ss_barrier<G>();
-        plap(4);
     } else {
     // B: the right stoppers of rank < m leave their positions in the rank-indexed list (chunks from the right end; those further left only hold higher ranks)
     for (int c0 = nch - 1 - wv * U; c0 >= 0; c0 -= kSsWaves * U) {
@@ -867,14 +883,12 @@ __device__ __forceinline__ void seed_introsort_loop(uint32_t* ent, int n, int de
     const int tid = threadIdx.x;
     SsCtl* ctl = (SsCtl*)(lds + kOffCtl);
     SsWin W{(uint32_t*)(lds + kOffWin), (lrpos_t*)(lds + kOffRpos), (unsigned long long*)(lds + kOffQ), (uint32_t*)(lds + kOffSmall), ctl, dbg, skip_key};
-    const SsMem ML{W.win, W.rpos, nullptr, (unsigned long long*)(lds + kOffML), (unsigned long long*)(lds + kOffMR), (uint32_t*)(lds + kOffPA), (uint32_t*)(lds + kOffPBx), (uint32_t*)(lds + kOffPBi), 0};
+    const SsMem ML{W.win, W.rpos, (unsigned long long*)(lds + kOffML), (unsigned long long*)(lds + kOffMR), (uint32_t*)(lds + kOffPA), (uint32_t*)(lds + kOffPBx), (uint32_t*)(lds + kOffPBi), 0};
     const int nchg = (n + 63) / 64 + 1;
-    // the frame's scratch (seed_sort_ws_entries): word 0 = n_live (out), then the two rank-indexed entry lists of a global partition (n / 2 + 64 each), then the chunk masks
-    const size_t xlen = ((size_t)n / 2 + 64 + 1) & ~(size_t)1;
-    uint32_t* g_xl = ws + 2;
-    unsigned long long* g_mL = (unsigned long long*)(ws + 2 + 2 * xlen);
+    // the frame's scratch (seed_sort_ws_entries): word 0 = n_live (out), then the chunk masks of a partition that does not hold them in LDS
+    unsigned long long* g_mL = (unsigned long long*)(ws + 2);
     const size_t lds_total = kSsLdsBytes > kOffRpos + 12 * ((size_t)(n + 63) / 64 + 1) + 16 ? kSsLdsBytes : kOffRpos + 12 * ((size_t)(n + 63) / 64 + 1) + 16;   // = lds_bytes(n) below: what the launch asked for
-    const SsMem MG{ent, g_xl, g_xl + xlen, g_mL, g_mL + nchg, (uint32_t*)(lds + kOffRpos), nullptr, nullptr, lds_total - kOffRpos - 16};
+    const SsMem MG{ent, nullptr, g_mL, g_mL + nchg, (uint32_t*)(lds + kOffRpos), nullptr, nullptr, lds_total - kOffRpos - 16};
     if (tid == 0) { ctl->g_n = 1; ctl->g_first[0] = 0; ctl->g_last[0] = n; ctl->g_depth[0] = depth; ctl->overflow = 0; ctl->n_live = n; for (int k = 0; k < 24; ++k) ctl->t[k] = 0; }
     while (true) {
         ss_barrier<true>();                                      // (the entries: built, or moved by the last partition / window, by all waves)
@@ -895,9 +909,10 @@ __device__ __forceinline__ void seed_introsort_loop(uint32_t* ent, int n, int de
         }
         const long long tg = dbg ? clock64() : 0;
         // two instantiations, so that the masks' address space is known at compile time (LDS instructions, not flat ones)
-        const int nch_p = (last - first - 1 + 63) >> 6;
-        const bool lm = (size_t)((nch_p + 2) & ~1) * 12 + (size_t)nch_p * 16 <= MG.lds_bytes_g;
-        const int cut = lm ? wg_partition<true, true>(MG, ctl, first, last, skip_key, dbg != nullptr) : wg_partition<true, false>(MG, ctl, first, last, skip_key, dbg != nullptr);
+        bool lm = false;
+        const int tile = uni(ss_tile_plan(last - first, MG.lds_bytes_g, &lm));
+        if (tile < 1) { if (tid == 0) ctl->overflow = 10; continue; }   // (cannot happen: ss_tile_plan's assertion; the frame stops sorting instead of writing outside its LDS)
+        const int cut = lm ? wg_partition<true, true>(MG, ctl, first, last, skip_key, dbg != nullptr, tile) : wg_partition<true, false>(MG, ctl, first, last, skip_key, dbg != nullptr, tile);
         if (dbg && tid == 0) { ctl->t[0] += clock64() - tg; ctl->t[7] += 1; }
         if (tid == 0) {
             int i = ctl->g_n;
@@ -909,7 +924,7 @@ __device__ __forceinline__ void seed_introsort_loop(uint32_t* ent, int n, int de
         }
     }
     // status word 1: WHY the first reporting frame stopped (1 a partition's swap count or cut failed its check, 2 list of small subtrees full, 3 stack of workgroup
-    // partitions full, 4 a wave waited for a task beyond the limit, 5 a claimed queue slot stayed empty, 6 / 7 a wave's own stack, 8 stack of global segments), word 2: that frame
+    // partitions full, 4 a wave waited for a task beyond the limit, 5 a claimed queue slot stayed empty, 6 / 7 a wave's own stack, 8 stack of global segments, 10 no room for an exchange tile), word 2: that frame
     if (tid == 0) { ws[0] = (uint32_t)(ctl->overflow ? n : ctl->n_live); if (ctl->overflow) { if (atomicOr(status, 32) & 32) {} else { status[1] = ctl->overflow; status[2] = (int32_t)blockIdx.x; status[3] = ctl->overflow == 9 ? ctl->bc[7] : ctl->bc[6]; } } }   // (a frame that stopped sorting: every entry is still there exactly once only over the whole array)
     if (dbg && tid == 0) for (int k = 0; k < 24; ++k) { dbg[2 + 6 * 4000 + 2 * k] = (int)(ctl->t[k] & 0xffffffff); dbg[2 + 6 * 4000 + 2 * k + 1] = (int)(ctl->t[k] >> 32); }
 }

@@ -5,7 +5,7 @@
 //
 // One workgroup of 16 waves per frame, the array in HBM / L2 (`ent`, 4 bytes per pixel: pixel | defined << 19 | bin << 20):
 //   G  segments longer than the LDS window (kSsT entries): the whole workgroup partitions one segment in global memory
-//      (wg_partition<true>: chunk masks -> prefix sums -> partner positions by rank -> swaps; four barriers)
+//      (wg_partition<true>: chunk masks -> prefix sums -> the stoppers' entries change sides by rank through an LDS tile, tile after tile)
 //   W  a segment that fits is loaded into LDS and finished there:
 //      - above kSsTask entries the whole workgroup partitions it (wg_partition<false>, the same code on LDS)
 //      - 65 .. kSsTask entries: ONE WAVE per segment, chunk masks in registers (lane c = chunk c), a task queue in LDS, no barriers
@@ -53,7 +53,7 @@ namespace plp {
 
 constexpr int kSsLatMaxFrames = 256;   // batches up to this many frames take the 16-wave configuration (one workgroup per CU)
 
-size_t seed_sort_ws_entries(size_t nv) { return 2 + 2 * ((nv / 2 + 64 + 1) & ~(size_t)1) + 2 * 2 * ((nv + 63) / 64 + 1); }   // u32 units per frame: n_live, two rank-indexed entry lists, chunk masks
+size_t seed_sort_ws_entries(size_t nv) { return 2 + 2 * 2 * ((nv + 63) / 64 + 1); }   // u32 units per frame: n_live, chunk masks
 
 // The final insertion sort = a stable counting sort by bin of the DEFINED entries, in array order (k_lsd_order's steps 2-4 on the
 // permuted array instead of the row-major pixel sequence).
@@ -157,6 +157,13 @@ hipError_t seed_sort_configure() {
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+// How a global partition of n_seg entries of a frame of nv exchanges its stoppers' entries: the ranks per LDS tile, *lm: its masks are in LDS
+int seed_sort_tile_ranks(size_t nv, size_t n_seg, int variant, int* lm) {
+    bool l = false;
+    const int r = variant ? ss_lat::ss_tile_plan((int)n_seg, ss_lat::lds_bytes(nv) - ss_lat::kOffRpos - 16, &l) : ss_thr::ss_tile_plan((int)n_seg, ss_thr::lds_bytes(nv) - ss_thr::kOffRpos - 16, &l);
+    if (lm) *lm = l ? 1 : 0;
+    return r;
 }
 // variant 0: the configuration of large batches, 1: of small ones
 void launch_seed_sort_debug(hipStream_t st, uint32_t* ent, int n, int depth, uint32_t skip_key, uint32_t* ws, int32_t* status, int* dbg, int variant, int copies) {
