@@ -1816,6 +1816,176 @@ int32_t plp_model_check_pose_host(const plp_two_view_pose_args* args, const doub
                                   double* out_pts, uint8_t* out_is_triangulated, uint8_t* out_code);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Map initialisation of the perspective and fisheye cameras (module/initializer.cc:166-172), the two solvers of
+ * initialize::perspective::initialize (src/PLPSLAM/initialize/perspective.cc:84-120) for P frame pairs at once:
+ *   solve::homography_solver   (src/PLPSLAM/solve/homography_solver.cc)   find_via_ransac :60-155, compute_H_21 :405-436, check_inliers :556-631,
+ *                              and what find_via_graph_cut_ransac does with the matrix its RANSAC found, :388-402
+ *   solve::fundamental_solver  (src/PLPSLAM/solve/fundamental_solver.cc)  find_via_ransac :50-144, compute_F_21 :299-332, check_inliers :349-426
+ *   solve::normalize           (src/PLPSLAM/solve/common.cc:31-76), over ALL key points of a frame
+ *   the choice between the two (perspective.cc:99-120)
+ * Numeric contract: DESIGN.md section 5, D27.  sigma is 1.0 (perspective.cc:84-87).
+ *
+ * The match list is given in slot form as for the essential entry: match [P][n_cap], slot = key-point index in frame 1, the value the index in
+ * frame 2 or a negative number; match k is the k-th matched slot in slot order; a value at or above counts_2[p] is no match.  The key points are
+ * the frames' undist_keypts_ (pt is read).
+ *
+ * Each solver runs `iters` hypotheses.  Hypothesis i of H takes the matches samples_h[p][i][0..7], of F samples_f[p][i][0..7]; a NULL table is
+ * drawn from `seed` (D27 item f: the two solvers draw from different streams).  A sample with an index outside [0, num_matches) or a repeated
+ * index gives a hypothesis of score 0.  Per solver the best hypothesis is the reference's: a strictly greater score wins, among equals the
+ * lowest iteration; a NaN score never wins.  recompute: the matrix is fitted once more over the inliers of the best hypothesis in match order and
+ * checked once more (:133-154, :122-143).
+ *
+ * A given homography (the graph-cut path): with given_H_21 and given_H_num_inliers both non-NULL, a problem whose given_H_num_inliers[p] >= 0
+ * runs no H hypothesis.  Its given_H_21[p] is scored by check_inliers (:398), which also gives its mask, and it is valid when that score is
+ * > 0 and given_H_num_inliers[p] >= 8 (:401-402).  A negative given_H_num_inliers[p] leaves problem p to the RANSAC.  F is not affected.
+ *
+ * Outputs per problem:
+ *   out_status_h / _f       a plp_perspective_status per solver
+ *   out_num_matches         matches_12_.size()
+ *   out_H_21 / out_F_21     (9, row-major) get_best_H_21() / get_best_F_21(); zero unless the solver's status is PLP_PERSPECTIVE_OK
+ *   out_score_h / _f        get_best_score() as the reference leaves it: the score of the matrix held, also where the solution is not valid
+ *                           (fewer than eight inliers); 0 for PLP_PERSPECTIVE_TOO_FEW_MATCHES
+ *   out_best_iter_h / _f    the iteration that won; -1 unless OK, and -1 for a given homography
+ *   out_num_inliers_h / _f  the inlier matches of the matrix returned; 0 unless OK
+ *   out_rel_score_h         score_H / (score_H + score_F) as a float (perspective.cc:102); NaN when both are 0
+ *   out_choice              a plp_perspective_choice, perspective.cc:105-120
+ *   out_inliers             [P][n_cap] in slot order: is_inlier_match of the chosen solver (0 for a slot that is no match, all 0 for no choice);
+ *                           slots at or above counts_1[p] keep the caller's values
+ *   out_inliers_h / _f      optional, likewise per solver (all 0 unless OK)
+ *   out_hyp_score_h / _f    optional, [P][iters]: the score of every hypothesis (0 where none runs) */
+typedef enum plp_perspective_status {
+    PLP_PERSPECTIVE_OK = 0,               /* solution_is_valid_                                     homography_solver.cc:131, :402; fundamental_solver.cc:120 */
+    PLP_PERSPECTIVE_TOO_FEW_MATCHES = 1,  /* num_matches < 8                                        homography_solver.cc:78; fundamental_solver.cc:68 */
+    PLP_PERSPECTIVE_INVALID = 2           /* !(best_score_ > 0.0 && num_inliers >= 8) */
+} plp_perspective_status;
+typedef enum plp_perspective_choice {
+    PLP_PERSPECTIVE_CHOICE_NONE = 0,      /* perspective.cc:117-120 */
+    PLP_PERSPECTIVE_CHOICE_H = 1,         /* 0.40 < rel_score_H and H valid                         perspective.cc:105 */
+    PLP_PERSPECTIVE_CHOICE_F = 2          /* otherwise, F valid                                     perspective.cc:111 */
+} plp_perspective_choice;
+typedef struct plp_perspective_ransac_args {
+    int32_t P, n_cap, m_cap;        /* P >= 0 problems of n_cap >= 0 key points of frame 1 against m_cap >= 0 of frame 2; n_cap <= 8192 */
+    int32_t iters;                  /* num_ransac_iters_, >= 1 */
+    int32_t recompute;              /* true in perspective.cc:90-95 */
+    uint64_t seed;                  /* the generator's seed where a sample table is NULL */
+    const int32_t* counts_1;        /* P: key points of frame 1, or NULL = n_cap everywhere */
+    const int32_t* counts_2;        /* P: key points of frame 2, or NULL = m_cap everywhere */
+    const plp_keypoint* undist_1;   /* P x n_cap: ref_undist_keypts_ */
+    const plp_keypoint* undist_2;   /* P x m_cap: cur_undist_keypts_ */
+    const int32_t* match;           /* P x n_cap */
+    const int32_t* samples_h;       /* P x iters x 8 indices of matches, or NULL = drawn from seed */
+    const int32_t* samples_f;       /* P x iters x 8, or NULL */
+    const double* given_H_21;       /* P x 9, or NULL */
+    const int32_t* given_H_num_inliers; /* P: statistics.inliers.size() of the caller's RANSAC, negative = none given; or NULL */
+    uint8_t* out_status_h;          /* P */
+    uint8_t* out_status_f;          /* P */
+    int32_t* out_num_matches;       /* P */
+    double* out_H_21;               /* P x 9 */
+    double* out_F_21;               /* P x 9 */
+    float* out_score_h;             /* P */
+    float* out_score_f;             /* P */
+    int32_t* out_best_iter_h;       /* P */
+    int32_t* out_best_iter_f;       /* P */
+    int32_t* out_num_inliers_h;     /* P */
+    int32_t* out_num_inliers_f;     /* P */
+    float* out_rel_score_h;         /* P */
+    uint8_t* out_choice;            /* P */
+    uint8_t* out_inliers;           /* P x n_cap */
+    uint8_t* out_inliers_h;         /* P x n_cap, or NULL */
+    uint8_t* out_inliers_f;         /* P x n_cap, or NULL */
+    float* out_hyp_score_h;         /* P x iters, or NULL */
+    float* out_hyp_score_f;         /* P x iters, or NULL */
+} plp_perspective_ransac_args;
+/* Checked before anything is written (PLP_ERR_INVALID_ARG): NULL ctx / args; P < 0, n_cap < 0, m_cap < 0, iters < 1; exactly one of given_H_21
+ * and given_H_num_inliers; and -- when P > 0 and n_cap > 0 -- a NULL undist_1, match, undist_2 (with m_cap > 0) or required output (every out_
+ * field that is not marked "or NULL").  n_cap > 8192, P > 65535 or iters > 65536: PLP_ERR_UNSUPPORTED.  P == 0 or n_cap == 0: PLP_OK,
+ * nothing written.
+ * _device: every array a DEVICE pointer; five kernels on hip_stream, no host synchronisation; bad samples are never an error.  The kernels hand
+ * their work to one another through buffers the context owns, so the calls of one context must be ordered on the device.  _host: HOST
+ * pointers, staged (the outputs too, so that every slot the kernels do not write keeps the caller's value), the same kernels, synchronous. */
+plp_status plp_perspective_ransac_device(plp_matcher* ctx, const plp_perspective_ransac_args* args, void* hip_stream);
+plp_status plp_perspective_ransac_host(plp_matcher* ctx, const plp_perspective_ransac_args* args);
+/* Host builds of the same source (csrc/perspective_init.hpp), HOST pointers, no GPU and no context needed; -1 for a bad argument.
+ * plp_model_perspective_ransac_host: the entry above, one problem and one hypothesis after the other; the same checks.  Returns P.
+ * plp_model_normalize_keypoints_host: solve::normalize of n key points: out_normalized n x 2 floats (may be NULL), out_stats 4 floats (mean_x,
+ * mean_y, 1 / dev_x, 1 / dev_y), out_transform 9.  Returns n.
+ * plp_model_homography_fit_host / plp_model_fundamental_fit_host: compute_H_21 / compute_F_21 for n lists of point pairs: list i holds rows
+ * offsets[i] .. offsets[i+1] of pts_1 / pts_2 (x, y floats, as normalised).  out n x 9, out_sweeps n (may be NULL; the 9 x 9 Jacobi).  Returns n.
+ * plp_model_homography_check_host / plp_model_fundamental_check_host: check_inliers of n matrices (n x 9) against one problem (undist_1 n_cap,
+ * undist_2 m_cap, match n_cap; a match outside [0, m_cap) is none): out_score n, out_num_inliers n, out_inliers n x n_cap in slot order (may be
+ * NULL).  Returns n.
+ * plp_model_perspective_draw_host: the samples the entries draw for problem p, iterations iter0 .. iter0 + n_iters - 1, of num_matches >= 8
+ * matches; solver 0 = H, 1 = F.  out n_iters x 8.  Returns n_iters. */
+int32_t plp_model_perspective_ransac_host(const plp_perspective_ransac_args* args);
+int32_t plp_model_normalize_keypoints_host(const plp_keypoint* keypts, int32_t n, float* out_normalized, float* out_stats, double* out_transform);
+int32_t plp_model_homography_fit_host(const float* pts_1, const float* pts_2, const int32_t* offsets, int32_t n, double* out_H_21, int32_t* out_sweeps);
+int32_t plp_model_fundamental_fit_host(const float* pts_1, const float* pts_2, const int32_t* offsets, int32_t n, double* out_F_21, int32_t* out_sweeps);
+int32_t plp_model_homography_check_host(const plp_keypoint* undist_1, const plp_keypoint* undist_2, const int32_t* match, int32_t n_cap, int32_t m_cap,
+                                        const double* H_21, int32_t n, float* out_score, int32_t* out_num_inliers, uint8_t* out_inliers);
+int32_t plp_model_fundamental_check_host(const plp_keypoint* undist_1, const plp_keypoint* undist_2, const int32_t* match, int32_t n_cap, int32_t m_cap,
+                                         const double* F_21, int32_t n, float* out_score, int32_t* out_num_inliers, uint8_t* out_inliers);
+int32_t plp_model_perspective_draw_host(int32_t solver, uint64_t seed, int32_t p, int32_t iter0, int32_t n_iters, int32_t num_matches, int32_t* out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Map initialisation of the perspective and fisheye cameras, from the chosen matrix to the pose: perspective::reconstruct_with_H and
+ * reconstruct_with_F (src/PLPSLAM/initialize/perspective.cc:123-174) for P frame pairs -- homography_solver::decompose
+ * (solve/homography_solver.cc:438-554; eight hypotheses, the normals are not formed) or fundamental_solver::decompose
+ * (solve/fundamental_solver.cc:334-340; four), then initialize::base::find_most_plausible_pose(..., true) with one check_pose call per
+ * hypothesis (initialize/base.cc:62-243), depth_is_positive true.  Numeric contract: DESIGN.md section 5, D27 items e and h, with D24 items
+ * c, f and g.  The inputs are the outputs of the RANSAC entry above (in_choice <- out_choice, H_21 <- out_H_21, F_21 <- out_F_21, inliers <-
+ * out_inliers, the same match and key-point tables) and the frames' bearings, so the two entries chain on one stream without the host.
+ * The camera matrix of both frames is the camera's (get_camera_matrix, perspective.cc:176-199): perspective and fisheye; the
+ * equirectangular model, where the reference throws, is PLP_ERR_UNSUPPORTED.
+ * Outputs per problem as for plp_two_view_pose_args, over eight hypotheses:
+ *   out_status             a plp_two_view_status, or PLP_PERSPECTIVE_POSE_NO_DECOMPOSITION; PLP_TWO_VIEW_NO_SOLUTION for in_choice[p] == 0
+ *   out_hypothesis         0 .. 7 (H) or 0 .. 3 (F), -1 unless PLP_TWO_VIEW_OK
+ *   out_num_valid [P][8], out_parallax_deg [P][8]   the first four used for F, the others zero; all zero without a decomposition
+ *   out_hyp_is_triangulated   optional, [P][8][n_cap] */
+typedef enum plp_perspective_pose_status {
+    PLP_PERSPECTIVE_POSE_NO_DECOMPOSITION = 5   /* homography_solver::decompose returned false: the rank test of homography_solver.cc:462 */
+} plp_perspective_pose_status;
+typedef struct plp_perspective_pose_args {
+    plp_camera_model camera;        /* camera_ of both frames; perspective or fisheye */
+    float img_bounds[4];            /* camera::base img_bounds_: min_x, max_x, min_y, max_y */
+    int32_t P, n_cap, m_cap;        /* as plp_perspective_ransac_args */
+    int32_t min_num_triangulated;   /* min_num_triangulated_ (base.cc:92), >= 0; 50 */
+    float parallax_deg_thr;         /* parallax_deg_thr_ (base.cc:109); 1.0 */
+    float reproj_err_thr;           /* reproj_err_thr_ (base.cc:130); 4.0 */
+    const int32_t* counts_1;        /* P, or NULL = n_cap everywhere */
+    const int32_t* counts_2;        /* P, or NULL = m_cap everywhere */
+    const uint8_t* in_choice;       /* P: a plp_perspective_choice */
+    const double* H_21;             /* P x 9, row-major; read where in_choice[p] is PLP_PERSPECTIVE_CHOICE_H */
+    const double* F_21;             /* P x 9; read where it is PLP_PERSPECTIVE_CHOICE_F */
+    const uint8_t* inliers;         /* P x n_cap: is_inlier_match of the chosen solver in slot order */
+    const int32_t* match;           /* P x n_cap */
+    const double* bearing_1;        /* P x n_cap x 3 */
+    const double* bearing_2;        /* P x m_cap x 3 */
+    const plp_keypoint* undist_1;   /* P x n_cap */
+    const plp_keypoint* undist_2;   /* P x m_cap */
+    uint8_t* out_status;            /* P */
+    double* out_rot_ref_to_cur;     /* P x 9 */
+    double* out_trans_ref_to_cur;   /* P x 3 */
+    int32_t* out_hypothesis;        /* P */
+    int32_t* out_num_valid;         /* P x 8 */
+    float* out_parallax_deg;        /* P x 8 */
+    double* out_triangulated_pts;   /* P x n_cap x 3 */
+    uint8_t* out_is_triangulated;   /* P x n_cap */
+    uint8_t* out_hyp_is_triangulated;   /* P x 8 x n_cap, or NULL */
+} plp_perspective_pose_args;
+/* Checked before anything is written: as for plp_two_view_pose_args, with in_choice, H_21 and F_21 in the place of E_21, and the equirectangular
+ * camera PLP_ERR_UNSUPPORTED.  _device: every array a DEVICE pointer; one kernel on hip_stream, no host synchronisation; the points and flags
+ * of the hypotheses wait in buffers the context owns, so the calls of one context must be ordered on the device.  _host: HOST pointers,
+ * staged, the same kernel, synchronous. */
+plp_status plp_perspective_pose_device(plp_matcher* ctx, const plp_perspective_pose_args* args, void* hip_stream);
+plp_status plp_perspective_pose_host(plp_matcher* ctx, const plp_perspective_pose_args* args);
+/* Host builds (csrc/perspective_init.hpp), HOST pointers, no GPU and no context needed; -1 for a bad argument.
+ * plp_model_perspective_pose_host: the entry above, one problem after the other; the same checks.  Returns P.
+ * plp_model_homography_decompose_host: homography_solver::decompose of n matrices (n x 9) under the camera matrix cam_matrix (9, row-major,
+ * of both frames): out_ok n (0 = it returned false, the poses then zero), out_rots n x 8 x 9, out_trans n x 8 x 3.  Returns n. */
+int32_t plp_model_perspective_pose_host(const plp_perspective_pose_args* args);
+int32_t plp_model_homography_decompose_host(const double* H_21, const double* cam_matrix, int32_t n, uint8_t* out_ok, double* out_rots, double* out_trans);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Per-frame pose optimisation: optimize::pose_optimizer::optimize (src/PLPSLAM/optimize/pose_optimizer.cc:53-229) and
  * optimize::pose_optimizer_extended_line::optimize (optimize/pose_optimizer_extended_line.cc:62-305) for B frames at once, in slot form --
  * what the tracker runs after the last-frame match (module/frame_tracker.cc:83-96), after the local-map match (tracking_module.cc:750-759)

@@ -30,6 +30,10 @@ from ._essential import (ESSENTIAL_OUTPUTS, _essential_ransac_host, essential_so
                          model_essential_ransac)
 from ._two_view import (TWO_VIEW_OUTPUTS, _two_view_pose_host, bearing_vector_initializer, model_check_pose, model_essential_decompose, model_two_view_pose,
                         two_view_args)
+from ._perspective import (PERSPECTIVE_POSE_OUTPUTS, PERSPECTIVE_RANSAC_OUTPUTS, _perspective_pose_host, _perspective_ransac_host, fundamental_solver,
+                           homography_solver, model_fundamental_check, model_fundamental_fit, model_homography_check, model_homography_decompose,
+                           model_homography_fit, model_normalize_keypoints, model_perspective_draw, model_perspective_pose, model_perspective_ransac,
+                           perspective_initializer, perspective_pose_args)
 from ._line_update import (CORRECT_LINE_ERASED, CORRECT_LINE_NO_REF, CORRECT_LINE_NO_VERTEX, CORRECT_LINE_OK, LINE_MOVE_OUTPUTS, TRIM_DEPTH_POSITIVE, TRIM_INDEX_RANGE,
                            TRIM_MAX_CHANGE, TRIM_MAX_CHANGE_THR, TRIM_NO_REF, TRIM_NOT_OBSERVED, TRIM_OK, TRIM_OUTPUTS, TRIM_REJECTED, TRIM_SKIPPED,
                            correct_landmark_lines_args_c, line_update_entries, loop_ba_propagate_lines_args_c, model_correct_landmark_lines,
@@ -2834,6 +2838,50 @@ class matcher(line_update_entries):
                     dev_ptrs(counts_1=counts_1, counts_2=counts_2, bearing_1=bearing_1, bearing_2=bearing_2, match=match, samples=samples))
         set_outputs(a, ESSENTIAL_OUTPUTS, out, dev_ptr)
         self._device("plp_essential_ransac_device", a, stream)
+
+    def perspective_ransac(self, undist_1, undist_2, match, iters=100, recompute=True, samples_h=None, samples_f=None, seed=0, counts_1=None, counts_2=None,
+                           given_H_21=None, given_H_num_inliers=None, outputs=None, out=None):
+        """The homography and the fundamental RANSAC of initialize::perspective::initialize and the choice between them for P pairs of frames
+        (plp_perspective_ransac_host): undist_1 (P, n_cap) / undist_2 (P, m_cap) key points (KP_DTYPE records, or (.., 2)
+        points), match (P, n_cap) i32: the index in frame 2 or a negative number, samples_h / samples_f (P, iters, 8) indices of matches or None =
+        drawn from seed, counts_1 / counts_2 (P,) or None, given_H_21 (P, 3, 3) with given_H_num_inliers (P,): the homography of the caller's own
+        RANSAC for the problems whose count is not negative.  Returns a dict named as PERSPECTIVE_RANSAC_OUTPUTS; `outputs` names the optional ones
+        wanted (default all); out[name]: the caller's array."""
+        return _perspective_ransac_host(self._host("plp_perspective_ransac_host"), undist_1, undist_2, match, iters, recompute, samples_h, samples_f, seed,
+                                        counts_1, counts_2, given_H_21, given_H_num_inliers, outputs, out)
+
+    def perspective_ransac_device(self, P, n_cap, m_cap, undist_1, undist_2, match, out, iters=100, recompute=True, samples_h=None, samples_f=None, seed=0,
+                                  counts_1=None, counts_2=None, given_H_21=None, given_H_num_inliers=None, stream=None):
+        """plp_perspective_ransac_device: every array a device pointer (int) or a torch tensor on the matcher's device (the key points as bytes of
+        KP_DTYPE records); out: dict of the device outputs named as in PERSPECTIVE_RANSAC_OUTPUTS (the optional ones may be absent); asynchronous,
+        five kernels on the stream"""
+        a = _struct(perspective_ransac_args_c, dict(P=int(P), n_cap=int(n_cap), m_cap=int(m_cap), iters=int(iters), recompute=int(bool(recompute)),
+                                                    seed=int(seed) & 0xFFFFFFFFFFFFFFFF),
+                    dev_ptrs(counts_1=counts_1, counts_2=counts_2, undist_1=undist_1, undist_2=undist_2, match=match, samples_h=samples_h, samples_f=samples_f,
+                             given_H_21=given_H_21, given_H_num_inliers=given_H_num_inliers))
+        set_outputs(a, PERSPECTIVE_RANSAC_OUTPUTS, out, dev_ptr)
+        self._device("plp_perspective_ransac_device", a, stream)
+
+    def perspective_pose(self, camera, choice, H_21, F_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2, min_num_triangulated=50,
+                         parallax_deg_thr=1.0, reproj_err_thr=4.0, counts_1=None, counts_2=None, img_bounds=None, outputs=None, out=None):
+        """perspective::reconstruct_with_H / reconstruct_with_F for P frame pairs (plp_perspective_pose_host; DESIGN.md section 5, D27): camera a
+        camera_model of the perspective or fisheye model, choice (P,) u8, H_21 / F_21 (P, 3, 3), inliers (P, n_cap) u8 and match (P, n_cap) i32 as
+        matcher.perspective_ransac gives and takes them, bearing_1 (P, n_cap, 3) / bearing_2 (P, m_cap, 3), undist_1 / undist_2 the key points.
+        Returns a dict named as PERSPECTIVE_POSE_OUTPUTS (status: TWO_VIEW_* or PERSPECTIVE_POSE_NO_DECOMPOSITION; num_valid / parallax_deg (P, 8));
+        `outputs` names the optional ones wanted; out[name]: the caller's array."""
+        return _perspective_pose_host(self._host("plp_perspective_pose_host"), camera, choice, H_21, F_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2,
+                                      min_num_triangulated, parallax_deg_thr, reproj_err_thr, counts_1, counts_2, img_bounds, outputs, out)
+
+    def perspective_pose_device(self, camera, P, n_cap, m_cap, choice, H_21, F_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2, out,
+                                min_num_triangulated=50, parallax_deg_thr=1.0, reproj_err_thr=4.0, counts_1=None, counts_2=None, img_bounds=None, stream=None):
+        """plp_perspective_pose_device: every array a device pointer (int) or a torch tensor on the matcher's device; out: dict of the device outputs
+        named as in PERSPECTIVE_POSE_OUTPUTS (hyp_is_triangulated may be absent); asynchronous, one kernel on the stream"""
+        a = perspective_pose_args(camera, dict(P=int(P), n_cap=int(n_cap), m_cap=int(m_cap), min_num_triangulated=int(min_num_triangulated),
+                                               parallax_deg_thr=float(parallax_deg_thr), reproj_err_thr=float(reproj_err_thr)),
+                                  dev_ptrs(counts_1=counts_1, counts_2=counts_2, in_choice=choice, H_21=H_21, F_21=F_21, inliers=inliers, match=match,
+                                           bearing_1=bearing_1, bearing_2=bearing_2, undist_1=undist_1, undist_2=undist_2), img_bounds)
+        set_outputs(a, PERSPECTIVE_POSE_OUTPUTS, out, dev_ptr)
+        self._device("plp_perspective_pose_device", a, stream)
 
     def two_view_pose(self, camera, E_21, inliers, match, bearing_1, bearing_2, undist_1, undist_2, min_num_triangulated=50, parallax_deg_thr=1.0,
                       reproj_err_thr=4.0, depth_is_positive=False, in_status=None, counts_1=None, counts_2=None, img_bounds=None, outputs=None, out=None):

@@ -203,6 +203,25 @@ class essential_ransac_args_c(C.Structure):
                 ("out_hyp_score", _VP)]
 
 
+class perspective_ransac_args_c(C.Structure):
+    """plp_perspective_ransac_args"""
+    _fields_ = [("P", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32), ("iters", C.c_int32), ("recompute", C.c_int32), ("seed", C.c_uint64),
+                ("counts_1", _VP), ("counts_2", _VP), ("undist_1", _VP), ("undist_2", _VP), ("match", _VP), ("samples_h", _VP), ("samples_f", _VP),
+                ("given_H_21", _VP), ("given_H_num_inliers", _VP), ("out_status_h", _VP), ("out_status_f", _VP), ("out_num_matches", _VP), ("out_H_21", _VP),
+                ("out_F_21", _VP), ("out_score_h", _VP), ("out_score_f", _VP), ("out_best_iter_h", _VP), ("out_best_iter_f", _VP), ("out_num_inliers_h", _VP),
+                ("out_num_inliers_f", _VP), ("out_rel_score_h", _VP), ("out_choice", _VP), ("out_inliers", _VP), ("out_inliers_h", _VP), ("out_inliers_f", _VP),
+                ("out_hyp_score_h", _VP), ("out_hyp_score_f", _VP)]
+
+
+class perspective_pose_args_c(C.Structure):
+    """plp_perspective_pose_args"""
+    _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("P", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
+                ("min_num_triangulated", C.c_int32), ("parallax_deg_thr", C.c_float), ("reproj_err_thr", C.c_float), ("counts_1", _VP), ("counts_2", _VP),
+                ("in_choice", _VP), ("H_21", _VP), ("F_21", _VP), ("inliers", _VP), ("match", _VP), ("bearing_1", _VP), ("bearing_2", _VP), ("undist_1", _VP),
+                ("undist_2", _VP), ("out_status", _VP), ("out_rot_ref_to_cur", _VP), ("out_trans_ref_to_cur", _VP), ("out_hypothesis", _VP), ("out_num_valid", _VP),
+                ("out_parallax_deg", _VP), ("out_triangulated_pts", _VP), ("out_is_triangulated", _VP), ("out_hyp_is_triangulated", _VP)]
+
+
 class two_view_pose_args_c(C.Structure):
     """plp_two_view_pose_args"""
     _fields_ = [("camera", camera_model_c), ("img_bounds", C.c_float * 4), ("P", C.c_int32), ("n_cap", C.c_int32), ("m_cap", C.c_int32),
@@ -404,6 +423,10 @@ PNP_OK, PNP_TOO_FEW_MATCHES, PNP_TOO_FEW_INLIERS = range(3)
 
 # plp_essential_status: where essential_solver::find_via_ransac leaves a problem
 ESSENTIAL_OK, ESSENTIAL_TOO_FEW_MATCHES, ESSENTIAL_INVALID = range(3)
+# plp_perspective_status: where homography_solver / fundamental_solver leave a problem; plp_perspective_choice: what initialize::perspective takes
+PERSPECTIVE_OK, PERSPECTIVE_TOO_FEW_MATCHES, PERSPECTIVE_INVALID = range(3)
+PERSPECTIVE_CHOICE_NONE, PERSPECTIVE_CHOICE_H, PERSPECTIVE_CHOICE_F = range(3)
+PERSPECTIVE_POSE_NO_DECOMPOSITION = 5      # plp_perspective_pose_status: beside the TWO_VIEW_* values, homography_solver::decompose returned false
 # plp_two_view_status: where bearing_vector::reconstruct_with_E leaves a problem
 TWO_VIEW_OK, TWO_VIEW_NO_SOLUTION, TWO_VIEW_TOO_FEW_TRIANGULATED, TWO_VIEW_AMBIGUOUS, TWO_VIEW_SMALL_PARALLAX = range(5)
 

@@ -157,6 +157,19 @@ _API = [
     ("plp_model_two_view_pose_host", _I32, [_VP]),
     ("plp_model_essential_decompose_host", _I32, [_VP, _I32, _VP, _VP]),
     ("plp_model_check_pose_host", _I32, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_perspective_ransac_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_perspective_ransac_host", C.c_int, [_VP, _VP]),
+    ("plp_model_perspective_ransac_host", _I32, [_VP]),
+    ("plp_model_normalize_keypoints_host", _I32, [_VP, _I32, _VP, _VP, _VP]),
+    ("plp_model_homography_fit_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_model_fundamental_fit_host", _I32, [_VP, _VP, _VP, _I32, _VP, _VP]),
+    ("plp_model_homography_check_host", _I32, [_VP, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
+    ("plp_model_fundamental_check_host", _I32, [_VP, _VP, _VP, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
+    ("plp_model_perspective_draw_host", _I32, [_I32, C.c_uint64, _I32, _I32, _I32, _I32, _VP]),
+    ("plp_perspective_pose_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_perspective_pose_host", C.c_int, [_VP, _VP]),
+    ("plp_model_perspective_pose_host", _I32, [_VP]),
+    ("plp_model_homography_decompose_host", _I32, [_VP, _VP, _I32, _VP, _VP, _VP]),
     ("plp_pose_optimize_device", C.c_int, [_VP, _VP, _VP]),
     ("plp_pose_optimize_host", C.c_int, [_VP, _VP]),
     ("plp_model_pose_optimize_host", _I32, [_VP]),

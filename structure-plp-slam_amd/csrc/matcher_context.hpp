@@ -1,5 +1,5 @@
 // The matcher context (plp_matcher of include/plp_front.h) and what the files that implement its entry points share: match_context.hip and one
-// *_context.hip per solver (sim3, pnp, essential, two_view, pose_opt, transform_opt, local_ba, local_map, plane, plane_refinement, map_cull,
+// *_context.hip per solver (sim3, pnp, essential, two_view, perspective_init, pose_opt, transform_opt, local_ba, local_map, plane, plane_refinement, map_cull,
 // covisibility, pose_graph, global_ba, line_update).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -18,6 +18,8 @@ struct plp_matcher {
     plp::DevBuf pnp_ctx, pnp_slot, pnp_hyp, pnp_corr, pnp_pose, pnp_sign;   // plp_pnp_ransac_device: likewise
     plp::DevBuf ess_ctx, ess_slot, ess_hyp, ess_pairs, ess_E, ess_code, ess_key;     // plp_essential_ransac_device: likewise
     plp::DevBuf tv_pts, tv_flag;                  // plp_two_view_pose_device: the points and flags of the four hypotheses
+    plp::DevBuf persp_ctx, persp_norm, persp_T, persp_slot, persp_hyp, persp_pairs, persp_M, persp_code, persp_key;   // plp_perspective_ransac_device: likewise
+    plp::DevBuf persp_pts, persp_flag;            // plp_perspective_pose_device: the points and flags of the eight hypotheses
     plp::DevBuf pose_slot, pose_slot_lines, pose_chi2, pose_n;              // plp_pose_optimize_device: likewise
     plp::DevBuf tf_slot, tf_chi2, tf_n, tf_level, tf_edge;                                   // plp_transform_optimize_device: likewise
     plp::DevBuf la_d, la_i, la_b;                                                            // plp_local_ba_device: likewise

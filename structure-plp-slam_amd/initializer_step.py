@@ -93,3 +93,57 @@ class initializer_step:
         not valid; status [B] u8).  samples [B, 50, 8] i32 or None = drawn from seed.  Nothing is synchronised."""
         out = self._ransac(bearing_1, bearing_2, match, 50, False, counts_1, counts_2, samples, seed, stream)
         return dict(inliers=out["inliers"], num_inlier_matches=out["num_inliers"], status=out["status"])
+
+    def run_perspective(self, camera, bearing_1, bearing_2, match, undist_1, undist_2, counts_1=None, counts_2=None, samples_h=None, samples_f=None, seed=0,
+                        given_H_21=None, given_H_num_inliers=None, min_num_triangulated=50, parallax_deg_thr=1.0, reproj_err_thr=4.0, img_bounds=None, stream=None):
+        """Enqueue initialize::perspective::initialize (initialize/perspective.cc:48-174) of B (reference, current) pairs on `stream` (default: the
+        current stream): homography_fundamental(...) -> plp_perspective_pose_device, the second reading the first's choice, matrices and mask in HBM
+        (DESIGN.md section 5, D27).  camera: a camera_model of the perspective or fisheye model.  Returns the tensors named as
+        PERSPECTIVE_POSE_OUTPUTS without the per-hypothesis flags (status [B] u8: TWO_VIEW_* or PERSPECTIVE_POSE_NO_DECOMPOSITION, the pose ref -> cur,
+        hypothesis, num_valid / parallax_deg [B, 8], triangulated_pts [B, n_cap, 3], is_triangulated [B, n_cap]) and ransac: the solvers' outputs.
+        Nothing is synchronised; the object creation and scale_map stay with the caller."""
+        torch = self.torch
+        st = stream or torch.cuda.current_stream(self.dev)
+        e = self.homography_fundamental(undist_1, undist_2, match, counts_1, counts_2, samples_h, samples_f, seed, given_H_21, given_H_num_inliers, st)
+        B, n_cap = match.shape
+        m_cap = bearing_2.shape[1]
+        tt = {np.uint8: torch.uint8, np.int32: torch.int32, np.float64: torch.float64, np.float32: torch.float32}
+        with torch.cuda.stream(st):
+            out = {k: torch.zeros((B,) + shape(n_cap), dtype=tt[dt], device=self.dev) for k, (shape, dt, _) in self.plp.PERSPECTIVE_POSE_OUTPUTS.items()
+                   if k != "hyp_is_triangulated"}
+            if B and n_cap:
+                out["status"].fill_(self.plp.TWO_VIEW_NO_SOLUTION)
+                out["hypothesis"].fill_(-1)
+        if B and n_cap and m_cap:
+            self.mt.perspective_pose_device(camera, B, n_cap, m_cap, e["choice"], e["H_21"], e["F_21"], e["inliers"], match.contiguous(), bearing_1.contiguous(),
+                                            bearing_2.contiguous(), undist_1.contiguous(), undist_2.contiguous(), out, min_num_triangulated=min_num_triangulated,
+                                            parallax_deg_thr=parallax_deg_thr, reproj_err_thr=reproj_err_thr, counts_1=counts_1, counts_2=counts_2,
+                                            img_bounds=img_bounds, stream=st)
+        out["ransac"] = e
+        return out
+
+    def homography_fundamental(self, undist_1, undist_2, match, counts_1=None, counts_2=None, samples_h=None, samples_f=None, seed=0, given_H_21=None,
+                               given_H_num_inliers=None, stream=None):
+        """Enqueue the two solvers of initialize::perspective::initialize (initialize/perspective.cc:84-120) and the choice between them for B pairs
+        on `stream` (default: the current stream): plp_perspective_ransac_device with num_ransac_iters hypotheses per
+        solver and the refit.  undist_1 [B, n_cap] / undist_2 [B, m_cap]: the post-extract step's undistorted key points (plp_keypoint rows, any
+        tensor of 28 bytes per key point); samples_h / samples_f [B, num_ransac_iters, 8] i32 or None = drawn from seed; given_H_21 [B, 3, 3] f64
+        with given_H_num_inliers [B] i32: the homography of the caller's graph-cut RANSAC for the pairs whose count is not negative, which then
+        run no H hypotheses.  Returns the tensors named as PERSPECTIVE_RANSAC_OUTPUTS without the per-hypothesis scores: status_h / status_f [B] u8
+        PERSPECTIVE_*, choice [B] u8 PERSPECTIVE_CHOICE_*, H_21 / F_21 [B, 3, 3] f64, the scores, rel_score_h, and the inlier masks per key point
+        of frame 1 (inliers: the chosen solver's).  Nothing is synchronised."""
+        torch = self.torch
+        st = stream or torch.cuda.current_stream(self.dev)
+        B, n_cap = match.shape
+        kp_bytes = self.plp.KP_DTYPE.itemsize
+        m_cap = undist_2.numel() * undist_2.element_size() // (kp_bytes * B) if B else 0
+        tt = {np.uint8: torch.uint8, np.int32: torch.int32, np.float64: torch.float64, np.float32: torch.float32}
+        iters = self.num_ransac_iters
+        with torch.cuda.stream(st):
+            out = {k: torch.zeros((B,) + shape(n_cap, iters), dtype=tt[dt], device=self.dev) for k, (shape, dt, _) in self.plp.PERSPECTIVE_RANSAC_OUTPUTS.items()
+                   if not k.startswith("hyp_score")}
+        if B and n_cap:
+            self.mt.perspective_ransac_device(B, n_cap, m_cap, undist_1.contiguous(), undist_2.contiguous() if m_cap else None, match.contiguous(), out, iters=iters,
+                                              recompute=True, samples_h=samples_h, samples_f=samples_f, seed=seed, counts_1=counts_1, counts_2=counts_2,
+                                              given_H_21=given_H_21, given_H_num_inliers=given_H_num_inliers, stream=st)
+        return out
