@@ -2277,6 +2277,78 @@ int32_t plp_model_local_ba_solve_host(int32_t P, int32_t M, int32_t E, const dou
 int32_t plp_model_inv3_host(const double* a, int32_t n, double* out, int32_t* out_ok);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Local bundle adjustment with line landmarks: optimize::local_bundle_adjuster_extended_line::optimize
+ * (src/PLPSLAM/optimize/local_bundle_adjuster_extended_line.cc:70-674) for G problems at once over shared map tables -- what mapping_module runs
+ * for every new key frame when line tracking is on (mapping_module.cc:252-257).  Numeric contract: DESIGN.md section 5, D28, on top of D17 and
+ * D15: the 4-DoF line vertex in orthonormal representation (g2o/line3d.h:137-186), the binary line edge with g2o's numeric Jacobian on both
+ * vertices (g2o/se3/reproj_edge_line3d_orthonormal.h:60-88), 4 x 4 marginalised blocks beside the 3 x 3 ones, and the line half of the outlier
+ * schedule with the end-point depth test (:97-177 of the same file; :486-505, :555-573 of the adjuster).  g2o is not linked; force_stop_flag is
+ * not modelled; step [8]'s map mutation (erase_landmark_line, erase_observation, prepare_for_erasing) stays with the caller.
+ *
+ * `points` is a whole plp_local_ba_args and every field means what it means there; L and T may be 0.  The line table, LL rows, uses the
+ * observation-list layout of the landmarks: pluecker (get_PlueckerCoord(), moment then direction), line_erased (will_be_erased(), :371),
+ * obs_offsets_lines (LL + 1), obs_kf_lines, obs_idx_lines (TL entries).  keylines is the key frames' _keylsd, kl_stride slots per key-frame row
+ * (start point, end point and octave are read), kl_counts the key lines per key frame (NULL = kl_stride).
+ * Sets (:108-224): a line is local iff not erased and a local key frame is among its observations; a key frame is fixed iff it is not local, not
+ * erased and among the observations of a local landmark or a local line.  One line edge per observation of a local line by a key frame that is
+ * not erased; an observation whose obs_kf_lines is outside [0, F), whose obs_idx_lines is outside [0, kl_counts[kf]) or whose octave is outside
+ * [0, num_levels_lsd) is not an edge.  Order: key frames, landmarks, lines in table order; point edges before line edges; line edges in line
+ * order, then list order.
+ * Outputs per problem beside those of `points`; slots that are not written keep the caller's values:
+ *   out_line_role      [G][LL]: 1 = local
+ *   out_pluecker       [G][LL][6]: local lines only
+ *   out_outlier_lines  [G][TL]: step [7]'s verdict (:555-573), one byte per observation entry, edges only
+ * points.out_round_info[.][0][2] counts the point and the line edges moved to level 1 together.  A problem with neither a point nor a line edge
+ * is PLP_LOCAL_BA_NO_EDGES (out_pluecker the input's). */
+typedef struct plp_local_ba_lines_args {
+    plp_local_ba_args points;             /* every field as the point adjuster reads it; L and T may be 0 */
+    int32_t LL, TL;                       /* line landmarks, entries of their observation list; <= 2^18 each, G * TL and G * LL <= 2^22 */
+    int32_t kl_stride, num_levels_lsd;    /* key-line slots per key-frame row; 1 .. 16 */
+    const float* inv_level_sigma_sq_lsd;  /* HOST, num_levels_lsd: keyframe::_inv_level_sigma_sq_lsd */
+    const plp_keyline* keylines;          /* F x kl_stride: _keylsd; start point, end point and octave are read */
+    const int32_t* kl_counts;             /* F, or NULL = kl_stride */
+    const double* pluecker;               /* LL x 6 (m, d): get_PlueckerCoord() */
+    const uint8_t* line_erased;           /* LL, or NULL */
+    const int32_t* obs_offsets_lines;     /* LL + 1 */
+    const int32_t* obs_kf_lines;          /* TL */
+    const int32_t* obs_idx_lines;         /* TL */
+    uint8_t* out_line_role;               /* G x LL: 1 = local */
+    double* out_pluecker;                 /* G x LL x 6: local lines only */
+    uint8_t* out_outlier_lines;           /* G x TL: step [7]'s verdict, edges only */
+} plp_local_ba_lines_args;
+/* Checked before anything is written: everything the point adjuster checks of `points`, with its status codes; LL, TL or kl_stride negative,
+ * num_levels_lsd outside 1 .. 16 or a NULL lsd sigma table, and -- when G > 0 -- a NULL obs_offsets_lines, pluecker (LL > 0), obs_kf_lines,
+ * obs_idx_lines (TL > 0), keylines (F > 0 and kl_stride > 0) or a NULL required output of non-zero size: PLP_ERR_INVALID_ARG.  LL or TL > 2^18,
+ * G * TL or G * LL > 2^22: PLP_ERR_UNSUPPORTED (the context holds G (96 TL + 89 LL + 5376) more doubles than the point adjuster's state).
+ * _host and the host build also check that obs_offsets_lines rises from 0 to TL.  _device: every array but the two sigma tables a DEVICE
+ * pointer; four kernels on hip_stream (the sets and edges; one per round; the outputs), one workgroup of 512 per problem, no host
+ * synchronisation; the state lives in the context's buffers, so
+ * the calls of one context must be ordered on the device.  _host: HOST pointers, staged (the outputs too), the same kernels, synchronous. */
+plp_status plp_local_ba_lines_device(plp_matcher* ctx, const plp_local_ba_lines_args* args, void* hip_stream);
+plp_status plp_local_ba_lines_host(plp_matcher* ctx, const plp_local_ba_lines_args* args);
+/* Host builds of the same source (csrc/local_ba_lines.hpp), HOST pointers, no GPU and no context needed.
+ * plp_model_local_ba_lines_host: the entry above with a team of one lane; the same checks.  Returns G, or the negated plp_status.
+ * plp_model_line_oplus_host: Line3D::oplus for n lines: line n x 6, update n x 4 (the quaternion's vector part, the angle), out n x 6.  Returns n or -1.
+ * plp_model_local_ba_lines_linearize_host: one linearisation of problem 0 (G must be 1) at the inputs' estimates with every edge at level 0; the
+ * output pointers of `args` are neither read nor checked.  out_free_kf [64], out_hpp [64][27], out_hll [L][9], out_chi2 [1] as the point
+ * adjuster's linearize build gives them, the sums running over the line edges too; out_hnn [LL][14]: every active line's H (upper triangle
+ * row-major, 10) and b (4); out_w_lines [TL][24]: H_pl of every line edge with an active free pose, 6 x 4 row-major; out_edge_chi2_lines [TL].
+ * Slots without a value keep the caller's; any may be NULL.  Returns the number of active free poses, or the negated status.
+ * plp_model_local_ba_lines_solve_host: one damped Schur solve from given blocks with mixed 3- and 4-blocks: P <= 64 poses (hpp P x 27),
+ * M landmarks (hll M x 9), N lines (hnn N x 14), E3 point edges in landmark order (e_pose, e_lm, w E3 x 18) and E4 line edges in line order
+ * (e_pose_lines, e_line, w_lines E4 x 24); -1 in e_pose / e_pose_lines is a constant pose.  out_xp P x 6, out_xl M x 3, out_xn N x 4; returns
+ * 1 = solved, 0 = a pivot or an inverse failed (every x is then 0), -1 = a bad argument. */
+int32_t plp_model_local_ba_lines_host(const plp_local_ba_lines_args* args);
+int32_t plp_model_line_oplus_host(const double* line, const double* update, int32_t n, double* out);
+int32_t plp_model_local_ba_lines_linearize_host(const plp_local_ba_lines_args* args, int32_t robust, int32_t* out_free_kf, double* out_hpp,
+                                                double* out_hll, double* out_hnn, double* out_w_lines, double* out_chi2,
+                                                double* out_edge_chi2_lines);
+int32_t plp_model_local_ba_lines_solve_host(int32_t P, int32_t M, int32_t N, int32_t E3, int32_t E4, const double* hpp, const double* hll,
+                                            const double* hnn, const int32_t* e_pose, const int32_t* e_lm, const double* w,
+                                            const int32_t* e_pose_lines, const int32_t* e_line, const double* w_lines, double lambda,
+                                            double* out_xp, double* out_xl, double* out_xn);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Global bundle adjustment: optimize::global_bundle_adjuster::optimize (src/PLPSLAM/optimize/global_bundle_adjuster.cc:64-311) over the whole
  * point map -- what module::loop_bundle_adjuster::optimize runs after a loop closure (Huber off) and module::initializer on its first two key
  * frames (Huber on) -- and the array half of the loop adjuster's map update (module/loop_bundle_adjuster.cc:109-181).  Numeric contract:

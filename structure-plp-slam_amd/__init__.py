@@ -1014,6 +1014,128 @@ class local_bundle_adjuster:
         return {k: v[0] for k, v in r.items()}
 
 
+# the outputs plp_local_ba_lines_* adds to LOCAL_BA_OUTPUTS: name -> (shape per problem given (LL, TL), dtype)
+LOCAL_BA_LINES_OUTPUTS = dict(line_role=(lambda LL, TL: (LL,), np.uint8), pluecker=(lambda LL, TL: (LL, 6), np.float64), outlier_lines=(lambda LL, TL: (TL,), np.uint8))
+
+
+def _local_ba_lines_inputs(points, keylines, pluecker, obs_offsets_lines, obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, kl_counts, line_erased):
+    """the input half of a plp_local_ba_lines_args: `points` the keywords of _local_ba_inputs; (args struct, the arrays it points to, G, F, L, T, LL, TL)"""
+    pa, keep, G, F, L, T = _local_ba_inputs(**points)
+    kl = np.ascontiguousarray(keylines, KL_DTYPE)
+    kl = kl.reshape(F, -1) if F else kl.reshape(0, 0)
+    pk = np.ascontiguousarray(pluecker, np.float64).reshape(-1, 6)
+    LL = len(pk)
+    oo = np.ascontiguousarray(obs_offsets_lines, np.int32).reshape(-1); ok = np.ascontiguousarray(obs_kf_lines, np.int32).reshape(-1)
+    oi = np.ascontiguousarray(obs_idx_lines, np.int32).reshape(-1)
+    if len(oo) != LL + 1 or len(ok) != len(oi):
+        raise PlpError(PLP_ERR_INVALID_ARG, "obs_offsets_lines must have LL + 1 entries, obs_kf_lines and obs_idx_lines one length")
+    TL = len(ok)
+    kc = None if kl_counts is None else np.ascontiguousarray(kl_counts, np.int32).reshape(F)
+    le = None if line_erased is None else np.ascontiguousarray(line_erased, np.uint8).reshape(LL)
+    sg = np.ascontiguousarray(inv_level_sigma_sq_lsd, np.float32).reshape(-1)
+    a = _struct(local_ba_lines_args_c, dict(LL=LL, TL=TL, kl_stride=int(kl.shape[1]), num_levels_lsd=len(sg)), host_ptrs(
+        inv_level_sigma_sq_lsd=sg, keylines=kl, kl_counts=kc, pluecker=pk, line_erased=le, obs_offsets_lines=oo, obs_kf_lines=ok, obs_idx_lines=oi))
+    a.points = pa
+    return a, (keep, kl, pk, oo, ok, oi, kc, le, sg), G, F, L, T, LL, TL
+
+
+def _local_ba_lines_host(call, inputs, outputs, out):
+    """the numpy side of plp_local_ba_lines_host and plp_model_local_ba_lines_host: call(args struct) runs the entry"""
+    a, keep, G, F, L, T, LL, TL = _local_ba_lines_inputs(**inputs)
+    o = out_arrays([(k, (G,) + shape(F, L, T), dt) for k, (shape, dt, optional) in LOCAL_BA_OUTPUTS.items() if wanted(k, optional, outputs)] +
+                   [(k, (G,) + shape(LL, TL), dt) for k, (shape, dt) in LOCAL_BA_LINES_OUTPUTS.items()], out)
+    set_outputs(a.points, LOCAL_BA_OUTPUTS, o, host_ptr)
+    set_outputs(a, LOCAL_BA_LINES_OUTPUTS, o, host_ptr)
+    call(a)
+    return o
+
+
+def _local_ba_lines_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker, obs_offsets_lines,
+                       obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, x_right, counts, kf_erased, kf_is_origin, lm_erased, kl_counts, line_erased,
+                       num_first_iter, num_second_iter):
+    return dict(points=_local_ba_kw(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, x_right, counts, kf_erased,
+                                    kf_is_origin, lm_erased, num_first_iter, num_second_iter),
+                keylines=keylines, pluecker=pluecker, obs_offsets_lines=obs_offsets_lines, obs_kf_lines=obs_kf_lines, obs_idx_lines=obs_idx_lines,
+                inv_level_sigma_sq_lsd=inv_level_sigma_sq_lsd, kl_counts=kl_counts, line_erased=line_erased)
+
+
+def _model_lines_call(a):
+    r = lib().plp_model_local_ba_lines_host(C.byref(a))
+    if r != a.points.G:
+        raise PlpError(-r, lib().plp_last_error().decode())
+
+
+def model_local_ba_lines(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker, obs_offsets_lines,
+                         obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, x_right=None, counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None,
+                         kl_counts=None, line_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
+    """Host build of optimize::local_bundle_adjuster_extended_line::optimize (csrc/local_ba_lines.hpp, DESIGN.md section 5, D28; no GPU needed): the
+    arguments and the result of matcher.local_ba_lines."""
+    return _local_ba_lines_host(_model_lines_call, _local_ba_lines_kw(
+        camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker, obs_offsets_lines, obs_kf_lines,
+        obs_idx_lines, inv_level_sigma_sq_lsd, x_right, counts, kf_erased, kf_is_origin, lm_erased, kl_counts, line_erased, num_first_iter, num_second_iter),
+        outputs, out)
+
+
+def model_line_oplus(line, update):
+    """Host build of D28's Line3D::oplus (no GPU needed): line (n, 6) Pluecker (m, d), update (n, 4).  Returns (n, 6)."""
+    ln = np.ascontiguousarray(line, np.float64).reshape(-1, 6); up = np.ascontiguousarray(update, np.float64).reshape(-1, 4)
+    o = np.zeros_like(ln)
+    if len(ln) != len(up) or lib().plp_model_line_oplus_host(_p(ln), _p(up), len(ln), _p(o)) != len(ln):
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_line_oplus_host")
+    return o
+
+
+def model_local_ba_lines_linearize(robust=True, **kw):
+    """Host build of one linearisation of D28 at the inputs' estimates, every edge at level 0 (no GPU needed); the keywords of model_local_ba_lines with
+    kf_local (F,) or (1, F).  Returns model_local_ba_linearize's dict without W and edge_chi2, and Hnn (LL, 10) upper triangle row-major, bn (LL, 4), NaN for
+    a line without an edge, W_lines (TL, 6, 4) NaN where the edge has no active free pose, edge_chi2_lines (TL,) NaN where no edge."""
+    full = dict(x_right=None, counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None, kl_counts=None, line_erased=None, num_first_iter=1, num_second_iter=1)
+    full.update(kw)
+    a, keep, G, F, L, T, LL, TL = _local_ba_lines_inputs(**_local_ba_lines_kw(**full))
+    fk = np.full(LOCAL_BA_MAX_FREE, -1, np.int32); hpp = np.full((LOCAL_BA_MAX_FREE, 27), np.nan); hll = np.full((L, 9), np.nan); hnn = np.full((LL, 14), np.nan)
+    w = np.full((TL, 24), np.nan); chi = np.zeros(1); ec = np.full(TL, np.nan)
+    r = lib().plp_model_local_ba_lines_linearize_host(C.byref(a), int(bool(robust)), *map(host_ptr, (fk, hpp, hll, hnn, w, chi, ec)))
+    if r < 0:
+        raise PlpError(-r, lib().plp_last_error().decode())
+    return dict(free_kf=fk[:r].copy(), Hpp=hpp[:r, :21].copy(), bp=hpp[:r, 21:].copy(), Hll=hll[:, :6].copy(), bl=hll[:, 6:].copy(), Hnn=hnn[:, :10].copy(),
+                bn=hnn[:, 10:].copy(), W_lines=w.reshape(TL, 6, 4), chi2=float(chi[0]), edge_chi2_lines=ec)
+
+
+def model_local_ba_lines_solve(Hpp, bp, Hll, bl, Hnn, bn, e_pose, e_lm, W, e_pose_lines, e_line, W_lines, lam):
+    """Host build of one damped Schur solve of D28 with mixed 3- and 4-blocks (no GPU needed): model_local_ba_solve's arguments, and Hnn (N, 10), bn (N, 4),
+    the line edges in line order with e_pose_lines (-1: a constant pose), e_line and W_lines (E4, 6, 4).  Returns (x_p (P, 6), x_l (M, 3), x_n (N, 4), ok)."""
+    hp = np.concatenate([np.asarray(Hpp, np.float64).reshape(-1, 21), np.asarray(bp, np.float64).reshape(-1, 6)], axis=1).copy()
+    hl = np.concatenate([np.asarray(Hll, np.float64).reshape(-1, 6), np.asarray(bl, np.float64).reshape(-1, 3)], axis=1).copy()
+    hn = np.concatenate([np.asarray(Hnn, np.float64).reshape(-1, 10), np.asarray(bn, np.float64).reshape(-1, 4)], axis=1).copy()
+    ep = np.ascontiguousarray(e_pose, np.int32).reshape(-1); el = np.ascontiguousarray(e_lm, np.int32).reshape(-1)
+    eq = np.ascontiguousarray(e_pose_lines, np.int32).reshape(-1); en = np.ascontiguousarray(e_line, np.int32).reshape(-1)
+    w = np.ascontiguousarray(W, np.float64).reshape(len(ep), 18); wn = np.ascontiguousarray(W_lines, np.float64).reshape(len(eq), 24)
+    xp = np.zeros((len(hp), 6)); xl = np.zeros((len(hl), 3)); xn = np.zeros((len(hn), 4))
+    r = lib().plp_model_local_ba_lines_solve_host(len(hp), len(hl), len(hn), len(ep), len(eq), *map(host_ptr, (hp, hl, hn, ep, el, w, eq, en, wn)), float(lam),
+                                                  *map(host_ptr, (xp, xl, xn)))
+    if r < 0:
+        raise PlpError(PLP_ERR_INVALID_ARG, "plp_model_local_ba_lines_solve_host")
+    return xp, xl, xn, bool(r)
+
+
+class local_bundle_adjuster_extended_line:
+    """Mirror of optimize::local_bundle_adjuster_extended_line (optimize/local_bundle_adjuster_extended_line.h): optimize() takes the map tables with the
+    line tables and one problem's kf_local and returns that problem's result dict; mt: a matcher (the GPU entry), or None = the host build."""
+
+    def __init__(self, num_first_iter=5, num_second_iter=10, mt=None):
+        self.num_first_iter, self.num_second_iter, self._mt = int(num_first_iter), int(num_second_iter), mt
+
+    def optimize(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker, obs_offsets_lines,
+                 obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, **optional):
+        """kf_local (F,).  Returns local_bundle_adjuster.optimize's dict and line_role (LL,), pluecker (LL, 6), outlier_lines (TL,); rows the adjuster does not
+        write are zero.  optional: x_right, counts, kf_erased, kf_is_origin, lm_erased, kl_counts, line_erased."""
+        fn = model_local_ba_lines if self._mt is None else self._mt.local_ba_lines
+        r = fn(camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, np.asarray(kf_local, np.uint8).reshape(1, -1), inv_level_sigma_sq, keylines,
+               pluecker, obs_offsets_lines, obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, num_first_iter=self.num_first_iter,
+               num_second_iter=self.num_second_iter, **optional)
+        return {k: v[0] for k, v in r.items()}
+
+
 # the outputs of plp_pose_graph_optimize_*: name -> (shape per problem given (F, edge_cap), dtype, optional)
 POSE_GRAPH_OUTPUTS = dict(status=(lambda F, E: (), np.uint8, False), num_edges=(lambda F, E: (), np.int32, True), edges=(lambda F, E: (E, 3), np.int32, True),
                           sim3_cw=(lambda F, E: (F, 8), np.float64, True), corrected_wc=(lambda F, E: (F, 8), np.float64, True),
@@ -2990,6 +3112,40 @@ class matcher(line_update_entries):
         set_outputs(a, LOCAL_BA_OUTPUTS, out, dev_ptr)
         a.camera = camera_model_c.from_buffer_copy(camera)
         self._device("plp_local_ba_device", a, stream)
+
+    def local_ba_lines(self, camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker,
+                       obs_offsets_lines, obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, x_right=None, counts=None, kf_erased=None, kf_is_origin=None,
+                       lm_erased=None, kl_counts=None, line_erased=None, num_first_iter=5, num_second_iter=10, outputs=None, out=None):
+        """optimize::local_bundle_adjuster_extended_line::optimize for G problems over shared map tables (plp_local_ba_lines_host; DESIGN.md section 5, D28):
+        local_ba's arguments, and keylines (F, kl_stride) KL_DTYPE, pluecker (LL, 6), the lines' observation lists obs_offsets_lines (LL + 1,), obs_kf_lines /
+        obs_idx_lines (TL,), the lsd sigma table, kl_counts (F,) and line_erased (LL,) or None.  Returns local_ba's dict and line_role (G, LL), pluecker
+        (G, LL, 6), outlier_lines (G, TL)."""
+        return _local_ba_lines_host(self._host("plp_local_ba_lines_host"), _local_ba_lines_kw(
+            camera, setup_type, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq, keylines, pluecker, obs_offsets_lines, obs_kf_lines,
+            obs_idx_lines, inv_level_sigma_sq_lsd, x_right, counts, kf_erased, kf_is_origin, lm_erased, kl_counts, line_erased, num_first_iter, num_second_iter),
+            outputs, out)
+
+    def local_ba_lines_device(self, camera, setup_type, G, F, L, T, kp_stride, pose, undist, pos_w, obs_offsets, obs_kf, obs_idx, kf_local, inv_level_sigma_sq,
+                              LL, TL, kl_stride, keylines, pluecker, obs_offsets_lines, obs_kf_lines, obs_idx_lines, inv_level_sigma_sq_lsd, out, x_right=None,
+                              counts=None, kf_erased=None, kf_is_origin=None, lm_erased=None, kl_counts=None, line_erased=None, pose_stride=15, num_first_iter=5,
+                              num_second_iter=10, stream=None):
+        """plp_local_ba_lines_device: every array a device pointer (int) or a torch tensor on the matcher's device (the two sigma tables are host vectors);
+        out: dict of the device outputs named as in LOCAL_BA_OUTPUTS and LOCAL_BA_LINES_OUTPUTS (round_info / round_chi2 may be absent); asynchronous,
+        four kernels on the stream"""
+        sg = np.ascontiguousarray(inv_level_sigma_sq, np.float32).reshape(-1)             # live until the call has returned
+        sl = np.ascontiguousarray(inv_level_sigma_sq_lsd, np.float32).reshape(-1)
+        pa = _struct(local_ba_args_c, dict(setup_type=int(setup_type), num_first_iter=int(num_first_iter), num_second_iter=int(num_second_iter), G=int(G), F=int(F),
+                                           L=int(L), T=int(T), kp_stride=int(kp_stride), pose_stride=int(pose_stride), num_levels=len(sg)), dict(
+            dev_ptrs(pose=pose, kf_erased=kf_erased, kf_is_origin=kf_is_origin, undist=undist, x_right=x_right, counts=counts, pos_w=pos_w,
+                     lm_erased=lm_erased, obs_offsets=obs_offsets, obs_kf=obs_kf, obs_idx=obs_idx, kf_local=kf_local), inv_level_sigma_sq=host_ptr(sg)))
+        set_outputs(pa, LOCAL_BA_OUTPUTS, out, dev_ptr)
+        pa.camera = camera_model_c.from_buffer_copy(camera)
+        a = _struct(local_ba_lines_args_c, dict(LL=int(LL), TL=int(TL), kl_stride=int(kl_stride), num_levels_lsd=len(sl)), dict(
+            dev_ptrs(keylines=keylines, kl_counts=kl_counts, pluecker=pluecker, line_erased=line_erased, obs_offsets_lines=obs_offsets_lines,
+                     obs_kf_lines=obs_kf_lines, obs_idx_lines=obs_idx_lines), inv_level_sigma_sq_lsd=host_ptr(sl)))
+        a.points = pa
+        set_outputs(a, LOCAL_BA_LINES_OUTPUTS, out, dev_ptr)
+        self._device("plp_local_ba_lines_device", a, stream)
 
     def pose_graph_optimize(self, tables, problems, edge_cap=POSE_GRAPH_MAX_EDGES, env_cap=POSE_GRAPH_MAX_ENV, max_iter=50, outputs=None, out=None):
         """optimize::graph_optimizer::optimize for G problems over one key-frame table (plp_pose_graph_optimize_host; DESIGN.md section 5, D22): tables a dict of

@@ -260,6 +260,13 @@ class local_ba_args_c(C.Structure):
                 ("out_round_chi2", _VP)]
 
 
+class local_ba_lines_args_c(C.Structure):
+    """plp_local_ba_lines_args"""
+    _fields_ = [("points", local_ba_args_c), ("LL", C.c_int32), ("TL", C.c_int32), ("kl_stride", C.c_int32), ("num_levels_lsd", C.c_int32)] + [(k, _VP) for k in (
+        "inv_level_sigma_sq_lsd", "keylines", "kl_counts", "pluecker", "line_erased", "obs_offsets_lines", "obs_kf_lines", "obs_idx_lines", "out_line_role",
+        "out_pluecker", "out_outlier_lines")]
+
+
 class global_ba_args_c(C.Structure):
     """plp_global_ba_args"""
     _fields_ = [("camera", camera_model_c), ("setup_type", C.c_int32), ("num_iter", C.c_int32), ("use_huber_kernel", C.c_int32), ("F", C.c_int32), ("L", C.c_int32),

@@ -193,6 +193,12 @@ _API = [
     ("plp_model_local_ba_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("plp_model_local_ba_solve_host", _I32, [_I32, _I32, _I32, _VP, _VP, _VP, _VP, _VP, C.c_double, _VP, _VP]),
     ("plp_model_inv3_host", _I32, [_VP, _I32, _VP, _VP]),
+    ("plp_local_ba_lines_device", C.c_int, [_VP, _VP, _VP]),
+    ("plp_local_ba_lines_host", C.c_int, [_VP, _VP]),
+    ("plp_model_local_ba_lines_host", _I32, [_VP]),
+    ("plp_model_line_oplus_host", _I32, [_VP, _VP, _I32, _VP]),
+    ("plp_model_local_ba_lines_linearize_host", _I32, [_VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("plp_model_local_ba_lines_solve_host", _I32, [_I32] * 5 + [_VP] * 9 + [C.c_double, _VP, _VP, _VP]),
     ("plp_lbd_match_1nn_host", C.c_int, [_VP, _VP, _I32, _VP, _I32, _VP, _VP]),
     ("plp_lbd_match_1nn_device", C.c_int, [_VP, _VP, _VP, _I32, _VP, _VP, _I32, _I32, _VP, _VP, _VP]),
     ("plp_stereo_compute", C.c_int, [_VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, C.c_float, C.c_float, _VP, _VP]),

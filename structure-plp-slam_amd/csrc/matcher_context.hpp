@@ -1,5 +1,5 @@
 // The matcher context (plp_matcher of include/plp_front.h) and what the files that implement its entry points share: match_context.hip and one
-// *_context.hip per solver (sim3, pnp, essential, two_view, perspective_init, pose_opt, transform_opt, local_ba, local_map, plane, plane_refinement, map_cull,
+// *_context.hip per solver (sim3, pnp, essential, two_view, perspective_init, pose_opt, transform_opt, local_ba, local_ba_lines, local_map, plane, plane_refinement, map_cull,
 // covisibility, pose_graph, global_ba, line_update).
 #pragma once
 #include <hip/hip_runtime.h>
