@@ -4,6 +4,10 @@
 // the reduced system and the two rounds; g2o's Levenberg-Marquardt accept / reject step and end rule are levenberg.hpp's.  f64 with IEEE
 // + - * / sqrt only, in the order written; translation units that include this file are compiled with -ffp-contract=off.
 //
+// The active sets, the damped solve and the round (la_round_setup, la_solve_system, la_round) are the only ones of both local adjusters: they
+// take an extension `X` for a second kind of marginalised vertex and call it at the places where its half of a step stands, always behind the
+// landmarks' half.  LaNoLines, the extension of this adjuster, is empty; local_ba_lines.hpp's LlLines (D28) holds the line vertices.
+//
 // The steps are written once over a team `P` of lanes (P::NT lanes in waves of P::WS): the kernels run them with a workgroup of 512, the host
 // build with a team of one, for which every barrier is empty and every strided loop is the plain loop.  No sum depends on the team's size: each
 // coefficient is owned by one lane that adds its terms in the defined order.  All state between the steps lives in memory the caller names (a
@@ -136,6 +140,40 @@ __host__ __device__ __forceinline__ bool la_inv3(const double* a, double* o) {
     return ok;
 }
 
+// the verdict of :305-331 and of step [7] on point edge t at the estimates of buffer (kc, lc): its chi-square bound below the chi2 of its last
+// evaluation, or a depth that is not positive (NaN fails)
+__host__ __device__ __forceinline__ bool la_point_bad(const LaView& V, int t, int kc, int lc) {
+    const int kf = V.e_kf()[t], l = V.e_l()[t];
+    double est[7], p[3], x, y, z;
+    _Pragma("unroll") for (int i = 0; i < 7; ++i) est[i] = la_k(V, kf, kc + i);
+    _Pragma("unroll") for (int i = 0; i < 3; ++i) p[i] = la_l(V, l, lc + i);
+    pose_map(est, p, x, y, z);
+    const double thr = (double)(la_e(V, t, kLaRowObs + 2) < 0.0 ? kPoseChiSq2D : kPoseChiSq3D);
+    return thr < la_e(V, t, kLaRowChi) || !(0.0 < z);
+}
+
+// the extension of an adjuster without a second kind of marginalised vertex: every half of a step is empty.  The members are the places where
+// la_round_setup, la_solve_system and la_round call an extension (LlLines of local_ba_lines.hpp says what each one does).
+struct LaNoLines {
+    __host__ __device__ __forceinline__ bool any_active() const { return false; }
+    __host__ __device__ __forceinline__ int cnt(int) const { return 0; }
+    __host__ __device__ __forceinline__ void rank(int, int) const {}
+    template <class P> __host__ __device__ __forceinline__ void count(const LaView&, P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void place(P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void active(P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void inverse(P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void y(P&) const {}
+    __host__ __device__ __forceinline__ void schur(const LaView&, int, int, int) const {}
+    template <class P> __host__ __device__ __forceinline__ void x(P&, bool) const {}
+    template <class P> __host__ __device__ __forceinline__ void perturb(const LaView&, P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void edge_pass(const LaView&, P&, bool, bool) const {}
+    template <class P> __host__ __device__ __forceinline__ void sums(const LaView&, P&, bool) const {}
+    template <class P> __host__ __device__ __forceinline__ void chain(P&, int) const {}
+    template <class P> __host__ __device__ __forceinline__ void scale_parts(P&) const {}
+    template <class P> __host__ __device__ __forceinline__ void update(P&) const {}
+    template <class P> __host__ __device__ __forceinline__ int level1(const LaView&, P&, int) const { return 0; }
+};
+
 // the observations of landmark l: [lo, hi) of the observation list, cut to the list
 template <class AA> __host__ __device__ __forceinline__ void la_run(const AA& A, int l, int& lo, int& hi) {
     lo = A.obs_offsets[l]; hi = A.obs_offsets[l + 1];
@@ -235,8 +273,8 @@ template <class P> __host__ __device__ __forceinline__ void la_prepare(const LaA
 }
 
 // ---- the active sets of a round (initializeOptimization at level 0): the free key frames and landmarks with a level-0 edge, the list of every
-// active pose's edges in edge order
-template <class P, class AA> __host__ __device__ __forceinline__ void la_round_setup(const AA& A, const LaView& V, LaShared& sh, P& par) {
+// active pose's edges in edge order.  The extension's edges count into a pose's activity; its lists and its active vertices are its own.
+template <class P, class AA, class X> __host__ __device__ __forceinline__ void la_round_setup(const AA& A, const LaView& V, LaShared& sh, P& par, X& ext) {
     const int tid = par.tid(), F = A.F, L = A.L, T = A.T, nf = V.hdr()[kLaHNf];
     for (int q = par.wave(); q < nf; q += P::NW) {
         const int kf = V.hdr()[kLaHFl + q];
@@ -248,15 +286,17 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_round_s
         }
         if (par.lane() == 0) sh.cnt[q] = c;
     }
+    ext.count(V, par);
     for (int f = tid; f < F; f += P::NT) sh.kf2ai[f] = -1;
     if (tid == 0) sh.nla = 0;
     par.barrier();
     if (tid == 0) {
         int a = 0, o = 0;
         for (int q = 0; q < nf; ++q)
-            if (sh.cnt[q] > 0) {
+            if (sh.cnt[q] + ext.cnt(q) > 0) {
                 const int kf = V.hdr()[kLaHFl + q];
                 sh.kf2ai[kf] = (int16_t)a; sh.akf[a] = kf; sh.aoff[a] = o; sh.acnt[a] = sh.cnt[q];
+                ext.rank(a, q);
                 o += sh.cnt[q]; ++a;
             }
         sh.nfa = a;
@@ -273,6 +313,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_round_s
             pos += (int)__builtin_popcountll(m);
         }
     }
+    ext.place(par);
     for (int l = tid; l < L; l += P::NT) {
         bool act = false;
         if (V.lm_role()[l]) {
@@ -283,6 +324,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_round_s
         V.lm_act()[l] = act ? 1 : 0;
         if (act) sh.nla = 1;
     }
+    ext.active(par);
     par.barrier_g();
 }
 
@@ -406,25 +448,17 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_sums(co
     par.barrier_g();
 }
 
-// one chain over the active landmarks in table order, from sh.acc: mode 0 adds row `row` of the landmark table, mode 1 takes the largest
-// |diagonal| of the landmark blocks.  The result is in sh.acc after the closing barrier.
-template <class P, class AA> __host__ __device__ __forceinline__ void la_chain(const AA& A, const LaView& V, LaShared& sh, P& par, int mode, int row) {
-    const int L = A.L, tid = par.tid();
-    for (int base = 0; base < L; base += P::NT) {
+// one chain over the n vertices of a table in table order, going on from sh.acc: every lane puts val(l) of its vertex (0 for one that is not
+// active) into the tile, lane 0 adds the tile in order (mode 0) or takes its largest value (mode 1).  The result is in sh.acc after the closing
+// barrier.
+template <class P, class Val> __host__ __device__ __forceinline__ void la_chain_over(int n, LaShared& sh, P& par, int mode, Val val) {
+    const int tid = par.tid();
+    for (int base = 0; base < n; base += P::NT) {
         const int l = base + tid;
-        double v = 0.0;
-        if (l < L && V.lm_act()[l]) {
-            if (mode == 0) v = la_l(V, l, row);
-            else
-                _Pragma("unroll") for (int i = 0; i < 3; ++i) {
-                    const double d = __builtin_fabs(la_l(V, l, kLaLmH + (i == 0 ? 0 : i == 1 ? 3 : 5)));
-                    v = d > v ? d : v;
-                }
-        }
-        sh.tile[tid] = v;
+        sh.tile[tid] = l < n ? val(l) : 0.0;
         par.barrier();
         if (tid == 0) {
-            const int cnt = L - base < P::NT ? L - base : P::NT;
+            const int cnt = n - base < P::NT ? n - base : P::NT;
             double acc = sh.acc;
             if (mode == 0) for (int i = 0; i < cnt; ++i) acc = acc + sh.tile[i];
             else for (int i = 0; i < cnt; ++i) acc = sh.tile[i] > acc ? sh.tile[i] : acc;
@@ -433,10 +467,26 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_chain(c
         par.barrier();
     }
 }
+// the chain over the active landmarks: mode 0 adds row `row` of the landmark table, mode 1 takes the largest |diagonal| of the landmark blocks
+template <class P, class AA> __host__ __device__ __forceinline__ void la_chain(const AA& A, const LaView& V, LaShared& sh, P& par, int mode, int row) {
+    la_chain_over(A.L, sh, par, mode, [&V, mode, row](int l) {
+        double v = 0.0;
+        if (V.lm_act()[l]) {
+            if (mode == 0) v = la_l(V, l, row);
+            else
+                _Pragma("unroll") for (int i = 0; i < 3; ++i) {
+                    const double d = __builtin_fabs(la_l(V, l, kLaLmH + (i == 0 ? 0 : i == 1 ? 3 : 5)));
+                    v = d > v ? d : v;
+                }
+        }
+        return v;
+    });
+}
 
 // ---- one damped solve (BlockSolver<6,3>::solve): lambda on every diagonal, Hll^-1 closed, the Schur complement in the defined order, the
 // Cholesky of the reduced system column by column, x_l = Hll^-1 (b_l - W^T x_p).  sh.ok = 0: a pivot or an inverse failed, every x is then zero.
-template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_system(const AA& A, const LaView& V, LaShared& sh, P& par) {
+// The extension's inverse, its Y, its subtractions and its x stand behind the landmarks'.
+template <class P, class AA, class X> __host__ __device__ __forceinline__ void la_solve_system(const AA& A, const LaView& V, LaShared& sh, P& par, X& ext) {
     const int L = A.L, T = A.T, tid = par.tid(), nfa = sh.nfa, n = 6 * nfa;
     const double lambda = sh.lambda;
     if (tid == 0) sh.ok = 1;
@@ -449,6 +499,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
         if (!la_inv3(a, o)) sh.ok = 0;
         _Pragma("unroll") for (int i = 0; i < 6; ++i) la_l(V, l, kLaLmInv + i) = o[i];
     }
+    ext.inverse(par);
     for (int it = tid; it < n * n; it += P::NT) {
         const int p = it / n, q = it % n;
         double v = 0.0;
@@ -473,9 +524,10 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
             la_e(V, t, kLaRowY + 3 * r + 2) = (w0 * h[2] + w1 * h[4]) + w2 * h[5];
         }
     }
+    ext.y(par);
     par.barrier_g();
     // the Schur complement: coefficient (r, c) of every block (i, j >= i) belongs to item (i, r, c), which walks pose i's edges in edge order and
-    // for each the level-0 edges of its landmark in list order; item (i, r, 6) owns the right-hand side
+    // for each the level-0 edges of its landmark in list order, then the extension's edges of pose i likewise; item (i, r, 6) owns the right-hand side
     for (int it = tid; it < 42 * nfa; it += P::NT) {
         const int i = it / 42, r = (it % 42) / 7, c = it % 7;
         const int32_t* list = V.byp() + sh.aoff[i];
@@ -498,6 +550,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
                 *s = *s - ((y0 * la_e(V, tb, kLaRowW + 3 * c) + y1 * la_e(V, tb, kLaRowW + 3 * c + 1)) + y2 * la_e(V, tb, kLaRowW + 3 * c + 2));
             }
         }
+        ext.schur(V, i, r, c);
     }
     par.barrier_g();
     // Cholesky, one column and one barrier per step: row p of the factor is lane p's; L(p, k) takes the place of S(k, p).  After a failed pivot
@@ -565,6 +618,7 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_solve_s
         }
         _Pragma("unroll") for (int i = 0; i < 3; ++i) la_l(V, l, kLaLmX + i) = t3[i];
     }
+    ext.x(par, ok);
     par.barrier_g();
 }
 
@@ -621,7 +675,103 @@ template <class P, class AA> __host__ __device__ __forceinline__ void la_scale(c
     la_chain(A, V, sh, par, 0, kLaLmPart);
 }
 
-// ---- both rounds of one problem (:286-335).  One body serves the linearisation and the evaluation of a tried step, chosen at run time.
+// ---- one round of one problem (:286-335; with lines, local_bundle_adjuster_extended_line.cc:434-510): the active sets, the Levenberg-Marquardt
+// loop and the round's record in the problem's header.  One body serves the linearisation and the evaluation of a tried step, chosen at run
+// time.  Round 0 runs with the Huber kernels and ends with the edges that go to level 1; `round` is a literal or a loop counter of the caller.
+template <class P, class AA, class X>
+__host__ __device__ __forceinline__ void la_round(const AA& D, const LaView& V, LaShared& sh, P& par, X& ext, int round, const int& iters) {
+    const int tid = par.tid();
+    const bool robust = round == 0;
+    la_round_setup(D, V, sh, par, ext);
+    if (tid == 0) { sh.iterations = 0; sh.rejected = 0; sh.end = 0; sh.drops = 0; }
+    par.barrier();
+    int it = 0;
+    bool lin = true;
+    while (sh.nla || ext.any_active()) {
+        if (!lin) {
+            la_solve_system(D, V, sh, par, ext);
+            la_update(D, V, sh, par);
+            ext.update(par);
+        } else {
+            ext.perturb(V, par);
+        }
+        la_edge_pass(D, V, sh, par, lin, robust);
+        ext.edge_pass(V, par, lin, robust);
+        la_sums(D, V, sh, par, lin);
+        ext.sums(V, par, lin);
+        if (tid == 0) sh.acc = 0.0;
+        par.barrier();
+        la_chain(D, V, sh, par, 0, kLaLmPart);
+        ext.chain(par, 0);
+        if (lin) {
+            if (tid == 0) {
+                sh.current_chi = sh.acc;
+                double m = 0.0;                              // computeLambdaInit over every active vertex, at iteration 0
+                for (int a = 0; a < sh.nfa; ++a)
+                    _Pragma("unroll") for (int j = 0; j < 6; ++j) {
+                        const double d = __builtin_fabs(la_p(V, a, lev_h_index<6>(j, j)));
+                        m = d > m ? d : m;
+                    }
+                sh.acc = m;
+            }
+            par.barrier();
+            if (it == 0) {
+                la_chain(D, V, sh, par, 1, 0);
+                ext.chain(par, 1);
+                if (tid == 0) { sh.lambda = 1e-5 * sh.acc; sh.ni = 2.0; }
+            }
+            if (tid == 0) { sh.qmax = 0; sh.rho = 0.0; }
+            par.barrier();
+            lin = false;
+            continue;
+        }
+        const double temp_sum = sh.acc;
+        par.barrier();
+        ext.scale_parts(par);
+        la_scale(D, V, sh, par);
+        ext.chain(par, 0);
+        if (tid == 0) {
+            lev_decide(sh, sh.ok != 0, temp_sum, sh.acc, [&sh] { sh.cur = 1 - sh.cur; }, [] {});   // kept: the tried estimates become the kept ones
+            if (!sh.go_on) {
+                sh.iterations += 1;
+                sh.end = lev_end(sh);
+            }
+        }
+        par.barrier();
+        if (sh.go_on) continue;
+        ++it;
+        if (sh.end || it >= iters) break;
+        lin = true;
+    }
+    if (round == 0) {                                        // :305-331: the edges that go to level 1, both kinds counted together
+        const int T = D.T, kc = 7 * sh.cur, lc = 3 * sh.cur;
+        int drops = 0;
+        for (int t = tid; t < T; t += P::NT) {
+            if (V.e_kf()[t] < 0) continue;
+            const bool bad = la_point_bad(V, t, kc, lc);
+            V.lvl()[t] = bad ? 1 : 0;
+            drops += bad ? 1 : 0;
+        }
+        drops += ext.level1(V, par, kc);
+        if (drops) par.add(sh.drops, drops);
+    }
+    par.barrier_g();
+    if (tid == 0) {
+        int32_t* ri = V.hdr() + kLaHInfo + 4 * round;
+        ri[0] = sh.iterations; ri[1] = sh.rejected; ri[2] = sh.drops; ri[3] = sh.end ? sh.end : sh.iterations ? kLevEndIterations : 0;
+        V.hd()[2 * round] = sh.current_chi; V.hd()[2 * round + 1] = sh.lambda;
+        V.hdr()[kLaHCur] = sh.cur;
+    }
+}
+
+// what a round reads of the camera and the Huber delta, into the shared state (lane 0)
+__host__ __device__ __forceinline__ void la_round_consts(const LaArgs& A, LaShared& sh) {
+    sh.cam.fx = A.cam.fx; sh.cam.fy = A.cam.fy; sh.cam.cx = A.cam.cx; sh.cam.cy = A.cam.cy; sh.cam.fxb = A.cam.fxb;   // field by field: a struct copy went through the stack
+    sh.cam.k20 = A.cam.k20; sh.cam.k21 = A.cam.k21; sh.cam.k22 = A.cam.k22;
+    sh.delta = A.mono_setup ? A.delta_2d : A.delta_3d; sh.ni = 2.0;
+}
+
+// ---- both rounds of one problem in one launch
 template <class P> __host__ __device__ __forceinline__ void la_solve(const LaArgs& A, int g, LaShared& sh, P& par) {
     const int tid = par.tid();
     if (tid == 0) { la_offsets(A, g, sh.O); sh.D.F = A.F; sh.D.L = A.L; sh.D.T = A.T; }
@@ -631,92 +781,12 @@ template <class P> __host__ __device__ __forceinline__ void la_solve(const LaArg
     if (V.hdr()[kLaHStatus] != PLP_LOCAL_BA_OK) return;
     const int it1 = A.it1, it2 = A.it2;
     for (int f = tid; f < D.F; f += P::NT) sh.role[f] = V.kf_role()[f];
-    if (tid == 0) {
-        sh.cam.fx = A.cam.fx; sh.cam.fy = A.cam.fy; sh.cam.cx = A.cam.cx; sh.cam.cy = A.cam.cy; sh.cam.fxb = A.cam.fxb;   // field by field: a struct copy went through the stack
-        sh.cam.k20 = A.cam.k20; sh.cam.k21 = A.cam.k21; sh.cam.k22 = A.cam.k22;
-        sh.delta = A.mono_setup ? A.delta_2d : A.delta_3d; sh.lambda = 0.0; sh.ni = 2.0; sh.current_chi = 0.0; sh.cur = 0;
-    }
+    if (tid == 0) { la_round_consts(A, sh); sh.lambda = 0.0; sh.current_chi = 0.0; sh.cur = 0; }
     par.barrier();
+    LaNoLines none;
     for (int round = 0; round < 2; ++round) {
-        const bool robust = round == 0;
         const int iters = round == 0 ? it1 : it2;
-        la_round_setup(D, V, sh, par);
-        if (tid == 0) { sh.iterations = 0; sh.rejected = 0; sh.end = 0; sh.drops = 0; }
-        par.barrier();
-        int it = 0;
-        bool lin = true;
-        while (sh.nla) {
-            if (!lin) {
-                la_solve_system(D, V, sh, par);
-                la_update(D, V, sh, par);
-            }
-            la_edge_pass(D, V, sh, par, lin, robust);
-            la_sums(D, V, sh, par, lin);
-            if (tid == 0) sh.acc = 0.0;
-            par.barrier();
-            la_chain(D, V, sh, par, 0, kLaLmPart);
-            if (lin) {
-                if (tid == 0) {
-                    sh.current_chi = sh.acc;
-                    double m = 0.0;                          // computeLambdaInit over every active vertex, at iteration 0
-                    for (int a = 0; a < sh.nfa; ++a)
-                        _Pragma("unroll") for (int j = 0; j < 6; ++j) {
-                            const double d = __builtin_fabs(la_p(V, a, lev_h_index<6>(j, j)));
-                            m = d > m ? d : m;
-                        }
-                    sh.acc = m;
-                }
-                par.barrier();
-                if (it == 0) {
-                    la_chain(D, V, sh, par, 1, 0);
-                    if (tid == 0) { sh.lambda = 1e-5 * sh.acc; sh.ni = 2.0; }
-                }
-                if (tid == 0) { sh.qmax = 0; sh.rho = 0.0; }
-                par.barrier();
-                lin = false;
-                continue;
-            }
-            const double temp_sum = sh.acc;
-            par.barrier();
-            la_scale(D, V, sh, par);
-            if (tid == 0) {
-                lev_decide(sh, sh.ok != 0, temp_sum, sh.acc, [&sh] { sh.cur = 1 - sh.cur; }, [] {});   // kept: the tried estimates become the kept ones
-                if (!sh.go_on) {
-                    sh.iterations += 1;
-                    sh.end = lev_end(sh);
-                }
-            }
-            par.barrier();
-            if (sh.go_on) continue;
-            ++it;
-            if (sh.end || it >= iters) break;
-            lin = true;
-        }
-        if (round == 0) {                                    // :305-331: the edges that go to level 1
-            const int T = D.T, kc = 7 * sh.cur, lc = 3 * sh.cur;
-            int drops = 0;
-            for (int t = tid; t < T; t += P::NT) {
-                const int kf = V.e_kf()[t];
-                if (kf < 0) continue;
-                const int l = V.e_l()[t];
-                double est[7], p[3], x, y, z;
-                _Pragma("unroll") for (int i = 0; i < 7; ++i) est[i] = la_k(V, kf, kc + i);
-                _Pragma("unroll") for (int i = 0; i < 3; ++i) p[i] = la_l(V, l, lc + i);
-                pose_map(est, p, x, y, z);
-                const double thr = (double)(la_e(V, t, kLaRowObs + 2) < 0.0 ? kPoseChiSq2D : kPoseChiSq3D);
-                const bool bad = thr < la_e(V, t, kLaRowChi) || !(0.0 < z);
-                V.lvl()[t] = bad ? 1 : 0;
-                drops += bad ? 1 : 0;
-            }
-            if (drops) par.add(sh.drops, drops);
-        }
-        par.barrier_g();
-        if (tid == 0) {
-            int32_t* ri = V.hdr() + kLaHInfo + 4 * round;
-            ri[0] = sh.iterations; ri[1] = sh.rejected; ri[2] = sh.drops; ri[3] = sh.end ? sh.end : sh.iterations ? kLevEndIterations : 0;
-            V.hd()[2 * round] = sh.current_chi; V.hd()[2 * round + 1] = sh.lambda;
-            V.hdr()[kLaHCur] = sh.cur;
-        }
+        la_round(D, V, sh, par, none, round, iters);
         par.barrier();
     }
 }
@@ -751,15 +821,8 @@ template <class P> __host__ __device__ __forceinline__ void la_finish(const LaAr
         _Pragma("unroll") for (int i = 0; i < 3; ++i) A.out_pos_w[((size_t)g * L + l) * 3 + i] = la_l(V, l, lc + i);
     }
     for (int t = tid; t < T; t += P::NT) {
-        const int kf = V.e_kf()[t];
-        if (kf < 0) continue;
-        const int l = V.e_l()[t];
-        double est[7], p[3], x, y, z;
-        _Pragma("unroll") for (int i = 0; i < 7; ++i) est[i] = la_k(V, kf, kc + i);
-        _Pragma("unroll") for (int i = 0; i < 3; ++i) p[i] = la_l(V, l, lc + i);
-        pose_map(est, p, x, y, z);
-        const double thr = (double)(la_e(V, t, kLaRowObs + 2) < 0.0 ? kPoseChiSq2D : kPoseChiSq3D);
-        A.out_outlier[(size_t)g * T + t] = (thr < la_e(V, t, kLaRowChi) || !(0.0 < z)) ? 1 : 0;
+        if (V.e_kf()[t] < 0) continue;
+        A.out_outlier[(size_t)g * T + t] = la_point_bad(V, t, kc, lc) ? 1 : 0;
     }
     if (tid == 0) {
         if (A.out_round_info) for (int i = 0; i < 8; ++i) A.out_round_info[(size_t)8 * g + i] = V.hdr()[kLaHInfo + i];

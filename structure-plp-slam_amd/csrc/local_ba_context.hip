@@ -53,21 +53,8 @@ int32_t plp_model_local_ba_linearize_host(const plp_local_ba_args* a, int32_t ro
     LaOff O;
     la_offsets(B, 0, O);
     const LaView V = la_view(B, O);
-    if (out_free_kf) for (int i = 0; i < kLaMaxFree; ++i) out_free_kf[i] = -1;
-    if (V.hdr()[kLaHStatus] != PLP_LOCAL_BA_OK) { if (out_chi2) out_chi2[0] = 0.0; return 0; }
-    sh.cam = B.cam; sh.delta = B.mono_setup ? B.delta_2d : B.delta_3d;
-    la_round_setup(B, V, sh, par);
-    la_edge_pass(B, V, sh, par, true, robust != 0);
-    la_sums(B, V, sh, par, true);
-    sh.acc = 0.0;
-    la_chain(B, V, sh, par, 0, kLaLmPart);
-    if (out_chi2) out_chi2[0] = sh.acc;
-    for (int i = 0; i < sh.nfa; ++i) {
-        if (out_free_kf) out_free_kf[i] = sh.akf[i];
-        if (out_hpp) for (int t = 0; t < 27; ++t) out_hpp[27 * i + t] = la_p(V, i, t);
-    }
-    for (int l = 0; l < B.L; ++l)
-        if (out_hll && V.lm_act()[l]) for (int t = 0; t < 9; ++t) out_hll[(size_t)9 * l + t] = la_l(V, l, kLaLmH + t);
+    LaNoLines none;
+    if (!la_model_linearize(B, V, sh, none, robust != 0, out_free_kf, out_hpp, out_hll, out_chi2)) return 0;
     for (int t = 0; t < B.T; ++t) {
         if (V.e_kf()[t] < 0) continue;
         if (out_edge_chi2) out_edge_chi2[t] = la_e(V, t, kLaRowChi);
@@ -78,38 +65,18 @@ int32_t plp_model_local_ba_linearize_host(const plp_local_ba_args* a, int32_t ro
 
 int32_t plp_model_local_ba_solve_host(int32_t P, int32_t M, int32_t E, const double* hpp, const double* hll, const int32_t* e_pose, const int32_t* e_lm,
                                       const double* w, double lambda, double* out_xp, double* out_xl) {
-    if (P < 0 || P > kLaMaxFree || M < 0 || M > kLaMaxObs || E < 0 || E > kLaMaxObs || (P > 0 && (!hpp || !out_xp)) || (M > 0 && (!hll || !out_xl)) ||
-        (E > 0 && (!e_pose || !e_lm || !w))) return -1;
-    for (int e = 0; e < E; ++e)
-        if (e_pose[e] < -1 || e_pose[e] >= P || e_lm[e] < 0 || e_lm[e] >= M || (e > 0 && e_lm[e] < e_lm[e - 1])) return -1;
-    // the blocks as a problem of P + 1 key frames (row P: the constant pose), M landmarks and E observations
+    if (P < 0 || P > kLaMaxFree || !la_model_edges_ok(P, M, E, e_pose, e_lm) || (P > 0 && (!hpp || !out_xp)) || (M > 0 && (!hll || !out_xl)) || (E > 0 && !w)) return -1;
     LaArgs B{};
     B.G = 1; B.F = P + 1; B.L = M; B.T = E;
-    std::vector<int32_t> off(M + 1, 0);
-    for (int e = 0; e < E; ++e) off[e_lm[e] + 1] += 1;
-    for (int l = 0; l < M; ++l) off[l + 1] += off[l];
+    const std::vector<int32_t> off = la_model_offsets(M, E, e_lm);
     B.obs_offsets = off.data();
     LaHostCtx ctx;
     ctx.bind(B);
     LaShared sh{};
-    LaTeamHost par;
     LaOff O;
     la_offsets(B, 0, O);
-    const LaView V = la_view(B, O);
-    V.hdr()[kLaHNf] = P;
-    for (int i = 0; i < P; ++i) V.hdr()[kLaHFl + i] = i;
-    for (int l = 0; l < M; ++l) V.lm_role()[l] = 1;
-    for (int e = 0; e < E; ++e) { V.e_kf()[e] = e_pose[e] < 0 ? P : e_pose[e]; V.e_l()[e] = e_lm[e]; V.lvl()[e] = 0; }
-    la_round_setup(B, V, sh, par);
-    for (int i = 0; i < sh.nfa; ++i) for (int t = 0; t < 27; ++t) la_p(V, i, t) = hpp[27 * sh.akf[i] + t];
-    for (int l = 0; l < M; ++l) for (int t = 0; t < 9; ++t) la_l(V, l, kLaLmH + t) = hll[(size_t)9 * l + t];
-    for (int e = 0; e < E; ++e) for (int k = 0; k < 18; ++k) la_e(V, e, kLaRowW + k) = w[(size_t)18 * e + k];
-    sh.lambda = lambda;
-    la_solve_system(B, V, sh, par);
-    for (int i = 0; i < 6 * P; ++i) out_xp[i] = 0.0;
-    for (int i = 0; i < sh.nfa; ++i) for (int k = 0; k < 6; ++k) out_xp[6 * sh.akf[i] + k] = sh.x[6 * i + k];
-    for (int l = 0; l < M; ++l) for (int k = 0; k < 3; ++k) out_xl[(size_t)3 * l + k] = V.lm_act()[l] ? la_l(V, l, kLaLmX + k) : 0.0;
-    return sh.ok ? 1 : 0;
+    LaNoLines none;
+    return la_model_solve(B, la_view(B, O), sh, none, hpp, hll, e_pose, e_lm, w, lambda, out_xp, out_xl);
 }
 
 int32_t plp_model_inv3_host(const double* a, int32_t n, double* out, int32_t* out_ok) {

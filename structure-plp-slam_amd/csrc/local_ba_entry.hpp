@@ -97,4 +97,70 @@ LaArgs la_one(const LaArgs& A, int g) {
     B.out_round_chi2 = A.out_round_chi2 ? A.out_round_chi2 + (size_t)g * 4 : nullptr;
     return B;
 }
+
+// ---- the model entries of both adjusters (plp_model_local_ba[_lines]_{linearize,solve}_host): the shared body over the extension `ext`
+// (LaNoLines, or LlLines with the lines' tables filled by the caller)
+
+// the first linearisation of round 1 of the prepared problem B and the outputs both adjusters give; false: the problem has no edges
+template <class X> bool la_model_linearize(const LaArgs& B, const LaView& V, LaShared& sh, X& ext, bool robust, int32_t* out_free_kf, double* out_hpp,
+                                           double* out_hll, double* out_chi2) {
+    LaTeamHost par;
+    if (out_free_kf) for (int i = 0; i < kLaMaxFree; ++i) out_free_kf[i] = -1;
+    if (V.hdr()[kLaHStatus] != PLP_LOCAL_BA_OK) { if (out_chi2) out_chi2[0] = 0.0; return false; }
+    sh.cam = B.cam; sh.delta = B.mono_setup ? B.delta_2d : B.delta_3d;
+    la_round_setup(B, V, sh, par, ext);
+    ext.perturb(V, par);
+    la_edge_pass(B, V, sh, par, true, robust);
+    ext.edge_pass(V, par, true, robust);
+    la_sums(B, V, sh, par, true);
+    ext.sums(V, par, true);
+    sh.acc = 0.0;
+    la_chain(B, V, sh, par, 0, kLaLmPart);
+    ext.chain(par, 0);
+    if (out_chi2) out_chi2[0] = sh.acc;
+    for (int i = 0; i < sh.nfa; ++i) {
+        if (out_free_kf) out_free_kf[i] = sh.akf[i];
+        if (out_hpp) for (int t = 0; t < 27; ++t) out_hpp[27 * i + t] = la_p(V, i, t);
+    }
+    for (int l = 0; l < B.L; ++l)
+        if (out_hll && V.lm_act()[l]) for (int t = 0; t < 9; ++t) out_hll[(size_t)9 * l + t] = la_l(V, l, kLaLmH + t);
+    return true;
+}
+
+// the edges (pose, vertex) of given blocks: poses -1 .. P - 1, vertices 0 .. M - 1 in rising order
+bool la_model_edges_ok(int P, int M, int E, const int32_t* e_pose, const int32_t* e_v) {
+    if (M < 0 || M > kLaMaxObs || E < 0 || E > kLaMaxObs || (E > 0 && (!e_pose || !e_v))) return false;
+    for (int e = 0; e < E; ++e)
+        if (e_pose[e] < -1 || e_pose[e] >= P || e_v[e] < 0 || e_v[e] >= M || (e > 0 && e_v[e] < e_v[e - 1])) return false;
+    return true;
+}
+// ... and their observation list
+std::vector<int32_t> la_model_offsets(int M, int E, const int32_t* e_v) {
+    std::vector<int32_t> off(M + 1, 0);
+    for (int e = 0; e < E; ++e) off[e_v[e] + 1] += 1;
+    for (int l = 0; l < M; ++l) off[l + 1] += off[l];
+    return off;
+}
+
+// one damped solve of given blocks as a problem B of P + 1 key frames (row P: the constant pose), M landmarks and E observations; the return
+// value is sh.ok
+template <class X> int32_t la_model_solve(const LaArgs& B, const LaView& V, LaShared& sh, X& ext, const double* hpp, const double* hll, const int32_t* e_pose,
+                                          const int32_t* e_lm, const double* w, double lambda, double* out_xp, double* out_xl) {
+    LaTeamHost par;
+    const int P = B.F - 1, M = B.L, E = B.T;
+    V.hdr()[kLaHNf] = P;
+    for (int i = 0; i < P; ++i) V.hdr()[kLaHFl + i] = i;
+    for (int l = 0; l < M; ++l) V.lm_role()[l] = 1;
+    for (int e = 0; e < E; ++e) { V.e_kf()[e] = e_pose[e] < 0 ? P : e_pose[e]; V.e_l()[e] = e_lm[e]; V.lvl()[e] = 0; }
+    la_round_setup(B, V, sh, par, ext);
+    for (int i = 0; i < sh.nfa; ++i) for (int t = 0; t < 27; ++t) la_p(V, i, t) = hpp[27 * sh.akf[i] + t];
+    for (int l = 0; l < M; ++l) for (int t = 0; t < 9; ++t) la_l(V, l, kLaLmH + t) = hll[(size_t)9 * l + t];
+    for (int e = 0; e < E; ++e) for (int k = 0; k < 18; ++k) la_e(V, e, kLaRowW + k) = w[(size_t)18 * e + k];
+    sh.lambda = lambda;
+    la_solve_system(B, V, sh, par, ext);
+    for (int i = 0; i < 6 * P; ++i) out_xp[i] = 0.0;
+    for (int i = 0; i < sh.nfa; ++i) for (int k = 0; k < 6; ++k) out_xp[6 * sh.akf[i] + k] = sh.x[6 * i + k];
+    for (int l = 0; l < M; ++l) for (int k = 0; k < 3; ++k) out_xl[(size_t)3 * l + k] = V.lm_act()[l] ? la_l(V, l, kLaLmX + k) : 0.0;
+    return sh.ok ? 1 : 0;
+}
 }  // namespace

@@ -13,22 +13,10 @@
 // k_la_finish:  step [7]'s verdict for every edge and the outputs.
 #include <hip/hip_runtime.h>
 
-#include "plp_barrier.hpp"
-#include "local_ba.hpp"
+#include "local_ba_team.hpp"
 
 namespace plp {
 namespace {
-
-struct LaTeamWg {
-    static constexpr int NT = kLaThreads, WS = 64, NW = kLaThreads / 64;
-    __device__ __forceinline__ int tid() const { return threadIdx.x; }
-    __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
-    __device__ __forceinline__ int wave() const { return threadIdx.x >> 6; }
-    __device__ __forceinline__ void barrier() const { wg_barrier(); }
-    __device__ __forceinline__ void barrier_g() const { wg_barrier_after_global_stores(); }
-    __device__ __forceinline__ unsigned long long ballot(bool v) const { return __ballot(v); }
-    __device__ __forceinline__ void add(int32_t& t, int v) const { atomicAdd(&t, v); }
-};
 
 __global__ __launch_bounds__(kLaThreads) void k_la_prepare(LaArgs A) {
     __shared__ LaShared sh;

@@ -137,26 +137,9 @@ int32_t plp_model_local_ba_lines_linearize_host(const plp_local_ba_lines_args* a
     LlOff Q;
     ll_offsets(B, 0, Q);
     const LlView W = ll_view(B, Q);
-    const LlDims E{B.LL, B.TL, B.obs_offsets_lines};
-    if (out_free_kf) for (int i = 0; i < kLaMaxFree; ++i) out_free_kf[i] = -1;
-    if (V.hdr()[kLaHStatus] != PLP_LOCAL_BA_OK) { if (out_chi2) out_chi2[0] = 0.0; return 0; }
-    sh.s.cam = B.p.cam; sh.s.delta = B.p.mono_setup ? B.p.delta_2d : B.p.delta_3d;
-    ll_round_setup(B.p, E, V, W, sh, par);
-    ll_perturb(E, V, W, sh, par);
-    la_edge_pass(B.p, V, sh.s, par, true, robust != 0);
-    ll_edge_pass(E, V, W, sh, par, true, robust != 0, B.p.delta_2d);
-    la_sums(B.p, V, sh.s, par, true);
-    ll_sums(E, V, W, sh, par, true);
-    sh.s.acc = 0.0;
-    la_chain(B.p, V, sh.s, par, 0, kLaLmPart);
-    ll_chain(E, W, sh, par, 0, kLlLnPart);
-    if (out_chi2) out_chi2[0] = sh.s.acc;
-    for (int i = 0; i < sh.s.nfa; ++i) {
-        if (out_free_kf) out_free_kf[i] = sh.s.akf[i];
-        if (out_hpp) for (int t = 0; t < 27; ++t) out_hpp[27 * i + t] = la_p(V, i, t);
-    }
-    for (int l = 0; l < B.p.L; ++l)
-        if (out_hll && V.lm_act()[l]) for (int t = 0; t < 9; ++t) out_hll[(size_t)9 * l + t] = la_l(V, l, kLaLmH + t);
+    LlLines lines{{B.LL, B.TL, B.obs_offsets_lines}, W, sh};
+    sh.delta_lines = B.p.delta_2d;
+    if (!la_model_linearize(B.p, V, sh.s, lines, robust != 0, out_free_kf, out_hpp, out_hll, out_chi2)) return 0;
     for (int l = 0; l < B.LL; ++l)
         if (out_hnn && W.act()[l]) for (int t = 0; t < 14; ++t) out_hnn[(size_t)14 * l + t] = ll_l(W, l, kLlLnH + t);
     for (int t = 0; t < B.TL; ++t) {
@@ -170,52 +153,29 @@ int32_t plp_model_local_ba_lines_linearize_host(const plp_local_ba_lines_args* a
 int32_t plp_model_local_ba_lines_solve_host(int32_t P, int32_t M, int32_t N, int32_t E3, int32_t E4, const double* hpp, const double* hll, const double* hnn,
                                             const int32_t* e_pose, const int32_t* e_lm, const double* w, const int32_t* e_pose_lines, const int32_t* e_line,
                                             const double* w_lines, double lambda, double* out_xp, double* out_xl, double* out_xn) {
-    if (P < 0 || P > kLaMaxFree || M < 0 || M > kLaMaxObs || N < 0 || N > kLaMaxObs || E3 < 0 || E3 > kLaMaxObs || E4 < 0 || E4 > kLaMaxObs ||
-        (P > 0 && (!hpp || !out_xp)) || (M > 0 && (!hll || !out_xl)) || (N > 0 && (!hnn || !out_xn)) || (E3 > 0 && (!e_pose || !e_lm || !w)) ||
-        (E4 > 0 && (!e_pose_lines || !e_line || !w_lines))) return -1;
-    for (int e = 0; e < E3; ++e)
-        if (e_pose[e] < -1 || e_pose[e] >= P || e_lm[e] < 0 || e_lm[e] >= M || (e > 0 && e_lm[e] < e_lm[e - 1])) return -1;
-    for (int e = 0; e < E4; ++e)
-        if (e_pose_lines[e] < -1 || e_pose_lines[e] >= P || e_line[e] < 0 || e_line[e] >= N || (e > 0 && e_line[e] < e_line[e - 1])) return -1;
-    // the blocks as a problem of P + 1 key frames (row P: the constant pose), M landmarks, N lines and their observations
+    if (P < 0 || P > kLaMaxFree || !la_model_edges_ok(P, M, E3, e_pose, e_lm) || !la_model_edges_ok(P, N, E4, e_pose_lines, e_line) || (P > 0 && (!hpp || !out_xp)) ||
+        (M > 0 && (!hll || !out_xl)) || (N > 0 && (!hnn || !out_xn)) || (E3 > 0 && !w) || (E4 > 0 && !w_lines)) return -1;
+    // the lines' blocks beside la_model_solve's problem: N lines and their E4 observations
     LlArgs B{};
     B.p.G = 1; B.p.F = P + 1; B.p.L = M; B.p.T = E3; B.LL = N; B.TL = E4;
-    std::vector<int32_t> off(M + 1, 0), offl(N + 1, 0);
-    for (int e = 0; e < E3; ++e) off[e_lm[e] + 1] += 1;
-    for (int l = 0; l < M; ++l) off[l + 1] += off[l];
-    for (int e = 0; e < E4; ++e) offl[e_line[e] + 1] += 1;
-    for (int l = 0; l < N; ++l) offl[l + 1] += offl[l];
+    const std::vector<int32_t> off = la_model_offsets(M, E3, e_lm), offl = la_model_offsets(N, E4, e_line);
     B.p.obs_offsets = off.data(); B.obs_offsets_lines = offl.data();
     LlHostCtx ctx;
     ctx.bind(B);
     LlShared sh{};
-    LaTeamHost par;
     LaOff O;
     la_offsets(B.p, 0, O);
-    const LaView V = la_view(B.p, O);
     LlOff Q;
     ll_offsets(B, 0, Q);
     const LlView W = ll_view(B, Q);
-    const LlDims E{B.LL, B.TL, B.obs_offsets_lines};
-    V.hdr()[kLaHNf] = P;
-    for (int i = 0; i < P; ++i) V.hdr()[kLaHFl + i] = i;
-    for (int l = 0; l < M; ++l) V.lm_role()[l] = 1;
     for (int l = 0; l < N; ++l) W.role()[l] = 1;
-    for (int e = 0; e < E3; ++e) { V.e_kf()[e] = e_pose[e] < 0 ? P : e_pose[e]; V.e_l()[e] = e_lm[e]; V.lvl()[e] = 0; }
     for (int e = 0; e < E4; ++e) { W.e_kf()[e] = e_pose_lines[e] < 0 ? P : e_pose_lines[e]; W.e_l()[e] = e_line[e]; W.lvl()[e] = 0; }
-    ll_round_setup(B.p, E, V, W, sh, par);
-    for (int i = 0; i < sh.s.nfa; ++i) for (int t = 0; t < 27; ++t) la_p(V, i, t) = hpp[27 * sh.s.akf[i] + t];
-    for (int l = 0; l < M; ++l) for (int t = 0; t < 9; ++t) la_l(V, l, kLaLmH + t) = hll[(size_t)9 * l + t];
     for (int l = 0; l < N; ++l) for (int t = 0; t < 14; ++t) ll_l(W, l, kLlLnH + t) = hnn[(size_t)14 * l + t];
-    for (int e = 0; e < E3; ++e) for (int k = 0; k < 18; ++k) la_e(V, e, kLaRowW + k) = w[(size_t)18 * e + k];
     for (int e = 0; e < E4; ++e) for (int k = 0; k < 24; ++k) ll_e(W, e, kLlRowW + k) = w_lines[(size_t)24 * e + k];
-    sh.s.lambda = lambda;
-    ll_solve_system(B.p, E, V, W, sh, par);
-    for (int i = 0; i < 6 * P; ++i) out_xp[i] = 0.0;
-    for (int i = 0; i < sh.s.nfa; ++i) for (int k = 0; k < 6; ++k) out_xp[6 * sh.s.akf[i] + k] = sh.s.x[6 * i + k];
-    for (int l = 0; l < M; ++l) for (int k = 0; k < 3; ++k) out_xl[(size_t)3 * l + k] = V.lm_act()[l] ? la_l(V, l, kLaLmX + k) : 0.0;
+    LlLines lines{{B.LL, B.TL, B.obs_offsets_lines}, W, sh};
+    const int32_t ok = la_model_solve(B.p, la_view(B.p, O), sh.s, lines, hpp, hll, e_pose, e_lm, w, lambda, out_xp, out_xl);
     for (int l = 0; l < N; ++l) for (int k = 0; k < 4; ++k) out_xn[(size_t)4 * l + k] = W.act()[l] ? ll_l(W, l, kLlLnX + k) : 0.0;
-    return sh.s.ok ? 1 : 0;
+    return ok;
 }
 
 }  // extern "C"

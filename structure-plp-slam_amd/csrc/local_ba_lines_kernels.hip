@@ -12,37 +12,26 @@
 // k_ll_finish:  k_la_finish's work, then step [7]'s verdict for every line edge and the lines' outputs.
 #include <hip/hip_runtime.h>
 
-#include "plp_barrier.hpp"
+#include "local_ba_team.hpp"
 #include "local_ba_lines.hpp"
 
 namespace plp {
 namespace {
 
-struct LlTeamWg {
-    static constexpr int NT = kLaThreads, WS = 64, NW = kLaThreads / 64;
-    __device__ __forceinline__ int tid() const { return threadIdx.x; }
-    __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
-    __device__ __forceinline__ int wave() const { return threadIdx.x >> 6; }
-    __device__ __forceinline__ void barrier() const { wg_barrier(); }
-    __device__ __forceinline__ void barrier_g() const { wg_barrier_after_global_stores(); }
-    __device__ __forceinline__ unsigned long long ballot(bool v) const { return __ballot(v); }
-    __device__ __forceinline__ void add(int32_t& t, int v) const { atomicAdd(&t, v); }
-};
-
 __global__ __launch_bounds__(kLaThreads) void k_ll_prepare(LlArgs A) {
     __shared__ LlShared sh;
-    LlTeamWg par;
+    LaTeamWg par;
     ll_prepare(A, blockIdx.x, sh, par);
 }
 
 template <int ROUND> __global__ __launch_bounds__(kLaThreads) void k_ll_solve(LlArgs A) {
     __shared__ LlShared sh;
-    LlTeamWg par;
+    LaTeamWg par;
     ll_solve_round<ROUND>(A, blockIdx.x, sh, par);
 }
 
 __global__ __launch_bounds__(kLaThreads) void k_ll_finish(LlArgs A) {
-    LlTeamWg par;
+    LaTeamWg par;
     ll_finish(A, blockIdx.x, par);
 }
 

@@ -203,6 +203,39 @@ def test_d_the_mixed_schur_solve_agrees_with_the_dense_solve():
     assert gn.tobytes() == np.array([xn[l] for l in P.na]).tobytes()
 
 
+@pytest.mark.parametrize("name", ["mono", "rgbd", "fisheye"])
+def test_h_without_lines_the_model_entries_are_the_point_adjusters(name):
+    """the linearisation and the damped solve are written once for both adjusters (csrc/local_ba.hpp's la_round_setup and la_solve_system with an
+    extension for the lines): with no line, the lines' model entries return what the points' return, bit for bit, a failed solve included"""
+    sc = dict(census()[name])
+    sc.update(pluecker=np.zeros((0, 6)), obs_offsets_lines=np.zeros(1, np.int32), obs_kf_lines=np.zeros(0, np.int32), obs_idx_lines=np.zeros(0, np.int32),
+              line_erased=np.zeros(0, np.uint8))
+    for robust in (True, False):
+        lin = plp.model_local_ba_linearize(**S.call_args(sc), robust=robust)
+        lin_l = plp.model_local_ba_lines_linearize(robust=robust, **LS.call_args(sc))
+        shared = ("free_kf", "Hpp", "bp", "Hll", "bl")
+        assert len(lin["free_kf"]) >= 2 and S.same({k: lin_l[k] for k in shared}, {k: lin[k] for k in shared})
+        assert np.float64(lin_l["chi2"]).tobytes() == np.float64(lin["chi2"]).tobytes()
+        assert lin_l["Hnn"].shape == (0, 10) and lin_l["W_lines"].shape == (0, 6, 4) and lin_l["edge_chi2_lines"].shape == (0,)
+    # the blocks of the last linearisation (Huber off) as a solve's arguments, as tests/test_local_ba_cpu.py builds them
+    row = {int(f): i for i, f in enumerate(lin["free_kf"])}
+    ts = np.where(~np.isnan(lin["edge_chi2"]))[0]
+    e_pose = np.array([row.get(int(sc["obs_kf"][t]), -1) for t in ts])
+    e_lm = (np.searchsorted(sc["obs_offsets"], np.arange(len(sc["obs_kf"])), side="right") - 1)[ts]
+    W = np.nan_to_num(lin["W"][ts])
+    Hll, bl = np.nan_to_num(lin["Hll"]), np.nan_to_num(lin["bl"])
+    lam = 1e-5 * max(np.abs(lin["Hpp"][:, [0, 6, 11, 15, 18, 20]]).max(), np.abs(Hll[:, [0, 3, 5]]).max())
+    bad_pivot = lin["Hpp"].copy(); bad_pivot[-1, 20] = -1e12                 # the last pivot of the reduced system is negative
+    singular = Hll.copy(); singular[e_lm[0]] = 0.0                           # a landmark block without an inverse at lambda = 0
+    none_n, none_e = np.zeros((0, 10)), np.zeros(0, np.int32)
+    for what, hpp, hll, lm, want_ok in [("regular", lin["Hpp"], Hll, lam, True), ("failed pivot", bad_pivot, Hll, lam, False), ("failed inverse", lin["Hpp"], singular, 0.0, False)]:
+        xp, xl, ok = plp.model_local_ba_solve(hpp, lin["bp"], hll, bl, e_pose, e_lm, W, lm)
+        gp, gl, gn, gok = plp.model_local_ba_lines_solve(hpp, lin["bp"], hll, bl, none_n, np.zeros((0, 4)), e_pose, e_lm, W, none_e, none_e, np.zeros((0, 6, 4)), lm)
+        assert ok == want_ok and gok == ok, what
+        assert S.same(dict(xp=gp, xl=gl), dict(xp=xp, xl=xl)) and gn.shape == (0, 4), what
+        assert xp.any() == want_ok and xl.any() == want_ok, what
+
+
 def normalised(L):
     L = np.asarray(L, float)
     return L / np.linalg.norm(L[..., 3:], axis=-1, keepdims=True)
